@@ -20,11 +20,22 @@ HBM output buffer.  Streams are independent (rate_base.h:533-540), so N GPUs = N
 data-path collective; torch.distributed (RCCL) is used only for the barrier and the max-over-ranks of the time.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job input channel-samples per
-second (Msamples/s); roofline = algorithmic HBM bytes (4*(1+out/in) B per input channel-sample) /
-summed HIP-event time of the chain's stage kernels on the launch stream, against the 8 TB/s HBM3E peak, with the
-kernel names reported by the engine (RRX_profile_report), the HBM traffic looked up in profiles/traffic.json (PMC
-passes; null when no pass matches this exact workload and kernel) and the fp64 issue fraction next to it;
-cpu_baseline = the plain-C oracle ("port") timed on this box's host cores on a bounded sample of the same workload.
+second (Msamples/s), ms_per_step = wall milliseconds of one timed step.  A plain run does only that: set up, warm up,
+time --steps steps, write the outputs (--dump-outputs), print the line.
+
+`--full` adds what takes runs or checks of its own, after the timed steps: roofline = algorithmic HBM bytes (SURVEY.md 8d:
+4*(1+out/in) B per input channel-sample) / summed HIP-event time of the chain's stage kernels on the launch stream (a
+second, profiled pass of the same steps), against the 8 TB/s HBM3E peak, with the kernel names reported by the engine
+(RRX_profile_report), the HBM traffic looked up in profiles/traffic.json (PMC passes; null when no pass matches this exact
+workload and kernel) and the fp64 issue fraction next to it; checked = stream 0 of the last timed step against the CPU
+oracle (--no-check drops it); cpu_baseline = the plain-C oracle ("port") timed on this box's host cores on a bounded sample
+of the same workload (--no-cpu-baseline drops it).
+
+`--dump-outputs DIR` (rank 0): what the last timed step returned to its caller, as float32/float64 .npy files, at most
+64 MB in all -- out_frames (frames written per stream), y_streams (the output of a seeded sample of streams, stream 0
+first; their indices in y_streams_index) and y_scatter (values at seeded positions over all streams' output; flat indices
+into [stream, frame, channel] in y_scatter_index).  The input is a fixed function of the arguments, so two builds can be
+compared file by file.
 """
 import argparse
 import json
@@ -204,19 +215,56 @@ def check_against_oracle(cfg, x0, pushes, y_last):
                                            "frames": int(ref.shape[0]), "max_ulp": float(rep["max_ulp"]), "rel_rms": float(rep["rel_rms"])}}
 
 
+DUMP_BYTES_STREAMS = 48 << 20  # y_streams; y_scatter and its indices add 12 MB: 64 MB in all at most
+DUMP_SCATTER = 1 << 20
+DUMP_SEED = 20240917
+
+
+def dump_outputs(torch, outdir, y, og, nch):
+    """Writes what the last timed step returned (y[:, :og, :] and og) as a fixed, seeded sample (see the module docstring)."""
+    import numpy as np
+    S = y.shape[0]
+    rng = np.random.default_rng(DUMP_SEED)
+    per_stream = max(1, og * nch * 4)
+    k = max(1, min(S, 8, DUMP_BYTES_STREAMS // per_stream))
+    n = min(og, DUMP_BYTES_STREAMS // (k * nch * 4))
+    streams = [0] + sorted(int(s) for s in rng.choice(np.arange(1, S), k - 1, replace=False)) if S > 1 else [0]
+    sel = torch.tensor(streams, dtype=torch.int64, device=y.device)
+    y_streams = y.index_select(0, sel)[:, :n].cpu().numpy()
+    total = S * og * nch
+    flat, y_scatter = np.zeros(0, np.int64), np.zeros(0, np.float32)
+    if total:
+        flat = np.sort(rng.choice(total, min(total, DUMP_SCATTER), replace=False))
+        fi = torch.from_numpy(flat).to(y.device)
+        s_i, rem = fi // (og * nch), fi % (og * nch)  # all within y[:S, :og, :nch]
+        y_scatter = y[s_i, rem // nch, rem % nch].cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"out_frames": np.array([og], dtype=np.float64),
+              "y_streams": y_streams.astype(np.float32), "y_streams_index": np.array(streams, dtype=np.float64),
+              "y_scatter": y_scatter.astype(np.float32), "y_scatter_index": flat.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled pass (roofline, per-kernel times), the oracle check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; a seeded sample, <= 64 MB)")
     ap.add_argument("--config", type=int, default=1, choices=sorted(CONFIGS), help="BASELINE.json configs[K] (default 1: the headline metric)")
     ap.add_argument("--streams", type=int, default=0, help="override: independent streams per GPU")
     ap.add_argument("--frames", type=int, default=0, help="override: frames per push (default: isamp_max, rate_base.h:531)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--check", dest="check", action="store_true", default=True,
-                    help="after the timed region: stream 0 of the last timed step against the CPU oracle (\"checked\": true); default")
+                    help="with --full, after the timed region: stream 0 of the last timed step against the CPU oracle (\"checked\": true); default")
     ap.add_argument("--no-check", dest="check", action="store_false")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
     cfg = CONFIGS[args.config]
@@ -315,21 +363,25 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)  # HIP events on the stream the kernels were launched on
-    # stream 0's output of the last timed step, kept for the check (the profiling pass below overwrites y)
-    y_last = y[0, :last_og[0]].clone() if args.check and rank == 0 else None
-    torch.cuda.synchronize()  # the copy runs on torch's current stream, the engine on `stream`: it must have finished before the
-    #                           profiling pass overwrites y (two ranks sharing one GPU lost that race: "checked": false on good data)
+    if args.dump_outputs and rank == 0:  # before anything below overwrites y
+        dump_outputs(torch, args.dump_outputs, y, last_og[0], nch)
 
-    # second pass of the same K steps with HIP events around every stage launch (profiling keeps all
-    # kernels on one stream, so it stays out of the pass that defines `value`)
-    r.profile(True)
-    for _ in range(args.steps):
-        step()
-    kernels = r.profile_report()    # per kernel instance: launches and summed duration, names as rocprofv3 prints them
-    r.profile(False)
-    checked = None
-    if y_last is not None:  # after everything that is timed: the CPU replay would let the GPU clocks fall in between
-        checked = check_against_oracle(cfg, x[0].cpu().numpy(), args.warmup + args.steps, y_last.cpu().numpy())
+    kernels, checked = [], None
+    if args.full:
+        # stream 0's output of the last timed step, kept for the check (the profiling pass below overwrites y)
+        y_last = y[0, :last_og[0]].clone() if args.check and rank == 0 else None
+        torch.cuda.synchronize()  # the copy runs on torch's current stream, the engine on `stream`: it must have finished before the
+        #                           profiling pass overwrites y (two ranks sharing one GPU lost that race: "checked": false on good data)
+
+        # second pass of the same K steps with HIP events around every stage launch (profiling keeps all
+        # kernels on one stream, so it stays out of the pass that defines `value`)
+        r.profile(True)
+        for _ in range(args.steps):
+            step()
+        kernels = r.profile_report()    # per kernel instance: launches and summed duration, names as rocprofv3 prints them
+        r.profile(False)
+        if y_last is not None:  # after everything that is timed: the CPU replay would let the GPU clocks fall in between
+            checked = check_against_oracle(cfg, x[0].cpu().numpy(), args.warmup + args.steps, y_last.cpu().numpy())
 
     units_per_step_rank = S * P * nch                    # input channel-samples per step on this GPU
     units_all = units_per_step_rank
@@ -376,30 +428,31 @@ def main():
                        "chain": "->".join("%s" % s["kind"] for s in plan["stages"]),
                        "output_Msamples_per_s": round(value * fo / fi, 2),
                        "out_frames_per_stream": out_frames},
-            "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved_gbs / HBM_PEAK_GBS, 5),
-                         # PMC bytes per launch of the dominant kernel (fused chain: its bytes per step / its launches per step,
-                         # like `achieved`) or per step of the chain's stage kernels together (modular chain)
-                         "traffic": ((lambda t: None if t is None else round(t / max(1.0, launches_per_step)))(lookup_traffic(args.config, S, P, [dom["kernel"]]))
-                                     if fused else lookup_traffic(args.config, S, P, [k["kernel"] for k in chain])),
-                         "kernel": dom["kernel"],
-                         "kernel_time_basis": "dominant kernel (fused chain)" if fused else "sum of the chain's stage kernels",
-                         "launches_per_step": launches_per_step,
-                         "avg_launch_ms": round(dom["ms"] / max(1, dom["launches"]), 5),
-                         "algorithmic_bytes_per_launch": round(alg_bytes_step / max(1.0, launches_per_step)) if fused else None,
-                         "algorithmic_bytes_per_step": round(alg_bytes_step),
-                         "bytes_per_unit": round(bytes_per_unit, 4),
-                         "kernels_ms_per_step": {k["kernel"]: round(k["ms"] / args.steps, 5) for k in kernels},
-                         "device_ms_per_step": round(step_dev_s * 1e3, 4),
-                         "whole_step_frac": round(alg_bytes_step / step_dev_s / 1e9 / HBM_PEAK_GBS, 5),
-                         # fp64 work of the chain at complex-FFT efficiency / the vector(=matrix) fp64 peak
-                         "fp64_flops_per_unit": round(flops_unit, 1),
-                         "fp64_issue_frac": round(units_per_step_rank * flops_unit / (div_ms / 1e3) / 1e12 / FP64_PEAK_TFLOPS, 5) if div_ms else None,
-                         "fp64_peak_tflops": FP64_PEAK_TFLOPS},
         }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved_gbs / HBM_PEAK_GBS, 5),
+                               # PMC bytes per launch of the dominant kernel (fused chain: its bytes per step / its launches per step,
+                               # like `achieved`) or per step of the chain's stage kernels together (modular chain)
+                               "traffic": ((lambda t: None if t is None else round(t / max(1.0, launches_per_step)))(lookup_traffic(args.config, S, P, [dom["kernel"]]))
+                                           if fused else lookup_traffic(args.config, S, P, [k["kernel"] for k in chain])),
+                               "kernel": dom["kernel"],
+                               "kernel_time_basis": "dominant kernel (fused chain)" if fused else "sum of the chain's stage kernels",
+                               "launches_per_step": launches_per_step,
+                               "avg_launch_ms": round(dom["ms"] / max(1, dom["launches"]), 5),
+                               "algorithmic_bytes_per_launch": round(alg_bytes_step / max(1.0, launches_per_step)) if fused else None,
+                               "algorithmic_bytes_per_step": round(alg_bytes_step),
+                               "bytes_per_unit": round(bytes_per_unit, 4),
+                               "kernels_ms_per_step": {k["kernel"]: round(k["ms"] / args.steps, 5) for k in kernels},
+                               "device_ms_per_step": round(step_dev_s * 1e3, 4),
+                               "whole_step_frac": round(alg_bytes_step / step_dev_s / 1e9 / HBM_PEAK_GBS, 5),
+                               # fp64 work of the chain at complex-FFT efficiency / the vector(=matrix) fp64 peak
+                               "fp64_flops_per_unit": round(flops_unit, 1),
+                               "fp64_issue_frac": round(units_per_step_rank * flops_unit / (div_ms / 1e3) / 1e12 / FP64_PEAK_TFLOPS, 5) if div_ms else None,
+                               "fp64_peak_tflops": FP64_PEAK_TFLOPS}
         if checked is not None:
             out.update(checked)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if dist:

@@ -66,7 +66,7 @@ def bench_name(kern):
     return re.sub(r"(dftx_kernel<\d+), \d+>", r"\1>", kern)
 
 
-PMC_STEPS = 7  # tools/gpu_evidence.sh runs the counter passes as `bench.py --steps 3 --warmup 1`: 1 + 3 timed + 3 in the profiling pass
+PMC_STEPS = 7  # tools/gpu_evidence.sh runs the counter passes as `bench.py --full --steps 3 --warmup 1`: 1 + 3 timed + 3 in the profiling pass
 
 
 def per_step(pass_summary, counter):

@@ -12,7 +12,7 @@ tag=${1:?tag}; parts=${2:-"tests fuzz bench stats traffic sq ranks"}
 O=gpurun_out/$tag
 mkdir -p $O
 has() { [[ " $parts " == *" $1 "* ]]; }
-B="python3 bench.py --no-cpu-baseline --no-check"
+B="python3 bench.py --full --no-cpu-baseline --no-check"
 if has tests; then timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gputests.log 2>&1; echo "pytest rc $?" >> $O/gputests.log; tail -3 $O/gputests.log; fi
 if has fuzz; then
   timeout -k 10 300 python tools/fuzz_parity.py 200 4242 > $O/fuzz_parity.log 2>&1; tail -1 $O/fuzz_parity.log
@@ -20,8 +20,8 @@ if has fuzz; then
   timeout -k 10 200 python tools/fuzz_plugin.py 60 5 > $O/fuzz_plugin.log 2>&1; tail -1 $O/fuzz_plugin.log
 fi
 if has bench; then
-  timeout -k 10 300 python bench.py --config 1 --steps 20 --warmup 5 > $O/bench_cfg1.json 2> $O/bench_cfg1.err || echo "bench cfg1 failed"
-  for k in 0 2 3 4; do timeout -k 10 300 python bench.py --config $k --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg$k.json 2> $O/bench_cfg$k.err || echo "bench cfg$k failed"; done
+  timeout -k 10 300 python bench.py --full --config 1 --steps 20 --warmup 5 > $O/bench_cfg1.json 2> $O/bench_cfg1.err || echo "bench cfg1 failed"
+  for k in 0 2 3 4; do timeout -k 10 300 python bench.py --full --config $k --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg$k.json 2> $O/bench_cfg$k.err || echo "bench cfg$k failed"; done
   for k in 1 0 2 3 4; do python3 -c "
 import json; d=json.load(open('$O/bench_cfg$k.json')); r=d['roofline']; print($k, d['value'], d.get('checked'), r['frac'], r['fp64_issue_frac'], r['kernels_ms_per_step'])"; done
 fi
@@ -38,7 +38,7 @@ if has sq; then
   timeout -k 10 150 rocprofv3 --kernel-trace --pmc TCP_PENDING_STALL_CYCLES TCP_CACHE_MISS TCP_PERF_SEL_TOTAL_READ TCP_PERF_SEL_TOTAL_NONREAD GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_cfg1_tcp -o run -- $B --config 1 --steps 3 --warmup 1 > $O/pmc_cfg1_tcp.log 2>&1
 fi
 if has ranks; then
-  BENCH_SHARE_GPU=1 BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --config 4 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg4_2rank.json 2> $O/bench_cfg4_2rank.err; tail -c 400 $O/bench_cfg4_2rank.json
+  BENCH_SHARE_GPU=1 BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --config 4 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg4_2rank.json 2> $O/bench_cfg4_2rank.err; tail -c 400 $O/bench_cfg4_2rank.json
 fi
 python3 - <<PY
 import csv, glob
