@@ -85,7 +85,7 @@ template <class Fn> int guarded(RR_handle *h, Fn fn)
 }
 
 // device: -1 = the default placement (RATELIB_AMD_DEVICES round-robin, else the calling thread's current device)
-int open_common(const RR_config *config, int nchannels, int nstreams, int device, RR_handle **const handle)
+int open_common(const RR_config *config, int nchannels, int nstreams, int device, RR_handle **const handle, int format = RRX_FMT_FLOAT)
 {
   if (handle == nullptr) return RR_INVPARAM;
   *handle = nullptr;
@@ -97,7 +97,7 @@ int open_common(const RR_config *config, int nchannels, int nstreams, int device
   if (device < 0 && !g_devices.empty()) device = g_devices[g_next_device.fetch_add(1) % g_devices.size()];
   int rc;
   try {
-    rc = rsmp::Engine::create(to_config(config), nchannels, nstreams, device, &h->eng);
+    rc = rsmp::Engine::create(to_config(config), nchannels, nstreams, device, &h->eng, format);
   } catch (const std::bad_alloc &) {
     rc = RR_ENOMEM;
   } catch (...) {
@@ -149,15 +149,84 @@ int RRX_open_batch_on(const RR_config *config, int nchannels, int nstreams, int 
 
 int RRX_device(const RR_handle *h) { return h ? h->eng->device() : -1; }
 
+int RRX_open_batch_fmt(const RR_config *config, int nchannels, int nstreams, int device, int format, RR_handle **const handle)
+{
+  if (format != RRX_FMT_FLOAT && format != RRX_FMT_DOUBLE) { // checked before anything touches a device
+    if (handle) *handle = nullptr;
+    return RR_INVPARAM;
+  }
+  if (device < -1) {
+    if (handle) *handle = nullptr;
+    return RR_INVPARAM;
+  }
+  return open_common(config, nchannels, nstreams, device, handle, format);
+}
+
+int RRX_format(const RR_handle *h) { return h ? h->eng->format() : -1; }
+
+// The double forms hand the engine their buffers behind a float pointer: a double handle's engine moves its frames as
+// 2 * nchannels 4-byte words (Engine::w_) and its kernels read them as float64 (kFramesF64).
+namespace {
+inline const float *cwords(const double *p) { return reinterpret_cast<const float *>(p); }
+inline float *words(double *p) { return reinterpret_cast<float *>(p); }
+} // namespace
+
+int RRX_push_double(RR_handle *h, const double *ibuf, size_t in_stride, size_t isamp)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->push_host(cwords(ibuf), in_stride, isamp); });
+}
+
+int RRX_pull_double(RR_handle *h, double *obuf, size_t out_stride, size_t osamp, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->pull_host(words(obuf), out_stride, osamp, ogen); });
+}
+
+int RRX_flow_double(RR_handle *h, const double *ibuf, size_t in_stride, double *obuf, size_t out_stride, size_t isamp, size_t osamp,
+                    size_t *iused, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (h->eng->nstreams() == 1) in_stride = isamp, out_stride = osamp; // packed, as RR_flow
+  return guarded(h, [&] { return h->eng->flow_host(cwords(ibuf), in_stride, words(obuf), out_stride, isamp, osamp, iused, ogen); });
+}
+
+int RRX_push_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, size_t isamp)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->push_device(cwords(d_ibuf), in_stride, isamp); });
+}
+
+int RRX_pull_device_double(RR_handle *h, double *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->pull_device(words(d_obuf), out_stride, osamp, ogen); });
+}
+
+int RRX_flow_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, double *d_obuf, size_t out_stride, size_t isamp,
+                           size_t osamp, size_t *iused, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->flow_device(cwords(d_ibuf), in_stride, words(d_obuf), out_stride, isamp, osamp, iused, ogen); });
+}
+
 int RR_push(RR_handle *h, const fb_sample_t *ibuf, size_t isamp)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   return guarded(h, [&] { return h->eng->push_host(ibuf, isamp, isamp); });
 }
 
 int RR_pull(RR_handle *h, fb_sample_t *obuf, size_t osamp, size_t *ogen)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   size_t n = osamp < h->eng->available() ? osamp : h->eng->available();
   return guarded(h, [&] { return h->eng->pull_host(obuf, n, osamp, ogen); });
 }
@@ -165,6 +234,7 @@ int RR_pull(RR_handle *h, fb_sample_t *obuf, size_t osamp, size_t *ogen)
 int RR_flow(RR_handle *h, const fb_sample_t *ibuf, fb_sample_t *obuf, size_t isamp, size_t osamp, size_t *iused, size_t *ogen)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   if (h->eng->nstreams() != 1) return RR_INVPARAM; // packed layout of a batch is ambiguous here
   return guarded(h, [&] { return h->eng->flow_host(ibuf, isamp, obuf, osamp, isamp, osamp, iused, ogen); });
 }
@@ -199,12 +269,14 @@ const char *RR_strerror(int error)
 int RRX_push_device(RR_handle *h, const fb_sample_t *d_ibuf, size_t in_stride, size_t isamp)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   return guarded(h, [&] { return h->eng->push_device(d_ibuf, in_stride, isamp); });
 }
 
 int RRX_pull_device(RR_handle *h, fb_sample_t *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   return guarded(h, [&] { return h->eng->pull_device(d_obuf, out_stride, osamp, ogen); });
 }
 
@@ -212,18 +284,21 @@ int RRX_flow_device(RR_handle *h, const fb_sample_t *d_ibuf, size_t in_stride, f
                     size_t isamp, size_t osamp, size_t *iused, size_t *ogen)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   return guarded(h, [&] { return h->eng->flow_device(d_ibuf, in_stride, d_obuf, out_stride, isamp, osamp, iused, ogen); });
 }
 
 int RRX_push_strided(RR_handle *h, const fb_sample_t *ibuf, size_t in_stride, size_t isamp)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   return guarded(h, [&] { return h->eng->push_host(ibuf, in_stride, isamp); });
 }
 
 int RRX_pull_strided(RR_handle *h, fb_sample_t *obuf, size_t out_stride, size_t osamp, size_t *ogen)
 {
   if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
   return guarded(h, [&] { return h->eng->pull_host(obuf, out_stride, osamp, ogen); });
 }
 

@@ -101,8 +101,8 @@ template <int DIR> __device__ __forceinline__ void fft8x(c64 (&u)[8], int tid, c
 }
 } // namespace
 
-// OKIND = 1 / 2: every block of the launch reads one contiguous span and writes one contiguous span of float frames /
-// of the planar fp64 rings (launch_dftx checks that on the host by calling pair_span itself, span_contiguous), and the
+// OKIND = 1 / 2 / 3: every block of the launch reads one contiguous span and writes one contiguous span of float frames /
+// of the planar fp64 rings / of float64 frames (pair_span's kinds; launch_dftx checks that on the host by calling pair_span itself, span_contiguous), and the
 // kernel has no other path -- which is what lets the compiler count the stores between a load and its use;
 // OKIND = 0 (generic): any block, element-wise fifo addressing where a span is split
 // (ring wrap, a block half in the ring and half in the caller's buffer, odd channel count) -- same arithmetic, so which
@@ -135,6 +135,12 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
       for (int s = 0; s < 8; ++s) {
         const float2 f = sp.p2[(tid + s * T8) * sp.fstride];
         x[s] = {(double)f.x, (double)f.y};
+      }
+    } else if (sp.kind == 3) { // float64 frames
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const double2 f = sp.d2[(tid + s * T8) * sp.fstride];
+        x[s] = {f.x, f.y};
       }
     } else if (sp.kind == 2) { // (pb == pa when the pair has one channel: every load is unconditional)
 #pragma unroll
@@ -224,6 +230,12 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
               *reinterpret_cast<float2 *>(ob8 + (unsigned)(jj[j] * (128 * LL)) * fbytes) = f[j];
         }
       }
+    } else if ((GENERIC && so.kind == 3) || OKIND == 3) { // float64 frames, contiguous: one 16-byte store per output
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int m = LL * (tid + s * T8) + r;
+        if (m < a.Vout) so.d2[m * so.fstride] = make_double2(v[s].x, v[s].y);
+      }
     } else if ((GENERIC && so.kind == 2) || OKIND == 2) { // planar fp64 rings, contiguous
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
@@ -256,7 +268,7 @@ static bool span_contiguous(const AnyView &v, long long a0, long long len, int C
 {
   if (v.is_f32 && ((v.f.nch & 1) || (C & 1))) return false;
   const int npairs = C / 2, hp = v.is_f32 ? v.f.nch / 2 : npairs;
-  const int want = v.is_f32 ? 1 : 2;
+  const int want = v.is_f32 == kFramesF64 ? 3 : v.is_f32 ? 1 : 2;
   for (int pair : {0, hp < npairs ? hp : 0, npairs - 1})
     if (pair_span(v, pair, true, a0, len).kind != want) return false;
   return true;
@@ -291,6 +303,7 @@ template <int LL> static hipError_t launch_dftx_t(const AnyView &in, const AnyVi
     b.B0 = a.B0 + k;
     b.nblocks = e - k;
     const hipError_t rc = !f ? launch_dftx_run<LL, 0>(in, out, b, st)
+                         : out.is_f32 == kFramesF64 ? launch_dftx_run<LL, 3>(in, out, b, st)
                          : out.is_f32 ? launch_dftx_run<LL, 1>(in, out, b, st) : launch_dftx_run<LL, 2>(in, out, b, st);
     if (rc != hipSuccess) return rc;
     k = e;
@@ -304,7 +317,7 @@ bool dftx_supported(int log2n, int log2p, int log2nd)
   return !knobs().no_dftx && log2p == kXP && log2nd == log2n && (log2n == 13 || log2n == 14);
 }
 
-hipError_t launch_dftx(int log2n, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_dftx(int log2n, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                        const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname)
 {
   const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);

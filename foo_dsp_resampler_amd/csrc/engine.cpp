@@ -82,10 +82,11 @@ int num_passes(int log2m) { return (log2m + 3) / 4; }
 
 } // namespace
 
-int Engine::create(const Config &cfg, int nch, int nstreams, int device, Engine **out)
+int Engine::create(const Config &cfg, int nch, int nstreams, int device, Engine **out, int fmt)
 {
   if (!out) return kInvParam;
   *out = nullptr;
+  if (fmt != 0 && fmt != 1) return kInvParam;
   if (nch < 1 || nstreams < 1) return kInvParam;
   if ((long long)nch * nstreams > INT_MAX / 4096) return kNoMem; // parameter guard: more channels than any device could hold fifos for
   int dev_count = 0;
@@ -97,6 +98,8 @@ int Engine::create(const Config &cfg, int nch, int nstreams, int device, Engine 
   Engine *e = new (std::nothrow) Engine();
   if (!e) return kNoMem;
   e->device_ = device;
+  e->w_ = fmt ? 2 : 1;
+  e->fk_ = fmt ? kFramesF64 : kFramesF32;
   int rc = e->init(cfg, nch, nstreams);
   if (rc != kOk) {
     delete e;
@@ -800,12 +803,12 @@ F32View Engine::f32_view(int f, const ExtIn *ein, const ExtOut *eout) const
     v.ext = const_cast<float *>(ein->ptr);
     v.ext_begin = ein->begin;
     v.ext_end = ein->end;
-    v.ext_stream_stride = ein->stride_floats;
+    v.ext_stream_stride = ein->stride_elems;
   } else if (eout && eout->ptr) {
     v.ext = eout->ptr;
     v.ext_begin = eout->begin;
     v.ext_end = eout->end;
-    v.ext_stream_stride = eout->stride_floats;
+    v.ext_stream_stride = eout->stride_elems;
   }
   return v;
 }
@@ -828,7 +831,7 @@ int Engine::ensure_ring(int f, long long live_needed)
   if (r.buf && r.cap >= live_needed) return kOk;
   { int rcj = join_side(); if (rcj) return rcj; } // seam kernels on the side stream may still write the old ring
   const long long cap = next_pow2(std::max<long long>({live_needed, r.cap * 2, 4096}));
-  const size_t bytes = r.f32 ? size_t(cap) * nch_ * S_ * sizeof(float) : size_t(cap) * C_ * sizeof(double);
+  const size_t bytes = r.f32 ? size_t(cap) * nch_ * S_ * w_ * sizeof(float) : size_t(cap) * C_ * sizeof(double);
   void *nb = nullptr;
   ALLOC_TRY(&nb, bytes);
   HIP_TRY(hipMemsetAsync(nb, 0, bytes, stream_));
@@ -852,7 +855,7 @@ int Engine::ensure_ring(int f, long long live_needed)
       sd.mask = old.cap - 1;
       sd.chan_stride = old.cap;
     }
-    HIP_TRY(launch_copy(r.f32, sf, sd, df, dd, a0, a1, C_, stream_));
+    HIP_TRY(launch_copy(r.f32 ? fk_ : 0, sf, sd, df, dd, a0, a1, C_, stream_));
     garbage_.push_back(old.buf);
   } else {
     r.buf = nb;
@@ -882,7 +885,8 @@ void Engine::note_input(Book &b, size_t n) const
   long long &rd = b.rd[i];                                                                                         \
   long long &wro = b.wr[(i) + 1];                                                                                  \
   const long long occ = b.wr[i] - rd;                                                                              \
-  const bool src_f32 = (i) == 0, dst_f32 = (i) + 1 == ns;                                                          \
+  /* frame kind of each end (0 = fp64 ring): the launchers' src_f32 / dst_f32, also read as "frames?" */               \
+  const int src_f32 = (i) == 0 ? fk_ : 0, dst_f32 = (i) + 1 == ns ? fk_ : 0;                                     \
   const long long rd_before = rd, wro_before = wro;                                                                \
   const long long out_offset = (i) + 1 < ns ? plan_.stages[(i) + 1].preload : -b.trimmed;                          \
   const F32View nof = {};                                                                                          \
@@ -1139,19 +1143,21 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     // fp64 rings on either side) to the generic one.  At most three launches: generic head, lean middle, generic tail.
     int f0 = 0, f1 = 0;
     FastIo io = {};
+    io.dio = w_ == 2 ? 1 : 0;                  // float64 frames: the *_dio_kernel instances
+    const uintptr_t amask = 8 * uintptr_t(w_) - 1; // a channel pair of a frame as one 8- (16-) byte word
     if (split) {
       // Sub-blocked form: ONE launch of nblocks * nsub workgroups per channel pair.  Every sub-block's 4096-frame window lies
       // inside its block's own input span, i.e. in the caller's buffer or, below it, in fifo 0's ring; outputs go to the next
       // fifo's fp64 ring at any position.  (Decided when the handle was opened: first stage, even channels, not the last stage.)
-      if (!s32 || (nch_ & 1) || !ein.ptr || (ein.stride_floats & 1)) return kInternal;
+      if (!s32 || (nch_ & 1) || !ein.ptr || (ein.stride_elems & 1)) return kInternal;
       io.in = ein.ptr;
       io.in_ring = static_cast<const float *>(rings_[0].buf);
       io.in_ring_mask = rings_[0].cap - 1;
       io.in_ring_stream_stride = rings_[0].cap * nch_;
       io.in_abs0 = ein.begin;
-      io.in_stream_stride = ein.stride_floats;
+      io.in_stream_stride = ein.stride_elems;
       io.nch = nch_;
-      io.in_unaligned = (reinterpret_cast<uintptr_t>(ein.ptr) & 7) ? 1 : 0;
+      io.in_unaligned = (reinterpret_cast<uintptr_t>(ein.ptr) & amask) ? 1 : 0;
       int omode = 1;
       if (!dst_f32) {
         io.out64 = static_cast<double *>(rings_[i + 1].buf);
@@ -1160,14 +1166,14 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       } else {
         // float frames out: straight into the caller's buffer when every output of this launch lies inside it (a flow / a
         // mirrored push), else output by output wherever the fifo has it (RR_push: everything into the ring)
-        const bool ext_ok = eout.ptr && !(eout.stride_floats & 1);
+        const bool ext_ok = eout.ptr && !(eout.stride_elems & 1);
         const bool all_inside = ext_ok && wro >= eout.begin && wro + count <= eout.end;
-        omode = (all_inside && !(reinterpret_cast<uintptr_t>(eout.ptr) & 7)) ? 0 : 2;
+        omode = (all_inside && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 0 : 2;
         io.out = ext_ok ? eout.ptr : nullptr;
         io.out_abs0 = ext_ok ? eout.begin : 0;
         io.out_end = ext_ok ? eout.end : 0; // (empty range: every output goes to the ring)
-        io.out_stream_stride = ext_ok ? eout.stride_floats : 0;
-        io.out_unaligned = (ext_ok && (reinterpret_cast<uintptr_t>(eout.ptr) & 7)) ? 1 : 0;
+        io.out_stream_stride = ext_ok ? eout.stride_elems : 0;
+        io.out_unaligned = (ext_ok && (reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 1 : 0;
         io.out_ring = static_cast<float *>(rings_[i + 1].buf);
         io.out_ring_mask = rings_[i + 1].cap - 1;
         io.out_ring_stream_stride = rings_[i + 1].cap * nch_;
@@ -1193,8 +1199,8 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       prof_end(pi);
     } else
     if (fu.cfm && s32 && dst_f32 && !(nch_ & 1) && ein.ptr && eout.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
-        !(reinterpret_cast<uintptr_t>(ein.ptr) & 7) && !(reinterpret_cast<uintptr_t>(eout.ptr) & 7) && !(ein.stride_floats & 1) &&
-        !(eout.stride_floats & 1)) {
+        !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask) && !(ein.stride_elems & 1) &&
+        !(eout.stride_elems & 1)) {
       const long long P = 1LL << pend_log2p, q = fa.d.q;
       // (a block that starts below the caller's buffer takes its head from fifo 0's ring: the lean kernel handles that too)
       const long long hi = (ein.end - P) >= 0 ? (ein.end - P) / q - pend.B0 + 1 : 0;
@@ -1215,11 +1221,11 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       io.out = eout.ptr;
       io.in_abs0 = ein.begin;
       io.out_abs0 = eout.begin;
-      io.in_stream_stride = ein.stride_floats;
-      io.out_stream_stride = eout.stride_floats;
+      io.in_stream_stride = ein.stride_elems;
+      io.out_stream_stride = eout.stride_elems;
       io.nch = nch_;
     } else if (fu.cfm && s32 && !dst_f32 && !(nch_ & 1) && ein.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
-               !(reinterpret_cast<uintptr_t>(ein.ptr) & 7) && !(ein.stride_floats & 1)) {
+               !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(ein.stride_elems & 1)) {
       // the polyphase stage feeds another stage: same lean kernel, its outputs into the next fifo's fp64 ring (any ring
       // position: the kernel masks the index), so only the input side limits the range
       const long long P = 1LL << pend_log2p, q = fa.d.q;
@@ -1231,7 +1237,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       io.in_ring_mask = rings_[0].cap - 1;
       io.in_ring_stream_stride = rings_[0].cap * nch_;
       io.in_abs0 = ein.begin;
-      io.in_stream_stride = ein.stride_floats;
+      io.in_stream_stride = ein.stride_elems;
       io.nch = nch_;
       io.out64 = static_cast<double *>(rings_[i + 1].buf);
       io.out64_mask = rings_[i + 1].cap - 1;
@@ -1247,7 +1253,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       const char *kn = nullptr;
       if (fast) HIP_TRY(launch_fused_fast(pend_log2p, fr, io, stream_, &kn));
       else
-        HIP_TRY(launch_fused(pend_log2n, pend_log2p, s32, dst_f32, s32 ? f32_view(0, &ein, nullptr) : nof,
+        HIP_TRY(launch_fused(pend_log2n, pend_log2p, s32 ? fk_ : 0, dst_f32, s32 ? f32_view(0, &ein, nullptr) : nof,
                              s32 ? nod : f64_view(i - 1), dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof,
                              dst_f32 ? nod : f64_view(i + 1), fr, stream_, &kn));
       prof_name(pi, kn);
@@ -1440,7 +1446,7 @@ int Engine::spill_mirror()
   src.ext_end = a1;
   src.ext_stream_stride = (long long)mir_stride_ * nch_;
   F64View nod = {};
-  HIP_TRY(launch_copy(true, src, nod, dst, nod, a0, a1, C_, stream_));
+  HIP_TRY(launch_copy(fk_, src, nod, dst, nod, a0, a1, C_, stream_));
   return kOk;
 }
 
@@ -1456,14 +1462,14 @@ int Engine::feed_impl(const float *d_in, size_t stride_frames, size_t isamp, flo
   ein.ptr = d_in;
   ein.begin = book_.wr[0];
   ein.end = ein.begin + (long long)isamp;
-  ein.stride_floats = (long long)stride_frames * nch_;
+  ein.stride_elems = (long long)stride_frames * nch_;
   ExtOut eout;
   const long long wr_out0 = book_.wr.back();
   if (d_out && out_cap && book_.rd.back() == wr_out0) {
     eout.ptr = d_out;
     eout.begin = wr_out0;
     eout.end = wr_out0 + (long long)out_cap;
-    eout.stride_floats = (long long)out_stride * nch_;
+    eout.stride_elems = (long long)out_stride * nch_;
   }
   size_t done = 0;
   while (done < isamp) {
@@ -1480,7 +1486,7 @@ int Engine::feed_impl(const float *d_in, size_t stride_frames, size_t isamp, flo
     if (rc) return rc;
     F32View src = f32_view(0, &ein, nullptr), dst = f32_view(0, nullptr, nullptr);
     F64View nod = {};
-    HIP_TRY(launch_copy(true, src, nod, dst, nod, a0, a1, C_, stream_));
+    HIP_TRY(launch_copy(fk_, src, nod, dst, nod, a0, a1, C_, stream_));
   }
   { int rcj = join_side(); if (rcj) return rcj; }
   if (eout.ptr) {
@@ -1508,8 +1514,9 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
   if (poisoned_) return kInternal;
   if (!ibuf || !isamp) return kOk;
   if (isamp > plan_.isamp_max) isamp = plan_.isamp_max;
-  const size_t need = isamp * size_t(nch_) * size_t(S_);
-  const size_t row = isamp * nch_ * sizeof(float);
+  const size_t nw = size_t(nch_) * w_; // 4-byte words per frame
+  const size_t need = isamp * nw * size_t(S_);
+  const size_t row = isamp * nw * sizeof(float);
   if (need * sizeof(float) <= kZeroCopyMaxBytes) {
     // plugin-sized push: the kernels read it in place from the page-locked slot; the slot is released by an event behind the
     // push's last kernel (two slots alternate, so this only ever waits for the push before the previous one)
@@ -1520,7 +1527,7 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
     }
     int rp = pinned_reserve(slot, need);
     if (rp) return rp;
-    for (int s = 0; s < S_; ++s) std::memcpy(slot.p + size_t(s) * isamp * nch_, ibuf + size_t(s) * stream_stride * nch_, row);
+    for (int s = 0; s < S_; ++s) std::memcpy(slot.p + size_t(s) * isamp * nw, ibuf + size_t(s) * stream_stride * nw, row);
     // mirror the output when the fifo is empty (the plugin pulls until it is): the exact number of frames this push makes
     // available comes from a dry run of the counters
     float *mir = nullptr;
@@ -1536,8 +1543,8 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
         done += n;
       }
       cap = size_t(trial.wr.back() - trial.rd.back());
-      if (cap && cap * size_t(nch_) * size_t(S_) * sizeof(float) <= kZeroCopyMaxBytes) {
-        int rm = pinned_reserve(pin_mir_, cap * size_t(nch_) * size_t(S_));
+      if (cap && cap * nw * size_t(S_) * sizeof(float) <= kZeroCopyMaxBytes) {
+        int rm = pinned_reserve(pin_mir_, cap * nw * size_t(S_));
         if (rm) return rm;
         mir = pin_mir_.p;
       }
@@ -1573,12 +1580,12 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
     }
     int rp = pinned_reserve(slot, need);
     if (rp) return rp;
-    for (int s = 0; s < S_; ++s) std::memcpy(slot.p + size_t(s) * isamp * nch_, ibuf + size_t(s) * stream_stride * nch_, row);
+    for (int s = 0; s < S_; ++s) std::memcpy(slot.p + size_t(s) * isamp * nw, ibuf + size_t(s) * stream_stride * nw, row);
     HIP_TRY(hipMemcpyAsync(d_stage_, slot.p, need * sizeof(float), hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipEventRecord(slot.done, stream_));
     slot.pending = true;
   } else if (S_ == 1) HIP_TRY(hipMemcpyAsync(d_stage_, ibuf, row, hipMemcpyHostToDevice, stream_));
-  else HIP_TRY(hipMemcpy2DAsync(d_stage_, row, ibuf, stream_stride * nch_ * sizeof(float), row, S_, hipMemcpyHostToDevice, stream_));
+  else HIP_TRY(hipMemcpy2DAsync(d_stage_, row, ibuf, stream_stride * nw * sizeof(float), row, S_, hipMemcpyHostToDevice, stream_));
   return feed(d_stage_, isamp, isamp, nullptr, 0, 0, nullptr);
 }
 
@@ -1589,7 +1596,8 @@ int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_ho
   const Ring &r = rings_[f];
   const long long rd = book_.rd[f];
   if (to_host) {
-    const size_t total = frames * size_t(nch_) * size_t(S_) * sizeof(float);
+    const size_t nw = size_t(nch_) * w_; // 4-byte words per frame
+    const size_t total = frames * nw * size_t(S_) * sizeof(float);
     const bool pinned = total <= kPinnedMaxBytes;
     if (pinned) {
       int rp = pinned_reserve(pin_out_, total / sizeof(float));
@@ -1599,27 +1607,27 @@ int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_ho
     while (done < frames) { // at most two segments (ring wrap)
       const long long pos = (rd + (long long)done) & (r.cap - 1);
       const size_t n = std::min<size_t>(frames - done, size_t(r.cap - pos));
-      const size_t row = n * nch_ * sizeof(float);
-      const float *src = static_cast<const float *>(r.buf) + pos * nch_;
-      float *d = pinned ? pin_out_.p + done * nch_ : dst + done * nch_;
-      const size_t dpitch = (pinned ? frames : stride_frames) * nch_ * sizeof(float);
-      HIP_TRY(hipMemcpy2DAsync(d, dpitch, src, size_t(r.cap) * nch_ * sizeof(float), row, S_, hipMemcpyDeviceToHost, stream_));
+      const size_t row = n * nw * sizeof(float);
+      const float *src = static_cast<const float *>(r.buf) + pos * nw;
+      float *d = pinned ? pin_out_.p + done * nw : dst + done * nw;
+      const size_t dpitch = (pinned ? frames : stride_frames) * nw * sizeof(float);
+      HIP_TRY(hipMemcpy2DAsync(d, dpitch, src, size_t(r.cap) * nw * sizeof(float), row, S_, hipMemcpyDeviceToHost, stream_));
       done += n;
     }
     HIP_TRY(hipStreamSynchronize(stream_));
     if (pinned)
       for (int s = 0; s < S_; ++s)
-        std::memcpy(dst + size_t(s) * stride_frames * nch_, pin_out_.p + size_t(s) * frames * nch_, frames * nch_ * sizeof(float));
+        std::memcpy(dst + size_t(s) * stride_frames * nw, pin_out_.p + size_t(s) * frames * nw, frames * nw * sizeof(float));
     free_garbage(); // everything queued before this point has finished: retired rings / drain buffers can go
   } else {
     ExtOut eo;
     eo.ptr = dst;
     eo.begin = rd;
     eo.end = rd + (long long)frames;
-    eo.stride_floats = (long long)stride_frames * nch_;
+    eo.stride_elems = (long long)stride_frames * nch_;
     F32View src = f32_view(f, nullptr, nullptr), dv = f32_view(f, nullptr, &eo);
     F64View nod = {};
-    HIP_TRY(launch_copy(true, src, nod, dv, nod, rd, rd + (long long)frames, C_, stream_));
+    HIP_TRY(launch_copy(fk_, src, nod, dv, nod, rd, rd + (long long)frames, C_, stream_));
   }
   return kOk;
 }
@@ -1643,10 +1651,10 @@ int Engine::pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *o
         HIP_TRY(hipEventSynchronize(pin_mir_.done));
         pin_mir_.pending = false;
       }
-      const size_t dstride = S_ > 1 ? stream_stride : n;
+      const size_t dstride = S_ > 1 ? stream_stride : n, nw = size_t(nch_) * w_;
       for (int s = 0; s < S_; ++s)
-        std::memcpy(obuf + size_t(s) * dstride * nch_, pin_mir_.p + (size_t(s) * mir_stride_ + size_t(rd - mir_begin_)) * nch_,
-                    n * nch_ * sizeof(float));
+        std::memcpy(obuf + size_t(s) * dstride * nw, pin_mir_.p + (size_t(s) * mir_stride_ + size_t(rd - mir_begin_)) * nw,
+                    n * nw * sizeof(float));
       if (rd + (long long)n == mir_end_) mir_begin_ = mir_end_ = 0;
     } else {
       if (mir_end_ > mir_begin_) { // the request reaches past the mirror: the device ring takes what is left of it first
@@ -1698,7 +1706,7 @@ int Engine::flow_host(const float *ibuf, size_t in_stride, float *obuf, size_t o
   int rc = pull_host(obuf, out_stride, osamp, &n1);
   if (rc) return rc;
   if (isamp && (rc = push_host(ibuf, in_stride, isamp))) return rc;
-  if (n1 < osamp && obuf && (rc = pull_host(obuf + n1 * nch_, out_stride, osamp - n1, &n2))) return rc;
+  if (n1 < osamp && obuf && (rc = pull_host(obuf + n1 * nch_ * w_, out_stride, osamp - n1, &n2))) return rc;
   if (iused) *iused = isamp;
   if (ogen) *ogen = n1 + n2;
   return kOk;
@@ -1715,7 +1723,7 @@ int Engine::flow_device(const float *ibuf, size_t in_stride, float *obuf, size_t
   if (rc) return rc;
   if (isamp) {
     // frames produced by this push land directly in the caller's buffer (no ring round trip)
-    float *direct = obuf && n1 < osamp ? obuf + n1 * nch_ : nullptr;
+    float *direct = obuf && n1 < osamp ? obuf + n1 * nch_ * w_ : nullptr;
     rc = feed(ibuf, S_ > 1 ? in_stride : isamp, isamp, direct, S_ > 1 ? out_stride : osamp, direct ? osamp - n1 : 0, &n2);
     if (rc) return rc;
     if (direct && !n2 && available() && n1 < osamp) { // the ring was not empty: fall back to a copy
@@ -1747,13 +1755,13 @@ int Engine::drain()
     if (++blocks > (1u << 20)) return fail(kInternal);
   }
   if (blocks) {
-    const size_t frames = blocks * 1024, floats = frames * size_t(nch_) * size_t(S_);
+    const size_t frames = blocks * 1024, floats = frames * size_t(nch_) * w_ * size_t(S_); // (all-zero bits: 0.0 in either format)
     float *zeros = nullptr;
     ALLOC_TRY(&zeros, floats * sizeof(float));
     HIP_TRY(hipMemsetAsync(zeros, 0, floats * sizeof(float), stream_));
     // feed them one reference block at a time so that the counter wrap in rate_input sees the same sequence
     for (size_t k = 0; k < blocks; ++k) {
-      int rc = feed(zeros + k * 1024 * nch_, frames, 1024, nullptr, 0, 0, nullptr);
+      int rc = feed(zeros + k * 1024 * nch_ * w_, frames, 1024, nullptr, 0, 0, nullptr);
       if (rc) { garbage_.push_back(zeros); return fail(rc); }
     }
     garbage_.push_back(zeros);

@@ -58,10 +58,12 @@ class Engine {
 public:
   // device: HIP device index the handle lives on; -1 = the calling thread's current device.  kInvParam for an index the
   // process does not have, kUninit for a device that is not gfx950.
-  static int create(const Config &cfg, int nch, int nstreams, int device, Engine **out);
+  // fmt: 0 = interleaved float32 frames at both ends, 1 = interleaved float64 frames (RRX_FMT_*); fixed for the handle's life
+  static int create(const Config &cfg, int nch, int nstreams, int device, Engine **out, int fmt = 0);
   ~Engine();
 
   int device() const { return device_; }
+  int format() const { return w_ == 2 ? 1 : 0; }
 
   const ChainPlan &plan() const { return plan_; }
   int nch() const { return nch_; }
@@ -81,7 +83,9 @@ public:
   // test hook: make the n-th device allocation from now on (n >= 1, process-wide) fail with hipErrorOutOfMemory; 0 disarms
   static void fail_alloc_after(int n);
 
-  // Host-memory API (RR_push / RR_pull / RR_flow semantics). Buffers: [stream][frame][channel] with
+  // Host-memory API (RR_push / RR_pull / RR_flow semantics). Buffers: [stream][frame][channel] of the handle's sample
+  // format (float, or double behind a float pointer on a format-1 handle: the pointers are only ever moved in 4-byte words)
+  // with
   // `stream_stride` frames between streams (ignored when there is one stream).
   int push_host(const float *ibuf, size_t stream_stride, size_t isamp);
   int pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *ogen);
@@ -103,14 +107,19 @@ public:
 private:
   Engine() = default;
   int init(const Config &cfg, int nch, int nstreams);
+  // Sample format of fifo 0 and the last fifo (the intermediate fifos are fp64 rings either way): w_ = 4-byte words per
+  // sample (1: float32 frames, 2: float64 frames), fk_ = the frame kind the kernels see (kFramesF32 / kFramesF64).  Host
+  // code moves frames as w_ * nch_ floats; kernel views and FastIo count samples.
+  int w_ = 1, fk_ = kFramesF32;
 
   struct Ring { // device ring of fifo f
     void *buf = nullptr;
-    long long cap = 0; // items (f64) or frames (f32), power of two
+    long long cap = 0; // items (f64) or frames (f32: caller-facing frames of either format), power of two
     bool f32 = false;
   };
-  struct ExtIn { const float *ptr = nullptr; long long begin = 0, end = 0, stride_floats = 0; };
-  struct ExtOut { float *ptr = nullptr; long long begin = 0, end = 0, stride_floats = 0; };
+  // caller buffers at the two ends; stride_elems = samples (floats or doubles, the handle's format) between streams
+  struct ExtIn { const float *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
+  struct ExtOut { float *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
 
   // keep_direct: frames written straight to d_out stay in the output fifo (not counted as pulled): the host mirror
   int feed(const float *d_in, size_t stride_frames, size_t isamp, float *d_out, size_t out_stride, size_t out_cap,

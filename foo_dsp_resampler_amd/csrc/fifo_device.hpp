@@ -4,6 +4,9 @@
 
 namespace rsmp {
 
+// is_f32: kFramesF32 / kFramesF64 = interleaved frames (F32View; with kFramesF64 its ring / ext pointers address doubles
+// and its strides count doubles), 0 = planar fp64 rings (F64View).  Frames of either width are the caller-facing ends
+// (stage-0 input, final output); every test of `is_f32` as a truth value means "frames".
 struct AnyView {
   int is_f32;
   F32View f;
@@ -11,8 +14,8 @@ struct AnyView {
 };
 
 struct ChanRef { // per-channel precomputed addressing
-  int is_f32;
-  // f32
+  int is_f32; // as AnyView::is_f32
+  // frames (with kFramesF64 the two pointers address doubles)
   const float *ring32;
   const float *ext32;
   long long mask32, ext_begin, ext_end;
@@ -28,8 +31,13 @@ __device__ __forceinline__ ChanRef chan_ref(const AnyView &v, int c)
   r.is_f32 = v.is_f32;
   if (v.is_f32) {
     const int s = c / v.f.nch, ch = c - s * v.f.nch;
-    r.ring32 = v.f.ring + s * v.f.ring_stream_stride + ch;
-    r.ext32 = v.f.ext ? v.f.ext + s * v.f.ext_stream_stride + ch : nullptr;
+    if (v.is_f32 == kFramesF64) { // (the same element offsets, in doubles)
+      r.ring32 = reinterpret_cast<const float *>(reinterpret_cast<const double *>(v.f.ring) + s * v.f.ring_stream_stride + ch);
+      r.ext32 = v.f.ext ? reinterpret_cast<const float *>(reinterpret_cast<const double *>(v.f.ext) + s * v.f.ext_stream_stride + ch) : nullptr;
+    } else {
+      r.ring32 = v.f.ring + s * v.f.ring_stream_stride + ch;
+      r.ext32 = v.f.ext ? v.f.ext + s * v.f.ext_stream_stride + ch : nullptr;
+    }
     r.mask32 = v.f.ring_mask;
     r.ext_begin = v.f.ext_begin;
     r.ext_end = v.f.ext_end;
@@ -48,6 +56,11 @@ __device__ __forceinline__ ChanRef chan_ref(const AnyView &v, int c)
 
 __device__ __forceinline__ double fifo_get(const ChanRef &r, long long a)
 {
+  if (r.is_f32 == kFramesF64) {
+    const double *e = reinterpret_cast<const double *>(r.ext32), *g = reinterpret_cast<const double *>(r.ring32);
+    if (e && a >= r.ext_begin && a < r.ext_end) return e[(a - r.ext_begin) * r.nch];
+    return g[(a & r.mask32) * r.nch];
+  }
   if (r.is_f32) {
     if (r.ext32 && a >= r.ext_begin && a < r.ext_end) return (double)r.ext32[(a - r.ext_begin) * r.nch];
     return (double)r.ring32[(a & r.mask32) * r.nch];
@@ -57,7 +70,11 @@ __device__ __forceinline__ double fifo_get(const ChanRef &r, long long a)
 
 __device__ __forceinline__ void fifo_put(const ChanRef &r, long long a, double v)
 {
-  if (r.is_f32) {
+  if (r.is_f32 == kFramesF64) {
+    double *e = reinterpret_cast<double *>(const_cast<float *>(r.ext32)), *g = reinterpret_cast<double *>(const_cast<float *>(r.ring32));
+    if (e && a >= r.ext_begin && a < r.ext_end) e[(a - r.ext_begin) * r.nch] = v;
+    else g[(a & r.mask32) * r.nch] = v;
+  } else if (r.is_f32) {
     if (r.ext32 && a >= r.ext_begin && a < r.ext_end) const_cast<float *>(r.ext32)[(a - r.ext_begin) * r.nch] = (float)v;
     else const_cast<float *>(r.ring32)[(a & r.mask32) * r.nch] = (float)v;
   } else
@@ -66,7 +83,8 @@ __device__ __forceinline__ void fifo_put(const ChanRef &r, long long a, double v
 
 
 // `len` consecutive samples of ONE channel starting at absolute index a0, when they lie contiguously in one buffer:
-// kind 1 = float32 frames (element i at p32[i * stride32]), kind 2 = the channel's fp64 ring, kind 0 = split (fifo_get).
+// kind 1 = float32 frames (element i at p32[i * stride32]), kind 2 = the channel's fp64 ring, kind 3 = float64 frames
+// (element i at p64[i * stride32]), kind 0 = split (fifo_get).
 struct ChanSpan {
   int kind;
   const float *p32;
@@ -79,12 +97,23 @@ __device__ __forceinline__ ChanSpan chan_span(const AnyView &v, int c, long long
   if (v.is_f32) {
     const int s = c / v.f.nch, ch = c - s * v.f.nch;
     r.stride32 = v.f.nch;
+    long long off = -1; // element offset from the buffer's base
+    const float *base = nullptr;
     if (v.f.ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end) {
-      r.kind = 1;
-      r.p32 = v.f.ext + s * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + ch;
+      base = v.f.ext;
+      off = s * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + ch;
     } else if ((!v.f.ext || a0 + len <= v.f.ext_begin || a0 >= v.f.ext_end) && a0 >= 0 && (a0 & v.f.ring_mask) + len <= v.f.ring_mask + 1) {
-      r.kind = 1;
-      r.p32 = v.f.ring + s * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + ch;
+      base = v.f.ring;
+      off = s * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + ch;
+    }
+    if (off >= 0) {
+      if (v.is_f32 == kFramesF64) {
+        r.kind = 3;
+        r.p64 = reinterpret_cast<const double *>(base) + off;
+      } else {
+        r.kind = 1;
+        r.p32 = base + off;
+      }
     }
   } else if (a0 >= 0 && (a0 & v.d.mask) + len <= v.d.mask + 1) {
     r.kind = 2;
@@ -116,19 +145,25 @@ __device__ __forceinline__ PairCh pair_channels(int pair, int C, int nchs, unsig
 
 // Direct addressing of `len` consecutive samples of channel pair (2*pair, 2*pair+1) starting at absolute index a0,
 // when they lie contiguously in one buffer: kind 1 = float32 frames with the two channels side by side (one 8-byte
-// word per sample), kind 2 = the two planar fp64 rings, kind 0 = not contiguous (use fifo_get / fifo_put).
+// word per sample), kind 2 = the two planar fp64 rings, kind 3 = float64 frames (one 16-byte word per sample), kind 0 = not
+// contiguous (use fifo_get / fifo_put).
 struct PairSpan {
   int kind;
   float2 *p2;
-  long long fstride; // float2 elements between consecutive frames
+  long long fstride; // float2 (kind 3: double2) elements between consecutive frames
   double *pa, *pb;
   bool hasb;
+  double2 *d2;       // kind 3 = float64 frames with the two channels side by side (one 16-byte word per sample)
   __device__ __forceinline__ void get(int i, double &x, double &y) const
   {
     if (kind == 1) {
       const float2 f = p2[i * fstride];
       x = (double)f.x;
       y = (double)f.y;
+    } else if (kind == 3) {
+      const double2 f = d2[i * fstride];
+      x = f.x;
+      y = f.y;
     } else {
       x = pa[i];
       y = hasb ? pb[i] : 0.0;
@@ -137,6 +172,7 @@ struct PairSpan {
   __device__ __forceinline__ void put(int i, double x, double y) const
   {
     if (kind == 1) p2[i * fstride] = make_float2((float)x, (float)y);
+    else if (kind == 3) d2[i * fstride] = make_double2(x, y);
     else {
       pa[i] = x;
       if (hasb) pb[i] = y;
@@ -155,6 +191,13 @@ template <int NPTS, typename CT> __device__ __forceinline__ void span_load(const
       const float2 f = sp.p2[(i0 + s * istride) * sp.fstride];
       dst[s].x = (double)f.x;
       dst[s].y = (double)f.y;
+    }
+  } else if (sp.kind == 3) {
+#pragma unroll
+    for (int s = 0; s < NPTS; ++s) {
+      const double2 f = sp.d2[(i0 + s * istride) * sp.fstride];
+      dst[s].x = f.x;
+      dst[s].y = f.y;
     }
   } else { // (pair_span sets pb = pa for a one-channel pair: both loads are unconditional)
 #pragma unroll
@@ -179,7 +222,23 @@ __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pai
   r.fstride = 1;
   r.pa = r.pb = nullptr;
   r.hasb = hasb;
-  if (v.is_f32) {
+  r.d2 = nullptr;
+  if (v.is_f32 == kFramesF64) { // as below, in doubles; a pair is 16-byte aligned or not taken
+    if (hasb && !(v.f.nch & 1)) {
+      const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
+      const double *ext = reinterpret_cast<const double *>(v.f.ext), *ring = reinterpret_cast<const double *>(v.f.ring);
+      const double *p = nullptr;
+      if (ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end)
+        p = ext + strm * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + 2 * pin;
+      else if ((!ext || a0 + len <= v.f.ext_begin || a0 >= v.f.ext_end) && (a0 & v.f.ring_mask) + len <= v.f.ring_mask + 1)
+        p = ring + strm * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + 2 * pin;
+      if (p && (reinterpret_cast<unsigned long long>(p) & 15) == 0) {
+        r.kind = 3;
+        r.d2 = reinterpret_cast<double2 *>(const_cast<double *>(p));
+        r.fstride = hp;
+      }
+    }
+  } else if (v.is_f32) {
     if (hasb && !(v.f.nch & 1)) {
       const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
       float *p = nullptr;
@@ -240,10 +299,11 @@ inline int frame_pairs(const AnyView &in, const AnyView &out, int C)
   return v->f.nch / 2;
 }
 
-inline AnyView make_view(bool is_f32, const F32View &f, const F64View &d)
+// frames: 0 = the fp64 rings `d`, kFramesF32 / kFramesF64 = the frames `f` (the launchers' src_f32 / dst_f32 arguments)
+inline AnyView make_view(int frames, const F32View &f, const F64View &d)
 {
   AnyView v;
-  v.is_f32 = is_f32 ? 1 : 0;
+  v.is_f32 = frames;
   v.f = f;
   v.d = d;
   return v;

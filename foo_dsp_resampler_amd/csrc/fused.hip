@@ -136,7 +136,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       bool fast = false;
       const float2 *p2 = nullptr;
       int fstride = 1; // float2 elements between consecutive frames of this channel pair
-      if (in.is_f32 && hasb && !(in.f.nch & 1)) { // channels 2p, 2p+1 sit side by side in every frame
+      if (in.is_f32 == kFramesF32 && hasb && !(in.f.nch & 1)) { // channels 2p, 2p+1 sit side by side in every frame
         const int hp = in.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
         fstride = hp;
         if (in.f.ext && e0 >= in.f.ext_begin && e0 + P <= in.f.ext_end) {
@@ -149,12 +149,20 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           p2 = reinterpret_cast<const float2 *>(p);
         }
       }
+      // float64 frames: the same pairs as one 16-byte word per sample (pair_span kind 3), else element-wise
+      const PairSpan d64 = in.is_f32 == kFramesF64 ? pair_span(in, pair, hasb, e0, P, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
       if constexpr (FWD8) { // every thread takes 8 points of the P-point forward transform: x[tid + s*T], T = P/8
         if (fast) {
 #pragma unroll
           for (int s = 0; s < 8; ++s) {
             const float2 f = p2[(tid + s * T) * fstride];
             u8[s] = {(double)f.x, (double)f.y};
+          }
+        } else if (d64.kind == 3) {
+#pragma unroll
+          for (int s = 0; s < 8; ++s) {
+            const double2 f = d64.d2[(tid + s * T) * d64.fstride];
+            u8[s] = {f.x, f.y};
           }
         } else {
           const ChanRef ia = chan_ref(in, ca), ib = chan_ref(in, hasb ? cb : ca);
@@ -173,8 +181,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             v[s] = {(double)f.x, (double)f.y};
           }
         } else {
-          const PairSpan sp = in.is_f32 ? PairSpan{0, nullptr, 1, nullptr, nullptr, hasb} : pair_span(in, pair, hasb, e0, P, ca);
-          if (sp.kind) { // planar fp64 rings (the producer is another stage), block contiguous in both
+          const PairSpan sp = in.is_f32 == kFramesF32 ? PairSpan{0, nullptr, 1, nullptr, nullptr, hasb} : in.is_f32 ? d64 : pair_span(in, pair, hasb, e0, P, ca);
+          if (sp.kind) { // planar fp64 rings (the producer is another stage) or float64 frames, block contiguous
             span_load<16>(sp, tid, TF, v);
           } else {
             const ChanRef ia = chan_ref(in, ca), ib = chan_ref(in, hasb ? cb : ca);
@@ -323,32 +331,33 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       const bool run = !(RSMP_DBGBITS & 1) && fb.cnt > 0;
 
       bool ofast = false;
-      float *obase = nullptr; // frame i_lo's first float of this pair
-      int ofs = 2;            // floats between consecutive frames
+      char *obase = nullptr;  // frame i_lo's first sample of this pair
+      int ofs = 2;            // samples between consecutive frames
+      const int esz = out.is_f32 == kFramesF64 ? 8 : 4; // bytes per sample of the destination frames
       {
         const long long o0 = a.out_offset2 + fb.i_lo, o1 = o0 + fb.cnt;
         if (out.is_f32 && hasb && !(out.f.nch & 1)) {
           const int hp = out.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
           ofs = out.f.nch;
           if (out.f.ext && o0 >= out.f.ext_begin && o1 <= out.f.ext_end) {
-            obase = out.f.ext + strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin;
+            obase = reinterpret_cast<char *>(out.f.ext) + (strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin) * esz;
             ofast = true;
           } else if ((!out.f.ext || o0 >= out.f.ext_end || o1 <= out.f.ext_begin) &&
                      (o0 & out.f.ring_mask) + (o1 - o0) <= out.f.ring_mask + 1) {
-            obase = out.f.ring + strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin;
+            obase = reinterpret_cast<char *>(out.f.ring) + (strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin) * esz;
             ofast = true;
           }
-          ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & 7) == 0;
+          ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & (2 * esz - 1)) == 0;
         }
       }
-      // The whole two-round sequence is instantiated twice and chosen by one uniform branch: FAST writes
-      // float2 frames at obase + 32-bit offsets and keeps none of the generic fifo addressing state alive
+      // The whole two-round sequence is instantiated three times and chosen by one uniform branch: FAST writes
+      // float2 (DBL: double2) frames at obase + 32-bit offsets and keeps none of the generic fifo addressing state alive
       // (that state is what used to spill scalar registers inside the loop).
       auto both_rounds = [&](auto fast_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value;
+        constexpr bool FAST = decltype(fast_tag)::value != 0, DBL = decltype(fast_tag)::value == 2;
         const ChanRef oa = chan_ref(out, ca), ob = chan_ref(out, hasb ? cb : ca); // dead code when FAST
-        char *const obytes = reinterpret_cast<char *>(obase);
-        const int frame_bytes = ofs * 4, period4_bytes = 4 * pl * frame_bytes; // output bytes per frame / per column step
+        char *const obytes = obase;
+        const int frame_bytes = ofs * (DBL ? 8 : 4), period4_bytes = 4 * pl * frame_bytes; // output bytes per frame / per column step
 
         // A operands are double-buffered: the next item's tile is in flight (L2 latency) while this one computes
         double cn_[SPAN];
@@ -371,7 +380,9 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           const int ib = pend_ib + u * 4 * pl;
           if (((pend_allv >> u) & 1) || (ib >= fb.irel_lo && ib < pend_hi)) {
             const int orel = ib - fb.irel_lo;
-            if (FAST) {
+            if (DBL) {
+              *reinterpret_cast<double2 *>(obytes + (pend_off + u * period4_bytes)) = make_double2(pA[u], pB[u]);
+            } else if (FAST) {
               *reinterpret_cast<float2 *>(obytes + (pend_off + u * period4_bytes)) = make_float2((float)pA[u], (float)pB[u]);
             } else {
               const long long oabs = a.out_offset2 + fb.i_lo + orel;
@@ -386,7 +397,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             // Two column steps whose 2 x 64 outputs are all stored, stereo frames: lane rows hi and hi^1 hold adjacent
             // frames, so after a v_permlane16_swap even rows own two adjacent frames of step u and odd rows two of
             // step u+1 -- one 16-byte store per lane instead of two 8-byte ones (a store costs a wave ~390 cycles here).
-            if (FAST && ofs == 2 && u + 1 < pend_n && ((pend_allv >> u) & 3) == 3) {
+            if (FAST && !DBL && ofs == 2 && u + 1 < pend_n && ((pend_allv >> u) & 3) == 3) {
               typedef unsigned u2v __attribute__((ext_vector_type(2)));
               const u2v sA = __builtin_amdgcn_permlane16_swap(__float_as_uint((float)pA[u]), __float_as_uint((float)pA[u + 1]), false, false);
               const u2v sB = __builtin_amdgcn_permlane16_swap(__float_as_uint((float)pB[u]), __float_as_uint((float)pB[u + 1]), false, false);
@@ -509,8 +520,9 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           poly_round(fb.KA, fb.K, reinterpret_cast<const double2 *>(lds) - kSB0 * T, kSB0 * T, V + kPad - 4 * SPAN);
         flush();
       };
-      if (ofast) both_rounds(std::true_type{});
-      else both_rounds(std::false_type{});
+      if (ofast && esz == 8) both_rounds(std::integral_constant<int, 2>{});
+      else if (ofast) both_rounds(std::integral_constant<int, 1>{});
+      else both_rounds(std::integral_constant<int, 0>{});
     } else
     // ---------------------------------------------------------------- polyphase FIR from LDS (vector pipe)
     if (!(RSMP_DBGBITS & 1) && poly_thread && fb.cnt > 0) {
@@ -522,9 +534,12 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       bool ofast = false;
       float *obase = nullptr; // points at frame i_lo's first float of this pair
       int ostride = 1;        // float2 elements between consecutive frames
+      // float64 frames: pair_span's kind 3 over the block's outputs (one 16-byte store per output)
+      const PairSpan o64 = out.is_f32 == kFramesF64 ? pair_span(out, pair, hasb, a.out_offset2 + fb.i_lo, fb.cnt, ca)
+                                                    : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
       {
         const long long o0 = a.out_offset2 + fb.i_lo, o1 = o0 + fb.cnt;
-        if (out.is_f32 && hasb && !(out.f.nch & 1)) {
+        if (out.is_f32 == kFramesF32 && hasb && !(out.f.nch & 1)) {
           const int hp = out.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
           ostride = hp;
           if (out.f.ext && o0 >= out.f.ext_begin && o1 <= out.f.ext_end) {
@@ -573,6 +588,10 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             for (int g = 0; g < G; ++g)
               if (ok[g]) o2[g * ostride] = make_float2((float)accA[g], (float)accB[g]);
           }
+        } else if (o64.kind == 3) {
+#pragma unroll
+          for (int g = 0; g < G; ++g)
+            if (ok[g]) o64.d2[(orel + g) * o64.fstride] = make_double2(accA[g], accB[g]);
         } else {
           const ChanRef oa = chan_ref(out, ca), ob = chan_ref(out, hasb ? cb : ca);
           const long long oabs = a.out_offset2 + fb.i_lo + orel;
@@ -719,7 +738,7 @@ static hipError_t launch_fused_t(const AnyView &in, const AnyView &out, const Fu
   return hipGetLastError();
 }
 
-hipError_t launch_seam(bool dst_f32, const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st)
+hipError_t launch_seam(int dst_f32, const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st)
 {
   const AnyView out = make_view(dst_f32, df, dd);
   dim3 sgrid(a.d.nblocks, (a.d.C + kSeamC - 1) / kSeamC), sblock(256);
@@ -755,7 +774,7 @@ bool fused_shape_supported(int log2n, int log2p, int n, int span, int max_seam_o
     return launch_fused_t<n, p, 2, ks, true>(in, out, a, st);                     \
   }
 
-hipError_t launch_fused(int log2n, int log2p, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd,
+hipError_t launch_fused(int log2n, int log2p, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
                         const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st, const char **kname)
 {
   const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);

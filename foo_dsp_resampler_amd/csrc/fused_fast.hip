@@ -66,6 +66,11 @@ namespace {
 #endif
 typedef double rsmp_d2v __attribute__((ext_vector_type(2)));
 typedef unsigned int rsmp_v2u __attribute__((ext_vector_type(2)));
+typedef unsigned int rsmp_v4u __attribute__((ext_vector_type(4)));
+// a frame's two samples of one channel pair as one word: 8 bytes of float32 frames, 16 bytes of float64 frames
+template <typename E> struct Pair2;
+template <> struct Pair2<float> { typedef float2 T; };
+template <> struct Pair2<double> { typedef double2 T; };
 __device__ __forceinline__ double2 load_g(const double2 *p)
 {
 #if RSMP_G_NT
@@ -94,9 +99,14 @@ constexpr int kSA = kFusedSA, kSB0 = kFusedSB0;
 // fifo's ring (RR_push without a destination, outputs beyond the caller's capacity): fifo_put for a channel pair.
 // TWO (sub-blocked form, 8192-point blocks): the block is ONE workgroup -- its V samples fit a pair of 4096-point component
 // transforms whole -- and the polyphase stage runs in two rounds, the second from the register slots kept across the first.
-template <int LOG2P, int KS, bool OUT64, bool SPLIT, bool OGEN, bool TWO = false>
+// E: the sample type of the caller-facing frames (float; double for the *_dio_kernel instances, FastIo::dio): only the width
+// of the frame loads and stores depends on it, the arithmetic is the same fp64 code.
+template <int LOG2P, int KS, bool OUT64, bool SPLIT, bool OGEN, bool TWO = false, typename E = float>
 __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo &io)
 {
+  typedef typename Pair2<E>::T E2;
+  const E *const io_in = reinterpret_cast<const E *>(io.in), *const io_in_ring = reinterpret_cast<const E *>(io.in_ring);
+  E *const io_out = reinterpret_cast<E *>(io.out), *const io_out_ring = reinterpret_cast<E *>(io.out_ring);
   static_assert(!TWO || SPLIT, "two rounds from registers: sub-blocked form only");
   static_assert(!SPLIT || LOG2P == 12, "sub-blocked form: 4096-point components");
   static_assert(!OGEN || (SPLIT && !OUT64), "generic float output exists for the sub-blocked form only");
@@ -165,29 +175,29 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     }
     if (SPLIT && io.in_unaligned) { // (uniform) a caller's buffer that is only 4-byte aligned: the sub-blocked form has no generic
       // kernel to hand such blocks to, so it reads the two channels separately
-      const float *pe = io.in + strm * io.in_stream_stride + 2 * pin, *pr = io.in_ring + strm * io.in_ring_stream_stride + 2 * pin;
+      const E *pe = io_in + strm * io.in_stream_stride + 2 * pin, *pr = io_in_ring + strm * io.in_ring_stream_stride + 2 * pin;
 #pragma unroll
       for (int s = 0; s < NLD; ++s) {
         const long long e = e0 + tid + s * TL;
-        const float *f = e >= io.in_abs0 ? pe + (e - io.in_abs0) * io.nch : pr + (e & io.in_ring_mask) * io.nch;
+        const E *f = e >= io.in_abs0 ? pe + (e - io.in_abs0) * io.nch : pr + (e & io.in_ring_mask) * io.nch;
         v[s] = {(double)f[0], (double)f[1]};
       }
     } else
     if (e0 >= io.in_abs0) { // uniform: the whole block lies in the caller's buffer
-      const float2 *p2 = reinterpret_cast<const float2 *>(io.in + strm * io.in_stream_stride + (e0 - io.in_abs0) * io.nch + 2 * pin);
+      const E2 *p2 = reinterpret_cast<const E2 *>(io_in + strm * io.in_stream_stride + (e0 - io.in_abs0) * io.nch + 2 * pin);
       if (ld_active) {
 #pragma unroll
         for (int s = 0; s < NLD; ++s) {
-          const float2 f = p2[(unsigned)((tid + s * TL) * hp)]; // (unsigned: scalar base + 32-bit lane offset, no 64-bit address per load)
+          const E2 f = p2[(unsigned)((tid + s * TL) * hp)]; // (unsigned: scalar base + 32-bit lane offset, no 64-bit address per load)
           (FWD8 ? u8[s & 7] : v[s]) = {(double)f.x, (double)f.y};
         }
       }
     } else if (ld_active) { // first block of a push: its head is the previous push's tail, kept in fifo 0's ring
-      const float *pe = io.in + strm * io.in_stream_stride + 2 * pin, *pr = io.in_ring + strm * io.in_ring_stream_stride + 2 * pin;
+      const E *pe = io_in + strm * io.in_stream_stride + 2 * pin, *pr = io_in_ring + strm * io.in_ring_stream_stride + 2 * pin;
 #pragma unroll
       for (int s = 0; s < NLD; ++s) {
         const long long e = e0 + tid + s * TL;
-        const float2 f = *reinterpret_cast<const float2 *>(e >= io.in_abs0 ? pe + (e - io.in_abs0) * io.nch : pr + (e & io.in_ring_mask) * io.nch);
+        const E2 f = *reinterpret_cast<const E2 *>(e >= io.in_abs0 ? pe + (e - io.in_abs0) * io.nch : pr + (e & io.in_ring_mask) * io.nch);
         (FWD8 ? u8[s & 7] : v[s]) = {(double)f.x, (double)f.y};
       }
     }
@@ -373,13 +383,13 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
   const int pl = a.polyL, step = a.step;
   const int irel_hi = fb.irel_lo + fb.cnt;
-  const int frame_bytes = io.nch * 4;
+  const int frame_bytes = io.nch * (int)sizeof(E);
   char *const obytes = (OUT64 || OGEN) ? nullptr
-                            : reinterpret_cast<char *>(io.out + strm * io.out_stream_stride + (a.out_offset2 + fb.i_lo - io.out_abs0) * io.nch + 2 * pin);
+                            : reinterpret_cast<char *>(io_out + strm * io.out_stream_stride + (a.out_offset2 + fb.i_lo - io.out_abs0) * io.nch + 2 * pin);
   // OGEN: absolute index (in the output fifo) of the block's output 0, this pair's slot of a frame in either buffer
   const long long oabs0 = a.out_offset2 + fb.i_lo;
-  float *const oext = OGEN ? io.out + strm * io.out_stream_stride + 2 * pin : nullptr;
-  float *const oring = OGEN ? io.out_ring + strm * io.out_ring_stream_stride + 2 * pin : nullptr;
+  E *const oext = OGEN ? io_out + strm * io.out_stream_stride + 2 * pin : nullptr;
+  E *const oring = OGEN ? io_out_ring + strm * io.out_ring_stream_stride + 2 * pin : nullptr;
   // OUT64: one descriptor per channel over its whole ring; output ib of the block sits at ring slot (o64 + ib) & mask
   const unsigned o64 = OUT64 ? (unsigned)((a.out_offset2 + fb.i_lo) & io.out64_mask) : 0u;
   const unsigned m64 = (unsigned)io.out64_mask;
@@ -405,9 +415,9 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     const int lane_ib = (kb + jq) * pl + rloc - fb.irel_lo; // output index relative to i_lo = lane_ib + 16 g + c * 4 * pl
     const int cnt = hi_bound - fb.irel_lo;
 #if RSMP_BUFSTORE
-    // raw buffer over this round's outputs [0, cnt) of the block: frame ib at byte ib * frame_bytes, 8 bytes of it are ours
+    // raw buffer over this round's outputs [0, cnt) of the block: frame ib at byte ib * frame_bytes, 8 (16) bytes of it are ours
     const __amdgpu_buffer_rsrc_t orsrc =
-        __builtin_amdgcn_make_buffer_rsrc(obytes, 0, (!OUT64 && !OGEN && cnt > 0) ? (cnt - 1) * frame_bytes + 8 : 0, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(obytes, 0, (!OUT64 && !OGEN && cnt > 0) ? (cnt - 1) * frame_bytes + 2 * (int)sizeof(E) : 0, 0x00020000);
 #endif
     const int step4 = 4 * step, pl4 = 4 * pl;
     // store offset of a tile = (this lane's part, once per round) + (the tile's part, scalar): one vector add per tile.  Only the
@@ -491,12 +501,12 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       if constexpr (OGEN) {
         if ((unsigned)ib < (unsigned)cnt && 16 * g + rloc < pl) {
           const long long A = oabs0 + ib;
-          float *const p = (A >= io.out_abs0 && A < io.out_end) ? oext + (A - io.out_abs0) * io.nch : oring + (A & io.out_ring_mask) * io.nch;
-          if (io.out_unaligned) { // (uniform) a caller's buffer that is only 4-byte aligned
-            p[0] = (float)accA;
-            p[1] = (float)accB;
+          E *const p = (A >= io.out_abs0 && A < io.out_end) ? oext + (A - io.out_abs0) * io.nch : oring + (A & io.out_ring_mask) * io.nch;
+          if (io.out_unaligned) { // (uniform) a caller's buffer that is only 4-byte (float64 frames: 8-byte) aligned
+            p[0] = (E)accA;
+            p[1] = (E)accB;
           } else
-            *reinterpret_cast<float2 *>(p) = make_float2((float)accA, (float)accB);
+            *reinterpret_cast<E2 *>(p) = E2{(E)accA, (E)accB};
         }
       } else if constexpr (OUT64) {
         // (the descriptor spans the ring, so the block's range test is explicit here; lanes that fail it get an offset
@@ -518,15 +528,21 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
           off = lane_dead_last ? 0xffffffffu : off;
           asm volatile("" : "+v"(off)); // (keeps it a branch: as selects it is two more vector instructions in every tile)
         }
+        if constexpr (sizeof(E) == 8) { // float64 frames: the pair as one 16-byte store
+          const rsmp_v4u d = {(unsigned)__double2loint(accA), (unsigned)__double2hiint(accA), (unsigned)__double2loint(accB),
+                              (unsigned)__double2hiint(accB)};
+          __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, (int)off, 0, 0);
+        } else {
         const rsmp_v2u d = {__float_as_uint((float)accA), __float_as_uint((float)accB)};
         if constexpr ((RSMP_EXP_SKIP & 8) != 0) { // no stores: only a result nobody produces would be written
           if (accA == 1.2345e300) __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
         } else
         __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
+        }
       }
 #else
       if (ib >= 0 && ib < cnt && 16 * g + rloc < pl)
-        *reinterpret_cast<float2 *>(obytes + (unsigned)(ib * frame_bytes)) = make_float2((float)accA, (float)accB);
+        *reinterpret_cast<E2 *>(obytes + (unsigned)(ib * frame_bytes)) = E2{(E)accA, (E)accB};
 #endif
       if (wrap != 0 && left > 1) { // uniform: the group switches
 #pragma unroll
@@ -620,18 +636,38 @@ __global__ __launch_bounds__(256, 2) void fused_split2_kernel(FusedArgs a, FastI
   fused_fast_body<12, KS, OMODE == 1, true, OMODE == 2, true>(a, io);
 }
 
+// the same three around the float64-frame body (FastIo::dio)
+template <int LOG2P, int KS, bool OUT64>
+__global__ __launch_bounds__(256, kFusedWaves) void fused_fast_dio_kernel(FusedArgs a, FastIo io)
+{
+  fused_fast_body<LOG2P, KS, OUT64, false, false, false, double>(a, io);
+}
+template <int KS, int OMODE>
+__global__ __launch_bounds__(256, 2) void fused_split_dio_kernel(FusedArgs a, FastIo io)
+{
+  fused_fast_body<12, KS, OMODE == 1, true, OMODE == 2, false, double>(a, io);
+}
+template <int KS, int OMODE>
+__global__ __launch_bounds__(256, 2) void fused_split2_dio_kernel(FusedArgs a, FastIo io)
+{
+  fused_fast_body<12, KS, OMODE == 1, true, OMODE == 2, true, double>(a, io);
+}
+
 template <int LOG2P, int KS, bool OUT64> static hipError_t launch_fast_t(const FusedArgs &a, const FastIo &io, hipStream_t st)
 {
   constexpr int N = 4096;
   size_t lds_bytes = 8 * size_t(fft_lds_doubles_halves(12));
   if (LOG2P < 12) lds_bytes = std::max(lds_bytes, 8 * size_t(std::max(fft_lds_doubles(LOG2P), fft8_lds_doubles(LOG2P))));
   lds_bytes = std::max(lds_bytes, size_t(kPad + kSA * (N / 16) + kPad) * 16);
-  static DynLdsOnce attr;
-  if (hipError_t e = attr.set(reinterpret_cast<const void *>(&fused_fast_kernel<LOG2P, KS, OUT64>), int(lds_bytes)); e != hipSuccess) return e;
+  static DynLdsOnce attr[2];
+  const void *fn = io.dio ? reinterpret_cast<const void *>(&fused_fast_dio_kernel<LOG2P, KS, OUT64>)
+                          : reinterpret_cast<const void *>(&fused_fast_kernel<LOG2P, KS, OUT64>);
+  if (hipError_t e = attr[io.dio ? 1 : 0].set(fn, int(lds_bytes)); e != hipSuccess) return e;
   FusedArgs b = a;
   b.d.hp = io.nch >= 4 ? io.nch / 2 : 0;
   dim3 grid(item_grid(a.d.nblocks, a.d.C / 2, b.d.hp)), block(N / 16);
-  hipLaunchKernelGGL((fused_fast_kernel<LOG2P, KS, OUT64>), grid, block, lds_bytes, st, b, io);
+  if (io.dio) hipLaunchKernelGGL((fused_fast_dio_kernel<LOG2P, KS, OUT64>), grid, block, lds_bytes, st, b, io);
+  else hipLaunchKernelGGL((fused_fast_kernel<LOG2P, KS, OUT64>), grid, block, lds_bytes, st, b, io);
   return hipGetLastError();
 }
 
@@ -641,13 +677,17 @@ template <int KS, int OMODE, bool TWO> static hipError_t launch_split_t(const Fu
   // transforms, whichever is larger: <= 80 KB, two per CU
   const size_t lds_max = std::max(size_t(8) * fft_lds_doubles_halves(12), size_t(kPad + (TWO ? kSplitRaEnd : kSplitVsMax) + kPad) * 16);
   const size_t lds_bytes = TWO ? lds_max : std::max(size_t(8) * fft_lds_doubles_halves(12), size_t(kPad + a.d.Vs + kPad) * 16);
-  static DynLdsOnce attr;
-  const void *fn = TWO ? reinterpret_cast<const void *>(&fused_split2_kernel<KS, OMODE>) : reinterpret_cast<const void *>(&fused_split_kernel<KS, OMODE>);
-  if (hipError_t e = attr.set(fn, int(lds_max)); e != hipSuccess) return e;
+  static DynLdsOnce attr[2];
+  const void *fn = io.dio ? (TWO ? reinterpret_cast<const void *>(&fused_split2_dio_kernel<KS, OMODE>) : reinterpret_cast<const void *>(&fused_split_dio_kernel<KS, OMODE>))
+                          : (TWO ? reinterpret_cast<const void *>(&fused_split2_kernel<KS, OMODE>) : reinterpret_cast<const void *>(&fused_split_kernel<KS, OMODE>));
+  if (hipError_t e = attr[io.dio ? 1 : 0].set(fn, int(lds_max)); e != hipSuccess) return e;
   FusedArgs b = a;
   b.d.hp = io.nch >= 4 ? io.nch / 2 : 0;
   dim3 grid(item_grid(a.d.nblocks, a.d.C / 2, b.d.hp)), block(256);
-  if (TWO) hipLaunchKernelGGL((fused_split2_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
+  if (io.dio) {
+    if (TWO) hipLaunchKernelGGL((fused_split2_dio_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
+    else hipLaunchKernelGGL((fused_split_dio_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
+  } else if (TWO) hipLaunchKernelGGL((fused_split2_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
   else hipLaunchKernelGGL((fused_split_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
   return hipGetLastError();
 }
@@ -682,11 +722,11 @@ hipError_t launch_fused_split(int omode, const FusedArgs &a, const FastIo &io, h
   }
 #define RSMP_SPLIT_CASE(ks, om)                                                        \
   if (a.KS == ks && omode == om && !a.d.two) {                                         \
-    if (kname) *kname = "rsmp::fused_split_kernel<" #ks ", " #om ">";                  \
+    if (kname) *kname = io.dio ? "rsmp::fused_split_dio_kernel<" #ks ", " #om ">" : "rsmp::fused_split_kernel<" #ks ", " #om ">"; \
     return launch_split_t<ks, om, false>(a, io, st);                                   \
   }                                                                                    \
   if (a.KS == ks && omode == om && a.d.two) {                                          \
-    if (kname) *kname = "rsmp::fused_split2_kernel<" #ks ", " #om ">";                 \
+    if (kname) *kname = io.dio ? "rsmp::fused_split2_dio_kernel<" #ks ", " #om ">" : "rsmp::fused_split2_kernel<" #ks ", " #om ">"; \
     return launch_split_t<ks, om, true>(a, io, st);                                    \
   }
   // (9 k-steps: 80 phases at step 147, the windows of a 4-residue block spread over 34 samples)
@@ -703,7 +743,8 @@ bool fused_fast_supported(int log2n, int log2p, int ksteps)
 
 #define RSMP_FAST_CASE(p, ks)                                                                        \
   if (log2p == p && a.KS == ks) {                                                                    \
-    if (kname) *kname = io.out64 ? "rsmp::fused_fast_kernel<" #p ", " #ks ", true>" : "rsmp::fused_fast_kernel<" #p ", " #ks ", false>"; \
+    if (kname) *kname = io.dio ? (io.out64 ? "rsmp::fused_fast_dio_kernel<" #p ", " #ks ", true>" : "rsmp::fused_fast_dio_kernel<" #p ", " #ks ", false>") \
+                               : (io.out64 ? "rsmp::fused_fast_kernel<" #p ", " #ks ", true>" : "rsmp::fused_fast_kernel<" #p ", " #ks ", false>"); \
     return io.out64 ? launch_fast_t<p, ks, true>(a, io, st) : launch_fast_t<p, ks, false>(a, io, st); \
   }
 

@@ -146,6 +146,12 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, (LOG2N == 13 && LOG2ND == 13) ? 
             const float2 f = sp.p2[q[s] * sp.fstride];
             v[s] = {(double)f.x, (double)f.y};
           }
+        } else if (sp.kind == 3) {
+#pragma unroll
+          for (int s = 0; s < 16; ++s) {
+            const double2 f = sp.d2[q[s] * sp.fstride];
+            v[s] = {f.x, f.y};
+          }
         } else {
 #pragma unroll
           for (int s = 0; s < 16; ++s) v[s] = {sp.pa[q[s]], sp.pb[q[s]]};
@@ -631,6 +637,9 @@ template <int NC> __global__ __launch_bounds__(256) void half_kernel(AnyView in,
     } else if (cs.kind == 2) {
 #pragma unroll
       for (int j = 0; j < 6; ++j) t[j] = cs.p64[min(ib + 256 * j, wlen - 1)];
+    } else if (cs.kind == 3) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) t[j] = cs.p64[min(ib + 256 * j, wlen - 1) * cs.stride32];
     } else {
 #pragma unroll
       for (int j = 0; j < 6; ++j) t[j] = ib + 256 * j < wlen ? fifo_get(src, w0 + ib + 256 * j) : 0.0;
@@ -726,7 +735,7 @@ bool dft_shape_supported(int log2n, int log2p, int log2nd)
   return log2nd == log2n && log2p >= log2n - 2;
 }
 
-hipError_t launch_dft(int log2n, int log2p, int log2nd, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd,
+hipError_t launch_dft(int log2n, int log2p, int log2nd, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
                       const F32View &df, const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname)
 {
   const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
@@ -737,7 +746,7 @@ hipError_t launch_dft(int log2n, int log2p, int log2nd, bool src_f32, bool dst_f
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_poly(int order, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_poly(int order, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                        const F64View &dd, const PolyArgs &a, hipStream_t st, const char **kname)
 {
   static const char *const names[2][4] = {{"rsmp::poly_kernel<0>", "rsmp::poly_kernel<1>", "rsmp::poly_kernel<2>", "rsmp::poly_kernel<3>"},
@@ -805,30 +814,32 @@ __global__ __launch_bounds__(256) void copy_frames_kernel(const float *src, long
   }
 }
 
-// base pointer of frames [a0, a1) of stream 0 when every stream holds them contiguously in one buffer of the view, else null
-static const float *frames_base(const F32View &v, long long a0, long long a1, long long &stream_stride)
+// base pointer of frames [a0, a1) of stream 0 when every stream holds them contiguously in one buffer of the view, else null;
+// `w` = 4-byte words per sample (2 for float64 frames: a copy moves bits, so those frames go as twice the floats)
+static const float *frames_base(const F32View &v, long long a0, long long a1, long long &stream_stride, int w = 1)
 {
   if (v.ext && a0 >= v.ext_begin && a1 <= v.ext_end) {
-    stream_stride = v.ext_stream_stride;
-    return v.ext + (a0 - v.ext_begin) * v.nch;
+    stream_stride = v.ext_stream_stride * w;
+    return v.ext + (a0 - v.ext_begin) * v.nch * w;
   }
   if ((!v.ext || a1 <= v.ext_begin || a0 >= v.ext_end) && a0 >= 0 && (a0 & v.ring_mask) + (a1 - a0) <= v.ring_mask + 1) {
-    stream_stride = v.ring_stream_stride;
-    return v.ring + (a0 & v.ring_mask) * v.nch;
+    stream_stride = v.ring_stream_stride * w;
+    return v.ring + (a0 & v.ring_mask) * v.nch * w;
   }
   return nullptr;
 }
 
-static hipError_t copy_range(bool f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
+static hipError_t copy_range(int f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
                              long long a1, int C, hipStream_t st, int depth)
 {
   if (a1 <= a0) return hipSuccess;
   if (f32 && depth < 3 && sf.nch == df.nch && sf.nch > 0 && C % sf.nch == 0) { // (at most 8 pieces, then element-wise)
     long long ss = 0, ds = 0;
-    const float *sp = frames_base(sf, a0, a1, ss);
-    float *dp = const_cast<float *>(frames_base(df, a0, a1, ds));
+    const int w = f32 == kFramesF64 ? 2 : 1;
+    const float *sp = frames_base(sf, a0, a1, ss, w);
+    float *dp = const_cast<float *>(frames_base(df, a0, a1, ds, w));
     if (sp && dp) {
-      const long long nfloats = (a1 - a0) * sf.nch;
+      const long long nfloats = (a1 - a0) * sf.nch * w;
       const int vec4 = ((reinterpret_cast<unsigned long long>(sp) | reinterpret_cast<unsigned long long>(dp) |
                          (unsigned long long)(ss * 4) | (unsigned long long)(ds * 4)) & 15) == 0;
       const long long blocks = std::min<long long>(std::max<long long>(1, (nfloats / (vec4 ? 4 : 1) + 255) / 256), 1024);
@@ -863,13 +874,13 @@ static hipError_t copy_range(bool f32, const F32View &sf, const F64View &sd, con
   return hipGetLastError();
 }
 
-hipError_t launch_copy(bool f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
+hipError_t launch_copy(int f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
                        long long a1, int C, hipStream_t st)
 {
   return copy_range(f32, sf, sd, df, dd, a0, a1, C, st, 0);
 }
 
-hipError_t launch_half(bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_half(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                        const F64View &dd, const HalfArgs &a, hipStream_t st, const char **kname)
 {
   static const char *const names[6] = {"rsmp::half_kernel<8>", "rsmp::half_kernel<9>", "rsmp::half_kernel<10>",

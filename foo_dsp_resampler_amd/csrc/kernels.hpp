@@ -34,6 +34,9 @@ struct DynLdsOnce {
 // A frame with absolute index a lives in the external buffer when ext != nullptr and
 // ext_begin <= a < ext_end, else in the ring.  This is what lets a device-resident push be
 // consumed in place and a device-resident pull be produced in place (no staging copy of bulk data).
+// With float64 frames (kFramesF64: a handle opened with RRX_FMT_DOUBLE) the same struct describes them: ring / ext then
+// address doubles and every stride counts doubles; the launchers' src_f32 / dst_f32 say which (0 = the fp64 rings).
+enum { kFramesF32 = 1, kFramesF64 = 2 };
 struct F32View {
   float *ring;
   long long ring_mask;          // frames - 1
@@ -117,7 +120,7 @@ struct BigDftArgs {
   int item0;             // first (block, pair) item of this launch (filled in by launch_dft_big)
 };
 bool big_dft_supported(int log2n, int log2p, int log2nd);
-hipError_t launch_dft_big(bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd,
+hipError_t launch_dft_big(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd,
                           BigDftArgs a, int ws_items, hipStream_t st);
 
 // per-block output bookkeeping of the fused launch, computed on the host (64-bit divisions stay there)
@@ -241,6 +244,9 @@ struct FastIo {
   // OUT64 instances (the polyphase stage feeds another stage): planar fp64 ring of the destination fifo instead of `out`
   double *out64;              // ring of channel 0
   long long out64_mask, out64_chan_stride; // items - 1, items between channels
+  // 1: the caller-facing frames hold float64 samples (*_dio_kernel instances): in / in_ring / out / out_ring then address
+  // doubles, every stride and frame offset above counts doubles, and in_unaligned / out_unaligned mean "not 16-byte aligned"
+  int dio;
 };
 bool fused_fast_supported(int log2n, int log2p, int ksteps);
 hipError_t launch_fused_fast(int log2p, const FusedArgs &a, const FastIo &io, hipStream_t st, const char **kname = nullptr);
@@ -278,21 +284,21 @@ struct HalfArgs {
 
 // All launchers return hipSuccess or the launch error; `kname` (optional) receives the name of the kernel instance
 // that was picked, as rocprofv3 prints it (static string).
-hipError_t launch_dft(int log2n, int log2p, int log2nd, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd,
+hipError_t launch_dft(int log2n, int log2p, int log2nd, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
                       const F32View &df, const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname = nullptr);
-hipError_t launch_poly(int order, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_poly(int order, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                        const F64View &dd, const PolyArgs &a, hipStream_t st, const char **kname = nullptr);
-hipError_t launch_half(bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_half(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                        const F64View &dd, const HalfArgs &a, hipStream_t st, const char **kname = nullptr);
 bool dft_shape_supported(int log2n, int log2p, int log2nd);
 // x4 upsampling on 8192-point blocks as four 2048-point component transforms (dftx.hip); needs DftArgs::Gr
 bool dftx_supported(int log2n, int log2p, int log2nd);
-hipError_t launch_dftx(int log2n, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_dftx(int log2n, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                        const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname = nullptr);
-hipError_t launch_fused(int log2n, int log2p, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd,
+hipError_t launch_fused(int log2n, int log2p, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
                         const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st, const char **kname = nullptr);
 // seam_kernel: the outputs whose window straddles two blocks; launch after launch_fused on the same stream
-hipError_t launch_seam(bool dst_f32, const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st);
+hipError_t launch_seam(int dst_f32, const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st);
 bool fused_shape_supported(int log2n, int log2p, int n, int span, int max_seam_outputs);
 bool fused_mfma_supported(int log2n, int log2p, int ksteps);
 hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st);
@@ -311,11 +317,11 @@ struct PolyMfArgs {
   unsigned pps_magic;    // as DftArgs::pps_magic
 };
 bool polymf_supported(int ksteps);
-hipError_t launch_polymf(int ksteps, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_polymf(int ksteps, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                          const F64View &dd, const PolyMfArgs &a, hipStream_t st, const char **kname = nullptr);
 // element-wise copy of absolute range [a0, a1) of every channel from one fifo view to another
 // (ring regrow, carrying the unconsumed tail of an in-place push into the ring, device pulls)
-hipError_t launch_copy(bool f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
+hipError_t launch_copy(int f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
                        long long a1, int C, hipStream_t st);
 
 } // namespace rsmp

@@ -46,6 +46,13 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
             x[j] = (double)f.x;
             y[j] = (double)f.y;
           }
+        } else if (sp.kind == 3) {
+#pragma unroll
+          for (int j = 0; j < 5; ++j) {
+            const double2 f = sp.d2[min(ib + 256 * j, W - 1) * sp.fstride];
+            x[j] = f.x;
+            y[j] = f.y;
+          }
         } else { // (pb == pa when the pair has one channel: every load is unconditional)
 #pragma unroll
           for (int j = 0; j < 5; ++j) {
@@ -81,24 +88,25 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
   const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
   const int irel_hi = fb.irel_lo + fb.cnt;
 
-  // float32 destination with both channels of the pair side by side in a frame: one 8-byte store per lane
+  // float32 (float64) destination with both channels of the pair side by side in a frame: one 8-byte (16-byte) store per lane
   bool ofast = false;
-  float *obase = nullptr;
+  char *obase = nullptr;
   int ofs = 2;
+  const int esz = out.is_f32 == kFramesF64 ? 8 : 4; // bytes per sample of the destination frames
   {
     const long long o0 = a.out_offset + fb.i_lo, o1 = o0 + fb.cnt;
     if (out.is_f32 && hasb && !(out.f.nch & 1)) {
       const int hp = out.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
       ofs = out.f.nch;
       if (out.f.ext && o0 >= out.f.ext_begin && o1 <= out.f.ext_end) {
-        obase = out.f.ext + strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin;
+        obase = reinterpret_cast<char *>(out.f.ext) + (strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin) * esz;
         ofast = true;
       } else if ((!out.f.ext || o0 >= out.f.ext_end || o1 <= out.f.ext_begin) &&
                  (o0 & out.f.ring_mask) + (o1 - o0) <= out.f.ring_mask + 1) {
-        obase = out.f.ring + strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin;
+        obase = reinterpret_cast<char *>(out.f.ring) + (strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin) * esz;
         ofast = true;
       }
-      ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & 7) == 0;
+      ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & (2 * esz - 1)) == 0;
     }
   }
 
@@ -106,10 +114,10 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
   // range per wave; coefficient tile double-buffered a group ahead, window start of a group from the host table, every
   // store issued straight after its tile under a per-lane range test, next tile's samples always prefetched.
   auto run = [&](auto fast_tag) {
-    constexpr bool FAST = decltype(fast_tag)::value;
+    constexpr bool FAST = decltype(fast_tag)::value != 0, DBL = decltype(fast_tag)::value == 2;
     const ChanRef oa = chan_ref(out, ca), ob = chan_ref(out, hasb ? cb : ca);
-    char *const obytes = reinterpret_cast<char *>(obase);
-    const int frame_bytes = ofs * 4;
+    char *const obytes = obase;
+    const int frame_bytes = ofs * (DBL ? 8 : 4);
     const int li_lo = -kPmPad, li_hi = W + kPmPad - 4 * KS;
     const int ncs = (fb.K + 3) >> 2, nt = a.NGRP * ncs;
     const int t0 = (nt * wave) >> 2, t1 = (nt * (wave + 1)) >> 2;
@@ -159,7 +167,9 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
       }
       const int ib = lane_ib + 16 * g + c * pl4;
       if (ib >= 0 && ib < cnt && 16 * g + rloc < pl) {
-        if (FAST) {
+        if (DBL) {
+          *reinterpret_cast<double2 *>(obytes + (unsigned)(ib * frame_bytes)) = make_double2(accA, accB);
+        } else if (FAST) {
           *reinterpret_cast<float2 *>(obytes + (unsigned)(ib * frame_bytes)) = make_float2((float)accA, (float)accB);
         } else {
           const long long oabs = a.out_offset + fb.i_lo + ib;
@@ -184,13 +194,14 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
       if (left == 0) break;
     }
   };
-  if (ofast) run(std::true_type{});
-  else run(std::false_type{});
+  if (ofast && esz == 8) run(std::integral_constant<int, 2>{});
+  else if (ofast) run(std::integral_constant<int, 1>{});
+  else run(std::integral_constant<int, 0>{});
 }
 
 bool polymf_supported(int ksteps) { return ksteps >= 7 && ksteps <= 9; }
 
-hipError_t launch_polymf(int ksteps, bool src_f32, bool dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
+hipError_t launch_polymf(int ksteps, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
                          const F64View &dd, const PolyMfArgs &a, hipStream_t st, const char **kname)
 {
   if (kname) *kname = ksteps == 7 ? "rsmp::polymf_kernel<7>" : ksteps == 8 ? "rsmp::polymf_kernel<8>" : "rsmp::polymf_kernel<9>";

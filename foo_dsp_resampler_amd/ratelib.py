@@ -13,9 +13,13 @@ RR_BEST, RR_NORM = 0, 1
 EXPECTED_SYMBOLS = [
     "init_ratelib", "close_ratelib", "RR_open", "RR_flow", "RR_push", "RR_pull", "RR_drain", "RR_close", "RR_strerror",
     "RRX_open_batch", "RRX_open_batch_on", "RRX_device", "RRX_push_device", "RRX_pull_device", "RRX_flow_device", "RRX_push_strided", "RRX_pull_strided",
-    "RRX_set_stream", "RRX_sync", "RRX_profile", "RRX_profile_read", "RRX_profile_report", "RRX_debug_fail_alloc", "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
+    "RRX_set_stream", "RRX_sync", "RRX_profile", "RRX_profile_read", "RRX_profile_report", "RRX_debug_fail_alloc",
+    "RRX_open_batch_fmt", "RRX_format", "RRX_push_double", "RRX_pull_double", "RRX_flow_double", "RRX_push_device_double",
+    "RRX_pull_device_double", "RRX_flow_device_double",
+    "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
+RRX_FMT_FLOAT, RRX_FMT_DOUBLE = 0, 1  # sample formats of a handle (ratelib_amd.h)
 
 
 class RRConfig(C.Structure):
@@ -91,6 +95,14 @@ def lib():
         L.RRX_open_batch.argtypes = [P(RRConfig), C.c_int, C.c_int, P(vp)]
         L.RRX_open_batch_on.argtypes = [P(RRConfig), C.c_int, C.c_int, C.c_int, P(vp)]
         L.RRX_device.argtypes = [vp]
+        L.RRX_open_batch_fmt.argtypes = [P(RRConfig), C.c_int, C.c_int, C.c_int, C.c_int, P(vp)]
+        L.RRX_format.argtypes = [vp]
+        L.RRX_push_double.argtypes = [vp, vp, sz, sz]
+        L.RRX_pull_double.argtypes = [vp, vp, sz, sz, P(sz)]
+        L.RRX_flow_double.argtypes = [vp, vp, sz, vp, sz, sz, sz, P(sz), P(sz)]
+        L.RRX_push_device_double.argtypes = [vp, vp, sz, sz]
+        L.RRX_pull_device_double.argtypes = [vp, vp, sz, sz, P(sz)]
+        L.RRX_flow_device_double.argtypes = [vp, vp, sz, vp, sz, sz, sz, P(sz), P(sz)]
         L.RR_push.argtypes = [vp, vp, sz]
         L.RR_pull.argtypes = [vp, vp, sz, P(sz)]
         L.RR_flow.argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
@@ -183,15 +195,24 @@ class Resampler:
 
     Host arrays are numpy float32 shaped [frames, nch] (one stream) or [streams, frames, nch].
     Device buffers are anything with `data_ptr()` (torch CUDA tensors) of the same shapes.
+    dtype=np.float64 opens a double-format handle (RRX_open_batch_fmt, RRX_FMT_DOUBLE): host arrays and device tensors are
+    then float64 and go through the RRX_*_double calls.  A buffer of the other precision is refused before any C call.
     """
 
-    def __init__(self, in_rate, out_rate, nch=2, nstreams=1, device=None, **kw):
+    def __init__(self, in_rate, out_rate, nch=2, nstreams=1, device=None, dtype=np.float32, **kw):
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("Resampler dtype must be float32 or float64, not %s" % dtype)
         _ensure_init()
         self.L = lib()
         self.nch, self.nstreams = nch, nstreams
+        self.dtype = dtype
         self.cfg = _config(in_rate, out_rate, **kw)
         self.h = C.c_void_p()
-        if device is not None:  # explicit HIP device index (RRX_open_batch_on)
+        if dtype == np.float64:
+            _check(self.L.RRX_open_batch_fmt(C.byref(self.cfg), nch, nstreams, -1 if device is None else int(device), RRX_FMT_DOUBLE,
+                                             C.byref(self.h)), "RRX_open_batch_fmt")
+        elif device is not None:  # explicit HIP device index (RRX_open_batch_on)
             _check(self.L.RRX_open_batch_on(C.byref(self.cfg), nch, nstreams, int(device), C.byref(self.h)), "RRX_open_batch_on")
         elif nstreams == 1:
             _check(self.L.RR_open(C.byref(self.cfg), nch, C.byref(self.h)), "RR_open")
@@ -208,6 +229,15 @@ class Resampler:
             self.close()
         except Exception:
             pass
+
+    @property
+    def double(self):
+        return self.dtype == np.float64
+
+    @property
+    def format(self):
+        """RRX_format of the handle (RRX_FMT_FLOAT / RRX_FMT_DOUBLE)."""
+        return self.L.RRX_format(self.h)
 
     @property
     def device(self):
@@ -251,7 +281,11 @@ class Resampler:
 
     # -- host API (RR_push / RR_pull / RR_flow / RR_drain)
     def _host_in(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float32)
+        if getattr(x, "dtype", None) == np.float64 and not self.double:
+            raise TypeError("float64 samples on a float32 handle: open the Resampler with dtype=np.float64")
+        if getattr(x, "dtype", None) == np.float32 and self.double:
+            raise TypeError("float32 samples on a float64 handle: pass float64 arrays (or open it with dtype=np.float32)")
+        x = np.ascontiguousarray(x, dtype=self.dtype)
         if self.nstreams == 1:
             x = x.reshape(-1, self.nch)
             return x, x.shape[0]
@@ -262,15 +296,20 @@ class Resampler:
         x, n = self._host_in(x)
         if n == 0:
             return
-        if self.nstreams == 1:
+        if self.double:
+            _check(self.L.RRX_push_double(self.h, x.ctypes.data, n, n), "RRX_push_double")
+        elif self.nstreams == 1:
             _check(self.L.RR_push(self.h, x.ctypes.data, n), "RR_push")
         else:
             _check(self.L.RRX_push_strided(self.h, x.ctypes.data, n, n), "RRX_push_strided")
 
     def pull(self, max_frames):
         shape = (max_frames, self.nch) if self.nstreams == 1 else (self.nstreams, max_frames, self.nch)
-        out = np.empty(shape, dtype=np.float32)
+        out = np.empty(shape, dtype=self.dtype)
         n = C.c_size_t(0)
+        if self.double:
+            _check(self.L.RRX_pull_double(self.h, out.ctypes.data, max_frames, max_frames, C.byref(n)), "RRX_pull_double")
+            return out[: n.value] if self.nstreams == 1 else out[:, : n.value]
         if self.nstreams == 1:
             _check(self.L.RR_pull(self.h, out.ctypes.data, max_frames, C.byref(n)), "RR_pull")
             return out[: n.value]
@@ -287,13 +326,17 @@ class Resampler:
             parts.append(p.copy())
         if parts:
             return np.concatenate(parts, axis=ax)
-        return np.empty((0, self.nch) if self.nstreams == 1 else (self.nstreams, 0, self.nch), np.float32)
+        return np.empty((0, self.nch) if self.nstreams == 1 else (self.nstreams, 0, self.nch), self.dtype)
 
     def flow(self, x, max_out):
         assert self.nstreams == 1
         x, n = self._host_in(x)
-        out = np.empty((max_out, self.nch), dtype=np.float32)
+        out = np.empty((max_out, self.nch), dtype=self.dtype)
         iu, og = C.c_size_t(0), C.c_size_t(0)
+        if self.double:
+            _check(self.L.RRX_flow_double(self.h, x.ctypes.data if n else None, n, out.ctypes.data, max_out, n, max_out,
+                                          C.byref(iu), C.byref(og)), "RRX_flow_double")
+            return iu.value, out[: og.value]
         _check(self.L.RR_flow(self.h, x.ctypes.data if n else None, out.ctypes.data, n, max_out, C.byref(iu), C.byref(og)),
                "RR_flow")
         return iu.value, out[: og.value]
@@ -315,17 +358,42 @@ class Resampler:
         return np.concatenate(parts, axis=ax)
 
     # -- device API (buffers expose data_ptr(); strides in frames)
+    def _dev_check(self, t):
+        """A tensor whose dtype names the other precision is refused (torch.float32 / torch.float64 vs the handle)."""
+        dt = str(getattr(t, "dtype", ""))
+        if dt.endswith("float64") and not self.double:
+            raise TypeError("torch.float64 buffer on a float32 handle: open the Resampler with dtype=np.float64")
+        if dt.endswith("float32") and self.double:
+            raise TypeError("torch.float32 buffer on a float64 handle: pass torch.float64 tensors")
+        return C.c_void_p(t.data_ptr())
+
     def push_device(self, t, frames, stride=None):
-        _check(self.L.RRX_push_device(self.h, C.c_void_p(t.data_ptr()), stride or frames, frames), "RRX_push_device")
+        p = self._dev_check(t)
+        if self.double:
+            _check(self.L.RRX_push_device_double(self.h, p, stride or frames, frames), "RRX_push_device_double")
+            return
+        _check(self.L.RRX_push_device(self.h, p, stride or frames, frames), "RRX_push_device")
 
     def pull_device(self, t, max_frames, stride=None):
         n = C.c_size_t(0)
-        _check(self.L.RRX_pull_device(self.h, C.c_void_p(t.data_ptr()), stride or max_frames, max_frames, C.byref(n)),
+        p = self._dev_check(t)
+        if self.double:
+            _check(self.L.RRX_pull_device_double(self.h, p, stride or max_frames, max_frames, C.byref(n)), "RRX_pull_device_double")
+            return n.value
+        _check(self.L.RRX_pull_device(self.h, p, stride or max_frames, max_frames, C.byref(n)),
                "RRX_pull_device")
         return n.value
 
     def flow_device(self, tin, in_frames, tout, out_cap, in_stride=None, out_stride=None):
         iu, og = C.c_size_t(0), C.c_size_t(0)
+        if tin is not None:
+            self._dev_check(tin)
+        self._dev_check(tout)
+        if self.double:
+            _check(self.L.RRX_flow_device_double(self.h, C.c_void_p(tin.data_ptr()) if tin is not None else None,
+                                                 in_stride or in_frames, C.c_void_p(tout.data_ptr()), out_stride or out_cap,
+                                                 in_frames, out_cap, C.byref(iu), C.byref(og)), "RRX_flow_device_double")
+            return iu.value, og.value
         _check(self.L.RRX_flow_device(self.h, C.c_void_p(tin.data_ptr()) if tin is not None else None,
                                       in_stride or in_frames, C.c_void_p(tout.data_ptr()), out_stride or out_cap,
                                       in_frames, out_cap, C.byref(iu), C.byref(og)), "RRX_flow_device")

@@ -81,6 +81,36 @@ int RRX_profile_report(RR_handle *h, char *buf, size_t cap);
  * longer describe the device fifos; the reference has no recovery path either, chain.h:26-29 tears the chain down). */
 void RRX_debug_fail_alloc(int nth);
 
+/* Sample formats.  A handle gets its format when it is opened and keeps it: every handle opened by the calls above is
+ * RRX_FMT_FLOAT (interleaved float32, fb_sample_t).  An RRX_FMT_DOUBLE handle takes and gives interleaved float64 frames
+ * at both ends; the chain in between is the same fp64 arithmetic, stage kernels and geometry as on a float handle of the
+ * same config, so its output rounded to float32 equals the float handle's bit for bit, and nothing is rounded to 24 bits
+ * on the way in or out.
+ * A data call whose format does not match the handle's -- RR_push / RR_pull / RR_flow, RRX_*_device and RRX_*_strided on a
+ * double handle, a *_double call on a float handle -- returns RR_INVPARAM and leaves the handle as it was (not poisoned,
+ * counters unchanged).  Format-free calls (RR_drain, RR_close, RRX_sync, RRX_set_stream, profiling, introspection) work on
+ * both kinds of handle. */
+#define RRX_FMT_FLOAT  0   /* interleaved float32: what every other data call uses */
+#define RRX_FMT_DOUBLE 1   /* interleaved float64 */
+/* RRX_open_batch / RRX_open_batch_on with a sample format: device = -1 is RRX_open_batch's placement (the current device,
+ * or round-robin under RATELIB_AMD_DEVICES), any other value is RRX_open_batch_on's.  An unknown format returns
+ * RR_INVPARAM before any device is touched. */
+int RRX_open_batch_fmt(const RR_config *config, int nchannels, int nstreams, int device, int format, RR_handle **const handle);
+int RRX_format(const RR_handle *h); /* RRX_FMT_*, or -1 for NULL */
+
+/* The double forms mirror RR_push / RR_pull / RR_flow (host memory, packed: the stride is ignored on one-stream handles
+ * exactly as RRX_push_strided / RRX_pull_strided use it on batches) and RRX_push_device / RRX_pull_device /
+ * RRX_flow_device (HBM pointers, the stream-ordering contract above) word for word: units are frames, isamp is clamped
+ * to RRX_isamp_max, availability and drain totals are the float ones.  A float64 pointer need only be 8-byte aligned. */
+int RRX_push_double(RR_handle *h, const double *ibuf, size_t in_stride, size_t isamp);                   /* RRX_push_strided */
+int RRX_pull_double(RR_handle *h, double *obuf, size_t out_stride, size_t osamp, size_t *ogen);         /* RRX_pull_strided */
+int RRX_flow_double(RR_handle *h, const double *ibuf, size_t in_stride, double *obuf, size_t out_stride, /* RR_flow, strided */
+                    size_t isamp, size_t osamp, size_t *iused, size_t *ogen);
+int RRX_push_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, size_t isamp);          /* RRX_push_device */
+int RRX_pull_device_double(RR_handle *h, double *d_obuf, size_t out_stride, size_t osamp, size_t *ogen); /* RRX_pull_device */
+int RRX_flow_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, double *d_obuf,        /* RRX_flow_device */
+                           size_t out_stride, size_t isamp, size_t osamp, size_t *iused, size_t *ogen);
+
 /* Introspection: isamp_max of rate_base.h:531, frames currently pullable (fifo_occupancy of the last
  * fifo, rate_base.h:447-448), shape of the handle. */
 size_t RRX_isamp_max(const RR_handle *h);
