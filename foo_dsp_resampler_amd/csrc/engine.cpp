@@ -51,7 +51,6 @@ const Knobs &knobs()
     r.no_polycoop = on("RSMP_NO_POLYCOOP");
     r.spread_vector = on("RSMP_SPREAD_VECTOR");
     r.no_side = on("RSMP_NO_SIDE");
-    r.no_graph = on("RSMP_NO_GRAPH");
     r.stamps = on("RSMP_STAMPS");
     r.occ = on("RSMP_OCC");
     r.test_hooks = on("RSMP_TEST_HOOKS");
@@ -136,10 +135,12 @@ int Engine::dev_alloc(void **p, size_t bytes)
     if (rc_ != kOk) return rc_;                                           \
   } while (0)
 
-int Engine::upload(const void *src, size_t bytes, void **dst)
+template <class T> int Engine::upload(const std::vector<T> &src, T **dst)
 {
-  ALLOC_TRY(dst, bytes);
-  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  void *d = nullptr;
+  ALLOC_TRY(&d, src.size() * sizeof(T));
+  HIP_TRY(hipMemcpy(d, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  *dst = static_cast<T *>(d);
   return kOk;
 }
 
@@ -156,10 +157,7 @@ const double2 *Engine::twiddles(int log2m)
         tab.push_back(make_double2((double)cosl(th), (double)sinl(th)));
       }
   if (tab.empty()) tab.push_back(make_double2(1, 0));
-  void *d = nullptr;
-  if (upload(tab.data(), tab.size() * sizeof(double2), &d) != kOk) return nullptr;
-  d_tw_[log2m] = static_cast<double2 *>(d);
-  return d_tw_[log2m];
+  return upload(tab, &d_tw_[log2m]) == kOk ? d_tw_[log2m] : nullptr;
 }
 
 const double2 *Engine::twiddles8(int log2m)
@@ -178,11 +176,104 @@ const double2 *Engine::twiddles8(int log2m)
       }
   }
   if (tab.empty()) tab.push_back(make_double2(1, 0));
-  void *d = nullptr;
-  if (upload(tab.data(), tab.size() * sizeof(double2), &d) != kOk) return nullptr;
-  d_tw8_[log2m] = static_cast<double2 *>(d);
-  return d_tw8_[log2m];
+  return upload(tab, &d_tw8_[log2m]) == kOk ? d_tw8_[log2m] : nullptr;
 }
+
+namespace {
+
+// Window geometry of the 4-residue blocks of a rational order-0 polyphase stage on the matrix pipe: KS k-steps of 4 taps cover
+// the common window of every block, NGRP groups of 16 residues, and the window starts of the blocks span [qb_min, qb_max].
+// It decides which kernel a chain runs (split_geometry, the fused and polymf setups): computed here only.
+struct MfGeom { int KS, NGRP, qb_min, qb_max; };
+
+MfGeom mf_geom(const StageSpec &p)
+{
+  const int pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32);
+  int d4 = 0, qb_min = at0 / p.L, qb_max = qb_min;
+  for (int rb = 0; rb < p.L; rb += 4) {
+    const long long a0 = at0 + (long long)rb * pstep, a1 = at0 + (long long)std::min(rb + 3, p.L - 1) * pstep;
+    d4 = std::max(d4, int(a1 / p.L - a0 / p.L));
+    qb_max = std::max(qb_max, int(a0 / p.L));
+  }
+  return MfGeom{std::max(7, (p.n + d4 + 3) / 4), (p.L + 15) / 16, qb_min, qb_max};
+}
+
+// A operands of v_mfma_f64_4x4x4 (fused.hip, polymf.hip): lane = 16k + 4b + i of cfm holds the coefficient of residue
+// 16g + 4b + i at tap 4s + k of its 4-residue block's common window, which starts at period qtab[4g + b].  cfm2 holds the same
+// tiles two k-steps per 16-byte element (half the load instructions in the lean kernel).
+struct MfOperands { std::vector<double> cfm; std::vector<int> qtab; std::vector<double2> cfm2; };
+
+MfOperands mf_operands(const MfGeom &mg, const StageSpec &p, const std::vector<double> &poly_table)
+{
+  const int pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32), KS = mg.KS, KSP = (KS + 1) / 2;
+  MfOperands op;
+  op.qtab.resize(size_t(mg.NGRP) * 4);
+  for (int g = 0; g < mg.NGRP; ++g)
+    for (int bq = 0; bq < 4; ++bq) {
+      int rb = 16 * g + 4 * bq;
+      if (rb >= p.L) rb = 0; // idle block: all-zero coefficients, any in-range window will do
+      op.qtab[size_t(g) * 4 + bq] = (at0 + rb * pstep) / p.L;
+    }
+  op.cfm.assign(size_t(mg.NGRP) * KS * 64, 0.0);
+  op.cfm2.assign(size_t(mg.NGRP) * KSP * 64, make_double2(0.0, 0.0));
+  for (int g = 0; g < mg.NGRP; ++g)
+    for (int s = 0; s < KS; ++s)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int k = lane >> 4, bq = (lane >> 2) & 3, r = 16 * g + 4 * bq + (lane & 3);
+        const int qb = op.qtab[size_t(g) * 4 + bq];
+        if ((KS & 1) && s == KS - 1) // the spare half of the last element carries the lane's window start
+          op.cfm2[(size_t(g) * KSP + KSP - 1) * 64 + lane].y = double(qb);
+        if (r >= p.L) continue;
+        const int ar = at0 + r * pstep, q = ar / p.L, ph = ar - q * p.L;
+        const int j = 4 * s + k - (q - qb);
+        if (j < 0 || j >= p.n) continue;
+        const double c = poly_table[size_t(ph) * p.n + j];
+        op.cfm[(size_t(g) * KS + s) * 64 + lane] = c;
+        double2 &c2 = op.cfm2[(size_t(g) * KSP + s / 2) * 64 + lane];
+        (s & 1 ? c2.y : c2.x) = c;
+      }
+  return op;
+}
+
+// Coefficient tiles of the vector variant of fused_kernel, one per thread: tile[mm][g] = row(phase of residue G*m+g)[mm - d_g]
+std::vector<double> vector_tiles(const StageSpec &p, int G, int NG, int KC, int threads, const std::vector<double> &poly_table)
+{
+  const int pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32);
+  std::vector<double> tiles(size_t(32) * G * threads, 0.0);
+  for (int t = 0; t < threads; ++t) {
+    const int m = t % NG, kc = t / NG;
+    if (kc >= KC) continue;
+    const int q0 = (at0 + G * m * pstep) / p.L;
+    for (int g = 0; g < G; ++g) {
+      const int r = G * m + g;
+      if (r >= p.L) continue;
+      const int ar = at0 + r * pstep, q = ar / p.L, ph = ar - q * p.L, dsh = q - q0;
+      for (int j = 0; j < p.n; ++j)
+        if (j + dsh < 32) tiles[(size_t(j + dsh) * G + g) * threads + t] = poly_table[size_t(ph) * p.n + j];
+    }
+  }
+  return tiles;
+}
+
+// G_r = DFT_{N/L}(gain * h placed at (i + N - taps + 1) mod N, points L j + r) / (N / L), r < L: the spectra of the L polyphase
+// components of an N-point block (L = 1: the whole block, rate_base.h:173-175)
+std::vector<double2> component_spectra(const DftFilter &f, int N, int L, int gain)
+{
+  const int P = N / L;
+  std::vector<double2> G(size_t(L) * P);
+  for (int r = 0; r < L; ++r) {
+    std::vector<cplx> g(P);
+    for (int i = 0; i < f.num_taps; ++i) {
+      const int m = (i + N - f.num_taps + 1) & (N - 1);
+      if (m % L == r) g[m / L] = f.taps[i] * gain;
+    }
+    fft_inplace(g, -1);
+    for (int k = 0; k < P; ++k) G[size_t(r) * P + k] = make_double2(g[k].real() / P, g[k].imag() / P);
+  }
+  return G;
+}
+
+} // namespace
 
 // Can dft stage i and the rational polyphase stage behind it run as the sub-blocked fused kernel (fused_split_kernel)?  If
 // so: sub-blocks per block and valid samples per sub-block.  The kernel has no generic form behind it, so everything it
@@ -200,19 +291,12 @@ bool split_geometry(const ChainPlan &plan_, int nch_, int i, int &nsub, int &vs)
   if (d.kind != StageKind::Dft || p.kind != StageKind::Poly || p.order != 0 || d.step != 1 || d.L != 2 || d.remL0 != 0) return false;
   const DftFilter &f = plan_.dft[d.filt];
   const int log2n = ilog2(f.N), V = f.N - (f.num_taps - 1), Pref = f.N / 2;
-  const int pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32);
-  int d4 = 0;
-  for (int rb = 0; rb < p.L; rb += 4) {
-    const long long a0 = at0 + (long long)rb * pstep, a1 = at0 + (long long)std::min(rb + 3, p.L - 1) * pstep;
-    d4 = std::max(d4, int(a1 / p.L - a0 / p.L));
-  }
-  const int KS = std::max(7, (p.n + d4 + 3) / 4);
+  const int pstep = int(p.step64 >> 32);
+  const MfGeom mg = mf_geom(p);
   const int max_seam = int(((long long)(p.n - 1) * p.L + pstep - 1) / pstep) + 1;
-  if ((V & 1) || p.L < 64 || p.n > 32 || max_seam > 64 || !fused_split_supported(log2n, d.L, KS)) return false;
+  if ((V & 1) || p.L < 64 || p.n > 32 || max_seam > 64 || !fused_split_supported(log2n, d.L, mg.KS)) return false;
   if (Pref == 4096) { // 8192-point blocks: the whole block from ONE pair of component transforms, polyphase stage in two rounds
-    int qb_min = at0 / p.L, qb_max = qb_min;
-    for (int rb = 0; rb < p.L; rb += 4) qb_max = std::max(qb_max, int((at0 + (long long)rb * pstep) / p.L));
-    if (fused_split_two_supported(V, f.num_taps, KS, qb_max - qb_min) && V >= 2 * p.n) {
+    if (fused_split_two_supported(V, f.num_taps, mg.KS, mg.qb_max - mg.qb_min) && V >= 2 * p.n) {
       nsub = 1;
       vs = V;
       return true;
@@ -241,14 +325,7 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
   C_ = nch * nstreams;
 
   if (!device_is_gfx950(device_)) return kUninit; // the code object is built for gfx950 only: refuse here, not at the first launch
-  HIP_TRY(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
-  stream_ = own_;
-  HIP_TRY(hipEventCreateWithFlags(&ev_switch_, hipEventDisableTiming));
-  HIP_TRY(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&ev_fused_, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&ev_seam_[0], hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&ev_seam_[1], hipEventDisableTiming));
-
+  if ((rc = init_streams()) != kOk) return rc;
   const Knobs &kn = knobs(); // the environment was read once per process; nothing below or on the launch path calls getenv
   dbg_ = kn.dbg;
   no_side_ = kn.no_side;
@@ -262,325 +339,217 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
   book_.st.assign(ns, Book::St());
   rings_.assign(ns + 1, Ring());
   big_.assign(ns, BigDft());
+  fuse_.assign(ns, Fuse());
+  polymf_.assign(ns, PolyMf());
   for (int i = 0; i <= ns; ++i) rings_[i].f32 = (i == 0 || i == ns);
-
-  double bytes_per_in_frame = 0, rate = 1;
   for (int i = 0; i < ns; ++i) {
     const StageSpec &sp = plan_.stages[i];
     book_.wr[i] = sp.preload; // rate_base.h:417-422
-    Book::St &st = book_.st[i];
     if (sp.kind == StageKind::Dft) {
-      const DftFilter &f = plan_.dft[sp.filt];
-      const int Ng = f.N;
-      const int log2n = ilog2(Ng);
-      const int log2p = fdomain_up(sp.L) ? log2n - ilog2(sp.L) : log2n;
-      const int log2nd = sp.step < 0 ? log2n + sp.step : log2n;
-      int sub_n = 0, sub_v = 0;
-      const bool sub = split_geometry(i, sub_n, sub_v); // runs as fused_split_kernel: no transform of the block's own length
-      const bool big = log2n > 14 && !sub; // the reference's long blocks: four-step transform (dftbig.hip)
-      if (!sub && (big ? !big_dft_supported(log2n, log2p, log2nd) : !dft_shape_supported(log2n, log2p, log2nd))) return kInvParam;
-      st.remL = sp.remL0;
-      if (!d_G_[sp.filt]) { // G = DFT_N(L * h placed at (i + N - taps + 1) mod N) / N, rate_base.h:173-175
-        std::vector<cplx> g(Ng);
-        for (int i2 = 0; i2 < f.num_taps; ++i2) g[(i2 + Ng - f.num_taps + 1) & (Ng - 1)] = f.taps[i2] * sp.L;
-        fft_inplace(g, -1);
-        std::vector<double2> G(Ng);
-        for (int k = 0; k < Ng; ++k) G[k] = make_double2(g[k].real() / Ng, g[k].imag() / Ng);
-        void *d = nullptr;
-        if ((rc = upload(G.data(), G.size() * sizeof(double2), &d)) != kOk) return rc;
-        d_G_[sp.filt] = static_cast<double2 *>(d);
-      }
-      if (!big && !d_Gr_[sp.filt] && sp.step == 1 && fdomain_up(sp.L) && dftx_supported(log2n, log2p, log2nd)) {
-        // G_r = DFT_P(L * h_placed[L j + r]) / P, r < L: the block's L polyphase components (dftx.hip)
-        const int Lx = sp.L, Px = Ng / Lx;
-        std::vector<double2> Gr(size_t(Lx) * Px);
-        for (int r = 0; r < Lx; ++r) {
-          std::vector<cplx> g(Px);
-          for (int i2 = 0; i2 < f.num_taps; ++i2) {
-            const int m = (i2 + Ng - f.num_taps + 1) & (Ng - 1);
-            if (m % Lx == r) g[m / Lx] = f.taps[i2] * sp.L;
-          }
-          fft_inplace(g, -1);
-          for (int k = 0; k < Px; ++k) Gr[size_t(r) * Px + k] = make_double2(g[k].real() / Px, g[k].imag() / Px);
-        }
-        void *d = nullptr;
-        if ((rc = upload(Gr.data(), Gr.size() * sizeof(double2), &d)) != kOk) return rc;
-        d_Gr_[sp.filt] = static_cast<double2 *>(d);
-      }
-      if (big) {
-        BigDft &bg = big_[i];
-        bg.on = true;
-        if (!twiddles(log2p - 4) || !twiddles(log2nd - 4)) return kNoMem;
-        std::vector<double2> tw(Ng);
-        for (int j = 0; j < Ng; ++j) {
-          const long double th = 2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)Ng;
-          tw[j] = make_double2((double)cosl(th), (double)sinl(th));
-        }
-        void *d = nullptr;
-        if ((rc = upload(tw.data(), tw.size() * sizeof(double2), &d)) != kOk) return rc;
-        bg.twN = static_cast<double2 *>(d);
-        // (block, pair) items in flight per round of the three launches: at most 256 MB per workspace
-        const int npairs = pair_count(C_, pair_nchs());
-        bg.ws_items = int(std::max<long long>(1, std::min<long long>((256LL << 20) / (16LL * Ng), std::max(4 * npairs, 16))));
-        ALLOC_TRY(&bg.w1, size_t(bg.ws_items) * (size_t(1) << log2p) * sizeof(double2));
-        ALLOC_TRY(&bg.w2, size_t(bg.ws_items) * (size_t(1) << log2nd) * sizeof(double2));
-      } else if (!sub && (!twiddles(log2p) || !twiddles(log2nd))) return kNoMem;
-      double r = double(sp.L);
-      if (sp.step > 0) r /= sp.step; else r /= double(1 << -sp.step);
-      rate *= r;
+      book_.st[i].remL = sp.remL0;
+      if ((rc = init_dft_stage(i)) != kOk) return rc;
     } else if (sp.kind == StageKind::Poly) {
-      st.at = sp.order == 0 ? (sp.at0 >> 32) : sp.at0;
-      if (!d_poly_) {
-        void *d = nullptr;
-        if ((rc = upload(plan_.poly_table.data(), plan_.poly_table.size() * sizeof(double), &d)) != kOk) return rc;
-        d_poly_ = static_cast<double *>(d);
-      }
-      rate *= sp.out_in_ratio;
-    } else {
-      rate *= 0.5;
+      book_.st[i].at = sp.order == 0 ? (sp.at0 >> 32) : sp.at0;
+      if (!d_poly_ && (rc = upload(plan_.poly_table, &d_poly_)) != kOk) return rc;
     }
-    if (i + 1 < ns) bytes_per_in_frame += rate * 8.0 * C_;
   }
-  // dft(step 1, L = 1,2,4) directly followed by a rational polyphase stage runs as ONE kernel (fused.hip)
-  fuse_.assign(ns, Fuse());
   size_t fused_slab_cap = 0;
-  for (int i = 0; i + 1 < ns; ++i) {
-    const StageSpec &d = plan_.stages[i], &p = plan_.stages[i + 1];
-    if (d.kind != StageKind::Dft || p.kind != StageKind::Poly || p.order != 0 || d.step != 1) continue;
-    if (!(d.L == 1 || (pow2_ge2(d.L) && d.L <= 4))) continue;
-    const DftFilter &f = plan_.dft[d.filt];
-    const int log2n = ilog2(f.N), log2p = log2n - (d.L == 1 ? 0 : ilog2(d.L));
-    const int G = 2, pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32);
-    int dmax = 0;
-    const int NG = (p.L + G - 1) / G;
-    for (int m = 0; m < NG; ++m) {
-      const long long a0 = at0 + (long long)(G * m) * pstep, a1 = at0 + (long long)std::min(G * m + G - 1, p.L - 1) * pstep;
-      dmax = std::max(dmax, int(a1 / p.L - a0 / p.L));
-    }
-    const int max_seam = int(((long long)(p.n - 1) * p.L + pstep - 1) / pstep) + 1;
-    // Blocks too long for one workgroup (8192 / 16384 points): the sub-blocked form of the lean kernel, for the chains it
-    // covers -- x2 stage first in the chain (float frames in), even channel count, matrix-pipe tiles; the polyphase stage
-    // either last (float frames out) or feeding a further stage (fp64 ring out).  There is no generic kernel behind it, so
-    // everything is decided here.
-    int split_nsub = 0, split_vs = 0;
-    split_geometry(i, split_nsub, split_vs);
-    const bool split = split_nsub > 0;
-    const int threads = split ? 256 : f.N / 16;
-    if (!split && (NG > threads || !fused_shape_supported(log2n, log2p, p.n, p.n + dmax, max_seam))) continue;
-    if (kn.no_fuse) continue;
-    Fuse &fu = fuse_[i];
-    fu.on = true;
-    fu.nsub = split_nsub;
-    fu.Vs = split_vs;
-    if (split) { // G_r = DFT_4096(L * h_placed[2 j + r]) / 4096 with h placed at -(taps - 1) .. 0 mod 8192: the block's two components
-      if (!twiddles(12)) return kNoMem;
-      std::vector<double2> Gs(size_t(2) * 4096);
-      for (int r = 0; r < 2; ++r) {
-        std::vector<cplx> g(4096);
-        for (int i2 = 0; i2 < f.num_taps; ++i2) {
-          const int m = (i2 + 8192 - f.num_taps + 1) & 8191;
-          if ((m & 1) == r) g[m >> 1] = f.taps[i2] * d.L;
-        }
-        fft_inplace(g, -1);
-        for (int k = 0; k < 4096; ++k) Gs[size_t(r) * 4096 + k] = make_double2(g[k].real() / 4096, g[k].imag() / 4096);
-      }
-      void *dg = nullptr;
-      if ((rc = upload(Gs.data(), Gs.size() * sizeof(double2), &dg)) != kOk) return rc;
-      fu.Gs = static_cast<double2 *>(dg);
-    }
-    fu.span = p.n + dmax;
-    fu.NG = NG;
-    fu.KC = split ? 1 : threads / NG; // (vector variant's thread map: unused by the sub-blocked form, whose NG may exceed 256)
-    // blocks per launch: as many as a seam ring of at most 1280 MB allows (0.4 % of the card; round 2's 320 MB cut a 963 379-frame
-    // push of 256 stereo streams into three launches, each with its own prep / seam kernels and gaps; two launches worth of slots: seam(k) still
-    // reads its slots while fused(k+1) fills the next ones)
-    fu.blk_cap = 64;
-    while (fu.blk_cap < kFusedMaxBlocks && double(C_ + 1) * double(4 * fu.blk_cap) * 512 <= kn.seam_ring_mb * 1048576.0) fu.blk_cap *= 2;
-    while (fu.blk_cap < 8 * split_nsub) fu.blk_cap *= 2; // (sub-blocked: the table counts sub-blocks; at least 6 whole blocks per launch)
-    fu.slots = 2 * fu.blk_cap;
-    ALLOC_TRY(&fu.blk_dev, size_t(2 * fu.blk_cap) * sizeof(FusedBlock)); // two halves: launch k uses half k & 1 (see advance)
-    const size_t bytes = size_t(C_ + 1) * fu.slots * 2 * 32 * sizeof(double);
-    ALLOC_TRY(&fu.seam, bytes);
-    HIP_TRY(hipMemset(fu.seam, 0, bytes));
-    const int V = f.N - (f.num_taps - 1);
-    // periods a block can touch: ceil(outputs per block / L) + 1; chunk length fixed from it
-    const int Kmax = int(((long long)V * p.L / pstep + p.L - 1) / p.L) + 2;
-    fu.kper = (Kmax + fu.KC - 1) / fu.KC;
-    if (!split) { // coefficient tiles, one per thread of the fused kernel: tile[mm][g] = row(phase of residue G*m+g)[mm - d_g]
-      std::vector<double> tiles(size_t(32) * G * threads, 0.0);
-      for (int t = 0; t < threads; ++t) {
-        const int m = t % NG, kc = t / NG;
-        if (kc >= fu.KC) continue;
-        const int q0 = (at0 + G * m * pstep) / p.L;
-        for (int g = 0; g < G; ++g) {
-          const int r = G * m + g;
-          if (r >= p.L) continue;
-          const int ar = at0 + r * pstep, q = ar / p.L, ph = ar - q * p.L, dsh = q - q0;
-          for (int j = 0; j < p.n; ++j)
-            if (j + dsh < 32) tiles[(size_t(j + dsh) * G + g) * threads + t] = plan_.poly_table[size_t(ph) * p.n + j];
-        }
-      }
-      void *d = nullptr;
-      if ((rc = upload(tiles.data(), tiles.size() * sizeof(double), &d)) != kOk) return rc;
-      fu.cft = static_cast<double *>(d);
-    }
-    { // matrix-pipe variant (fused.hip): A operands of v_mfma_f64_4x4x4, lane = 16k + 4b + i holds the
-      // coefficient of residue 16g + 4b + i at tap 4s + k of its 4-residue block's common window
-      int d4 = 0;
-      for (int rb = 0; rb < p.L; rb += 4) {
-        const long long a0 = at0 + (long long)rb * pstep, a1 = at0 + (long long)std::min(rb + 3, p.L - 1) * pstep;
-        d4 = std::max(d4, int(a1 / p.L - a0 / p.L));
-      }
-      const int KS = std::max(7, (p.n + d4 + 3) / 4), NGRP = (p.L + 15) / 16;
-      // window starts of the 4-residue blocks span [qb_min, qb_max]; the two-round sample image of the kernel
-      // needs every period to fit one of the rounds (fused.hip, kSA / kSB0)
-      int qb_min = at0 / p.L, qb_max = qb_min;
-      for (int rb = 0; rb < p.L; rb += 4) qb_max = std::max(qb_max, int((at0 + (long long)rb * pstep) / p.L));
-      // ... and at most 32 periods per block (4 column steps per item), enough phases to fill 16-row tiles
-      // (The four periods of a tile -- lanes j = 0..3 of a B read, `step` samples apart -- fall on the same LDS banks when
-      // step is a multiple of 8 samples: 96k->44.1k (step 320), 48k->44.1k (160).  Such chains used to be kept on the vector
-      // variant (3.90 against 3.74 ms at the time); with the lean kernel's later gains the matrix-pipe variant wins despite
-      // its 4-way conflicts: 96k->44.1k 3.26 against 3.74 ms, 48k->44.1k +25 %.  RSMP_SPREAD_VECTOR=1 restores the old choice.)
-      bool lanes_spread = true;
-      if (kn.spread_vector)
-        for (int j1 = 0; j1 < 4; ++j1)
-          for (int j2 = j1 + 1; j2 < 4; ++j2)
-            if (((j2 - j1) * pstep) % 16 == 0) lanes_spread = false;
-      const bool rounds_ok = (qb_max - qb_min) + 4 * KS + 4 <= (kFusedSA - kFusedSB0) * 256 + 32 && Kmax <= 32 && p.L >= 64 && lanes_spread;
-      if (split || (!kn.no_mfma && fused_mfma_supported(log2n, log2p, KS) && rounds_ok)) { // (split: one image, no rounds to fit)
-        std::vector<double> am(size_t(NGRP) * KS * 64, 0.0);
-        for (int g = 0; g < NGRP; ++g)
-          for (int s = 0; s < KS; ++s)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int k = lane >> 4, bq = (lane >> 2) & 3, ii = lane & 3;
-              const int rb = 16 * g + 4 * bq, r = rb + ii;
-              if (r >= p.L) continue;
-              const int qb = (at0 + rb * pstep) / p.L;
-              const int ar = at0 + r * pstep, q = ar / p.L, ph = ar - q * p.L;
-              const int j = 4 * s + k - (q - qb);
-              if (j >= 0 && j < p.n) am[(size_t(g) * KS + s) * 64 + lane] = plan_.poly_table[size_t(ph) * p.n + j];
-            }
-        void *dm = nullptr;
-        if ((rc = upload(am.data(), am.size() * sizeof(double), &dm)) != kOk) return rc;
-        fu.cfm = static_cast<double *>(dm);
-        { // the same tiles, two k-steps per 16-byte element (half the load instructions in the lean kernel)
-          const int KSP = (KS + 1) / 2;
-          std::vector<double2> am2(size_t(NGRP) * KSP * 64, make_double2(0.0, 0.0));
-          for (int g = 0; g < NGRP; ++g)
-            for (int s = 0; s < KS; ++s)
-              for (int lane = 0; lane < 64; ++lane) {
-                double2 &d = am2[(size_t(g) * KSP + s / 2) * 64 + lane];
-                (s & 1 ? d.y : d.x) = am[(size_t(g) * KS + s) * 64 + lane];
-              }
-          if (KS & 1) // the spare half of the last element carries the lane's window start (as qtab: block bq = (lane >> 2) & 3)
-            for (int g = 0; g < NGRP; ++g)
-              for (int lane = 0; lane < 64; ++lane) {
-                int rb = 16 * g + 4 * ((lane >> 2) & 3);
-                if (rb >= p.L) rb = 0;
-                am2[(size_t(g) * KSP + KSP - 1) * 64 + lane].y = double((at0 + rb * pstep) / p.L);
-              }
-          void *d2 = nullptr;
-          if ((rc = upload(am2.data(), am2.size() * sizeof(double2), &d2)) != kOk) return rc;
-          fu.cfm2 = static_cast<double2 *>(d2);
-        }
-        fu.NGRP = NGRP;
-        fu.KS = KS;
-        fu.qb_max = qb_max;
-        fu.qb_min = qb_min;
-        std::vector<int> qt(size_t(NGRP) * 4);
-        for (int g = 0; g < NGRP; ++g)
-          for (int bq = 0; bq < 4; ++bq) {
-            int rb = 16 * g + 4 * bq;
-            if (rb >= p.L) rb = 0; // idle block: all-zero coefficients, any in-range window will do
-            qt[size_t(g) * 4 + bq] = (at0 + rb * pstep) / p.L;
-          }
-        void *dq = nullptr;
-        if ((rc = upload(qt.data(), qt.size() * sizeof(int), &dq)) != kOk) return rc;
-        fu.qtab = static_cast<int *>(dq);
-      }
-    }
-    const size_t per_launch = size_t(fu.blk_cap / std::max(1, fu.nsub) - 2) * size_t((V - d.remL0 + d.L - 1) / d.L);
-    // frames of chain input per launch: divide by the rate of everything ahead of the dft stage
-    double ahead = 1;
-    for (int k = 0; k < i; ++k) ahead *= plan_.stages[k].kind == StageKind::Half ? 0.5 : plan_.stages[k].out_in_ratio;
-    const size_t cap = size_t(double(per_launch) / std::max(ahead, 1e-9));
-    fused_slab_cap = fused_slab_cap ? std::min(fused_slab_cap, cap) : cap;
+  for (int i = 0; i + 1 < ns; ++i)
+    if ((rc = init_fused_pair(i, fused_slab_cap)) != kOk) return rc;
+  for (int i = 0; i < ns; ++i)
+    if ((rc = init_polymf(i)) != kOk) return rc;
+  size_slabs(fused_slab_cap);
+  for (int i = 0; i <= ns; ++i)
+    if ((rc = ensure_ring(i, std::max<long long>(book_.wr[i], 1))) != kOk) return rc;
+  HIP_TRY(hipStreamSynchronize(stream_));
+  return kOk;
+}
+
+// the handle's own stream, the side stream of the seam kernels and the events that order them
+int Engine::init_streams()
+{
+  HIP_TRY(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
+  stream_ = own_;
+  HIP_TRY(hipEventCreateWithFlags(&ev_switch_, hipEventDisableTiming));
+  HIP_TRY(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&ev_fused_, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&ev_seam_[0], hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&ev_seam_[1], hipEventDisableTiming));
+  return kOk;
+}
+
+// dft stage i: the filter's spectra, the twiddle tables of its transforms and, for long blocks, the four-step workspace
+int Engine::init_dft_stage(int i)
+{
+  const StageSpec &sp = plan_.stages[i];
+  const DftFilter &f = plan_.dft[sp.filt];
+  const int Ng = f.N;
+  const int log2n = ilog2(Ng);
+  const int log2p = fdomain_up(sp.L) ? log2n - ilog2(sp.L) : log2n;
+  const int log2nd = sp.step < 0 ? log2n + sp.step : log2n;
+  int sub_n = 0, sub_v = 0;
+  const bool sub = split_geometry(i, sub_n, sub_v); // runs as fused_split_kernel: no transform of the block's own length
+  const bool big = log2n > 14 && !sub; // the reference's long blocks: four-step transform (dftbig.hip)
+  if (!sub && (big ? !big_dft_supported(log2n, log2p, log2nd) : !dft_shape_supported(log2n, log2p, log2nd))) return kInvParam;
+  int rc;
+  // G = DFT_N(L * h placed at (i + N - taps + 1) mod N) / N
+  if (!d_G_[sp.filt] && (rc = upload(component_spectra(f, Ng, 1, sp.L), &d_G_[sp.filt])) != kOk) return rc;
+  // the block's L polyphase components (dftx.hip)
+  if (!big && !d_Gr_[sp.filt] && sp.step == 1 && fdomain_up(sp.L) && dftx_supported(log2n, log2p, log2nd) &&
+      (rc = upload(component_spectra(f, Ng, sp.L, sp.L), &d_Gr_[sp.filt])) != kOk)
+    return rc;
+  if (!big) return sub || (twiddles(log2p) && twiddles(log2nd)) ? kOk : kNoMem;
+  BigDft &bg = big_[i];
+  bg.on = true;
+  if (!twiddles(log2p - 4) || !twiddles(log2nd - 4)) return kNoMem;
+  std::vector<double2> tw(Ng);
+  for (int j = 0; j < Ng; ++j) {
+    const long double th = 2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)Ng;
+    tw[j] = make_double2((double)cosl(th), (double)sinl(th));
   }
-  // rational polyphase stages that are not fused run as a matrix-pipe stage of their own (polymf.hip) when
-  // they have enough phases to fill 16-row tiles
-  polymf_.assign(ns, PolyMf());
-  for (int i = 0; i < ns; ++i) {
-    const StageSpec &p = plan_.stages[i];
-    if (p.kind != StageKind::Poly || p.order != 0 || (i > 0 && fuse_[i - 1].on) || p.L < 64) continue;
-    if (kn.no_mfma || kn.no_polymf) continue;
-    const int pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32);
-    int d4 = 0;
-    for (int rb = 0; rb < p.L; rb += 4) {
-      const long long a0 = at0 + (long long)rb * pstep, a1 = at0 + (long long)std::min(rb + 3, p.L - 1) * pstep;
-      d4 = std::max(d4, int(a1 / p.L - a0 / p.L));
-    }
-    const int KS = std::max(7, (p.n + d4 + 3) / 4), NGRP = (p.L + 15) / 16;
-    if (!polymf_supported(KS)) continue;
-    // tile length: at most 2048 stage-input samples and at most 30 output periods per tile
-    int Vt = 2048;
-    while (Vt > 256 && ((long long)Vt * p.L / pstep + p.L - 1) / p.L + 2 > 30) Vt -= 256;
-    if (((long long)Vt * p.L / pstep + p.L - 1) / p.L + 2 > 30) continue;
-    std::vector<double> am(size_t(NGRP) * KS * 64, 0.0);
-    for (int g = 0; g < NGRP; ++g)
-      for (int s = 0; s < KS; ++s)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int k = lane >> 4, bq = (lane >> 2) & 3, ii = lane & 3;
-          const int rb = 16 * g + 4 * bq, r = rb + ii;
-          if (r >= p.L) continue;
-          const int qb = (at0 + rb * pstep) / p.L;
-          const int ar = at0 + r * pstep, q = ar / p.L, ph = ar - q * p.L;
-          const int j = 4 * s + k - (q - qb);
-          if (j >= 0 && j < p.n) am[(size_t(g) * KS + s) * 64 + lane] = plan_.poly_table[size_t(ph) * p.n + j];
-        }
-    PolyMf &pm = polymf_[i];
-    void *dm = nullptr;
-    if ((rc = upload(am.data(), am.size() * sizeof(double), &dm)) != kOk) return rc;
-    pm.cfm = static_cast<double *>(dm);
-    {
-      std::vector<int> qt(size_t(NGRP) * 4);
-      for (int g = 0; g < NGRP; ++g)
-        for (int bq = 0; bq < 4; ++bq) {
-          int rb = 16 * g + 4 * bq;
-          if (rb >= p.L) rb = 0;
-          qt[size_t(g) * 4 + bq] = (at0 + rb * pstep) / p.L;
-        }
-      void *dq = nullptr;
-      if ((rc = upload(qt.data(), qt.size() * sizeof(int), &dq)) != kOk) return rc;
-      pm.qtab = static_cast<int *>(dq);
-    }
-    pm.KS = KS;
-    pm.NGRP = NGRP;
-    pm.Vt = Vt;
-    pm.blk_cap = 4096;
-    ALLOC_TRY(&pm.blk, size_t(pm.blk_cap) * sizeof(FusedBlock));
+  if ((rc = upload(tw, &bg.twN)) != kOk) return rc;
+  // (block, pair) items in flight per round of the three launches: at most 256 MB per workspace
+  const int npairs = pair_count(C_, pair_nchs());
+  bg.ws_items = int(std::max<long long>(1, std::min<long long>((256LL << 20) / (16LL * Ng), std::max(4 * npairs, 16))));
+  ALLOC_TRY(&bg.w1, size_t(bg.ws_items) * (size_t(1) << log2p) * sizeof(double2));
+  ALLOC_TRY(&bg.w2, size_t(bg.ws_items) * (size_t(1) << log2nd) * sizeof(double2));
+  return kOk;
+}
+
+// dft(step 1, L = 1,2,4) stage i directly followed by a rational polyphase stage runs as ONE kernel (fused.hip): its seam
+// ring, block table and coefficient tables.  slab_cap comes down to the frames of chain input one fused launch covers.
+int Engine::init_fused_pair(int i, size_t &slab_cap)
+{
+  const Knobs &kn = knobs();
+  const StageSpec &d = plan_.stages[i], &p = plan_.stages[i + 1];
+  if (d.kind != StageKind::Dft || p.kind != StageKind::Poly || p.order != 0 || d.step != 1) return kOk;
+  if (!(d.L == 1 || (pow2_ge2(d.L) && d.L <= 4))) return kOk;
+  const DftFilter &f = plan_.dft[d.filt];
+  const int log2n = ilog2(f.N), log2p = log2n - (d.L == 1 ? 0 : ilog2(d.L));
+  const int G = 2, pstep = int(p.step64 >> 32), at0 = int(p.at0 >> 32);
+  int dmax = 0;
+  const int NG = (p.L + G - 1) / G;
+  for (int m = 0; m < NG; ++m) {
+    const long long a0 = at0 + (long long)(G * m) * pstep, a1 = at0 + (long long)std::min(G * m + G - 1, p.L - 1) * pstep;
+    dmax = std::max(dmax, int(a1 / p.L - a0 / p.L));
   }
-  // the fifo between two fused stages carries no bulk data
-  bytes_per_in_frame = 0;
-  rate = 1;
+  const int max_seam = int(((long long)(p.n - 1) * p.L + pstep - 1) / pstep) + 1;
+  // Blocks too long for one workgroup (8192 / 16384 points): the sub-blocked form of the lean kernel, for the chains it
+  // covers -- x2 stage first in the chain (float frames in), even channel count, matrix-pipe tiles; the polyphase stage
+  // either last (float frames out) or feeding a further stage (fp64 ring out).  There is no generic kernel behind it, so
+  // everything is decided here.
+  int split_nsub = 0, split_vs = 0;
+  split_geometry(i, split_nsub, split_vs);
+  const bool split = split_nsub > 0;
+  const int threads = split ? 256 : f.N / 16;
+  if (!split && (NG > threads || !fused_shape_supported(log2n, log2p, p.n, p.n + dmax, max_seam))) return kOk;
+  if (kn.no_fuse) return kOk;
+  Fuse &fu = fuse_[i];
+  fu.on = true;
+  fu.nsub = split_nsub;
+  fu.Vs = split_vs;
+  int rc;
+  if (split) { // the block's two components: h placed at -(taps - 1) .. 0 mod 8192, 4096-point spectra
+    if (!twiddles(12)) return kNoMem;
+    if ((rc = upload(component_spectra(f, 8192, 2, d.L), &fu.Gs)) != kOk) return rc;
+  }
+  fu.span = p.n + dmax;
+  fu.NG = NG;
+  fu.KC = split ? 1 : threads / NG; // (vector variant's thread map: unused by the sub-blocked form, whose NG may exceed 256)
+  // blocks per launch: as many as a seam ring of at most 1280 MB allows (0.4 % of the card; round 2's 320 MB cut a 963 379-frame
+  // push of 256 stereo streams into three launches, each with its own prep / seam kernels and gaps; two launches worth of slots: seam(k) still
+  // reads its slots while fused(k+1) fills the next ones)
+  fu.blk_cap = 64;
+  while (fu.blk_cap < kFusedMaxBlocks && double(C_ + 1) * double(4 * fu.blk_cap) * 512 <= kn.seam_ring_mb * 1048576.0) fu.blk_cap *= 2;
+  while (fu.blk_cap < 8 * split_nsub) fu.blk_cap *= 2; // (sub-blocked: the table counts sub-blocks; at least 6 whole blocks per launch)
+  fu.slots = 2 * fu.blk_cap;
+  ALLOC_TRY(&fu.blk_dev, size_t(2 * fu.blk_cap) * sizeof(FusedBlock)); // two halves: launch k uses half k & 1 (see advance)
+  const size_t bytes = size_t(C_ + 1) * fu.slots * 2 * 32 * sizeof(double);
+  ALLOC_TRY(&fu.seam, bytes);
+  HIP_TRY(hipMemset(fu.seam, 0, bytes));
+  const int V = f.N - (f.num_taps - 1);
+  // periods a block can touch: ceil(outputs per block / L) + 1; chunk length fixed from it
+  const int Kmax = int(((long long)V * p.L / pstep + p.L - 1) / p.L) + 2;
+  fu.kper = (Kmax + fu.KC - 1) / fu.KC;
+  if (!split && (rc = upload(vector_tiles(p, G, NG, fu.KC, threads, plan_.poly_table), &fu.cft)) != kOk) return rc;
+  // matrix-pipe variant (fused.hip, fused_fast.hip): the two-round sample image of the kernel needs every period to fit one
+  // of the rounds (fused.hip, kSA / kSB0) ...
+  const MfGeom mg = mf_geom(p);
+  // ... and at most 32 periods per block (4 column steps per item), enough phases to fill 16-row tiles
+  // (The four periods of a tile -- lanes j = 0..3 of a B read, `step` samples apart -- fall on the same LDS banks when
+  // step is a multiple of 8 samples: 96k->44.1k (step 320), 48k->44.1k (160).  Such chains used to be kept on the vector
+  // variant (3.90 against 3.74 ms at the time); with the lean kernel's later gains the matrix-pipe variant wins despite
+  // its 4-way conflicts: 96k->44.1k 3.26 against 3.74 ms, 48k->44.1k +25 %.  RSMP_SPREAD_VECTOR=1 restores the old choice.)
+  bool lanes_spread = true;
+  if (kn.spread_vector)
+    for (int j1 = 0; j1 < 4; ++j1)
+      for (int j2 = j1 + 1; j2 < 4; ++j2)
+        if (((j2 - j1) * pstep) % 16 == 0) lanes_spread = false;
+  const bool rounds_ok = (mg.qb_max - mg.qb_min) + 4 * mg.KS + 4 <= (kFusedSA - kFusedSB0) * 256 + 32 && Kmax <= 32 && p.L >= 64 && lanes_spread;
+  if (split || (!kn.no_mfma && fused_mfma_supported(log2n, log2p, mg.KS) && rounds_ok)) { // (split: one image, no rounds to fit)
+    const MfOperands op = mf_operands(mg, p, plan_.poly_table);
+    if ((rc = upload(op.cfm, &fu.cfm)) != kOk || (rc = upload(op.cfm2, &fu.cfm2)) != kOk || (rc = upload(op.qtab, &fu.qtab)) != kOk)
+      return rc;
+    fu.NGRP = mg.NGRP;
+    fu.KS = mg.KS;
+    fu.qb_max = mg.qb_max;
+    fu.qb_min = mg.qb_min;
+  }
+  const size_t per_launch = size_t(fu.blk_cap / std::max(1, fu.nsub) - 2) * size_t((V - d.remL0 + d.L - 1) / d.L);
+  // frames of chain input per launch: divide by the rate of everything ahead of the dft stage
+  double ahead = 1;
+  for (int k = 0; k < i; ++k) ahead *= plan_.stages[k].kind == StageKind::Half ? 0.5 : plan_.stages[k].out_in_ratio;
+  const size_t cap = size_t(double(per_launch) / std::max(ahead, 1e-9));
+  slab_cap = slab_cap ? std::min(slab_cap, cap) : cap;
+  return kOk;
+}
+
+// a rational polyphase stage i that is not fused runs as a matrix-pipe stage of its own (polymf.hip) when it has enough phases
+// to fill 16-row tiles
+int Engine::init_polymf(int i)
+{
+  const Knobs &kn = knobs();
+  const StageSpec &p = plan_.stages[i];
+  if (p.kind != StageKind::Poly || p.order != 0 || (i > 0 && fuse_[i - 1].on) || p.L < 64) return kOk;
+  if (kn.no_mfma || kn.no_polymf) return kOk;
+  const int pstep = int(p.step64 >> 32);
+  const MfGeom mg = mf_geom(p);
+  if (!polymf_supported(mg.KS)) return kOk;
+  // tile length: at most 2048 stage-input samples and at most 30 output periods per tile
+  int Vt = 2048;
+  while (Vt > 256 && ((long long)Vt * p.L / pstep + p.L - 1) / p.L + 2 > 30) Vt -= 256;
+  if (((long long)Vt * p.L / pstep + p.L - 1) / p.L + 2 > 30) return kOk;
+  const MfOperands op = mf_operands(mg, p, plan_.poly_table);
+  PolyMf &pm = polymf_[i];
+  int rc;
+  if ((rc = upload(op.cfm, &pm.cfm)) != kOk || (rc = upload(op.qtab, &pm.qtab)) != kOk) return rc;
+  pm.KS = mg.KS;
+  pm.NGRP = mg.NGRP;
+  pm.Vt = Vt;
+  pm.blk_cap = 4096;
+  ALLOC_TRY(&pm.blk, size_t(pm.blk_cap) * sizeof(FusedBlock));
+  return kOk;
+}
+
+// Bound the fp64 fifos between stages: a push is cut into time slabs, each slab runs through every stage
+// before the next one starts.  Measured on the 3-stage 44.1k->192k chain (32 streams x 8 ch): 96 MB slabs 15.0,
+// 192 MB 15.5, 400 MB 16.6, 1600 MB 17.3 Gsamples/s -- launch size matters more than Infinity-Cache residency.
+void Engine::size_slabs(size_t fused_slab_cap)
+{
+  const int ns = int(plan_.stages.size());
+  double bytes_per_in_frame = 0, rate = 1;
   for (int i = 0; i < ns; ++i) {
     const StageSpec &sp = plan_.stages[i];
     if (sp.kind == StageKind::Dft) rate *= sp.step > 0 ? double(sp.L) / sp.step : double(sp.L) / double(1 << -sp.step);
     else if (sp.kind == StageKind::Poly) rate *= sp.out_in_ratio;
     else rate *= 0.5;
-    if (i + 1 < ns && !fuse_[i].on) bytes_per_in_frame += rate * 8.0 * C_;
+    if (i + 1 < ns && !fuse_[i].on) bytes_per_in_frame += rate * 8.0 * C_; // (the fifo between two fused stages carries no bulk data)
   }
-  // Bound the fp64 fifos between stages: a push is cut into time slabs, each slab runs through every stage
-  // before the next one starts.  Measured on the 3-stage 44.1k->192k chain (32 streams x 8 ch): 96 MB slabs 15.0,
-  // 192 MB 15.5, 400 MB 16.6, 1600 MB 17.3 Gsamples/s -- launch size matters more than Infinity-Cache residency.
-  const double budget = kn.slab_mb * 1024 * 1024;
+  const double budget = knobs().slab_mb * 1024 * 1024;
   slab_frames_ = bytes_per_in_frame > 0 ? size_t(budget / bytes_per_in_frame) : plan_.isamp_max;
   slab_frames_ = std::max<size_t>(slab_frames_, 8192);
   slab_frames_ = std::min<size_t>(slab_frames_, std::max<size_t>(plan_.isamp_max, 1));
   if (fused_slab_cap) slab_frames_ = std::max<size_t>(1024, std::min(slab_frames_, fused_slab_cap));
-  for (int i = 0; i <= ns; ++i)
-    if ((rc = ensure_ring(i, std::max<long long>(book_.wr[i], 1))) != kOk) return rc;
-  HIP_TRY(hipStreamSynchronize(stream_));
-  return kOk;
 }
 
 void Engine::set_profiling(bool on)
@@ -719,6 +688,7 @@ Engine::~Engine()
   DeviceScope on(device_);
   (void)hipStreamSynchronize(stream_); // nullptr is the default stream (RRX_set_stream(h, NULL)): it too may hold queued work on our buffers
   if (own_ && own_ != stream_) (void)hipStreamSynchronize(own_);
+  if (side_) (void)hipStreamSynchronize(side_); // seam kernels queued there read the seam ring, block tables and rings freed below
   free_garbage();
   for (Ring &r : rings_) if (r.buf) (void)hipFree(r.buf);
   for (double2 *&g : d_G_) if (g) (void)hipFree(g);
@@ -763,7 +733,7 @@ Engine::~Engine()
     if (m.qtab) (void)hipFree(m.qtab);
     if (m.blk) (void)hipFree(m.blk);
   }
-  if (side_) { (void)hipStreamSynchronize(side_); (void)hipStreamDestroy(side_); }
+  if (side_) (void)hipStreamDestroy(side_);
   if (ev_fused_) (void)hipEventDestroy(ev_fused_);
   for (hipEvent_t &e : ev_seam_) if (e) (void)hipEventDestroy(e);
   if (ev_switch_) (void)hipEventDestroy(ev_switch_);
@@ -1068,216 +1038,205 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   const bool more_slabs = ps.more_slabs;
   DftArgs &pend_args = pend.args;
   const int pend_log2n = pend.log2n, pend_log2p = pend.log2p;
-  {
-    int rc = ensure_ring(i + 1, dst_need(wro + count));
-    if (rc) return rc;
-    const Fuse &fu = fuse_[i - 1];
-    FusedArgs fa;
-    fa.d = pend_args;
-    fa.tab = d_poly_;
-    fa.seam = fu.seam;
-    fa.cft = fu.cft;
-    fa.at0 = sp.at0 >> 32;
-    fa.b_offset = sp.preload;
-    fa.out_offset2 = out_offset;
-    fa.seam_mask = fu.slots - 1;
-    fa.n = sp.n;
-    fa.polyL = sp.L;
-    fa.step = int(step);
-    fa.span = fu.span;
-    fa.NG = fu.NG;
-    fa.KC = fu.KC;
-    fa.kper = fu.kper;
-    fa.cfm = fu.cfm;
-    fa.qtab = fu.qtab;
-    fa.cfm2 = fu.cfm2;
-    fa.NGRP = fu.NGRP;
-    fa.KS = fu.KS;
-    fa.dbg = dbg_;
-    fa.stamps = stamps_;
-    const bool split = fu.nsub > 0;
-    const int ntab = split ? pend.nblocks * fu.nsub : pend.nblocks; // table entries = workgroups per pair: blocks, or sub-blocks
-    if (ntab > fu.blk_cap) return kInternal;
-    FusedPrepArgs pa; // output bookkeeping of each block (closed forms in kernels.hpp), evaluated on the device
-    pa.b_offset = fa.b_offset;
-    pa.B0 = pend.B0;
-    pa.at0 = fa.at0;
-    pa.V = fa.d.V;
-    pa.polyL = sp.L;
-    pa.step = int(step);
-    pa.n = sp.n;
-    pa.nblocks = ntab;
-    pa.nsub = fu.nsub;
-    pa.Vs = fu.Vs;
-    const bool split_two = split && fu.nsub == 1 && fu.Vs > kSplitVsMax; // whole 8192-point blocks, two rounds (split_geometry)
-    pa.two_round = fu.cfm != nullptr && (!split || split_two);
-    pa.ra_end = split_two ? kSplitRaEnd : 0;
-    pa.rb_start = split_two ? kSplitRbStart : 0;
-    pa.KS = fu.KS;
-    pa.qb_max = fu.qb_max;
-    pa.qb_min = fu.qb_min;
-    pa.clip_lo = 0;
-    pa.clip_hi = 0x7fffffffffffffffLL;
-    if (!split)
-      for (int k : {0, pend.nblocks - 1}) // same closed forms on the host: bounds the kernels rely on
-        if (fused_block_info(pa, k).K > (fu.cfm ? 32 : fu.KC * fu.kper)) return kInternal;
-    // side stream for the seam kernel only when nothing downstream in this pass reads the seam outputs (poly is the last stage)
-    // ... and only when another slab of this push follows: seam(k) then runs beside fused(k+1).  Behind the LAST fused
-    // launch of a push the side stream has nothing to overlap with but the small carry copy, and the two cross-queue
-    // hand-overs (event -> side stream -> join) cost more than they hide: 2.455 against 2.505 ms per step measured.
-    const bool seam_on_side = more_slabs && !(profiling_ || !dst_f32 || no_side_);
-    // seam(k-2), possibly still pending on the side stream, reads the seam-ring slots AND the half of the block table
-    // that this launch is about to overwrite: both the table fill and the fused launch wait for it.  (The table has
-    // two halves, launch k uses half k & 1: seam(k-1) may still be reading the other one.  With ONE table, a push cut
-    // into three launches lost the seam outputs of its first blocks: tests/test_gpu_round3.py::test_cfg0_bench_shape_*.)
-    if (seam_launches_ >= 2) HIP_TRY(hipStreamWaitEvent(stream_, ev_seam_[seam_launches_ & 1], 0));
-    FusedBlock *const blk_half = fu.blk_dev + size_t(seam_launches_ & 1) * fu.blk_cap;
-    { const int pp = prof_begin(false, "rsmp::fused_prep_kernel"); HIP_TRY(launch_fused_prep(pa, blk_half, stream_)); prof_end(pp); }
-    fa.blk = blk_half;
-    // the fused launch emits exactly the outputs [wro, wro + count): windows ending before wr of fifo i
-    const long long endnum = (b.wr[i] - sp.n + 1) * sp.L - fa.at0;
-    if (wro - out_offset + count != (endnum <= 0 ? 0 : (endnum + step - 1) / step)) return kInternal;
-    const bool s32 = i - 1 == 0;
-    // Blocks whose input span and outputs lie in the caller's buffers as plain interleaved frames go to the lean
-    // kernel (fused_fast.hip); the others (the block that straddles ring and buffer, ring wrap, odd channel counts,
-    // fp64 rings on either side) to the generic one.  At most three launches: generic head, lean middle, generic tail.
-    int f0 = 0, f1 = 0;
-    FastIo io = {};
-    io.dio = w_ == 2 ? 1 : 0;                  // float64 frames: the *_dio_kernel instances
-    const uintptr_t amask = 8 * uintptr_t(w_) - 1; // a channel pair of a frame as one 8- (16-) byte word
-    if (split) {
-      // Sub-blocked form: ONE launch of nblocks * nsub workgroups per channel pair.  Every sub-block's 4096-frame window lies
-      // inside its block's own input span, i.e. in the caller's buffer or, below it, in fifo 0's ring; outputs go to the next
-      // fifo's fp64 ring at any position.  (Decided when the handle was opened: first stage, even channels, not the last stage.)
-      if (!s32 || (nch_ & 1) || !ein.ptr || (ein.stride_elems & 1)) return kInternal;
-      io.in = ein.ptr;
-      io.in_ring = static_cast<const float *>(rings_[0].buf);
-      io.in_ring_mask = rings_[0].cap - 1;
-      io.in_ring_stream_stride = rings_[0].cap * nch_;
-      io.in_abs0 = ein.begin;
-      io.in_stream_stride = ein.stride_elems;
-      io.nch = nch_;
-      io.in_unaligned = (reinterpret_cast<uintptr_t>(ein.ptr) & amask) ? 1 : 0;
-      int omode = 1;
-      if (!dst_f32) {
-        io.out64 = static_cast<double *>(rings_[i + 1].buf);
-        io.out64_mask = rings_[i + 1].cap - 1;
-        io.out64_chan_stride = rings_[i + 1].cap;
-      } else {
-        // float frames out: straight into the caller's buffer when every output of this launch lies inside it (a flow / a
-        // mirrored push), else output by output wherever the fifo has it (RR_push: everything into the ring)
-        const bool ext_ok = eout.ptr && !(eout.stride_elems & 1);
-        const bool all_inside = ext_ok && wro >= eout.begin && wro + count <= eout.end;
-        omode = (all_inside && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 0 : 2;
-        io.out = ext_ok ? eout.ptr : nullptr;
-        io.out_abs0 = ext_ok ? eout.begin : 0;
-        io.out_end = ext_ok ? eout.end : 0; // (empty range: every output goes to the ring)
-        io.out_stream_stride = ext_ok ? eout.stride_elems : 0;
-        io.out_unaligned = (ext_ok && (reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 1 : 0;
-        io.out_ring = static_cast<float *>(rings_[i + 1].buf);
-        io.out_ring_mask = rings_[i + 1].cap - 1;
-        io.out_ring_stream_stride = rings_[i + 1].cap * nch_;
-        if (eout.ptr && !ext_ok) return kInternal; // (an odd frame stride with an even channel count cannot happen)
-        if (omode == 2 && !io.out_ring) return kInternal;
-      }
-      FusedArgs fr = fa;
-      fr.d.G = fu.Gs;
-      fr.d.tw_fwd = fr.d.tw_inv = twiddles(12);
-      if (!fr.d.tw_fwd) return kNoMem;
-      fr.d.nsub = fu.nsub;
-      fr.d.Vs = fu.Vs;
-      fr.d.two = split_two ? 1 : 0;
-      fr.d.Pref = 1 << pend_log2p;
-      fr.d.Bref0 = pend.B0;
-      fr.d.B0 = pend.B0 * fu.nsub;
-      fr.d.nblocks = ntab;
-      fa = fr; // seam_kernel below: sub-block indices, same table
-      const int pi = prof_begin(true);
-      const char *kn = nullptr;
-      HIP_TRY(launch_fused_split(omode, fr, io, stream_, &kn));
-      prof_name(pi, kn);
-      prof_end(pi);
-    } else
-    if (fu.cfm && s32 && dst_f32 && !(nch_ & 1) && ein.ptr && eout.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
-        !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask) && !(ein.stride_elems & 1) &&
-        !(eout.stride_elems & 1)) {
-      const long long P = 1LL << pend_log2p, q = fa.d.q;
-      // (a block that starts below the caller's buffer takes its head from fifo 0's ring: the lean kernel handles that too)
-      const long long hi = (ein.end - P) >= 0 ? (ein.end - P) / q - pend.B0 + 1 : 0;
-      f0 = 0;
-      f1 = int(std::min<long long>(pend.nblocks, hi));
-      // outputs of blocks [f0, f1) must lie inside the caller's output buffer
-      while (f0 < f1) {
-        const FusedBlock b0 = fused_block_info(pa, f0), b1 = fused_block_info(pa, f1 - 1);
-        if (out_offset + b0.i_lo < eout.begin) { ++f0; continue; }
-        if (out_offset + b1.i_lo + b1.cnt > eout.end) { --f1; continue; }
-        break;
-      }
-      if (f0 >= f1) f0 = f1 = 0;
-      io.in = ein.ptr;
-      io.in_ring = static_cast<const float *>(rings_[0].buf);
-      io.in_ring_mask = rings_[0].cap - 1;
-      io.in_ring_stream_stride = rings_[0].cap * nch_;
-      io.out = eout.ptr;
-      io.in_abs0 = ein.begin;
-      io.out_abs0 = eout.begin;
-      io.in_stream_stride = ein.stride_elems;
-      io.out_stream_stride = eout.stride_elems;
-      io.nch = nch_;
-    } else if (fu.cfm && s32 && !dst_f32 && !(nch_ & 1) && ein.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
-               !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(ein.stride_elems & 1)) {
-      // the polyphase stage feeds another stage: same lean kernel, its outputs into the next fifo's fp64 ring (any ring
-      // position: the kernel masks the index), so only the input side limits the range
-      const long long P = 1LL << pend_log2p, q = fa.d.q;
-      const long long hi = (ein.end - P) >= 0 ? (ein.end - P) / q - pend.B0 + 1 : 0;
-      f0 = 0;
-      f1 = int(std::max<long long>(0, std::min<long long>(pend.nblocks, hi)));
-      io.in = ein.ptr;
-      io.in_ring = static_cast<const float *>(rings_[0].buf);
-      io.in_ring_mask = rings_[0].cap - 1;
-      io.in_ring_stream_stride = rings_[0].cap * nch_;
-      io.in_abs0 = ein.begin;
-      io.in_stream_stride = ein.stride_elems;
-      io.nch = nch_;
-      io.out64 = static_cast<double *>(rings_[i + 1].buf);
-      io.out64_mask = rings_[i + 1].cap - 1;
-      io.out64_chan_stride = rings_[i + 1].cap;
+  int rc = ensure_ring(i + 1, dst_need(wro + count));
+  if (rc) return rc;
+  const Fuse &fu = fuse_[i - 1];
+  FusedArgs fa;
+  fa.d = pend_args;
+  fa.tab = d_poly_;
+  fa.seam = fu.seam;
+  fa.cft = fu.cft;
+  fa.at0 = sp.at0 >> 32;
+  fa.b_offset = sp.preload;
+  fa.out_offset2 = out_offset;
+  fa.seam_mask = fu.slots - 1;
+  fa.n = sp.n;
+  fa.polyL = sp.L;
+  fa.step = int(step);
+  fa.span = fu.span;
+  fa.NG = fu.NG;
+  fa.KC = fu.KC;
+  fa.kper = fu.kper;
+  fa.cfm = fu.cfm;
+  fa.qtab = fu.qtab;
+  fa.cfm2 = fu.cfm2;
+  fa.NGRP = fu.NGRP;
+  fa.KS = fu.KS;
+  fa.dbg = dbg_;
+  fa.stamps = stamps_;
+  const bool split = fu.nsub > 0;
+  const int ntab = split ? pend.nblocks * fu.nsub : pend.nblocks; // table entries = workgroups per pair: blocks, or sub-blocks
+  if (ntab > fu.blk_cap) return kInternal;
+  FusedPrepArgs pa; // output bookkeeping of each block (closed forms in kernels.hpp), evaluated on the device
+  pa.b_offset = fa.b_offset;
+  pa.B0 = pend.B0;
+  pa.at0 = fa.at0;
+  pa.V = fa.d.V;
+  pa.polyL = sp.L;
+  pa.step = int(step);
+  pa.n = sp.n;
+  pa.nblocks = ntab;
+  pa.nsub = fu.nsub;
+  pa.Vs = fu.Vs;
+  const bool split_two = split && fu.nsub == 1 && fu.Vs > kSplitVsMax; // whole 8192-point blocks, two rounds (split_geometry)
+  pa.two_round = fu.cfm != nullptr && (!split || split_two);
+  pa.ra_end = split_two ? kSplitRaEnd : 0;
+  pa.rb_start = split_two ? kSplitRbStart : 0;
+  pa.KS = fu.KS;
+  pa.qb_max = fu.qb_max;
+  pa.qb_min = fu.qb_min;
+  pa.clip_lo = 0;
+  pa.clip_hi = 0x7fffffffffffffffLL;
+  if (!split)
+    for (int k : {0, pend.nblocks - 1}) // same closed forms on the host: bounds the kernels rely on
+      if (fused_block_info(pa, k).K > (fu.cfm ? 32 : fu.KC * fu.kper)) return kInternal;
+  // side stream for the seam kernel only when nothing downstream in this pass reads the seam outputs (poly is the last stage)
+  // ... and only when another slab of this push follows: seam(k) then runs beside fused(k+1).  Behind the LAST fused
+  // launch of a push the side stream has nothing to overlap with but the small carry copy, and the two cross-queue
+  // hand-overs (event -> side stream -> join) cost more than they hide: 2.455 against 2.505 ms per step measured.
+  const bool seam_on_side = more_slabs && !(profiling_ || !dst_f32 || no_side_);
+  // seam(k-2), possibly still pending on the side stream, reads the seam-ring slots AND the half of the block table
+  // that this launch is about to overwrite: both the table fill and the fused launch wait for it.  (The table has
+  // two halves, launch k uses half k & 1: seam(k-1) may still be reading the other one.  With ONE table, a push cut
+  // into three launches lost the seam outputs of its first blocks: tests/test_gpu_round3.py::test_cfg0_bench_shape_*.)
+  if (seam_launches_ >= 2) HIP_TRY(hipStreamWaitEvent(stream_, ev_seam_[seam_launches_ & 1], 0));
+  FusedBlock *const blk_half = fu.blk_dev + size_t(seam_launches_ & 1) * fu.blk_cap;
+  { const int pp = prof_begin(false, "rsmp::fused_prep_kernel"); HIP_TRY(launch_fused_prep(pa, blk_half, stream_)); prof_end(pp); }
+  fa.blk = blk_half;
+  // the fused launch emits exactly the outputs [wro, wro + count): windows ending before wr of fifo i
+  const long long endnum = (b.wr[i] - sp.n + 1) * sp.L - fa.at0;
+  if (wro - out_offset + count != (endnum <= 0 ? 0 : (endnum + step - 1) / step)) return kInternal;
+  const bool s32 = i - 1 == 0;
+  // Blocks whose input span and outputs lie in the caller's buffers as plain interleaved frames go to the lean
+  // kernel (fused_fast.hip); the others (the block that straddles ring and buffer, ring wrap, odd channel counts,
+  // fp64 rings on either side) to the generic one.  At most three launches: generic head, lean middle, generic tail.
+  int f0 = 0, f1 = 0;
+  FastIo io = {};
+  io.dio = w_ == 2 ? 1 : 0;                  // float64 frames: the *_dio_kernel instances
+  const uintptr_t amask = 8 * uintptr_t(w_) - 1; // a channel pair of a frame as one 8- (16-) byte word
+  auto io_in = [&] { // the caller's frames from in_abs0 on, fifo 0's ring below them
+    io.in = ein.ptr;
+    io.in_ring = static_cast<const float *>(rings_[0].buf);
+    io.in_ring_mask = rings_[0].cap - 1;
+    io.in_ring_stream_stride = rings_[0].cap * nch_;
+    io.in_abs0 = ein.begin;
+    io.in_stream_stride = ein.stride_elems;
+    io.nch = nch_;
+  };
+  auto io_out64 = [&] { // the next fifo's fp64 ring
+    io.out64 = static_cast<double *>(rings_[i + 1].buf);
+    io.out64_mask = rings_[i + 1].cap - 1;
+    io.out64_chan_stride = rings_[i + 1].cap;
+  };
+  if (split) {
+    // Sub-blocked form: ONE launch of nblocks * nsub workgroups per channel pair.  Every sub-block's 4096-frame window lies
+    // inside its block's own input span, i.e. in the caller's buffer or, below it, in fifo 0's ring; outputs go to the next
+    // fifo's fp64 ring at any position.  (Decided when the handle was opened: first stage, even channels, not the last stage.)
+    if (!s32 || (nch_ & 1) || !ein.ptr || (ein.stride_elems & 1)) return kInternal;
+    io_in();
+    io.in_unaligned = (reinterpret_cast<uintptr_t>(ein.ptr) & amask) ? 1 : 0;
+    int omode = 1;
+    if (!dst_f32)
+      io_out64();
+    else {
+      // float frames out: straight into the caller's buffer when every output of this launch lies inside it (a flow / a
+      // mirrored push), else output by output wherever the fifo has it (RR_push: everything into the ring)
+      const bool ext_ok = eout.ptr && !(eout.stride_elems & 1);
+      const bool all_inside = ext_ok && wro >= eout.begin && wro + count <= eout.end;
+      omode = (all_inside && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 0 : 2;
+      io.out = ext_ok ? eout.ptr : nullptr;
+      io.out_abs0 = ext_ok ? eout.begin : 0;
+      io.out_end = ext_ok ? eout.end : 0; // (empty range: every output goes to the ring)
+      io.out_stream_stride = ext_ok ? eout.stride_elems : 0;
+      io.out_unaligned = (ext_ok && (reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 1 : 0;
+      io.out_ring = static_cast<float *>(rings_[i + 1].buf);
+      io.out_ring_mask = rings_[i + 1].cap - 1;
+      io.out_ring_stream_stride = rings_[i + 1].cap * nch_;
+      if (eout.ptr && !ext_ok) return kInternal; // (an odd frame stride with an even channel count cannot happen)
+      if (omode == 2 && !io.out_ring) return kInternal;
     }
-    auto launch_range = [&](int b0, int b1, bool fast) -> int {
-      if (b0 >= b1) return kOk;
-      FusedArgs fr = fa;
-      fr.d.B0 = fa.d.B0 + b0;
-      fr.d.nblocks = b1 - b0;
-      fr.blk = fa.blk + b0;
-      const int pi = prof_begin(true);
-      const char *kn = nullptr;
-      if (fast) HIP_TRY(launch_fused_fast(pend_log2p, fr, io, stream_, &kn));
-      else
-        HIP_TRY(launch_fused(pend_log2n, pend_log2p, s32 ? fk_ : 0, dst_f32, s32 ? f32_view(0, &ein, nullptr) : nof,
-                             s32 ? nod : f64_view(i - 1), dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof,
-                             dst_f32 ? nod : f64_view(i + 1), fr, stream_, &kn));
-      prof_name(pi, kn);
-      prof_end(pi);
-      return kOk;
-    };
-    if (!split) {
-      { int rl = launch_range(0, f0, false); if (rl) return rl; }
-      { int rl = launch_range(f0, f1, true); if (rl) return rl; }
-      { int rl = launch_range(f1, pend.nblocks, false); if (rl) return rl; }
+    FusedArgs fr = fa;
+    fr.d.G = fu.Gs;
+    fr.d.tw_fwd = fr.d.tw_inv = twiddles(12);
+    if (!fr.d.tw_fwd) return kNoMem;
+    fr.d.nsub = fu.nsub;
+    fr.d.Vs = fu.Vs;
+    fr.d.two = split_two ? 1 : 0;
+    fr.d.Pref = 1 << pend_log2p;
+    fr.d.Bref0 = pend.B0;
+    fr.d.B0 = pend.B0 * fu.nsub;
+    fr.d.nblocks = ntab;
+    fa = fr; // seam_kernel below: sub-block indices, same table
+    const int pi = prof_begin(true);
+    const char *kn = nullptr;
+    HIP_TRY(launch_fused_split(omode, fr, io, stream_, &kn));
+    prof_name(pi, kn);
+    prof_end(pi);
+  } else if (fu.cfm && s32 && dst_f32 && !(nch_ & 1) && ein.ptr && eout.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
+             !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask) &&
+             !(ein.stride_elems & 1) && !(eout.stride_elems & 1)) {
+    const long long P = 1LL << pend_log2p, q = fa.d.q;
+    // (a block that starts below the caller's buffer takes its head from fifo 0's ring: the lean kernel handles that too)
+    const long long hi = (ein.end - P) >= 0 ? (ein.end - P) / q - pend.B0 + 1 : 0;
+    f0 = 0;
+    f1 = int(std::min<long long>(pend.nblocks, hi));
+    // outputs of blocks [f0, f1) must lie inside the caller's output buffer
+    while (f0 < f1) {
+      const FusedBlock b0 = fused_block_info(pa, f0), b1 = fused_block_info(pa, f1 - 1);
+      if (out_offset + b0.i_lo < eout.begin) { ++f0; continue; }
+      if (out_offset + b1.i_lo + b1.cnt > eout.end) { --f1; continue; }
+      break;
     }
-    if (!seam_on_side) {
-      { int rcj = join_side(); if (rcj) return rcj; } // (a seam kernel of an earlier launch of this push may still be on the side stream)
-      const int ps = prof_begin(false, "rsmp::seam_kernel");
-      HIP_TRY(launch_seam(dst_f32, dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), fa, stream_));
-      prof_end(ps);
-    } else {
-      HIP_TRY(hipEventRecord(ev_fused_, stream_));
-      HIP_TRY(hipStreamWaitEvent(side_, ev_fused_, 0));
-      HIP_TRY(launch_seam(dst_f32, dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), fa, side_));
-      HIP_TRY(hipEventRecord(ev_seam_[seam_launches_ & 1], side_));
-      ++seam_launches_;
-      side_pending_ = true;
-    }
+    if (f0 >= f1) f0 = f1 = 0;
+    io_in();
+    io.out = eout.ptr;
+    io.out_abs0 = eout.begin;
+    io.out_stream_stride = eout.stride_elems;
+  } else if (fu.cfm && s32 && !dst_f32 && !(nch_ & 1) && ein.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
+             !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(ein.stride_elems & 1)) {
+    // the polyphase stage feeds another stage: same lean kernel, its outputs into the next fifo's fp64 ring (any ring
+    // position: the kernel masks the index), so only the input side limits the range
+    const long long P = 1LL << pend_log2p, q = fa.d.q;
+    const long long hi = (ein.end - P) >= 0 ? (ein.end - P) / q - pend.B0 + 1 : 0;
+    f0 = 0;
+    f1 = int(std::max<long long>(0, std::min<long long>(pend.nblocks, hi)));
+    io_in();
+    io_out64();
+  }
+  auto launch_range = [&](int b0, int b1, bool fast) -> int {
+    if (b0 >= b1) return kOk;
+    FusedArgs fr = fa;
+    fr.d.B0 = fa.d.B0 + b0;
+    fr.d.nblocks = b1 - b0;
+    fr.blk = fa.blk + b0;
+    const int pi = prof_begin(true);
+    const char *kn = nullptr;
+    if (fast) HIP_TRY(launch_fused_fast(pend_log2p, fr, io, stream_, &kn));
+    else
+      HIP_TRY(launch_fused(pend_log2n, pend_log2p, s32 ? fk_ : 0, dst_f32, s32 ? f32_view(0, &ein, nullptr) : nof,
+                           s32 ? nod : f64_view(i - 1), dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof,
+                           dst_f32 ? nod : f64_view(i + 1), fr, stream_, &kn));
+    prof_name(pi, kn);
+    prof_end(pi);
+    return kOk;
+  };
+  if (!split) {
+    { int rl = launch_range(0, f0, false); if (rl) return rl; }
+    { int rl = launch_range(f0, f1, true); if (rl) return rl; }
+    { int rl = launch_range(f1, pend.nblocks, false); if (rl) return rl; }
+  }
+  if (!seam_on_side) {
+    { int rcj = join_side(); if (rcj) return rcj; } // (a seam kernel of an earlier launch of this push may still be on the side stream)
+    const int ps = prof_begin(false, "rsmp::seam_kernel");
+    HIP_TRY(launch_seam(dst_f32, dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), fa, stream_));
+    prof_end(ps);
+  } else {
+    HIP_TRY(hipEventRecord(ev_fused_, stream_));
+    HIP_TRY(hipStreamWaitEvent(side_, ev_fused_, 0));
+    HIP_TRY(launch_seam(dst_f32, dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), fa, side_));
+    HIP_TRY(hipEventRecord(ev_seam_[seam_launches_ & 1], side_));
+    ++seam_launches_;
+    side_pending_ = true;
   }
   return kOk;
 }

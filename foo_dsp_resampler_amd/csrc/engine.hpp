@@ -107,6 +107,12 @@ public:
 private:
   Engine() = default;
   int init(const Config &cfg, int nch, int nstreams);
+  // the steps of init, in order
+  int init_streams();
+  int init_dft_stage(int i);
+  int init_fused_pair(int i, size_t &slab_cap);
+  int init_polymf(int i);
+  void size_slabs(size_t fused_slab_cap);
   // Sample format of fifo 0 and the last fifo (the intermediate fifos are fp64 rings either way): w_ = 4-byte words per
   // sample (1: float32 frames, 2: float64 frames), fk_ = the frame kind the kernels see (kFramesF32 / kFramesF64).  Host
   // code moves frames as w_ * nch_ floats; kernel views and FastIo count samples.
@@ -144,7 +150,7 @@ private:
   F32View f32_view(int f, const ExtIn *ein, const ExtOut *eout) const;
   F64View f64_view(int f) const;
   void note_input(Book &b, size_t n) const;
-  int upload(const void *src, size_t bytes, void **dst);
+  template <class T> int upload(const std::vector<T> &src, T **dst); // allocate, copy; *dst is set on success
   const double2 *twiddles(int log2m);
   const double2 *twiddles8(int log2m);
   void free_garbage();
