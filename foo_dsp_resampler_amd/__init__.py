@@ -6,7 +6,8 @@ ctypes mirror of that interface used by the tests and bench.py; it contains no s
 no CPU fallback: if the library (or a GPU) is missing, calls fail.
 """
 from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_dispatch, describe_plan, lib, lib_path,  # noqa: F401
-                      plan_table, RR_BEST, RR_NORM, RRX_FMT_FLOAT, RRX_FMT_DOUBLE, EXPECTED_SYMBOLS)
+                      plan_table, RR_BEST, RR_NORM, RRX_FMT_FLOAT, RRX_FMT_DOUBLE, RRX_FMT_S16, RRX_FMT_S32, EXPECTED_SYMBOLS)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "lib", "lib_path",
-           "available_symbols", "RR_BEST", "RR_NORM", "RRX_FMT_FLOAT", "RRX_FMT_DOUBLE", "EXPECTED_SYMBOLS"]
+           "available_symbols", "RR_BEST", "RR_NORM", "RRX_FMT_FLOAT", "RRX_FMT_DOUBLE", "RRX_FMT_S16", "RRX_FMT_S32",
+           "EXPECTED_SYMBOLS"]

@@ -151,7 +151,7 @@ int RRX_device(const RR_handle *h) { return h ? h->eng->device() : -1; }
 
 int RRX_open_batch_fmt(const RR_config *config, int nchannels, int nstreams, int device, int format, RR_handle **const handle)
 {
-  if (format != RRX_FMT_FLOAT && format != RRX_FMT_DOUBLE) { // checked before anything touches a device
+  if (format != RRX_FMT_FLOAT && format != RRX_FMT_DOUBLE && format != RRX_FMT_S16 && format != RRX_FMT_S32) { // checked before anything touches a device
     if (handle) *handle = nullptr;
     return RR_INVPARAM;
   }
@@ -164,12 +164,60 @@ int RRX_open_batch_fmt(const RR_config *config, int nchannels, int nstreams, int
 
 int RRX_format(const RR_handle *h) { return h ? h->eng->format() : -1; }
 
-// The double forms hand the engine their buffers behind a float pointer: a double handle's engine moves its frames as
-// 2 * nchannels 4-byte words (Engine::w_) and its kernels read them as float64 (kFramesF64).
+// The double and format-tagged forms hand the engine their buffers behind a float pointer: the engine moves a handle's frames
+// as raw memory (Engine::eb_ bytes per sample) and its kernels read them as the handle's type (kFramesF64 / kFramesS16 / ...).
 namespace {
-inline const float *cwords(const double *p) { return reinterpret_cast<const float *>(p); }
-inline float *words(double *p) { return reinterpret_cast<float *>(p); }
+inline const float *cwords(const void *p) { return reinterpret_cast<const float *>(p); }
+inline float *words(void *p) { return reinterpret_cast<float *>(p); }
 } // namespace
+
+// One format-tagged set for all four formats: `format` is what the caller believes the buffer holds and must be the handle's
+// (checked before anything moves: a mismatch leaves the handle as it was).  On float and double handles this is the code path
+// of RRX_*_strided / RRX_*_device and RRX_*_double.
+int RRX_push_samples(RR_handle *h, int format, const void *ibuf, size_t in_stride, size_t isamp)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->push_host(cwords(ibuf), in_stride, isamp); });
+}
+
+int RRX_pull_samples(RR_handle *h, int format, void *obuf, size_t out_stride, size_t osamp, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->pull_host(words(obuf), out_stride, osamp, ogen); });
+}
+
+int RRX_flow_samples(RR_handle *h, int format, const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp,
+                     size_t osamp, size_t *iused, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  if (h->eng->nstreams() == 1) in_stride = isamp, out_stride = osamp; // packed, as RR_flow
+  return guarded(h, [&] { return h->eng->flow_host(cwords(ibuf), in_stride, words(obuf), out_stride, isamp, osamp, iused, ogen); });
+}
+
+int RRX_push_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, size_t isamp)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->push_device(cwords(d_ibuf), in_stride, isamp); });
+}
+
+int RRX_pull_device_samples(RR_handle *h, int format, void *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->pull_device(words(d_obuf), out_stride, osamp, ogen); });
+}
+
+int RRX_flow_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, void *d_obuf, size_t out_stride,
+                            size_t isamp, size_t osamp, size_t *iused, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->flow_device(cwords(d_ibuf), in_stride, words(d_obuf), out_stride, isamp, osamp, iused, ogen); });
+}
 
 int RRX_push_double(RR_handle *h, const double *ibuf, size_t in_stride, size_t isamp)
 {

@@ -101,8 +101,8 @@ template <int DIR> __device__ __forceinline__ void fft8x(c64 (&u)[8], int tid, c
 }
 } // namespace
 
-// OKIND = 1 / 2 / 3: every block of the launch reads one contiguous span and writes one contiguous span of float frames /
-// of the planar fp64 rings / of float64 frames (pair_span's kinds; launch_dftx checks that on the host by calling pair_span itself, span_contiguous), and the
+// OKIND = 1 / 2 / 3 / 4 / 5: every block of the launch reads one contiguous span and writes one contiguous span of float frames /
+// of the planar fp64 rings / of float64 frames / of 16-bit / of 32-bit PCM frames (pair_span's kinds; launch_dftx checks that on the host by calling pair_span itself, span_contiguous), and the
 // kernel has no other path -- which is what lets the compiler count the stores between a load and its use;
 // OKIND = 0 (generic): any block, element-wise fifo addressing where a span is split
 // (ring wrap, a block half in the ring and half in the caller's buffer, odd channel count) -- same arithmetic, so which
@@ -129,7 +129,7 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
   c64 x[8];
   {
     const long long base = B * a.q;
-    const PairSpan sp = pair_span(in, pair, hasb, base, P, ca);
+    const PairSpan sp = pair_span<GENERIC>(in, pair, hasb, base, P, ca); // (integer frames are read by the generic instance only)
     if (sp.kind == 1) {
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
@@ -142,6 +142,9 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
         const double2 f = sp.d2[(tid + s * T8) * sp.fstride];
         x[s] = {f.x, f.y};
       }
+    } else if (GENERIC && sp.kind >= 4) { // integer PCM frames (span_load: the raw words first, then the conversions); the lean
+      // instances never see them: launch_dftx_t hands blocks that READ integer frames to the generic instance
+      span_load<8>(sp, tid, T8, x);
     } else if (sp.kind == 2) { // (pb == pa when the pair has one channel: every load is unconditional)
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
@@ -174,7 +177,7 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
   // ---- the L components, staged and stored two at a time
   const long long o0 = B * a.Vout;
   const bool whole = o0 >= a.clip_lo && o0 + a.Vout <= a.clip_hi;
-  const PairSpan so = whole ? pair_span(out, pair, hasb, a.out_offset + o0, a.Vout, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
+  const PairSpan so = whole ? pair_span<GENERIC || (OKIND >= 4)>(out, pair, hasb, a.out_offset + o0, a.Vout, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
   if (!GENERIC && so.kind != OKIND) __builtin_trap(); // the host's range check and pair_span disagree
   const double2 *__restrict__ Gt = a.Gr + tid;
   float2 keep[8];
@@ -196,22 +199,29 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
 #pragma unroll
       for (int s = 0; s < 8; ++s) g[s] = Gt[rn * P + s * T8];
     }
-    if ((GENERIC && so.kind == 1) || OKIND == 1) { // float frames, contiguous: the usual case
+    constexpr bool S32 = OKIND == 5;
+    if ((GENERIC && so.kind == 1) || OKIND == 1 || S32) { // 8-byte pair words, contiguous: float frames (the usual case), or
+      // 32-bit PCM frames -- the same LDS-staged stores, of the quantised integers carried through float2 as raw bits
+      auto word = [&](const c64 &c) {
+        return S32 ? make_float2(__int_as_float(pcm_out32(c.x)), __int_as_float(pcm_out32(c.y))) : make_float2((float)c.x, (float)c.y);
+      };
       // the even component's values wait in registers for the odd one; both go to the stage (element (n, r & 1) at
       // [2 n + (r & 1)], aliasing the exchange area while no transform runs) and leave it in linear order
       float2 *stg = reinterpret_cast<float2 *>(lds);
       if (!(r & 1)) {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) keep[s] = make_float2((float)v[s].x, (float)v[s].y);
+        for (int s = 0; s < 8; ++s) keep[s] = word(v[s]);
       } else {
 #pragma unroll
-        for (int s = 0; s < 8; ++s)
-          *reinterpret_cast<float4 *>(stg + 2 * (tid + s * T8)) = make_float4(keep[s].x, keep[s].y, (float)v[s].x, (float)v[s].y);
+        for (int s = 0; s < 8; ++s) {
+          const float2 w = word(v[s]);
+          *reinterpret_cast<float4 *>(stg + 2 * (tid + s * T8)) = make_float4(keep[s].x, keep[s].y, w.x, w.y);
+        }
         __syncthreads();
         // idx = tid + 256 j is element (n, c) = (idx >> 1, idx & 1): output m = LL n + (r - 1) + c = mb + 128 LL j
         const unsigned fbytes = 8u * (unsigned)so.fstride;
         const int mb = LL * (tid >> 1) + (tid & 1) + (r - 1);
-        char *const ob8 = reinterpret_cast<char *>(so.p2) + (unsigned)mb * fbytes;
+        char *const ob8 = (S32 ? reinterpret_cast<char *>(so.w32) : reinterpret_cast<char *>(so.p2)) + (unsigned)mb * fbytes;
         // Branch-free: a slot behind the block's last output repeats the store of the same lane's slot 8 earlier (same
         // value, same address), so that the number of stores is fixed and the wait for the filter values prefetched
         // above can leave all of them outstanding (s_waitcnt vmcnt(16) instead of vmcnt(0)).
@@ -235,6 +245,16 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
       for (int s = 0; s < 8; ++s) {
         const int m = LL * (tid + s * T8) + r;
         if (m < a.Vout) so.d2[m * so.fstride] = make_double2(v[s].x, v[s].y);
+      }
+    } else if ((GENERIC && so.kind >= 4) || OKIND == 4) { // 16-bit PCM frames, contiguous: one 4-byte store per output (and, in
+      // the generic instance, 32-bit ones: one 8-byte store)
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int m = LL * (tid + s * T8) + r;
+        if (m < a.Vout) {
+          if (OKIND == 4) so.w16[m * so.fstride] = pcm_pack16(v[s].x, v[s].y);
+          else so.puti(m, v[s].x, v[s].y);
+        }
       }
     } else if ((GENERIC && so.kind == 2) || OKIND == 2) { // planar fp64 rings, contiguous
 #pragma unroll
@@ -268,7 +288,7 @@ static bool span_contiguous(const AnyView &v, long long a0, long long len, int C
 {
   if (v.is_f32 && ((v.f.nch & 1) || (C & 1))) return false;
   const int npairs = C / 2, hp = v.is_f32 ? v.f.nch / 2 : npairs;
-  const int want = v.is_f32 == kFramesF64 ? 3 : v.is_f32 ? 1 : 2;
+  const int want = v.is_f32 == kFramesF64 ? 3 : v.is_f32 == kFramesS16 ? 4 : v.is_f32 == kFramesS32 ? 5 : v.is_f32 ? 1 : 2;
   for (int pair : {0, hp < npairs ? hp : 0, npairs - 1})
     if (pair_span(v, pair, true, a0, len).kind != want) return false;
   return true;
@@ -292,9 +312,10 @@ template <int LL> static hipError_t launch_dftx_t(const AnyView &in, const AnyVi
   b.npairs = pair_count(a.C, a.nchs);
   b.pps_magic = pair_magic(a.C, a.nchs);
   const bool clip_all = a.clip_lo <= a.B0 * (long long)a.Vout && (a.B0 + a.nblocks) * (long long)a.Vout <= a.clip_hi;
+  const bool int_in = in.is_f32 >= kFramesS16; // (a x4 / x8 stage that is the chain's first: the generic instance converts)
   auto fast = [&](int k) {
     const long long B = a.B0 + k;
-    return clip_all && span_contiguous(in, B * a.q, kP, a.C) && span_contiguous(out, a.out_offset + B * a.Vout, a.Vout, a.C);
+    return clip_all && !int_in && span_contiguous(in, B * a.q, kP, a.C) && span_contiguous(out, a.out_offset + B * a.Vout, a.Vout, a.C);
   };
   for (int k = 0; k < a.nblocks;) {
     const bool f = fast(k);
@@ -304,6 +325,8 @@ template <int LL> static hipError_t launch_dftx_t(const AnyView &in, const AnyVi
     b.nblocks = e - k;
     const hipError_t rc = !f ? launch_dftx_run<LL, 0>(in, out, b, st)
                          : out.is_f32 == kFramesF64 ? launch_dftx_run<LL, 3>(in, out, b, st)
+                         : out.is_f32 == kFramesS16 ? launch_dftx_run<LL, 4>(in, out, b, st)
+                         : out.is_f32 == kFramesS32 ? launch_dftx_run<LL, 5>(in, out, b, st)
                          : out.is_f32 ? launch_dftx_run<LL, 1>(in, out, b, st) : launch_dftx_run<LL, 2>(in, out, b, st);
     if (rc != hipSuccess) return rc;
     k = e;

@@ -85,7 +85,7 @@ int Engine::create(const Config &cfg, int nch, int nstreams, int device, Engine 
 {
   if (!out) return kInvParam;
   *out = nullptr;
-  if (fmt != 0 && fmt != 1) return kInvParam;
+  if (fmt != 0 && fmt != 1 && fmt != 16 && fmt != 32) return kInvParam;
   if (nch < 1 || nstreams < 1) return kInvParam;
   if ((long long)nch * nstreams > INT_MAX / 4096) return kNoMem; // parameter guard: more channels than any device could hold fifos for
   int dev_count = 0;
@@ -97,8 +97,9 @@ int Engine::create(const Config &cfg, int nch, int nstreams, int device, Engine 
   Engine *e = new (std::nothrow) Engine();
   if (!e) return kNoMem;
   e->device_ = device;
-  e->w_ = fmt ? 2 : 1;
-  e->fk_ = fmt ? kFramesF64 : kFramesF32;
+  e->fmt_ = fmt;
+  e->fk_ = fmt == 1 ? kFramesF64 : fmt == 16 ? kFramesS16 : fmt == 32 ? kFramesS32 : kFramesF32;
+  e->eb_ = frame_elem_bytes(e->fk_);
   int rc = e->init(cfg, nch, nstreams);
   if (rc != kOk) {
     delete e;
@@ -801,7 +802,7 @@ int Engine::ensure_ring(int f, long long live_needed)
   if (r.buf && r.cap >= live_needed) return kOk;
   { int rcj = join_side(); if (rcj) return rcj; } // seam kernels on the side stream may still write the old ring
   const long long cap = next_pow2(std::max<long long>({live_needed, r.cap * 2, 4096}));
-  const size_t bytes = r.f32 ? size_t(cap) * nch_ * S_ * w_ * sizeof(float) : size_t(cap) * C_ * sizeof(double);
+  const size_t bytes = r.f32 ? size_t(cap) * nch_ * S_ * size_t(eb_) : size_t(cap) * C_ * sizeof(double);
   void *nb = nullptr;
   ALLOC_TRY(&nb, bytes);
   HIP_TRY(hipMemsetAsync(nb, 0, bytes, stream_));
@@ -1112,8 +1113,8 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   // fp64 rings on either side) to the generic one.  At most three launches: generic head, lean middle, generic tail.
   int f0 = 0, f1 = 0;
   FastIo io = {};
-  io.dio = w_ == 2 ? 1 : 0;                  // float64 frames: the *_dio_kernel instances
-  const uintptr_t amask = 8 * uintptr_t(w_) - 1; // a channel pair of a frame as one 8- (16-) byte word
+  io.dio = fk_ - kFramesF32;                      // which instance: float32, float64 (*_dio), 16- / 32-bit PCM (*_s16 / *_s32)
+  const uintptr_t amask = 2 * uintptr_t(eb_) - 1; // a channel pair of a frame as one word of two samples
   auto io_in = [&] { // the caller's frames from in_abs0 on, fifo 0's ring below them
     io.in = ein.ptr;
     io.in_ring = static_cast<const float *>(rings_[0].buf);
@@ -1473,10 +1474,10 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
   if (poisoned_) return kInternal;
   if (!ibuf || !isamp) return kOk;
   if (isamp > plan_.isamp_max) isamp = plan_.isamp_max;
-  const size_t nw = size_t(nch_) * w_; // 4-byte words per frame
-  const size_t need = isamp * nw * size_t(S_);
-  const size_t row = isamp * nw * sizeof(float);
-  if (need * sizeof(float) <= kZeroCopyMaxBytes) {
+  const size_t fb = frame_bytes();
+  const size_t row = isamp * fb, need_bytes = row * size_t(S_); // bytes of one stream's frames / of the push
+  const size_t need = (need_bytes + 3) / 4;                     // the same in 4-byte words, rounded up
+  if (need_bytes <= kZeroCopyMaxBytes) {
     // plugin-sized push: the kernels read it in place from the page-locked slot; the slot is released by an event behind the
     // push's last kernel (two slots alternate, so this only ever waits for the push before the previous one)
     Pinned &slot = pin_in_[pin_k_ ^= 1];
@@ -1486,7 +1487,7 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
     }
     int rp = pinned_reserve(slot, need);
     if (rp) return rp;
-    for (int s = 0; s < S_; ++s) std::memcpy(slot.p + size_t(s) * isamp * nw, ibuf + size_t(s) * stream_stride * nw, row);
+    for (int s = 0; s < S_; ++s) std::memcpy(at_bytes(slot.p, size_t(s) * row), at_bytes(ibuf, size_t(s) * stream_stride * fb), row);
     // mirror the output when the fifo is empty (the plugin pulls until it is): the exact number of frames this push makes
     // available comes from a dry run of the counters
     float *mir = nullptr;
@@ -1502,8 +1503,8 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
         done += n;
       }
       cap = size_t(trial.wr.back() - trial.rd.back());
-      if (cap && cap * nw * size_t(S_) * sizeof(float) <= kZeroCopyMaxBytes) {
-        int rm = pinned_reserve(pin_mir_, cap * nw * size_t(S_));
+      if (cap && cap * fb * size_t(S_) <= kZeroCopyMaxBytes) {
+        int rm = pinned_reserve(pin_mir_, (cap * fb * size_t(S_) + 3) / 4);
         if (rm) return rm;
         mir = pin_mir_.p;
       }
@@ -1531,7 +1532,7 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
     ALLOC_TRY(&d_stage_, need * sizeof(float));
     stage_floats_ = need;
   }
-  if (need * sizeof(float) <= kPinnedMaxBytes) {
+  if (need_bytes <= kPinnedMaxBytes) {
     Pinned &slot = pin_in_[pin_k_ ^= 1];
     if (slot.pending) { // the copy that last used this slot (two pushes ago) must have left it
       HIP_TRY(hipEventSynchronize(slot.done));
@@ -1539,12 +1540,12 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
     }
     int rp = pinned_reserve(slot, need);
     if (rp) return rp;
-    for (int s = 0; s < S_; ++s) std::memcpy(slot.p + size_t(s) * isamp * nw, ibuf + size_t(s) * stream_stride * nw, row);
-    HIP_TRY(hipMemcpyAsync(d_stage_, slot.p, need * sizeof(float), hipMemcpyHostToDevice, stream_));
+    for (int s = 0; s < S_; ++s) std::memcpy(at_bytes(slot.p, size_t(s) * row), at_bytes(ibuf, size_t(s) * stream_stride * fb), row);
+    HIP_TRY(hipMemcpyAsync(d_stage_, slot.p, need_bytes, hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipEventRecord(slot.done, stream_));
     slot.pending = true;
   } else if (S_ == 1) HIP_TRY(hipMemcpyAsync(d_stage_, ibuf, row, hipMemcpyHostToDevice, stream_));
-  else HIP_TRY(hipMemcpy2DAsync(d_stage_, row, ibuf, stream_stride * nw * sizeof(float), row, S_, hipMemcpyHostToDevice, stream_));
+  else HIP_TRY(hipMemcpy2DAsync(d_stage_, row, ibuf, stream_stride * fb, row, S_, hipMemcpyHostToDevice, stream_));
   return feed(d_stage_, isamp, isamp, nullptr, 0, 0, nullptr);
 }
 
@@ -1555,28 +1556,28 @@ int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_ho
   const Ring &r = rings_[f];
   const long long rd = book_.rd[f];
   if (to_host) {
-    const size_t nw = size_t(nch_) * w_; // 4-byte words per frame
-    const size_t total = frames * nw * size_t(S_) * sizeof(float);
+    const size_t fb = frame_bytes();
+    const size_t total = frames * fb * size_t(S_);
     const bool pinned = total <= kPinnedMaxBytes;
     if (pinned) {
-      int rp = pinned_reserve(pin_out_, total / sizeof(float));
+      int rp = pinned_reserve(pin_out_, (total + 3) / 4);
       if (rp) return rp;
     }
     size_t done = 0;
     while (done < frames) { // at most two segments (ring wrap)
       const long long pos = (rd + (long long)done) & (r.cap - 1);
       const size_t n = std::min<size_t>(frames - done, size_t(r.cap - pos));
-      const size_t row = n * nw * sizeof(float);
-      const float *src = static_cast<const float *>(r.buf) + pos * nw;
-      float *d = pinned ? pin_out_.p + done * nw : dst + done * nw;
-      const size_t dpitch = (pinned ? frames : stride_frames) * nw * sizeof(float);
-      HIP_TRY(hipMemcpy2DAsync(d, dpitch, src, size_t(r.cap) * nw * sizeof(float), row, S_, hipMemcpyDeviceToHost, stream_));
+      const size_t row = n * fb;
+      const float *src = at_bytes(static_cast<const float *>(r.buf), size_t(pos) * fb);
+      float *d = at_bytes(pinned ? pin_out_.p : dst, done * fb);
+      const size_t dpitch = (pinned ? frames : stride_frames) * fb;
+      HIP_TRY(hipMemcpy2DAsync(d, dpitch, src, size_t(r.cap) * fb, row, S_, hipMemcpyDeviceToHost, stream_));
       done += n;
     }
     HIP_TRY(hipStreamSynchronize(stream_));
     if (pinned)
       for (int s = 0; s < S_; ++s)
-        std::memcpy(dst + size_t(s) * stride_frames * nw, pin_out_.p + size_t(s) * frames * nw, frames * nw * sizeof(float));
+        std::memcpy(at_bytes(dst, size_t(s) * stride_frames * fb), at_bytes(pin_out_.p, size_t(s) * frames * fb), frames * fb);
     free_garbage(); // everything queued before this point has finished: retired rings / drain buffers can go
   } else {
     ExtOut eo;
@@ -1610,10 +1611,10 @@ int Engine::pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *o
         HIP_TRY(hipEventSynchronize(pin_mir_.done));
         pin_mir_.pending = false;
       }
-      const size_t dstride = S_ > 1 ? stream_stride : n, nw = size_t(nch_) * w_;
+      const size_t dstride = S_ > 1 ? stream_stride : n, fb = frame_bytes();
       for (int s = 0; s < S_; ++s)
-        std::memcpy(obuf + size_t(s) * dstride * nw, pin_mir_.p + (size_t(s) * mir_stride_ + size_t(rd - mir_begin_)) * nw,
-                    n * nw * sizeof(float));
+        std::memcpy(at_bytes(obuf, size_t(s) * dstride * fb), at_bytes(pin_mir_.p, (size_t(s) * mir_stride_ + size_t(rd - mir_begin_)) * fb),
+                    n * fb);
       if (rd + (long long)n == mir_end_) mir_begin_ = mir_end_ = 0;
     } else {
       if (mir_end_ > mir_begin_) { // the request reaches past the mirror: the device ring takes what is left of it first
@@ -1665,7 +1666,7 @@ int Engine::flow_host(const float *ibuf, size_t in_stride, float *obuf, size_t o
   int rc = pull_host(obuf, out_stride, osamp, &n1);
   if (rc) return rc;
   if (isamp && (rc = push_host(ibuf, in_stride, isamp))) return rc;
-  if (n1 < osamp && obuf && (rc = pull_host(obuf + n1 * nch_ * w_, out_stride, osamp - n1, &n2))) return rc;
+  if (n1 < osamp && obuf && (rc = pull_host(at_bytes(obuf, n1 * frame_bytes()), out_stride, osamp - n1, &n2))) return rc;
   if (iused) *iused = isamp;
   if (ogen) *ogen = n1 + n2;
   return kOk;
@@ -1682,7 +1683,7 @@ int Engine::flow_device(const float *ibuf, size_t in_stride, float *obuf, size_t
   if (rc) return rc;
   if (isamp) {
     // frames produced by this push land directly in the caller's buffer (no ring round trip)
-    float *direct = obuf && n1 < osamp ? obuf + n1 * nch_ * w_ : nullptr;
+    float *direct = obuf && n1 < osamp ? at_bytes(obuf, n1 * frame_bytes()) : nullptr;
     rc = feed(ibuf, S_ > 1 ? in_stride : isamp, isamp, direct, S_ > 1 ? out_stride : osamp, direct ? osamp - n1 : 0, &n2);
     if (rc) return rc;
     if (direct && !n2 && available() && n1 < osamp) { // the ring was not empty: fall back to a copy
@@ -1714,13 +1715,13 @@ int Engine::drain()
     if (++blocks > (1u << 20)) return fail(kInternal);
   }
   if (blocks) {
-    const size_t frames = blocks * 1024, floats = frames * size_t(nch_) * w_ * size_t(S_); // (all-zero bits: 0.0 in either format)
+    const size_t frames = blocks * 1024, zbytes = frames * frame_bytes() * size_t(S_); // (all-zero bits: silence in every format)
     float *zeros = nullptr;
-    ALLOC_TRY(&zeros, floats * sizeof(float));
-    HIP_TRY(hipMemsetAsync(zeros, 0, floats * sizeof(float), stream_));
+    ALLOC_TRY(&zeros, zbytes);
+    HIP_TRY(hipMemsetAsync(zeros, 0, zbytes, stream_));
     // feed them one reference block at a time so that the counter wrap in rate_input sees the same sequence
     for (size_t k = 0; k < blocks; ++k) {
-      int rc = feed(zeros + k * 1024 * nch_ * w_, frames, 1024, nullptr, 0, 0, nullptr);
+      int rc = feed(at_bytes(zeros, k * 1024 * frame_bytes()), frames, 1024, nullptr, 0, 0, nullptr);
       if (rc) { garbage_.push_back(zeros); return fail(rc); }
     }
     garbage_.push_back(zeros);

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace rsmp {
@@ -58,12 +59,13 @@ class Engine {
 public:
   // device: HIP device index the handle lives on; -1 = the calling thread's current device.  kInvParam for an index the
   // process does not have, kUninit for a device that is not gfx950.
-  // fmt: 0 = interleaved float32 frames at both ends, 1 = interleaved float64 frames (RRX_FMT_*); fixed for the handle's life
+  // fmt: 0 = interleaved float32 frames at both ends, 1 = float64 frames, 16 / 32 = signed 16- / 32-bit PCM frames (RRX_FMT_*);
+  // fixed for the handle's life
   static int create(const Config &cfg, int nch, int nstreams, int device, Engine **out, int fmt = 0);
   ~Engine();
 
   int device() const { return device_; }
-  int format() const { return w_ == 2 ? 1 : 0; }
+  int format() const { return fmt_; }
 
   const ChainPlan &plan() const { return plan_; }
   int nch() const { return nch_; }
@@ -84,8 +86,8 @@ public:
   static void fail_alloc_after(int n);
 
   // Host-memory API (RR_push / RR_pull / RR_flow semantics). Buffers: [stream][frame][channel] of the handle's sample
-  // format (float, or double behind a float pointer on a format-1 handle: the pointers are only ever moved in 4-byte words)
-  // with
+  // format (float, or double / short / int behind a float pointer on a handle of another format: the pointers are only ever
+  // moved as raw bytes, eb_ per sample) with
   // `stream_stride` frames between streams (ignored when there is one stream).
   int push_host(const float *ibuf, size_t stream_stride, size_t isamp);
   int pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *ogen);
@@ -113,17 +115,25 @@ private:
   int init_fused_pair(int i, size_t &slab_cap);
   int init_polymf(int i);
   void size_slabs(size_t fused_slab_cap);
-  // Sample format of fifo 0 and the last fifo (the intermediate fifos are fp64 rings either way): w_ = 4-byte words per
-  // sample (1: float32 frames, 2: float64 frames), fk_ = the frame kind the kernels see (kFramesF32 / kFramesF64).  Host
-  // code moves frames as w_ * nch_ floats; kernel views and FastIo count samples.
-  int w_ = 1, fk_ = kFramesF32;
+  // Sample format of fifo 0 and the last fifo (the intermediate fifos are fp64 rings either way): fmt_ = RRX_FMT_*, eb_ = bytes
+  // per sample (4: float32, 8: float64, 2: 16-bit PCM, 4: 32-bit PCM), fk_ = the frame kind the kernels see (kFramesF32 ...).
+  // Host code moves frames as raw memory, eb_ * nch_ bytes each (with 16-bit PCM and an odd channel count not a multiple of 4:
+  // every copy is exact to 2 bytes); kernel views and FastIo count samples.
+  int fmt_ = 0, eb_ = 4, fk_ = kFramesF32;
+  size_t frame_bytes() const { return size_t(nch_) * size_t(eb_); }
+  // a frame pointer advanced by whole frames / samples (the float type is only a handle: see push_host)
+  template <class T> T *at_bytes(T *p, size_t bytes) const
+  {
+    typedef typename std::conditional<std::is_const<T>::value, const char, char>::type B;
+    return reinterpret_cast<T *>(reinterpret_cast<B *>(p) + bytes);
+  }
 
   struct Ring { // device ring of fifo f
     void *buf = nullptr;
     long long cap = 0; // items (f64) or frames (f32: caller-facing frames of either format), power of two
     bool f32 = false;
   };
-  // caller buffers at the two ends; stride_elems = samples (floats or doubles, the handle's format) between streams
+  // caller buffers at the two ends; stride_elems = samples (of the handle's format) between streams
   struct ExtIn { const float *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
   struct ExtOut { float *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
 
@@ -210,7 +220,8 @@ private:
   // into page-locked memory on the CPU, so the H2D copy is a true asynchronous DMA and a push returns without waiting for
   // the device; two input slots alternate, each guarded by an event recorded behind its copy.  Pushes larger than
   // kPinnedMaxBytes keep the direct (runtime-staged) path.
-  struct Pinned { float *p = nullptr; size_t floats = 0; hipEvent_t done = nullptr; bool pending = false; };
+  struct Pinned { float *p = nullptr; size_t floats = 0; // (sized in 4-byte words, used as raw bytes)
+                  hipEvent_t done = nullptr; bool pending = false; };
   Pinned pin_in_[2], pin_out_;
   int pin_k_ = 0;
   static constexpr size_t kPinnedMaxBytes = size_t(64) << 20;

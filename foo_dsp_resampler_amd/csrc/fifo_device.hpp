@@ -4,9 +4,9 @@
 
 namespace rsmp {
 
-// is_f32: kFramesF32 / kFramesF64 = interleaved frames (F32View; with kFramesF64 its ring / ext pointers address doubles
-// and its strides count doubles), 0 = planar fp64 rings (F64View).  Frames of either width are the caller-facing ends
-// (stage-0 input, final output); every test of `is_f32` as a truth value means "frames".
+// is_f32: kFramesF32 / kFramesF64 / kFramesS16 / kFramesS32 = interleaved frames (F32View; its ring / ext pointers address
+// samples of that type and its strides count samples), 0 = planar fp64 rings (F64View).  Frames of any type are the
+// caller-facing ends (stage-0 input, final output); every test of `is_f32` as a truth value means "frames".
 struct AnyView {
   int is_f32;
   F32View f;
@@ -15,7 +15,7 @@ struct AnyView {
 
 struct ChanRef { // per-channel precomputed addressing
   int is_f32; // as AnyView::is_f32
-  // frames (with kFramesF64 the two pointers address doubles)
+  // frames (the two pointers address samples of the frame kind's type)
   const float *ring32;
   const float *ext32;
   long long mask32, ext_begin, ext_end;
@@ -34,6 +34,9 @@ __device__ __forceinline__ ChanRef chan_ref(const AnyView &v, int c)
     if (v.is_f32 == kFramesF64) { // (the same element offsets, in doubles)
       r.ring32 = reinterpret_cast<const float *>(reinterpret_cast<const double *>(v.f.ring) + s * v.f.ring_stream_stride + ch);
       r.ext32 = v.f.ext ? reinterpret_cast<const float *>(reinterpret_cast<const double *>(v.f.ext) + s * v.f.ext_stream_stride + ch) : nullptr;
+    } else if (v.is_f32 == kFramesS16) { // (in shorts)
+      r.ring32 = reinterpret_cast<const float *>(reinterpret_cast<const short *>(v.f.ring) + s * v.f.ring_stream_stride + ch);
+      r.ext32 = v.f.ext ? reinterpret_cast<const float *>(reinterpret_cast<const short *>(v.f.ext) + s * v.f.ext_stream_stride + ch) : nullptr;
     } else {
       r.ring32 = v.f.ring + s * v.f.ring_stream_stride + ch;
       r.ext32 = v.f.ext ? v.f.ext + s * v.f.ext_stream_stride + ch : nullptr;
@@ -61,6 +64,13 @@ __device__ __forceinline__ double fifo_get(const ChanRef &r, long long a)
     if (e && a >= r.ext_begin && a < r.ext_end) return e[(a - r.ext_begin) * r.nch];
     return g[(a & r.mask32) * r.nch];
   }
+  if (r.is_f32 >= kFramesS16) { // integer PCM frames: convert on load
+    const bool in_ext = r.ext32 && a >= r.ext_begin && a < r.ext_end;
+    const long long i = in_ext ? (a - r.ext_begin) * r.nch : (a & r.mask32) * r.nch;
+    const float *base = in_ext ? r.ext32 : r.ring32;
+    if (r.is_f32 == kFramesS16) return pcm_in(reinterpret_cast<const short *>(base)[i]);
+    return pcm_in(reinterpret_cast<const int *>(base)[i]);
+  }
   if (r.is_f32) {
     if (r.ext32 && a >= r.ext_begin && a < r.ext_end) return (double)r.ext32[(a - r.ext_begin) * r.nch];
     return (double)r.ring32[(a & r.mask32) * r.nch];
@@ -74,6 +84,12 @@ __device__ __forceinline__ void fifo_put(const ChanRef &r, long long a, double v
     double *e = reinterpret_cast<double *>(const_cast<float *>(r.ext32)), *g = reinterpret_cast<double *>(const_cast<float *>(r.ring32));
     if (e && a >= r.ext_begin && a < r.ext_end) e[(a - r.ext_begin) * r.nch] = v;
     else g[(a & r.mask32) * r.nch] = v;
+  } else if (r.is_f32 >= kFramesS16) { // integer PCM frames: quantise on store
+    const bool in_ext = r.ext32 && a >= r.ext_begin && a < r.ext_end;
+    const long long i = in_ext ? (a - r.ext_begin) * r.nch : (a & r.mask32) * r.nch;
+    float *base = const_cast<float *>(in_ext ? r.ext32 : r.ring32);
+    if (r.is_f32 == kFramesS16) reinterpret_cast<short *>(base)[i] = pcm_out16(v);
+    else reinterpret_cast<int *>(base)[i] = pcm_out32(v);
   } else if (r.is_f32) {
     if (r.ext32 && a >= r.ext_begin && a < r.ext_end) const_cast<float *>(r.ext32)[(a - r.ext_begin) * r.nch] = (float)v;
     else const_cast<float *>(r.ring32)[(a & r.mask32) * r.nch] = (float)v;
@@ -84,16 +100,23 @@ __device__ __forceinline__ void fifo_put(const ChanRef &r, long long a, double v
 
 // `len` consecutive samples of ONE channel starting at absolute index a0, when they lie contiguously in one buffer:
 // kind 1 = float32 frames (element i at p32[i * stride32]), kind 2 = the channel's fp64 ring, kind 3 = float64 frames
-// (element i at p64[i * stride32]), kind 0 = split (fifo_get).
+// (element i at p64[i * stride32]), kind 4 / 5 = 16- / 32-bit PCM frames (element i at p16 / pi32 [i * stride32], through
+// get()), kind 0 = split (fifo_get).
 struct ChanSpan {
   int kind;
   const float *p32;
   long long stride32;
   const double *p64;
+  const short *p16;
+  const int *pi32;
+  __device__ __forceinline__ double geti(long long i) const // kinds 4 / 5
+  {
+    return kind == 4 ? pcm_in(p16[i * stride32]) : pcm_in(pi32[i * stride32]);
+  }
 };
 __device__ __forceinline__ ChanSpan chan_span(const AnyView &v, int c, long long a0, long long len)
 {
-  ChanSpan r = {0, nullptr, 1, nullptr};
+  ChanSpan r = {0, nullptr, 1, nullptr, nullptr, nullptr};
   if (v.is_f32) {
     const int s = c / v.f.nch, ch = c - s * v.f.nch;
     r.stride32 = v.f.nch;
@@ -110,6 +133,12 @@ __device__ __forceinline__ ChanSpan chan_span(const AnyView &v, int c, long long
       if (v.is_f32 == kFramesF64) {
         r.kind = 3;
         r.p64 = reinterpret_cast<const double *>(base) + off;
+      } else if (v.is_f32 == kFramesS16) {
+        r.kind = 4;
+        r.p16 = reinterpret_cast<const short *>(base) + off;
+      } else if (v.is_f32 == kFramesS32) {
+        r.kind = 5;
+        r.pi32 = reinterpret_cast<const int *>(base) + off;
       } else {
         r.kind = 1;
         r.p32 = base + off;
@@ -145,15 +174,36 @@ __device__ __forceinline__ PairCh pair_channels(int pair, int C, int nchs, unsig
 
 // Direct addressing of `len` consecutive samples of channel pair (2*pair, 2*pair+1) starting at absolute index a0,
 // when they lie contiguously in one buffer: kind 1 = float32 frames with the two channels side by side (one 8-byte
-// word per sample), kind 2 = the two planar fp64 rings, kind 3 = float64 frames (one 16-byte word per sample), kind 0 = not
-// contiguous (use fifo_get / fifo_put).
+// word per sample), kind 2 = the two planar fp64 rings, kind 3 = float64 frames (one 16-byte word per sample), kind 4 = 16-bit
+// PCM frames (one 4-byte word per sample), kind 5 = 32-bit PCM frames (one 8-byte word), kind 0 = not contiguous (use
+// fifo_get / fifo_put).  The pair words of kinds 4 and 5 convert on load and quantise on store (pcm_in / pcm_out*).
 struct PairSpan {
   int kind;
   float2 *p2;
-  long long fstride; // float2 (kind 3: double2) elements between consecutive frames
+  long long fstride; // pair words (float2; kind 3: double2, kind 4: unsigned, kind 5: int2) between consecutive frames
   double *pa, *pb;
   bool hasb;
   double2 *d2;       // kind 3 = float64 frames with the two channels side by side (one 16-byte word per sample)
+  unsigned *w16;     // kind 4
+  int2 *w32;         // kind 5
+  // kinds 4 / 5: pair word i
+  __device__ __forceinline__ void geti(long long i, double &x, double &y) const
+  {
+    if (kind == 4) {
+      const unsigned w = w16[i * fstride];
+      x = pcm_lo16(w);
+      y = pcm_hi16(w);
+    } else {
+      const int2 w = w32[i * fstride];
+      x = pcm_in(w.x);
+      y = pcm_in(w.y);
+    }
+  }
+  __device__ __forceinline__ void puti(long long i, double x, double y) const
+  {
+    if (kind == 4) w16[i * fstride] = pcm_pack16(x, y);
+    else w32[i * fstride] = make_int2(pcm_out32(x), pcm_out32(y));
+  }
   __device__ __forceinline__ void get(int i, double &x, double &y) const
   {
     if (kind == 1) {
@@ -164,6 +214,8 @@ struct PairSpan {
       const double2 f = d2[i * fstride];
       x = f.x;
       y = f.y;
+    } else if (kind >= 4) {
+      geti(i, x, y);
     } else {
       x = pa[i];
       y = hasb ? pb[i] : 0.0;
@@ -173,6 +225,7 @@ struct PairSpan {
   {
     if (kind == 1) p2[i * fstride] = make_float2((float)x, (float)y);
     else if (kind == 3) d2[i * fstride] = make_double2(x, y);
+    else if (kind >= 4) puti(i, x, y);
     else {
       pa[i] = x;
       if (hasb) pb[i] = y;
@@ -199,6 +252,24 @@ template <int NPTS, typename CT> __device__ __forceinline__ void span_load(const
       dst[s].x = f.x;
       dst[s].y = f.y;
     }
+  } else if (sp.kind == 4) { // (the raw words first: every load issues before the first conversion waits)
+    unsigned w[NPTS];
+#pragma unroll
+    for (int s = 0; s < NPTS; ++s) w[s] = sp.w16[(i0 + s * istride) * sp.fstride];
+#pragma unroll
+    for (int s = 0; s < NPTS; ++s) {
+      dst[s].x = pcm_lo16(w[s]);
+      dst[s].y = pcm_hi16(w[s]);
+    }
+  } else if (sp.kind == 5) {
+    int2 w[NPTS];
+#pragma unroll
+    for (int s = 0; s < NPTS; ++s) w[s] = sp.w32[(i0 + s * istride) * sp.fstride];
+#pragma unroll
+    for (int s = 0; s < NPTS; ++s) {
+      dst[s].x = pcm_in(w[s].x);
+      dst[s].y = pcm_in(w[s].y);
+    }
   } else { // (pair_span sets pb = pa for a one-channel pair: both loads are unconditional)
 #pragma unroll
     for (int s = 0; s < NPTS; ++s) {
@@ -213,6 +284,9 @@ template <int NPTS, typename CT> __device__ __forceinline__ void span_load(const
 }
 
 // (__host__ too: the launchers that pick a lean kernel instance ask this very function, not a copy of its predicate)
+// INTS = false: for callers that are never handed integer PCM frames (the lean dftx instances; their launcher sees to it) --
+// the integer branch is then not even compiled, and the function is instruction for instruction what it was without it.
+template <bool INTS = true>
 __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pair, bool hasb, long long a0, long long len, int ca = -1)
 {
   if (ca < 0) ca = 2 * pair; // (pair_channels: differs only with an odd channel count per stream, where float frames are never contiguous pairs)
@@ -223,7 +297,29 @@ __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pai
   r.pa = r.pb = nullptr;
   r.hasb = hasb;
   r.d2 = nullptr;
-  if (v.is_f32 == kFramesF64) { // as below, in doubles; a pair is 16-byte aligned or not taken
+  r.w16 = nullptr;
+  r.w32 = nullptr;
+  if (INTS && v.is_f32 >= kFramesS16) { // as below, in shorts / ints; a pair is aligned as one word (4 / 8 bytes) or not taken
+    if (hasb && !(v.f.nch & 1)) {
+      const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp, eb = frame_elem_bytes(v.is_f32);
+      const char *ext = reinterpret_cast<const char *>(v.f.ext), *ring = reinterpret_cast<const char *>(v.f.ring);
+      const char *p = nullptr;
+      if (ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end)
+        p = ext + (strm * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + 2 * pin) * eb;
+      else if ((!ext || a0 + len <= v.f.ext_begin || a0 >= v.f.ext_end) && (a0 & v.f.ring_mask) + len <= v.f.ring_mask + 1)
+        p = ring + (strm * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + 2 * pin) * eb;
+      if (p && (reinterpret_cast<unsigned long long>(p) & (2 * eb - 1)) == 0) {
+        r.fstride = hp;
+        if (v.is_f32 == kFramesS16) {
+          r.kind = 4;
+          r.w16 = reinterpret_cast<unsigned *>(const_cast<char *>(p));
+        } else {
+          r.kind = 5;
+          r.w32 = reinterpret_cast<int2 *>(const_cast<char *>(p));
+        }
+      }
+    }
+  } else if (v.is_f32 == kFramesF64) { // as below, in doubles; a pair is 16-byte aligned or not taken
     if (hasb && !(v.f.nch & 1)) {
       const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
       const double *ext = reinterpret_cast<const double *>(v.f.ext), *ring = reinterpret_cast<const double *>(v.f.ring);
@@ -299,7 +395,7 @@ inline int frame_pairs(const AnyView &in, const AnyView &out, int C)
   return v->f.nch / 2;
 }
 
-// frames: 0 = the fp64 rings `d`, kFramesF32 / kFramesF64 = the frames `f` (the launchers' src_f32 / dst_f32 arguments)
+// frames: 0 = the fp64 rings `d`, a frame kind (kFramesF32 ...) = the frames `f` (the launchers' src_f32 / dst_f32 arguments)
 inline AnyView make_view(int frames, const F32View &f, const F64View &d)
 {
   AnyView v;

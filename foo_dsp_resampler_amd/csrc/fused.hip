@@ -149,8 +149,9 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           p2 = reinterpret_cast<const float2 *>(p);
         }
       }
-      // float64 frames: the same pairs as one 16-byte word per sample (pair_span kind 3), else element-wise
-      const PairSpan d64 = in.is_f32 == kFramesF64 ? pair_span(in, pair, hasb, e0, P, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
+      // float64 / integer PCM frames: the same pairs as one 16- / 4- / 8-byte word per sample (pair_span kinds 3 / 4 / 5), else
+      // element-wise
+      const PairSpan d64 = in.is_f32 >= kFramesF64 ? pair_span(in, pair, hasb, e0, P, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
       if constexpr (FWD8) { // every thread takes 8 points of the P-point forward transform: x[tid + s*T], T = P/8
         if (fast) {
 #pragma unroll
@@ -164,6 +165,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             const double2 f = d64.d2[(tid + s * T) * d64.fstride];
             u8[s] = {f.x, f.y};
           }
+        } else if (d64.kind >= 4) {
+          span_load<8>(d64, tid, T, u8);
         } else {
           const ChanRef ia = chan_ref(in, ca), ib = chan_ref(in, hasb ? cb : ca);
 #pragma unroll
@@ -182,7 +185,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           }
         } else {
           const PairSpan sp = in.is_f32 == kFramesF32 ? PairSpan{0, nullptr, 1, nullptr, nullptr, hasb} : in.is_f32 ? d64 : pair_span(in, pair, hasb, e0, P, ca);
-          if (sp.kind) { // planar fp64 rings (the producer is another stage) or float64 frames, block contiguous
+          if (sp.kind) { // planar fp64 rings (the producer is another stage), float64 or integer PCM frames, block contiguous
             span_load<16>(sp, tid, TF, v);
           } else {
             const ChanRef ia = chan_ref(in, ca), ib = chan_ref(in, hasb ? cb : ca);
@@ -333,7 +336,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       bool ofast = false;
       char *obase = nullptr;  // frame i_lo's first sample of this pair
       int ofs = 2;            // samples between consecutive frames
-      const int esz = out.is_f32 == kFramesF64 ? 8 : 4; // bytes per sample of the destination frames
+      const int esz = frame_elem_bytes(out.is_f32); // bytes per sample of the destination frames
       {
         const long long o0 = a.out_offset2 + fb.i_lo, o1 = o0 + fb.cnt;
         if (out.is_f32 && hasb && !(out.f.nch & 1)) {
@@ -350,14 +353,15 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & (2 * esz - 1)) == 0;
         }
       }
-      // The whole two-round sequence is instantiated three times and chosen by one uniform branch: FAST writes
-      // float2 (DBL: double2) frames at obase + 32-bit offsets and keeps none of the generic fifo addressing state alive
+      // The whole two-round sequence is instantiated once per store form and chosen by one uniform branch: FAST writes
+      // float2 (DBL: double2, MODE 3 / 4: quantised 16- / 32-bit PCM pair words) frames at obase + 32-bit offsets and keeps none of the generic fifo addressing state alive
       // (that state is what used to spill scalar registers inside the loop).
       auto both_rounds = [&](auto fast_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value != 0, DBL = decltype(fast_tag)::value == 2;
+        constexpr int MODE = decltype(fast_tag)::value;
+        constexpr bool FAST = MODE != 0, DBL = MODE == 2;
         const ChanRef oa = chan_ref(out, ca), ob = chan_ref(out, hasb ? cb : ca); // dead code when FAST
         char *const obytes = obase;
-        const int frame_bytes = ofs * (DBL ? 8 : 4), period4_bytes = 4 * pl * frame_bytes; // output bytes per frame / per column step
+        const int frame_bytes = ofs * (DBL ? 8 : MODE == 3 ? 2 : 4), period4_bytes = 4 * pl * frame_bytes; // output bytes per frame / per column step
 
         // A operands are double-buffered: the next item's tile is in flight (L2 latency) while this one computes
         double cn_[SPAN];
@@ -380,7 +384,11 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           const int ib = pend_ib + u * 4 * pl;
           if (((pend_allv >> u) & 1) || (ib >= fb.irel_lo && ib < pend_hi)) {
             const int orel = ib - fb.irel_lo;
-            if (DBL) {
+            if (MODE == 3) {
+              *reinterpret_cast<unsigned *>(obytes + (pend_off + u * period4_bytes)) = pcm_pack16(pA[u], pB[u]);
+            } else if (MODE == 4) {
+              *reinterpret_cast<int2 *>(obytes + (pend_off + u * period4_bytes)) = make_int2(pcm_out32(pA[u]), pcm_out32(pB[u]));
+            } else if (DBL) {
               *reinterpret_cast<double2 *>(obytes + (pend_off + u * period4_bytes)) = make_double2(pA[u], pB[u]);
             } else if (FAST) {
               *reinterpret_cast<float2 *>(obytes + (pend_off + u * period4_bytes)) = make_float2((float)pA[u], (float)pB[u]);
@@ -397,7 +405,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             // Two column steps whose 2 x 64 outputs are all stored, stereo frames: lane rows hi and hi^1 hold adjacent
             // frames, so after a v_permlane16_swap even rows own two adjacent frames of step u and odd rows two of
             // step u+1 -- one 16-byte store per lane instead of two 8-byte ones (a store costs a wave ~390 cycles here).
-            if (FAST && !DBL && ofs == 2 && u + 1 < pend_n && ((pend_allv >> u) & 3) == 3) {
+            if (MODE == 1 && ofs == 2 && u + 1 < pend_n && ((pend_allv >> u) & 3) == 3) {
               typedef unsigned u2v __attribute__((ext_vector_type(2)));
               const u2v sA = __builtin_amdgcn_permlane16_swap(__float_as_uint((float)pA[u]), __float_as_uint((float)pA[u + 1]), false, false);
               const u2v sB = __builtin_amdgcn_permlane16_swap(__float_as_uint((float)pB[u]), __float_as_uint((float)pB[u + 1]), false, false);
@@ -521,6 +529,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
         flush();
       };
       if (ofast && esz == 8) both_rounds(std::integral_constant<int, 2>{});
+      else if (ofast && out.is_f32 == kFramesS16) both_rounds(std::integral_constant<int, 3>{});
+      else if (ofast && out.is_f32 == kFramesS32) both_rounds(std::integral_constant<int, 4>{});
       else if (ofast) both_rounds(std::integral_constant<int, 1>{});
       else both_rounds(std::integral_constant<int, 0>{});
     } else
@@ -534,8 +544,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       bool ofast = false;
       float *obase = nullptr; // points at frame i_lo's first float of this pair
       int ostride = 1;        // float2 elements between consecutive frames
-      // float64 frames: pair_span's kind 3 over the block's outputs (one 16-byte store per output)
-      const PairSpan o64 = out.is_f32 == kFramesF64 ? pair_span(out, pair, hasb, a.out_offset2 + fb.i_lo, fb.cnt, ca)
+      // float64 / integer PCM frames: pair_span's kinds 3 / 4 / 5 over the block's outputs (one pair-word store per output)
+      const PairSpan o64 = out.is_f32 >= kFramesF64 ? pair_span(out, pair, hasb, a.out_offset2 + fb.i_lo, fb.cnt, ca)
                                                     : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
       {
         const long long o0 = a.out_offset2 + fb.i_lo, o1 = o0 + fb.cnt;
@@ -592,6 +602,10 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
 #pragma unroll
           for (int g = 0; g < G; ++g)
             if (ok[g]) o64.d2[(orel + g) * o64.fstride] = make_double2(accA[g], accB[g]);
+        } else if (o64.kind >= 4) {
+#pragma unroll
+          for (int g = 0; g < G; ++g)
+            if (ok[g]) o64.puti(orel + g, accA[g], accB[g]);
         } else {
           const ChanRef oa = chan_ref(out, ca), ob = chan_ref(out, hasb ? cb : ca);
           const long long oabs = a.out_offset2 + fb.i_lo + orel;

@@ -23,6 +23,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstdio>
+#include <type_traits>
 
 #ifndef RSMP_FAST_FWD8
 #define RSMP_FAST_FWD8 1
@@ -67,10 +68,30 @@ namespace {
 typedef double rsmp_d2v __attribute__((ext_vector_type(2)));
 typedef unsigned int rsmp_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned int rsmp_v4u __attribute__((ext_vector_type(4)));
-// a frame's two samples of one channel pair as one word: 8 bytes of float32 frames, 16 bytes of float64 frames
-template <typename E> struct Pair2;
-template <> struct Pair2<float> { typedef float2 T; };
-template <> struct Pair2<double> { typedef double2 T; };
+// What the lean body needs to know about the sample type E of the caller-facing frames: the word that holds a frame's two
+// samples of one channel pair (8 bytes of float32 frames, 16 of float64, 4 of 16-bit PCM, 8 of 32-bit PCM), the conversion of a
+// loaded sample to fp64 and of a result to E (integer PCM: scale / round-to-even, saturate, narrow -- pcm_in / pcm_out*).
+template <typename E> struct Frame;
+template <> struct Frame<float> {
+  typedef float2 P;
+  static __device__ __forceinline__ double in(float s) { return (double)s; }
+  static __device__ __forceinline__ float out(double y) { return (float)y; }
+};
+template <> struct Frame<double> {
+  typedef double2 P;
+  static __device__ __forceinline__ double in(double s) { return s; }
+  static __device__ __forceinline__ double out(double y) { return y; }
+};
+template <> struct Frame<short> {
+  typedef short2 P;
+  static __device__ __forceinline__ double in(short s) { return pcm_in(s); }
+  static __device__ __forceinline__ short out(double y) { return pcm_out16(y); }
+};
+template <> struct Frame<int> {
+  typedef int2 P;
+  static __device__ __forceinline__ double in(int s) { return pcm_in(s); }
+  static __device__ __forceinline__ int out(double y) { return pcm_out32(y); }
+};
 __device__ __forceinline__ double2 load_g(const double2 *p)
 {
 #if RSMP_G_NT
@@ -99,12 +120,13 @@ constexpr int kSA = kFusedSA, kSB0 = kFusedSB0;
 // fifo's ring (RR_push without a destination, outputs beyond the caller's capacity): fifo_put for a channel pair.
 // TWO (sub-blocked form, 8192-point blocks): the block is ONE workgroup -- its V samples fit a pair of 4096-point component
 // transforms whole -- and the polyphase stage runs in two rounds, the second from the register slots kept across the first.
-// E: the sample type of the caller-facing frames (float; double for the *_dio_kernel instances, FastIo::dio): only the width
-// of the frame loads and stores depends on it, the arithmetic is the same fp64 code.
+// E: the sample type of the caller-facing frames (float; double / short / int for the *_dio_kernel / *_s16_kernel / *_s32_kernel
+// instances, FastIo::dio): only the frame loads and stores depend on it (Frame<E>), the arithmetic is the same fp64 code.
 template <int LOG2P, int KS, bool OUT64, bool SPLIT, bool OGEN, bool TWO = false, typename E = float>
 __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo &io)
 {
-  typedef typename Pair2<E>::T E2;
+  typedef Frame<E> Fr;
+  typedef typename Fr::P E2;
   const E *const io_in = reinterpret_cast<const E *>(io.in), *const io_in_ring = reinterpret_cast<const E *>(io.in_ring);
   E *const io_out = reinterpret_cast<E *>(io.out), *const io_out_ring = reinterpret_cast<E *>(io.out_ring);
   static_assert(!TWO || SPLIT, "two rounds from registers: sub-blocked form only");
@@ -180,7 +202,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       for (int s = 0; s < NLD; ++s) {
         const long long e = e0 + tid + s * TL;
         const E *f = e >= io.in_abs0 ? pe + (e - io.in_abs0) * io.nch : pr + (e & io.in_ring_mask) * io.nch;
-        v[s] = {(double)f[0], (double)f[1]};
+        v[s] = {Fr::in(f[0]), Fr::in(f[1])};
       }
     } else
     if (e0 >= io.in_abs0) { // uniform: the whole block lies in the caller's buffer
@@ -189,7 +211,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
 #pragma unroll
         for (int s = 0; s < NLD; ++s) {
           const E2 f = p2[(unsigned)((tid + s * TL) * hp)]; // (unsigned: scalar base + 32-bit lane offset, no 64-bit address per load)
-          (FWD8 ? u8[s & 7] : v[s]) = {(double)f.x, (double)f.y};
+          (FWD8 ? u8[s & 7] : v[s]) = {Fr::in(f.x), Fr::in(f.y)};
         }
       }
     } else if (ld_active) { // first block of a push: its head is the previous push's tail, kept in fifo 0's ring
@@ -198,7 +220,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       for (int s = 0; s < NLD; ++s) {
         const long long e = e0 + tid + s * TL;
         const E2 f = *reinterpret_cast<const E2 *>(e >= io.in_abs0 ? pe + (e - io.in_abs0) * io.nch : pr + (e & io.in_ring_mask) * io.nch);
-        (FWD8 ? u8[s & 7] : v[s]) = {(double)f.x, (double)f.y};
+        (FWD8 ? u8[s & 7] : v[s]) = {Fr::in(f.x), Fr::in(f.y)};
       }
     }
   }
@@ -502,11 +524,11 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
         if ((unsigned)ib < (unsigned)cnt && 16 * g + rloc < pl) {
           const long long A = oabs0 + ib;
           E *const p = (A >= io.out_abs0 && A < io.out_end) ? oext + (A - io.out_abs0) * io.nch : oring + (A & io.out_ring_mask) * io.nch;
-          if (io.out_unaligned) { // (uniform) a caller's buffer that is only 4-byte (float64 frames: 8-byte) aligned
-            p[0] = (E)accA;
-            p[1] = (E)accB;
+          if (io.out_unaligned) { // (uniform) a caller's buffer that is only aligned for one sample, not for a pair
+            p[0] = Fr::out(accA);
+            p[1] = Fr::out(accB);
           } else
-            *reinterpret_cast<E2 *>(p) = E2{(E)accA, (E)accB};
+            *reinterpret_cast<E2 *>(p) = E2{Fr::out(accA), Fr::out(accB)};
         }
       } else if constexpr (OUT64) {
         // (the descriptor spans the ring, so the block's range test is explicit here; lanes that fail it get an offset
@@ -532,6 +554,11 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
           const rsmp_v4u d = {(unsigned)__double2loint(accA), (unsigned)__double2hiint(accA), (unsigned)__double2loint(accB),
                               (unsigned)__double2hiint(accB)};
           __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, (int)off, 0, 0);
+        } else if constexpr (sizeof(E) == 2) { // 16-bit PCM frames: the pair as one 4-byte store
+          __builtin_amdgcn_raw_buffer_store_b32(pcm_pack16(accA, accB), orsrc, (int)off, 0, 0);
+        } else if constexpr (std::is_same<E, int>::value) { // 32-bit PCM frames: one 8-byte store
+          const rsmp_v2u d = {(unsigned)pcm_out32(accA), (unsigned)pcm_out32(accB)};
+          __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
         } else {
         const rsmp_v2u d = {__float_as_uint((float)accA), __float_as_uint((float)accB)};
         if constexpr ((RSMP_EXP_SKIP & 8) != 0) { // no stores: only a result nobody produces would be written
@@ -542,7 +569,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       }
 #else
       if (ib >= 0 && ib < cnt && 16 * g + rloc < pl)
-        *reinterpret_cast<E2 *>(obytes + (unsigned)(ib * frame_bytes)) = E2{(E)accA, (E)accB};
+        *reinterpret_cast<E2 *>(obytes + (unsigned)(ib * frame_bytes)) = E2{Fr::out(accA), Fr::out(accB)};
 #endif
       if (wrap != 0 && left > 1) { // uniform: the group switches
 #pragma unroll
@@ -653,21 +680,42 @@ __global__ __launch_bounds__(256, 2) void fused_split2_dio_kernel(FusedArgs a, F
   fused_fast_body<12, KS, OMODE == 1, true, OMODE == 2, true, double>(a, io);
 }
 
+// and around the integer PCM bodies
+#define RSMP_PCM_KERNELS(tag, E)                                                                                          \
+  template <int LOG2P, int KS, bool OUT64>                                                                                \
+  __global__ __launch_bounds__(256, kFusedWaves) void fused_fast_##tag##_kernel(FusedArgs a, FastIo io)                  \
+  {                                                                                                                       \
+    fused_fast_body<LOG2P, KS, OUT64, false, false, false, E>(a, io);                                                     \
+  }                                                                                                                       \
+  template <int KS, int OMODE> __global__ __launch_bounds__(256, 2) void fused_split_##tag##_kernel(FusedArgs a, FastIo io) \
+  {                                                                                                                       \
+    fused_fast_body<12, KS, OMODE == 1, true, OMODE == 2, false, E>(a, io);                                               \
+  }                                                                                                                       \
+  template <int KS, int OMODE> __global__ __launch_bounds__(256, 2) void fused_split2_##tag##_kernel(FusedArgs a, FastIo io) \
+  {                                                                                                                       \
+    fused_fast_body<12, KS, OMODE == 1, true, OMODE == 2, true, E>(a, io);                                                \
+  }
+RSMP_PCM_KERNELS(s16, short)
+RSMP_PCM_KERNELS(s32, int)
+#undef RSMP_PCM_KERNELS
+
+typedef void (*FastKernel)(FusedArgs, FastIo);
+
 template <int LOG2P, int KS, bool OUT64> static hipError_t launch_fast_t(const FusedArgs &a, const FastIo &io, hipStream_t st)
 {
   constexpr int N = 4096;
   size_t lds_bytes = 8 * size_t(fft_lds_doubles_halves(12));
   if (LOG2P < 12) lds_bytes = std::max(lds_bytes, 8 * size_t(std::max(fft_lds_doubles(LOG2P), fft8_lds_doubles(LOG2P))));
   lds_bytes = std::max(lds_bytes, size_t(kPad + kSA * (N / 16) + kPad) * 16);
-  static DynLdsOnce attr[2];
-  const void *fn = io.dio ? reinterpret_cast<const void *>(&fused_fast_dio_kernel<LOG2P, KS, OUT64>)
-                          : reinterpret_cast<const void *>(&fused_fast_kernel<LOG2P, KS, OUT64>);
-  if (hipError_t e = attr[io.dio ? 1 : 0].set(fn, int(lds_bytes)); e != hipSuccess) return e;
+  static DynLdsOnce attr[4];
+  static const FastKernel fns[4] = {&fused_fast_kernel<LOG2P, KS, OUT64>, &fused_fast_dio_kernel<LOG2P, KS, OUT64>,
+                                    &fused_fast_s16_kernel<LOG2P, KS, OUT64>, &fused_fast_s32_kernel<LOG2P, KS, OUT64>};
+  if (io.dio < 0 || io.dio > 3) return hipErrorInvalidValue;
+  if (hipError_t e = attr[io.dio].set(reinterpret_cast<const void *>(fns[io.dio]), int(lds_bytes)); e != hipSuccess) return e;
   FusedArgs b = a;
   b.d.hp = io.nch >= 4 ? io.nch / 2 : 0;
   dim3 grid(item_grid(a.d.nblocks, a.d.C / 2, b.d.hp)), block(N / 16);
-  if (io.dio) hipLaunchKernelGGL((fused_fast_dio_kernel<LOG2P, KS, OUT64>), grid, block, lds_bytes, st, b, io);
-  else hipLaunchKernelGGL((fused_fast_kernel<LOG2P, KS, OUT64>), grid, block, lds_bytes, st, b, io);
+  hipLaunchKernelGGL(fns[io.dio], grid, block, lds_bytes, st, b, io);
   return hipGetLastError();
 }
 
@@ -677,18 +725,16 @@ template <int KS, int OMODE, bool TWO> static hipError_t launch_split_t(const Fu
   // transforms, whichever is larger: <= 80 KB, two per CU
   const size_t lds_max = std::max(size_t(8) * fft_lds_doubles_halves(12), size_t(kPad + (TWO ? kSplitRaEnd : kSplitVsMax) + kPad) * 16);
   const size_t lds_bytes = TWO ? lds_max : std::max(size_t(8) * fft_lds_doubles_halves(12), size_t(kPad + a.d.Vs + kPad) * 16);
-  static DynLdsOnce attr[2];
-  const void *fn = io.dio ? (TWO ? reinterpret_cast<const void *>(&fused_split2_dio_kernel<KS, OMODE>) : reinterpret_cast<const void *>(&fused_split_dio_kernel<KS, OMODE>))
-                          : (TWO ? reinterpret_cast<const void *>(&fused_split2_kernel<KS, OMODE>) : reinterpret_cast<const void *>(&fused_split_kernel<KS, OMODE>));
-  if (hipError_t e = attr[io.dio ? 1 : 0].set(fn, int(lds_max)); e != hipSuccess) return e;
+  static DynLdsOnce attr[4];
+  static const FastKernel fns[4] = {
+      TWO ? &fused_split2_kernel<KS, OMODE> : &fused_split_kernel<KS, OMODE>, TWO ? &fused_split2_dio_kernel<KS, OMODE> : &fused_split_dio_kernel<KS, OMODE>,
+      TWO ? &fused_split2_s16_kernel<KS, OMODE> : &fused_split_s16_kernel<KS, OMODE>, TWO ? &fused_split2_s32_kernel<KS, OMODE> : &fused_split_s32_kernel<KS, OMODE>};
+  if (io.dio < 0 || io.dio > 3) return hipErrorInvalidValue;
+  if (hipError_t e = attr[io.dio].set(reinterpret_cast<const void *>(fns[io.dio]), int(lds_max)); e != hipSuccess) return e;
   FusedArgs b = a;
   b.d.hp = io.nch >= 4 ? io.nch / 2 : 0;
   dim3 grid(item_grid(a.d.nblocks, a.d.C / 2, b.d.hp)), block(256);
-  if (io.dio) {
-    if (TWO) hipLaunchKernelGGL((fused_split2_dio_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
-    else hipLaunchKernelGGL((fused_split_dio_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
-  } else if (TWO) hipLaunchKernelGGL((fused_split2_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
-  else hipLaunchKernelGGL((fused_split_kernel<KS, OMODE>), grid, block, lds_bytes, st, b, io);
+  hipLaunchKernelGGL(fns[io.dio], grid, block, lds_bytes, st, b, io);
   return hipGetLastError();
 }
 
@@ -720,13 +766,16 @@ hipError_t launch_fused_split(int omode, const FusedArgs &a, const FastIo &io, h
     const int ov = 2 * a.d.Pref - a.d.V; // taps - 1
     if (sb.win < 0 || sb.shift < 0 || sb.shift + sb.len / 2 + (ov + 1) / 2 > 4096 || (sb.len & 1) || sb.win + 4096 > a.d.Pref) return hipErrorInvalidValue;
   }
+// the instance's name by sample format (FastIo::dio), as rocprofv3 prints it
+#define RSMP_IO_NAME(fmt, head, tail) \
+  ((fmt) == 1 ? head "_dio_" tail : (fmt) == 2 ? head "_s16_" tail : (fmt) == 3 ? head "_s32_" tail : head "_" tail)
 #define RSMP_SPLIT_CASE(ks, om)                                                        \
   if (a.KS == ks && omode == om && !a.d.two) {                                         \
-    if (kname) *kname = io.dio ? "rsmp::fused_split_dio_kernel<" #ks ", " #om ">" : "rsmp::fused_split_kernel<" #ks ", " #om ">"; \
+    if (kname) *kname = RSMP_IO_NAME(io.dio, "rsmp::fused_split", "kernel<" #ks ", " #om ">");  \
     return launch_split_t<ks, om, false>(a, io, st);                                   \
   }                                                                                    \
   if (a.KS == ks && omode == om && a.d.two) {                                          \
-    if (kname) *kname = io.dio ? "rsmp::fused_split2_dio_kernel<" #ks ", " #om ">" : "rsmp::fused_split2_kernel<" #ks ", " #om ">"; \
+    if (kname) *kname = RSMP_IO_NAME(io.dio, "rsmp::fused_split2", "kernel<" #ks ", " #om ">"); \
     return launch_split_t<ks, om, true>(a, io, st);                                    \
   }
   // (9 k-steps: 80 phases at step 147, the windows of a 4-residue block spread over 34 samples)
@@ -743,8 +792,8 @@ bool fused_fast_supported(int log2n, int log2p, int ksteps)
 
 #define RSMP_FAST_CASE(p, ks)                                                                        \
   if (log2p == p && a.KS == ks) {                                                                    \
-    if (kname) *kname = io.dio ? (io.out64 ? "rsmp::fused_fast_dio_kernel<" #p ", " #ks ", true>" : "rsmp::fused_fast_dio_kernel<" #p ", " #ks ", false>") \
-                               : (io.out64 ? "rsmp::fused_fast_kernel<" #p ", " #ks ", true>" : "rsmp::fused_fast_kernel<" #p ", " #ks ", false>"); \
+    if (kname) *kname = io.out64 ? RSMP_IO_NAME(io.dio, "rsmp::fused_fast", "kernel<" #p ", " #ks ", true>") \
+                                 : RSMP_IO_NAME(io.dio, "rsmp::fused_fast", "kernel<" #p ", " #ks ", false>"); \
     return io.out64 ? launch_fast_t<p, ks, true>(a, io, st) : launch_fast_t<p, ks, false>(a, io, st); \
   }
 

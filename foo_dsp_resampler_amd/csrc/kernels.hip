@@ -152,6 +152,18 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, (LOG2N == 13 && LOG2ND == 13) ? 
             const double2 f = sp.d2[q[s] * sp.fstride];
             v[s] = {f.x, f.y};
           }
+        } else if (sp.kind == 4) { // 16-bit PCM frames: the raw pair words first, then the conversions
+          unsigned w[16];
+#pragma unroll
+          for (int s = 0; s < 16; ++s) w[s] = sp.w16[q[s] * sp.fstride];
+#pragma unroll
+          for (int s = 0; s < 16; ++s) v[s] = {pcm_lo16(w[s]), pcm_hi16(w[s])};
+        } else if (sp.kind == 5) { // 32-bit PCM frames
+          int2 w[16];
+#pragma unroll
+          for (int s = 0; s < 16; ++s) w[s] = sp.w32[q[s] * sp.fstride];
+#pragma unroll
+          for (int s = 0; s < 16; ++s) v[s] = {pcm_in(w[s].x), pcm_in(w[s].y)};
         } else {
 #pragma unroll
           for (int s = 0; s < 16; ++s) v[s] = {sp.pa[q[s]], sp.pb[q[s]]};
@@ -640,6 +652,18 @@ template <int NC> __global__ __launch_bounds__(256) void half_kernel(AnyView in,
     } else if (cs.kind == 3) {
 #pragma unroll
       for (int j = 0; j < 6; ++j) t[j] = cs.p64[min(ib + 256 * j, wlen - 1) * cs.stride32];
+    } else if (cs.kind == 4) { // 16-bit PCM frames: the raw samples first, then the conversions
+      short w[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) w[j] = cs.p16[min(ib + 256 * j, wlen - 1) * cs.stride32];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) t[j] = pcm_in(w[j]);
+    } else if (cs.kind == 5) { // 32-bit PCM frames
+      int w[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) w[j] = cs.pi32[min(ib + 256 * j, wlen - 1) * cs.stride32];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) t[j] = pcm_in(w[j]);
     } else {
 #pragma unroll
       for (int j = 0; j < 6; ++j) t[j] = ib + 256 * j < wlen ? fifo_get(src, w0 + ib + 256 * j) : 0.0;
@@ -814,17 +838,28 @@ __global__ __launch_bounds__(256) void copy_frames_kernel(const float *src, long
   }
 }
 
+// the same for frames whose byte count, stream strides or addresses are not multiples of 4 (16-bit PCM, odd channel counts
+// or buffers that are only 2-byte aligned): two bytes per thread
+__global__ __launch_bounds__(256) void copy_frames16_kernel(const unsigned short *src, long long src_stride, unsigned short *dst,
+                                                            long long dst_stride, long long nhalves)
+{
+  const unsigned short *s = src + (long long)blockIdx.y * src_stride;
+  unsigned short *d = dst + (long long)blockIdx.y * dst_stride;
+  const long long step = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nhalves; i += step) d[i] = s[i];
+}
+
 // base pointer of frames [a0, a1) of stream 0 when every stream holds them contiguously in one buffer of the view, else null;
-// `w` = 4-byte words per sample (2 for float64 frames: a copy moves bits, so those frames go as twice the floats)
-static const float *frames_base(const F32View &v, long long a0, long long a1, long long &stream_stride, int w = 1)
+// `eb` = bytes per sample (a copy moves bits, so frames of any type go as raw memory); stream_stride comes back in bytes
+static const char *frames_base(const F32View &v, long long a0, long long a1, long long &stream_stride, int eb = 4)
 {
   if (v.ext && a0 >= v.ext_begin && a1 <= v.ext_end) {
-    stream_stride = v.ext_stream_stride * w;
-    return v.ext + (a0 - v.ext_begin) * v.nch * w;
+    stream_stride = v.ext_stream_stride * eb;
+    return reinterpret_cast<const char *>(v.ext) + (a0 - v.ext_begin) * v.nch * eb;
   }
   if ((!v.ext || a1 <= v.ext_begin || a0 >= v.ext_end) && a0 >= 0 && (a0 & v.ring_mask) + (a1 - a0) <= v.ring_mask + 1) {
-    stream_stride = v.ring_stream_stride * w;
-    return v.ring + (a0 & v.ring_mask) * v.nch * w;
+    stream_stride = v.ring_stream_stride * eb;
+    return reinterpret_cast<const char *>(v.ring) + (a0 & v.ring_mask) * v.nch * eb;
   }
   return nullptr;
 }
@@ -835,15 +870,25 @@ static hipError_t copy_range(int f32, const F32View &sf, const F64View &sd, cons
   if (a1 <= a0) return hipSuccess;
   if (f32 && depth < 3 && sf.nch == df.nch && sf.nch > 0 && C % sf.nch == 0) { // (at most 8 pieces, then element-wise)
     long long ss = 0, ds = 0;
-    const int w = f32 == kFramesF64 ? 2 : 1;
-    const float *sp = frames_base(sf, a0, a1, ss, w);
-    float *dp = const_cast<float *>(frames_base(df, a0, a1, ds, w));
+    const int eb = frame_elem_bytes(f32);
+    const char *sp = frames_base(sf, a0, a1, ss, eb);
+    char *dp = const_cast<char *>(frames_base(df, a0, a1, ds, eb));
     if (sp && dp) {
-      const long long nfloats = (a1 - a0) * sf.nch * w;
-      const int vec4 = ((reinterpret_cast<unsigned long long>(sp) | reinterpret_cast<unsigned long long>(dp) |
-                         (unsigned long long)(ss * 4) | (unsigned long long)(ds * 4)) & 15) == 0;
+      const long long nbytes = (a1 - a0) * sf.nch * eb;
+      const unsigned long long all = reinterpret_cast<unsigned long long>(sp) | reinterpret_cast<unsigned long long>(dp) |
+                                     (unsigned long long)ss | (unsigned long long)ds;
+      if ((all | (unsigned long long)nbytes) & 3) { // (16-bit PCM only: everything else is made of 4-byte words)
+        const long long nhalves = nbytes / 2;
+        const long long blocks = std::min<long long>(std::max<long long>(1, (nhalves + 255) / 256), 1024);
+        hipLaunchKernelGGL(copy_frames16_kernel, dim3((unsigned)blocks, C / sf.nch), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned short *>(sp), ss / 2, reinterpret_cast<unsigned short *>(dp), ds / 2, nhalves);
+        return hipGetLastError();
+      }
+      const long long nfloats = nbytes / 4;
+      const int vec4 = (all & 15) == 0;
       const long long blocks = std::min<long long>(std::max<long long>(1, (nfloats / (vec4 ? 4 : 1) + 255) / 256), 1024);
-      hipLaunchKernelGGL(copy_frames_kernel, dim3((unsigned)blocks, C / sf.nch), dim3(256), 0, st, sp, ss, dp, ds, nfloats, vec4);
+      hipLaunchKernelGGL(copy_frames_kernel, dim3((unsigned)blocks, C / sf.nch), dim3(256), 0, st, reinterpret_cast<const float *>(sp),
+                         ss / 4, reinterpret_cast<float *>(dp), ds / 4, nfloats, vec4);
       return hipGetLastError();
     }
     // not contiguous on one side: cut the range where a view changes buffers (its external buffer's ends, a ring wrap)

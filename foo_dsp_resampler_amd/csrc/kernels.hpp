@@ -36,7 +36,33 @@ struct DynLdsOnce {
 // consumed in place and a device-resident pull be produced in place (no staging copy of bulk data).
 // With float64 frames (kFramesF64: a handle opened with RRX_FMT_DOUBLE) the same struct describes them: ring / ext then
 // address doubles and every stride counts doubles; the launchers' src_f32 / dst_f32 say which (0 = the fp64 rings).
-enum { kFramesF32 = 1, kFramesF64 = 2 };
+// Integer PCM frames (kFramesS16 / kFramesS32: RRX_FMT_S16 / RRX_FMT_S32) are described the same way: the pointers address
+// elements of the handle's type (short / int), strides count samples, and every load converts / every store quantises
+// (pcm_in / pcm_out below) around the same fp64 arithmetic.
+enum { kFramesF32 = 1, kFramesF64 = 2, kFramesS16 = 3, kFramesS32 = 4 };
+// bytes per sample of a frame kind
+__host__ __device__ constexpr int frame_elem_bytes(int kind) { return kind == kFramesF64 ? 8 : kind == kFramesS16 ? 2 : 4; }
+
+// The integer formats' conversions (the ABI contract of include/ratelib_amd.h).  In: s * 2^-bits, exact in fp64.  Out:
+// round half to even (v_rndne_f64), saturate to [-2^bits, 2^bits - 1] in fp64, then narrow -- the integer convert never sees
+// a value it cannot hold (a NaN saturates to -2^bits: fmax / fmin return their other operand).
+__host__ __device__ __forceinline__ double pcm_in(short s) { return (double)s * 0x1p-15; }
+__host__ __device__ __forceinline__ double pcm_in(int s) { return (double)s * 0x1p-31; }
+__host__ __device__ __forceinline__ short pcm_out16(double y)
+{
+  return (short)(int)fmin(fmax(rint(y * 32768.0), -32768.0), 32767.0);
+}
+__host__ __device__ __forceinline__ int pcm_out32(double y)
+{
+  return (int)fmin(fmax(rint(y * 2147483648.0), -2147483648.0), 2147483647.0);
+}
+// a channel pair of one S16 frame as one 4-byte word (channel 2p in the low half)
+__host__ __device__ __forceinline__ unsigned pcm_pack16(double a, double b)
+{
+  return (unsigned)(unsigned short)pcm_out16(a) | ((unsigned)(unsigned short)pcm_out16(b) << 16);
+}
+__host__ __device__ __forceinline__ double pcm_lo16(unsigned w) { return pcm_in((short)(w & 0xffffu)); }
+__host__ __device__ __forceinline__ double pcm_hi16(unsigned w) { return pcm_in((short)(w >> 16)); }
 struct F32View {
   float *ring;
   long long ring_mask;          // frames - 1
@@ -244,8 +270,10 @@ struct FastIo {
   // OUT64 instances (the polyphase stage feeds another stage): planar fp64 ring of the destination fifo instead of `out`
   double *out64;              // ring of channel 0
   long long out64_mask, out64_chan_stride; // items - 1, items between channels
-  // 1: the caller-facing frames hold float64 samples (*_dio_kernel instances): in / in_ring / out / out_ring then address
-  // doubles, every stride and frame offset above counts doubles, and in_unaligned / out_unaligned mean "not 16-byte aligned"
+  // Sample format of the caller-facing frames, which picks the kernel instance: 0 = float32, 1 = float64 (*_dio_kernel),
+  // 2 = 16-bit PCM (*_s16_kernel), 3 = 32-bit PCM (*_s32_kernel).  in / in_ring / out / out_ring then address samples of that
+  // type, every stride and frame offset above counts samples, and in_unaligned / out_unaligned mean "a channel pair is not
+  // aligned as one word" (8 / 16 / 4 / 8 bytes)
   int dio;
 };
 bool fused_fast_supported(int log2n, int log2p, int ksteps);

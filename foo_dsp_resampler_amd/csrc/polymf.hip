@@ -53,6 +53,24 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
             x[j] = f.x;
             y[j] = f.y;
           }
+        } else if (sp.kind == 4) { // 16-bit PCM frames: the raw pair words first, then the conversions
+          unsigned w[5];
+#pragma unroll
+          for (int j = 0; j < 5; ++j) w[j] = sp.w16[min(ib + 256 * j, W - 1) * sp.fstride];
+#pragma unroll
+          for (int j = 0; j < 5; ++j) {
+            x[j] = pcm_lo16(w[j]);
+            y[j] = pcm_hi16(w[j]);
+          }
+        } else if (sp.kind == 5) { // 32-bit PCM frames
+          int2 w[5];
+#pragma unroll
+          for (int j = 0; j < 5; ++j) w[j] = sp.w32[min(ib + 256 * j, W - 1) * sp.fstride];
+#pragma unroll
+          for (int j = 0; j < 5; ++j) {
+            x[j] = pcm_in(w[j].x);
+            y[j] = pcm_in(w[j].y);
+          }
         } else { // (pb == pa when the pair has one channel: every load is unconditional)
 #pragma unroll
           for (int j = 0; j < 5; ++j) {
@@ -92,7 +110,7 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
   bool ofast = false;
   char *obase = nullptr;
   int ofs = 2;
-  const int esz = out.is_f32 == kFramesF64 ? 8 : 4; // bytes per sample of the destination frames
+  const int esz = frame_elem_bytes(out.is_f32); // bytes per sample of the destination frames
   {
     const long long o0 = a.out_offset + fb.i_lo, o1 = o0 + fb.cnt;
     if (out.is_f32 && hasb && !(out.f.nch & 1)) {
@@ -114,10 +132,11 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
   // range per wave; coefficient tile double-buffered a group ahead, window start of a group from the host table, every
   // store issued straight after its tile under a per-lane range test, next tile's samples always prefetched.
   auto run = [&](auto fast_tag) {
-    constexpr bool FAST = decltype(fast_tag)::value != 0, DBL = decltype(fast_tag)::value == 2;
+    constexpr int MODE = decltype(fast_tag)::value; // 3 / 4: quantised 16- / 32-bit PCM pair words
+    constexpr bool FAST = MODE != 0, DBL = MODE == 2;
     const ChanRef oa = chan_ref(out, ca), ob = chan_ref(out, hasb ? cb : ca);
     char *const obytes = obase;
-    const int frame_bytes = ofs * (DBL ? 8 : 4);
+    const int frame_bytes = ofs * (DBL ? 8 : MODE == 3 ? 2 : 4);
     const int li_lo = -kPmPad, li_hi = W + kPmPad - 4 * KS;
     const int ncs = (fb.K + 3) >> 2, nt = a.NGRP * ncs;
     const int t0 = (nt * wave) >> 2, t1 = (nt * (wave + 1)) >> 2;
@@ -167,7 +186,11 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
       }
       const int ib = lane_ib + 16 * g + c * pl4;
       if (ib >= 0 && ib < cnt && 16 * g + rloc < pl) {
-        if (DBL) {
+        if (MODE == 3) {
+          *reinterpret_cast<unsigned *>(obytes + (unsigned)(ib * frame_bytes)) = pcm_pack16(accA, accB);
+        } else if (MODE == 4) {
+          *reinterpret_cast<int2 *>(obytes + (unsigned)(ib * frame_bytes)) = make_int2(pcm_out32(accA), pcm_out32(accB));
+        } else if (DBL) {
           *reinterpret_cast<double2 *>(obytes + (unsigned)(ib * frame_bytes)) = make_double2(accA, accB);
         } else if (FAST) {
           *reinterpret_cast<float2 *>(obytes + (unsigned)(ib * frame_bytes)) = make_float2((float)accA, (float)accB);
@@ -195,6 +218,8 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
     }
   };
   if (ofast && esz == 8) run(std::integral_constant<int, 2>{});
+  else if (ofast && out.is_f32 == kFramesS16) run(std::integral_constant<int, 3>{});
+  else if (ofast && out.is_f32 == kFramesS32) run(std::integral_constant<int, 4>{});
   else if (ofast) run(std::integral_constant<int, 1>{});
   else run(std::integral_constant<int, 0>{});
 }

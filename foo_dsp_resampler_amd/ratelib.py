@@ -16,10 +16,16 @@ EXPECTED_SYMBOLS = [
     "RRX_set_stream", "RRX_sync", "RRX_profile", "RRX_profile_read", "RRX_profile_report", "RRX_debug_fail_alloc",
     "RRX_open_batch_fmt", "RRX_format", "RRX_push_double", "RRX_pull_double", "RRX_flow_double", "RRX_push_device_double",
     "RRX_pull_device_double", "RRX_flow_device_double",
+    "RRX_push_samples", "RRX_pull_samples", "RRX_flow_samples", "RRX_push_device_samples", "RRX_pull_device_samples",
+    "RRX_flow_device_samples",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
 RRX_FMT_FLOAT, RRX_FMT_DOUBLE = 0, 1  # sample formats of a handle (ratelib_amd.h)
+RRX_FMT_S16, RRX_FMT_S32 = 16, 32      # interleaved signed integer PCM (24-bit audio left-justified in S32)
+_FMT_DTYPE = {RRX_FMT_FLOAT: np.dtype(np.float32), RRX_FMT_DOUBLE: np.dtype(np.float64), RRX_FMT_S16: np.dtype(np.int16),
+              RRX_FMT_S32: np.dtype(np.int32)}
+_DTYPE_FMT = {d: f for f, d in _FMT_DTYPE.items()}
 
 
 class RRConfig(C.Structure):
@@ -103,6 +109,12 @@ def lib():
         L.RRX_push_device_double.argtypes = [vp, vp, sz, sz]
         L.RRX_pull_device_double.argtypes = [vp, vp, sz, sz, P(sz)]
         L.RRX_flow_device_double.argtypes = [vp, vp, sz, vp, sz, sz, sz, P(sz), P(sz)]
+        L.RRX_push_samples.argtypes = [vp, C.c_int, vp, sz, sz]
+        L.RRX_pull_samples.argtypes = [vp, C.c_int, vp, sz, sz, P(sz)]
+        L.RRX_flow_samples.argtypes = [vp, C.c_int, vp, sz, vp, sz, sz, sz, P(sz), P(sz)]
+        L.RRX_push_device_samples.argtypes = [vp, C.c_int, vp, sz, sz]
+        L.RRX_pull_device_samples.argtypes = [vp, C.c_int, vp, sz, sz, P(sz)]
+        L.RRX_flow_device_samples.argtypes = [vp, C.c_int, vp, sz, vp, sz, sz, sz, P(sz), P(sz)]
         L.RR_push.argtypes = [vp, vp, sz]
         L.RR_pull.argtypes = [vp, vp, sz, P(sz)]
         L.RR_flow.argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
@@ -197,20 +209,37 @@ class Resampler:
     Device buffers are anything with `data_ptr()` (torch CUDA tensors) of the same shapes.
     dtype=np.float64 opens a double-format handle (RRX_open_batch_fmt, RRX_FMT_DOUBLE): host arrays and device tensors are
     then float64 and go through the RRX_*_double calls.  A buffer of the other precision is refused before any C call.
+    sample_format=RRX_FMT_S16 / RRX_FMT_S32 opens an integer PCM handle: host arrays are int16 / int32, device tensors
+    torch.int16 / torch.int32, and every data call goes through the format-tagged RRX_*_samples calls (conversions:
+    ratelib_amd.h).  `dtype` keeps meaning float32 or float64 only; `self.dtype` is the handle's sample dtype.
+    What a handle accepts: an integer handle takes arrays and tensors of exactly its own dtype.  A float or double handle
+    refuses the other float precision and the two PCM dtypes (int16, int32: data meant for an integer handle); anything else
+    (lists, float16, int8, uint8, int64 ...) is converted to the handle's dtype by value, as numpy does, with no PCM scaling.
+    A wrong type is a TypeError, an unknown `sample_format` value a ValueError, both before any C call.
     """
 
-    def __init__(self, in_rate, out_rate, nch=2, nstreams=1, device=None, dtype=np.float32, **kw):
-        dtype = np.dtype(dtype)
-        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("Resampler dtype must be float32 or float64, not %s" % dtype)
+    def __init__(self, in_rate, out_rate, nch=2, nstreams=1, device=None, dtype=None, sample_format=None, **kw):
+        if dtype is not None:
+            dtype = np.dtype(dtype)
+            if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise TypeError("Resampler dtype must be float32 or float64, not %s (integer PCM: sample_format=RRX_FMT_S16 / "
+                                "RRX_FMT_S32)" % dtype)
+        if sample_format is not None:
+            if sample_format not in _FMT_DTYPE:
+                raise ValueError("unknown sample_format %r" % (sample_format,))
+            if dtype is not None and dtype != _FMT_DTYPE[sample_format]:
+                raise TypeError("dtype %s does not go with sample_format %r: give one of the two" % (dtype, sample_format))
+            dtype = _FMT_DTYPE[sample_format]
+        elif dtype is None:
+            dtype = np.dtype(np.float32)
         _ensure_init()
         self.L = lib()
         self.nch, self.nstreams = nch, nstreams
         self.dtype = dtype
         self.cfg = _config(in_rate, out_rate, **kw)
         self.h = C.c_void_p()
-        if dtype == np.float64:
-            _check(self.L.RRX_open_batch_fmt(C.byref(self.cfg), nch, nstreams, -1 if device is None else int(device), RRX_FMT_DOUBLE,
+        if dtype != np.float32:
+            _check(self.L.RRX_open_batch_fmt(C.byref(self.cfg), nch, nstreams, -1 if device is None else int(device), _DTYPE_FMT[dtype],
                                              C.byref(self.h)), "RRX_open_batch_fmt")
         elif device is not None:  # explicit HIP device index (RRX_open_batch_on)
             _check(self.L.RRX_open_batch_on(C.byref(self.cfg), nch, nstreams, int(device), C.byref(self.h)), "RRX_open_batch_on")
@@ -235,8 +264,18 @@ class Resampler:
         return self.dtype == np.float64
 
     @property
+    def integer(self):
+        """The handle takes and gives integer PCM frames (RRX_FMT_S16 / RRX_FMT_S32)."""
+        return self.dtype.kind == "i"
+
+    @property
+    def sample_format(self):
+        """The RRX_FMT_* that goes with the handle's sample dtype (what the *_samples calls are tagged with)."""
+        return _DTYPE_FMT[self.dtype]
+
+    @property
     def format(self):
-        """RRX_format of the handle (RRX_FMT_FLOAT / RRX_FMT_DOUBLE)."""
+        """RRX_format of the handle (RRX_FMT_*)."""
         return self.L.RRX_format(self.h)
 
     @property
@@ -281,6 +320,12 @@ class Resampler:
 
     # -- host API (RR_push / RR_pull / RR_flow / RR_drain)
     def _host_in(self, x):
+        xd = getattr(x, "dtype", None)
+        if self.integer:
+            if xd != self.dtype:
+                raise TypeError("%s samples on an %s handle: integer PCM handles take arrays of their own dtype only" % (xd, self.dtype))
+        elif xd is not None and np.dtype(xd) in (np.dtype(np.int16), np.dtype(np.int32)):
+            raise TypeError("%s samples on a %s handle: open the Resampler with sample_format=RRX_FMT_S16 / RRX_FMT_S32" % (xd, self.dtype))
         if getattr(x, "dtype", None) == np.float64 and not self.double:
             raise TypeError("float64 samples on a float32 handle: open the Resampler with dtype=np.float64")
         if getattr(x, "dtype", None) == np.float32 and self.double:
@@ -296,7 +341,9 @@ class Resampler:
         x, n = self._host_in(x)
         if n == 0:
             return
-        if self.double:
+        if self.integer:
+            _check(self.L.RRX_push_samples(self.h, self.sample_format, x.ctypes.data, n, n), "RRX_push_samples")
+        elif self.double:
             _check(self.L.RRX_push_double(self.h, x.ctypes.data, n, n), "RRX_push_double")
         elif self.nstreams == 1:
             _check(self.L.RR_push(self.h, x.ctypes.data, n), "RR_push")
@@ -307,6 +354,9 @@ class Resampler:
         shape = (max_frames, self.nch) if self.nstreams == 1 else (self.nstreams, max_frames, self.nch)
         out = np.empty(shape, dtype=self.dtype)
         n = C.c_size_t(0)
+        if self.integer:
+            _check(self.L.RRX_pull_samples(self.h, self.sample_format, out.ctypes.data, max_frames, max_frames, C.byref(n)), "RRX_pull_samples")
+            return out[: n.value] if self.nstreams == 1 else out[:, : n.value]
         if self.double:
             _check(self.L.RRX_pull_double(self.h, out.ctypes.data, max_frames, max_frames, C.byref(n)), "RRX_pull_double")
             return out[: n.value] if self.nstreams == 1 else out[:, : n.value]
@@ -333,6 +383,10 @@ class Resampler:
         x, n = self._host_in(x)
         out = np.empty((max_out, self.nch), dtype=self.dtype)
         iu, og = C.c_size_t(0), C.c_size_t(0)
+        if self.integer:
+            _check(self.L.RRX_flow_samples(self.h, self.sample_format, x.ctypes.data if n else None, n, out.ctypes.data, max_out, n,
+                                           max_out, C.byref(iu), C.byref(og)), "RRX_flow_samples")
+            return iu.value, out[: og.value]
         if self.double:
             _check(self.L.RRX_flow_double(self.h, x.ctypes.data if n else None, n, out.ctypes.data, max_out, n, max_out,
                                           C.byref(iu), C.byref(og)), "RRX_flow_double")
@@ -361,6 +415,12 @@ class Resampler:
     def _dev_check(self, t):
         """A tensor whose dtype names the other precision is refused (torch.float32 / torch.float64 vs the handle)."""
         dt = str(getattr(t, "dtype", ""))
+        if self.integer:
+            if not dt.endswith("." + self.dtype.name) and dt != self.dtype.name:
+                raise TypeError("%s buffer on an %s handle: integer PCM handles take tensors of their own dtype only" % (dt or "untyped", self.dtype))
+            return C.c_void_p(t.data_ptr())
+        if dt.endswith("int16") or dt.endswith("int32"):
+            raise TypeError("%s buffer on a %s handle: open the Resampler with sample_format=RRX_FMT_S16 / RRX_FMT_S32" % (dt, self.dtype))
         if dt.endswith("float64") and not self.double:
             raise TypeError("torch.float64 buffer on a float32 handle: open the Resampler with dtype=np.float64")
         if dt.endswith("float32") and self.double:
@@ -369,6 +429,9 @@ class Resampler:
 
     def push_device(self, t, frames, stride=None):
         p = self._dev_check(t)
+        if self.integer:
+            _check(self.L.RRX_push_device_samples(self.h, self.sample_format, p, stride or frames, frames), "RRX_push_device_samples")
+            return
         if self.double:
             _check(self.L.RRX_push_device_double(self.h, p, stride or frames, frames), "RRX_push_device_double")
             return
@@ -377,6 +440,10 @@ class Resampler:
     def pull_device(self, t, max_frames, stride=None):
         n = C.c_size_t(0)
         p = self._dev_check(t)
+        if self.integer:
+            _check(self.L.RRX_pull_device_samples(self.h, self.sample_format, p, stride or max_frames, max_frames, C.byref(n)),
+                   "RRX_pull_device_samples")
+            return n.value
         if self.double:
             _check(self.L.RRX_pull_device_double(self.h, p, stride or max_frames, max_frames, C.byref(n)), "RRX_pull_device_double")
             return n.value
@@ -389,6 +456,11 @@ class Resampler:
         if tin is not None:
             self._dev_check(tin)
         self._dev_check(tout)
+        if self.integer:
+            _check(self.L.RRX_flow_device_samples(self.h, self.sample_format, C.c_void_p(tin.data_ptr()) if tin is not None else None,
+                                                  in_stride or in_frames, C.c_void_p(tout.data_ptr()), out_stride or out_cap,
+                                                  in_frames, out_cap, C.byref(iu), C.byref(og)), "RRX_flow_device_samples")
+            return iu.value, og.value
         if self.double:
             _check(self.L.RRX_flow_device_double(self.h, C.c_void_p(tin.data_ptr()) if tin is not None else None,
                                                  in_stride or in_frames, C.c_void_p(tout.data_ptr()), out_stride or out_cap,

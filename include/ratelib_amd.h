@@ -94,7 +94,7 @@ void RRX_debug_fail_alloc(int nth);
 #define RRX_FMT_DOUBLE 1   /* interleaved float64 */
 /* RRX_open_batch / RRX_open_batch_on with a sample format: device = -1 is RRX_open_batch's placement (the current device,
  * or round-robin under RATELIB_AMD_DEVICES), any other value is RRX_open_batch_on's.  An unknown format returns
- * RR_INVPARAM before any device is touched. */
+ * RR_INVPARAM before any device is touched.  (RRX_FMT_S16 / RRX_FMT_S32: below.) */
 int RRX_open_batch_fmt(const RR_config *config, int nchannels, int nstreams, int device, int format, RR_handle **const handle);
 int RRX_format(const RR_handle *h); /* RRX_FMT_*, or -1 for NULL */
 
@@ -110,6 +110,37 @@ int RRX_push_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride,
 int RRX_pull_device_double(RR_handle *h, double *d_obuf, size_t out_stride, size_t osamp, size_t *ogen); /* RRX_pull_device */
 int RRX_flow_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, double *d_obuf,        /* RRX_flow_device */
                            size_t out_stride, size_t isamp, size_t osamp, size_t *iused, size_t *ogen);
+
+/* Integer PCM formats: audio at rest.  A handle opened with one of them takes and gives interleaved signed integer frames at
+ * both ends; the conversions below are part of this ABI, the chain in between is the same fp64 arithmetic, stage kernels and
+ * geometry as on a float handle of the same config (availability, the RRX_isamp_max clamp and drain totals are the float ones).
+ *   in :  x = (double)s * 2^-15 (S16) or (double)s * 2^-31 (S32); both are exact in fp64.
+ *   out:  q = rint(y * 2^bits), bits = 15 or 31, round half to even; saturated IN FP64 to [-2^bits, 2^bits - 1]; then narrowed
+ *         to the integer type.  No wrap-around, no dither, no clipped-sample counter.
+ * So an integer handle's output equals, bit for bit, the output of an RRX_FMT_DOUBLE handle fed s * 2^-bits, quantised by the
+ * rule above.  24-bit audio travels left-justified in RRX_FMT_S32 (sample << 8).
+ * Any format value other than these four makes RRX_open_batch_fmt return RR_INVPARAM before any device is touched. */
+#define RRX_FMT_S16 16   /* interleaved signed 16-bit PCM */
+#define RRX_FMT_S32 32   /* interleaved signed 32-bit PCM (24-bit audio left-justified in it) */
+
+/* One format-tagged set of data calls for all four formats.  `format` is the RRX_FMT_* the caller believes the buffers hold
+ * and must equal the handle's: otherwise the call returns RR_INVPARAM and leaves the handle as it was (not poisoned, counters
+ * unchanged).  Units (frames), strides (frames between streams; ignored by the host calls on one-stream handles), NULL and
+ * zero-count handling, the RRX_isamp_max clamp and the stream-ordering contract of the device calls are those of the
+ * *_double and *_strided / *_device calls above, word for word; on float and double handles these ARE those calls' code path.
+ * The typed calls (RR_push / RR_pull / RR_flow, RRX_*_device, RRX_*_strided, RRX_*_double) return RR_INVPARAM on an S16 or
+ * S32 handle.
+ * Alignment: host and device pointers need only the alignment of one sample (2 bytes for S16, 4 for S32, 4 / 8 for float /
+ * double).  A channel pair that is aligned as a pair (4 or 8 bytes for S16 / S32) takes the kernels' pair-word path, anything
+ * else is read and written one sample at a time; the result is the same bits either way. */
+int RRX_push_samples(RR_handle *h, int format, const void *ibuf, size_t in_stride, size_t isamp);
+int RRX_pull_samples(RR_handle *h, int format, void *obuf, size_t out_stride, size_t osamp, size_t *ogen);
+int RRX_flow_samples(RR_handle *h, int format, const void *ibuf, size_t in_stride, void *obuf, size_t out_stride,
+                     size_t isamp, size_t osamp, size_t *iused, size_t *ogen);
+int RRX_push_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, size_t isamp);
+int RRX_pull_device_samples(RR_handle *h, int format, void *d_obuf, size_t out_stride, size_t osamp, size_t *ogen);
+int RRX_flow_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, void *d_obuf, size_t out_stride,
+                            size_t isamp, size_t osamp, size_t *iused, size_t *ogen);
 
 /* Introspection: isamp_max of rate_base.h:531, frames currently pullable (fifo_occupancy of the last
  * fifo, rate_base.h:447-448), shape of the handle. */
