@@ -390,6 +390,32 @@ int RRX_profile_report(RR_handle *h, char *buf, size_t cap)
 
 void RRX_debug_fail_alloc(int nth) { rsmp::Engine::fail_alloc_after(nth); }
 
+long long RRX_debug_tile_walk(const RRX_walk_geom *g, int k, long long *head, int *slots, size_t cap)
+{
+  if (!rsmp::knobs().test_hooks || !g || !head || (cap && !slots) || k < 0) return -1;
+  if (g->polyL < 1 || g->step < 1 || g->V < 1 || g->n < 1 || g->KS < 1 || g->nsub < 0 || (g->nsub > 0 && g->Vs < 1)) return -1;
+  rsmp::FusedPrepArgs pa;
+  pa.b_offset = g->b_offset;
+  pa.B0 = g->B0;
+  pa.at0 = g->at0;
+  pa.V = g->V;
+  pa.polyL = g->polyL;
+  pa.step = g->step;
+  pa.n = g->n;
+  pa.nblocks = k + 1;
+  pa.two_round = g->two_round;
+  pa.KS = g->KS;
+  pa.qb_max = g->qb_max;
+  pa.qb_min = g->qb_min;
+  pa.ra_end = g->ra_end;
+  pa.rb_start = g->rb_start;
+  pa.clip_lo = 0;
+  pa.clip_hi = 0x7fffffffffffffffLL;
+  pa.nsub = g->nsub;
+  pa.Vs = g->Vs;
+  return (long long)rsmp::fused_walk_enumerate(pa, k, head, slots, cap);
+}
+
 size_t RRX_isamp_max(const RR_handle *h) { return h ? h->eng->isamp_max() : 0; }
 size_t RRX_available(const RR_handle *h) { return h ? h->eng->available() : 0; }
 int RRX_channels(const RR_handle *h) { return h ? h->eng->nch() : 0; }

@@ -404,7 +404,6 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
   const int pl = a.polyL, step = a.step;
-  const int irel_hi = fb.irel_lo + fb.cnt;
   const int frame_bytes = io.nch * (int)sizeof(E);
   char *const obytes = (OUT64 || OGEN) ? nullptr
                             : reinterpret_cast<char *>(io_out + strm * io.out_stream_stride + (a.out_offset2 + fb.i_lo - io.out_abs0) * io.nch + 2 * pin);
@@ -426,22 +425,32 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   const double2 *const cfm_lane = a.cfm2 + lane;
   const int *const qtab_lane = a.qtab + bq;
 
+  // Every group walks its OWN periods (kernels.hpp, FusedWalk): group g starts at period kb + p0_g, p0_g = 1 when all its
+  // residues lie in front of the block's first output, and has ncs_g column steps of 4 periods, one less than its neighbours
+  // when it ends a period early.  `pc` counts periods from kb: p0_g, p0_g + 4, ... up to `pend` = p0_g + 4 ncs_g.
+  const FusedWalk fw = fused_walk(fb, ngrp);
   auto poly_round = [&](int kb, int ke, const double2 *xs, int li_lo, int li_hi) {
-    const int ncs = (ke - kb + 3) >> 2; // column steps (4 periods each) of this round
-    const int nt = ngrp * ncs;
-    const int t0 = (nt * wave) >> 2, t1 = (nt * (wave + 1)) >> 2; // this wave's tiles, group-major
+    if (ke <= kb) return;
+    const WalkRound wr = walk_round(fw, fb.K, kb, ke, ngrp);
+    const int t0 = (wr.nt * wave) >> 2, t1 = (wr.nt * (wave + 1)) >> 2; // this wave's tiles, group-major
     if (t0 >= t1) return;
-    int g = t0 / ncs, c = t0 - g * ncs;
-    const int hi_bound = min(irel_hi, ke * pl);
-    const int lane_li = fb.base_li + hi + (kb + jq) * step; // window start = lane_li + q(group, block) + c * 4 * step
-    const int lane_ib = (kb + jq) * pl + rloc - fb.irel_lo; // output index relative to i_lo = lane_ib + 16 g + c * 4 * pl
-    const int cnt = hi_bound - fb.irel_lo;
+    // (readfirstlane: the walk's state is uniform and has to stay in scalar registers -- the loop below tests it with scalar
+    // instructions; it costs one move here and one per group switch, none per tile)
+    int g, pc;
+    walk_seek(wr, t0, g, pc);
+    g = __builtin_amdgcn_readfirstlane(g);
+    int p0 = __builtin_amdgcn_readfirstlane(walk_p0(fw, g)); // the current group's first period, then the next group's
+    pc = __builtin_amdgcn_readfirstlane(4 * pc + p0);
+    int pend = __builtin_amdgcn_readfirstlane(p0 + 4 * walk_ncs(fw, fb.K, kb, ke, g));
+    // (a first round that stops short of K ends at period ke for the groups that start at 0 and at ke + 1 for the others)
+    const int lane_li = walk_lane_li(fb, kb, hi, jq, step); // window start = lane_li + q(group, block) + pc * step
+    const int lane_ib = walk_lane_ib(fb, kb, jq, rloc, pl); // output index relative to i_lo = lane_ib + 16 g + pc * pl
+    const int cnt = walk_round_cnt(fb, fw, ke, pl);
 #if RSMP_BUFSTORE
     // raw buffer over this round's outputs [0, cnt) of the block: frame ib at byte ib * frame_bytes, 8 (16) bytes of it are ours
     const __amdgpu_buffer_rsrc_t orsrc =
         __builtin_amdgcn_make_buffer_rsrc(obytes, 0, (!OUT64 && !OGEN && cnt > 0) ? (cnt - 1) * frame_bytes + 2 * (int)sizeof(E) : 0, 0x00020000);
 #endif
-    const int step4 = 4 * step, pl4 = 4 * pl;
     // store offset of a tile = (this lane's part, once per round) + (the tile's part, scalar): one vector add per tile.  Only the
     // last residue group can hold residues >= polyL (polyL not a multiple of 16): its lanes get the dropped offset there.
     const int lane_off0 = __mul24(lane_ib, frame_bytes); // |lane_ib| < 2^23
@@ -473,18 +482,19 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     load_tile(min(g + 1, ngrp - 1), cn, qnd, qni); // (unconditional, clamped: see the group switch below)
 
     double2 x0[KS], x1[KS];
-    auto fill = [&](double2 (&x)[KS], int q, int cstep) {
+    auto fill = [&](double2 (&x)[KS], int q, int pstep) {
 #if RSMP_EXP_LINEAR // timing experiment only (WRONG results): lane-linear, conflict-free window addresses
-      const int li = li_lo + 32 + lane + ((cstep * 64 + (q & 63)) & 1023);
+      const int li = li_lo + 32 + lane + ((pstep * 16 + (q & 63)) & 1023);
 #else
-      const int li = max(li_lo, min(li_hi, lane_li + q + cstep * step4));
+      const int li = max(li_lo, min(li_hi, q + pstep * step)); // (q = lane_li + the group's window start)
 #endif
       const double2 *xp = xs + li;
 #pragma unroll
       for (int s = 0; s < KS; ++s) x[s] = xp[4 * s];
     };
-    int qc = qof(qcd, qci);
-    fill(x0, qc, c);
+    // (lane_li is added where qc changes, at the group switch: one vector add per tile for the window address, as before)
+    int qc = qof(qcd, qci) + lane_li;
+    fill(x0, qc, pc);
 
     int left = t1 - t0;
     // one tile: prefetch the next tile's samples into `xn`, run the two accumulation chains on `xc`, store
@@ -492,18 +502,26 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       // (loop control in plain ints: uniform bools that live across blocks came back as v_cndmask / v_readfirstlane pairs)
       // (and every condition is recomputed from them where it is used: carried from one block to the next it takes a trip through
       // a vector register)
-      // wrap = 1 when this is its group's last tile (c + 1 == ncs), by arithmetic the optimiser cannot see through: as a compare
+      // wrap = 1 when this is its group's last tile (pc + 4 == pend), by arithmetic the optimiser cannot see through: as a compare
       // (+ select) it widens the flag through a vector register (v_cndmask, v_readfirstlane, v_cmp_ne) in every tile
-      int wrap, keep;
-      asm("s_lshr_b32 %0, %1, 31" : "=s"(wrap) : "s"(ncs - 2 - c));
-      asm("s_add_i32 %0, %1, -1" : "=s"(keep) : "s"(wrap) : "scc"); // all ones unless the group ends
-      const int cnext = (c + 1) & keep, gnext = g + wrap;
+      int wrap;
+      asm("s_lshr_b32 %0, %1, 31" : "=s"(wrap) : "s"(pend - 8 - pc));
+      const int gnext = g + wrap;
+      int pnext = pc + 4, pend_next = pend;
       if (wrap != 0 && left > 1) { // uniform.  Volatile so that it STAYS a branch: as a select the conversion runs in every tile and the
                           // tile right behind a switch waits for the tile load that was just issued
         if constexpr (KS & 1) asm volatile("v_cvt_i32_f64 %0, %1" : "=v"(qc) : "v"(qnd));
         else asm volatile("v_mov_b32 %0, %1" : "=v"(qc) : "v"(qni));
+        qc += lane_li;
+        // the next group's first period and column steps: they differ from this group's only where a run of groups ends
+        // (WalkRound: twice per round at most, never in the uniform walk), so a group switch costs two scalar compares
+        if (gnext == wr.b1 || gnext == wr.b2) {
+          p0 = __builtin_amdgcn_readfirstlane(walk_p0(fw, gnext));
+          pend_next = __builtin_amdgcn_readfirstlane(p0 + 4 * walk_ncs(fw, fb.K, kb, ke, gnext));
+        }
+        pnext = p0;
       }
-      if constexpr (!(RSMP_EXP_SKIP & 16)) fill(xn, qc, left > 1 ? cnext : c); // after the last tile: a harmless re-read
+      if constexpr (!(RSMP_EXP_SKIP & 16)) fill(xn, qc, left > 1 ? pnext : pc); // after the last tile: a harmless re-read
       double accA = 0.0, accB = 0.0;
 #pragma unroll
       for (int s = 0; s < (RSMP_EXP_HALFMFMA ? 3 : KS); ++s) { // RSMP_EXP_HALFMFMA: timing experiment only (WRONG results)
@@ -519,7 +537,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
 #pragma unroll
       for (int s = 3; s < KS; ++s) { accA += xc[s].x * 1e-30; accB += cc[s] * 1e-30 + xc[s].y * 1e-30; } // keep the loads alive
 #endif
-      const int ib = lane_ib + 16 * g + c * pl4;
+      const int ib = lane_ib + 16 * g + pc * pl;
       if constexpr (OGEN) {
         if ((unsigned)ib < (unsigned)cnt && 16 * g + rloc < pl) {
           const long long A = oabs0 + ib;
@@ -545,7 +563,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
         // one unconditional buffer store per tile: outputs in front of the block (ib < 0 wraps to a huge offset) and behind
         // the round's last one fail the descriptor's range check and are dropped by the hardware; only the residue test of
         // the last (partial) group needs a select
-        unsigned off = (unsigned)(lane_off0 + (16 * g + c * pl4) * frame_bytes);
+        unsigned off = (unsigned)(lane_off0 + (16 * g + pc * pl) * frame_bytes);
         if (g == ngrp - 1 && (pl & 15)) { // uniform, and only chains whose polyL is not a multiple of 16 ever take it
           off = lane_dead_last ? 0xffffffffu : off;
           asm volatile("" : "+v"(off)); // (keeps it a branch: as selects it is two more vector instructions in every tile)
@@ -583,7 +601,8 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
         load_tile(min(gnext + 1, ngrp - 1), cn, qnd, qni);
       }
       g = gnext;
-      c = cnext;
+      pc = pnext;
+      pend = pend_next;
       --left;
     };
     while (true) {
@@ -599,7 +618,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   if (RSMP_PRIO == 2) __builtin_amdgcn_s_setprio(3);
   // round A: periods whose windows end inside the samples written above
   if constexpr (SPLIT && TWO) {
-    if (run) poly_round(0, fb.KA, smp, -kPad, min(V, kSplitRaEnd) + kPad - 4 * KS);
+    if (run) poly_round(0, fw.ka, smp, -kPad, min(V, kSplitRaEnd) + kPad - 4 * KS);
     __syncthreads();
     { // second image: samples [kSplitRbStart, V) from the slots kept in registers, element 0 = sample kSplitRbStart
       double2 *l2 = reinterpret_cast<double2 *>(lds);
@@ -615,13 +634,13 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     }
     __syncthreads();
     if (tail_in_b) store_tail(reinterpret_cast<const double2 *>(lds), kSplitRbStart);
-    if (run && fb.KA < fb.K) poly_round(fb.KA, fb.K, reinterpret_cast<const double2 *>(lds) - kSplitRbStart, kSplitRbStart, V + kPad - 4 * KS);
+    if (run && fw.ka < fb.K) poly_round(fw.ka, fb.K, reinterpret_cast<const double2 *>(lds) - kSplitRbStart, kSplitRbStart, V + kPad - 4 * KS);
     return;
   } else if constexpr (SPLIT) {
     if (run) poly_round(0, fb.K, smp, -kPad, V + kPad - 4 * KS); // one round over the whole image
     return;
   }
-  if (run) poly_round(0, fb.KA, smp, -kPad, min(V, kSA * T) + kPad - 4 * KS);
+  if (run) poly_round(0, fw.ka, smp, -kPad, min(V, kSA * T) + kPad - 4 * KS);
   RSMP_STAMP(6)
   __syncthreads();
   // round B: the rest of the block's samples replace the image, element 0 = sample kSB0*T
@@ -636,7 +655,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   }
   __syncthreads();
   if (tail_in_b) store_tail(reinterpret_cast<const double2 *>(lds), kSB0 * T);
-  if (run && fb.KA < fb.K) poly_round(fb.KA, fb.K, reinterpret_cast<const double2 *>(lds) - kSB0 * T, kSB0 * T, V + kPad - 4 * KS);
+  if (run && fw.ka < fb.K) poly_round(fw.ka, fb.K, reinterpret_cast<const double2 *>(lds) - kSB0 * T, kSB0 * T, V + kPad - 4 * KS);
   RSMP_STAMP(5)
 #ifdef RSMP_STAMPS_BUILD
   if (stamping && tid == 0) atomicAdd(a.stamps + 7, 1ull);
@@ -783,6 +802,59 @@ hipError_t launch_fused_split(int omode, const FusedArgs &a, const FastIo &io, h
   RSMP_SPLIT_CASE(9, 0) RSMP_SPLIT_CASE(9, 1) RSMP_SPLIT_CASE(9, 2)
 #undef RSMP_SPLIT_CASE
   return hipErrorInvalidValue;
+}
+
+// poly_round's walk restated on the host, slot by slot, for the tile-walk tests (RRX_debug_tile_walk): the block's table
+// entry, the rounds, each wave's tile range and the group / column stepping come from the functions the kernel uses
+// (fused_block_info, fused_walk, walk_round, walk_seek, walk_ncs), and so do a lane's window start, its output index and the
+// round's output count (walk_lane_li, walk_lane_ib, walk_round_cnt); a slot is one lane of one tile.
+size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int *slots, size_t cap)
+{
+  const FusedBlock fb = fused_block_info(p, k);
+  const int pl = p.polyL, step = p.step, ngrp = (pl + 15) >> 4;
+  const FusedWalk fw = fused_walk(fb, ngrp);
+  const FusedWalk uni = {0, ngrp, fb.KA};
+  const long long h[13] = {fb.i_lo, fb.cnt, fb.K, fb.KA, fb.walk < 0, fw.g_lo, fw.g_hi, fw.ka,
+                           fb.cnt > 0 ? fused_walk_tiles(fw, fb.K, ngrp) : 0, fb.cnt > 0 ? fused_walk_tiles(uni, fb.K, ngrp) : 0,
+                           fb.irel_lo, fb.base_li, ngrp};
+  for (int i = 0; i < 13; ++i) head[i] = h[i];
+  size_t n = 0;
+  if (fb.cnt <= 0) return 0;
+  for (int round = 0; round < 2; ++round) {
+    const int kb = round ? fw.ka : 0, ke = round ? fb.K : fw.ka;
+    if (ke <= kb) continue;
+    const WalkRound wr = walk_round(fw, fb.K, kb, ke, ngrp);
+    const int cnt = walk_round_cnt(fb, fw, ke, pl);
+    for (int wave = 0; wave < 4; ++wave) {
+      const int t0 = (wr.nt * wave) >> 2, t1 = (wr.nt * (wave + 1)) >> 2;
+      if (t0 >= t1) continue;
+      int g, c;
+      walk_seek(wr, t0, g, c);
+      int pc = 4 * c + walk_p0(fw, g), pend = walk_p0(fw, g) + 4 * walk_ncs(fw, fb.K, kb, ke, g);
+      for (int left = t1 - t0; left > 0; --left) {
+        for (int lane = 0; lane < 64; ++lane) {
+          const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3, rloc = 4 * bq + hi;
+          const long long a0 = p.at0 + (long long)(16 * g + 4 * bq) * step; // qtab: window start of the 4-residue block
+          const int li = walk_lane_li(fb, kb, hi, jq, step) + int(a0 / pl) + pc * step;
+          const int ib = walk_lane_ib(fb, kb, jq, rloc, pl) + 16 * g + pc * pl;
+          if (n < cap) {
+            int *o = slots + 7 * n;
+            o[0] = round, o[1] = g, o[2] = (pc - walk_p0(fw, g)) >> 2, o[3] = lane, o[4] = ib;
+            o[5] = ib >= 0 && ib < cnt && 16 * g + rloc < pl;
+            o[6] = li;
+          }
+          ++n;
+        }
+        if (pc + 4 == pend) { // the group's last tile
+          ++g;
+          pc = walk_p0(fw, g);
+          pend = pc + 4 * walk_ncs(fw, fb.K, kb, ke, g);
+        } else
+          pc += 4;
+      }
+    }
+  }
+  return n;
 }
 
 bool fused_fast_supported(int log2n, int log2p, int ksteps)

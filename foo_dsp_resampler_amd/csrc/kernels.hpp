@@ -157,6 +157,11 @@ struct FusedBlock {
   int base_li;    // kk_lo * step - b0: window start of (period kk_lo, residue r) is qr(r) + base_li
   int K;          // periods touched by [i_lo, i_lo + cnt)
   int KA;         // matrix-pipe variant: periods [0, KA) are computed from the first LDS image, the rest from the second
+  // lean kernels' tile walk (fused_walk below): bit 31 set = every 16-residue group starts at its OWN first period; bits 0-9
+  // the first group whose residues do not all lie below irel_lo (groups in front of it start at period 1), bits 10-19 the
+  // first group whose residues all lie at or behind the block's last partial period (its groups end one period early),
+  // bits 20-30 the periods (counted from the group's first) that the first LDS image takes.  0 = the uniform walk of KA.
+  int walk;
   // seam outputs in front of this block (window straddles blocks B-1 | B): indices [seam_i0, i_lo); output seam_i0 has
   // phase seam_ph0 and its window starts seam_q0 samples into the [tail of B-1 | head of B] image (seam_kernel)
   long long seam_i0;
@@ -174,6 +179,76 @@ struct FusedBlock {
 #define RSMP_WG2 0
 #endif
 constexpr int kFusedSA = RSMP_WG2 ? 14 : RSMP_WG4 ? 9 : 12, kFusedSB0 = kFusedSA - 2, kFusedWaves = RSMP_WG2 ? 2 : RSMP_WG4 ? 4 : 3;
+
+// The lean kernels' tile walk (fused_fast.hip: poly_round).  A tile is one 16-residue group x 4 consecutive periods.  Group g
+// owns periods [p0, pend) of the block (counted from kk_lo): p0 = 1 for the groups in front of g_lo, pend = K - 1 for the
+// groups from g_hi on.  A round of periods [kb, ke) gives group g the periods [kb + p0, min(ke + p0, pend)), so with
+// g_lo = 0 and g_hi = NGRP every group walks [kb, ke): the uniform walk.  The same functions serve the kernel, the block
+// table (fused_block_info) and the host-side enumeration behind RRX_debug_tile_walk.
+struct FusedWalk { int g_lo, g_hi, ka; }; // ka: the first round is [0, ka), the second [ka, K)
+__host__ __device__ inline FusedWalk fused_walk(const FusedBlock &fb, int ngrp)
+{
+  if (fb.walk >= 0) return FusedWalk{0, ngrp, fb.KA};
+  return FusedWalk{fb.walk & 1023, (fb.walk >> 10) & 1023, (fb.walk >> 20) & 2047};
+}
+__host__ __device__ inline int walk_p0(const FusedWalk &w, int g) { return g < w.g_lo ? 1 : 0; }
+// column steps of group g in the round [kb, ke); a group with nothing in the round keeps one (all its lanes are dropped by
+// the store's range check), so that the walk never has to jump over a group
+__host__ __device__ inline int walk_ncs(const FusedWalk &w, int K, int kb, int ke, int g)
+{
+  const int p0 = walk_p0(w, g), pend = g >= w.g_hi ? K - 1 : K;
+  const int e = ke + p0 < pend ? ke + p0 : pend, n = (e - kb - p0 + 3) >> 2;
+  return n > 0 ? n : 1;
+}
+// A round's tiles in group-major order: the groups form at most three runs of equal column-step count, [0, b1), [b1, b2)
+// and [b2, ngrp), which start at tiles 0, T1 and T2 of the round's nt.
+// Invariant the kernel's group switch relies on: walk_p0 and walk_ncs are constant inside each run (they depend on g only
+// through g < g_lo and g >= g_hi), so poly_round refetches them only when the next group is b1 or b2.
+struct WalkRound { int b1, b2, n0, n1, n2, T1, T2, nt; };
+__host__ __device__ inline WalkRound walk_round(const FusedWalk &w, int K, int kb, int ke, int ngrp)
+{
+  WalkRound r;
+  const int lo = w.g_lo < ngrp ? w.g_lo : ngrp, hi = w.g_hi < ngrp ? w.g_hi : ngrp;
+  r.b1 = lo < hi ? lo : hi;
+  r.b2 = lo < hi ? hi : lo;
+  r.n0 = walk_ncs(w, K, kb, ke, 0);
+  r.n1 = walk_ncs(w, K, kb, ke, r.b1);
+  r.n2 = walk_ncs(w, K, kb, ke, r.b2);
+  r.T1 = r.b1 * r.n0;
+  r.T2 = r.T1 + (r.b2 - r.b1) * r.n1;
+  r.nt = r.T2 + (ngrp - r.b2) * r.n2;
+  return r;
+}
+// tile t of the round -> its group and column step (the one integer division of a wave's walk)
+__host__ __device__ inline void walk_seek(const WalkRound &r, int t, int &g, int &c)
+{
+  int gb = 0, tb = 0, n = r.n0;
+  if (t >= r.T2) {
+    gb = r.b2, tb = r.T2, n = r.n2;
+  } else if (t >= r.T1) {
+    gb = r.b1, tb = r.T1, n = r.n1;
+  }
+  const int dg = (t - tb) / n;
+  g = gb + dg;
+  c = t - tb - dg * n;
+}
+// A lane's part of a tile's addresses in the round that starts at period kb (lane = 16 hi + 4 bq + jq, rloc = 4 bq + hi): the
+// window of (group g, period offset pc) starts at walk_lane_li + q(g, bq) + pc * step, its output is number
+// walk_lane_ib + 16 g + pc * polyL of the block, kept when that lies in [0, walk_round_cnt).
+__host__ __device__ inline int walk_lane_li(const FusedBlock &fb, int kb, int hi, int jq, int step) { return fb.base_li + hi + (kb + jq) * step; }
+__host__ __device__ inline int walk_lane_ib(const FusedBlock &fb, int kb, int jq, int rloc, int pl) { return (kb + jq) * pl + rloc - fb.irel_lo; }
+// outputs of the block that a round up to period ke may store: the round ends at period ke for the groups that start at 0
+// and at ke + 1 for the others (a group that starts at 0 has exact column steps there and never reaches period ke)
+__host__ __device__ inline int walk_round_cnt(const FusedBlock &fb, const FusedWalk &w, int ke, int pl)
+{
+  const int irel_hi = fb.irel_lo + fb.cnt, e = (ke + (w.g_lo > 0 ? 1 : 0)) * pl;
+  return (irel_hi < e ? irel_hi : e) - fb.irel_lo;
+}
+// tiles of a block: both rounds (the second only when the first leaves periods over)
+__host__ __device__ inline int fused_walk_tiles(const FusedWalk &w, int K, int ngrp)
+{
+  return (w.ka > 0 ? walk_round(w, K, 0, w.ka, ngrp).nt : 0) + (w.ka < K ? walk_round(w, K, w.ka, K, ngrp).nt : 0);
+}
 
 // Closed forms of a block's bookkeeping; evaluated by fused_prep_kernel on the device (one thread per block of the
 // launch) and by the engine for its consistency checks.
@@ -208,6 +283,7 @@ __host__ __device__ inline FusedBlock fused_block_info(const FusedPrepArgs &p, i
   fb.base_li = int(kk_lo * p.step - b0);
   fb.K = fb.cnt > 0 ? int((ihi - 1) / p.polyL - kk_lo) + 1 : 0;
   fb.KA = fb.K;
+  int fit = fb.K; // periods (from 0) whose windows end inside the first LDS image: all of them unless there are two
   { // first output whose window starts at or behind the previous block's tail: (b0 - (n - 1)) * L - at0 over step, rounded up
     const long long ns = (b0 - (p.n - 1)) * p.polyL - p.at0;
     const long long s0 = ns <= 0 ? 0 : (ns + p.step - 1) / p.step;
@@ -225,6 +301,44 @@ __host__ __device__ inline FusedBlock fused_block_info(const FusedPrepArgs &p, i
     // ceil(K / 4) column steps of 4 periods together instead of one more
     const int k4 = fb.KA & ~3;
     if (fb.KA < fb.K && k4 > 0 && fb.base_li + p.qb_min + k4 * p.step >= rb_start) fb.KA = k4;
+    fit = ka;
+  }
+  // Per-group period ranges.  Residues >= irel_lo own periods 0 .., the others 1 ..; residues below (irel_lo + cnt) mod polyL
+  // own the last period K - 1, the others end at K - 2: a group whose 16 residues agree needs one column step of 4 periods
+  // less than ceil(K / 4) whenever K is one past a multiple of 4 -- the common case, since a block's first output has an
+  // arbitrary residue.  With two LDS images the split moves with the group's start, group g's periods [p0_g, p0_g + 4a) go
+  // to the first image: the last of them (4a - 1, or 4a where some group starts at 1) must end inside it, and period 4a of
+  // a group that starts at 0 must start inside the second -- the conditions of KA above.  Among the a that satisfy both the
+  // one with the fewest tiles is taken; where there is none, or the uniform walk has fewer tiles, `walk` stays 0.
+  fb.walk = 0;
+  const int ngrp = (p.polyL + 15) >> 4;
+  if (fb.cnt > 0 && ngrp <= 1023 && fb.K <= 2047) {
+    FusedWalk w;
+    w.g_lo = fb.irel_lo >> 4;
+    w.g_hi = (fb.irel_lo + fb.cnt - 1 - (fb.K - 1) * p.polyL + 16) >> 4;
+    w.ka = fb.K;
+    const int p1 = w.g_lo > 0 ? 1 : 0;                  // some group starts at period 1
+    const int maxlen = w.g_lo < w.g_hi ? fb.K : fb.K - 1; // periods of the longest group
+    int best = -1, best_ka = 0;
+    if (fit >= fb.K) {
+      best = fused_walk_tiles(w, fb.K, ngrp);
+      best_ka = fb.K;
+    } else {
+      for (int a4 = 4; a4 + p1 <= fit; a4 += 4) {
+        const bool all = a4 >= maxlen; // nothing left for the second image: one round
+        if (!all && fb.base_li + p.qb_min + a4 * p.step < rb_start) continue;
+        w.ka = all ? fb.K : a4;
+        const int t = fused_walk_tiles(w, fb.K, ngrp);
+        if (best < 0 || t < best) {
+          best = t;
+          best_ka = w.ka;
+        }
+        if (all) break;
+      }
+    }
+    const FusedWalk u = {0, ngrp, fb.KA};
+    if (best >= 0 && best <= fused_walk_tiles(u, fb.K, ngrp))
+      fb.walk = int(0x80000000u | unsigned(w.g_lo) | unsigned(w.g_hi) << 10 | unsigned(best_ka) << 20);
   }
   return fb;
 }
@@ -330,6 +444,11 @@ hipError_t launch_seam(int dst_f32, const F32View &df, const F64View &dd, const 
 bool fused_shape_supported(int log2n, int log2p, int n, int span, int max_seam_outputs);
 bool fused_mfma_supported(int log2n, int log2p, int ksteps);
 hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st);
+// host only (test hook): every (round, group, column step, lane) slot of entry k's tile walk in the lean kernels, 7 ints per slot
+// (round, group, column step, lane, output index relative to i_lo, 1 if the store's range check keeps it, window start);
+// head[13] = i_lo, cnt, K, KA, per-group walk?, g_lo, g_hi, ka, tiles, tiles of the uniform walk, irel_lo, base_li, groups.
+// Returns the number of slots (only the first `cap` are written).
+size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int *slots, size_t cap);
 
 // standalone rational polyphase stage on the matrix pipe (polymf.hip)
 struct PolyMfArgs {

@@ -81,6 +81,21 @@ int RRX_profile_report(RR_handle *h, char *buf, size_t cap);
  * longer describe the device fifos; the reference has no recovery path either, chain.h:26-29 tears the chain down). */
 void RRX_debug_fail_alloc(int nth);
 
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the tile walk of the lean
+ * fused kernels' polyphase stage for block `k` of a launch that starts at block B0, from the same closed forms the kernels
+ * and their block table use.  Geometry: the polyphase stage (polyL phases of n taps, clock step `step`, initial clock at0,
+ * preload b_offset of its input fifo), V valid samples per block, KS k-steps of 4 taps, window starts of the 4-residue
+ * blocks within [qb_min, qb_max]; two_round = 1 with the two LDS images [0, ra_end) and [rb_start, V) (ra_end = 0: the lean
+ * kernel's own 3072 / 2560); nsub > 0: sub-blocks of Vs samples.  slots receives 7 ints per (round, group, column step,
+ * lane): those four, the output index relative to head[0], whether the store keeps it, and the window's first sample;
+ * head[13] = i_lo, cnt, K, KA, per-group walk (1) or uniform (0), g_lo, g_hi, periods of the first round, tiles, tiles of
+ * the uniform walk, irel_lo, base_li, groups.  Returns the number of slots of the block (at most cap are written). */
+typedef struct RRX_walk_geom {
+  long long at0, b_offset, B0;
+  int V, polyL, step, n, KS, qb_min, qb_max, two_round, ra_end, rb_start, nsub, Vs;
+} RRX_walk_geom;
+long long RRX_debug_tile_walk(const RRX_walk_geom *geom, int k, long long *head, int *slots, size_t cap);
+
 /* Sample formats.  A handle gets its format when it is opened and keeps it: every handle opened by the calls above is
  * RRX_FMT_FLOAT (interleaved float32, fb_sample_t).  An RRX_FMT_DOUBLE handle takes and gives interleaved float64 frames
  * at both ends; the chain in between is the same fp64 arithmetic, stage kernels and geometry as on a float handle of the

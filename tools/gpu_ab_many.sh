@@ -14,7 +14,7 @@ for spec in "$@"; do
   while [ -n "$rest" ]; do rest=${rest#@}; e=${rest%%@*}; envs+=("$e"); rest=${rest#"$e"}; done
   if [ "$v" = base ]; then so=""; else so="RATELIB_AMD_SO=$PWD/foo_dsp_resampler_amd/libratelib_amd_$v.so"; fi
   tag=$(echo "$spec" | tr '@=' '__')
-  env $so "${envs[@]}" timeout -k 10 120 python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-check > $O/$tag.json 2> $O/$tag.err || { echo "$spec FAILED"; tail -3 $O/$tag.err; continue; }
+  env $so "${envs[@]}" timeout -k 10 120 python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-check > $O/$tag.json 2> $O/$tag.err || { echo "$spec FAILED"; tail -3 $O/$tag.err; exit 1; } # nothing more on a GPU that a run has just failed on
   python3 -c "
 import json; d=json.load(open('$O/$tag.json')); r=d['roofline']; print('%-24s' % '$spec', d['value'], d['ms_per_step'], {k.replace('rsmp::',''): round(v, 4) for k, v in r['kernels_ms_per_step'].items()})"
 done
