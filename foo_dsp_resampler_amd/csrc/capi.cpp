@@ -84,6 +84,52 @@ template <class Fn> int guarded(RR_handle *h, Fn fn)
   return finish(rc);
 }
 
+// The data calls, for host and for device memory: `format` is what the caller believes the buffers hold and must be the
+// handle's.  It is checked before anything moves, so a mismatch leaves the handle as it was.
+int push_host(RR_handle *h, int format, const void *ibuf, size_t in_stride, size_t isamp)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->push_host(ibuf, in_stride, isamp); });
+}
+
+int pull_host(RR_handle *h, int format, void *obuf, size_t out_stride, size_t osamp, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->pull_host(obuf, out_stride, osamp, ogen); });
+}
+
+int flow_host(RR_handle *h, int format, const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp, size_t osamp,
+              size_t *iused, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->flow_host(ibuf, in_stride, obuf, out_stride, isamp, osamp, iused, ogen); });
+}
+
+int push_device(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, size_t isamp)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->push_device(d_ibuf, in_stride, isamp); });
+}
+
+int pull_device(RR_handle *h, int format, void *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->pull_device(d_obuf, out_stride, osamp, ogen); });
+}
+
+int flow_device(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, void *d_obuf, size_t out_stride, size_t isamp,
+                size_t osamp, size_t *iused, size_t *ogen)
+{
+  if (!h) return RR_NULLHANDLE;
+  if (h->eng->format() != format) return RR_INVPARAM;
+  return guarded(h, [&] { return h->eng->flow_device(d_ibuf, in_stride, d_obuf, out_stride, isamp, osamp, iused, ogen); });
+}
+
 // device: -1 = the default placement (RATELIB_AMD_DEVICES round-robin, else the calling thread's current device)
 int open_common(const RR_config *config, int nchannels, int nstreams, int device, RR_handle **const handle, int format = RRX_FMT_FLOAT)
 {
@@ -164,127 +210,66 @@ int RRX_open_batch_fmt(const RR_config *config, int nchannels, int nstreams, int
 
 int RRX_format(const RR_handle *h) { return h ? h->eng->format() : -1; }
 
-// The double and format-tagged forms hand the engine their buffers behind a float pointer: the engine moves a handle's frames
-// as raw memory (Engine::eb_ bytes per sample) and its kernels read them as the handle's type (kFramesF64 / kFramesS16 / ...).
-namespace {
-inline const float *cwords(const void *p) { return reinterpret_cast<const float *>(p); }
-inline float *words(void *p) { return reinterpret_cast<float *>(p); }
-} // namespace
-
-// One format-tagged set for all four formats: `format` is what the caller believes the buffer holds and must be the handle's
-// (checked before anything moves: a mismatch leaves the handle as it was).  On float and double handles this is the code path
-// of RRX_*_strided / RRX_*_device and RRX_*_double.
+// One format-tagged set for all four formats; on float and double handles this is the code path of RRX_*_strided /
+// RRX_*_device and RRX_*_double.
 int RRX_push_samples(RR_handle *h, int format, const void *ibuf, size_t in_stride, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != format) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->push_host(cwords(ibuf), in_stride, isamp); });
-}
+{ return push_host(h, format, ibuf, in_stride, isamp); }
 
 int RRX_pull_samples(RR_handle *h, int format, void *obuf, size_t out_stride, size_t osamp, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != format) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->pull_host(words(obuf), out_stride, osamp, ogen); });
-}
+{ return pull_host(h, format, obuf, out_stride, osamp, ogen); }
 
 int RRX_flow_samples(RR_handle *h, int format, const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp,
                      size_t osamp, size_t *iused, size_t *ogen)
 {
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != format) return RR_INVPARAM;
-  if (h->eng->nstreams() == 1) in_stride = isamp, out_stride = osamp; // packed, as RR_flow
-  return guarded(h, [&] { return h->eng->flow_host(cwords(ibuf), in_stride, words(obuf), out_stride, isamp, osamp, iused, ogen); });
+  if (h && h->eng->nstreams() == 1) in_stride = isamp, out_stride = osamp; // packed, as RR_flow
+  return flow_host(h, format, ibuf, in_stride, obuf, out_stride, isamp, osamp, iused, ogen);
 }
 
 int RRX_push_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != format) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->push_device(cwords(d_ibuf), in_stride, isamp); });
-}
+{ return push_device(h, format, d_ibuf, in_stride, isamp); }
 
 int RRX_pull_device_samples(RR_handle *h, int format, void *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != format) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->pull_device(words(d_obuf), out_stride, osamp, ogen); });
-}
+{ return pull_device(h, format, d_obuf, out_stride, osamp, ogen); }
 
 int RRX_flow_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, void *d_obuf, size_t out_stride,
                             size_t isamp, size_t osamp, size_t *iused, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != format) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->flow_device(cwords(d_ibuf), in_stride, words(d_obuf), out_stride, isamp, osamp, iused, ogen); });
-}
+{ return flow_device(h, format, d_ibuf, in_stride, d_obuf, out_stride, isamp, osamp, iused, ogen); }
 
 int RRX_push_double(RR_handle *h, const double *ibuf, size_t in_stride, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->push_host(cwords(ibuf), in_stride, isamp); });
-}
+{ return push_host(h, RRX_FMT_DOUBLE, ibuf, in_stride, isamp); }
 
 int RRX_pull_double(RR_handle *h, double *obuf, size_t out_stride, size_t osamp, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->pull_host(words(obuf), out_stride, osamp, ogen); });
-}
+{ return pull_host(h, RRX_FMT_DOUBLE, obuf, out_stride, osamp, ogen); }
 
 int RRX_flow_double(RR_handle *h, const double *ibuf, size_t in_stride, double *obuf, size_t out_stride, size_t isamp, size_t osamp,
                     size_t *iused, size_t *ogen)
 {
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
-  if (h->eng->nstreams() == 1) in_stride = isamp, out_stride = osamp; // packed, as RR_flow
-  return guarded(h, [&] { return h->eng->flow_host(cwords(ibuf), in_stride, words(obuf), out_stride, isamp, osamp, iused, ogen); });
+  if (h && h->eng->nstreams() == 1) in_stride = isamp, out_stride = osamp; // packed, as RR_flow
+  return flow_host(h, RRX_FMT_DOUBLE, ibuf, in_stride, obuf, out_stride, isamp, osamp, iused, ogen);
 }
 
 int RRX_push_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->push_device(cwords(d_ibuf), in_stride, isamp); });
-}
+{ return push_device(h, RRX_FMT_DOUBLE, d_ibuf, in_stride, isamp); }
 
 int RRX_pull_device_double(RR_handle *h, double *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->pull_device(words(d_obuf), out_stride, osamp, ogen); });
-}
+{ return pull_device(h, RRX_FMT_DOUBLE, d_obuf, out_stride, osamp, ogen); }
 
 int RRX_flow_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride, double *d_obuf, size_t out_stride, size_t isamp,
                            size_t osamp, size_t *iused, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_DOUBLE) return RR_INVPARAM;
-  return guarded(h, [&] { return h->eng->flow_device(cwords(d_ibuf), in_stride, words(d_obuf), out_stride, isamp, osamp, iused, ogen); });
-}
+{ return flow_device(h, RRX_FMT_DOUBLE, d_ibuf, in_stride, d_obuf, out_stride, isamp, osamp, iused, ogen); }
 
-int RR_push(RR_handle *h, const fb_sample_t *ibuf, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  return guarded(h, [&] { return h->eng->push_host(ibuf, isamp, isamp); });
-}
+int RR_push(RR_handle *h, const fb_sample_t *ibuf, size_t isamp) { return push_host(h, RRX_FMT_FLOAT, ibuf, isamp, isamp); }
 
 int RR_pull(RR_handle *h, fb_sample_t *obuf, size_t osamp, size_t *ogen)
 {
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  size_t n = osamp < h->eng->available() ? osamp : h->eng->available();
-  return guarded(h, [&] { return h->eng->pull_host(obuf, n, osamp, ogen); });
+  const size_t n = h ? (osamp < h->eng->available() ? osamp : h->eng->available()) : 0; // (one stream: the stride is not used)
+  return pull_host(h, RRX_FMT_FLOAT, obuf, n, osamp, ogen);
 }
 
 int RR_flow(RR_handle *h, const fb_sample_t *ibuf, fb_sample_t *obuf, size_t isamp, size_t osamp, size_t *iused, size_t *ogen)
 {
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  if (h->eng->nstreams() != 1) return RR_INVPARAM; // packed layout of a batch is ambiguous here
-  return guarded(h, [&] { return h->eng->flow_host(ibuf, isamp, obuf, osamp, isamp, osamp, iused, ogen); });
+  if (h && h->eng->nstreams() != 1) return RR_INVPARAM; // packed layout of a batch is ambiguous here
+  return flow_host(h, RRX_FMT_FLOAT, ibuf, isamp, obuf, osamp, isamp, osamp, iused, ogen);
 }
 
 int RR_drain(RR_handle *h)
@@ -315,40 +300,20 @@ const char *RR_strerror(int error)
 }
 
 int RRX_push_device(RR_handle *h, const fb_sample_t *d_ibuf, size_t in_stride, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  return guarded(h, [&] { return h->eng->push_device(d_ibuf, in_stride, isamp); });
-}
+{ return push_device(h, RRX_FMT_FLOAT, d_ibuf, in_stride, isamp); }
 
 int RRX_pull_device(RR_handle *h, fb_sample_t *d_obuf, size_t out_stride, size_t osamp, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  return guarded(h, [&] { return h->eng->pull_device(d_obuf, out_stride, osamp, ogen); });
-}
+{ return pull_device(h, RRX_FMT_FLOAT, d_obuf, out_stride, osamp, ogen); }
 
 int RRX_flow_device(RR_handle *h, const fb_sample_t *d_ibuf, size_t in_stride, fb_sample_t *d_obuf, size_t out_stride,
                     size_t isamp, size_t osamp, size_t *iused, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  return guarded(h, [&] { return h->eng->flow_device(d_ibuf, in_stride, d_obuf, out_stride, isamp, osamp, iused, ogen); });
-}
+{ return flow_device(h, RRX_FMT_FLOAT, d_ibuf, in_stride, d_obuf, out_stride, isamp, osamp, iused, ogen); }
 
 int RRX_push_strided(RR_handle *h, const fb_sample_t *ibuf, size_t in_stride, size_t isamp)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  return guarded(h, [&] { return h->eng->push_host(ibuf, in_stride, isamp); });
-}
+{ return push_host(h, RRX_FMT_FLOAT, ibuf, in_stride, isamp); }
 
 int RRX_pull_strided(RR_handle *h, fb_sample_t *obuf, size_t out_stride, size_t osamp, size_t *ogen)
-{
-  if (!h) return RR_NULLHANDLE;
-  if (h->eng->format() != RRX_FMT_FLOAT) return RR_INVPARAM; // (before anything moves: the handle stays as it was)
-  return guarded(h, [&] { return h->eng->pull_host(obuf, out_stride, osamp, ogen); });
-}
+{ return pull_host(h, RRX_FMT_FLOAT, obuf, out_stride, osamp, ogen); }
 
 int RRX_set_stream(RR_handle *h, void *hip_stream)
 {

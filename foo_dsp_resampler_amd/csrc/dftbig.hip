@@ -241,10 +241,8 @@ static hipError_t launch_rows(const BigDftArgs &a, int nitems, hipStream_t st)
 }
 
 // `a.item0` / workspaces are filled in here per chunk: at most `ws_items` (block, pair) items are in flight at once.
-hipError_t launch_dft_big(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd,
-                          BigDftArgs a, int ws_items, hipStream_t st)
+hipError_t launch_dft_big(const AnyView &in, const AnyView &out, BigDftArgs a, int ws_items, hipStream_t st)
 {
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   a.d.npairs = pair_count(a.d.C, a.d.nchs);
   a.d.pps_magic = pair_magic(a.d.C, a.d.nchs);
   const int npairs = a.d.npairs;

@@ -286,9 +286,9 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
 // other path and trap if the kernel's own pair_span ever disagrees with this.
 static bool span_contiguous(const AnyView &v, long long a0, long long len, int C)
 {
-  if (v.is_f32 && ((v.f.nch & 1) || (C & 1))) return false;
-  const int npairs = C / 2, hp = v.is_f32 ? v.f.nch / 2 : npairs;
-  const int want = v.is_f32 == kFramesF64 ? 3 : v.is_f32 == kFramesS16 ? 4 : v.is_f32 == kFramesS32 ? 5 : v.is_f32 ? 1 : 2;
+  if (v.kind && ((v.f.nch & 1) || (C & 1))) return false;
+  const int npairs = C / 2, hp = v.kind ? v.f.nch / 2 : npairs;
+  const int want = v.kind == kFramesF64 ? 3 : v.kind == kFramesS16 ? 4 : v.kind == kFramesS32 ? 5 : v.kind ? 1 : 2;
   for (int pair : {0, hp < npairs ? hp : 0, npairs - 1})
     if (pair_span(v, pair, true, a0, len).kind != want) return false;
   return true;
@@ -312,7 +312,7 @@ template <int LL> static hipError_t launch_dftx_t(const AnyView &in, const AnyVi
   b.npairs = pair_count(a.C, a.nchs);
   b.pps_magic = pair_magic(a.C, a.nchs);
   const bool clip_all = a.clip_lo <= a.B0 * (long long)a.Vout && (a.B0 + a.nblocks) * (long long)a.Vout <= a.clip_hi;
-  const bool int_in = in.is_f32 >= kFramesS16; // (a x4 / x8 stage that is the chain's first: the generic instance converts)
+  const bool int_in = in.kind >= kFramesS16; // (a x4 / x8 stage that is the chain's first: the generic instance converts)
   auto fast = [&](int k) {
     const long long B = a.B0 + k;
     return clip_all && !int_in && span_contiguous(in, B * a.q, kP, a.C) && span_contiguous(out, a.out_offset + B * a.Vout, a.Vout, a.C);
@@ -324,10 +324,10 @@ template <int LL> static hipError_t launch_dftx_t(const AnyView &in, const AnyVi
     b.B0 = a.B0 + k;
     b.nblocks = e - k;
     const hipError_t rc = !f ? launch_dftx_run<LL, 0>(in, out, b, st)
-                         : out.is_f32 == kFramesF64 ? launch_dftx_run<LL, 3>(in, out, b, st)
-                         : out.is_f32 == kFramesS16 ? launch_dftx_run<LL, 4>(in, out, b, st)
-                         : out.is_f32 == kFramesS32 ? launch_dftx_run<LL, 5>(in, out, b, st)
-                         : out.is_f32 ? launch_dftx_run<LL, 1>(in, out, b, st) : launch_dftx_run<LL, 2>(in, out, b, st);
+                         : out.kind == kFramesF64 ? launch_dftx_run<LL, 3>(in, out, b, st)
+                         : out.kind == kFramesS16 ? launch_dftx_run<LL, 4>(in, out, b, st)
+                         : out.kind == kFramesS32 ? launch_dftx_run<LL, 5>(in, out, b, st)
+                         : out.kind ? launch_dftx_run<LL, 1>(in, out, b, st) : launch_dftx_run<LL, 2>(in, out, b, st);
     if (rc != hipSuccess) return rc;
     k = e;
   }
@@ -340,10 +340,8 @@ bool dftx_supported(int log2n, int log2p, int log2nd)
   return !knobs().no_dftx && log2p == kXP && log2nd == log2n && (log2n == 13 || log2n == 14);
 }
 
-hipError_t launch_dftx(int log2n, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                       const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname)
+hipError_t launch_dftx(int log2n, const AnyView &in, const AnyView &out, const DftArgs &a, hipStream_t st, const char **kname)
 {
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   if (log2n == 13) {
     if (kname) *kname = "rsmp::dftx_kernel<4>";
     return launch_dftx_t<4>(in, out, a, st);

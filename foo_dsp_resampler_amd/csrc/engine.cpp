@@ -342,7 +342,7 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
   big_.assign(ns, BigDft());
   fuse_.assign(ns, Fuse());
   polymf_.assign(ns, PolyMf());
-  for (int i = 0; i <= ns; ++i) rings_[i].f32 = (i == 0 || i == ns);
+  for (int i = 0; i <= ns; ++i) rings_[i].frames = (i == 0 || i == ns);
   for (int i = 0; i < ns; ++i) {
     const StageSpec &sp = plan_.stages[i];
     book_.wr[i] = sp.preload; // rate_base.h:417-422
@@ -647,10 +647,10 @@ int Engine::join_side()
   return kOk;
 }
 
-int Engine::pinned_reserve(Pinned &b, size_t floats)
+int Engine::pinned_reserve(Pinned &b, size_t bytes)
 {
   if (!b.done) HIP_TRY(hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
-  if (b.floats >= floats) return kOk;
+  if (b.bytes >= bytes) return kOk;
   if (b.p) {
     // growing: queued work may still read or write the old block (a mirror being spilled into the device ring, a copy out of
     // it); nothing that is queued may outlive the block
@@ -658,16 +658,16 @@ int Engine::pinned_reserve(Pinned &b, size_t floats)
     (void)hipHostFree(b.p);
   }
   b.p = nullptr;
-  b.floats = 0;
-  size_t want = 4096;
-  while (want < floats) want <<= 1;
+  b.bytes = 0;
+  size_t want = 16384;
+  while (want < bytes) want <<= 1;
   void *p = nullptr;
-  if (hipHostMalloc(&p, want * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+  if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError();
     return kNoMem;
   }
-  b.p = static_cast<float *>(p);
-  b.floats = want;
+  b.p = p;
+  b.bytes = want;
   return kOk;
 }
 
@@ -759,38 +759,33 @@ int Engine::sync()
   return kOk;
 }
 
-F32View Engine::f32_view(int f, const ExtIn *ein, const ExtOut *eout) const
+AnyView Engine::view(int f, const ExtIn *ein, const ExtOut *eout) const
 {
   const Ring &r = rings_[f];
-  F32View v;
-  v.ring = static_cast<float *>(r.buf);
-  v.ring_mask = r.cap - 1;
-  v.ring_stream_stride = r.cap * nch_;
-  v.ext = nullptr;
-  v.ext_begin = v.ext_end = 0;
-  v.ext_stream_stride = 0;
-  v.nch = nch_;
-  if (ein && ein->ptr) {
-    v.ext = const_cast<float *>(ein->ptr);
-    v.ext_begin = ein->begin;
-    v.ext_end = ein->end;
-    v.ext_stream_stride = ein->stride_elems;
-  } else if (eout && eout->ptr) {
-    v.ext = eout->ptr;
-    v.ext_begin = eout->begin;
-    v.ext_end = eout->end;
-    v.ext_stream_stride = eout->stride_elems;
+  AnyView v = {};
+  if (!r.frames) {
+    v.kind = kRingF64;
+    v.d.ring = static_cast<double *>(r.buf);
+    v.d.mask = r.cap - 1;
+    v.d.chan_stride = r.cap;
+    return v;
   }
-  return v;
-}
-
-F64View Engine::f64_view(int f) const
-{
-  const Ring &r = rings_[f];
-  F64View v;
-  v.ring = static_cast<double *>(r.buf);
-  v.mask = r.cap - 1;
-  v.chan_stride = r.cap;
+  v.kind = fk_;
+  v.f.ring = r.buf;
+  v.f.ring_mask = r.cap - 1;
+  v.f.ring_stream_stride = r.cap * nch_;
+  v.f.nch = nch_;
+  if (ein && ein->ptr) {
+    v.f.ext = const_cast<void *>(ein->ptr);
+    v.f.ext_begin = ein->begin;
+    v.f.ext_end = ein->end;
+    v.f.ext_stream_stride = ein->stride_elems;
+  } else if (eout && eout->ptr) {
+    v.f.ext = eout->ptr;
+    v.f.ext_begin = eout->begin;
+    v.f.ext_end = eout->end;
+    v.f.ext_stream_stride = eout->stride_elems;
+  }
   return v;
 }
 
@@ -802,7 +797,7 @@ int Engine::ensure_ring(int f, long long live_needed)
   if (r.buf && r.cap >= live_needed) return kOk;
   { int rcj = join_side(); if (rcj) return rcj; } // seam kernels on the side stream may still write the old ring
   const long long cap = next_pow2(std::max<long long>({live_needed, r.cap * 2, 4096}));
-  const size_t bytes = r.f32 ? size_t(cap) * nch_ * S_ * size_t(eb_) : size_t(cap) * C_ * sizeof(double);
+  const size_t bytes = r.frames ? size_t(cap) * nch_ * S_ * size_t(eb_) : size_t(cap) * C_ * sizeof(double);
   void *nb = nullptr;
   ALLOC_TRY(&nb, bytes);
   HIP_TRY(hipMemsetAsync(nb, 0, bytes, stream_));
@@ -811,22 +806,18 @@ int Engine::ensure_ring(int f, long long live_needed)
     r.buf = nb;
     r.cap = cap;
     const long long a0 = book_.rd[f], a1 = book_.wr[f];
-    F32View sf = {}, df = {};
-    F64View sd = {}, dd = {};
-    if (r.f32) {
-      df = f32_view(f, nullptr, nullptr);
-      sf = df;
-      sf.ring = static_cast<float *>(old.buf);
-      sf.ring_mask = old.cap - 1;
-      sf.ring_stream_stride = old.cap * nch_;
+    const AnyView dst = view(f);
+    AnyView src = dst; // the same fifo in the old ring
+    if (r.frames) {
+      src.f.ring = old.buf;
+      src.f.ring_mask = old.cap - 1;
+      src.f.ring_stream_stride = old.cap * nch_;
     } else {
-      dd = f64_view(f);
-      sd = dd;
-      sd.ring = static_cast<double *>(old.buf);
-      sd.mask = old.cap - 1;
-      sd.chan_stride = old.cap;
+      src.d.ring = static_cast<double *>(old.buf);
+      src.d.mask = old.cap - 1;
+      src.d.chan_stride = old.cap;
     }
-    HIP_TRY(launch_copy(r.f32 ? fk_ : 0, sf, sd, df, dd, a0, a1, C_, stream_));
+    HIP_TRY(launch_copy(src, dst, a0, a1, C_, stream_));
     garbage_.push_back(old.buf);
   } else {
     r.buf = nb;
@@ -856,20 +847,18 @@ void Engine::note_input(Book &b, size_t n) const
   long long &rd = b.rd[i];                                                                                         \
   long long &wro = b.wr[(i) + 1];                                                                                  \
   const long long occ = b.wr[i] - rd;                                                                              \
-  /* frame kind of each end (0 = fp64 ring): the launchers' src_f32 / dst_f32, also read as "frames?" */               \
-  const int src_f32 = (i) == 0 ? fk_ : 0, dst_f32 = (i) + 1 == ns ? fk_ : 0;                                     \
+  /* which ends are caller-facing frames (the others are fp64 rings) */                                            \
+  const bool src_frames = (i) == 0, dst_frames = (i) + 1 == ns;                                                    \
   const long long rd_before = rd, wro_before = wro;                                                                \
   const long long out_offset = (i) + 1 < ns ? plan_.stages[(i) + 1].preload : -b.trimmed;                          \
-  const F32View nof = {};                                                                                          \
-  const F64View nod = {};                                                                                          \
   Pending &pend = (ps).pend;                                                                                       \
   /* what the destination ring must be able to hold once this stage has run */                                    \
   auto dst_need = [&](long long wr_after) {                                                                        \
-    if (dst_f32 && eout.ptr) return std::max<long long>(0, wr_after - std::max(eout.end, b.rd[(i) + 1]));         \
+    if (dst_frames && eout.ptr) return std::max<long long>(0, wr_after - std::max(eout.end, b.rd[(i) + 1]));      \
     return wr_after - b.rd[(i) + 1];                                                                               \
   };                                                                                                               \
-  (void)rd_before; (void)wro_before; (void)out_offset; (void)occ; (void)src_f32; (void)dst_f32; (void)launch;      \
-  (void)ein; (void)nof; (void)nod; (void)pend; (void)st; (void)dst_need
+  (void)rd_before; (void)wro_before; (void)out_offset; (void)occ; (void)src_frames; (void)dst_frames;             \
+  (void)launch; (void)ein; (void)pend; (void)st; (void)dst_need
 
 // One pass of rate_process (rate_base.h:425-432) after `n_new` frames were appended to fifo 0: every stage runs once over
 // what is available.  With launch == false only the counters move (used to size a drain or a host mirror).
@@ -965,9 +954,7 @@ int Engine::advance_dft(Pass &ps, int i)
       ba.fdomain_in = (log2p < log2n || L == 1) ? 1 : 0;
       ba.item0 = 0;
       const int pi = prof_begin(true, "rsmp::big_cols_fwd_kernel + big_rows_kernel + big_cols_inv_kernel");
-      HIP_TRY(launch_dft_big(src_f32, dst_f32, src_f32 ? f32_view(i, &ein, nullptr) : nof, src_f32 ? nod : f64_view(i),
-                             dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), ba, bg.ws_items,
-                             stream_));
+      HIP_TRY(launch_dft_big(view(i, &ein), view(i + 1, nullptr, &eout), ba, bg.ws_items, stream_));
       prof_end(pi);
     } else
     if (fused) { // launched together with the polyphase stage below
@@ -979,16 +966,13 @@ int Engine::advance_dft(Pass &ps, int i)
     } else if (a.Gr && sp.step == 1 && fdomain_up(L) && dftx_supported(log2n, log2p, log2nd)) {
       const int pi = prof_begin(true);
       const char *kn = nullptr;
-      HIP_TRY(launch_dftx(log2n, src_f32, dst_f32, src_f32 ? f32_view(i, &ein, nullptr) : nof, src_f32 ? nod : f64_view(i),
-                          dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), a, stream_, &kn));
+      HIP_TRY(launch_dftx(log2n, view(i, &ein), view(i + 1, nullptr, &eout), a, stream_, &kn));
       prof_name(pi, kn);
       prof_end(pi);
     } else {
     const int pi = prof_begin(true);
     const char *kn = nullptr;
-    HIP_TRY(launch_dft(log2n, log2p, log2nd, src_f32, dst_f32, src_f32 ? f32_view(i, &ein, nullptr) : nof,
-                       src_f32 ? nod : f64_view(i), dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof,
-                       dst_f32 ? nod : f64_view(i + 1), a, stream_, &kn));
+    HIP_TRY(launch_dft(log2n, log2p, log2nd, view(i, &ein), view(i + 1, nullptr, &eout), a, stream_, &kn));
     prof_name(pi, kn);
     prof_end(pi);
     }
@@ -1095,7 +1079,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   // ... and only when another slab of this push follows: seam(k) then runs beside fused(k+1).  Behind the LAST fused
   // launch of a push the side stream has nothing to overlap with but the small carry copy, and the two cross-queue
   // hand-overs (event -> side stream -> join) cost more than they hide: 2.455 against 2.505 ms per step measured.
-  const bool seam_on_side = more_slabs && !(profiling_ || !dst_f32 || no_side_);
+  const bool seam_on_side = more_slabs && !(profiling_ || !dst_frames || no_side_);
   // seam(k-2), possibly still pending on the side stream, reads the seam-ring slots AND the half of the block table
   // that this launch is about to overwrite: both the table fill and the fused launch wait for it.  (The table has
   // two halves, launch k uses half k & 1: seam(k-1) may still be reading the other one.  With ONE table, a push cut
@@ -1107,7 +1091,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   // the fused launch emits exactly the outputs [wro, wro + count): windows ending before wr of fifo i
   const long long endnum = (b.wr[i] - sp.n + 1) * sp.L - fa.at0;
   if (wro - out_offset + count != (endnum <= 0 ? 0 : (endnum + step - 1) / step)) return kInternal;
-  const bool s32 = i - 1 == 0;
+  const bool in_frames = i - 1 == 0;
   // Blocks whose input span and outputs lie in the caller's buffers as plain interleaved frames go to the lean
   // kernel (fused_fast.hip); the others (the block that straddles ring and buffer, ring wrap, odd channel counts,
   // fp64 rings on either side) to the generic one.  At most three launches: generic head, lean middle, generic tail.
@@ -1117,7 +1101,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   const uintptr_t amask = 2 * uintptr_t(eb_) - 1; // a channel pair of a frame as one word of two samples
   auto io_in = [&] { // the caller's frames from in_abs0 on, fifo 0's ring below them
     io.in = ein.ptr;
-    io.in_ring = static_cast<const float *>(rings_[0].buf);
+    io.in_ring = rings_[0].buf;
     io.in_ring_mask = rings_[0].cap - 1;
     io.in_ring_stream_stride = rings_[0].cap * nch_;
     io.in_abs0 = ein.begin;
@@ -1133,11 +1117,11 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     // Sub-blocked form: ONE launch of nblocks * nsub workgroups per channel pair.  Every sub-block's 4096-frame window lies
     // inside its block's own input span, i.e. in the caller's buffer or, below it, in fifo 0's ring; outputs go to the next
     // fifo's fp64 ring at any position.  (Decided when the handle was opened: first stage, even channels, not the last stage.)
-    if (!s32 || (nch_ & 1) || !ein.ptr || (ein.stride_elems & 1)) return kInternal;
+    if (!in_frames || (nch_ & 1) || !ein.ptr || (ein.stride_elems & 1)) return kInternal;
     io_in();
     io.in_unaligned = (reinterpret_cast<uintptr_t>(ein.ptr) & amask) ? 1 : 0;
     int omode = 1;
-    if (!dst_f32)
+    if (!dst_frames)
       io_out64();
     else {
       // float frames out: straight into the caller's buffer when every output of this launch lies inside it (a flow / a
@@ -1150,7 +1134,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       io.out_end = ext_ok ? eout.end : 0; // (empty range: every output goes to the ring)
       io.out_stream_stride = ext_ok ? eout.stride_elems : 0;
       io.out_unaligned = (ext_ok && (reinterpret_cast<uintptr_t>(eout.ptr) & amask)) ? 1 : 0;
-      io.out_ring = static_cast<float *>(rings_[i + 1].buf);
+      io.out_ring = rings_[i + 1].buf;
       io.out_ring_mask = rings_[i + 1].cap - 1;
       io.out_ring_stream_stride = rings_[i + 1].cap * nch_;
       if (eout.ptr && !ext_ok) return kInternal; // (an odd frame stride with an even channel count cannot happen)
@@ -1173,7 +1157,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     HIP_TRY(launch_fused_split(omode, fr, io, stream_, &kn));
     prof_name(pi, kn);
     prof_end(pi);
-  } else if (fu.cfm && s32 && dst_f32 && !(nch_ & 1) && ein.ptr && eout.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
+  } else if (fu.cfm && in_frames && dst_frames && !(nch_ & 1) && ein.ptr && eout.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
              !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(reinterpret_cast<uintptr_t>(eout.ptr) & amask) &&
              !(ein.stride_elems & 1) && !(eout.stride_elems & 1)) {
     const long long P = 1LL << pend_log2p, q = fa.d.q;
@@ -1193,7 +1177,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     io.out = eout.ptr;
     io.out_abs0 = eout.begin;
     io.out_stream_stride = eout.stride_elems;
-  } else if (fu.cfm && s32 && !dst_f32 && !(nch_ & 1) && ein.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
+  } else if (fu.cfm && in_frames && !dst_frames && !(nch_ & 1) && ein.ptr && fused_fast_supported(pend_log2n, pend_log2p, fu.KS) &&
              !(reinterpret_cast<uintptr_t>(ein.ptr) & amask) && !(ein.stride_elems & 1)) {
     // the polyphase stage feeds another stage: same lean kernel, its outputs into the next fifo's fp64 ring (any ring
     // position: the kernel masks the index), so only the input side limits the range
@@ -1214,9 +1198,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     const char *kn = nullptr;
     if (fast) HIP_TRY(launch_fused_fast(pend_log2p, fr, io, stream_, &kn));
     else
-      HIP_TRY(launch_fused(pend_log2n, pend_log2p, s32 ? fk_ : 0, dst_f32, s32 ? f32_view(0, &ein, nullptr) : nof,
-                           s32 ? nod : f64_view(i - 1), dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof,
-                           dst_f32 ? nod : f64_view(i + 1), fr, stream_, &kn));
+      HIP_TRY(launch_fused(pend_log2n, pend_log2p, view(i - 1, &ein), view(i + 1, nullptr, &eout), fr, stream_, &kn));
     prof_name(pi, kn);
     prof_end(pi);
     return kOk;
@@ -1229,12 +1211,12 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   if (!seam_on_side) {
     { int rcj = join_side(); if (rcj) return rcj; } // (a seam kernel of an earlier launch of this push may still be on the side stream)
     const int ps = prof_begin(false, "rsmp::seam_kernel");
-    HIP_TRY(launch_seam(dst_f32, dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), fa, stream_));
+    HIP_TRY(launch_seam(view(i + 1, nullptr, &eout), fa, stream_));
     prof_end(ps);
   } else {
     HIP_TRY(hipEventRecord(ev_fused_, stream_));
     HIP_TRY(hipStreamWaitEvent(side_, ev_fused_, 0));
-    HIP_TRY(launch_seam(dst_f32, dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), fa, side_));
+    HIP_TRY(launch_seam(view(i + 1, nullptr, &eout), fa, side_));
     HIP_TRY(hipEventRecord(ev_seam_[seam_launches_ & 1], side_));
     ++seam_launches_;
     side_pending_ = true;
@@ -1290,8 +1272,7 @@ int Engine::launch_polymf_stage(Pass &ps, int i, long long count, long long step
     a.nchs = pair_nchs();
     const int pi = prof_begin(false);
     const char *kn = nullptr;
-    HIP_TRY(launch_polymf(pm.KS, src_f32, dst_f32, src_f32 ? f32_view(i, &ein, nullptr) : nof, src_f32 ? nod : f64_view(i),
-                          dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), a, stream_, &kn));
+    HIP_TRY(launch_polymf(pm.KS, view(i, &ein), view(i + 1, nullptr, &eout), a, stream_, &kn));
     prof_name(pi, kn);
     prof_end(pi);
   }
@@ -1341,9 +1322,7 @@ int Engine::launch_poly_stage(Pass &ps, int i, long long count, long long step)
   }
   const int pi = prof_begin(false);
   const char *kn = nullptr;
-  HIP_TRY(launch_poly(sp.order, src_f32, dst_f32, src_f32 ? f32_view(i, &ein, nullptr) : nof,
-                      src_f32 ? nod : f64_view(i), dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof,
-                      dst_f32 ? nod : f64_view(i + 1), a, stream_, &kn));
+  HIP_TRY(launch_poly(sp.order, view(i, &ein), view(i + 1, nullptr, &eout), a, stream_, &kn));
   prof_name(pi, kn);
   prof_end(pi);
   return kOk;
@@ -1368,8 +1347,7 @@ int Engine::advance_half(Pass &ps, int i)
     for (int k = 0; k < 13; ++k) a.coef[k] = k < sp.hb_n ? sp.hb[k] : 0.0;
     const int pi = prof_begin(false);
     const char *kn = nullptr;
-    HIP_TRY(launch_half(src_f32, dst_f32, src_f32 ? f32_view(i, &ein, nullptr) : nof, src_f32 ? nod : f64_view(i),
-                        dst_f32 ? f32_view(i + 1, nullptr, &eout) : nof, dst_f32 ? nod : f64_view(i + 1), a, stream_, &kn));
+    HIP_TRY(launch_half(view(i, &ein), view(i + 1, nullptr, &eout), a, stream_, &kn));
     prof_name(pi, kn);
     prof_end(pi);
   }
@@ -1382,7 +1360,7 @@ int Engine::advance_half(Pass &ps, int i)
 // Append `isamp` frames that live in device memory at d_in ([stream][frame][ch], `stride_frames`
 // between streams) and run the chain.  If d_out is given and the output fifo is empty, up to
 // out_cap produced frames are written straight into d_out (and counted as pulled).
-int Engine::feed(const float *d_in, size_t stride_frames, size_t isamp, float *d_out, size_t out_stride, size_t out_cap,
+int Engine::feed(const void *d_in, size_t stride_frames, size_t isamp, void *d_out, size_t out_stride, size_t out_cap,
                  size_t *direct_out, bool keep_direct)
 {
   if (poisoned_) return kInternal;
@@ -1400,17 +1378,16 @@ int Engine::spill_mirror()
   if (a1 <= a0) return kOk;
   int rc = ensure_ring(f, book_.wr[f] - book_.rd[f]);
   if (rc) return rc;
-  F32View dst = f32_view(f, nullptr, nullptr), src = dst;
-  src.ext = pin_mir_.p; // frame `base` of stream 0
-  src.ext_begin = base;
-  src.ext_end = a1;
-  src.ext_stream_stride = (long long)mir_stride_ * nch_;
-  F64View nod = {};
-  HIP_TRY(launch_copy(fk_, src, nod, dst, nod, a0, a1, C_, stream_));
+  ExtIn mir;
+  mir.ptr = pin_mir_.p; // frame `base` of stream 0
+  mir.begin = base;
+  mir.end = a1;
+  mir.stride_elems = (long long)mir_stride_ * nch_;
+  HIP_TRY(launch_copy(view(f, &mir), view(f), a0, a1, C_, stream_));
   return kOk;
 }
 
-int Engine::feed_impl(const float *d_in, size_t stride_frames, size_t isamp, float *d_out, size_t out_stride, size_t out_cap,
+int Engine::feed_impl(const void *d_in, size_t stride_frames, size_t isamp, void *d_out, size_t out_stride, size_t out_cap,
                       size_t *direct_out, bool keep_direct)
 {
   if (!keep_direct && mir_end_ > mir_begin_) { // (a push that does not mirror, a device push / flow: one place for the fifo)
@@ -1444,9 +1421,7 @@ int Engine::feed_impl(const float *d_in, size_t stride_frames, size_t isamp, flo
   if (a1 > a0) {
     int rc = ensure_ring(0, book_.wr[0] - book_.rd[0]);
     if (rc) return rc;
-    F32View src = f32_view(0, &ein, nullptr), dst = f32_view(0, nullptr, nullptr);
-    F64View nod = {};
-    HIP_TRY(launch_copy(fk_, src, nod, dst, nod, a0, a1, C_, stream_));
+    HIP_TRY(launch_copy(view(0, &ein), view(0), a0, a1, C_, stream_));
   }
   { int rcj = join_side(); if (rcj) return rcj; }
   if (eout.ptr) {
@@ -1461,7 +1436,7 @@ int Engine::feed_impl(const float *d_in, size_t stride_frames, size_t isamp, flo
   return kOk;
 }
 
-int Engine::push_device(const float *ibuf, size_t stream_stride, size_t isamp)
+int Engine::push_device(const void *ibuf, size_t stream_stride, size_t isamp)
 {
   if (poisoned_) return kInternal;
   if (!ibuf || !isamp) return kOk; // rate_base.h:623
@@ -1469,14 +1444,13 @@ int Engine::push_device(const float *ibuf, size_t stream_stride, size_t isamp)
   return feed(ibuf, S_ > 1 ? stream_stride : isamp, isamp, nullptr, 0, 0, nullptr);
 }
 
-int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
+int Engine::push_host(const void *ibuf, size_t stream_stride, size_t isamp)
 {
   if (poisoned_) return kInternal;
   if (!ibuf || !isamp) return kOk;
   if (isamp > plan_.isamp_max) isamp = plan_.isamp_max;
   const size_t fb = frame_bytes();
   const size_t row = isamp * fb, need_bytes = row * size_t(S_); // bytes of one stream's frames / of the push
-  const size_t need = (need_bytes + 3) / 4;                     // the same in 4-byte words, rounded up
   if (need_bytes <= kZeroCopyMaxBytes) {
     // plugin-sized push: the kernels read it in place from the page-locked slot; the slot is released by an event behind the
     // push's last kernel (two slots alternate, so this only ever waits for the push before the previous one)
@@ -1485,12 +1459,12 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
       HIP_TRY(hipEventSynchronize(slot.done));
       slot.pending = false;
     }
-    int rp = pinned_reserve(slot, need);
+    int rp = pinned_reserve(slot, need_bytes);
     if (rp) return rp;
     for (int s = 0; s < S_; ++s) std::memcpy(at_bytes(slot.p, size_t(s) * row), at_bytes(ibuf, size_t(s) * stream_stride * fb), row);
     // mirror the output when the fifo is empty (the plugin pulls until it is): the exact number of frames this push makes
     // available comes from a dry run of the counters
-    float *mir = nullptr;
+    void *mir = nullptr;
     size_t cap = 0;
     if (!plan_.stages.empty() && available() == 0 && mir_end_ == mir_begin_) { // (no stages: the input ring IS the output fifo)
       Book trial = book_;
@@ -1504,7 +1478,7 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
       }
       cap = size_t(trial.wr.back() - trial.rd.back());
       if (cap && cap * fb * size_t(S_) <= kZeroCopyMaxBytes) {
-        int rm = pinned_reserve(pin_mir_, (cap * fb * size_t(S_) + 3) / 4);
+        int rm = pinned_reserve(pin_mir_, cap * fb * size_t(S_));
         if (rm) return rm;
         mir = pin_mir_.p;
       }
@@ -1524,13 +1498,13 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
     slot.pending = true;
     return kOk;
   }
-  if (need > stage_floats_) {
+  if (need_bytes > stage_bytes_) {
     HIP_TRY(hipStreamSynchronize(stream_));
     if (d_stage_) (void)hipFree(d_stage_);
     d_stage_ = nullptr;
-    stage_floats_ = 0;
-    ALLOC_TRY(&d_stage_, need * sizeof(float));
-    stage_floats_ = need;
+    stage_bytes_ = 0;
+    ALLOC_TRY(&d_stage_, need_bytes);
+    stage_bytes_ = need_bytes;
   }
   if (need_bytes <= kPinnedMaxBytes) {
     Pinned &slot = pin_in_[pin_k_ ^= 1];
@@ -1538,7 +1512,7 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
       HIP_TRY(hipEventSynchronize(slot.done));
       slot.pending = false;
     }
-    int rp = pinned_reserve(slot, need);
+    int rp = pinned_reserve(slot, need_bytes);
     if (rp) return rp;
     for (int s = 0; s < S_; ++s) std::memcpy(at_bytes(slot.p, size_t(s) * row), at_bytes(ibuf, size_t(s) * stream_stride * fb), row);
     HIP_TRY(hipMemcpyAsync(d_stage_, slot.p, need_bytes, hipMemcpyHostToDevice, stream_));
@@ -1550,7 +1524,7 @@ int Engine::push_host(const float *ibuf, size_t stream_stride, size_t isamp)
 }
 
 // copy `frames` frames starting at the output read pointer to dst; does not move the pointer
-int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_host)
+int Engine::copy_out(void *dst, size_t stride_frames, size_t frames, bool to_host)
 {
   const int f = int(rings_.size()) - 1;
   const Ring &r = rings_[f];
@@ -1560,7 +1534,7 @@ int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_ho
     const size_t total = frames * fb * size_t(S_);
     const bool pinned = total <= kPinnedMaxBytes;
     if (pinned) {
-      int rp = pinned_reserve(pin_out_, (total + 3) / 4);
+      int rp = pinned_reserve(pin_out_, total);
       if (rp) return rp;
     }
     size_t done = 0;
@@ -1568,8 +1542,8 @@ int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_ho
       const long long pos = (rd + (long long)done) & (r.cap - 1);
       const size_t n = std::min<size_t>(frames - done, size_t(r.cap - pos));
       const size_t row = n * fb;
-      const float *src = at_bytes(static_cast<const float *>(r.buf), size_t(pos) * fb);
-      float *d = at_bytes(pinned ? pin_out_.p : dst, done * fb);
+      const void *src = at_bytes(r.buf, size_t(pos) * fb);
+      void *d = at_bytes(pinned ? pin_out_.p : dst, done * fb);
       const size_t dpitch = (pinned ? frames : stride_frames) * fb;
       HIP_TRY(hipMemcpy2DAsync(d, dpitch, src, size_t(r.cap) * fb, row, S_, hipMemcpyDeviceToHost, stream_));
       done += n;
@@ -1585,14 +1559,12 @@ int Engine::copy_out(float *dst, size_t stride_frames, size_t frames, bool to_ho
     eo.begin = rd;
     eo.end = rd + (long long)frames;
     eo.stride_elems = (long long)stride_frames * nch_;
-    F32View src = f32_view(f, nullptr, nullptr), dv = f32_view(f, nullptr, &eo);
-    F64View nod = {};
-    HIP_TRY(launch_copy(fk_, src, nod, dv, nod, rd, rd + (long long)frames, C_, stream_));
+    HIP_TRY(launch_copy(view(f), view(f, nullptr, &eo), rd, rd + (long long)frames, C_, stream_));
   }
   return kOk;
 }
 
-int Engine::pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *ogen)
+int Engine::pull_host(void *obuf, size_t stream_stride, size_t osamp, size_t *ogen)
 {
   if (poisoned_) {
     if (ogen) *ogen = 0;
@@ -1631,7 +1603,7 @@ int Engine::pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *o
   return kOk;
 }
 
-int Engine::pull_device(float *obuf, size_t stream_stride, size_t osamp, size_t *ogen)
+int Engine::pull_device(void *obuf, size_t stream_stride, size_t osamp, size_t *ogen)
 {
   if (poisoned_) {
     if (ogen) *ogen = 0;
@@ -1657,8 +1629,8 @@ int Engine::pull_device(float *obuf, size_t stream_stride, size_t osamp, size_t 
 }
 
 // rate_base.h:571-614: deliver what is ready, take the input, deliver again
-int Engine::flow_host(const float *ibuf, size_t in_stride, float *obuf, size_t out_stride, size_t isamp, size_t osamp,
-                      size_t *iused, size_t *ogen)
+int Engine::flow_host(const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp, size_t osamp, size_t *iused,
+                      size_t *ogen)
 {
   size_t n1 = 0, n2 = 0;
   if (!ibuf) isamp = 0;
@@ -1672,8 +1644,8 @@ int Engine::flow_host(const float *ibuf, size_t in_stride, float *obuf, size_t o
   return kOk;
 }
 
-int Engine::flow_device(const float *ibuf, size_t in_stride, float *obuf, size_t out_stride, size_t isamp, size_t osamp,
-                        size_t *iused, size_t *ogen)
+int Engine::flow_device(const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp, size_t osamp, size_t *iused,
+                        size_t *ogen)
 {
   size_t n1 = 0, n2 = 0;
   if (!ibuf) isamp = 0;
@@ -1683,7 +1655,7 @@ int Engine::flow_device(const float *ibuf, size_t in_stride, float *obuf, size_t
   if (rc) return rc;
   if (isamp) {
     // frames produced by this push land directly in the caller's buffer (no ring round trip)
-    float *direct = obuf && n1 < osamp ? at_bytes(obuf, n1 * frame_bytes()) : nullptr;
+    void *direct = obuf && n1 < osamp ? at_bytes(obuf, n1 * frame_bytes()) : nullptr;
     rc = feed(ibuf, S_ > 1 ? in_stride : isamp, isamp, direct, S_ > 1 ? out_stride : osamp, direct ? osamp - n1 : 0, &n2);
     if (rc) return rc;
     if (direct && !n2 && available() && n1 < osamp) { // the ring was not empty: fall back to a copy
@@ -1716,7 +1688,7 @@ int Engine::drain()
   }
   if (blocks) {
     const size_t frames = blocks * 1024, zbytes = frames * frame_bytes() * size_t(S_); // (all-zero bits: silence in every format)
-    float *zeros = nullptr;
+    void *zeros = nullptr;
     ALLOC_TRY(&zeros, zbytes);
     HIP_TRY(hipMemsetAsync(zeros, 0, zbytes, stream_));
     // feed them one reference block at a time so that the counter wrap in rate_input sees the same sequence

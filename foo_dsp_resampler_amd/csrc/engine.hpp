@@ -6,6 +6,10 @@
 // No sample data is ever inspected on the host: how many frames each stage can produce after a push
 // is a pure function of the counters, so everything is enqueued asynchronously and the host only
 // synchronises when the caller needs bytes back (pull to host memory).
+//
+// Sample buffers cross the host side as void pointers: a handle's format is fixed when it is opened, the host moves
+// frames as raw bytes (eb_ per sample), and only the kernels read them as samples, through the view of a fifo end
+// (Engine::view -> AnyView, kernels.hpp).
 #pragma once
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -14,7 +18,6 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 namespace rsmp {
@@ -86,18 +89,17 @@ public:
   static void fail_alloc_after(int n);
 
   // Host-memory API (RR_push / RR_pull / RR_flow semantics). Buffers: [stream][frame][channel] of the handle's sample
-  // format (float, or double / short / int behind a float pointer on a handle of another format: the pointers are only ever
-  // moved as raw bytes, eb_ per sample) with
-  // `stream_stride` frames between streams (ignored when there is one stream).
-  int push_host(const float *ibuf, size_t stream_stride, size_t isamp);
-  int pull_host(float *obuf, size_t stream_stride, size_t osamp, size_t *ogen);
-  int flow_host(const float *ibuf, size_t in_stride, float *obuf, size_t out_stride, size_t isamp, size_t osamp,
-                size_t *iused, size_t *ogen);
+  // format (the host moves them as raw bytes, eb_ per sample) with `stream_stride` frames between streams (ignored when
+  // there is one stream).
+  int push_host(const void *ibuf, size_t stream_stride, size_t isamp);
+  int pull_host(void *obuf, size_t stream_stride, size_t osamp, size_t *ogen);
+  int flow_host(const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp, size_t osamp, size_t *iused,
+                size_t *ogen);
   // Device-memory API: same semantics, pointers are HBM addresses, nothing is synchronised.
-  int push_device(const float *ibuf, size_t stream_stride, size_t isamp);
-  int pull_device(float *obuf, size_t stream_stride, size_t osamp, size_t *ogen);
-  int flow_device(const float *ibuf, size_t in_stride, float *obuf, size_t out_stride, size_t isamp, size_t osamp,
-                  size_t *iused, size_t *ogen);
+  int push_device(const void *ibuf, size_t stream_stride, size_t isamp);
+  int pull_device(void *obuf, size_t stream_stride, size_t osamp, size_t *ogen);
+  int flow_device(const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp, size_t osamp, size_t *iused,
+                  size_t *ogen);
   int drain();
 
   // optional per-kernel timing: HIP events recorded on the launch stream around every stage launch
@@ -121,26 +123,22 @@ private:
   // every copy is exact to 2 bytes); kernel views and FastIo count samples.
   int fmt_ = 0, eb_ = 4, fk_ = kFramesF32;
   size_t frame_bytes() const { return size_t(nch_) * size_t(eb_); }
-  // a frame pointer advanced by whole frames / samples (the float type is only a handle: see push_host)
-  template <class T> T *at_bytes(T *p, size_t bytes) const
-  {
-    typedef typename std::conditional<std::is_const<T>::value, const char, char>::type B;
-    return reinterpret_cast<T *>(reinterpret_cast<B *>(p) + bytes);
-  }
+  static const void *at_bytes(const void *p, size_t bytes) { return static_cast<const char *>(p) + bytes; }
+  static void *at_bytes(void *p, size_t bytes) { return static_cast<char *>(p) + bytes; }
 
   struct Ring { // device ring of fifo f
     void *buf = nullptr;
-    long long cap = 0; // items (f64) or frames (f32: caller-facing frames of either format), power of two
-    bool f32 = false;
+    long long cap = 0; // items (fp64 ring) or frames, power of two
+    bool frames = false; // caller-facing frames of the handle's format (fifo 0 and the last fifo), else a planar fp64 ring
   };
   // caller buffers at the two ends; stride_elems = samples (of the handle's format) between streams
-  struct ExtIn { const float *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
-  struct ExtOut { float *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
+  struct ExtIn { const void *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
+  struct ExtOut { void *ptr = nullptr; long long begin = 0, end = 0, stride_elems = 0; };
 
   // keep_direct: frames written straight to d_out stay in the output fifo (not counted as pulled): the host mirror
-  int feed(const float *d_in, size_t stride_frames, size_t isamp, float *d_out, size_t out_stride, size_t out_cap,
+  int feed(const void *d_in, size_t stride_frames, size_t isamp, void *d_out, size_t out_stride, size_t out_cap,
            size_t *direct_out, bool keep_direct = false);
-  int feed_impl(const float *d_in, size_t stride_frames, size_t isamp, float *d_out, size_t out_stride, size_t out_cap,
+  int feed_impl(const void *d_in, size_t stride_frames, size_t isamp, void *d_out, size_t out_stride, size_t out_cap,
                 size_t *direct_out, bool keep_direct);
   // more_slabs: another time slab of the same push follows (seam kernels may then run beside the next slab's launches)
   int advance(Book &b, size_t n_new, bool launch, const ExtIn &ein, const ExtOut &eout, bool more_slabs = false);
@@ -156,9 +154,9 @@ private:
   int launch_polymf_stage(Pass &ps, int i, long long count, long long step);
   int launch_poly_stage(Pass &ps, int i, long long count, long long step);
   int ensure_ring(int f, long long live_needed);
-  int copy_out(float *dst, size_t stride_frames, size_t frames, bool to_host);
-  F32View f32_view(int f, const ExtIn *ein, const ExtOut *eout) const;
-  F64View f64_view(int f) const;
+  int copy_out(void *dst, size_t stride_frames, size_t frames, bool to_host);
+  // fifo f as the kernels see it: frames of kind fk_ (with the caller's buffer, if one is given) or the fp64 ring
+  AnyView view(int f, const ExtIn *ein = nullptr, const ExtOut *eout = nullptr) const;
   void note_input(Book &b, size_t n) const;
   template <class T> int upload(const std::vector<T> &src, T **dst); // allocate, copy; *dst is set on success
   const double2 *twiddles(int log2m);
@@ -214,14 +212,13 @@ private:
   int dbg_ = 0;           // RSMP_DBG ablation bits (0 in production)
   bool no_side_ = false;  // RSMP_NO_SIDE: keep seam kernels on the main stream
   unsigned long long *stamps_ = nullptr; // RSMP_STAMPS: device buffer of per-phase cycle sums
-  float *d_stage_ = nullptr;
-  size_t stage_floats_ = 0;
+  void *d_stage_ = nullptr;
+  size_t stage_bytes_ = 0;
   // Pinned host staging for RR_push / RR_pull (the plugin's 1-8 k-frame chunks): the caller's pageable buffer is copied
   // into page-locked memory on the CPU, so the H2D copy is a true asynchronous DMA and a push returns without waiting for
   // the device; two input slots alternate, each guarded by an event recorded behind its copy.  Pushes larger than
   // kPinnedMaxBytes keep the direct (runtime-staged) path.
-  struct Pinned { float *p = nullptr; size_t floats = 0; // (sized in 4-byte words, used as raw bytes)
-                  hipEvent_t done = nullptr; bool pending = false; };
+  struct Pinned { void *p = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool pending = false; };
   Pinned pin_in_[2], pin_out_;
   int pin_k_ = 0;
   static constexpr size_t kPinnedMaxBytes = size_t(64) << 20;
@@ -236,7 +233,7 @@ private:
   long long mir_begin_ = 0, mir_end_ = 0; // frames of the output fifo held by the mirror (empty: begin == end)
   size_t mir_stride_ = 0;                 // frames between streams in the mirror
   int spill_mirror();
-  int pinned_reserve(Pinned &b, size_t floats);
+  int pinned_reserve(Pinned &b, size_t bytes);
   void pinned_free(Pinned &b);
   size_t slab_frames_ = 0;
 };

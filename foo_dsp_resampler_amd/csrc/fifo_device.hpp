@@ -1,26 +1,18 @@
-// Device-side fifo accessors shared by the stage kernels (see kernels.hpp for the coordinate convention).
+// Device-side fifo accessors shared by the stage kernels (see kernels.hpp for the coordinate convention and the views).
+// A FrameView's pointers are untyped; every accessor below casts them once, to the sample type of the view's kind.
 #pragma once
 #include "kernels.hpp"
 
 namespace rsmp {
 
-// is_f32: kFramesF32 / kFramesF64 / kFramesS16 / kFramesS32 = interleaved frames (F32View; its ring / ext pointers address
-// samples of that type and its strides count samples), 0 = planar fp64 rings (F64View).  Frames of any type are the
-// caller-facing ends (stage-0 input, final output); every test of `is_f32` as a truth value means "frames".
-struct AnyView {
-  int is_f32;
-  F32View f;
-  F64View d;
-};
-
 struct ChanRef { // per-channel precomputed addressing
-  int is_f32; // as AnyView::is_f32
-  // frames (the two pointers address samples of the frame kind's type)
-  const float *ring32;
-  const float *ext32;
-  long long mask32, ext_begin, ext_end;
+  int kind; // AnyView::kind
+  // frames: sample 0 of the channel in the ring / the external buffer, consecutive frames nch samples apart
+  const void *fring;
+  const void *fext;
+  long long fmask, ext_begin, ext_end;
   int nch;
-  // f64
+  // fp64 ring
   const double *ring64;
   long long mask64;
 };
@@ -28,20 +20,20 @@ struct ChanRef { // per-channel precomputed addressing
 __device__ __forceinline__ ChanRef chan_ref(const AnyView &v, int c)
 {
   ChanRef r;
-  r.is_f32 = v.is_f32;
-  if (v.is_f32) {
+  r.kind = v.kind;
+  if (v.kind) {
     const int s = c / v.f.nch, ch = c - s * v.f.nch;
-    if (v.is_f32 == kFramesF64) { // (the same element offsets, in doubles)
-      r.ring32 = reinterpret_cast<const float *>(reinterpret_cast<const double *>(v.f.ring) + s * v.f.ring_stream_stride + ch);
-      r.ext32 = v.f.ext ? reinterpret_cast<const float *>(reinterpret_cast<const double *>(v.f.ext) + s * v.f.ext_stream_stride + ch) : nullptr;
-    } else if (v.is_f32 == kFramesS16) { // (in shorts)
-      r.ring32 = reinterpret_cast<const float *>(reinterpret_cast<const short *>(v.f.ring) + s * v.f.ring_stream_stride + ch);
-      r.ext32 = v.f.ext ? reinterpret_cast<const float *>(reinterpret_cast<const short *>(v.f.ext) + s * v.f.ext_stream_stride + ch) : nullptr;
-    } else {
-      r.ring32 = v.f.ring + s * v.f.ring_stream_stride + ch;
-      r.ext32 = v.f.ext ? v.f.ext + s * v.f.ext_stream_stride + ch : nullptr;
+    if (v.kind == kFramesF64) { // (the same element offsets, in doubles)
+      r.fring = static_cast<const double *>(v.f.ring) + s * v.f.ring_stream_stride + ch;
+      r.fext = v.f.ext ? static_cast<const double *>(v.f.ext) + s * v.f.ext_stream_stride + ch : nullptr;
+    } else if (v.kind == kFramesS16) { // (in shorts)
+      r.fring = static_cast<const short *>(v.f.ring) + s * v.f.ring_stream_stride + ch;
+      r.fext = v.f.ext ? static_cast<const short *>(v.f.ext) + s * v.f.ext_stream_stride + ch : nullptr;
+    } else { // (4-byte samples: float or 32-bit PCM)
+      r.fring = static_cast<const float *>(v.f.ring) + s * v.f.ring_stream_stride + ch;
+      r.fext = v.f.ext ? static_cast<const float *>(v.f.ext) + s * v.f.ext_stream_stride + ch : nullptr;
     }
-    r.mask32 = v.f.ring_mask;
+    r.fmask = v.f.ring_mask;
     r.ext_begin = v.f.ext_begin;
     r.ext_end = v.f.ext_end;
     r.nch = v.f.nch;
@@ -50,8 +42,8 @@ __device__ __forceinline__ ChanRef chan_ref(const AnyView &v, int c)
   } else {
     r.ring64 = v.d.ring + (long long)c * v.d.chan_stride;
     r.mask64 = v.d.mask;
-    r.ring32 = r.ext32 = nullptr;
-    r.mask32 = r.ext_begin = r.ext_end = 0;
+    r.fring = r.fext = nullptr;
+    r.fmask = r.ext_begin = r.ext_end = 0;
     r.nch = 1;
   }
   return r;
@@ -59,40 +51,40 @@ __device__ __forceinline__ ChanRef chan_ref(const AnyView &v, int c)
 
 __device__ __forceinline__ double fifo_get(const ChanRef &r, long long a)
 {
-  if (r.is_f32 == kFramesF64) {
-    const double *e = reinterpret_cast<const double *>(r.ext32), *g = reinterpret_cast<const double *>(r.ring32);
+  if (r.kind == kFramesF64) {
+    const double *e = static_cast<const double *>(r.fext), *g = static_cast<const double *>(r.fring);
     if (e && a >= r.ext_begin && a < r.ext_end) return e[(a - r.ext_begin) * r.nch];
-    return g[(a & r.mask32) * r.nch];
+    return g[(a & r.fmask) * r.nch];
   }
-  if (r.is_f32 >= kFramesS16) { // integer PCM frames: convert on load
-    const bool in_ext = r.ext32 && a >= r.ext_begin && a < r.ext_end;
-    const long long i = in_ext ? (a - r.ext_begin) * r.nch : (a & r.mask32) * r.nch;
-    const float *base = in_ext ? r.ext32 : r.ring32;
-    if (r.is_f32 == kFramesS16) return pcm_in(reinterpret_cast<const short *>(base)[i]);
-    return pcm_in(reinterpret_cast<const int *>(base)[i]);
+  if (r.kind >= kFramesS16) { // integer PCM frames: convert on load
+    const bool in_ext = r.fext && a >= r.ext_begin && a < r.ext_end;
+    const long long i = in_ext ? (a - r.ext_begin) * r.nch : (a & r.fmask) * r.nch;
+    const void *base = in_ext ? r.fext : r.fring;
+    if (r.kind == kFramesS16) return pcm_in(static_cast<const short *>(base)[i]);
+    return pcm_in(static_cast<const int *>(base)[i]);
   }
-  if (r.is_f32) {
-    if (r.ext32 && a >= r.ext_begin && a < r.ext_end) return (double)r.ext32[(a - r.ext_begin) * r.nch];
-    return (double)r.ring32[(a & r.mask32) * r.nch];
+  if (r.kind) {
+    if (r.fext && a >= r.ext_begin && a < r.ext_end) return (double)static_cast<const float *>(r.fext)[(a - r.ext_begin) * r.nch];
+    return (double)static_cast<const float *>(r.fring)[(a & r.fmask) * r.nch];
   }
   return r.ring64[a & r.mask64];
 }
 
 __device__ __forceinline__ void fifo_put(const ChanRef &r, long long a, double v)
 {
-  if (r.is_f32 == kFramesF64) {
-    double *e = reinterpret_cast<double *>(const_cast<float *>(r.ext32)), *g = reinterpret_cast<double *>(const_cast<float *>(r.ring32));
+  if (r.kind == kFramesF64) {
+    double *e = static_cast<double *>(const_cast<void *>(r.fext)), *g = static_cast<double *>(const_cast<void *>(r.fring));
     if (e && a >= r.ext_begin && a < r.ext_end) e[(a - r.ext_begin) * r.nch] = v;
-    else g[(a & r.mask32) * r.nch] = v;
-  } else if (r.is_f32 >= kFramesS16) { // integer PCM frames: quantise on store
-    const bool in_ext = r.ext32 && a >= r.ext_begin && a < r.ext_end;
-    const long long i = in_ext ? (a - r.ext_begin) * r.nch : (a & r.mask32) * r.nch;
-    float *base = const_cast<float *>(in_ext ? r.ext32 : r.ring32);
-    if (r.is_f32 == kFramesS16) reinterpret_cast<short *>(base)[i] = pcm_out16(v);
-    else reinterpret_cast<int *>(base)[i] = pcm_out32(v);
-  } else if (r.is_f32) {
-    if (r.ext32 && a >= r.ext_begin && a < r.ext_end) const_cast<float *>(r.ext32)[(a - r.ext_begin) * r.nch] = (float)v;
-    else const_cast<float *>(r.ring32)[(a & r.mask32) * r.nch] = (float)v;
+    else g[(a & r.fmask) * r.nch] = v;
+  } else if (r.kind >= kFramesS16) { // integer PCM frames: quantise on store
+    const bool in_ext = r.fext && a >= r.ext_begin && a < r.ext_end;
+    const long long i = in_ext ? (a - r.ext_begin) * r.nch : (a & r.fmask) * r.nch;
+    void *base = const_cast<void *>(in_ext ? r.fext : r.fring);
+    if (r.kind == kFramesS16) static_cast<short *>(base)[i] = pcm_out16(v);
+    else static_cast<int *>(base)[i] = pcm_out32(v);
+  } else if (r.kind) {
+    if (r.fext && a >= r.ext_begin && a < r.ext_end) static_cast<float *>(const_cast<void *>(r.fext))[(a - r.ext_begin) * r.nch] = (float)v;
+    else static_cast<float *>(const_cast<void *>(r.fring))[(a & r.fmask) * r.nch] = (float)v;
   } else
     const_cast<double *>(r.ring64)[a & r.mask64] = v;
 }
@@ -117,11 +109,11 @@ struct ChanSpan {
 __device__ __forceinline__ ChanSpan chan_span(const AnyView &v, int c, long long a0, long long len)
 {
   ChanSpan r = {0, nullptr, 1, nullptr, nullptr, nullptr};
-  if (v.is_f32) {
+  if (v.kind) {
     const int s = c / v.f.nch, ch = c - s * v.f.nch;
     r.stride32 = v.f.nch;
     long long off = -1; // element offset from the buffer's base
-    const float *base = nullptr;
+    const void *base = nullptr;
     if (v.f.ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end) {
       base = v.f.ext;
       off = s * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + ch;
@@ -130,18 +122,18 @@ __device__ __forceinline__ ChanSpan chan_span(const AnyView &v, int c, long long
       off = s * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + ch;
     }
     if (off >= 0) {
-      if (v.is_f32 == kFramesF64) {
+      if (v.kind == kFramesF64) {
         r.kind = 3;
-        r.p64 = reinterpret_cast<const double *>(base) + off;
-      } else if (v.is_f32 == kFramesS16) {
+        r.p64 = static_cast<const double *>(base) + off;
+      } else if (v.kind == kFramesS16) {
         r.kind = 4;
-        r.p16 = reinterpret_cast<const short *>(base) + off;
-      } else if (v.is_f32 == kFramesS32) {
+        r.p16 = static_cast<const short *>(base) + off;
+      } else if (v.kind == kFramesS32) {
         r.kind = 5;
-        r.pi32 = reinterpret_cast<const int *>(base) + off;
+        r.pi32 = static_cast<const int *>(base) + off;
       } else {
         r.kind = 1;
-        r.p32 = base + off;
+        r.p32 = static_cast<const float *>(base) + off;
       }
     }
   } else if (a0 >= 0 && (a0 & v.d.mask) + len <= v.d.mask + 1) {
@@ -299,10 +291,10 @@ __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pai
   r.d2 = nullptr;
   r.w16 = nullptr;
   r.w32 = nullptr;
-  if (INTS && v.is_f32 >= kFramesS16) { // as below, in shorts / ints; a pair is aligned as one word (4 / 8 bytes) or not taken
+  if (INTS && v.kind >= kFramesS16) { // as below, in shorts / ints; a pair is aligned as one word (4 / 8 bytes) or not taken
     if (hasb && !(v.f.nch & 1)) {
-      const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp, eb = frame_elem_bytes(v.is_f32);
-      const char *ext = reinterpret_cast<const char *>(v.f.ext), *ring = reinterpret_cast<const char *>(v.f.ring);
+      const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp, eb = frame_elem_bytes(v.kind);
+      const char *ext = static_cast<const char *>(v.f.ext), *ring = static_cast<const char *>(v.f.ring);
       const char *p = nullptr;
       if (ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end)
         p = ext + (strm * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + 2 * pin) * eb;
@@ -310,7 +302,7 @@ __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pai
         p = ring + (strm * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + 2 * pin) * eb;
       if (p && (reinterpret_cast<unsigned long long>(p) & (2 * eb - 1)) == 0) {
         r.fstride = hp;
-        if (v.is_f32 == kFramesS16) {
+        if (v.kind == kFramesS16) {
           r.kind = 4;
           r.w16 = reinterpret_cast<unsigned *>(const_cast<char *>(p));
         } else {
@@ -319,10 +311,10 @@ __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pai
         }
       }
     }
-  } else if (v.is_f32 == kFramesF64) { // as below, in doubles; a pair is 16-byte aligned or not taken
+  } else if (v.kind == kFramesF64) { // as below, in doubles; a pair is 16-byte aligned or not taken
     if (hasb && !(v.f.nch & 1)) {
       const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
-      const double *ext = reinterpret_cast<const double *>(v.f.ext), *ring = reinterpret_cast<const double *>(v.f.ring);
+      const double *ext = static_cast<const double *>(v.f.ext), *ring = static_cast<const double *>(v.f.ring);
       const double *p = nullptr;
       if (ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end)
         p = ext + strm * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + 2 * pin;
@@ -334,14 +326,14 @@ __host__ __device__ __forceinline__ PairSpan pair_span(const AnyView &v, int pai
         r.fstride = hp;
       }
     }
-  } else if (v.is_f32) {
+  } else if (v.kind) {
     if (hasb && !(v.f.nch & 1)) {
       const int hp = v.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
       float *p = nullptr;
       if (v.f.ext && a0 >= v.f.ext_begin && a0 + len <= v.f.ext_end)
-        p = v.f.ext + strm * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + 2 * pin;
+        p = static_cast<float *>(v.f.ext) + strm * v.f.ext_stream_stride + (a0 - v.f.ext_begin) * v.f.nch + 2 * pin;
       else if ((!v.f.ext || a0 + len <= v.f.ext_begin || a0 >= v.f.ext_end) && (a0 & v.f.ring_mask) + len <= v.f.ring_mask + 1)
-        p = v.f.ring + strm * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + 2 * pin;
+        p = static_cast<float *>(v.f.ring) + strm * v.f.ring_stream_stride + (a0 & v.f.ring_mask) * v.f.nch + 2 * pin;
       if (p && (reinterpret_cast<unsigned long long>(p) & 7) == 0) {
         r.kind = 1;
         r.p2 = reinterpret_cast<float2 *>(p);
@@ -390,19 +382,9 @@ inline int item_grid(int nblocks, int npairs, int hp)
 // pairs per interleaved frame that share cache lines (0 when the grouping does not apply)
 inline int frame_pairs(const AnyView &in, const AnyView &out, int C)
 {
-  const AnyView *v = in.is_f32 ? &in : out.is_f32 ? &out : nullptr;
+  const AnyView *v = in.kind ? &in : out.kind ? &out : nullptr;
   if (!v || (v->f.nch & 1) || v->f.nch < 4 || C % v->f.nch) return 0;
   return v->f.nch / 2;
-}
-
-// frames: 0 = the fp64 rings `d`, a frame kind (kFramesF32 ...) = the frames `f` (the launchers' src_f32 / dst_f32 arguments)
-inline AnyView make_view(int frames, const F32View &f, const F64View &d)
-{
-  AnyView v;
-  v.is_f32 = frames;
-  v.f = f;
-  v.d = d;
-  return v;
 }
 
 } // namespace rsmp

@@ -136,22 +136,22 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       bool fast = false;
       const float2 *p2 = nullptr;
       int fstride = 1; // float2 elements between consecutive frames of this channel pair
-      if (in.is_f32 == kFramesF32 && hasb && !(in.f.nch & 1)) { // channels 2p, 2p+1 sit side by side in every frame
+      if (in.kind == kFramesF32 && hasb && !(in.f.nch & 1)) { // channels 2p, 2p+1 sit side by side in every frame
         const int hp = in.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
         fstride = hp;
         if (in.f.ext && e0 >= in.f.ext_begin && e0 + P <= in.f.ext_end) {
-          const float *p = in.f.ext + strm * in.f.ext_stream_stride + (e0 - in.f.ext_begin) * in.f.nch + 2 * pin;
+          const float *p = static_cast<const float *>(in.f.ext) + strm * in.f.ext_stream_stride + (e0 - in.f.ext_begin) * in.f.nch + 2 * pin;
           fast = (reinterpret_cast<unsigned long long>(p) & 7) == 0;
           p2 = reinterpret_cast<const float2 *>(p);
         } else if ((!in.f.ext || e0 + P <= in.f.ext_begin) && (e0 & in.f.ring_mask) + P <= in.f.ring_mask + 1) {
-          const float *p = in.f.ring + strm * in.f.ring_stream_stride + (e0 & in.f.ring_mask) * in.f.nch + 2 * pin;
+          const float *p = static_cast<const float *>(in.f.ring) + strm * in.f.ring_stream_stride + (e0 & in.f.ring_mask) * in.f.nch + 2 * pin;
           fast = (reinterpret_cast<unsigned long long>(p) & 7) == 0;
           p2 = reinterpret_cast<const float2 *>(p);
         }
       }
       // float64 / integer PCM frames: the same pairs as one 16- / 4- / 8-byte word per sample (pair_span kinds 3 / 4 / 5), else
       // element-wise
-      const PairSpan d64 = in.is_f32 >= kFramesF64 ? pair_span(in, pair, hasb, e0, P, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
+      const PairSpan d64 = in.kind >= kFramesF64 ? pair_span(in, pair, hasb, e0, P, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
       if constexpr (FWD8) { // every thread takes 8 points of the P-point forward transform: x[tid + s*T], T = P/8
         if (fast) {
 #pragma unroll
@@ -184,7 +184,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             v[s] = {(double)f.x, (double)f.y};
           }
         } else {
-          const PairSpan sp = in.is_f32 == kFramesF32 ? PairSpan{0, nullptr, 1, nullptr, nullptr, hasb} : in.is_f32 ? d64 : pair_span(in, pair, hasb, e0, P, ca);
+          const PairSpan sp = in.kind == kFramesF32 ? PairSpan{0, nullptr, 1, nullptr, nullptr, hasb} : in.kind ? d64 : pair_span(in, pair, hasb, e0, P, ca);
           if (sp.kind) { // planar fp64 rings (the producer is another stage), float64 or integer PCM frames, block contiguous
             span_load<16>(sp, tid, TF, v);
           } else {
@@ -336,18 +336,18 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       bool ofast = false;
       char *obase = nullptr;  // frame i_lo's first sample of this pair
       int ofs = 2;            // samples between consecutive frames
-      const int esz = frame_elem_bytes(out.is_f32); // bytes per sample of the destination frames
+      const int esz = frame_elem_bytes(out.kind); // bytes per sample of the destination frames
       {
         const long long o0 = a.out_offset2 + fb.i_lo, o1 = o0 + fb.cnt;
-        if (out.is_f32 && hasb && !(out.f.nch & 1)) {
+        if (out.kind && hasb && !(out.f.nch & 1)) {
           const int hp = out.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
           ofs = out.f.nch;
           if (out.f.ext && o0 >= out.f.ext_begin && o1 <= out.f.ext_end) {
-            obase = reinterpret_cast<char *>(out.f.ext) + (strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin) * esz;
+            obase = static_cast<char *>(out.f.ext) + (strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin) * esz;
             ofast = true;
           } else if ((!out.f.ext || o0 >= out.f.ext_end || o1 <= out.f.ext_begin) &&
                      (o0 & out.f.ring_mask) + (o1 - o0) <= out.f.ring_mask + 1) {
-            obase = reinterpret_cast<char *>(out.f.ring) + (strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin) * esz;
+            obase = static_cast<char *>(out.f.ring) + (strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin) * esz;
             ofast = true;
           }
           ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & (2 * esz - 1)) == 0;
@@ -529,8 +529,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
         flush();
       };
       if (ofast && esz == 8) both_rounds(std::integral_constant<int, 2>{});
-      else if (ofast && out.is_f32 == kFramesS16) both_rounds(std::integral_constant<int, 3>{});
-      else if (ofast && out.is_f32 == kFramesS32) both_rounds(std::integral_constant<int, 4>{});
+      else if (ofast && out.kind == kFramesS16) both_rounds(std::integral_constant<int, 3>{});
+      else if (ofast && out.kind == kFramesS32) both_rounds(std::integral_constant<int, 4>{});
       else if (ofast) both_rounds(std::integral_constant<int, 1>{});
       else both_rounds(std::integral_constant<int, 0>{});
     } else
@@ -545,19 +545,19 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       float *obase = nullptr; // points at frame i_lo's first float of this pair
       int ostride = 1;        // float2 elements between consecutive frames
       // float64 / integer PCM frames: pair_span's kinds 3 / 4 / 5 over the block's outputs (one pair-word store per output)
-      const PairSpan o64 = out.is_f32 >= kFramesF64 ? pair_span(out, pair, hasb, a.out_offset2 + fb.i_lo, fb.cnt, ca)
+      const PairSpan o64 = out.kind >= kFramesF64 ? pair_span(out, pair, hasb, a.out_offset2 + fb.i_lo, fb.cnt, ca)
                                                     : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
       {
         const long long o0 = a.out_offset2 + fb.i_lo, o1 = o0 + fb.cnt;
-        if (out.is_f32 == kFramesF32 && hasb && !(out.f.nch & 1)) {
+        if (out.kind == kFramesF32 && hasb && !(out.f.nch & 1)) {
           const int hp = out.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
           ostride = hp;
           if (out.f.ext && o0 >= out.f.ext_begin && o1 <= out.f.ext_end) {
-            obase = out.f.ext + strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin;
+            obase = static_cast<float *>(out.f.ext) + strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin;
             ofast = true;
           } else if ((!out.f.ext || o0 >= out.f.ext_end || o1 <= out.f.ext_begin) &&
                      (o0 & out.f.ring_mask) + (o1 - o0) <= out.f.ring_mask + 1) {
-            obase = out.f.ring + strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin;
+            obase = static_cast<float *>(out.f.ring) + strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin;
             ofast = true;
           }
           ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & 7) == 0;
@@ -752,9 +752,8 @@ static hipError_t launch_fused_t(const AnyView &in, const AnyView &out, const Fu
   return hipGetLastError();
 }
 
-hipError_t launch_seam(int dst_f32, const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st)
+hipError_t launch_seam(const AnyView &out, const FusedArgs &a, hipStream_t st)
 {
-  const AnyView out = make_view(dst_f32, df, dd);
   dim3 sgrid(a.d.nblocks, (a.d.C + kSeamC - 1) / kSeamC), sblock(256);
   hipLaunchKernelGGL(seam_kernel, sgrid, sblock, 0, st, out, a);
   return hipGetLastError();
@@ -788,10 +787,9 @@ bool fused_shape_supported(int log2n, int log2p, int n, int span, int max_seam_o
     return launch_fused_t<n, p, 2, ks, true>(in, out, a, st);                     \
   }
 
-hipError_t launch_fused(int log2n, int log2p, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
-                        const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st, const char **kname)
+hipError_t launch_fused(int log2n, int log2p, const AnyView &in, const AnyView &out, const FusedArgs &a, hipStream_t st,
+                        const char **kname)
 {
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   if (a.cfm) { // polyphase on the matrix pipe
     RSMP_FUSED_MF(12, 11, 7) RSMP_FUSED_MF(12, 12, 7) RSMP_FUSED_MF(12, 11, 8) RSMP_FUSED_MF(12, 12, 8)
     return hipErrorInvalidValue;

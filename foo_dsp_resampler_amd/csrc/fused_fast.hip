@@ -127,8 +127,8 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
 {
   typedef Frame<E> Fr;
   typedef typename Fr::P E2;
-  const E *const io_in = reinterpret_cast<const E *>(io.in), *const io_in_ring = reinterpret_cast<const E *>(io.in_ring);
-  E *const io_out = reinterpret_cast<E *>(io.out), *const io_out_ring = reinterpret_cast<E *>(io.out_ring);
+  const E *const io_in = static_cast<const E *>(io.in), *const io_in_ring = static_cast<const E *>(io.in_ring);
+  E *const io_out = static_cast<E *>(io.out), *const io_out_ring = static_cast<E *>(io.out_ring);
   static_assert(!TWO || SPLIT, "two rounds from registers: sub-blocked form only");
   static_assert(!SPLIT || LOG2P == 12, "sub-blocked form: 4096-point components");
   static_assert(!OGEN || (SPLIT && !OUT64), "generic float output exists for the sub-blocked form only");

@@ -759,10 +759,9 @@ bool dft_shape_supported(int log2n, int log2p, int log2nd)
   return log2nd == log2n && log2p >= log2n - 2;
 }
 
-hipError_t launch_dft(int log2n, int log2p, int log2nd, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
-                      const F32View &df, const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname)
+hipError_t launch_dft(int log2n, int log2p, int log2nd, const AnyView &in, const AnyView &out, const DftArgs &a, hipStream_t st,
+                      const char **kname)
 {
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   RSMP_DFT_SIZE(11, 10, 9)
   RSMP_DFT_SIZE(12, 11, 10)
   RSMP_DFT_SIZE(13, 12, 11)
@@ -770,13 +769,11 @@ hipError_t launch_dft(int log2n, int log2p, int log2nd, int src_f32, int dst_f32
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_poly(int order, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                       const F64View &dd, const PolyArgs &a, hipStream_t st, const char **kname)
+hipError_t launch_poly(int order, const AnyView &in, const AnyView &out, const PolyArgs &a, hipStream_t st, const char **kname)
 {
   static const char *const names[2][4] = {{"rsmp::poly_kernel<0>", "rsmp::poly_kernel<1>", "rsmp::poly_kernel<2>", "rsmp::poly_kernel<3>"},
                                           {"", "rsmp::poly_coop_kernel<1>", "rsmp::poly_coop_kernel<2>", "rsmp::poly_coop_kernel<3>"}};
   if (kname && order >= 0 && order <= 3) *kname = names[(order >= 1 && a.coop) ? 1 : 0][order];
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   const long long tiles = (a.count + a.tile - 1) / a.tile;
   dim3 grid((unsigned)tiles, a.C), block(256);
   const size_t lds_bytes = sizeof(double) * (size_t(a.win) + (order == 0 && a.tab_lds ? size_t(a.L) * a.n : 0));
@@ -849,30 +846,33 @@ __global__ __launch_bounds__(256) void copy_frames16_kernel(const unsigned short
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nhalves; i += step) d[i] = s[i];
 }
 
-// base pointer of frames [a0, a1) of stream 0 when every stream holds them contiguously in one buffer of the view, else null;
-// `eb` = bytes per sample (a copy moves bits, so frames of any type go as raw memory); stream_stride comes back in bytes
-static const char *frames_base(const F32View &v, long long a0, long long a1, long long &stream_stride, int eb = 4)
+// base pointer of frames [a0, a1) of stream 0 when every stream holds them contiguously in one buffer of the view, else null
+// (a copy moves bits, so frames of any kind go as raw memory); stream_stride comes back in bytes
+static const char *frames_base(const AnyView &av, long long a0, long long a1, long long &stream_stride)
 {
+  const FrameView &v = av.f;
+  const int eb = frame_elem_bytes(av.kind);
   if (v.ext && a0 >= v.ext_begin && a1 <= v.ext_end) {
     stream_stride = v.ext_stream_stride * eb;
-    return reinterpret_cast<const char *>(v.ext) + (a0 - v.ext_begin) * v.nch * eb;
+    return static_cast<const char *>(v.ext) + (a0 - v.ext_begin) * v.nch * eb;
   }
   if ((!v.ext || a1 <= v.ext_begin || a0 >= v.ext_end) && a0 >= 0 && (a0 & v.ring_mask) + (a1 - a0) <= v.ring_mask + 1) {
     stream_stride = v.ring_stream_stride * eb;
-    return reinterpret_cast<const char *>(v.ring) + (a0 & v.ring_mask) * v.nch * eb;
+    return static_cast<const char *>(v.ring) + (a0 & v.ring_mask) * v.nch * eb;
   }
   return nullptr;
 }
 
-static hipError_t copy_range(int f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
-                             long long a1, int C, hipStream_t st, int depth)
+// both views are of one kind: frames of the same sample type, or fp64 rings
+static hipError_t copy_range(const AnyView &in, const AnyView &out, long long a0, long long a1, int C, hipStream_t st, int depth)
 {
   if (a1 <= a0) return hipSuccess;
-  if (f32 && depth < 3 && sf.nch == df.nch && sf.nch > 0 && C % sf.nch == 0) { // (at most 8 pieces, then element-wise)
+  const FrameView &sf = in.f, &df = out.f;
+  if (in.kind && depth < 3 && sf.nch == df.nch && sf.nch > 0 && C % sf.nch == 0) { // (at most 8 pieces, then element-wise)
     long long ss = 0, ds = 0;
-    const int eb = frame_elem_bytes(f32);
-    const char *sp = frames_base(sf, a0, a1, ss, eb);
-    char *dp = const_cast<char *>(frames_base(df, a0, a1, ds, eb));
+    const int eb = frame_elem_bytes(in.kind);
+    const char *sp = frames_base(in, a0, a1, ss);
+    char *dp = const_cast<char *>(frames_base(out, a0, a1, ds));
     if (sp && dp) {
       const long long nbytes = (a1 - a0) * sf.nch * eb;
       const unsigned long long all = reinterpret_cast<unsigned long long>(sp) | reinterpret_cast<unsigned long long>(dp) |
@@ -894,9 +894,10 @@ static hipError_t copy_range(int f32, const F32View &sf, const F64View &sd, cons
     // not contiguous on one side: cut the range where a view changes buffers (its external buffer's ends, a ring wrap)
     // and copy the pieces (a ring's capacity is just above what it must hold, so the carry of a push wraps every few pushes)
     long long cut = a1;
-    for (const F32View *v : {&sf, &df}) {
+    for (const AnyView *av : {&in, &out}) {
       long long dummy = 0;
-      if (frames_base(*v, a0, a1, dummy)) continue; // this side is in one piece already
+      if (frames_base(*av, a0, a1, dummy)) continue; // this side is in one piece already
+      const FrameView *v = &av->f;
       if (v->ext) {
         if (v->ext_begin > a0 && v->ext_begin < cut) cut = v->ext_begin;
         if (v->ext_end > a0 && v->ext_end < cut) cut = v->ext_end;
@@ -907,11 +908,10 @@ static hipError_t copy_range(int f32, const F32View &sf, const F64View &sd, cons
       }
     }
     if (cut < a1) {
-      const hipError_t e = copy_range(f32, sf, sd, df, dd, a0, cut, C, st, depth + 1);
-      return e != hipSuccess ? e : copy_range(f32, sf, sd, df, dd, cut, a1, C, st, depth + 1);
+      const hipError_t e = copy_range(in, out, a0, cut, C, st, depth + 1);
+      return e != hipSuccess ? e : copy_range(in, out, cut, a1, C, st, depth + 1);
     }
   }
-  const AnyView in = make_view(f32, sf, sd), out = make_view(f32, df, dd);
   long long blocks = (a1 - a0 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   dim3 grid((unsigned)blocks, C), block(256);
@@ -919,19 +919,16 @@ static hipError_t copy_range(int f32, const F32View &sf, const F64View &sd, cons
   return hipGetLastError();
 }
 
-hipError_t launch_copy(int f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
-                       long long a1, int C, hipStream_t st)
+hipError_t launch_copy(const AnyView &in, const AnyView &out, long long a0, long long a1, int C, hipStream_t st)
 {
-  return copy_range(f32, sf, sd, df, dd, a0, a1, C, st, 0);
+  return copy_range(in, out, a0, a1, C, st, 0);
 }
 
-hipError_t launch_half(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                       const F64View &dd, const HalfArgs &a, hipStream_t st, const char **kname)
+hipError_t launch_half(const AnyView &in, const AnyView &out, const HalfArgs &a, hipStream_t st, const char **kname)
 {
   static const char *const names[6] = {"rsmp::half_kernel<8>", "rsmp::half_kernel<9>", "rsmp::half_kernel<10>",
                                        "rsmp::half_kernel<11>", "rsmp::half_kernel<12>", "rsmp::half_kernel<13>"};
   if (kname && a.ncoef >= 8 && a.ncoef <= 13) *kname = names[a.ncoef - 8];
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   const long long tiles = (a.count + kHalfTile - 1) / kHalfTile;
   dim3 grid((unsigned)tiles, a.C), block(256);
   switch (a.ncoef) {

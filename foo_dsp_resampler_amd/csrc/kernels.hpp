@@ -30,18 +30,14 @@ struct DynLdsOnce {
   }
 };
 
-// Interleaved float32 frames: the caller-facing end of the chain (stage-0 input or final output).
-// A frame with absolute index a lives in the external buffer when ext != nullptr and
-// ext_begin <= a < ext_end, else in the ring.  This is what lets a device-resident push be
-// consumed in place and a device-resident pull be produced in place (no staging copy of bulk data).
-// With float64 frames (kFramesF64: a handle opened with RRX_FMT_DOUBLE) the same struct describes them: ring / ext then
-// address doubles and every stride counts doubles; the launchers' src_f32 / dst_f32 say which (0 = the fp64 rings).
-// Integer PCM frames (kFramesS16 / kFramesS32: RRX_FMT_S16 / RRX_FMT_S32) are described the same way: the pointers address
-// elements of the handle's type (short / int), strides count samples, and every load converts / every store quantises
-// (pcm_in / pcm_out below) around the same fp64 arithmetic.
-enum { kFramesF32 = 1, kFramesF64 = 2, kFramesS16 = 3, kFramesS32 = 4 };
-// bytes per sample of a frame kind
-__host__ __device__ constexpr int frame_elem_bytes(int kind) { return kind == kFramesF64 ? 8 : kind == kFramesS16 ? 2 : 4; }
+// Interleaved frames: the caller-facing end of the chain (stage-0 input or final output).  A frame with absolute index a lives
+// in the external buffer when ext != nullptr and ext_begin <= a < ext_end, else in the ring.  This is what lets a device-resident
+// push be consumed in place and a device-resident pull be produced in place (no staging copy of bulk data).  The frame kind says
+// what a sample is: float, double (RRX_FMT_DOUBLE) or integer PCM (RRX_FMT_S16 / RRX_FMT_S32).  ring / ext address samples of that
+// type and every stride counts samples; the integer kinds convert on every load and quantise on every store (pcm_in / pcm_out
+// below) around the same fp64 arithmetic.  kRingF64: no frames, the planar fp64 ring between two stages.
+enum { kRingF64 = 0, kFramesF32 = 1, kFramesF64 = 2, kFramesS16 = 3, kFramesS32 = 4 };
+__host__ __device__ constexpr int frame_elem_bytes(int kind) { return kind == kFramesF64 ? 8 : kind == kFramesS16 ? 2 : 4; } // per sample
 
 // The integer formats' conversions (the ABI contract of include/ratelib_amd.h).  In: s * 2^-bits, exact in fp64.  Out:
 // round half to even (v_rndne_f64), saturate to [-2^bits, 2^bits - 1] in fp64, then narrow -- the integer convert never sees
@@ -63,21 +59,29 @@ __host__ __device__ __forceinline__ unsigned pcm_pack16(double a, double b)
 }
 __host__ __device__ __forceinline__ double pcm_lo16(unsigned w) { return pcm_in((short)(w & 0xffffu)); }
 __host__ __device__ __forceinline__ double pcm_hi16(unsigned w) { return pcm_in((short)(w >> 16)); }
-struct F32View {
-  float *ring;
+struct FrameView {
+  void *ring;
   long long ring_mask;          // frames - 1
-  long long ring_stream_stride; // floats between streams
-  float *ext;
+  long long ring_stream_stride; // samples between streams
+  void *ext;
   long long ext_begin, ext_end; // absolute frame range held by ext
-  long long ext_stream_stride;  // floats between streams
+  long long ext_stream_stride;  // samples between streams
   int nch;                      // channels per stream
 };
 
 // Planar fp64 ring between two stages: [channel][cap].
-struct F64View {
+struct RingView {
   double *ring;
   long long mask;        // items - 1
   long long chan_stride; // items between channels
+};
+
+// One fifo end, from the engine (Engine::view) through a launcher to its kernel: kind = a frame kind (the frames `f`) or kRingF64
+// (the ring `d`); the half that is not in use is zero.  Read as a truth value, `kind` means "frames".
+struct AnyView {
+  int kind;
+  FrameView f;
+  RingView d;
 };
 
 struct DftArgs {
@@ -146,8 +150,7 @@ struct BigDftArgs {
   int item0;             // first (block, pair) item of this launch (filled in by launch_dft_big)
 };
 bool big_dft_supported(int log2n, int log2p, int log2nd);
-hipError_t launch_dft_big(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd,
-                          BigDftArgs a, int ws_items, hipStream_t st);
+hipError_t launch_dft_big(const AnyView &in, const AnyView &out, BigDftArgs a, int ws_items, hipStream_t st);
 
 // per-block output bookkeeping of the fused launch, computed on the host (64-bit divisions stay there)
 struct FusedBlock {
@@ -367,27 +370,26 @@ struct FusedArgs {
   const double2 *cfm2;   // the same A operands two k-steps per 16-byte element: [group][(KS + 1) / 2][lane] (lean kernel)
 };
 
-// Lean fast path of the matrix-pipe variant (fused_fast.hip): both ends are plain interleaved float frames in one buffer each
+// Lean fast path of the matrix-pipe variant (fused_fast.hip): both ends are plain interleaved frames in one buffer each
 struct FastIo {
-  const float *in;            // frame `in_abs0` (absolute input index) of stream 0, channel 0
-  const float *in_ring;       // frames below in_abs0 (the tail of the previous push): fifo 0's ring, frame (index & in_ring_mask)
+  const void *in;             // frame `in_abs0` (absolute input index) of stream 0, channel 0
+  const void *in_ring;        // frames below in_abs0 (the tail of the previous push): fifo 0's ring, frame (index & in_ring_mask)
   long long in_ring_mask, in_ring_stream_stride;
-  float *out;                 // frame `out_abs0` (absolute index in the output fifo) of stream 0, channel 0
+  void *out;                  // frame `out_abs0` (absolute index in the output fifo) of stream 0, channel 0
   long long in_abs0, out_abs0;
-  long long in_stream_stride, out_stream_stride; // floats between streams
+  long long in_stream_stride, out_stream_stride; // samples between streams
   int nch;                    // channels per stream (even)
-  int in_unaligned;           // sub-blocked form only: `in` is not 8-byte aligned (channels read one float at a time)
+  int in_unaligned;           // sub-blocked form only: a channel pair of `in` is not aligned as one word (channels read one sample at a time)
   // sub-blocked form, omode 2: frame with absolute index A is in `out` when out_abs0 <= A < out_end, else in the fifo's ring
-  float *out_ring;
+  void *out_ring;
   long long out_ring_mask, out_ring_stream_stride, out_end;
-  int out_unaligned;          // `out` is not 8-byte aligned
+  int out_unaligned;          // a channel pair of `out` is not aligned as one word
   // OUT64 instances (the polyphase stage feeds another stage): planar fp64 ring of the destination fifo instead of `out`
   double *out64;              // ring of channel 0
   long long out64_mask, out64_chan_stride; // items - 1, items between channels
   // Sample format of the caller-facing frames, which picks the kernel instance: 0 = float32, 1 = float64 (*_dio_kernel),
-  // 2 = 16-bit PCM (*_s16_kernel), 3 = 32-bit PCM (*_s32_kernel).  in / in_ring / out / out_ring then address samples of that
-  // type, every stride and frame offset above counts samples, and in_unaligned / out_unaligned mean "a channel pair is not
-  // aligned as one word" (8 / 16 / 4 / 8 bytes)
+  // 2 = 16-bit PCM (*_s16_kernel), 3 = 32-bit PCM (*_s32_kernel).  in / in_ring / out / out_ring address samples of that type,
+  // every stride and frame offset above counts samples, and a channel pair is one word of 8 / 16 / 4 / 8 bytes
   int dio;
 };
 bool fused_fast_supported(int log2n, int log2p, int ksteps);
@@ -426,21 +428,18 @@ struct HalfArgs {
 
 // All launchers return hipSuccess or the launch error; `kname` (optional) receives the name of the kernel instance
 // that was picked, as rocprofv3 prints it (static string).
-hipError_t launch_dft(int log2n, int log2p, int log2nd, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
-                      const F32View &df, const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname = nullptr);
-hipError_t launch_poly(int order, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                       const F64View &dd, const PolyArgs &a, hipStream_t st, const char **kname = nullptr);
-hipError_t launch_half(int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                       const F64View &dd, const HalfArgs &a, hipStream_t st, const char **kname = nullptr);
+hipError_t launch_dft(int log2n, int log2p, int log2nd, const AnyView &in, const AnyView &out, const DftArgs &a, hipStream_t st,
+                      const char **kname = nullptr);
+hipError_t launch_poly(int order, const AnyView &in, const AnyView &out, const PolyArgs &a, hipStream_t st, const char **kname = nullptr);
+hipError_t launch_half(const AnyView &in, const AnyView &out, const HalfArgs &a, hipStream_t st, const char **kname = nullptr);
 bool dft_shape_supported(int log2n, int log2p, int log2nd);
 // x4 upsampling on 8192-point blocks as four 2048-point component transforms (dftx.hip); needs DftArgs::Gr
 bool dftx_supported(int log2n, int log2p, int log2nd);
-hipError_t launch_dftx(int log2n, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                       const F64View &dd, const DftArgs &a, hipStream_t st, const char **kname = nullptr);
-hipError_t launch_fused(int log2n, int log2p, int src_f32, int dst_f32, const F32View &sf, const F64View &sd,
-                        const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st, const char **kname = nullptr);
+hipError_t launch_dftx(int log2n, const AnyView &in, const AnyView &out, const DftArgs &a, hipStream_t st, const char **kname = nullptr);
+hipError_t launch_fused(int log2n, int log2p, const AnyView &in, const AnyView &out, const FusedArgs &a, hipStream_t st,
+                        const char **kname = nullptr);
 // seam_kernel: the outputs whose window straddles two blocks; launch after launch_fused on the same stream
-hipError_t launch_seam(int dst_f32, const F32View &df, const F64View &dd, const FusedArgs &a, hipStream_t st);
+hipError_t launch_seam(const AnyView &out, const FusedArgs &a, hipStream_t st);
 bool fused_shape_supported(int log2n, int log2p, int n, int span, int max_seam_outputs);
 bool fused_mfma_supported(int log2n, int log2p, int ksteps);
 hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st);
@@ -464,11 +463,10 @@ struct PolyMfArgs {
   unsigned pps_magic;    // as DftArgs::pps_magic
 };
 bool polymf_supported(int ksteps);
-hipError_t launch_polymf(int ksteps, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                         const F64View &dd, const PolyMfArgs &a, hipStream_t st, const char **kname = nullptr);
+hipError_t launch_polymf(int ksteps, const AnyView &in, const AnyView &out, const PolyMfArgs &a, hipStream_t st,
+                         const char **kname = nullptr);
 // element-wise copy of absolute range [a0, a1) of every channel from one fifo view to another
 // (ring regrow, carrying the unconsumed tail of an in-place push into the ring, device pulls)
-hipError_t launch_copy(int f32, const F32View &sf, const F64View &sd, const F32View &df, const F64View &dd, long long a0,
-                       long long a1, int C, hipStream_t st);
+hipError_t launch_copy(const AnyView &in, const AnyView &out, long long a0, long long a1, int C, hipStream_t st);
 
 } // namespace rsmp

@@ -110,18 +110,18 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
   bool ofast = false;
   char *obase = nullptr;
   int ofs = 2;
-  const int esz = frame_elem_bytes(out.is_f32); // bytes per sample of the destination frames
+  const int esz = frame_elem_bytes(out.kind); // bytes per sample of the destination frames
   {
     const long long o0 = a.out_offset + fb.i_lo, o1 = o0 + fb.cnt;
-    if (out.is_f32 && hasb && !(out.f.nch & 1)) {
+    if (out.kind && hasb && !(out.f.nch & 1)) {
       const int hp = out.f.nch >> 1, strm = pair / hp, pin = pair - strm * hp;
       ofs = out.f.nch;
       if (out.f.ext && o0 >= out.f.ext_begin && o1 <= out.f.ext_end) {
-        obase = reinterpret_cast<char *>(out.f.ext) + (strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin) * esz;
+        obase = static_cast<char *>(out.f.ext) + (strm * out.f.ext_stream_stride + (o0 - out.f.ext_begin) * out.f.nch + 2 * pin) * esz;
         ofast = true;
       } else if ((!out.f.ext || o0 >= out.f.ext_end || o1 <= out.f.ext_begin) &&
                  (o0 & out.f.ring_mask) + (o1 - o0) <= out.f.ring_mask + 1) {
-        obase = reinterpret_cast<char *>(out.f.ring) + (strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin) * esz;
+        obase = static_cast<char *>(out.f.ring) + (strm * out.f.ring_stream_stride + (o0 & out.f.ring_mask) * out.f.nch + 2 * pin) * esz;
         ofast = true;
       }
       ofast = ofast && (reinterpret_cast<unsigned long long>(obase) & (2 * esz - 1)) == 0;
@@ -218,19 +218,18 @@ template <int KS> __global__ __launch_bounds__(256, KS <= 8 ? 4 : 3) void polymf
     }
   };
   if (ofast && esz == 8) run(std::integral_constant<int, 2>{});
-  else if (ofast && out.is_f32 == kFramesS16) run(std::integral_constant<int, 3>{});
-  else if (ofast && out.is_f32 == kFramesS32) run(std::integral_constant<int, 4>{});
+  else if (ofast && out.kind == kFramesS16) run(std::integral_constant<int, 3>{});
+  else if (ofast && out.kind == kFramesS32) run(std::integral_constant<int, 4>{});
   else if (ofast) run(std::integral_constant<int, 1>{});
   else run(std::integral_constant<int, 0>{});
 }
 
 bool polymf_supported(int ksteps) { return ksteps >= 7 && ksteps <= 9; }
 
-hipError_t launch_polymf(int ksteps, int src_f32, int dst_f32, const F32View &sf, const F64View &sd, const F32View &df,
-                         const F64View &dd, const PolyMfArgs &a, hipStream_t st, const char **kname)
+hipError_t launch_polymf(int ksteps, const AnyView &in, const AnyView &out, const PolyMfArgs &a, hipStream_t st,
+                         const char **kname)
 {
   if (kname) *kname = ksteps == 7 ? "rsmp::polymf_kernel<7>" : ksteps == 8 ? "rsmp::polymf_kernel<8>" : "rsmp::polymf_kernel<9>";
-  const AnyView in = make_view(src_f32, sf, sd), out = make_view(dst_f32, df, dd);
   const size_t lds_bytes = size_t(kPmPad + a.Vt + a.n + 4 + kPmPad) * 16;
   PolyMfArgs b = a;
   b.npairs = pair_count(a.C, a.nchs);
