@@ -3,7 +3,9 @@
 #include "../../include/ratelib_amd.h"
 
 #include "engine.hpp"
+#include "lpc.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -379,6 +381,47 @@ long long RRX_debug_tile_walk(const RRX_walk_geom *g, int k, long long *head, in
   pa.nsub = g->nsub;
   pa.Vs = g->Vs;
   return (long long)rsmp::fused_walk_enumerate(pa, k, head, slots, cap);
+}
+
+// lpc/lpc.h:27 on device-resident frames.  Everything that can be refused from the arguments alone is refused before any
+// device is touched.
+int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data, size_t stream_stride, int nstreams, size_t data_len,
+                               int nch, int lpc_order, size_t extra_bkwd, size_t extra_fwd)
+{
+  if (!d_data || nstreams < 1 || nch < 1 || lpc_order < 1 || lpc_order > rsmp::kLpcMaxOrder || data_len <= size_t(lpc_order)) return RR_INVPARAM;
+  if (nstreams > 1 && stream_stride < extra_bkwd + data_len + extra_fwd) return RR_INVPARAM;
+  if (device < -1 || (long long)nstreams * nch > 0x7fffffffLL) return RR_INVPARAM; // (one workgroup per channel of every stream)
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!extra_bkwd && !extra_fwd) return RR_OK;
+  if (device >= 0) { // as RRX_open_batch_on
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return RR_EXTUNINIT;
+    if (device >= n) return RR_INVPARAM;
+  }
+  if (!rsmp::device_is_gfx950(device)) return RR_EXTUNINIT;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  const hipError_t e = rsmp::launch_lpc_extrapolate(static_cast<hipStream_t>(hip_stream), d_data, stream_stride, nstreams, data_len,
+                                                    nch, lpc_order, extra_bkwd, extra_fwd);
+  return e == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// foo_dsp_rate.cpp:96-101 with samples_len of util.h:38-48
+int RRX_edge_geometry(size_t in_rate, size_t out_rate, size_t *n_add, size_t *n_drop, size_t *prime_len, size_t *inbuf)
+{
+  if (!in_rate || !out_rate || !n_add || !n_drop || !prime_len || !inbuf) return RR_INVPARAM;
+  size_t a = in_rate, b = out_rate;
+  while (b) { const size_t c = a % b; a = b; b = c; } // a = gcd
+  const size_t v = a, r1 = in_rate / v, r2 = out_rate / v, z = r1 > r2 ? r1 : r2;
+  size_t n = (v + 20 - 1) / 20; // 1/20 s ...
+  if (z * n > 8192) n = 8192 / z; // ... but neither count above 8192 ...
+  if (n < 1) n = 1;               // ... unless one period already is
+  *n_add = r1 * n;
+  *n_drop = r2 * n;
+  const size_t prime = std::min<size_t>(std::max<size_t>(in_rate / 20, 1024), 16384);
+  *prime_len = std::max<size_t>(prime, 2 * rsmp::kLpcMaxOrder + 1);
+  *inbuf = std::min<size_t>(std::max<size_t>(in_rate / 10, 2048), 65536);
+  return RR_OK;
 }
 
 size_t RRX_isamp_max(const RR_handle *h) { return h ? h->eng->isamp_max() : 0; }

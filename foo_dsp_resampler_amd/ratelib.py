@@ -19,6 +19,7 @@ EXPECTED_SYMBOLS = [
     "RRX_pull_device_double", "RRX_flow_device_double",
     "RRX_push_samples", "RRX_pull_samples", "RRX_flow_samples", "RRX_push_device_samples", "RRX_pull_device_samples",
     "RRX_flow_device_samples",
+    "RRX_lpc_extrapolate_device", "RRX_edge_geometry",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
@@ -153,6 +154,9 @@ def lib():
         L.RRX_describe_plan.argtypes = [P(RRConfig), C.c_char_p, sz]
         L.RRX_describe_dispatch.argtypes = [P(RRConfig), C.c_int, C.c_char_p, sz]
         L.RRX_plan_table.argtypes = [P(RRConfig), C.c_int, vp, sz, P(sz)]
+        if hasattr(L, "RRX_lpc_extrapolate_device"):  # (as above: an older tree's build has none)
+            L.RRX_lpc_extrapolate_device.argtypes = [C.c_int, vp, vp, sz, C.c_int, sz, C.c_int, C.c_int, sz, sz]
+            L.RRX_edge_geometry.argtypes = [sz, sz, P(sz), P(sz), P(sz), P(sz)]
         _lib = L
     return _lib
 
@@ -197,6 +201,42 @@ def plan_table(which, in_rate, out_rate, **kw):
     if n.value:
         lib().RRX_plan_table(C.byref(cfg), which, out.ctypes.data, n.value, C.byref(n))
     return out
+
+
+def edge_geometry(in_rate, out_rate):
+    """Host-only: the plugin's edge geometry for a rate pair, (n_add, n_drop, prime_len, inbuf) in frames (RRX_edge_geometry):
+    frames to extrapolate at each end of the input, frames to cut from each end of the output, base frames the extrapolator
+    looks at, the plugin's staging buffer.  Needs no GPU."""
+    v = [C.c_size_t(0) for _ in range(4)]
+    _check(lib().RRX_edge_geometry(int(in_rate), int(out_rate), *[C.byref(x) for x in v]), "RRX_edge_geometry")
+    return tuple(x.value for x in v)
+
+
+def lpc_extrapolate_device(t, first, data_len, extra_bkwd, extra_fwd, order=32, stream=None):
+    """LPC edge extrapolation in place on the device (RRX_lpc_extrapolate_device; lpc_extrapolate2 of lpc/lpc.h:27, bit for bit).
+
+    `t` is a contiguous float32 device tensor [frames, nch] or [nstreams, frames, nch]; the base data are the `data_len` frames
+    from frame `first` of every stream.  Frames [first - extra_bkwd, first) and [first + data_len, first + data_len + extra_fwd)
+    are overwritten, nothing else.  `stream`: a hipStream_t as an integer or a torch stream (None / 0 = the default stream); the
+    call only enqueues, and the ordering against work on other streams is the caller's (ratelib_amd.h)."""
+    shape = tuple(t.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    if not str(t.dtype).endswith("float32"):
+        raise TypeError("%s buffer: the LPC extrapolator works on float32 frames only" % (t.dtype,))
+    if not t.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
+    first, data_len, extra_bkwd, extra_fwd = int(first), int(data_len), int(extra_bkwd), int(extra_fwd)
+    if min(first, data_len, extra_bkwd, extra_fwd) < 0 or first < extra_bkwd or first + data_len + extra_fwd > frames:
+        raise ValueError("frames [%d, %d) do not lie inside the tensor's %d frames"
+                         % (first - extra_bkwd, first + data_len + extra_fwd, frames))
+    _ensure_init()
+    index = getattr(getattr(t, "device", None), "index", None)
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_lpc_extrapolate_device(-1 if index is None else int(index), C.c_void_p(ptr),
+                                            C.c_void_p(t.data_ptr() + first * nch * 4), frames, nstreams, data_len, nch, int(order),
+                                            extra_bkwd, extra_fwd), "RRX_lpc_extrapolate_device")
 
 
 def _ensure_init():
@@ -248,6 +288,7 @@ class Resampler:
         self.dtype = dtype
         self.cfg = _config(in_rate, out_rate, **kw)
         self.h = C.c_void_p()
+        self._stream = None  # the caller's hipStream_t (an integer) after set_stream, None while the handle uses its own
         if dtype != np.float32:
             _check(self.L.RRX_open_batch_fmt(C.byref(self.cfg), nch, nstreams, -1 if device is None else int(device), _DTYPE_FMT[dtype],
                                              C.byref(self.h)), "RRX_open_batch_fmt")
@@ -303,10 +344,12 @@ class Resampler:
     def set_stream(self, hip_stream_ptr):
         """hipStream_t as an integer (torch: stream.cuda_stream); 0 / None = the default stream."""
         _check(self.L.RRX_set_stream(self.h, C.c_void_p(hip_stream_ptr or 0)), "RRX_set_stream")
+        self._stream = int(hip_stream_ptr or 0)
 
     def use_own_stream(self):
         """Back to the stream the handle created for itself (RRX_STREAM_OWN)."""
         _check(self.L.RRX_set_stream(self.h, C.c_void_p(C.c_size_t(-1).value)), "RRX_set_stream")
+        self._stream = None
 
     def sync(self):
         _check(self.L.RRX_sync(self.h), "RRX_sync")
@@ -480,3 +523,62 @@ class Resampler:
                                       in_stride or in_frames, C.c_void_p(tout.data_ptr()), out_stride or out_cap,
                                       in_frames, out_cap, C.byref(iu), C.byref(og)), "RRX_flow_device")
         return iu.value, og.value
+
+    def convert_track_device(self, x):
+        """One whole track per stream, device to device, with the plugin's edge treatment (dsp_rate::on_chunk / flushwrite,
+        foo_dsp_rate.cpp:154-168, 218-313) for all streams of the handle at once: `x` is a float32 device tensor
+        [nstreams, frames, nch]; the resampled tracks are returned as a new tensor [nstreams, frames_out, nch].
+
+        Up to 2 * LPC_ORDER = 64 frames a track is pushed, drained and pulled as it is (:222-239).  A longer one is extended at
+        both ends by n_add frames of LPC extrapolation from its first and its last prime = min(frames, prime_len) frames
+        (edge_geometry), pushed in isamp_max-sized pieces and drained, and n_drop frames are cut from each end of what comes out.
+        Everything runs on torch's current stream of x's device (the handle is switched to it for the call and back afterwards);
+        no sample is copied to the host.  The handle is left drained, as after RR_drain: a track takes a handle of its own, as
+        in the plugin (foo_dsp_rate.cpp:282)."""
+        import torch
+        if self.dtype != np.float32:
+            raise TypeError("convert_track_device needs a float32 handle (the LPC arithmetic is float32), not %s" % self.dtype)
+        if tuple(x.shape[::2]) != (self.nstreams, self.nch) or x.dim() != 3:
+            raise ValueError("expected a [%d, frames, %d] tensor, got shape %r" % (self.nstreams, self.nch, tuple(x.shape)))
+        if x.dtype != torch.float32 or not x.is_cuda or x.device.index != self.device:
+            raise TypeError("expected a torch.float32 tensor on the handle's device (cuda:%d)" % self.device)
+        x = x.contiguous()
+        frames = x.shape[1]
+        in_rate, out_rate = self.cfg.in_rate, self.cfg.out_rate
+        n_add, n_drop, prime_len, _ = edge_geometry(in_rate, out_rate)
+        cur = torch.cuda.current_stream(x.device)
+        prev = self._stream
+        self.set_stream(cur.cuda_stream)
+        try:
+            if frames > 64:
+                prime = min(frames, prime_len)
+                src = x.new_empty((self.nstreams, n_add + frames + n_add, self.nch))
+                src[:, n_add:n_add + frames] = x
+                lpc_extrapolate_device(src, n_add, prime, n_add, 0, stream=cur)
+                lpc_extrapolate_device(src, n_add + frames - prime, prime, 0, n_add, stream=cur)
+            else:
+                src, n_drop = x, 0
+            total = src.shape[1]
+            cap = total * out_rate // in_rate + 2  # drain leaves round(total * out_rate / in_rate) frames in all
+            out = x.new_empty((self.nstreams, cap, self.nch))
+            got = 0
+
+            def pull():
+                nonlocal got
+                while self.available:
+                    if got >= cap:
+                        raise RuntimeError("convert_track_device: more output than %d frames in gives" % total)
+                    got += self.pull_device(out[:, got:], cap - got, stride=cap)
+
+            step = self.isamp_max
+            for pos in range(0, total, step):
+                self.push_device(src[:, pos:], min(step, total - pos), stride=total)
+                pull()
+            self.drain()
+            pull()
+            return out[:, n_drop:max(got - n_drop, n_drop)].contiguous()
+        finally:
+            if prev is None:
+                self.use_own_stream()
+            else:
+                self.set_stream(prev)

@@ -157,6 +157,41 @@ int RRX_pull_device_samples(RR_handle *h, int format, void *d_obuf, size_t out_s
 int RRX_flow_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t in_stride, void *d_obuf, size_t out_stride,
                             size_t isamp, size_t osamp, size_t *iused, size_t *ogen);
 
+/* Edge treatment for device-resident tracks.  The plugin never resamples a bare track: dsp_rate::on_chunk and flushwrite
+ * (foo_dsp_rate.cpp:154-168, 241-312) extend the first and the last buffer by N_samples_to_add frames of linear-prediction
+ * extrapolation (lpc/lpc.cpp), resample the extended signal and cut the resampled image of the extension (N_samples_to_drop
+ * frames at each end) away again, which keeps the long filters from ringing against a hard track edge.  These two calls give a
+ * caller whose frames are in HBM the same pieces; neither needs a handle.  (The drop-in plugin path keeps its own host lpc/:
+ * its data is on the host anyway.)
+ *
+ * RRX_lpc_extrapolate_device is lpc_extrapolate2(data, data_len, nch, lpc_order, extra_bkwd, extra_fwd) of lpc/lpc.h:27 for every
+ * stream of a [stream][frame][channel] float32 buffer in one call: d_data is frame 0 of stream 0's data_len base frames,
+ * stream_stride the distance between streams in frames.  Per (stream, channel) it reads the base frames, writes extra_fwd frames
+ * behind them and extra_bkwd frames in front of them (so d_data must have that many frames of room on either side) and touches
+ * nothing else; the base frames are unchanged.  The result is bit-identical to the reference's: Welch window in float
+ * (lpc.cpp:80-88), autocorrelation as serial ascending fp64 sums (:91-105), Levinson-Durbin in fp64 with the early stop and the
+ * 0.999^k damping (:107-160), float recursion with the +-10 clamp, through which a NaN passes (:162-191).
+ *   device: -1 is the calling thread's current device; any other value is checked as RRX_open_batch_on checks it (RR_INVPARAM for
+ *   an index the process does not have, RR_EXTUNINIT for a device that is not gfx950).  The caller's device is restored on return.
+ *   hip_stream: a hipStream_t as in RRX_set_stream (NULL = the device's default stream).  The call only enqueues: no allocation,
+ *   no host synchronisation.  Ordering is the caller's, exactly as for the *_device calls above: whatever filled the base frames
+ *   (or last wrote the frames around them) on ANOTHER stream must have completed, or be ordered before hip_stream by an event,
+ *   when the call is made; work on hip_stream itself is ordered by the stream.
+ * Returns RR_INVPARAM, before any device is touched, for NULL data, nstreams < 1, nch < 1, lpc_order outside 1..32,
+ * data_len <= lpc_order, or nstreams > 1 with stream_stride < extra_bkwd + data_len + extra_fwd; RR_EXTUNINIT before
+ * init_ratelib; RR_INTERNAL for a failed launch.  extra_bkwd == extra_fwd == 0 is RR_OK and does nothing.
+ * Float32 frames only (the reference arithmetic is float32): double and integer buffers have no such call. */
+int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data, size_t stream_stride, int nstreams,
+                               size_t data_len, int nch, int lpc_order, size_t extra_bkwd, size_t extra_fwd);
+
+/* Host-only (no GPU needed): the plugin's edge geometry for a rate pair (dsp_rate::reinit, foo_dsp_rate.cpp:96-101).
+ * *n_add / *n_drop = samples_len(in_rate, out_rate, 20, 8192) of util.h:38-48: frames to extrapolate at each end of the input
+ * and frames to cut from each end of the output, the same duration at the two rates (n_add * out_rate == n_drop * in_rate);
+ * *prime_len = max(clamp(in_rate / 20, 1024, 16384), 65): the base frames the extrapolator looks at (PRIME_LEN_);
+ * *inbuf = clamp(in_rate / 10, 2048, 65536): the plugin's staging buffer (INBUF_SIZE_).  RR_INVPARAM for a zero rate or a NULL
+ * output. */
+int RRX_edge_geometry(size_t in_rate, size_t out_rate, size_t *n_add, size_t *n_drop, size_t *prime_len, size_t *inbuf);
+
 /* Introspection: isamp_max of rate_base.h:531, frames currently pullable (fifo_occupancy of the last
  * fifo, rate_base.h:447-448), shape of the handle. */
 size_t RRX_isamp_max(const RR_handle *h);
