@@ -1180,6 +1180,23 @@ const double *orc_dft_taps(const orc_handle *h, int which, int *len) { *len = h-
 const double *orc_dft_spectrum(const orc_handle *h, int which, int *len) { *len = h->sh.dft[which].dft_length; return h->sh.dft[which].spec; }
 const double *orc_poly_table(const orc_handle *h, int *len) { *len = h->sh.poly_len; return h->sh.poly; }
 
+const double *orc_half_coefs(const orc_handle *h, int stage, int *len)
+{
+  const stage_t *s;
+  *len = 0;
+  if (stage < 0 || stage >= h->ch[0].num_stages) return NULL;
+  s = &h->ch[0].st[stage];
+  if (s->kind != ORC_STAGE_HALF) return NULL;
+  *len = s->hb_n;
+  return s->hb;
+}
+
+int orc_stage_dft_which(const orc_handle *h, int stage)
+{
+  if (stage < 0 || stage >= h->ch[0].num_stages || h->ch[0].st[stage].kind != ORC_STAGE_DFT) return -1;
+  return h->ch[0].st[stage].dft_idx;
+}
+
 const double *orc_stage_fifo(const orc_handle *h, int channel, int stage, int *len)
 {
   dfifo *f = &h->ch[channel].st[stage].in;

@@ -75,6 +75,10 @@ const double *orc_dft_taps(const orc_handle *h, int which, int *len);
 const double *orc_dft_spectrum(const orc_handle *h, int which, int *len);
 /* polyphase table [phase][tap][order+1] (rate/prepare_coefs.h:20-46) */
 const double *orc_poly_table(const orc_handle *h, int *len);
+/* half-band stage `stage`: its distinct coefficients, centre outwards (the centre tap itself is 0.5); NULL for other kinds */
+const double *orc_half_coefs(const orc_handle *h, int stage, int *len);
+/* dft stage `stage`: which shared filter it uses (0 = pre, 1 = post); -1 for other kinds */
+int orc_stage_dft_which(const orc_handle *h, int stage);
 /* current contents of the input fifo of stage `stage` (stage == num_stages: output fifo) */
 const double *orc_stage_fifo(const orc_handle *h, int channel, int stage, int *len);
 

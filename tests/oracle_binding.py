@@ -65,6 +65,9 @@ def lib():
             f.restype = P(C.c_double)
         L.orc_poly_table.argtypes = [C.c_void_p, P(C.c_int)]
         L.orc_poly_table.restype = P(C.c_double)
+        L.orc_half_coefs.argtypes = [C.c_void_p, C.c_int, P(C.c_int)]
+        L.orc_half_coefs.restype = P(C.c_double)
+        L.orc_stage_dft_which.argtypes = [C.c_void_p, C.c_int]
         L.orc_stage_fifo.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_int)]
         L.orc_stage_fifo.restype = P(C.c_double)
         L.orc_design_trace.argtypes = [C.c_void_p, P(OrcDesignCall), C.c_int]
@@ -201,6 +204,14 @@ class Oracle:
         n = C.c_int(0)
         p = self.L.orc_poly_table(self.h, C.byref(n))
         return np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.empty(0)
+
+    def half_coefs(self, stage):
+        n = C.c_int(0)
+        p = self.L.orc_half_coefs(self.h, stage, C.byref(n))
+        return np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.empty(0)
+
+    def dft_which(self, stage):
+        return self.L.orc_stage_dft_which(self.h, stage)
 
     def stage_fifo(self, channel, stage):
         n = C.c_int(0)
