@@ -27,8 +27,6 @@
 #include <atomic>
 #include <cstdlib>
 
-// RSMP_DFTX_SKIP (knobs.hpp; -DRSMP_EXPERIMENTS builds only, WRONG results): 1 = no stores of the first component pair, 2 = of the last
-
 namespace rsmp {
 
 namespace {
@@ -107,10 +105,8 @@ template <int DIR> __device__ __forceinline__ void fft8x(c64 (&u)[8], int tid, c
 // OKIND = 0 (generic): any block, element-wise fifo addressing where a span is split
 // (ring wrap, a block half in the ring and half in the caller's buffer, odd channel count) -- same arithmetic, so which
 // of the two a block gets changes no bit of its output.
-#ifndef RSMP_DFTX_WG // workgroups per CU the register budget is sized for (experiments: 2 = 256 VGPRs, 4 = 128)
-#define RSMP_DFTX_WG 3
-#endif
-template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) void dftx_kernel(AnyView in, AnyView out, DftArgs a)
+// (register budget: three workgroups per CU)
+template <int LL, int OKIND> __global__ __launch_bounds__(256, 3) void dftx_kernel(AnyView in, AnyView out, DftArgs a)
 {
   constexpr bool GENERIC = OKIND == 0;
   constexpr int P = kP, T8 = P / 8;
@@ -236,8 +232,7 @@ template <int LL, int OKIND> __global__ __launch_bounds__(256, RSMP_DFTX_WG) voi
           }
 #pragma unroll
           for (int j = 0; j < 8; ++j)
-            if (!(RSMP_DFTX_SKIP == 1 && r == 1) && !(RSMP_DFTX_SKIP == 2 && r == LL - 1))
-              *reinterpret_cast<float2 *>(ob8 + (unsigned)(jj[j] * (128 * LL)) * fbytes) = f[j];
+            *reinterpret_cast<float2 *>(ob8 + (unsigned)(jj[j] * (128 * LL)) * fbytes) = f[j];
         }
       }
     } else if ((GENERIC && so.kind == 3) || OKIND == 3) { // float64 frames, contiguous: one 16-byte store per output

@@ -57,9 +57,6 @@ const Knobs &knobs()
     if (const char *v = getenv("RSMP_SLAB_MB")) r.slab_mb = atof(v) > 0 ? atof(v) : r.slab_mb;
     if (const char *v = getenv("RSMP_SEAM_RING_MB")) r.seam_ring_mb = atof(v) > 0 ? atof(v) : r.seam_ring_mb;
     if (const char *v = getenv("RSMP_LDS_PAD")) r.lds_pad = size_t(std::max(0, atoi(v)));
-#ifdef RSMP_EXPERIMENTS
-    if (const char *v = getenv("RSMP_DBG")) r.dbg = atoi(v);
-#endif
     return r;
   }();
   return k;
@@ -328,7 +325,6 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
   if (!device_is_gfx950(device_)) return kUninit; // the code object is built for gfx950 only: refuse here, not at the first launch
   if ((rc = init_streams()) != kOk) return rc;
   const Knobs &kn = knobs(); // the environment was read once per process; nothing below or on the launch path calls getenv
-  dbg_ = kn.dbg;
   no_side_ = kn.no_side;
   if (kn.stamps) {
     ALLOC_TRY(&stamps_, 16 * sizeof(unsigned long long));
@@ -705,11 +701,7 @@ Engine::~Engine()
   pinned_free(pin_mir_);
   if (stamps_) {
     unsigned long long h[16] = {};
-    if (hipMemcpy(h, stamps_, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[7] && h[9])
-      fprintf(stderr, "RSMP_FINE per workgroup (wave 0): setup %.0f  drain %.0f  flush %.0f  Aload+addr+fill %.0f  first-LDS %.0f  steps %.0f  bookkeeping %.0f  loop %.0f\n",
-              double(h[8]) / h[7], double(h[9]) / h[7], double(h[10]) / h[7], double(h[11]) / h[7], double(h[12]) / h[7], double(h[13]) / h[7],
-              double(h[14]) / h[7], double(h[15]) / h[7]);
-    if (h[7])
+    if (hipMemcpy(h, stamps_, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[7])
       fprintf(stderr, "RSMP_STAMPS workgroups %llu  avg cycles: load %.0f  fwd %.0f  mul %.0f  inv %.0f  cf+smp %.0f  polyA %.0f  poly(B) %.0f  total %.0f\n",
               h[7], double(h[0]) / h[7], double(h[1]) / h[7], double(h[2]) / h[7], double(h[3]) / h[7], double(h[4]) / h[7],
               double(h[6]) / h[7], double(h[5]) / h[7], double(h[0] + h[1] + h[2] + h[3] + h[4] + h[5] + h[6]) / h[7]);
@@ -1047,7 +1039,6 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   fa.cfm2 = fu.cfm2;
   fa.NGRP = fu.NGRP;
   fa.KS = fu.KS;
-  fa.dbg = dbg_;
   fa.stamps = stamps_;
   const bool split = fu.nsub > 0;
   const int ntab = split ? pend.nblocks * fu.nsub : pend.nblocks; // table entries = workgroups per pair: blocks, or sub-blocks

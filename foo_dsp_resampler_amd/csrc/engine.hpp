@@ -209,7 +209,6 @@ private:
   int prof_begin(bool hot, const char *name = "");
   void prof_name(int idx, const char *name) { if (idx >= 0 && name) prof_[idx].name = name; }
   void prof_end(int idx);
-  int dbg_ = 0;           // RSMP_DBG ablation bits (0 in production)
   bool no_side_ = false;  // RSMP_NO_SIDE: keep seam kernels on the main stream
   unsigned long long *stamps_ = nullptr; // RSMP_STAMPS: device buffer of per-phase cycle sums
   void *d_stage_ = nullptr;

@@ -12,8 +12,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "knobs.hpp" // RSMP_EXP_* (wrong-result timing experiments): 0 unless the build says -DRSMP_EXPERIMENTS
-
 namespace rsmp {
 
 struct c64 { double x, y; };
@@ -141,30 +139,13 @@ constexpr int fft_lds_doubles_halves(int log2m) { return fft_lds_doubles(log2m) 
 // MODE 1 ("split"): real and imaginary halves in two rounds of 8-byte elements (M*8 bytes).
 // MODE 2 ("halves"): destinations [0, M/2) first, then [M/2, M), 16-byte elements both times (M*8 bytes plus
 //         padding): same LDS traffic as mode 0, two more barriers, half the footprint.
-// RSMP_EXP_NOBAR (timing experiments only, results are WRONG): exchanges after the first one of a transform run without
-// their workgroup barriers -- an upper bound for what wave-local exchanges could save.
-// default of the TWGEN template parameter of fft_regs / fft8_regs (every kernel that does not say otherwise)
-#ifndef RSMP_TWGEN_DEFAULT
-#define RSMP_TWGEN_DEFAULT 1
-#endif
-#ifndef RSMP_TWGEN_SQ
-#define RSMP_TWGEN_SQ 0
-#endif
-// RSMP_EXP_TWK0 (timing experiment only, WRONG results; knobs.hpp): every twiddle load reads entry k = 0 of its row (one
-// line per row: the loads stay, their misses and most of their latency go) -- upper bound of what twiddle tables in LDS
-// could buy.  RSMP_EXP_TWLOAD: only the twiddles r = 1, 2, 4, 8 are loaded.
-template <bool BAR> __device__ __forceinline__ void rsmp_xbar()
-{
-  if (BAR) (__syncthreads)();
-}
 // BYTHREAD (MODE 2 only): all 16 destinations of a thread lie in the same half of the image -- the lower one for tid < T / 2 --
 // which holds for every radix-16 pass whose butterfly stride NS is at most T / 2 (destinations of thread tid fill
 // [16 NS q, 16 NS (q + 1)), q = tid / NS).  The two rounds are then one uniform branch per wave each instead of 16 per-element
 // range tests with predicated stores (~60 vector instructions per exchange).
-template <int T, int MODE, int PADR = 1, bool BAR = true, bool BYTHREAD = false>
+template <int T, int MODE, int PADR = 1, bool BYTHREAD = false>
 __device__ __forceinline__ void lds_exchange(c64 (&v)[16], const int (&pos)[16], int tid, bool active, double *lds)
 {
-#define __syncthreads() rsmp_xbar<BAR>()
   if (MODE == 2 && BYTHREAD) {
     constexpr int H = 8 * T; // M / 2
     double2 *l2 = reinterpret_cast<double2 *>(lds);
@@ -288,15 +269,14 @@ __device__ __forceinline__ void lds_exchange(c64 (&v)[16], const int (&pos)[16],
   }
 }
 
-#undef __syncthreads
 // One pass.  PF > 0 (twiddle prefetch): this pass's twiddles were loaded into `wcur` ahead of the previous
 // exchange, and the first PF twiddles of the NEXT pass (table `twn`, butterfly stride NSN) are loaded into `wnext`
 // before this pass's exchange, so their L2 round trip runs behind the LDS round trip instead of after it.
-// TWGEN: only the twiddles w^1, w^2, w^4, w^8 of a butterfly are loaded; the other eleven are products of two of them
+// Twiddle generation: only the twiddles w^1, w^2, w^4, w^8 of a butterfly are loaded; the other eleven are products of two of them
 // (w^3 = w^1 w^2, w^5 = w^4 w^1, w^6 = w^4 w^2, w^7 = w^4 w^3, w^(8+m) = w^8 w^m): 11 complex multiplications instead of 11
 // 16-byte loads per thread and pass.  The vector-memory path, not the fp64 pipe, is what the headline kernel runs out of
 // (measured: dropping those loads -6.4 %, halving the kernel's MFMAs -3 %); a generated twiddle is off by 2-4e-16.
-template <int LOG2M, int R, int NS, int DIR, int MODE, bool LAST, int PF = 0, int NSN = 1, bool TWGEN = false>
+template <int LOG2M, int R, int NS, int DIR, int MODE, bool LAST, int PF = 0, int NSN = 1>
 __device__ __forceinline__ void fft_pass(c64 (&v)[16], int tid, bool active, const double2 *__restrict__ tw, double *lds,
                                          const double2 (&wcur)[15], double2 (&wnext)[15], const double2 *__restrict__ twn)
 {
@@ -307,15 +287,12 @@ __device__ __forceinline__ void fft_pass(c64 (&v)[16], int tid, bool active, con
       c64 b[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) b[r] = v[t + NB * r];
-      if (NS > 1 && TWGEN && R == 16) {
-        const int k = RSMP_EXP_TWK0 ? 0 : (tid + t * T) & (NS - 1);
+      if (NS > 1) { // (only the first pass has another radix than 16, and it has no twiddles)
+        static_assert(NS == 1 || R == 16, "fft_pass: twiddled passes are radix 16");
+        const int k = (tid + t * T) & (NS - 1);
         c64 w[16];
 #pragma unroll
         for (int r = 1; r < 16; r <<= 1) {
-          if (RSMP_TWGEN_SQ && r > 1) { // experiment: w^2, w^4, w^8 by squaring (one load per butterfly)
-            w[r] = cmul(w[r >> 1], w[r >> 1]);
-            continue;
-          }
           const double2 q = (PF > 0 && NB == 1) ? wcur[r - 1] : tw[(r - 1) * NS + k];
           w[r] = {q.x, q.y};
         }
@@ -336,15 +313,6 @@ __device__ __forceinline__ void fft_pass(c64 (&v)[16], int tid, bool active, con
         apply(8, w[8]);
 #pragma unroll
         for (int m = 1; m < 8; ++m) apply(8 + m, cmul(w[8], w[m]));
-      } else if (NS > 1) {
-        const int k = RSMP_EXP_TWK0 ? 0 : (tid + t * T) & (NS - 1);
-#pragma unroll
-        for (int r = 1; r < R; ++r) {
-          // RSMP_EXP_TWLOAD (timing experiment only, WRONG results): load the twiddles of r = 1, 2, 4, 8 only
-          const int rr = (RSMP_EXP_TWLOAD && (r & (r - 1))) ? 1 : r;
-          const double2 w = (PF > 0 && rr - 1 < PF && NB == 1) ? wcur[rr - 1] : tw[(rr - 1) * NS + k];
-          b[r] = DIR > 0 ? cmul(b[r], c64{w.x, w.y}) : cmulc(b[r], c64{w.x, w.y});
-        }
       }
       Bfly<R, DIR>::run(b);
 #pragma unroll
@@ -353,10 +321,9 @@ __device__ __forceinline__ void fft_pass(c64 (&v)[16], int tid, bool active, con
   }
   if (!LAST) {
     if (PF > 0 && active) {
-      const int kn = RSMP_EXP_TWK0 ? 0 : tid & (NSN - 1);
+      const int kn = tid & (NSN - 1);
 #pragma unroll
-      for (int r = 1; r <= (TWGEN ? 8 : PF); ++r)
-        if (!((RSMP_EXP_TWLOAD || TWGEN) && (r & (r - 1))) && !(TWGEN && RSMP_TWGEN_SQ && r > 1)) wnext[r - 1] = twn[(r - 1) * NSN + kn];
+      for (int r = 1; r <= 8; r <<= 1) wnext[r - 1] = twn[(r - 1) * NSN + kn];
     }
     int pos[16];
 #pragma unroll
@@ -365,24 +332,25 @@ __device__ __forceinline__ void fft_pass(c64 (&v)[16], int tid, bool active, con
 #pragma unroll
       for (int r = 0; r < R; ++r) pos[t + NB * r] = (j - k) * R + k + r * NS;
     }
-    lds_exchange<T, MODE, (NS == 1 && MODE != 1) ? R : 1, !(RSMP_EXP_NOBAR && NS > 1), (MODE == 2 && R == 16 && 2 * NS <= T)>(v, pos, tid, active, lds);
+    lds_exchange<T, MODE, (NS == 1 && MODE != 1) ? R : 1, (MODE == 2 && R == 16 && 2 * NS <= T)>(v, pos, tid, active, lds);
   }
 }
 
 // Full transform.  `tw` points at this size's table (fft_twiddle_count(LOG2M) entries).
 // PF = number of twiddles (of 15) per pass that are prefetched ahead of the preceding exchange (registers: 4 each).
-template <int LOG2M, int DIR, int MODE, int PF = 0, bool TWGEN = (RSMP_TWGEN_DEFAULT != 0)>
+constexpr int kPfFwd = 15, kPfInv = 8; // PF of the forward / inverse transform of the fused kernels' matrix-pipe variants
+template <int LOG2M, int DIR, int MODE, int PF = 0>
 __device__ __forceinline__ void fft_regs(c64 (&v)[16], int tid, bool active, const double2 *__restrict__ tw, double *lds)
 {
   constexpr int R0 = fft_first_radix(LOG2M), NP = fft_num_passes(LOG2M);
   double2 wa[15], wb[15];
-  fft_pass<LOG2M, R0, 1, DIR, MODE, NP == 1, NP >= 2 ? PF : 0, R0, TWGEN>(v, tid, active, tw, lds, wa, wa, tw);
+  fft_pass<LOG2M, R0, 1, DIR, MODE, NP == 1, NP >= 2 ? PF : 0, R0>(v, tid, active, tw, lds, wa, wa, tw);
   if constexpr (NP >= 2)
-    fft_pass<LOG2M, 16, R0, DIR, MODE, NP == 2, NP >= 3 ? PF : 0, R0 * 16, TWGEN>(v, tid, active, tw, lds, wa, wb, tw + 15 * R0);
+    fft_pass<LOG2M, 16, R0, DIR, MODE, NP == 2, NP >= 3 ? PF : 0, R0 * 16>(v, tid, active, tw, lds, wa, wb, tw + 15 * R0);
   if constexpr (NP >= 3)
-    fft_pass<LOG2M, 16, R0 * 16, DIR, MODE, NP == 3, NP >= 4 ? PF : 0, R0 * 256, TWGEN>(v, tid, active, tw + 15 * R0, lds, wb, wa,
+    fft_pass<LOG2M, 16, R0 * 16, DIR, MODE, NP == 3, NP >= 4 ? PF : 0, R0 * 256>(v, tid, active, tw + 15 * R0, lds, wb, wa,
                                                                                          tw + 15 * R0 * 17);
-  if constexpr (NP >= 4) fft_pass<LOG2M, 16, R0 * 256, DIR, MODE, NP == 4, 0, 1, TWGEN>(v, tid, active, tw + 15 * R0 * 17, lds, wa, wb, tw);
+  if constexpr (NP >= 4) fft_pass<LOG2M, 16, R0 * 256, DIR, MODE, NP == 4, 0, 1>(v, tid, active, tw + 15 * R0 * 17, lds, wa, wb, tw);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -404,7 +372,7 @@ constexpr int fft8_twiddle_count(int log2m)
 }
 constexpr int fft8_lds_doubles(int log2m) { return 2 * ((1 << log2m) + (1 << log2m) / 8); } // first exchange padded
 
-template <int LOG2M, int R, int NS, int DIR, bool LAST, bool TWGEN = false>
+template <int LOG2M, int R, int NS, int DIR, bool LAST>
 __device__ __forceinline__ void fft8_pass(c64 (&u)[8], int tid, const double2 *__restrict__ tw, double *lds, bool active = true)
 {
   constexpr int T8 = (1 << LOG2M) / 8, NB = 8 / R;
@@ -414,19 +382,15 @@ __device__ __forceinline__ void fft8_pass(c64 (&u)[8], int tid, const double2 *_
     c64 b[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) b[r] = u[t + NB * r];
-    if (NS > 1 && TWGEN && R >= 4) { // w^1, w^2 (, w^4) loaded, the rest multiplied up (see fft_pass)
-      const int k = RSMP_EXP_TWK0 ? 0 : (tid + t * T8) & (NS - 1);
+    if (NS > 1) { // w^1 (, w^2, w^4) loaded, the rest multiplied up (see fft_pass)
+      const int k = (tid + t * T8) & (NS - 1);
       c64 w[8];
 #pragma unroll
       for (int r = 1; r < R; r <<= 1) {
-        if (RSMP_TWGEN_SQ && r > 1) {
-          w[r] = cmul(w[r >> 1], w[r >> 1]);
-          continue;
-        }
         const double2 q = tw[(r - 1) * NS + k];
         w[r] = {q.x, q.y};
       }
-      w[3] = cmul(w[1], w[2]);
+      if (R >= 4) w[3] = cmul(w[1], w[2]);
       if (R == 8) {
         w[5] = cmul(w[4], w[1]);
         w[6] = cmul(w[4], w[2]);
@@ -434,14 +398,6 @@ __device__ __forceinline__ void fft8_pass(c64 (&u)[8], int tid, const double2 *_
       }
 #pragma unroll
       for (int r = 1; r < R; ++r) b[r] = DIR > 0 ? cmul(b[r], w[r]) : cmulc(b[r], w[r]);
-    } else if (NS > 1) {
-      const int k = RSMP_EXP_TWK0 ? 0 : (tid + t * T8) & (NS - 1);
-#pragma unroll
-      for (int r = 1; r < R; ++r) {
-        const int rr = (RSMP_EXP_TWLOAD && (r & (r - 1))) ? 1 : r;
-        const double2 w = tw[(rr - 1) * NS + k];
-        b[r] = DIR > 0 ? cmul(b[r], c64{w.x, w.y}) : cmulc(b[r], c64{w.x, w.y});
-      }
     }
     Bfly<R, DIR>::run(b);
 #pragma unroll
@@ -459,7 +415,7 @@ __device__ __forceinline__ void fft8_pass(c64 (&u)[8], int tid, const double2 *_
         for (int r = 0; r < R; ++r) l2[lds_phys<PADR>((j - k) * R + k + r * NS)] = make_double2(u[t + NB * r].x, u[t + NB * r].y);
       }
     }
-    if (!(RSMP_EXP_NOBAR >= 2 && NS > 1)) __syncthreads();
+    __syncthreads();
     if (active) { // element tid + s T8 sits at phys(tid) + s (T8 + T8 / pad period): one address, seven immediates
       constexpr int RS = T8 + (PADR >= 8 ? T8 / PADR : 0);
       int rb = lds_phys_u<PADR>(unsigned(tid));
@@ -471,12 +427,12 @@ __device__ __forceinline__ void fft8_pass(c64 (&u)[8], int tid, const double2 *_
         u[s] = {q.x, q.y};
       }
     }
-    if (!(RSMP_EXP_NOBAR >= 2 && NS > 1)) __syncthreads();
+    __syncthreads();
   }
 }
 
 // ---- the same transform with its twiddles PRELOADED: every table read of a thread (w^1, w^2 (, w^4) of each twiddled pass, the
-// rest multiplied up as in the TWGEN form) is issued by fft8_tw_load in one go, typically next to the block's input loads, so
+// rest multiplied up as in fft8_pass) is issued by fft8_tw_load in one go, typically next to the block's input loads, so
 // the whole transform pays one memory round trip instead of one per pass (hipcc does not hoist a pass's table loads over the
 // s_barrier of the exchange in front of it: in fft8_regs each pass exposes a full L2 latency).  Same arithmetic, same bits.
 constexpr int fft8_tw_regs(int log2m)
@@ -551,7 +507,7 @@ __device__ __forceinline__ void fft8_regs_pre(c64 (&u)[8], int tid, const double
 {
   constexpr int NP = fft8_num_passes(LOG2M), RL = fft8_last_radix(LOG2M), NW = fft8_tw_regs(LOG2M);
   static_assert(NP >= 3 && NP <= 4, "fft8_regs_pre: 512 <= M <= 4096");
-  fft8_pass<LOG2M, 8, 1, DIR, false, true>(u, tid, nullptr, lds, true); // twiddle-free first pass (padded exchange)
+  fft8_pass<LOG2M, 8, 1, DIR, false>(u, tid, nullptr, lds, true); // twiddle-free first pass (padded exchange)
   between(0);
   if constexpr (NP == 3) {
     fft8_pass_pre<LOG2M, 8, 8, DIR, false, 0, NW>(u, tid, w, lds);
@@ -567,26 +523,26 @@ __device__ __forceinline__ void fft8_regs_pre(c64 (&u)[8], int tid, const double
 }
 
 // `active`: threads that hold points (tid < M/8); every thread of the workgroup must call (barriers)
-template <int LOG2M, int DIR, bool TWGEN = (RSMP_TWGEN_DEFAULT != 0)>
+template <int LOG2M, int DIR>
 __device__ __forceinline__ void fft8_regs_masked(c64 (&u)[8], int tid, bool active, const double2 *__restrict__ tw, double *lds)
 {
   constexpr int NP = fft8_num_passes(LOG2M), RL = fft8_last_radix(LOG2M);
   static_assert(NP >= 2 && NP <= 5, "fft8_regs: 64 <= M <= 8192");
-  fft8_pass<LOG2M, 8, 1, DIR, false, TWGEN>(u, tid, tw, lds, active);
-  if constexpr (NP == 2) fft8_pass<LOG2M, RL, 8, DIR, true, TWGEN>(u, tid, tw, lds, active);
-  if constexpr (NP >= 3) fft8_pass<LOG2M, 8, 8, DIR, false, TWGEN>(u, tid, tw, lds, active);
-  if constexpr (NP == 3) fft8_pass<LOG2M, RL, 64, DIR, true, TWGEN>(u, tid, tw + 7 * 8, lds, active);
-  if constexpr (NP >= 4) fft8_pass<LOG2M, 8, 64, DIR, false, TWGEN>(u, tid, tw + 7 * 8, lds, active);
-  if constexpr (NP == 4) fft8_pass<LOG2M, RL, 512, DIR, true, TWGEN>(u, tid, tw + 7 * 8 + 7 * 64, lds, active);
+  fft8_pass<LOG2M, 8, 1, DIR, false>(u, tid, tw, lds, active);
+  if constexpr (NP == 2) fft8_pass<LOG2M, RL, 8, DIR, true>(u, tid, tw, lds, active);
+  if constexpr (NP >= 3) fft8_pass<LOG2M, 8, 8, DIR, false>(u, tid, tw, lds, active);
+  if constexpr (NP == 3) fft8_pass<LOG2M, RL, 64, DIR, true>(u, tid, tw + 7 * 8, lds, active);
+  if constexpr (NP >= 4) fft8_pass<LOG2M, 8, 64, DIR, false>(u, tid, tw + 7 * 8, lds, active);
+  if constexpr (NP == 4) fft8_pass<LOG2M, RL, 512, DIR, true>(u, tid, tw + 7 * 8 + 7 * 64, lds, active);
   if constexpr (NP == 5) {
-    fft8_pass<LOG2M, 8, 512, DIR, false, TWGEN>(u, tid, tw + 7 * 8 + 7 * 64, lds, active);
-    fft8_pass<LOG2M, RL, 4096, DIR, true, TWGEN>(u, tid, tw + 7 * 8 + 7 * 64 + 7 * 512, lds, active);
+    fft8_pass<LOG2M, 8, 512, DIR, false>(u, tid, tw + 7 * 8 + 7 * 64, lds, active);
+    fft8_pass<LOG2M, RL, 4096, DIR, true>(u, tid, tw + 7 * 8 + 7 * 64 + 7 * 512, lds, active);
   }
 }
-template <int LOG2M, int DIR, bool TWGEN = (RSMP_TWGEN_DEFAULT != 0)>
+template <int LOG2M, int DIR>
 __device__ __forceinline__ void fft8_regs(c64 (&u)[8], int tid, const double2 *__restrict__ tw, double *lds)
 {
-  fft8_regs_masked<LOG2M, DIR, TWGEN>(u, tid, true, tw, lds);
+  fft8_regs_masked<LOG2M, DIR>(u, tid, true, tw, lds);
 }
 
 } // namespace rsmp

@@ -23,40 +23,10 @@
 #include <cstdlib>
 #include <cstdio>
 
-// Profiling switches (knobs.hpp; read once per process, all zero / unset in production).  The RSMP_DBG ablation bits give
-// WRONG results and only exist in -DRSMP_EXPERIMENTS builds (RSMP_DBGBITS is the constant 0 otherwise):
-//   RSMP_DBG bit 0 (1): skip the polyphase stage       bit 1 (2): skip the inverse FFT      bit 2 (4): skip the forward FFT
-//            bit 4 (16): compute the polyphase sums but do not store them
-//            bit 5 (32) / 6 (64): matrix-pipe variant, skip round B / round A
-//            bit 9 (512): reuse the first B operands of an item (no further LDS reads)
-//            bit 10 (1024): do not reload A tiles      bit 8 (256): drain all counters at every RSMP_STAMPS stamp
+// Profiling switches (knobs.hpp; read once per process, all unset in production):
 //   RSMP_STAMPS=1   per-phase cycle sums of wave 0 (s_memtime), printed when the handle closes (intrusive: ~2x slower)
 //   RSMP_LDS_PAD=n  add n bytes of LDS per workgroup (occupancy experiments), RSMP_OCC=1 prints the resulting blocks/CU
 //   RSMP_NO_MFMA / RSMP_NO_FUSE / RSMP_NO_POLYMF / RSMP_NO_SIDE / RSMP_SLAB_MB: engine.cpp
-//
-// RSMP_FWD8=1: L = 2 forward transform on all four waves, 8 points per thread (fft8_regs), no replication exchange.
-// Parity-green; the FFT part of the kernel gets 21 % faster (1.71 -> 1.36 ms with the polyphase stage skipped) but the
-// whole kernel does not (2.67 vs 2.63 ms): the polyphase phase loses the FFT phases it used to overlap with.
-#ifndef RSMP_FWD8
-#define RSMP_FWD8 0
-#endif
-#ifdef RSMP_EXPERIMENTS
-#define RSMP_DBGBITS (a.dbg)
-#else
-#define RSMP_DBGBITS 0
-#endif
-// twiddles per pass prefetched ahead of the preceding LDS exchange (forward / inverse transform of the MF variant)
-// RSMP_FINE=1 (variant builds only): per-segment cycle sums of the polyphase item loop of wave 0 in the stamped workgroups,
-// with every counter drained at each segment boundary (slots 8..15 of the stamp buffer).
-#ifndef RSMP_FINE
-#define RSMP_FINE 0
-#endif
-#ifndef RSMP_PFW
-#define RSMP_PFW 15
-#endif
-#ifndef RSMP_PFI
-#define RSMP_PFI 8
-#endif
 
 namespace rsmp {
 
@@ -110,7 +80,6 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
   unsigned long long tstamp = stamping ? __builtin_readcyclecounter() : 0;
 #define RSMP_STAMP(slot) \
   if (stamping) { \
-    if (RSMP_DBGBITS & 256) __builtin_amdgcn_s_waitcnt(0); \
     const unsigned long long now = __builtin_readcyclecounter(); \
     if (tid == 0) atomicAdd(a.stamps + (slot), now - tstamp); \
     tstamp = now; \
@@ -125,12 +94,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
     const bool hasb = pc.hasb;
 
     // ---------------------------------------------------------------- load the block (fp32 -> fp64)
-    // L = 2 in the matrix-pipe variant: the forward transform has half the points of the inverse one and runs
-    // 8 points per thread on all waves (fft8_regs); a thread then already holds the 8 distinct spectrum values
-    // Zp[tid + (s & 7) * T] its 16 inverse-transform inputs need, so the replication exchange disappears
-    constexpr bool FWD8 = MF && (LOG2N - LOG2P == 1) && RSMP_FWD8;
     c64 v[16];
-    c64 u8[8];
     {
       const long long e0 = B * a.d.q;
       bool fast = false;
@@ -152,31 +116,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       // float64 / integer PCM frames: the same pairs as one 16- / 4- / 8-byte word per sample (pair_span kinds 3 / 4 / 5), else
       // element-wise
       const PairSpan d64 = in.kind >= kFramesF64 ? pair_span(in, pair, hasb, e0, P, ca) : PairSpan{0, nullptr, 1, nullptr, nullptr, hasb};
-      if constexpr (FWD8) { // every thread takes 8 points of the P-point forward transform: x[tid + s*T], T = P/8
-        if (fast) {
-#pragma unroll
-          for (int s = 0; s < 8; ++s) {
-            const float2 f = p2[(tid + s * T) * fstride];
-            u8[s] = {(double)f.x, (double)f.y};
-          }
-        } else if (d64.kind == 3) {
-#pragma unroll
-          for (int s = 0; s < 8; ++s) {
-            const double2 f = d64.d2[(tid + s * T) * d64.fstride];
-            u8[s] = {f.x, f.y};
-          }
-        } else if (d64.kind >= 4) {
-          span_load<8>(d64, tid, T, u8);
-        } else {
-          const ChanRef ia = chan_ref(in, ca), ib = chan_ref(in, hasb ? cb : ca);
-#pragma unroll
-          for (int s = 0; s < 8; ++s) {
-            const long long e = e0 + tid + s * T;
-            u8[s].x = fifo_get(ia, e);
-            u8[s].y = hasb ? fifo_get(ib, e) : 0.0;
-          }
-        }
-      } else if (fwd_active) {
+      if (fwd_active) {
         if (fast) {
 #pragma unroll
           for (int s = 0; s < 16; ++s) {
@@ -202,21 +142,10 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
 
     RSMP_STAMP(0)
     // ---------------------------------------------------------------- FFT-FIR (as dft_kernel)
-    if constexpr (FWD8) {
-      double2 g[16]; // in flight during the whole forward transform (32 + 64 registers live)
-#pragma unroll
-      for (int s = 0; s < 16; ++s) g[s] = Gp[tid + s * T];
-      if (!(RSMP_DBGBITS & 4)) fft8_regs<LOG2P, -1>(u8, tid, a.d.tw_fwd8, lds);
-      RSMP_STAMP(1)
-#pragma unroll
-      for (int s = 0; s < 16; ++s) v[s] = cmul(u8[s & 7], c64{g[s].x, g[s].y});
-      __syncthreads(); // the inverse transform's exchange reuses the LDS the forward one just read
-    } else {
-    if (!(RSMP_DBGBITS & 4)) fft_regs<LOG2P, -1, (MF && LOG2P == LOG2N) ? 2 : 0, MF ? RSMP_PFW : 0>(v, tid, fwd_active, a.d.tw_fwd, lds);
+    // (L = 2 on all four waves, 8 points per thread as in the lean kernel: FFT part 21 % faster, whole kernel not -- 2.67 vs 2.63 ms)
+    fft_regs<LOG2P, -1, (MF && LOG2P == LOG2N) ? 2 : 0, MF ? kPfFwd : 0>(v, tid, fwd_active, a.d.tw_fwd, lds);
     RSMP_STAMP(1)
-    }
-    if constexpr (FWD8) {
-    } else if constexpr (LOG2P < LOG2N) {
+    if constexpr (LOG2P < LOG2N) {
       double2 g[16]; // issued before the exchange so the L2 latency overlaps it
 #pragma unroll
       for (int s = 0; s < 16; ++s) g[s] = Gp[tid + s * T];
@@ -268,7 +197,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       }
     }
     RSMP_STAMP(2)
-    if (!(RSMP_DBGBITS & 2)) fft_regs<LOG2N, +1, MF ? 2 : 0, MF ? RSMP_PFI : 0>(v, tid, true, a.d.tw_inv, lds);
+    fft_regs<LOG2N, +1, MF ? 2 : 0, MF ? kPfInv : 0>(v, tid, true, a.d.tw_inv, lds);
     RSMP_STAMP(3)
 
     // coefficient tile of this thread: rows of its G phases shifted to a common window start and zero
@@ -331,7 +260,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
       const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
       const int irel_hi = fb.irel_lo + fb.cnt;
-      const bool run = !(RSMP_DBGBITS & 1) && fb.cnt > 0;
+      const bool run = fb.cnt > 0;
 
       bool ofast = false;
       char *obase = nullptr;  // frame i_lo's first sample of this pair
@@ -423,38 +352,20 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
         // the window start of outputs that are not stored anyway (block edges) into the image
         auto poly_round = [&](int kb, int ke, const double2 *xs, int li_lo, int li_hi) {
           const int ncs = (ke - kb + 3) >> 2, half0 = (ncs + 1) >> 1; // column steps of 4 periods
-#if RSMP_FINE
-#define RSMP_TICK(slot, drain)                                         \
-  if (stamping) {                                                       \
-    if (drain) __builtin_amdgcn_s_waitcnt(0);                           \
-    const unsigned long long now = __builtin_readcyclecounter();       \
-    if (tid == 0) atomicAdd(a.stamps + (slot), now - ftick);            \
-    ftick = __builtin_readcyclecounter();                               \
-  }
-          unsigned long long ftick = stamping ? __builtin_readcyclecounter() : 0;
-#else
-#define RSMP_TICK(slot, drain)
-#endif
           for (int it = wave; it < 2 * a.NGRP; it += NW) { // (16-residue group, half of the column steps)
-            RSMP_TICK(15, 0)
             const int g = it >> 1, second = (it + (it >> 2)) & 1; // halves alternate so the waves stay balanced
             int cs0 = second ? half0 : 0, cs1 = second ? ncs : half0;
             // column steps whose 64 outputs all lie outside [irel_lo, irel_hi) (block edges) are skipped
             while (cs0 < cs1 && (kb + 4 * cs0 + 3) * pl + 16 * g + 15 < fb.irel_lo) ++cs0;
             while (cs1 > cs0 && (kb + 4 * (cs1 - 1)) * pl + 16 * g >= irel_hi) --cs1;
-            RSMP_TICK(8, 0)   // item set-up (skip tests)
-            RSMP_TICK(9, 1)   // everything still in flight from the previous item: A tile loads, stores, LDS reads
             double ca_[SPAN];
 #pragma unroll
             for (int s = 0; s < SPAN; ++s) ca_[s] = cn_[s];
             flush();
-            RSMP_TICK(10, 0)  // conversions + store issue
-            if (!(RSMP_DBGBITS & 1024)) {
-              const int nx = it + NW < 2 * a.NGRP ? it + NW : wave; // wraps to the first item of the next round
-              const double *cp = a.cfm + (nx >> 1) * (SPAN * 64);    // uniform base, lane offset added by the load
+            const int nx = it + NW < 2 * a.NGRP ? it + NW : wave; // wraps to the first item of the next round
+            const double *cp = a.cfm + (nx >> 1) * (SPAN * 64);    // uniform base, lane offset added by the load
 #pragma unroll
-              for (int s = 0; s < SPAN; ++s) cn_[s] = cp[s * 64 + lane];
-            }
+            for (int s = 0; s < SPAN; ++s) cn_[s] = cp[s * 64 + lane];
             int rb = 16 * g + 4 * bq;
             if (rb >= pl) rb = 0; // idle block: all-zero coefficients, any in-range window will do
             // window start of this lane's block in period kb + jq; later column steps add a uniform 4 * step
@@ -480,22 +391,16 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
               }
             };
             if (cs0 < cs1) fill(x0, cs0);
-            RSMP_TICK(11, 0)  // A tile load issue, window address (integer division), first fill issue
-#if RSMP_FINE
-            if (stamping) { __builtin_amdgcn_s_waitcnt(0xc07f); } // lgkmcnt(0) only
-#endif
-            RSMP_TICK(12, 0)  // first fill's LDS round trip
 #pragma unroll
             for (int u = 0; u < MAXCS; ++u) {
               if (cs0 + u < cs1) {
-                if (cs0 + u + 1 < cs1 && !(RSMP_DBGBITS & 512)) fill((u & 1) ? x0 : x1, cs0 + u + 1);
+                if (cs0 + u + 1 < cs1) fill((u & 1) ? x0 : x1, cs0 + u + 1);
                 column_step((u & 1) ? x1 : x0, pA[u], pB[u]);
               }
             }
-            RSMP_TICK(13, 0)  // column steps
             // bookkeeping for the deferred stores
             const int rD = 16 * g + 4 * bq + hi, k0 = kb + 4 * cs0;
-            pend_n = (RSMP_DBGBITS & 16) ? 0 : cs1 - cs0;
+            pend_n = cs1 - cs0;
             pend_ib = (k0 + jq) * pl + rD;
             pend_off = (pend_ib - fb.irel_lo) * frame_bytes;
             pend_hi = rD < pl ? min(irel_hi, ke * pl) : -1;
@@ -506,11 +411,10 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
                 if (k0 + 4 * u + 3 < ke && (k0 + 4 * u) * pl + 16 * g >= fb.irel_lo && (k0 + 4 * u + 3) * pl + 16 * g + 15 < irel_hi)
                   pend_allv |= 1 << u;
             }
-            RSMP_TICK(14, 0)  // store bookkeeping
           }
         };
         // round A: periods whose windows end inside the samples written above
-        if (run && !(RSMP_DBGBITS & 64)) poly_round(0, fb.KA, smp, -kPad, min(V, kSA * T) + kPad - 4 * SPAN);
+        if (run) poly_round(0, fb.KA, smp, -kPad, min(V, kSA * T) + kPad - 4 * SPAN);
         RSMP_STAMP(6)
         __syncthreads();
         // round B: the rest of the block's samples replace the image, element 0 = sample kSB0*T
@@ -524,7 +428,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
           if (tid < kPad && V > kSB0 * T) l2[V - kSB0 * T + tid] = make_double2(0.0, 0.0);
         }
         __syncthreads();
-        if (run && fb.KA < fb.K && !(RSMP_DBGBITS & 32))
+        if (run && fb.KA < fb.K)
           poly_round(fb.KA, fb.K, reinterpret_cast<const double2 *>(lds) - kSB0 * T, kSB0 * T, V + kPad - 4 * SPAN);
         flush();
       };
@@ -535,7 +439,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
       else both_rounds(std::integral_constant<int, 0>{});
     } else
     // ---------------------------------------------------------------- polyphase FIR from LDS (vector pipe)
-    if (!(RSMP_DBGBITS & 1) && poly_thread && fb.cnt > 0) {
+    if (poly_thread && fb.cnt > 0) {
       const int irel_hi = fb.irel_lo + fb.cnt;
       const int kper = a.kper; // fixed chunk length (not per block) so that the lane map's bank pattern is static
       const int kr0 = kc * kper, kr1 = min(kr0 + kper, fb.K);
@@ -587,7 +491,6 @@ __global__ __launch_bounds__((1 << LOG2N) / 16, MF ? kFusedWaves : 2) void fused
             accB[g] = fma(cf[g][mm], xv.y, accB[g]);
           }
         }
-        if (RSMP_DBGBITS & 16) { if (accA[0] == 12345.678) lds[0] = accB[0] + accA[1] + accB[1]; continue; }
         const int orel = ib - fb.irel_lo; // frame offset from i_lo (-1 for a tile whose first output is a seam output)
         if (ofast) {
           float2 *o2 = reinterpret_cast<float2 *>(obase) + orel * ostride;

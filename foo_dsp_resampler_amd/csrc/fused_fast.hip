@@ -25,47 +25,9 @@
 #include <cstdio>
 #include <type_traits>
 
-#ifndef RSMP_FAST_FWD8
-#define RSMP_FAST_FWD8 1
-#endif
-// wave priority by phase: 1 = FFT phases above the polyphase phase, 2 = the other way round (experiments)
-// twiddles multiplied up from w^1, w^2, w^4, w^8 instead of loaded (fft_device.hpp, TWGEN)
-#ifndef RSMP_TWGEN
-#define RSMP_TWGEN 1
-#endif
-// output stores as raw buffer stores with the range check done by the buffer descriptor (no per-tile compare / branch)
-#ifndef RSMP_BUFSTORE
-#define RSMP_BUFSTORE 1
-#endif
-// RSMP_EXP_SKIP (same rules): phase ablations of the lean kernel for the cycle budget of DESIGN.md 5a -- bit 0 no polyphase
-// rounds, 1 no inverse transform, 2 no forward transform, 3 no output stores, 4 no polyphase LDS reads (first tile's samples
-// reused), 5 no MFMAs (loads and stores stay), 6 no sample image / seam writes, 7 no G loads, 8 no input loads
-// RSMP_EXP_TAB / RSMP_EXP_LINEAR / RSMP_EXP_HALFMFMA (knobs.hpp; -DRSMP_EXPERIMENTS builds only, WRONG results): bit 0 = every
-// coefficient tile is group 0's, bit 1 = every G value is slot 0's (the loads stay, their L1 misses go: upper bounds of what
-// smaller / shared tables could buy); lane-linear window reads; 6 of every 14 MFMAs removed
-// forward transform (FWD8 form) on twiddles loaded next to the block's input, G issued two passes before it is needed
-#ifndef RSMP_FWD_PRETW
-#define RSMP_FWD_PRETW 1
-#endif
-#ifndef RSMP_PRIO
-#define RSMP_PRIO 0
-#endif
-#ifndef RSMP_PFW
-#define RSMP_PFW 15
-#endif
-#ifndef RSMP_PFI
-#define RSMP_PFI 8
-#endif
-
 namespace rsmp {
 
 namespace {
-// G is read once per workgroup (64 KB, twice the vector L1): RSMP_G_NT = 1 loads it non-temporally so that it does not evict
-// the twiddle rows and coefficient tiles the workgroups of a CU share
-#ifndef RSMP_G_NT
-#define RSMP_G_NT 0
-#endif
-typedef double rsmp_d2v __attribute__((ext_vector_type(2)));
 typedef unsigned int rsmp_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned int rsmp_v4u __attribute__((ext_vector_type(4)));
 // What the lean body needs to know about the sample type E of the caller-facing frames: the word that holds a frame's two
@@ -92,15 +54,9 @@ template <> struct Frame<int> {
   static __device__ __forceinline__ double in(int s) { return pcm_in(s); }
   static __device__ __forceinline__ int out(double y) { return pcm_out32(y); }
 };
-__device__ __forceinline__ double2 load_g(const double2 *p)
-{
-#if RSMP_G_NT
-  const rsmp_d2v q = __builtin_nontemporal_load(reinterpret_cast<const rsmp_d2v *>(p));
-  return make_double2(q.x, q.y);
-#else
-  return *p;
-#endif
-}
+// a G value (plain load).  It stays a function: written as `Gp[i]` at the call sites the same loads come out of the compiler
+// with another register assignment in every instance of this file
+__device__ __forceinline__ double2 load_g(const double2 *p) { return *p; }
 constexpr int kPad = 32;
 constexpr int kSA = kFusedSA, kSB0 = kFusedSB0;
 } // namespace
@@ -149,17 +105,12 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     sb = sub_block(bl - kr * a.d.nsub, a.d.V, a.d.Vs, a.d.Pref);
     e0_split = (a.d.Bref0 + kr) * a.d.q + sb.win;
   }
-#if defined(RSMP_EXPERIMENTS) && defined(RSMP_VCONST) // what a block length known at compile time would buy (553-tap filters: 3544)
-  const int V = RSMP_VCONST;
-#else
   const int V = SPLIT ? sb.len : a.d.V;
-#endif
   const bool fwd_active = tid < TF;
   const double2 *__restrict__ Gp = a.d.G;
   double2 *smp = reinterpret_cast<double2 *>(lds) + kPad; // smp[n] = (channel A, channel B) sample n of the block
   const int nm1 = a.n - 1;
 
-  if (RSMP_PRIO == 1) __builtin_amdgcn_s_setprio(3);
   // Builds with -DRSMP_STAMPS_BUILD (tools/build_variant.sh) + RSMP_STAMPS=1 in the environment: per-phase cycle sums of wave 0
   // (s_memtime) in one workgroup of 64, printed when the handle closes.  The product build has no trace of it: the stamp
   // points were branches (and scheduling barriers) in every workgroup.
@@ -178,23 +129,19 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
 
   // ---------------------------------------------------------------- load the block (fp32 -> fp64)
   // L = 2 (FWD8): the forward transform has half the points of the inverse one and runs 8 points per thread on ALL
-  // waves (fft8_regs); a thread then already holds the 8 distinct spectrum values Zp[tid + (s & 7) * T] its 16
+  // waves (fft8_regs_pre); a thread then already holds the 8 distinct spectrum values Zp[tid + (s & 7) * T] its 16
   // inverse-transform inputs need, so the replication exchange disappears.
-  constexpr bool FWD8 = (LOG2P == LOG2N - 1) && RSMP_FAST_FWD8;
+  constexpr bool FWD8 = LOG2P == LOG2N - 1;
   constexpr int NLD = FWD8 ? 8 : 16, TL = FWD8 ? T : TF; // points per loading thread, loading threads
   c64 v[16];
   c64 u8[8];
   c64 z0[SPLIT ? 16 : 1]; // sub-blocked form: component 0 of the block (samples 2m), component 1 ends up in `v`
-  constexpr bool PRETW = FWD8 && RSMP_FWD_PRETW;
-  double2 wf[PRETW ? fft8_tw_regs(LOG2P) : 1];
-  if constexpr (PRETW) fft8_tw_load<LOG2P>(wf, tid, a.d.tw_fwd8); // in flight together with the input loads below
+  // its twiddles are loaded next to the block's input, G is issued two passes before it is needed
+  double2 wf[FWD8 ? fft8_tw_regs(LOG2P) : 1];
+  if constexpr (FWD8) fft8_tw_load<LOG2P>(wf, tid, a.d.tw_fwd8); // in flight together with the input loads below
   {
     const long long e0 = SPLIT ? e0_split : B * a.d.q;
-    const bool ld_active = (FWD8 || fwd_active) && !(RSMP_EXP_SKIP & 256);
-    if (RSMP_EXP_SKIP & 256) {
-#pragma unroll
-      for (int s = 0; s < NLD; ++s) (FWD8 ? u8[s & 7] : v[s]) = {1e-3 * tid, 1e-3 * s};
-    }
+    const bool ld_active = FWD8 || fwd_active;
     if (SPLIT && io.in_unaligned) { // (uniform) a caller's buffer that is only 4-byte aligned: the sub-blocked form has no generic
       // kernel to hand such blocks to, so it reads the two channels separately
       const E *pe = io_in + strm * io.in_stream_stride + 2 * pin, *pr = io_in_ring + strm * io.in_ring_stream_stride + 2 * pin;
@@ -228,31 +175,18 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   // ---------------------------------------------------------------- FFT-FIR (as fused_kernel)
   if constexpr (FWD8) {
     double2 g[16];
-    if constexpr ((RSMP_EXP_SKIP & 4) != 0) {
+    fft8_regs_pre<LOG2P, -1>(u8, tid, wf, lds, [&](int p) {
+      if (p == 1) { // two passes (two LDS round trips) ahead of the multiplication
 #pragma unroll
-      for (int s = 0; s < 16; ++s) g[s] = (RSMP_EXP_SKIP & 128) ? make_double2(1e-3 * s, 1e-4 * tid) : load_g(Gp + tid + s * T);
-      if constexpr (PRETW) {
-#pragma unroll
-        for (int i = 0; i < fft8_tw_regs(LOG2P); ++i) u8[i & 7].x += wf[i].x * 1e-30; // keep the loads alive
+        for (int s = 0; s < 16; ++s) g[s] = load_g(Gp + (unsigned)(tid + s * T));
       }
-    } else if constexpr (PRETW) {
-      fft8_regs_pre<LOG2P, -1>(u8, tid, wf, lds, [&](int p) {
-        if (p == 1) { // two passes (two LDS round trips) ahead of the multiplication
-#pragma unroll
-          for (int s = 0; s < 16; ++s) g[s] = (RSMP_EXP_SKIP & 128) ? make_double2(1e-3 * s, 1e-4 * tid) : load_g(Gp + (unsigned)(tid + (RSMP_EXP_TAB & 2 ? 0 : s * T)));
-        }
-      });
-    } else { // G in flight during the whole forward transform
-#pragma unroll
-      for (int s = 0; s < 16; ++s) g[s] = load_g(Gp + tid + (RSMP_EXP_TAB & 2 ? 0 : s * T));
-      fft8_regs<LOG2P, -1, RSMP_TWGEN != 0>(u8, tid, a.d.tw_fwd8, lds);
-    }
+    });
     RSMP_STAMP(1)
 #pragma unroll
     for (int s = 0; s < 16; ++s) v[s] = cmul(u8[s & 7], c64{g[s].x, g[s].y});
     __syncthreads(); // the inverse transform's exchange reuses the LDS the forward one just read
   } else {
-  fft_regs<LOG2P, -1, LOG2P == LOG2N ? 2 : 0, RSMP_PFW, RSMP_TWGEN != 0>(v, tid, fwd_active, a.d.tw_fwd, lds);
+  fft_regs<LOG2P, -1, LOG2P == LOG2N ? 2 : 0, kPfFwd>(v, tid, fwd_active, a.d.tw_fwd, lds);
   RSMP_STAMP(1)
   if constexpr (LOG2P < LOG2N) {
     double2 g[16]; // issued before the exchange so the L2 latency overlaps it
@@ -289,7 +223,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       const double2 g = load_g(Gp + tid + s * T);
       v[s] = cmul(xs[s], c64{g.x, g.y});
     }
-    fft_regs<LOG2N, +1, 2, RSMP_PFI, RSMP_TWGEN != 0>(v, tid, true, a.d.tw_inv, lds);
+    fft_regs<LOG2N, +1, 2, kPfInv>(v, tid, true, a.d.tw_inv, lds);
     double2 g1[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) g1[s] = load_g(Gp + N + tid + s * T);
@@ -299,7 +233,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       v[s] = cmul(xs[s], c64{g1[s].x, g1[s].y});
     }
     __syncthreads(); // the second inverse transform's exchange reuses the LDS the first one just read
-    fft_regs<LOG2N, +1, 2, RSMP_PFI, RSMP_TWGEN != 0>(v, tid, true, a.d.tw_inv, lds);
+    fft_regs<LOG2N, +1, 2, kPfInv>(v, tid, true, a.d.tw_inv, lds);
   } else {
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -309,7 +243,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   }
   }
   RSMP_STAMP(2)
-  if constexpr (!(RSMP_EXP_SKIP & 2) && !SPLIT) fft_regs<LOG2N, +1, 2, RSMP_PFI, RSMP_TWGEN != 0>(v, tid, true, a.d.tw_inv, lds);
+  if constexpr (!SPLIT) fft_regs<LOG2N, +1, 2, kPfInv>(v, tid, true, a.d.tw_inv, lds);
   RSMP_STAMP(3)
 
   // ---------------------------------------------------------------- stage-1 samples -> LDS (round A) and seam ring
@@ -359,11 +293,9 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     for (int s = 0; s <= kSA; ++s) {
       const int n = tid + s * T;
       const bool whole = (s + 1) * T <= V;                 // every sample of this slot is valid
-      if (!(RSMP_EXP_SKIP & 64)) {
-        if (s < kSA ? (whole || n < V) : (tid < kPad && n < V)) smp[n] = make_double2(v[s].x, v[s].y);
-      }
+      if (s < kSA ? (whole || n < V) : (tid < kPad && n < V)) smp[n] = make_double2(v[s].x, v[s].y);
     }
-    if (tid < nm1 && !(RSMP_EXP_SKIP & 64)) {
+    if (tid < nm1) {
       seamA[tid] = v[0].x;
       seamB[tid] = v[0].y;
     }
@@ -385,7 +317,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   // the block's last n-1 samples -> seam ring, read back from whichever LDS image holds them (element 0 of `img` = sample n0)
   const int tail0 = V - nm1;
   auto store_tail = [&](const double2 *img, int n0) {
-    if (tid < nm1 && !(RSMP_EXP_SKIP & 64)) {
+    if (tid < nm1) {
       const int slot = (int)(B & a.seam_mask);
       const double2 t = img[tail0 + tid - n0];
       a.seam[((long long)(slot * (a.d.C + 1) + ca) * 2 + 1) * 32 + tid] = t.x;
@@ -446,11 +378,10 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     const int lane_li = walk_lane_li(fb, kb, hi, jq, step); // window start = lane_li + q(group, block) + pc * step
     const int lane_ib = walk_lane_ib(fb, kb, jq, rloc, pl); // output index relative to i_lo = lane_ib + 16 g + pc * pl
     const int cnt = walk_round_cnt(fb, fw, ke, pl);
-#if RSMP_BUFSTORE
     // raw buffer over this round's outputs [0, cnt) of the block: frame ib at byte ib * frame_bytes, 8 (16) bytes of it are ours
+    // (the range check is done by the descriptor: no per-tile compare / branch)
     const __amdgpu_buffer_rsrc_t orsrc =
         __builtin_amdgcn_make_buffer_rsrc(obytes, 0, (!OUT64 && !OGEN && cnt > 0) ? (cnt - 1) * frame_bytes + 2 * (int)sizeof(E) : 0, 0x00020000);
-#endif
     // store offset of a tile = (this lane's part, once per round) + (the tile's part, scalar): one vector add per tile.  Only the
     // last residue group can hold residues >= polyL (polyL not a multiple of 16): its lanes get the dropped offset there.
     const int lane_off0 = __mul24(lane_ib, frame_bytes); // |lane_ib| < 2^23
@@ -467,7 +398,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     int qci = 0, qni = 0;
     auto load_tile = [&](int gg, double (&c_)[KS], double &qd_, int &qi_) {
       constexpr int KSP = (KS + 1) / 2;
-      const double2 *cp = cfm_lane + (RSMP_EXP_TAB & 1 ? 0 : gg) * (KSP * 64); // uniform offset; two k-steps per 16-byte load
+      const double2 *cp = cfm_lane + gg * (KSP * 64); // uniform offset; two k-steps per 16-byte load
 #pragma unroll
       for (int s2 = 0; s2 < KSP; ++s2) {
         const double2 d = cp[s2 * 64];
@@ -483,11 +414,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
 
     double2 x0[KS], x1[KS];
     auto fill = [&](double2 (&x)[KS], int q, int pstep) {
-#if RSMP_EXP_LINEAR // timing experiment only (WRONG results): lane-linear, conflict-free window addresses
-      const int li = li_lo + 32 + lane + ((pstep * 16 + (q & 63)) & 1023);
-#else
       const int li = max(li_lo, min(li_hi, q + pstep * step)); // (q = lane_li + the group's window start)
-#endif
       const double2 *xp = xs + li;
 #pragma unroll
       for (int s = 0; s < KS; ++s) x[s] = xp[4 * s];
@@ -521,22 +448,15 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
         }
         pnext = p0;
       }
-      if constexpr (!(RSMP_EXP_SKIP & 16)) fill(xn, qc, left > 1 ? pnext : pc); // after the last tile: a harmless re-read
+      fill(xn, qc, left > 1 ? pnext : pc); // after the last tile: a harmless re-read
       double accA = 0.0, accB = 0.0;
 #pragma unroll
-      for (int s = 0; s < (RSMP_EXP_HALFMFMA ? 3 : KS); ++s) { // RSMP_EXP_HALFMFMA: timing experiment only (WRONG results)
-        if constexpr ((RSMP_EXP_SKIP & 32) != 0) { // no MFMAs: one add per operand keeps the loads alive
-          accA += cc[s] + ((RSMP_EXP_SKIP & 16) ? x0[s].x : xc[s].x);
-          accB += (RSMP_EXP_SKIP & 16) ? x0[s].y : xc[s].y;
-        } else {
-          accA = __builtin_amdgcn_mfma_f64_4x4x4f64(cc[s], (RSMP_EXP_SKIP & 16) ? x0[s].x : xc[s].x, accA, 0, 0, 0);
-          accB = __builtin_amdgcn_mfma_f64_4x4x4f64(cc[s], (RSMP_EXP_SKIP & 16) ? x0[s].y : xc[s].y, accB, 0, 0, 0);
-        }
+      for (int s = 0; s < KS; ++s) {
+        accA = __builtin_amdgcn_mfma_f64_4x4x4f64(cc[s], xc[s].x, accA, 0, 0, 0);
+        accB = __builtin_amdgcn_mfma_f64_4x4x4f64(cc[s], xc[s].y, accB, 0, 0, 0);
       }
-#if RSMP_EXP_HALFMFMA
-#pragma unroll
-      for (int s = 3; s < KS; ++s) { accA += xc[s].x * 1e-30; accB += cc[s] * 1e-30 + xc[s].y * 1e-30; } // keep the loads alive
-#endif
+      (void)x0; // (names `x0` so that it stays among this lambda's captures, behind `cc`: without it the instances with an odd KS
+                // get another register assignment)
       const int ib = lane_ib + 16 * g + pc * pl;
       if constexpr (OGEN) {
         if ((unsigned)ib < (unsigned)cnt && 16 * g + rloc < pl) {
@@ -557,9 +477,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
         const rsmp_v2u db = {(unsigned)__double2loint(accB), (unsigned)__double2hiint(accB)};
         __builtin_amdgcn_raw_buffer_store_b64(da, orsrcA, (int)off, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b64(db, orsrcB, (int)off, 0, 0);
-      } else
-#if RSMP_BUFSTORE
-      {
+      } else {
         // one unconditional buffer store per tile: outputs in front of the block (ib < 0 wraps to a huge offset) and behind
         // the round's last one fail the descriptor's range check and are dropped by the hardware; only the residue test of
         // the last (partial) group needs a select
@@ -578,17 +496,10 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
           const rsmp_v2u d = {(unsigned)pcm_out32(accA), (unsigned)pcm_out32(accB)};
           __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
         } else {
-        const rsmp_v2u d = {__float_as_uint((float)accA), __float_as_uint((float)accB)};
-        if constexpr ((RSMP_EXP_SKIP & 8) != 0) { // no stores: only a result nobody produces would be written
-          if (accA == 1.2345e300) __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
-        } else
-        __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
+          const rsmp_v2u d = {__float_as_uint((float)accA), __float_as_uint((float)accB)};
+          __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (int)off, 0, 0);
         }
       }
-#else
-      if (ib >= 0 && ib < cnt && 16 * g + rloc < pl)
-        *reinterpret_cast<E2 *>(obytes + (unsigned)(ib * frame_bytes)) = E2{Fr::out(accA), Fr::out(accB)};
-#endif
       if (wrap != 0 && left > 1) { // uniform: the group switches
 #pragma unroll
         for (int s = 0; s < KS; ++s) asm volatile("v_mov_b64 %0, %1" : "=v"(cc[s]) : "v"(cn[s]));
@@ -613,9 +524,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     }
   };
 
-  const bool run = fb.cnt > 0 && !(RSMP_EXP_SKIP & 1);
-  if (RSMP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-  if (RSMP_PRIO == 2) __builtin_amdgcn_s_setprio(3);
+  const bool run = fb.cnt > 0;
   // round A: periods whose windows end inside the samples written above
   if constexpr (SPLIT && TWO) {
     if (run) poly_round(0, fw.ka, smp, -kPad, min(V, kSplitRaEnd) + kPad - 4 * KS);
@@ -649,7 +558,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
 #pragma unroll
     for (int s = kSB0; s < 16; ++s) {
       const int n = tid + s * T;
-      if (n < V && !(RSMP_EXP_SKIP & 64)) l2[n - kSB0 * T] = make_double2(v[s].x, v[s].y);
+      if (n < V) l2[n - kSB0 * T] = make_double2(v[s].x, v[s].y);
     }
     if (tid < kPad && V > kSB0 * T) l2[V - kSB0 * T + tid] = make_double2(0.0, 0.0);
   }

@@ -173,15 +173,8 @@ struct FusedBlock {
 // Matrix-pipe variant of the fused kernel (N = 4096, 256 threads): the block's samples sit in LDS in two rounds,
 // round A = register slots [0, kFusedSA) of the inverse FFT (samples [0, 256*kFusedSA) plus a 32-sample margin),
 // round B = slots [kFusedSB0, 16); the two overlap by (kFusedSA - kFusedSB0) * 256 + 32 samples, which every period's
-// windows (all residues) must fit into one way or the other.  RSMP_WG4 sizes them for four workgroups per CU instead of three.
-#ifndef RSMP_WG4
-#define RSMP_WG4 0
-#endif
-// RSMP_WG2 (experiment): two workgroups per CU with 256 VGPRs each, the whole block (V <= 3584) in the first image
-#ifndef RSMP_WG2
-#define RSMP_WG2 0
-#endif
-constexpr int kFusedSA = RSMP_WG2 ? 14 : RSMP_WG4 ? 9 : 12, kFusedSB0 = kFusedSA - 2, kFusedWaves = RSMP_WG2 ? 2 : RSMP_WG4 ? 4 : 3;
+// windows (all residues) must fit into one way or the other.  Sized for three workgroups per CU.
+constexpr int kFusedSA = 12, kFusedSB0 = 10, kFusedWaves = 3;
 
 // The lean kernels' tile walk (fused_fast.hip: poly_round).  A tile is one 16-residue group x 4 consecutive periods.  Group g
 // owns periods [p0, pend) of the block (counted from kk_lo): p0 = 1 for the groups in front of g_lo, pend = K - 1 for the
@@ -363,7 +356,7 @@ struct FusedArgs {
   int kper;              // periods per chunk
   const double *cfm;     // matrix-pipe variant: A operands [16-residue group][k-step][lane]; null = vector variant
   int NGRP, KS;          // 16-residue groups, k-steps (4 taps each) of a 4-residue block's common window
-  int dbg;               // profiling ablations (RSMP_DBG env); 0 in production
+  int reserved = 0;      // unused: holds the argument layout (the next change to FusedArgs may drop it)
   unsigned long long *stamps; // RSMP_STAMPS: per-phase cycle sums [8] (null in production)
   const FusedBlock *blk; // [nblocks] in HBM, written by fused_prep_kernel ahead of the launch
   const int *qtab;       // matrix-pipe variant: window start (at0 + rb*step)/polyL of every 4-residue block rb = 4*i, [NGRP*4]

@@ -241,21 +241,29 @@ def test_planner_agrees_with_oracle_on_large_upsampling(fi, fo):
 
 
 def test_experiment_switches_cannot_reach_the_product_build():
-    """Wrong-result timing switches (RSMP_EXP_*, RSMP_DFTX_SKIP) exist only under -DRSMP_EXPERIMENTS: csrc/knobs.hpp refuses a
-    build that sets one without it, and the product Makefile never sets either."""
+    """The wrong-result timing switches are gone from the sources, not merely guarded: no file the library or its tools are
+    built from names one (comments included), the Makefile sets none, and defining one changes nothing for knobs.hpp."""
+    import glob
     import subprocess
     csrc = os.path.join(ROOT, "foo_dsp_resampler_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "-DRSMP_EXPERIMENTS" not in "\n".join(ln for ln in mk.splitlines() if not ln.lstrip().startswith("#"))
     assert "RSMP_EXP_" not in "\n".join(ln for ln in mk.splitlines() if not ln.lstrip().startswith("#"))
-    src = '#include "knobs.hpp"\nint main() { return RSMP_EXP_TAB + RSMP_EXP_SKIP; }\n'
+    names = ("RSMP_EXP", "RSMP_DBG", "RSMP_DFTX_SKIP", "RSMP_VCONST", "RSMP_EXPERIMENTS")
+    files = [p for p in glob.glob(os.path.join(csrc, "*")) if p.endswith((".cpp", ".hip", ".hpp")) or os.path.basename(p) == "Makefile"]
+    files += [p for p in glob.glob(os.path.join(ROOT, "tools", "**", "*"), recursive=True) if os.path.isfile(p) and not p.endswith(".md")]
+    assert len(files) > 20
+    hits = []
+    for path in files:
+        text = open(path, errors="replace").read()
+        hits += ["%s: %s" % (os.path.relpath(path, ROOT), nm) for nm in names if nm in text]
+    assert not hits, hits
+    src = '#include "knobs.hpp"\nint main() { return int(sizeof(rsmp::Knobs)) == 0; }\n'
     def compiles(flags):
         return subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, "-x", "c++", "-"] + flags, input=src, text=True,
                               capture_output=True).returncode == 0
-    assert compiles([])                                              # product flags: every switch is the constant 0
-    assert not compiles(["-DRSMP_EXP_TAB=1"])                        # refused ...
-    assert not compiles(["-DRSMP_EXP_SKIP=4"])
-    assert compiles(["-DRSMP_EXPERIMENTS", "-DRSMP_EXP_TAB=1"])      # ... unless the build says it is an experiment
+    assert compiles([])
+    assert compiles(["-DRSMP_EXP_TAB=1"])                            # the name means nothing to the library any more
 
 
 def test_environment_is_read_once():
