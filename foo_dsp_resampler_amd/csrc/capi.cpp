@@ -3,6 +3,7 @@
 #include "../../include/ratelib_amd.h"
 
 #include "engine.hpp"
+#include "finish.hpp"
 #include "lpc.hpp"
 
 #include <algorithm>
@@ -404,6 +405,80 @@ int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data
   const hipError_t e = rsmp::launch_lpc_extrapolate(static_cast<hipStream_t>(hip_stream), d_data, stream_stride, nstreams, data_len,
                                                     nch, lpc_order, extra_bkwd, extra_fwd);
   return e == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+namespace {
+
+// RRX_finish_device / RRX_debug_finish_host: everything that can be refused from the arguments alone; fills `a` when it is RR_OK
+int finish_args(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams,
+                size_t frames, int nch, const double *gain, int dither, unsigned long long seed, unsigned long long first_frame,
+                double *peak, unsigned long long *clipped, rsmp::FinishArgs &a)
+{
+  if (!src || nstreams < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (dst && dst_format != RRX_FMT_S16 && dst_format != RRX_FMT_S24_3 && dst_format != RRX_FMT_S32) return RR_INVPARAM;
+  if (nstreams > 1 && (src_stride < frames || (dst && dst_stride < frames))) return RR_INVPARAM;
+  if (!dst && !peak && !clipped) return RR_INVPARAM;
+  if (first_frame + frames < first_frame) return RR_INVPARAM;               // the frame counter of the dither would wrap
+  // No buffer has 2^60 samples: with that, frames * nch, stride * nch and the row offsets stream * stride * nch below and in
+  // finish.hip (times up to 8 bytes a sample) cannot wrap, and a workgroup's 32-bit clip count cannot either (launch_typed).
+  const size_t most = (~size_t(0) >> 4) / size_t(nch);
+  if (frames > most) return RR_INVPARAM;
+  if (nstreams > 1 && (src_stride > most / size_t(nstreams) || (dst && dst_stride > most / size_t(nstreams)))) return RR_INVPARAM;
+  a.src = src;
+  a.dst = dst;
+  a.gain = gain;
+  a.peak = peak;
+  a.clipped = clipped;
+  a.src_stride = nstreams > 1 ? (unsigned long long)src_stride * nch : 0;
+  a.dst_stride = nstreams > 1 ? (unsigned long long)dst_stride * nch : 0;
+  a.n = (unsigned long long)frames * nch;
+  a.seed = seed;
+  a.first_frame = first_frame;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  a.bits = !dst ? 31 : dst_format == RRX_FMT_S16 ? 15 : dst_format == RRX_FMT_S24_3 ? 23 : 31; // measure only: the S32 grid
+  a.dither = dither != 0;
+  return RR_OK;
+}
+
+} // namespace
+
+// The output stage on device-resident frames (finish.hip).  Refusals first, as in RRX_lpc_extrapolate_device.
+int RRX_finish_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int dst_format, void *d_dst,
+                      size_t dst_stride, int nstreams, size_t frames, int nch, const double *d_gain, int dither, unsigned long long seed,
+                      unsigned long long first_frame, double *d_peak, unsigned long long *d_clipped)
+{
+  rsmp::FinishArgs a;
+  const int rc = finish_args(src_format, d_src, src_stride, dst_format, d_dst, dst_stride, nstreams, frames, nch, d_gain, dither, seed,
+                             first_frame, d_peak, d_clipped, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!frames) return RR_OK;
+  if (device >= 0) { // as RRX_open_batch_on
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return RR_EXTUNINIT;
+    if (device >= n) return RR_INVPARAM;
+  }
+  if (!rsmp::device_is_gfx950(device)) return RR_EXTUNINIT;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_finish(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_finish_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams,
+                          size_t frames, int nch, const double *gain, int dither, unsigned long long seed, unsigned long long first_frame,
+                          double *peak, unsigned long long *clipped)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::FinishArgs a;
+  const int rc = finish_args(src_format, src, src_stride, dst_format, dst, dst_stride, nstreams, frames, nch, gain, dither, seed,
+                             first_frame, peak, clipped, a);
+  if (rc != RR_OK) return rc;
+  if (frames) rsmp::finish_host(a);
+  return RR_OK;
 }
 
 // foo_dsp_rate.cpp:96-101 with samples_len of util.h:38-48

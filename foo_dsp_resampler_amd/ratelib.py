@@ -20,11 +20,13 @@ EXPECTED_SYMBOLS = [
     "RRX_push_samples", "RRX_pull_samples", "RRX_flow_samples", "RRX_push_device_samples", "RRX_pull_device_samples",
     "RRX_flow_device_samples",
     "RRX_lpc_extrapolate_device", "RRX_edge_geometry",
+    "RRX_finish_device", "RRX_debug_finish_host",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
 RRX_FMT_FLOAT, RRX_FMT_DOUBLE = 0, 1  # sample formats of a handle (ratelib_amd.h)
 RRX_FMT_S16, RRX_FMT_S32 = 16, 32      # interleaved signed integer PCM (24-bit audio left-justified in S32)
+RRX_FMT_S24_3 = 24                     # packed 3-byte PCM: a destination of finish_device only, never a handle format
 _FMT_DTYPE = {RRX_FMT_FLOAT: np.dtype(np.float32), RRX_FMT_DOUBLE: np.dtype(np.float64), RRX_FMT_S16: np.dtype(np.int16),
               RRX_FMT_S32: np.dtype(np.int32)}
 _DTYPE_FMT = {d: f for f, d in _FMT_DTYPE.items()}
@@ -157,6 +159,11 @@ def lib():
         if hasattr(L, "RRX_lpc_extrapolate_device"):  # (as above: an older tree's build has none)
             L.RRX_lpc_extrapolate_device.argtypes = [C.c_int, vp, vp, sz, C.c_int, sz, C.c_int, C.c_int, sz, sz]
             L.RRX_edge_geometry.argtypes = [sz, sz, P(sz), P(sz), P(sz), P(sz)]
+        if hasattr(L, "RRX_finish_device"):  # (as above)
+            u64 = C.c_ulonglong
+            host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_int, u64, u64, vp, vp]
+            L.RRX_finish_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_finish_host.argtypes = host
         _lib = L
     return _lib
 
@@ -237,6 +244,67 @@ def lpc_extrapolate_device(t, first, data_len, extra_bkwd, extra_fwd, order=32, 
     _check(lib().RRX_lpc_extrapolate_device(-1 if index is None else int(index), C.c_void_p(ptr),
                                             C.c_void_p(t.data_ptr() + first * nch * 4), frames, nstreams, data_len, nch, int(order),
                                             extra_bkwd, extra_fwd), "RRX_lpc_extrapolate_device")
+
+
+def finish_device(x, dst_format, gain=None, dither=False, seed=0, first_frame=0, out=None, peak=None, clipped=None, stream=None):
+    """The output stage on the device (RRX_finish_device): gain, TPDF dither, quantisation to integer PCM, peak and clip count.
+
+    `x` is a contiguous float32 or float64 device tensor [frames, nch] or [nstreams, frames, nch].  `dst_format` is RRX_FMT_S16
+    (int16 out), RRX_FMT_S32 (int32), RRX_FMT_S24_3 (uint8 [..., frames, nch * 3]: packed little-endian 24 bit) or None: measure
+    only, nothing is written and the statistics are those of the S32 quantiser.  `gain`: None, a float, or a float64 device
+    tensor [nstreams].  `seed` / `first_frame` (64-bit unsigned) fix the dither: a track finished in chunks with first_frame =
+    the frames done so far gets the bits of one call.  `out`, `peak` (float64 [nstreams, nch]) and `clipped` (int64
+    [nstreams, nch]) are allocated (the statistics zeroed) when not passed; statistics that are passed are accumulated into.
+    Returns (out, peak, clipped).  `stream` as in lpc_extrapolate_device: the call only enqueues."""
+    import torch
+    shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    dt = str(x.dtype)
+    if not (dt.endswith("float32") or dt.endswith("float64")):
+        raise TypeError("%s buffer: the output stage reads float32 or float64 frames" % (x.dtype,))
+    if not x.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    if dst_format not in (None, RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32 or None)" % (dst_format,))
+    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
+    seed, first_frame = int(seed), int(first_frame)
+    if not (0 <= seed < 1 << 64 and 0 <= first_frame and first_frame + frames < 1 << 64):
+        raise ValueError("seed and first_frame + frames must fit 64 unsigned bits")
+    if not getattr(x, "is_cuda", False):
+        raise TypeError("the output stage works on device tensors: the frames must be in HBM")
+    dev = x.device
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((nstreams,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (nstreams,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (nstreams, dev))
+    if dst_format is None:
+        if out is not None:
+            raise ValueError("dst_format=None measures only: there is nothing to write into `out`")
+    else:
+        odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
+        oshape = shape[:-1] + (last,)
+        if out is None:
+            out = torch.empty(oshape, dtype=odt, device=dev)
+        elif out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
+            raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
+    stats = []
+    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
+        if t is None:
+            t = torch.zeros((nstreams, nch), dtype=sdt, device=dev)
+        elif t.dtype != sdt or tuple(t.shape) != (nstreams, nch) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, nstreams, nch, dev))
+        stats.append(t)
+    peak, clipped = stats
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_finish_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+                                   RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
+                                   dst_format or 0, C.c_void_p(out.data_ptr()) if out is not None else None, frames, nstreams, frames, nch,
+                                   C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed, first_frame,
+                                   C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_finish_device")
+    return out, peak, clipped
 
 
 def _ensure_init():
@@ -582,3 +650,12 @@ class Resampler:
                 self.use_own_stream()
             else:
                 self.set_stream(prev)
+
+    def convert_track_to_pcm_device(self, x, dst_format, **finish_kw):
+        """convert_track_device followed by the output stage, finish_device(..., dst_format, **finish_kw), on torch's current
+        stream of x's device: whole tracks in, integer PCM (and peak / clip count per stream and channel) out.  Returns
+        finish_device's (out, peak, clipped)."""
+        import torch
+        y = self.convert_track_device(x)
+        finish_kw.setdefault("stream", torch.cuda.current_stream(y.device))
+        return finish_device(y, dst_format, **finish_kw)

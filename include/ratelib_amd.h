@@ -131,7 +131,8 @@ int RRX_flow_device_double(RR_handle *h, const double *d_ibuf, size_t in_stride,
  * geometry as on a float handle of the same config (availability, the RRX_isamp_max clamp and drain totals are the float ones).
  *   in :  x = (double)s * 2^-15 (S16) or (double)s * 2^-31 (S32); both are exact in fp64.
  *   out:  q = rint(y * 2^bits), bits = 15 or 31, round half to even; saturated IN FP64 to [-2^bits, 2^bits - 1]; then narrowed
- *         to the integer type.  No wrap-around, no dither, no clipped-sample counter.
+ *         to the integer type.  No wrap-around, no dither, no clipped-sample counter (RRX_finish_device, below, has both
+ *         for the frames of a float or double handle).
  * So an integer handle's output equals, bit for bit, the output of an RRX_FMT_DOUBLE handle fed s * 2^-bits, quantised by the
  * rule above.  24-bit audio travels left-justified in RRX_FMT_S32 (sample << 8).
  * Any format value other than these four makes RRX_open_batch_fmt return RR_INVPARAM before any device is touched. */
@@ -183,6 +184,54 @@ int RRX_flow_device_samples(RR_handle *h, int format, const void *d_ibuf, size_t
  * Float32 frames only (the reference arithmetic is float32): double and integer buffers have no such call. */
 int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data, size_t stream_stride, int nstreams,
                                size_t data_len, int nch, int lpc_order, size_t extra_bkwd, size_t extra_fwd);
+
+/* Output stage for device-resident tracks: the counterpart of RRX_lpc_extrapolate_device at the other end.  One pass over the
+ * float32 or float64 frames a handle produced ([stream][frame][channel], strides in frames between streams, ignored when
+ * nstreams == 1) applies a per-stream gain, adds deterministic TPDF dither, quantises to integer PCM and takes the peak and the
+ * number of clipped samples per (stream, channel).  It needs no handle, and no existing handle, format or kernel changes: an
+ * integer handle keeps quantising by its own rule above, which is this one without gain and dither.
+ *
+ * The arithmetic is part of this ABI.  For sample x of stream s, channel ch, frame i of the call (all fp64, every operation
+ * rounded on its own; 64-bit integers wrap):
+ *   c = s * nch + ch;   g = (double)x * d_gain[s]   (d_gain NULL: g = x);   a = fabs(g);   t = g * 2^bits, bits = 15 / 23 / 31
+ *   if dither:  z = seed + (first_frame + i) * 0x9E3779B97F4A7C15 + c * 0xBF58476D1CE4E5B9
+ *               z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;   z = z ^ (z >> 31)
+ *               t = t + ((double)(z >> 32) - (double)(z & 0xffffffff)) * 2^-32        triangular on (-1, 1) LSB
+ *   q = rint(t), round half to even;   clip = !(-2^bits <= q <= 2^bits - 1), true for a NaN;   q saturates to that range in
+ *   fp64 (a NaN to -2^bits) and is narrowed.
+ * With dither = 0 and d_gain = NULL the S16 / S32 result is the integer handles' rule bit for bit.  The noise of a sample
+ * depends on (seed, stream, channel, first_frame + i) alone: a track finished in chunks, with first_frame = the frames done so
+ * far, gets the bits of one call.
+ *   src_format: RRX_FMT_FLOAT or RRX_FMT_DOUBLE.
+ *   dst_format: RRX_FMT_S16, RRX_FMT_S32, or RRX_FMT_S24_3: three bytes a sample, little endian, two's complement (WAV's packed
+ *   24 bit).  RRX_FMT_S24_3 is a buffer format of this call only, never a handle format: RRX_open_batch_fmt refuses it.
+ *   d_dst NULL: measure only -- nothing is written, dst_format and dst_stride are ignored, and the statistics are those of the
+ *   RRX_FMT_S32 quantiser (bits = 31).
+ *   d_peak (double) / d_clipped: [nstreams * nch] each, on the device, either may be NULL.  The call ACCUMULATES into what they
+ *   hold -- peak = max(peak, every a), by an unsigned 64-bit maximum on the bit pattern (so a NaN sample leaves a NaN);
+ *   clipped += the count of clip -- so the caller zeroes them, and chunked calls over one track sum up.  Both are independent of
+ *   the order of the samples, hence deterministic.
+ *   Pointers need only the alignment of one sample (1 byte for RRX_FMT_S24_3); no byte outside the frames * nch samples of each
+ *   destination row is touched.
+ *   device, hip_stream: as in RRX_lpc_extrapolate_device, with the same stream-ordering contract; the call only enqueues (no
+ *   allocation, no host synchronisation) and restores the caller's device on return.
+ * Returns RR_INVPARAM, before any device is touched, for a NULL source, nstreams < 1, nch < 1, an unknown source format, an
+ * unknown destination format (d_dst not NULL), nstreams > 1 with a stride below frames, d_dst, d_peak and d_clipped all NULL,
+ * first_frame + frames overflowing 64 bits, a size no buffer has -- frames * nch, or with nstreams > 1 nstreams * src_stride * nch
+ * (nstreams * dst_stride * nch when d_dst is not NULL), of 2^60 samples or more, so that no offset the call computes can wrap --
+ * or device < -1; RR_EXTUNINIT before init_ratelib; RR_INVPARAM for a device index the process does not have; RR_INTERNAL for
+ * a failed launch.  frames == 0 is RR_OK and does nothing.  Noise shaping, integer or planar sources and float destinations are
+ * not offered. */
+#define RRX_FMT_S24_3 24   /* packed 3-byte signed 24-bit PCM: RRX_finish_device's destination only */
+int RRX_finish_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
+                      int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
+                      const double *d_gain, int dither, unsigned long long seed, unsigned long long first_frame,
+                      double *d_peak, unsigned long long *d_clipped);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: RRX_finish_device on HOST
+ * pointers, as one serial loop over the very per-sample function the kernel calls.  Same refusals, same results. */
+int RRX_debug_finish_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride,
+                          int nstreams, size_t frames, int nch, const double *gain, int dither, unsigned long long seed,
+                          unsigned long long first_frame, double *peak, unsigned long long *clipped);
 
 /* Host-only (no GPU needed): the plugin's edge geometry for a rate pair (dsp_rate::reinit, foo_dsp_rate.cpp:96-101).
  * *n_add / *n_drop = samples_len(in_rate, out_rate, 20, 8192) of util.h:38-48: frames to extrapolate at each end of the input
