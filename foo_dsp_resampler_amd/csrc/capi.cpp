@@ -358,11 +358,11 @@ int RRX_profile_report(RR_handle *h, char *buf, size_t cap)
 
 void RRX_debug_fail_alloc(int nth) { rsmp::Engine::fail_alloc_after(nth); }
 
-long long RRX_debug_tile_walk(const RRX_walk_geom *g, int k, long long *head, int *slots, size_t cap)
+// RRX_walk_geom -> the prep kernel's arguments for entries 0 .. k (false: refused)
+static bool walk_geom_args(const RRX_walk_geom *g, int k, rsmp::FusedPrepArgs &pa)
 {
-  if (!rsmp::knobs().test_hooks || !g || !head || (cap && !slots) || k < 0) return -1;
-  if (g->polyL < 1 || g->step < 1 || g->V < 1 || g->n < 1 || g->KS < 1 || g->nsub < 0 || (g->nsub > 0 && g->Vs < 1)) return -1;
-  rsmp::FusedPrepArgs pa;
+  if (!rsmp::knobs().test_hooks || !g || k < 0) return false;
+  if (g->polyL < 1 || g->step < 1 || g->V < 1 || g->n < 1 || g->KS < 1 || g->nsub < 0 || (g->nsub > 0 && g->Vs < 1)) return false;
   pa.b_offset = g->b_offset;
   pa.B0 = g->B0;
   pa.at0 = g->at0;
@@ -381,7 +381,23 @@ long long RRX_debug_tile_walk(const RRX_walk_geom *g, int k, long long *head, in
   pa.clip_hi = 0x7fffffffffffffffLL;
   pa.nsub = g->nsub;
   pa.Vs = g->Vs;
+  return true;
+}
+
+long long RRX_debug_tile_walk(const RRX_walk_geom *g, int k, long long *head, int *slots, size_t cap)
+{
+  rsmp::FusedPrepArgs pa;
+  if (!head || (cap && !slots) || !walk_geom_args(g, k, pa)) return -1;
   return (long long)rsmp::fused_walk_enumerate(pa, k, head, slots, cap);
+}
+
+int RRX_debug_walk_start(const RRX_walk_geom *g, int k, RRX_walk_start *out)
+{
+  rsmp::FusedPrepArgs pa;
+  if (!out || !walk_geom_args(g, k, pa)) return -1;
+  static_assert(sizeof(RRX_walk_start) == 56 * sizeof(int), "RRX_walk_start mirrors rsmp::WalkStart");
+  rsmp::fused_walk_start_host(pa, k, reinterpret_cast<int *>(out));
+  return 0;
 }
 
 // lpc/lpc.h:27 on device-resident frames.  Everything that can be refused from the arguments alone is refused before any

@@ -461,6 +461,7 @@ int Engine::init_fused_pair(int i, size_t &slab_cap)
   while (fu.blk_cap < 8 * split_nsub) fu.blk_cap *= 2; // (sub-blocked: the table counts sub-blocks; at least 6 whole blocks per launch)
   fu.slots = 2 * fu.blk_cap;
   ALLOC_TRY(&fu.blk_dev, size_t(2 * fu.blk_cap) * sizeof(FusedBlock)); // two halves: launch k uses half k & 1 (see advance)
+  ALLOC_TRY(&fu.wst_dev, size_t(2 * fu.blk_cap) * sizeof(WalkStart));  // the walk's start states, entry for entry: the same halves
   const size_t bytes = size_t(C_ + 1) * fu.slots * 2 * 32 * sizeof(double);
   ALLOC_TRY(&fu.seam, bytes);
   HIP_TRY(hipMemset(fu.seam, 0, bytes));
@@ -715,6 +716,7 @@ Engine::~Engine()
     if (f.cfm2) (void)hipFree(f.cfm2);
     if (f.Gs) (void)hipFree(f.Gs);
     if (f.blk_dev) (void)hipFree(f.blk_dev);
+    if (f.wst_dev) (void)hipFree(f.wst_dev);
   }
   for (BigDft &b : big_) {
     if (b.twN) (void)hipFree(b.twN);
@@ -1077,8 +1079,10 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   // into three launches lost the seam outputs of its first blocks: tests/test_gpu_round3.py::test_cfg0_bench_shape_*.)
   if (seam_launches_ >= 2) HIP_TRY(hipStreamWaitEvent(stream_, ev_seam_[seam_launches_ & 1], 0));
   FusedBlock *const blk_half = fu.blk_dev + size_t(seam_launches_ & 1) * fu.blk_cap;
-  { const int pp = prof_begin(false, "rsmp::fused_prep_kernel"); HIP_TRY(launch_fused_prep(pa, blk_half, stream_)); prof_end(pp); }
+  WalkStart *const wst_half = fu.wst_dev + size_t(seam_launches_ & 1) * fu.blk_cap;
+  { const int pp = prof_begin(false, "rsmp::fused_prep_kernel"); HIP_TRY(launch_fused_prep(pa, blk_half, stream_, wst_half)); prof_end(pp); }
   fa.blk = blk_half;
+  fa.wst = wst_half;
   // the fused launch emits exactly the outputs [wro, wro + count): windows ending before wr of fifo i
   const long long endnum = (b.wr[i] - sp.n + 1) * sp.L - fa.at0;
   if (wro - out_offset + count != (endnum <= 0 ? 0 : (endnum + step - 1) / step)) return kInternal;
@@ -1185,6 +1189,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     fr.d.B0 = fa.d.B0 + b0;
     fr.d.nblocks = b1 - b0;
     fr.blk = fa.blk + b0;
+    fr.wst = fa.wst + b0;
     const int pi = prof_begin(true);
     const char *kn = nullptr;
     if (fast) HIP_TRY(launch_fused_fast(pend_log2p, fr, io, stream_, &kn));

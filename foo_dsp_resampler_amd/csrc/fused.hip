@@ -612,15 +612,20 @@ __global__ __launch_bounds__(256) void seam_kernel(AnyView out, FusedArgs a)
   }
 }
 
-__global__ __launch_bounds__(256) void fused_prep_kernel(FusedPrepArgs p, FusedBlock *out)
+// one thread per table entry and polyphase round: both compute the entry, round 0's thread stores it, each stores its round of
+// the start-state record (no record: the second thread has nothing to do)
+__global__ __launch_bounds__(256) void fused_prep_kernel(FusedPrepArgs p, FusedBlock *out, WalkStart *wst)
 {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k < p.nblocks) out[k] = fused_block_info(p, k);
+  const int t = blockIdx.x * 256 + threadIdx.x, k = t >> 1, round = t & 1;
+  if (k >= p.nblocks || (round && !wst)) return;
+  const FusedBlock fb = fused_block_info(p, k);
+  if (!round) out[k] = fb;
+  if (wst) fused_walk_start_round(fb, (p.polyL + 15) >> 4, p.polyL, round, wst[k].r[round]);
 }
 
-hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st)
+hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st, WalkStart *wst)
 {
-  hipLaunchKernelGGL(fused_prep_kernel, dim3((p.nblocks + 255) / 256), dim3(256), 0, st, p, out);
+  hipLaunchKernelGGL(fused_prep_kernel, dim3((2 * p.nblocks + 255) / 256), dim3(256), 0, st, p, out, wst);
   return hipGetLastError();
 }
 

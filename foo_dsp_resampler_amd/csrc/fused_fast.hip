@@ -23,6 +23,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstdio>
+#include <cstring>
 #include <type_traits>
 
 namespace rsmp {
@@ -107,6 +108,34 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   }
   const int V = SPLIT ? sb.len : a.d.V;
   const bool fwd_active = tid < TF;
+  // The block's table entry and this wave's start states of both polyphase rounds (kernels.hpp, WalkStart): wave-uniform
+  // addresses in memory that no one writes while the kernel runs, so they are scalar loads (constant address space) and the
+  // values live in scalar registers.  TAB_AT_START (the x2 instances of 4096-point blocks, the headline among them): requested
+  // ahead of the input loads, whose latency covers them, and kept across the transforms.  The other instances have no scalar
+  // registers to spare there (their transforms run at 96 - 106 of them): they request the record behind the last transform,
+  // under the image writes.
+  // EARLY_TILES: each round's first two coefficient tiles are requested ahead of the barrier(s) in front of its image.  Not in
+  // the sub-blocked forms: at 252 - 256 vector registers the tiles would spill component 0.
+  constexpr bool TAB_AT_START = LOG2P == LOG2N - 1 && !SPLIT, EARLY_TILES = !SPLIT;
+  // round A's request: ahead of the image writes where the registers allow it (7 k-steps), else between them and the barrier
+  constexpr bool TILES_A_FIRST = TAB_AT_START && EARLY_TILES && KS <= 7;
+  typedef const int __attribute__((address_space(4))) *TabPtr;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  struct { long long i_lo; int cnt, irel_lo, base_li; } fb; // (FusedBlock's first five dwords)
+  struct RoundStart { int kb, cnt, b1, b2, p01, p02, pe1, pe2, n, g, pc, pend; }; // WalkStartRound without run 0, + this wave's entry
+  RoundStart rsA, rsB;
+  auto fetch_table = [&] {
+    const TabPtr tb = (TabPtr)(const void *)(a.blk + bl), ts = (TabPtr)(const void *)(a.wst + bl);
+    fb.i_lo = (long long)(((unsigned long long)(unsigned)tb[1] << 32) | (unsigned)tb[0]);
+    fb.cnt = tb[2], fb.irel_lo = tb[3], fb.base_li = tb[4];
+    auto round_start = [&](int r) {
+      const TabPtr q = ts + r * (int)(sizeof(WalkStartRound) / 4), w = q + 12 + 4 * wave;
+      return RoundStart{q[0], q[2], q[3], q[4], q[6], q[7], q[9], q[10], w[0], w[1], w[2], w[3]};
+    };
+    rsA = round_start(0);
+    rsB = round_start(1);
+  };
+  if constexpr (TAB_AT_START) fetch_table();
   const double2 *__restrict__ Gp = a.d.G;
   double2 *smp = reinterpret_cast<double2 *>(lds) + kPad; // smp[n] = (channel A, channel B) sample n of the block
   const int nm1 = a.n - 1;
@@ -246,6 +275,45 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   if constexpr (!SPLIT) fft_regs<LOG2N, +1, 2, kPfInv>(v, tid, true, a.d.tw_inv, lds);
   RSMP_STAMP(3)
 
+  // Lane maps of v_mfma_f64_4x4x4 (tools/probe_mfma4.hip): A lane = 16k + 4b + i, B lane = 16k + 4b + j, D lane = 16i + 4b + j:
+  // as an A/B lane this lane is (k = hi, block bq, i or j = jq); its D element is (row hi, block bq, period jq).
+  const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
+  const int rloc = 4 * bq + hi; // this lane's output residue within a 16-residue group
+  const int ngrp = a.NGRP;
+  const double2 *const cfm_lane = a.cfm2 + lane;
+  const int *const qtab_lane = a.qtab + bq;
+
+  // Coefficient tiles: current group, next group (in flight).  The window start of a group comes with its tile (odd KS: spare
+  // half of the last 16-byte element) and stays a double until the group becomes current, so that nothing waits for the
+  // tile load at the point where it is issued.
+  // (Measured and NOT kept, round 3: two register sets used alternately group by group, all four (set, sample buffer)
+  // combinations spelled out so that no set is ever copied and no s_waitcnt vmcnt(0) sits behind the prefetch -- 168 VGPRs
+  // with 19 spilled across round A, 2.37 against 1.96 ms.  The kernel has no registers to spare at three workgroups per CU.)
+  double cc[KS], cn[KS];
+  double qcd = 0.0, qnd = 0.0;
+  int qci = 0, qni = 0;
+  auto load_tile = [&](int gg, double (&c_)[KS], double &qd_, int &qi_) {
+    constexpr int KSP = (KS + 1) / 2;
+    const double2 *cp = cfm_lane + gg * (KSP * 64); // uniform offset; two k-steps per 16-byte load
+#pragma unroll
+    for (int s2 = 0; s2 < KSP; ++s2) {
+      const double2 d = cp[s2 * 64];
+      c_[2 * s2] = d.x;
+      if (2 * s2 + 1 < KS) c_[2 * s2 + 1] = d.y;
+      else qd_ = d.y;
+    }
+    if (!(KS & 1)) qi_ = qtab_lane[gg * 4];
+  };
+  // EARLY_TILES: a round's first two tiles are requested AHEAD of the barrier in front of its LDS image: the group comes from the
+  // table, the registers are dead there, and only the first `fill` needs the image.  Unconditional (a wave without tiles has g = 0).
+  auto request_tiles = [&](const RoundStart &rs) {
+    load_tile(rs.g, cc, qcd, qci);
+    load_tile(min(rs.g + 1, ngrp - 1), cn, qnd, qni); // (clamped: see the group switch below)
+  };
+  if constexpr (!TAB_AT_START) fetch_table();
+  if constexpr (TILES_A_FIRST) request_tiles(rsA); // behind the inverse transform's last exchange, ahead of the image and its barrier
+
+
   // ---------------------------------------------------------------- stage-1 samples -> LDS (round A) and seam ring
   const int ca = 2 * pair, cb = ca + 1;
   {
@@ -305,6 +373,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     }
     }
   }
+  if constexpr (EARLY_TILES && !TILES_A_FIRST) request_tiles(rsA); // (the image writes cover the table's round trip)
   __syncthreads();
   if constexpr (SPLIT) { // the head goes to the seam ring from the image (its register slot depends on the sub-block's shift)
     if (tid < nm1) {
@@ -330,11 +399,6 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   RSMP_STAMP(4)
 
   // ---------------------------------------------------------------- polyphase FIR on v_mfma_f64_4x4x4, tile by tile
-  // Lane maps (tools/probe_mfma4.hip): A lane = 16k + 4b + i, B lane = 16k + 4b + j, D lane = 16i + 4b + j:
-  // as an A/B lane this lane is (k = hi, block bq, i or j = jq); its D element is (row hi, block bq, period jq).
-  const FusedBlock fb = a.blk[bl];
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
   const int pl = a.polyL, step = a.step;
   const int frame_bytes = io.nch * (int)sizeof(E);
   char *const obytes = (OUT64 || OGEN) ? nullptr
@@ -352,32 +416,21 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     orsrcA = __builtin_amdgcn_make_buffer_rsrc(ra, 0, (int)((io.out64_mask + 1) * 8), 0x00020000);
     orsrcB = __builtin_amdgcn_make_buffer_rsrc(ra + io.out64_chan_stride, 0, (int)((io.out64_mask + 1) * 8), 0x00020000);
   }
-  const int rloc = 4 * bq + hi; // this lane's output residue within a 16-residue group
-  const int ngrp = a.NGRP;
-  const double2 *const cfm_lane = a.cfm2 + lane;
-  const int *const qtab_lane = a.qtab + bq;
-
   // Every group walks its OWN periods (kernels.hpp, FusedWalk): group g starts at period kb + p0_g, p0_g = 1 when all its
   // residues lie in front of the block's first output, and has ncs_g column steps of 4 periods, one less than its neighbours
   // when it ends a period early.  `pc` counts periods from kb: p0_g, p0_g + 4, ... up to `pend` = p0_g + 4 ncs_g.
-  const FusedWalk fw = fused_walk(fb, ngrp);
-  auto poly_round = [&](int kb, int ke, const double2 *xs, int li_lo, int li_hi) {
-    if (ke <= kb) return;
-    const WalkRound wr = walk_round(fw, fb.K, kb, ke, ngrp);
-    const int t0 = (wr.nt * wave) >> 2, t1 = (wr.nt * (wave + 1)) >> 2; // this wave's tiles, group-major
-    if (t0 >= t1) return;
-    // (readfirstlane: the walk's state is uniform and has to stay in scalar registers -- the loop below tests it with scalar
-    // instructions; it costs one move here and one per group switch, none per tile)
-    int g, pc;
-    walk_seek(wr, t0, g, pc);
-    g = __builtin_amdgcn_readfirstlane(g);
-    int p0 = __builtin_amdgcn_readfirstlane(walk_p0(fw, g)); // the current group's first period, then the next group's
-    pc = __builtin_amdgcn_readfirstlane(4 * pc + p0);
-    int pend = __builtin_amdgcn_readfirstlane(p0 + 4 * walk_ncs(fw, fb.K, kb, ke, g));
+  // The round's and the wave's start state is the table's (RoundStart, in scalar registers since the kernel began); what is
+  // left to do behind the barrier are the per-lane terms and the buffer descriptor.
+  auto poly_round = [&](const RoundStart &rs, const double2 *xs, int li_lo, int li_hi) {
+    if (rs.n == 0) return; // the round does not exist, or has no tile for this wave
+    if constexpr (!EARLY_TILES) request_tiles(rs);
+    const int kb = rs.kb;
+    int g = rs.g, pc = rs.pc, pend = rs.pend;
+    int p0 = pc & 3; // the current group's first period (pc = p0 + 4 column steps, p0 < 2), then the next group's
     // (a first round that stops short of K ends at period ke for the groups that start at 0 and at ke + 1 for the others)
-    const int lane_li = walk_lane_li(fb, kb, hi, jq, step); // window start = lane_li + q(group, block) + pc * step
-    const int lane_ib = walk_lane_ib(fb, kb, jq, rloc, pl); // output index relative to i_lo = lane_ib + 16 g + pc * pl
-    const int cnt = walk_round_cnt(fb, fw, ke, pl);
+    const int lane_li = walk_lane_li(fb.base_li, kb, hi, jq, step); // window start = lane_li + q(group, block) + pc * step
+    const int lane_ib = walk_lane_ib(fb.irel_lo, kb, jq, rloc, pl); // output index relative to i_lo = lane_ib + 16 g + pc * pl
+    const int cnt = rs.cnt;
     // raw buffer over this round's outputs [0, cnt) of the block: frame ib at byte ib * frame_bytes, 8 (16) bytes of it are ours
     // (the range check is done by the descriptor: no per-tile compare / branch)
     const __amdgpu_buffer_rsrc_t orsrc =
@@ -386,31 +439,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     // last residue group can hold residues >= polyL (polyL not a multiple of 16): its lanes get the dropped offset there.
     const int lane_off0 = __mul24(lane_ib, frame_bytes); // |lane_ib| < 2^23
     const bool lane_dead_last = 16 * (ngrp - 1) + rloc >= pl;
-
-    // Coefficient tiles: current group, next group (in flight).  The window start of a group comes with its tile (odd KS: spare
-    // half of the last 16-byte element) and stays a double until the group becomes current, so that nothing waits for the
-    // tile load at the point where it is issued.
-    // (Measured and NOT kept, round 3: two register sets used alternately group by group, all four (set, sample buffer)
-    // combinations spelled out so that no set is ever copied and no s_waitcnt vmcnt(0) sits behind the prefetch -- 168 VGPRs
-    // with 19 spilled across round A, 2.37 against 1.96 ms.  The kernel has no registers to spare at three workgroups per CU.)
-    double cc[KS], cn[KS];
-    double qcd = 0.0, qnd = 0.0;
-    int qci = 0, qni = 0;
-    auto load_tile = [&](int gg, double (&c_)[KS], double &qd_, int &qi_) {
-      constexpr int KSP = (KS + 1) / 2;
-      const double2 *cp = cfm_lane + gg * (KSP * 64); // uniform offset; two k-steps per 16-byte load
-#pragma unroll
-      for (int s2 = 0; s2 < KSP; ++s2) {
-        const double2 d = cp[s2 * 64];
-        c_[2 * s2] = d.x;
-        if (2 * s2 + 1 < KS) c_[2 * s2 + 1] = d.y;
-        else qd_ = d.y;
-      }
-      if (!(KS & 1)) qi_ = qtab_lane[gg * 4];
-    };
     auto qof = [&](double qd_, int qi_) { return (KS & 1) ? (int)qd_ : qi_; };
-    load_tile(g, cc, qcd, qci);
-    load_tile(min(g + 1, ngrp - 1), cn, qnd, qni); // (unconditional, clamped: see the group switch below)
 
     double2 x0[KS], x1[KS];
     auto fill = [&](double2 (&x)[KS], int q, int pstep) {
@@ -423,7 +452,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     int qc = qof(qcd, qci) + lane_li;
     fill(x0, qc, pc);
 
-    int left = t1 - t0;
+    int left = rs.n;
     // one tile: prefetch the next tile's samples into `xn`, run the two accumulation chains on `xc`, store
     auto tile = [&](const double2 (&xc)[KS], double2 (&xn)[KS]) {
       // (loop control in plain ints: uniform bools that live across blocks came back as v_cndmask / v_readfirstlane pairs)
@@ -442,10 +471,9 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
         qc += lane_li;
         // the next group's first period and column steps: they differ from this group's only where a run of groups ends
         // (WalkRound: twice per round at most, never in the uniform walk), so a group switch costs two scalar compares
-        if (gnext == wr.b1 || gnext == wr.b2) {
-          p0 = __builtin_amdgcn_readfirstlane(walk_p0(fw, gnext));
-          pend_next = __builtin_amdgcn_readfirstlane(p0 + 4 * walk_ncs(fw, fb.K, kb, ke, gnext));
-        }
+        // (walk_next_group, on the table's run values)
+        if (gnext == rs.b2) p0 = rs.p02, pend_next = rs.pe2;
+        else if (gnext == rs.b1) p0 = rs.p01, pend_next = rs.pe1;
         pnext = p0;
       }
       fill(xn, qc, left > 1 ? pnext : pc); // after the last tile: a harmless re-read
@@ -527,7 +555,8 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   const bool run = fb.cnt > 0;
   // round A: periods whose windows end inside the samples written above
   if constexpr (SPLIT && TWO) {
-    if (run) poly_round(0, fw.ka, smp, -kPad, min(V, kSplitRaEnd) + kPad - 4 * KS);
+    if (run) poly_round(rsA, smp, -kPad, min(V, kSplitRaEnd) + kPad - 4 * KS);
+    if constexpr (EARLY_TILES) request_tiles(rsB);
     __syncthreads();
     { // second image: samples [kSplitRbStart, V) from the slots kept in registers, element 0 = sample kSplitRbStart
       double2 *l2 = reinterpret_cast<double2 *>(lds);
@@ -543,13 +572,14 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     }
     __syncthreads();
     if (tail_in_b) store_tail(reinterpret_cast<const double2 *>(lds), kSplitRbStart);
-    if (run && fw.ka < fb.K) poly_round(fw.ka, fb.K, reinterpret_cast<const double2 *>(lds) - kSplitRbStart, kSplitRbStart, V + kPad - 4 * KS);
+    if (run) poly_round(rsB, reinterpret_cast<const double2 *>(lds) - kSplitRbStart, kSplitRbStart, V + kPad - 4 * KS);
     return;
   } else if constexpr (SPLIT) {
-    if (run) poly_round(0, fb.K, smp, -kPad, V + kPad - 4 * KS); // one round over the whole image
+    if (run) poly_round(rsA, smp, -kPad, V + kPad - 4 * KS); // one round over the whole image (the table's first round is [0, K))
     return;
   }
-  if (run) poly_round(0, fw.ka, smp, -kPad, min(V, kSA * T) + kPad - 4 * KS);
+  if (run) poly_round(rsA, smp, -kPad, min(V, kSA * T) + kPad - 4 * KS);
+  if constexpr (EARLY_TILES) request_tiles(rsB); // straight after this wave's last tile of round A, ahead of both barriers
   RSMP_STAMP(6)
   __syncthreads();
   // round B: the rest of the block's samples replace the image, element 0 = sample kSB0*T
@@ -564,7 +594,7 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   }
   __syncthreads();
   if (tail_in_b) store_tail(reinterpret_cast<const double2 *>(lds), kSB0 * T);
-  if (run && fw.ka < fb.K) poly_round(fw.ka, fb.K, reinterpret_cast<const double2 *>(lds) - kSB0 * T, kSB0 * T, V + kPad - 4 * KS);
+  if (run) poly_round(rsB, reinterpret_cast<const double2 *>(lds) - kSB0 * T, kSB0 * T, V + kPad - 4 * KS);
   RSMP_STAMP(5)
 #ifdef RSMP_STAMPS_BUILD
   if (stamping && tid == 0) atomicAdd(a.stamps + 7, 1ull);
@@ -682,6 +712,7 @@ bool fused_split_supported(int log2n, int L, int ksteps)
 hipError_t launch_fused_split(int omode, const FusedArgs &a, const FastIo &io, hipStream_t st, const char **kname)
 {
   // what the kernel's indexing assumes, checked where the launch is made
+  if (!a.blk || !a.wst) return hipErrorInvalidValue;
   if (a.d.two) { // whole 8192-point blocks: one "sub-block" per block, two rounds
     if (a.d.nsub != 1 || a.d.Vs != a.d.V || a.d.Pref != 4096 || a.d.V <= kSplitVsMax || a.d.V > 8192 || (a.d.V & 1)) return hipErrorInvalidValue;
   } else if (a.d.Vs > kSplitVsMax) return hipErrorInvalidValue;
@@ -714,9 +745,10 @@ hipError_t launch_fused_split(int omode, const FusedArgs &a, const FastIo &io, h
 }
 
 // poly_round's walk restated on the host, slot by slot, for the tile-walk tests (RRX_debug_tile_walk): the block's table
-// entry, the rounds, each wave's tile range and the group / column stepping come from the functions the kernel uses
-// (fused_block_info, fused_walk, walk_round, walk_seek, walk_ncs), and so do a lane's window start, its output index and the
-// round's output count (walk_lane_li, walk_lane_ib, walk_round_cnt); a slot is one lane of one tile.
+// entry and its start-state record come from the functions fused_prep_kernel uses (fused_block_info, fused_walk_start: each
+// round's output count, each wave's first tile and tile count, the runs' values), the group switch is the kernel's
+// (walk_next_group), and so are a lane's window start and output index (walk_lane_li, walk_lane_ib); a slot is one lane of
+// one tile.
 size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int *slots, size_t cap)
 {
   const FusedBlock fb = fused_block_info(p, k);
@@ -729,41 +761,43 @@ size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int 
   for (int i = 0; i < 13; ++i) head[i] = h[i];
   size_t n = 0;
   if (fb.cnt <= 0) return 0;
+  const WalkStart ws = fused_walk_start(fb, ngrp, pl); // what fused_prep_kernel puts beside the entry, and all the kernels start from
   for (int round = 0; round < 2; ++round) {
-    const int kb = round ? fw.ka : 0, ke = round ? fb.K : fw.ka;
-    if (ke <= kb) continue;
-    const WalkRound wr = walk_round(fw, fb.K, kb, ke, ngrp);
-    const int cnt = walk_round_cnt(fb, fw, ke, pl);
+    const WalkStartRound &r = ws.r[round];
+    const int kb = r.kb, cnt = r.cnt;
     for (int wave = 0; wave < 4; ++wave) {
-      const int t0 = (wr.nt * wave) >> 2, t1 = (wr.nt * (wave + 1)) >> 2;
-      if (t0 >= t1) continue;
-      int g, c;
-      walk_seek(wr, t0, g, c);
-      int pc = 4 * c + walk_p0(fw, g), pend = walk_p0(fw, g) + 4 * walk_ncs(fw, fb.K, kb, ke, g);
-      for (int left = t1 - t0; left > 0; --left) {
+      int g = r.w[wave].g, pc = r.w[wave].pc, pend = r.w[wave].pend, p0 = pc & 3;
+      for (int left = r.w[wave].n; left > 0; --left) {
         for (int lane = 0; lane < 64; ++lane) {
           const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3, rloc = 4 * bq + hi;
           const long long a0 = p.at0 + (long long)(16 * g + 4 * bq) * step; // qtab: window start of the 4-residue block
-          const int li = walk_lane_li(fb, kb, hi, jq, step) + int(a0 / pl) + pc * step;
-          const int ib = walk_lane_ib(fb, kb, jq, rloc, pl) + 16 * g + pc * pl;
+          const int li = walk_lane_li(fb.base_li, kb, hi, jq, step) + int(a0 / pl) + pc * step;
+          const int ib = walk_lane_ib(fb.irel_lo, kb, jq, rloc, pl) + 16 * g + pc * pl;
           if (n < cap) {
             int *o = slots + 7 * n;
-            o[0] = round, o[1] = g, o[2] = (pc - walk_p0(fw, g)) >> 2, o[3] = lane, o[4] = ib;
+            o[0] = round, o[1] = g, o[2] = (pc - p0) >> 2, o[3] = lane, o[4] = ib;
             o[5] = ib >= 0 && ib < cnt && 16 * g + rloc < pl;
             o[6] = li;
           }
           ++n;
         }
-        if (pc + 4 == pend) { // the group's last tile
+        if (pc + 4 == pend) { // the group's last tile: the kernel's group switch
           ++g;
-          pc = walk_p0(fw, g);
-          pend = pc + 4 * walk_ncs(fw, fb.K, kb, ke, g);
+          walk_next_group(r, g, p0, pend);
+          pc = p0;
         } else
           pc += 4;
       }
     }
   }
   return n;
+}
+
+void fused_walk_start_host(const FusedPrepArgs &p, int k, int *out56)
+{
+  static_assert(sizeof(WalkStart) == 56 * sizeof(int), "WalkStart as 56 ints");
+  const WalkStart ws = fused_walk_start(fused_block_info(p, k), (p.polyL + 15) >> 4, p.polyL);
+  memcpy(out56, &ws, sizeof ws);
 }
 
 bool fused_fast_supported(int log2n, int log2p, int ksteps)
@@ -780,6 +814,7 @@ bool fused_fast_supported(int log2n, int log2p, int ksteps)
 
 hipError_t launch_fused_fast(int log2p, const FusedArgs &a, const FastIo &io, hipStream_t st, const char **kname)
 {
+  if (!a.blk || !a.wst) return hipErrorInvalidValue; // the block table and its start-state records (fused_prep_kernel)
   RSMP_FAST_CASE(11, 7) RSMP_FAST_CASE(12, 7) RSMP_FAST_CASE(11, 8) RSMP_FAST_CASE(12, 8)
   return hipErrorInvalidValue;
 }

@@ -231,8 +231,8 @@ __host__ __device__ inline void walk_seek(const WalkRound &r, int t, int &g, int
 // A lane's part of a tile's addresses in the round that starts at period kb (lane = 16 hi + 4 bq + jq, rloc = 4 bq + hi): the
 // window of (group g, period offset pc) starts at walk_lane_li + q(g, bq) + pc * step, its output is number
 // walk_lane_ib + 16 g + pc * polyL of the block, kept when that lies in [0, walk_round_cnt).
-__host__ __device__ inline int walk_lane_li(const FusedBlock &fb, int kb, int hi, int jq, int step) { return fb.base_li + hi + (kb + jq) * step; }
-__host__ __device__ inline int walk_lane_ib(const FusedBlock &fb, int kb, int jq, int rloc, int pl) { return (kb + jq) * pl + rloc - fb.irel_lo; }
+__host__ __device__ inline int walk_lane_li(int base_li, int kb, int hi, int jq, int step) { return base_li + hi + (kb + jq) * step; }
+__host__ __device__ inline int walk_lane_ib(int irel_lo, int kb, int jq, int rloc, int pl) { return (kb + jq) * pl + rloc - irel_lo; }
 // outputs of the block that a round up to period ke may store: the round ends at period ke for the groups that start at 0
 // and at ke + 1 for the others (a group that starts at 0 has exact column steps there and never reaches period ke)
 __host__ __device__ inline int walk_round_cnt(const FusedBlock &fb, const FusedWalk &w, int ke, int pl)
@@ -338,6 +338,69 @@ __host__ __device__ inline FusedBlock fused_block_info(const FusedPrepArgs &p, i
   }
   return fb;
 }
+// Start states of the tile walk, one record per table entry beside its FusedBlock: everything poly_round used to derive from
+// the entry, the round and the wave index with ~250 dependent scalar instructions and one division -- behind a barrier, on
+// all four waves alike -- evaluated once per block by fused_prep_kernel.  The lean kernels fetch the record with their
+// input loads and keep only the per-lane terms (walk_lane_li / walk_lane_ib) on the path between a barrier and its first tile.
+// Round 0 = periods [0, ka), round 1 = [ka, K); a round the block does not have, and a wave without tiles, is all zero.
+struct WalkStartWave { int n, g, pc, pend; }; // tiles of the wave; its first group, and pc / pend as poly_round counts them
+struct WalkStartRound {
+  int kb, ke, cnt;      // periods of the round, outputs it may store (walk_round_cnt)
+  int b1, b2;           // run boundaries (WalkRound)
+  int p0[3], pend[3];   // first period and end (p0 + 4 column steps) of the groups of each run
+  int pad;
+  WalkStartWave w[4];
+};
+struct alignas(16) WalkStart { WalkStartRound r[2]; };
+static_assert(sizeof(WalkStartRound) == 112 && sizeof(WalkStart) == 224, "WalkStart: fixed layout (the kernels read it as dwords)");
+// one round of the record, written in place (fused_prep_kernel: one thread per entry and round, straight into the table)
+__host__ __device__ inline void fused_walk_start_round(const FusedBlock &fb, int ngrp, int pl, int round, WalkStartRound &r)
+{
+  const FusedWalk fw = fused_walk(fb, ngrp);
+  const int kb = round ? fw.ka : 0, ke = round ? fb.K : fw.ka;
+  const bool have = fb.cnt > 0 && ke > kb;
+  WalkRound wr = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (have) wr = walk_round(fw, fb.K, kb, ke, ngrp);
+  r.kb = have ? kb : 0;
+  r.ke = have ? ke : 0;
+  r.cnt = have ? walk_round_cnt(fb, fw, ke, pl) : 0;
+  r.b1 = wr.b1;
+  r.b2 = wr.b2;
+  r.pad = 0;
+  const int gs[3] = {0, wr.b1, wr.b2};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int p0 = walk_p0(fw, gs[i]);
+    r.p0[i] = have ? p0 : 0;
+    r.pend[i] = have ? p0 + 4 * walk_ncs(fw, fb.K, kb, ke, gs[i]) : 0;
+  }
+#pragma unroll
+  for (int wave = 0; wave < 4; ++wave) {
+    const int t0 = (wr.nt * wave) >> 2, t1 = (wr.nt * (wave + 1)) >> 2; // this wave's tiles, group-major
+    WalkStartWave e = {0, 0, 0, 0};
+    if (t0 < t1) {
+      int g, c;
+      walk_seek(wr, t0, g, c);
+      const int p0 = walk_p0(fw, g);
+      e = WalkStartWave{t1 - t0, g, 4 * c + p0, p0 + 4 * walk_ncs(fw, fb.K, kb, ke, g)};
+    }
+    r.w[wave] = e;
+  }
+}
+__host__ __device__ inline WalkStart fused_walk_start(const FusedBlock &fb, int ngrp, int pl)
+{
+  WalkStart s;
+  fused_walk_start_round(fb, ngrp, pl, 0, s.r[0]);
+  fused_walk_start_round(fb, ngrp, pl, 1, s.r[1]);
+  return s;
+}
+// the group switch of the walk: first period and end of group gnext when it opens a run, else the values it had (runs are
+// constant in both, WalkRound); b2 first, so that an empty middle run (b1 == b2) takes the last run's
+__host__ __device__ inline void walk_next_group(const WalkStartRound &r, int gnext, int &p0, int &pend)
+{
+  if (gnext == r.b2) p0 = r.p0[2], pend = r.pend[2];
+  else if (gnext == r.b1) p0 = r.p0[1], pend = r.pend[1];
+}
 constexpr int kFusedMaxBlocks = 1024; // capacity of the per-stage block table in HBM
 
 // dft -> vpoly0 fused launch (fused.hip)
@@ -356,11 +419,11 @@ struct FusedArgs {
   int kper;              // periods per chunk
   const double *cfm;     // matrix-pipe variant: A operands [16-residue group][k-step][lane]; null = vector variant
   int NGRP, KS;          // 16-residue groups, k-steps (4 taps each) of a 4-residue block's common window
-  int reserved = 0;      // unused: holds the argument layout (the next change to FusedArgs may drop it)
   unsigned long long *stamps; // RSMP_STAMPS: per-phase cycle sums [8] (null in production)
   const FusedBlock *blk; // [nblocks] in HBM, written by fused_prep_kernel ahead of the launch
   const int *qtab;       // matrix-pipe variant: window start (at0 + rb*step)/polyL of every 4-residue block rb = 4*i, [NGRP*4]
   const double2 *cfm2;   // the same A operands two k-steps per 16-byte element: [group][(KS + 1) / 2][lane] (lean kernel)
+  const WalkStart *wst = nullptr; // [nblocks] beside blk: the tile walk's start states (lean kernels only)
 };
 
 // Lean fast path of the matrix-pipe variant (fused_fast.hip): both ends are plain interleaved frames in one buffer each
@@ -435,12 +498,15 @@ hipError_t launch_fused(int log2n, int log2p, const AnyView &in, const AnyView &
 hipError_t launch_seam(const AnyView &out, const FusedArgs &a, hipStream_t st);
 bool fused_shape_supported(int log2n, int log2p, int n, int span, int max_seam_outputs);
 bool fused_mfma_supported(int log2n, int log2p, int ksteps);
-hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st);
+// wst (optional): the lean kernels' WalkStart record of every entry, next to it
+hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_t st, WalkStart *wst = nullptr);
 // host only (test hook): every (round, group, column step, lane) slot of entry k's tile walk in the lean kernels, 7 ints per slot
 // (round, group, column step, lane, output index relative to i_lo, 1 if the store's range check keeps it, window start);
 // head[13] = i_lo, cnt, K, KA, per-group walk?, g_lo, g_hi, ka, tiles, tiles of the uniform walk, irel_lo, base_li, groups.
 // Returns the number of slots (only the first `cap` are written).
 size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int *slots, size_t cap);
+// host only (test hook): entry k's WalkStart record as 56 ints
+void fused_walk_start_host(const FusedPrepArgs &p, int k, int *out56);
 
 // standalone rational polyphase stage on the matrix pipe (polymf.hip)
 struct PolyMfArgs {

@@ -14,7 +14,7 @@ EXPECTED_SYMBOLS = [
     "init_ratelib", "close_ratelib", "RR_open", "RR_flow", "RR_push", "RR_pull", "RR_drain", "RR_close", "RR_strerror",
     "RRX_open_batch", "RRX_open_batch_on", "RRX_device", "RRX_push_device", "RRX_pull_device", "RRX_flow_device", "RRX_push_strided", "RRX_pull_strided",
     "RRX_set_stream", "RRX_sync", "RRX_profile", "RRX_profile_read", "RRX_profile_report", "RRX_debug_fail_alloc",
-    "RRX_debug_tile_walk",
+    "RRX_debug_tile_walk", "RRX_debug_walk_start",
     "RRX_open_batch_fmt", "RRX_format", "RRX_push_double", "RRX_pull_double", "RRX_flow_double", "RRX_push_device_double",
     "RRX_pull_device_double", "RRX_flow_device_double",
     "RRX_push_samples", "RRX_pull_samples", "RRX_flow_samples", "RRX_push_device_samples", "RRX_pull_device_samples",
@@ -42,6 +42,20 @@ class WalkGeom(C.Structure):
     """RRX_walk_geom (ratelib_amd.h): geometry of a fused launch's polyphase stage, for RRX_debug_tile_walk."""
     _fields_ = [("at0", C.c_longlong), ("b_offset", C.c_longlong), ("B0", C.c_longlong)] + [
         (k, C.c_int) for k in ("V", "polyL", "step", "n", "KS", "qb_min", "qb_max", "two_round", "ra_end", "rb_start", "nsub", "Vs")]
+
+
+class WalkStartWave(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n", "g", "pc", "pend")]
+
+
+class WalkStartRound(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("kb", "ke", "cnt", "b1", "b2")] + [("p0", C.c_int * 3), ("pend", C.c_int * 3), ("pad", C.c_int),
+                                                                         ("wave", WalkStartWave * 4)]
+
+
+class WalkStart(C.Structure):
+    """RRX_walk_start (ratelib_amd.h): the start states of one block's tile walk, for RRX_debug_walk_start."""
+    _fields_ = [("round", WalkStartRound * 2)]
 
 
 class RRError(RuntimeError):
@@ -148,6 +162,8 @@ def lib():
         if hasattr(L, "RRX_debug_tile_walk"):  # (a RATELIB_AMD_SO build of an older tree, in A/B runs, has none)
             L.RRX_debug_tile_walk.argtypes = [P(WalkGeom), C.c_int, P(C.c_longlong), vp, sz]
             L.RRX_debug_tile_walk.restype = C.c_longlong
+        if hasattr(L, "RRX_debug_walk_start"):  # (likewise)
+            L.RRX_debug_walk_start.argtypes = [P(WalkGeom), C.c_int, P(WalkStart)]
         for n in ("RRX_isamp_max", "RRX_available"):
             getattr(L, n).argtypes = [vp]
             getattr(L, n).restype = sz

@@ -96,6 +96,20 @@ typedef struct RRX_walk_geom {
 } RRX_walk_geom;
 long long RRX_debug_tile_walk(const RRX_walk_geom *geom, int k, long long *head, int *slots, size_t cap);
 
+/* Test hook, as above (-1 unless RSMP_TEST_HOOKS is set, else 0): the start states of block `k`'s tile walk, the record that the
+ * block table holds beside the entry and that the lean kernels begin from, evaluated on the host by the same function.
+ * round[0] covers periods [0, ka), round[1] [ka, K): periods [kb, ke), the outputs the round may store (cnt), the boundaries
+ * b1 <= b2 of its three runs of groups with each run's first period p0 and end pend = p0 + 4 x column steps, and for every
+ * wave its number of tiles n, its first group g, and pc = p0 + 4 x (first column step) with that group's pend.  A round the
+ * block does not have, and a wave without tiles, is all zero. */
+typedef struct RRX_walk_start {
+  struct {
+    int kb, ke, cnt, b1, b2, p0[3], pend[3], pad;
+    struct { int n, g, pc, pend; } wave[4];
+  } round[2];
+} RRX_walk_start;
+int RRX_debug_walk_start(const RRX_walk_geom *geom, int k, RRX_walk_start *out);
+
 /* Sample formats.  A handle gets its format when it is opened and keeps it: every handle opened by the calls above is
  * RRX_FMT_FLOAT (interleaved float32, fb_sample_t).  An RRX_FMT_DOUBLE handle takes and gives interleaved float64 frames
  * at both ends; the chain in between is the same fp64 arithmetic, stage kernels and geometry as on a float handle of the

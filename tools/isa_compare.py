@@ -10,7 +10,14 @@ comments and directives are dropped and basic-block labels are renumbered per fu
 index in the file, which moves when instances are added).  What is left is the instruction stream with every register,
 immediate and kernel-argument offset in it, so "identical" here is stricter than "allowing for kernel-argument offsets".
 Prints one line per kernel present in both files (optionally only those whose demangled-ish name contains a substring) and
-the kernels that exist in only one; exit status 1 if any common kernel differs."""
+the kernels that exist in only one; exit status 1 if any common kernel differs.
+
+    python tools/isa_compare.py --prologue FILE.s substring
+
+prints, for every kernel of one file whose name contains the substring, its register counts, scratch size and occupancy
+(the file's metadata), and for every s_barrier that is followed by a matrix instruction before the next barrier -- the
+start of a polyphase round -- what lies between the two: instructions, integer-division sequences (v_rcp_iflag), loads
+issued, and every s_waitcnt."""
 import re
 import sys
 
@@ -39,7 +46,35 @@ def functions(path):
     return out
 
 
+def prologue(path, sub):
+    text = open(path).read()
+    meta = {}
+    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_count:\s+(\d+)\n(?:.*\n)*?"
+                         r"\s+\.vgpr_count:\s+(\d+)", text):
+        meta[m.group(1)] = m.groups()[1:]
+    for name, body in sorted(functions(path).items()):
+        if sub not in name:
+            continue
+        scratch, sgpr, vgpr = meta.get(name, ("?", "?", "?"))
+        m = re.search(re.escape(name) + r":.*?; Occupancy: (\d+)", text, re.S)
+        print("%s\n  vgpr %s sgpr %s scratch %s occupancy (waves per SIMD) %s, %d instructions" %
+              (name, vgpr, sgpr, scratch, m.group(1) if m else "?", len(body)))
+        bars = [i for i, s in enumerate(body) if s.startswith("s_barrier")] + [len(body)]
+        for b, nb in zip(bars, bars[1:]):
+            first = next((i for i in range(b, nb) if body[i].startswith("v_mfma")), None)
+            if first is None:
+                continue
+            part = body[b + 1:first]
+            loads = [s.split()[0] for s in part if re.match(r"(s_load|s_buffer_load|global_load|buffer_load|flat_load)", s)]
+            print("  barrier at %d -> first matrix instruction at %d: %d instructions, %d v_rcp_iflag, loads issued %s, waits %s" %
+                  (b, first, len(part), sum(s.startswith("v_rcp_iflag") for s in part), loads or "none",
+                   [s.replace("s_waitcnt ", "") for s in part if s.startswith("s_waitcnt")]))
+    return 0
+
+
 def main():
+    if sys.argv[1] == "--prologue":
+        return prologue(sys.argv[2], sys.argv[3])
     a, b = functions(sys.argv[1]), functions(sys.argv[2])
     subs = sys.argv[3:]
     bad = 0
