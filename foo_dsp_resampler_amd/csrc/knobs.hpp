@@ -10,6 +10,7 @@
 //   RSMP_SEAM_RING_MB=n   budget of a fused chain's seam ring (default 1280): bounds the blocks per launch (tests force many launches per push)
 //   RSMP_STAMPS=1         per-phase cycle sums of the fused kernels (s_memtime), printed when the handle closes
 //   RSMP_LDS_PAD=n / RSMP_OCC=1   occupancy experiments of fused_kernel (more LDS per workgroup / print blocks per CU)
+//   RSMP_TEST_HOOKS       arms the RRX_debug_* entry points (allocation failures, host models of the tile walk and the output stage)
 //   RATELIB_AMD_DEVICES=all | i,j,...   RR_open / RRX_open_batch deal new handles round-robin over these devices
 //                         (unset: a handle lives on the calling thread's current device)
 //

@@ -28,7 +28,7 @@ import os
 import numpy as np
 import pytest
 
-import foo_dsp_resampler_amd as F
+from callpatterns import run_flow, run_push
 from chain_ld import CASES, CASE_IDS, ChainLD, case_reference, distance
 from oracle_binding import Oracle, lcg_noise
 
@@ -69,54 +69,6 @@ REACHES = {
     "8k_352k8": ["rsmp::polymf_kernel<7>", "rsmp::dft_kernel<11, 11, 11"],
     "44k1_48k_phase25": ["rsmp::fused_split2_dio_kernel<"],
 }
-
-
-def run_flow(fi, fo, nch, S, kw, x):
-    """x: [S, n, nch] float64.  Device flow on torch's stream, drain, pull: (y [S, m, nch] float64, kernel names)."""
-    n = x.shape[1]
-    chunk = 16384 if n <= 48000 else 1 << 17
-    r = F.Resampler(fi, fo, nch=nch, nstreams=S, dtype=np.float64, **kw)
-    assert r.format == F.RRX_FMT_DOUBLE
-    r.set_stream(torch.cuda.current_stream().cuda_stream)
-    r.profile(True)
-    xd = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    cap = int(chunk * fo / fi) + 8192
-    parts, names = [], set()
-    for s0 in range(0, n, chunk):
-        k = min(chunk, n - s0)
-        xin = xd[:, s0:s0 + k].contiguous()
-        y = torch.zeros((S, cap, nch), dtype=torch.float64, device="cuda")
-        iu, og = r.flow_device(xin, k, y, cap)
-        assert iu == k
-        parts.append(y[:, :og].cpu().numpy())
-        names |= {k_["kernel"] for k_ in r.profile_report()}
-    r.drain()
-    tcap = int(n * fo / fi) + 16
-    tail = torch.zeros((S, tcap, nch), dtype=torch.float64, device="cuda")
-    og = r.pull_device(tail, tcap)
-    parts.append(tail[:, :og].cpu().numpy())
-    r.sync()
-    names |= {k_["kernel"] for k_ in r.profile_report()}
-    assert r.available == 0
-    r.close()
-    return np.concatenate(parts, axis=1), names
-
-
-def run_push(fi, fo, nch, kw, x, chunk=4096):
-    """x: [n, nch] float64.  Host push / pull_all, drain: (y [m, nch] float64, kernel names)."""
-    r = F.Resampler(fi, fo, nch=nch, dtype=np.float64, **kw)
-    assert r.format == F.RRX_FMT_DOUBLE
-    r.profile(True)
-    parts, names = [], set()
-    for s0 in range(0, x.shape[0], chunk):
-        r.push(x[s0:s0 + chunk])
-        parts.append(r.pull_all())
-        names |= {k_["kernel"] for k_ in r.profile_report()}
-    r.drain()
-    parts.append(r.pull_all())
-    names |= {k_["kernel"] for k_ in r.profile_report()}
-    r.close()
-    return np.concatenate(parts), names
 
 
 _gpu = {}
@@ -179,9 +131,10 @@ def test_true_double_input():
 
 def test_kernel_families_covered():
     """The union of the kernels the cases launched holds every family a double handle can launch; the instances are listed in
-    profiles/fp64_parity_kernels.txt.  Not reachable through RR_config and the double API, so not here: poly_coop_kernel<1..3>
+    profiles/fp64_parity_kernels.txt.  Not reachable through RR_config and the double API, so not here: poly_coop_kernel<2..3>
     and poly_kernel<1..3> (every interpolated stage the planner builds has n <= 32 taps and a step below 4, so launch_poly_stage
-    always takes the shared-rows polyi_kernel), half_kernel<10> and <13>."""
+    always takes the shared-rows polyi_kernel; tests/test_gpu_variants.py reaches them through RSMP_NO_POLYI), and not reachable
+    at all: poly_coop_kernel<1>, half_kernel<10> and <13>."""
     seen = set()
     for case in CASES:
         seen |= gpu_result(case)[3]
