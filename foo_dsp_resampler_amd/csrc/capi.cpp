@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "finish.hpp"
 #include "lpc.hpp"
+#include "tracks.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -513,6 +514,277 @@ int RRX_edge_geometry(size_t in_rate, size_t out_rate, size_t *n_add, size_t *n_
   *prime_len = std::max<size_t>(prime, 2 * rsmp::kLpcMaxOrder + 1);
   *inbuf = std::min<size_t>(std::max<size_t>(in_rate / 10, 2048), 65536);
   return RR_OK;
+}
+
+namespace {
+
+// The counters of a handle without the handle: Engine::init's fifo preloads and the counter half of Engine::advance
+// (engine.cpp: advance_dft / advance_poly / advance_half with launch == false), on the plan alone, so that the geometry of a
+// track can be stated without a device.  tests/test_tracks_api.py holds it to the CPU resampler's totals and
+// tests/test_gpu_tracks.py to a real handle's.
+struct CounterChain {
+  const rsmp::ChainPlan &plan;
+  rsmp::Book b;
+
+  explicit CounterChain(const rsmp::ChainPlan &p) : plan(p)
+  {
+    const int ns = int(plan.stages.size());
+    b.wr.assign(ns + 1, 0);
+    b.rd.assign(ns + 1, 0);
+    b.st.assign(ns, rsmp::Book::St());
+    for (int i = 0; i < ns; ++i) {
+      const rsmp::StageSpec &sp = plan.stages[i];
+      b.wr[i] = sp.preload; // rate_base.h:417-422
+      if (sp.kind == rsmp::StageKind::Dft) b.st[i].remL = sp.remL0;
+      else if (sp.kind == rsmp::StageKind::Poly) b.st[i].at = sp.order == 0 ? (sp.at0 >> 32) : sp.at0;
+    }
+  }
+
+  // one pass of rate_process after n frames were appended to fifo 0 (rate_base.h:425-441)
+  void push(size_t n)
+  {
+    b.samples_in += n;
+    while (b.samples_in > plan.cfg.in_rate && b.samples_out > plan.cfg.out_rate) {
+      b.samples_in -= plan.cfg.in_rate;
+      b.samples_out -= plan.cfg.out_rate;
+    }
+    b.wr[0] += (long long)n;
+    for (int i = 0; i < int(plan.stages.size()); ++i) {
+      const rsmp::StageSpec &sp = plan.stages[i];
+      rsmp::Book::St &st = b.st[i];
+      long long &rd = b.rd[i], &wro = b.wr[i + 1];
+      const long long occ = b.wr[i] - rd;
+      if (sp.kind == rsmp::StageKind::Dft) { // dft_filter.h:78-84, :150-152, :187
+        const rsmp::DftFilter &f = plan.dft[sp.filt];
+        const int N = f.N, ov = f.num_taps - 1, V = N - ov, L = sp.L;
+        const bool stuffing = L != 1 && !(L >= 2 && !(L & (L - 1)));
+        const int kept = sp.step < 0 ? N - ((((1 << -sp.step) - 1) * N + ov) >> -sp.step) : V;
+        long long num_in = std::max<long long>(0, occ);
+        while (st.remL + (long long)L * num_in >= N) {
+          const int span = V - st.remL + L - 1;
+          const int take = span / L, rem = span % L;
+          rd += take;
+          num_in -= take;
+          if (stuffing) st.remL = L - 1 - rem;
+          if (sp.step > 1) {
+            const int j = (V - st.remM + sp.step - 1) / sp.step;
+            st.remM = st.remM + j * sp.step - V;
+            wro += j;
+          } else
+            wro += kept;
+          ++st.B;
+        }
+      } else if (sp.kind == rsmp::StageKind::Poly) { // rate_filters_generic.h:281 / :477, :302-304 / :499-500
+        const long long num_in = std::max<long long>(0, occ - sp.pre_post);
+        long long count = 0;
+        const long long step = sp.order == 0 ? (sp.step64 >> 32) : sp.step64;
+        const long long lim = sp.order == 0 ? num_in * sp.L : (num_in << 32);
+        if (st.at < lim) count = (lim - st.at + step - 1) / step;
+        const long long at_end = st.at + count * step;
+        if (sp.order == 0) {
+          rd += at_end / sp.L;
+          st.at = at_end % sp.L;
+        } else {
+          rd += at_end >> 32;
+          st.at = at_end & 0xffffffffLL;
+        }
+        wro += count;
+      } else { // rate_filters_generic.h:83, fifo.h:169
+        const long long avail = std::max<long long>(0, occ - sp.pre_post);
+        const long long num_out = (avail + 1) / 2;
+        if (2 * num_out <= occ) rd += 2 * num_out;
+        wro += num_out;
+      }
+    }
+  }
+
+  // Frames a handle yields in all for `total` frames pushed in isamp_max pieces, everything available pulled after each push,
+  // then drained and pulled: Resampler.convert_track_device's loop.  The drain target is Engine::drain's (rate_base.h:454-468),
+  // from the counters as rate_input's wrap by whole seconds left them.
+  size_t drained_total(size_t total)
+  {
+    size_t pulled = 0;
+    const size_t step = std::max<size_t>(plan.isamp_max, 1);
+    for (size_t pos = 0; pos < total; pos += step) {
+      push(std::min(step, total - pos));
+      const size_t n = size_t(b.wr.back() - b.rd.back());
+      b.rd.back() += (long long)n; // rate_base.h:447-448
+      b.samples_out += n;
+      pulled += n;
+    }
+    const size_t target = size_t(double(b.samples_in) / plan.factor + .5);
+    return target <= b.samples_out ? pulled : pulled + (target - b.samples_out);
+  }
+};
+
+// No track has 2^36 frames (18 days at 44.1 kHz): the geometry below walks a track's pushes one by one, and with this bound no sum
+// of two of its terms can wrap.
+constexpr size_t kTrackFramesMax = size_t(1) << 36;
+
+// RRX_track_geometry on a plan that exists already
+int track_geometry(const rsmp::ChainPlan &plan, size_t frames, size_t *lead, size_t *ext_frames, size_t *out_first, size_t *out_frames)
+{
+  if (frames > kTrackFramesMax) return RR_INVPARAM;
+  size_t n_add = 0, n_drop = 0, prime = 0, inbuf = 0;
+  const int rc = RRX_edge_geometry(plan.cfg.in_rate, plan.cfg.out_rate, &n_add, &n_drop, &prime, &inbuf);
+  if (rc != RR_OK) return rc;
+  const bool extend = frames > size_t(2 * rsmp::kLpcMaxOrder); // foo_dsp_rate.cpp:222-239: up to 64 frames go through as they are
+  *lead = extend ? n_add : 0;
+  *ext_frames = frames + 2 * *lead;
+  *out_first = extend ? n_drop : 0;
+  const size_t total = CounterChain(plan).drained_total(*ext_frames);
+  *out_frames = total > 2 * *out_first ? total - 2 * *out_first : 0;
+  return RR_OK;
+}
+
+// rows of `frames` input frames give at most this many output frames (the capacity Resampler.convert_track_device allocates);
+// false: it does not fit a size_t
+bool out_row_capacity(const rsmp::ChainPlan &plan, size_t frames, size_t *cap)
+{
+  const unsigned __int128 c = (unsigned __int128)frames * plan.cfg.out_rate / plan.cfg.in_rate + 2;
+  if (c > (unsigned __int128)(~size_t(0))) return false;
+  *cap = size_t(c);
+  return true;
+}
+
+} // namespace
+
+int RRX_track_geometry(const RR_config *config, size_t frames, size_t *lead, size_t *ext_frames, size_t *out_first, size_t *out_frames)
+{
+  if (!config || !lead || !ext_frames || !out_first || !out_frames) return RR_INVPARAM;
+  try {
+    rsmp::ChainPlan plan;
+    const int rc = rsmp::make_plan(to_config(config), plan);
+    if (rc) return rc;
+    return track_geometry(plan, frames, lead, ext_frames, out_first, out_frames);
+  } catch (const std::bad_alloc &) {
+    return finish(RR_ENOMEM);
+  } catch (...) {
+    return RR_INTERNAL;
+  }
+}
+
+int RRX_tracks_plan(const RR_config *config, const size_t *frames, int ntracks, RRX_track *table, size_t *row_frames, size_t *out_row_cap,
+                    size_t *src_total, size_t *dst_total)
+{
+  if (!config || !frames || ntracks < 1 || !table || !row_frames || !out_row_cap || !src_total || !dst_total) return RR_INVPARAM;
+  try {
+    rsmp::ChainPlan plan;
+    int rc = rsmp::make_plan(to_config(config), plan);
+    if (rc) return rc;
+    size_t src = 0, dst = 0, row = 0;
+    for (int t = 0; t < ntracks; ++t) // (before any track is walked: a refusal costs nothing)
+      if (frames[t] > kTrackFramesMax || (src += frames[t]) < frames[t]) return RR_INVPARAM;
+    src = 0;
+    for (int t = 0; t < ntracks; ++t) {
+      size_t lead = 0, ext = 0, out_first = 0, out_frames = 0;
+      if (t > 0 && frames[t] == frames[t - 1]) { // equal neighbours (the zero-length tail of a batch, an album of singles): walked once
+        lead = table[t - 1].lead, ext = frames[t] + 2 * lead, out_first = table[t - 1].out_first, out_frames = table[t - 1].out_frames;
+      } else if ((rc = track_geometry(plan, frames[t], &lead, &ext, &out_first, &out_frames)) != RR_OK)
+        return rc;
+      table[t].src_first = src;
+      table[t].frames = frames[t];
+      table[t].lead = lead;
+      table[t].out_first = out_first;
+      table[t].out_frames = out_frames;
+      table[t].dst_first = dst;
+      src += frames[t];
+      if (dst + out_frames < dst) return RR_INVPARAM;
+      dst += out_frames;
+      row = std::max(row, ext);
+    }
+    size_t cap = 0;
+    if (!out_row_capacity(plan, row, &cap)) return RR_INVPARAM;
+    *row_frames = row;
+    *out_row_cap = cap;
+    *src_total = src;
+    *dst_total = dst;
+    return RR_OK;
+  } catch (const std::bad_alloc &) {
+    return finish(RR_ENOMEM);
+  } catch (...) {
+    return RR_INTERNAL;
+  }
+}
+
+namespace {
+
+// the device argument of a handle-free device call, checked as RRX_lpc_extrapolate_device checks it: RR_OK, or what the call returns
+int check_device(int device)
+{
+  if (device >= 0) { // as RRX_open_batch_on
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return RR_EXTUNINIT;
+    if (device >= n) return RR_INVPARAM;
+  }
+  return rsmp::device_is_gfx950(device) ? RR_OK : RR_EXTUNINIT;
+}
+
+} // namespace
+
+// The stage pass of a ragged batch (tracks.hip).  Refusals first, as in RRX_lpc_extrapolate_device.
+int RRX_tracks_stage_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks, int nch,
+                            const fb_sample_t *d_packed, size_t src_total, fb_sample_t *d_rows, size_t row_frames)
+{
+  static_assert(sizeof(RRX_track) == sizeof(rsmp::Track) && sizeof(RRX_track) == 6 * sizeof(unsigned long long), "RRX_track mirrors rsmp::Track");
+  if (!d_tracks || !d_packed || !d_rows || ntracks < 1 || nch < 1 || !in_rate || !out_rate || !row_frames) return RR_INVPARAM;
+  if (device < -1 || (long long)ntracks * nch > 0x3fffffffLL) return RR_INVPARAM; // (two workgroups per channel of every track)
+  // no buffer has 2^60 samples: with that no offset the kernels compute can wrap
+  const size_t most = (~size_t(0) >> 4) / size_t(nch);
+  if (src_total > most || row_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  size_t n_add = 0, n_drop = 0, prime = 0, inbuf = 0;
+  if (RRX_edge_geometry(in_rate, out_rate, &n_add, &n_drop, &prime, &inbuf) != RR_OK || prime > size_t(rsmp::kLpcLdsFrames)) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  const int rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  rsmp::TracksStageArgs a;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src = d_packed;
+  a.rows = d_rows;
+  a.src_total = src_total;
+  a.row_frames = row_frames;
+  a.ntracks = ntracks;
+  a.nch = nch;
+  a.prime_len = int(prime);
+  return rsmp::launch_tracks_stage(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// The output stage of a ragged batch (tracks.hip).  Refusals first, as in RRX_finish_device.
+int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                             const void *d_rows, size_t row_frames, int dst_format, void *d_dst, size_t dst_total, const double *d_gain,
+                             int dither, unsigned long long seed, double *d_peak, unsigned long long *d_clipped)
+{
+  if (!d_tracks || !d_rows || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (d_dst && dst_format != RRX_FMT_S16 && dst_format != RRX_FMT_S24_3 && dst_format != RRX_FMT_S32) return RR_INVPARAM;
+  if (!d_dst && !d_peak && !d_clipped) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks) || (d_dst && dst_total > most)) return RR_INVPARAM;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames) return RR_OK;
+  const int rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  rsmp::TracksFinishArgs a;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src = d_rows;
+  a.dst = d_dst;
+  a.gain = d_gain;
+  a.peak = d_peak;
+  a.clipped = d_clipped;
+  a.row_frames = row_frames;
+  a.dst_total = dst_total;
+  a.seed = seed;
+  a.ntracks = ntracks;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  a.bits = !d_dst ? 31 : dst_format == RRX_FMT_S16 ? 15 : dst_format == RRX_FMT_S24_3 ? 23 : 31; // measure only: the S32 grid
+  a.dither = dither != 0;
+  return rsmp::launch_tracks_finish(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
 size_t RRX_isamp_max(const RR_handle *h) { return h ? h->eng->isamp_max() : 0; }

@@ -1,0 +1,352 @@
+// Ragged track batches: the kernels around a batch handle whose streams hold tracks of unequal length.
+//
+// Stage (RRX_tracks_stage_device): packed tracks [sum of frames][nch] -> rows [ntracks][row_frames][nch].  Row t is
+//   [0, lead)                      backward LPC extension from the track's first min(frames, prime_len) frames   tracks_lpc_kernel
+//   [lead, lead + frames)          the track                                                                       tracks_copy_kernel
+//   [lead + frames, ext)           forward LPC extension from its last min(frames, prime_len) frames             tracks_lpc_kernel
+//   [ext, row_frames)              zeros: the track's drain                                         tracks_copy_kernel
+// with ext = lead + frames + lead.  tracks_lpc_kernel is one 64-lane workgroup per (track, channel, edge) around lpc_channel
+// (lpc_body.hpp), the body of lpc.hip's kernel: the two edges of a channel are sums over different base frames read from the
+// packed source, so they run side by side.  tracks_copy_kernel is uniform, bandwidth-bound work: grid = (chunk of a row, track),
+// every row has row_frames * nch samples to look at.  A row is cut into a head of 0..3 samples up to the first 16-byte boundary
+// of the DESTINATION, groups of 4 samples (one lane each: 16 bytes loaded, which needs dword alignment only, 16 aligned bytes
+// stored) and a tail of 0..3 samples; a group that straddles two regions goes sample by sample.  The two kernels write disjoint
+// frames and read only the source, so their order does not matter.
+//
+// Output stage (RRX_tracks_finish_device): finish_sample (finish.hpp) per track, finish.hip's shape with a per-track prologue --
+// grid = (chunk of a row, track), head / groups of 4 / tail decided per track from where ITS bytes begin in the packed
+// destination, statistics in registers and LDS where lcm(4, nch) <= 1024.  The grid is sized for a full row; the workgroups past
+// a shorter track's end exit at once.
+//
+// The table is the caller's, on the device, and is not validated: every value taken from it is clamped first (Entry; the prologue of tracks_finish_kernel), so
+// a wrong table gives wrong samples and never an access outside the source, the track's own row or the destination.
+#include "tracks.hpp"
+
+#include "finish.hpp"
+#include "lpc_body.hpp"
+
+namespace rsmp {
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int kThreads = 256, kSpanMax = kThreads * 4;
+
+__device__ __forceinline__ u64 min_u(u64 x, u64 y) { return x < y ? x : y; }
+
+// Track t's input side, clamped: lead + frames + fwd <= row_frames and first + have <= src_total whatever the table says
+struct Entry {
+  u64 first, have; // the track's frames in the packed source: [first, first + have), have <= frames
+  u64 lead, frames, fwd;
+  __device__ __forceinline__ Entry(const TracksStageArgs &a, u64 t)
+  {
+    const Track tr = a.tracks[t];
+    lead = min_u(tr.lead, a.row_frames);
+    frames = min_u(tr.frames, a.row_frames - lead);
+    fwd = min_u(lead, a.row_frames - lead - frames);
+    first = min_u(tr.src_first, a.src_total);
+    have = min_u(frames, a.src_total - first);
+  }
+};
+
+__global__ __launch_bounds__(64) void tracks_lpc_kernel(TracksStageArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char tracks_lds[];
+  const int lane = threadIdx.x, edge = blockIdx.x & 1, nch = a.nch;
+  const u64 t = (blockIdx.x >> 1) / (unsigned)nch, ch = (blockIdx.x >> 1) % (unsigned)nch;
+  const Entry e(a, t);
+  const long long extra = (long long)(edge ? e.fwd : e.lead);
+  if (!extra) return;
+  const long long n = (long long)min_u(e.frames, (u64)a.prime_len);      // base frames: the track's first n, or its last n
+  const u64 base = edge ? e.frames - (u64)n : 0;
+  const long long readable = e.have > base ? (long long)(e.have - base) : 0; // (all n of them, unless the table is wrong)
+  const float *x = a.src + (e.first + min_u(base, e.have)) * nch + ch;
+  float *y = a.rows + ((t * a.row_frames + e.lead + base) * nch + ch);
+  if (n <= kLpcMaxOrder) { // no table of RRX_tracks_plan: a lead means more than 64 frames.  Zeros, so that the row is written all the same.
+    for (long long i = lane; i < extra; i += 64) y[(edge ? n + i : -1 - i) * nch] = 0.0f;
+    return;
+  }
+  lpc_channel<true>(tracks_lds, lane, n, (float)(n + 1) / 2.0f, kLpcMaxOrder, edge ? 0 : extra, edge ? extra : 0,
+                    [=](long long i) { return i < readable ? x[i * nch] : 0.0f; }, [=](long long i, float v) { y[i * nch] = v; });
+}
+
+__global__ __launch_bounds__(kThreads) void tracks_copy_kernel(TracksStageArgs a, int t0, int steps)
+{
+  const unsigned tid = threadIdx.x;
+  const u64 t = (u64)(t0 + (int)blockIdx.y), nch = (u64)a.nch, n = a.row_frames * nch; // n: samples of a row
+  const Entry e(a, t);
+  // in samples of the row: [c0, c1) is the track, [z0, n) the zeros; what lies between belongs to tracks_lpc_kernel
+  const u64 c0 = e.lead * nch, c1 = c0 + e.frames * nch, z0 = c1 + e.fwd * nch, have = e.have * nch;
+  const float *s = a.src + e.first * nch; // sample j of the track, j < have
+  float *row = a.rows + t * n;
+  auto one = [&](u64 k) {
+    if (k >= c0 && k < c1) row[k] = k - c0 < have ? s[k - c0] : 0.0f;
+    else if (k >= z0) row[k] = 0.0f;
+  };
+  u64 head = ((16 - (reinterpret_cast<u64>(row) & 15)) & 15) >> 2; // samples in front of the row's first 16-byte boundary
+  if (head > n) head = n;
+  const u64 ngroups = (n - head) >> 2;
+  if (blockIdx.x == 0) { // head and tail samples, one lane each
+    const u64 ntail = n - head - (ngroups << 2);
+    if (tid < head) one(tid);
+    else if (tid >= 64 && tid < 64 + ntail) one(head + (ngroups << 2) + (tid - 64));
+  }
+  for (int u = 0; u < steps; ++u) {
+    const u64 g = ((u64)blockIdx.x * (unsigned)steps + (unsigned)u) * kThreads + tid;
+    if (g >= ngroups) break;
+    const u64 k = head + (g << 2);
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (k >= c0 && k + 4 <= c1 && k - c0 + 4 <= have) __builtin_memcpy(v, s + (k - c0), sizeof(v)); // 16 bytes, dword aligned
+    else if (k + 4 <= c0 || (k >= c1 && k + 4 <= z0)) continue;                                    // extension frames only
+    else if (k < z0) { // a group across two regions, or the track's frames that a wrong table puts past the source
+      for (int j = 0; j < 4; ++j) one(k + j);
+      continue;
+    }
+    __builtin_memcpy(__builtin_assume_aligned(row + k, 16), v, sizeof(v));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- output stage
+
+__device__ __forceinline__ u64 peak_bits(double a) { return (u64)__double_as_longlong(a); }
+
+// bits of a non-negative double order as unsigned integers (a NaN, sign cleared by fabs, lies above +inf and stays)
+__device__ __forceinline__ void global_stats(const TracksFinishArgs &a, u64 c, u64 pk, u64 cl)
+{
+  if (a.peak && pk) {
+    u64 *p = reinterpret_cast<u64 *>(a.peak) + c;
+    if (pk > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, pk); // the value only ever grows
+  }
+  if (a.clipped && cl) atomicAdd(a.clipped + c, cl);
+}
+
+// four consecutive quantised samples as whole dwords
+template <int kBits> struct Pack;
+template <> struct Pack<15> {
+  static constexpr int kBytes = 2, kWords = 2;
+  static __device__ __forceinline__ void words(const int *q, unsigned *w)
+  {
+    w[0] = ((unsigned)q[0] & 0xffffu) | ((unsigned)q[1] << 16);
+    w[1] = ((unsigned)q[2] & 0xffffu) | ((unsigned)q[3] << 16);
+  }
+};
+template <> struct Pack<23> {
+  static constexpr int kBytes = 3, kWords = 3;
+  static __device__ __forceinline__ void words(const int *q, unsigned *w)
+  {
+    const unsigned a = (unsigned)q[0] & 0xffffffu, b = (unsigned)q[1] & 0xffffffu, c = (unsigned)q[2] & 0xffffffu, d = (unsigned)q[3] & 0xffffffu;
+    w[0] = a | (b << 24);
+    w[1] = (b >> 8) | (c << 16);
+    w[2] = (c >> 16) | (d << 8);
+  }
+};
+template <> struct Pack<31> {
+  static constexpr int kBytes = 4, kWords = 4;
+  static __device__ __forceinline__ void words(const int *q, unsigned *w)
+  {
+    for (int j = 0; j < 4; ++j) w[j] = (unsigned)q[j];
+  }
+};
+
+// S: float or double rows.  kWrite = false: measure only.  kReg: statistics in registers and LDS (finish.hip).
+// Track t is stream t of RRX_finish_device: gain[t], statistics and dither channel t * nch + ch, frame 0 = its first output frame.
+template <typename S, int kBits, bool kWrite, bool kReg>
+__global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArgs a, int t0, int span, unsigned fps, int steps)
+{
+  __shared__ u64 sh_peak[kReg ? kFinishLdsChannels : 1];
+  __shared__ unsigned sh_clip[kReg ? kFinishLdsChannels : 1];
+  using P = Pack<kBits>;
+  const unsigned tid = threadIdx.x;
+  const unsigned nch = (unsigned)a.nch;
+  const u64 t = (u64)(t0 + (int)blockIdx.y), cbase = t * nch;
+  // the track's slice, clamped: inside its row, and (when written) inside the destination
+  const Track tr = a.tracks[t];
+  const u64 of = min_u(tr.out_first, a.row_frames), df = kWrite ? min_u(tr.dst_first, a.dst_total) : 0;
+  u64 frames = min_u(tr.out_frames, a.row_frames - of);
+  if (kWrite) frames = min_u(frames, a.dst_total - df);
+  const u64 n = frames * nch;
+  const S *src = static_cast<const S *>(a.src) + (t * a.row_frames + of) * nch;
+  unsigned char *dst = kWrite ? static_cast<unsigned char *>(a.dst) + df * nch * P::kBytes : nullptr;
+  const bool has_gain = a.gain != nullptr, dither = a.dither != 0;
+
+  // the track's head: samples in front of the first dword boundary of the destination
+  const u64 addr = reinterpret_cast<u64>(dst);
+  unsigned head = !kWrite ? 0u : kBits == 15 ? (unsigned)(addr >> 1) & 1u : kBits == 23 ? (unsigned)addr & 3u : 0u;
+  if (head > n) head = (unsigned)n;
+  const u64 ngroups = (n - head) >> 2;
+  const unsigned gps = (unsigned)span >> 2; // groups (= lanes at work) per step
+  const u64 step0 = (u64)blockIdx.x * (unsigned)steps;
+  if (blockIdx.x != 0 && step0 * gps >= ngroups) return; // past the end of a track shorter than the row
+  const double gain = has_gain ? a.gain[t] : 1.0;
+
+  if (kReg) {
+    for (unsigned c = tid; c < nch; c += kThreads) {
+      sh_peak[c] = 0;
+      sh_clip[c] = 0;
+    }
+    __syncthreads();
+  }
+
+  // head and tail samples: workgroup 0, one lane each, channel and frame by division
+  if (blockIdx.x == 0) {
+    const unsigned ntail = (unsigned)(n - head - (ngroups << 2));
+    const bool is_head = tid < head, is_tail = tid >= 64 && tid < 64 + ntail;
+    if (is_head || is_tail) {
+      const u64 k = is_head ? tid : head + (ngroups << 2) + (tid - 64);
+      const u64 fr = k / nch;
+      const unsigned ch = (unsigned)(k - fr * nch);
+      const FinishSample r = finish_sample<kBits>((double)src[k], has_gain, gain, dither, a.seed, fr, cbase + ch);
+      if (kWrite) finish_store_bytes<kBits>(dst + k * P::kBytes, r.q);
+      if (kReg) {
+        atomicMax(&sh_peak[ch], peak_bits(r.a));
+        if (r.clip) atomicAdd(&sh_clip[ch], 1u);
+      } else {
+        global_stats(a, cbase + ch, peak_bits(r.a), r.clip ? 1ull : 0ull);
+      }
+    }
+  }
+
+  if (tid < gps) {
+    // kReg: the lane's 4 samples are samples head + 4 tid + j of every step's span, a whole number of frames (fps) further each step
+    unsigned chj[4];
+    u64 frj[4], pk[4] = {0, 0, 0, 0};
+    unsigned cl[4] = {0, 0, 0, 0};
+    if (kReg) {
+      const unsigned k0 = head + 4 * tid, f0 = k0 / nch;
+      unsigned ch = k0 - f0 * nch;
+      u64 fr = f0 + step0 * fps;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        chj[j] = ch;
+        frj[j] = fr;
+        if (++ch == nch) ch = 0, ++fr;
+      }
+    }
+    for (int u = 0; u < steps; ++u) {
+      const u64 gi = (step0 + u) * gps + tid;
+      if (gi >= ngroups) break;
+      const u64 k = head + (gi << 2);
+      S x[4];
+      __builtin_memcpy(x, src + k, sizeof(x)); // 16-byte loads: one for float, two for double
+      if (!kReg) {
+        const u64 f0 = k / nch;
+        unsigned ch = (unsigned)(k - f0 * nch);
+        u64 fr = f0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          chj[j] = ch;
+          frj[j] = fr;
+          if (++ch == nch) ch = 0, ++fr;
+        }
+      }
+      int q[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const FinishSample r = finish_sample<kBits>((double)x[j], has_gain, gain, dither, a.seed, frj[j], cbase + chj[j]);
+        q[j] = r.q;
+        if (kReg) {
+          const u64 b = peak_bits(r.a);
+          pk[j] = b > pk[j] ? b : pk[j];
+          cl[j] += r.clip ? 1u : 0u;
+          frj[j] += fps;
+        } else {
+          global_stats(a, cbase + chj[j], peak_bits(r.a), r.clip ? 1ull : 0ull);
+        }
+      }
+      if (kWrite) {
+        unsigned w[P::kWords];
+        P::words(q, w);
+        __builtin_memcpy(reinterpret_cast<unsigned *>(dst + k * P::kBytes), w, sizeof(w)); // dword aligned: that is what the head is for
+      }
+    }
+    if (kReg) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (pk[j]) atomicMax(&sh_peak[chj[j]], pk[j]);
+        if (cl[j]) atomicAdd(&sh_clip[chj[j]], cl[j]);
+      }
+    }
+  }
+
+  if (kReg) {
+    __syncthreads();
+    for (unsigned c = tid; c < nch; c += kThreads) global_stats(a, cbase + c, sh_peak[c], sh_clip[c]);
+  }
+}
+
+u64 gcd_u(u64 x, u64 y)
+{
+  while (y) {
+    const u64 r = x % y;
+    x = y;
+    y = r;
+  }
+  return x;
+}
+
+template <typename S, int kBits, bool kWrite>
+hipError_t finish_typed(hipStream_t stream, const TracksFinishArgs &a)
+{
+  const u64 nch = (u64)a.nch, lcm4 = nch / gcd_u(nch, 4) * 4, n = a.row_frames * nch; // n: the most samples a track can have
+  static_assert(kFinishLdsChannels >= kSpanMax, "nch <= lcm(4, nch) <= kSpanMax has to fit the LDS table");
+  const bool reg = lcm4 <= (u64)kSpanMax;
+  const int span = reg ? int(kSpanMax / lcm4 * lcm4) : kSpanMax;
+  const unsigned fps = reg ? unsigned(span / a.nch) : 0u;
+  const u64 row_steps = ((n + 3) / 4 + span / 4 - 1) / (span / 4);
+  // steps per workgroup as in finish.hip: about 16 workgroups per CU, at most 32 steps, more only to stay inside the grid limit
+  // (n < 2^60, so a workgroup sees fewer than 2^31 samples, which its 32-bit clip counts hold)
+  u64 steps = row_steps * (u64)a.ntracks / 4096;
+  steps = steps < 1 ? 1 : steps > 32 ? 32 : steps;
+  while ((row_steps + steps - 1) / steps > 0x7fffffffull) steps *= 2;
+  const unsigned gx = (unsigned)((row_steps + steps - 1) / steps);
+  for (int t0 = 0; t0 < a.ntracks; t0 += 32768) { // grid.y is a 16-bit count
+    const int nt = a.ntracks - t0 < 32768 ? a.ntracks - t0 : 32768;
+    const dim3 grid(gx ? gx : 1, (unsigned)nt), block(kThreads);
+    if (reg) hipLaunchKernelGGL((tracks_finish_kernel<S, kBits, kWrite, true>), grid, block, 0, stream, a, t0, span, fps, (int)steps);
+    else hipLaunchKernelGGL((tracks_finish_kernel<S, kBits, kWrite, false>), grid, block, 0, stream, a, t0, span, fps, (int)steps);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <typename S> hipError_t finish_src(hipStream_t stream, const TracksFinishArgs &a)
+{
+  if (!a.dst) return finish_typed<S, 31, false>(stream, a);
+  switch (a.bits) {
+  case 15: return finish_typed<S, 15, true>(stream, a);
+  case 23: return finish_typed<S, 23, true>(stream, a);
+  default: return finish_typed<S, 31, true>(stream, a);
+  }
+}
+
+} // namespace
+
+hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a)
+{
+  // copy and zero fill: 8 steps of 256 groups (32 KiB written) per workgroup, more only to stay inside the grid limit
+  const u64 groups = (a.row_frames * (u64)a.nch + 3) / 4 + 1; // (+1: the head can move the last samples into one more group)
+  u64 steps = 8;
+  while ((groups + steps * kThreads - 1) / (steps * kThreads) > 0x7fffffffull) steps *= 2;
+  const unsigned gx = (unsigned)((groups + steps * kThreads - 1) / (steps * kThreads));
+  for (int t0 = 0; t0 < a.ntracks; t0 += 32768) { // grid.y is a 16-bit count
+    const int nt = a.ntracks - t0 < 32768 ? a.ntracks - t0 : 32768;
+    hipLaunchKernelGGL(tracks_copy_kernel, dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, t0, (int)steps);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  // the two extensions of every (track, channel)
+  static DynLdsOnce once;
+  const hipError_t e = once.set(reinterpret_cast<const void *>(&tracks_lpc_kernel), int(sizeof(LpcShared) + kLpcLdsFrames * sizeof(float)));
+  if (e != hipSuccess) return e;
+  const size_t lds = sizeof(LpcShared) + size_t(a.prime_len) * sizeof(float);
+  hipLaunchKernelGGL(tracks_lpc_kernel, dim3((unsigned)((long long)a.ntracks * a.nch * 2)), dim3(64), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tracks_finish(hipStream_t stream, const TracksFinishArgs &a)
+{
+  return a.src_double ? finish_src<double>(stream, a) : finish_src<float>(stream, a);
+}
+
+} // namespace rsmp

@@ -21,6 +21,7 @@ EXPECTED_SYMBOLS = [
     "RRX_flow_device_samples",
     "RRX_lpc_extrapolate_device", "RRX_edge_geometry",
     "RRX_finish_device", "RRX_debug_finish_host",
+    "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
@@ -42,6 +43,11 @@ class WalkGeom(C.Structure):
     """RRX_walk_geom (ratelib_amd.h): geometry of a fused launch's polyphase stage, for RRX_debug_tile_walk."""
     _fields_ = [("at0", C.c_longlong), ("b_offset", C.c_longlong), ("B0", C.c_longlong)] + [
         (k, C.c_int) for k in ("V", "polyL", "step", "n", "KS", "qb_min", "qb_max", "two_round", "ra_end", "rb_start", "nsub", "Vs")]
+
+
+class RRXTrack(C.Structure):
+    """RRX_track (ratelib_amd.h): where one track of a ragged batch lies, all in frames."""
+    _fields_ = [(k, C.c_ulonglong) for k in ("src_first", "frames", "lead", "out_first", "out_frames", "dst_first")]
 
 
 class WalkStartWave(C.Structure):
@@ -180,6 +186,12 @@ def lib():
             host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_int, u64, u64, vp, vp]
             L.RRX_finish_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_finish_host.argtypes = host
+        if hasattr(L, "RRX_tracks_plan"):  # (as above)
+            u64 = C.c_ulonglong
+            L.RRX_track_geometry.argtypes = [P(RRConfig), sz, P(sz), P(sz), P(sz), P(sz)]
+            L.RRX_tracks_plan.argtypes = [P(RRConfig), P(sz), C.c_int, P(RRXTrack), P(sz), P(sz), P(sz), P(sz)]
+            L.RRX_tracks_stage_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, vp, sz, vp, sz]
+            L.RRX_tracks_finish_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, sz, vp, C.c_int, u64, vp, vp]
         _lib = L
     return _lib
 
@@ -320,6 +332,146 @@ def finish_device(x, dst_format, gain=None, dither=False, seed=0, first_frame=0,
                                    dst_format or 0, C.c_void_p(out.data_ptr()) if out is not None else None, frames, nstreams, frames, nch,
                                    C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed, first_frame,
                                    C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_finish_device")
+    return out, peak, clipped
+
+
+class TracksPlan:
+    """RRX_tracks_plan's answer: `table` (a ctypes array of RRXTrack, one per track), `row_frames` (length of the rows the handle
+    is pushed from), `out_row_cap` (pitch of its output rows), `src_total` / `dst_total` (frames of the packed source /
+    destination).  `array()` is the table as uint64 [ntracks, 6]; `to_device(device)` uploads it (int64 [ntracks, 6])."""
+
+    def __init__(self, table, row_frames, out_row_cap, src_total, dst_total):
+        self.table, self.row_frames, self.out_row_cap, self.src_total, self.dst_total = table, row_frames, out_row_cap, src_total, dst_total
+
+    def __len__(self):
+        return len(self.table)
+
+    def array(self):
+        return np.frombuffer(self.table, dtype=np.uint64).reshape(len(self.table), 6).copy()
+
+    def to_device(self, device):
+        import torch
+        return torch.from_numpy(self.array().view(np.int64)).to(device)
+
+
+def track_geometry(in_rate, out_rate, frames, **kw):
+    """Host-only: (lead, ext_frames, out_first, out_frames) of one track of `frames` frames on a handle of its own
+    (RRX_track_geometry).  Needs no GPU."""
+    cfg = _config(in_rate, out_rate, **kw)
+    v = [C.c_size_t(0) for _ in range(4)]
+    _check(lib().RRX_track_geometry(C.byref(cfg), int(frames), *[C.byref(x) for x in v]), "RRX_track_geometry")
+    return tuple(x.value for x in v)
+
+
+def _tracks_plan(cfg, lengths):
+    n = len(lengths)
+    if n < 1:
+        raise ValueError("a plan needs at least one track")
+    if min(lengths) < 0:
+        raise ValueError("track lengths are frame counts: none may be negative")
+    fr = (C.c_size_t * n)(*[int(v) for v in lengths])
+    table = (RRXTrack * n)()
+    v = [C.c_size_t(0) for _ in range(4)]
+    _check(lib().RRX_tracks_plan(C.byref(cfg), fr, n, table, *[C.byref(x) for x in v]), "RRX_tracks_plan")
+    return TracksPlan(table, *[x.value for x in v])
+
+
+def tracks_plan(in_rate, out_rate, lengths, **kw):
+    """Host-only: the geometry of a ragged batch of tracks of `lengths` frames (RRX_tracks_plan), as a TracksPlan.  Needs no GPU."""
+    return _tracks_plan(_config(in_rate, out_rate, **kw), list(lengths))
+
+
+def _tracks_table(table, ntracks=None):
+    """the device copy of a plan's table: a contiguous int64 tensor [ntracks, 6]"""
+    if str(table.dtype) != "torch.int64" or table.dim() != 2 or table.shape[1] != 6 or not table.is_cuda or not table.is_contiguous():
+        raise TypeError("the table must be a contiguous int64 device tensor [ntracks, 6] (TracksPlan.to_device)")
+    if ntracks is not None and table.shape[0] != ntracks:
+        raise ValueError("the table has %d entries for %d rows" % (table.shape[0], ntracks))
+    return table.shape[0]
+
+
+def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, stream=None):
+    """The stage pass of a ragged batch on the device (RRX_tracks_stage_device): `packed` is a contiguous float32 device tensor
+    [src_total, nch] of tracks laid end to end, `table` the device copy of a plan's table (TracksPlan.to_device).  Returns the rows
+    the handle is pushed from, float32 [ntracks, row_frames, nch] (`out`, or a new tensor): each track behind and in front of
+    its own LPC extension, zeros behind it.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
+    import torch
+    if packed.dim() != 2 or packed.dtype != torch.float32 or not packed.is_cuda or not packed.is_contiguous():
+        raise TypeError("packed must be a contiguous float32 device tensor [frames, nch]")
+    ntracks = _tracks_table(table)
+    src_total, nch = packed.shape
+    shape = (ntracks, int(row_frames), nch)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=packed.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != packed.device or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 tensor %r on %s" % (shape, packed.device))
+    if table.device != packed.device:
+        raise TypeError("the table must be on %s" % (packed.device,))
+    _ensure_init()
+    if not src_total:  # (nothing but zero-length tracks: the call still wants a pointer, and never reads through it)
+        packed = torch.zeros((1, nch), dtype=torch.float32, device=packed.device)
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    index = packed.device.index
+    _check(lib().RRX_tracks_stage_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
+                                         C.c_void_p(table.data_ptr()), ntracks, nch, C.c_void_p(packed.data_ptr()), src_total,
+                                         C.c_void_p(out.data_ptr()), int(row_frames)), "RRX_tracks_stage_device")
+    return out
+
+
+def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=False, seed=0, out=None, peak=None, clipped=None, stream=None):
+    """The output stage of a ragged batch on the device (RRX_tracks_finish_device): finish_device per track, in one call.
+
+    `rows` is a contiguous float32 or float64 device tensor [ntracks, row_frames, nch] (a handle's output rows), `table` the
+    device copy of a plan's table: track t's frames [out_first, out_first + out_frames) of row t go to frames [dst_first,
+    dst_first + out_frames) of one packed destination of `dst_total` frames -- int16 / int32 [dst_total, nch], or uint8
+    [dst_total, nch * 3] for RRX_FMT_S24_3; `dst_format` None measures only.  `gain`: None, a float, or a float64 device tensor
+    [ntracks].  `peak` (float64 [ntracks, nch]) and `clipped` (int64 [ntracks, nch]) cover each track's own frames only; they
+    are allocated (zeroed) when not passed and accumulated into otherwise.  Returns (out, peak, clipped).  The call only enqueues."""
+    import torch
+    dt = str(rows.dtype)
+    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
+        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
+    if dst_format not in (None, RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32 or None)" % (dst_format,))
+    ntracks, row_frames, nch = rows.shape
+    _tracks_table(table, ntracks)
+    dev = rows.device
+    if table.device != dev:
+        raise TypeError("the table must be on %s" % (dev,))
+    seed, dst_total = int(seed), int(dst_total)
+    if not 0 <= seed < 1 << 64 or dst_total < 0:
+        raise ValueError("seed must fit 64 unsigned bits, dst_total is a frame count")
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((ntracks,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (ntracks,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (ntracks, dev))
+    if dst_format is None:
+        if out is not None:
+            raise ValueError("dst_format=None measures only: there is nothing to write into `out`")
+    else:
+        odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
+        oshape = (dst_total, last)
+        if out is None:
+            out = torch.empty(oshape, dtype=odt, device=dev)
+        elif out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
+            raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
+    stats = []
+    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
+        if t is None:
+            t = torch.zeros((ntracks, nch), dtype=sdt, device=dev)
+        elif t.dtype != sdt or tuple(t.shape) != (ntracks, nch) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, ntracks, nch, dev))
+        stats.append(t)
+    peak, clipped = stats
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
+    _check(lib().RRX_tracks_finish_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
+                                          RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), row_frames,
+                                          dst_format or 0, C.c_void_p(out.data_ptr()) if write else None, dst_total,
+                                          C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
+                                          C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_device")
     return out, peak, clipped
 
 
@@ -675,3 +827,87 @@ class Resampler:
         y = self.convert_track_device(x)
         finish_kw.setdefault("stream", torch.cuda.current_stream(y.device))
         return finish_device(y, dst_format, **finish_kw)
+
+    def _convert_tracks_rows(self, tracks):
+        """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch])"""
+        import torch
+        if self.dtype != np.float32:
+            raise TypeError("convert_tracks_device needs a float32 handle (the LPC arithmetic is float32), not %s" % self.dtype)
+        tracks = list(tracks)
+        if not 1 <= len(tracks) <= self.nstreams:
+            raise ValueError("expected 1 to %d tracks (the handle's streams), got %d" % (self.nstreams, len(tracks)))
+        for x in tracks:
+            if x.dim() != 2 or x.shape[1] != self.nch:
+                raise ValueError("expected [frames, %d] tensors, got shape %r" % (self.nch, tuple(x.shape)))
+            if x.dtype != torch.float32 or not x.is_cuda or x.device.index != self.device:
+                raise TypeError("expected torch.float32 tensors on the handle's device (cuda:%d)" % self.device)
+        dev = tracks[0].device
+        # the streams without a track are zero-length tracks: they own no output
+        plan = _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
+        table = plan.to_device(dev)
+        total, cap = plan.row_frames, plan.out_row_cap
+        out = tracks[0].new_empty((self.nstreams, cap, self.nch))
+        if not total:  # nothing but zero-length tracks
+            return plan, table, out
+        cur = torch.cuda.current_stream(dev)
+        prev = self._stream
+        self.set_stream(cur.cuda_stream)
+        try:
+            src = tracks_stage_device(torch.cat(tracks).contiguous(), table, self.cfg.in_rate, self.cfg.out_rate, total, stream=cur)
+            got = 0
+
+            def pull():
+                nonlocal got
+                while self.available:
+                    if got >= cap:
+                        raise RuntimeError("convert_tracks_device: more output than %d frames in gives" % total)
+                    got += self.pull_device(out[:, got:], cap - got, stride=cap)
+
+            step = self.isamp_max
+            for pos in range(0, total, step):
+                self.push_device(src[:, pos:], min(step, total - pos), stride=total)
+                pull()
+            self.drain()
+            pull()
+        finally:
+            if prev is None:
+                self.use_own_stream()
+            else:
+                self.set_stream(prev)
+        need = max(int(e.out_first + e.out_frames) for e in plan.table)
+        if got < need:
+            raise RuntimeError("convert_tracks_device: %d output frames where the plan expects %d" % (got, need))
+        return plan, table, out
+
+    def convert_tracks_device(self, tracks):
+        """Whole tracks of UNEQUAL length, one per stream, device to device: convert_track_device for a ragged batch.  `tracks`
+        is a list of float32 device tensors [frames_i, nch], at most `nstreams` of them (the streams left over run empty).
+
+        The tracks are planned (tracks_plan), packed end to end, staged into rows of the longest extended length -- each with the
+        LPC extension at its own two ends and zeros behind it (tracks_stage_device) -- and the rows are pushed in isamp_max
+        pieces, drained and pulled, which is convert_track_device's loop.  The zeros behind a shorter track are its drain, so
+        every track gets, shape and bits, what convert_track_device gives it on a one-stream handle of its own.  Returns a list
+        of tensors [out_frames_i, nch]: views of the handle's output rows.  Runs on torch's current stream of the tracks'
+        device, copies no sample to the host and leaves the handle drained, as convert_track_device does.  The padding is
+        resampled too: batch tracks of similar length."""
+        plan, _, out = self._convert_tracks_rows(tracks)
+        return [out[t, int(e.out_first):int(e.out_first + e.out_frames)] for t, e in zip(range(len(tracks)), plan.table)]
+
+    def convert_tracks_to_pcm_device(self, tracks, dst_format, **finish_kw):
+        """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
+        packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  Returns (list of per-track
+        views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views."""
+        import torch
+        tracks = list(tracks)
+        plan, table, out = self._convert_tracks_rows(tracks)
+        n = len(tracks)
+        if "gain" in finish_kw and hasattr(finish_kw["gain"], "data_ptr") and self.nstreams > n:  # per-track gains: the idle streams get unity
+            g = finish_kw["gain"]
+            finish_kw["gain"] = torch.cat([g, g.new_ones(self.nstreams - n)])
+        for k in ("peak", "clipped"):
+            if finish_kw.get(k) is not None:
+                raise ValueError("%s is allocated by convert_tracks_to_pcm_device" % k)
+        finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
+        pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
+        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
+        return views, peak[:n], clipped[:n]

@@ -255,6 +255,83 @@ int RRX_debug_finish_host(int src_format, const void *src, size_t src_stride, in
  * output. */
 int RRX_edge_geometry(size_t in_rate, size_t out_rate, size_t *n_add, size_t *n_drop, size_t *prime_len, size_t *inbuf);
 
+/* Ragged track batches: whole tracks of UNEQUAL length through one batch handle.  A batch handle's streams run in lock step, so
+ * the rows it is pushed from all have one length; a shorter track is followed by zeros up to the longest row.  Those zeros are
+ * what RR_drain would have fed a handle of its own, and the engine's output does not depend on how its input is cut into pushes,
+ * so over its own output range the track gets the bits of a one-stream handle that was drained after it.  What differs per
+ * track is where it lies: in the packed source, in its row (behind its own LPC extension), in its output row (behind the
+ * resampled image of that extension) and in the packed destination.  RRX_track says so, RRX_tracks_plan fills a table of them on
+ * the host, and the two device calls read that table from device memory.  All fields are in FRAMES. */
+typedef struct RRX_track {
+  unsigned long long src_first;  /* first frame of the track in the packed source            */
+  unsigned long long frames;     /* its length                                               */
+  unsigned long long lead;       /* where its frame 0 sits in its row: n_add, or 0           */
+  unsigned long long out_first;  /* first frame of its output in its output row: n_drop or 0 */
+  unsigned long long out_frames; /* frames of output it owns                                 */
+  unsigned long long dst_first;  /* first frame of its output in the packed destination      */
+} RRX_track;
+
+/* Host-only (no GPU needed): what the whole-track path does with ONE track of `frames` frames on a handle of its own
+ * (dsp_rate::on_chunk / flushwrite, foo_dsp_rate.cpp:154-168, 218-313).  More than 2 * LPC_ORDER = 64 frames: *lead = n_add frames
+ * of extrapolation in front of it and as many behind it, *ext_frames = frames + 2 * n_add, *out_first = n_drop (RRX_edge_geometry).
+ * Up to 64 frames (zero included): *lead = 0, *ext_frames = frames, *out_first = 0.  *out_frames = max(T - 2 * *out_first, 0), where
+ * T is what a handle yields in all for *ext_frames frames pushed in RRX_isamp_max pieces and drained -- computed from the handle's
+ * own counter arithmetic, the wrap of rate_input's counters by whole seconds included (rate_base.h:436-441, 454-468), not from a
+ * closed form.  A zero-length track owns no output.
+ * Returns RR_INVPARAM for a NULL argument, a config the planner refuses, or frames above 2^36 (the call walks the track's pushes). */
+int RRX_track_geometry(const RR_config *config, size_t frames, size_t *lead, size_t *ext_frames, size_t *out_first,
+                       size_t *out_frames);
+/* Host-only: the table for `ntracks` tracks of frames[t] frames, packed in that order.  table[t] is RRX_track_geometry's answer for
+ * frames[t]; src_first and dst_first are the running sums of frames and out_frames.  *row_frames = the largest ext_frames: the
+ * length of the rows the handle is pushed from.  *out_row_cap = *row_frames * out_rate / in_rate + 2: output frames a row can
+ * give, the pitch to allocate for the output rows.  *src_total / *dst_total = frames of the packed source / destination.
+ * Returns RR_INVPARAM for a NULL argument, ntracks < 1, a config the planner refuses, a track above 2^36 frames, or sums that
+ * overflow. */
+int RRX_tracks_plan(const RR_config *config, const size_t *frames, int ntracks, RRX_track *table, size_t *row_frames,
+                    size_t *out_row_cap, size_t *src_total, size_t *dst_total);
+
+/* One pass from the packed tracks (d_packed: [src_total][nch] float32) to the rows a batch handle is pushed from (d_rows:
+ * [ntracks][row_frames][nch]).  Row t receives, with ext = lead + frames + lead:
+ *   [lead, lead + frames)        the track, copied;
+ *   [0, lead)                    RRX_lpc_extrapolate_device's backward extension from its first min(frames, prime_len) frames;
+ *   [lead + frames, ext)         its forward extension from the track's last min(frames, prime_len) frames -- both with
+ *                                lpc_order 32 and bit for bit what that call writes (the kernels share one body);
+ *   [ext, row_frames)            zeros.
+ * Every frame of every row is written exactly once, nothing outside the rows is written, and d_packed is only read.  in_rate and
+ * out_rate fix prime_len (RRX_edge_geometry).
+ * d_tracks is DEVICE memory (a copy of RRX_tracks_plan's table) and a call that never synchronises cannot validate it.  So the
+ * kernels clamp instead: what a track reads is clamped to [0, src_total) (frames past it read as zeros) and what it writes to its
+ * own row (lead, frames and the extension are cut to row_frames).  A wrong table gives wrong samples, never an access outside
+ * the buffers.
+ * device, hip_stream, stream ordering: RRX_lpc_extrapolate_device's, word for word.  The call only enqueues (no allocation, no
+ * host synchronisation) and restores the caller's device on return.
+ * Returns RR_INVPARAM, before any device is touched, for a NULL pointer, ntracks < 1, nch < 1, a zero rate, row_frames == 0,
+ * ntracks * nch of 2^30 or more, a size no buffer has (src_total * nch or ntracks * row_frames * nch of 2^60 samples or more) or
+ * device < -1; RR_EXTUNINIT before init_ratelib or for a device that is not gfx950; RR_INVPARAM for a device index the process does
+ * not have; RR_INTERNAL for a failed launch.  Float32 only, as RRX_lpc_extrapolate_device. */
+int RRX_tracks_stage_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks,
+                            int nch, const fb_sample_t *d_packed, size_t src_total, fb_sample_t *d_rows, size_t row_frames);
+
+/* RRX_finish_device per track in one call.  Track t takes frames [out_first, out_first + out_frames) of row t of d_rows
+ * ([ntracks][row_frames][nch], float32 or float64: row_frames is here the pitch of the OUTPUT rows, RRX_tracks_plan's
+ * out_row_cap) to frames [dst_first, dst_first + out_frames) of the packed destination d_dst ([dst_total][nch] of RRX_FMT_S16,
+ * RRX_FMT_S24_3 or RRX_FMT_S32).  The arithmetic is RRX_finish_device's with stream s = t, first_frame = 0 and frame i counted
+ * from the track's own first output frame; d_gain [ntracks], d_peak and d_clipped [ntracks * nch] are per track as they are per
+ * stream there, and accumulate as there.  So track t's bytes and statistics are those of a one-stream RRX_finish_device call on
+ * its slice with seed + t * nch * 0xBF58476D1CE4E5B9 (mod 2^64) for seed.  The statistics cover the track's own frames and
+ * nothing else of its row.  d_dst NULL measures only (dst_format and dst_total are ignored).  Tracks are adjacent in the
+ * destination, at any byte offset; no byte of a neighbouring track and no byte beyond dst_total frames is touched.
+ * d_tracks is device memory and is clamped as in RRX_tracks_stage_device: a track's slice is cut to its row and (when written)
+ * to the destination, so a wrong table gives wrong samples, never an access outside the buffers.
+ * device, hip_stream, refusals: RRX_finish_device's -- RR_INVPARAM, before any device is touched, for a NULL table or source,
+ * ntracks < 1, nch < 1, an unknown source format, an unknown destination format (d_dst not NULL), d_dst, d_peak and d_clipped
+ * all NULL, ntracks * row_frames * nch or (d_dst not NULL) dst_total * nch of 2^60 samples or more, or device < -1.
+ * row_frames == 0 is RR_OK and does nothing. */
+int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                             const void *d_rows, size_t row_frames, int dst_format, void *d_dst, size_t dst_total,
+                             const double *d_gain, int dither, unsigned long long seed, double *d_peak,
+                             unsigned long long *d_clipped);
+
 /* Introspection: isamp_max of rate_base.h:531, frames currently pullable (fifo_occupancy of the last
  * fifo, rate_base.h:447-448), shape of the handle. */
 size_t RRX_isamp_max(const RR_handle *h);
