@@ -722,11 +722,29 @@ int check_device(int device)
 
 } // namespace
 
+namespace {
+
+// RRX_FMT_* of a packed source -> rsmp::TracksSrc, or -1: RRX_FMT_DOUBLE is no source of the stage pass (the rows are float32)
+int tracks_src_kind(int src_format)
+{
+  switch (src_format) {
+  case RRX_FMT_FLOAT: return rsmp::kTracksSrcF32;
+  case RRX_FMT_S16: return rsmp::kTracksSrcS16;
+  case RRX_FMT_S24_3: return rsmp::kTracksSrcS24;
+  case RRX_FMT_S32: return rsmp::kTracksSrcS32;
+  default: return -1;
+  }
+}
+
+} // namespace
+
 // The stage pass of a ragged batch (tracks.hip).  Refusals first, as in RRX_lpc_extrapolate_device.
-int RRX_tracks_stage_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks, int nch,
-                            const fb_sample_t *d_packed, size_t src_total, fb_sample_t *d_rows, size_t row_frames)
+int RRX_tracks_stage_device_samples(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks,
+                                    int nch, int src_format, const void *d_packed, size_t src_total, fb_sample_t *d_rows, size_t row_frames)
 {
   static_assert(sizeof(RRX_track) == sizeof(rsmp::Track) && sizeof(RRX_track) == 6 * sizeof(unsigned long long), "RRX_track mirrors rsmp::Track");
+  const int kind = tracks_src_kind(src_format);
+  if (kind < 0) return RR_INVPARAM;
   if (!d_tracks || !d_packed || !d_rows || ntracks < 1 || nch < 1 || !in_rate || !out_rate || !row_frames) return RR_INVPARAM;
   if (device < -1 || (long long)ntracks * nch > 0x3fffffffLL) return RR_INVPARAM; // (two workgroups per channel of every track)
   // no buffer has 2^60 samples: with that no offset the kernels compute can wrap
@@ -748,7 +766,25 @@ int RRX_tracks_stage_device(int device, void *hip_stream, size_t in_rate, size_t
   a.ntracks = ntracks;
   a.nch = nch;
   a.prime_len = int(prime);
+  a.src_kind = kind;
   return rsmp::launch_tracks_stage(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_tracks_stage_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks, int nch,
+                            const fb_sample_t *d_packed, size_t src_total, fb_sample_t *d_rows, size_t row_frames)
+{
+  return RRX_tracks_stage_device_samples(device, hip_stream, in_rate, out_rate, d_tracks, ntracks, nch, RRX_FMT_FLOAT, d_packed, src_total,
+                                         d_rows, row_frames);
+}
+
+// Test hook: the conversion of RRX_tracks_stage_device_samples on host memory, a serial loop over the function the kernels call
+int RRX_debug_tracks_load_host(int src_format, const void *src, size_t first_sample, size_t count, float *out)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  const int kind = tracks_src_kind(src_format);
+  if (kind < 0 || !src || !out) return RR_INVPARAM;
+  for (size_t i = 0; i < count; ++i) out[i] = rsmp::tracks_load_sample(kind, src, first_sample + i);
+  return RR_OK;
 }
 
 // The output stage of a ragged batch (tracks.hip).  Refusals first, as in RRX_finish_device.

@@ -1,6 +1,6 @@
 // Ragged track batches: the kernels around a batch handle whose streams hold tracks of unequal length.
 //
-// Stage (RRX_tracks_stage_device): packed tracks [sum of frames][nch] -> rows [ntracks][row_frames][nch].  Row t is
+// Stage (RRX_tracks_stage_device_samples): packed tracks [sum of frames][nch] -> rows [ntracks][row_frames][nch].  Row t is
 //   [0, lead)                      backward LPC extension from the track's first min(frames, prime_len) frames   tracks_lpc_kernel
 //   [lead, lead + frames)          the track                                                                       tracks_copy_kernel
 //   [lead + frames, ext)           forward LPC extension from its last min(frames, prime_len) frames             tracks_lpc_kernel
@@ -12,6 +12,12 @@
 // of the DESTINATION, groups of 4 samples (one lane each: 16 bytes loaded, which needs dword alignment only, 16 aligned bytes
 // stored) and a tail of 0..3 samples; a group that straddles two regions goes sample by sample.  The two kernels write disjoint
 // frames and read only the source, so their order does not matter.
+// Both are templates on what the packed source holds (TracksSrc, tracks.hpp): float32, or S16 / packed 3-byte S24 / S32 PCM, which
+// is converted on load by tracks_load_sample's rule; everything about the rows is the same.  An integer group is 8, 12 or 16 source
+// bytes at sample alignment (tracks are adjacent, so for S24 at any byte offset): the lane loads the 2 to 4 aligned dwords that
+// cover them, realigns by the track's misalignment (one value per workgroup), unpacks and converts (unpack4).  So the group path may
+// read the whole aligned dword that holds the first or the last byte of the source, and nothing further out; the sample-by-sample
+// paths and the LPC loads read exactly their samples' bytes.
 //
 // Output stage (RRX_tracks_finish_device): finish_sample (finish.hpp) per track, finish.hip's shape with a per-track prologue --
 // grid = (chunk of a row, track), head / groups of 4 / tail decided per track from where ITS bytes begin in the packed
@@ -49,8 +55,20 @@ struct Entry {
   }
 };
 
-__global__ __launch_bounds__(64) void tracks_lpc_kernel(TracksStageArgs a)
+// The packed source as the kernels address it: floats as floats (the float instances are the kernels they were before the
+// integer sources came), integer PCM as bytes, kStep of them a sample
+template <int kSrc> struct Src {
+  typedef unsigned char T;
+  static constexpr u64 kStep = tracks_src_bytes(kSrc);
+};
+template <> struct Src<kTracksSrcF32> {
+  typedef float T;
+  static constexpr u64 kStep = 1;
+};
+
+template <int kSrc> __global__ __launch_bounds__(64) void tracks_lpc_kernel(TracksStageArgs a)
 {
+  typedef typename Src<kSrc>::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char tracks_lds[];
   const int lane = threadIdx.x, edge = blockIdx.x & 1, nch = a.nch;
   const u64 t = (blockIdx.x >> 1) / (unsigned)nch, ch = (blockIdx.x >> 1) % (unsigned)nch;
@@ -60,32 +78,68 @@ __global__ __launch_bounds__(64) void tracks_lpc_kernel(TracksStageArgs a)
   const long long n = (long long)min_u(e.frames, (u64)a.prime_len);      // base frames: the track's first n, or its last n
   const u64 base = edge ? e.frames - (u64)n : 0;
   const long long readable = e.have > base ? (long long)(e.have - base) : 0; // (all n of them, unless the table is wrong)
-  const float *x = a.src + (e.first + min_u(base, e.have)) * nch + ch;
+  // base frame 0 of this channel: strided single samples, read once (into LDS) through tracks_load_sample
+  const T *x = static_cast<const T *>(a.src) + ((e.first + min_u(base, e.have)) * nch + ch) * Src<kSrc>::kStep;
   float *y = a.rows + ((t * a.row_frames + e.lead + base) * nch + ch);
   if (n <= kLpcMaxOrder) { // no table of RRX_tracks_plan: a lead means more than 64 frames.  Zeros, so that the row is written all the same.
     for (long long i = lane; i < extra; i += 64) y[(edge ? n + i : -1 - i) * nch] = 0.0f;
     return;
   }
   lpc_channel<true>(tracks_lds, lane, n, (float)(n + 1) / 2.0f, kLpcMaxOrder, edge ? 0 : extra, edge ? extra : 0,
-                    [=](long long i) { return i < readable ? x[i * nch] : 0.0f; }, [=](long long i, float v) { y[i * nch] = v; });
+                    [=](long long i) { return i < readable ? tracks_load_sample(kSrc, x, (u64)(i * nch)) : 0.0f; },
+                    [=](long long i, float v) { y[i * nch] = v; });
 }
 
-__global__ __launch_bounds__(kThreads) void tracks_copy_kernel(TracksStageArgs a, int t0, int steps)
+// Four consecutive samples of an integer source as integers, from the aligned dwords that cover them: the inverse of Pack<bits>
+// (below).  p is the address of the first sample, mis = p & 3 -- the same for every group of a track, because a group is 8, 12 or
+// 16 bytes further than the one before, and so decided once per workgroup: the branches on it are wave-uniform.  Reads
+// [p - mis, p - mis + 4 * ceil((mis + bytes) / 4)): no dword that does not hold a byte of the group.
+template <int kSrc> __device__ __forceinline__ void unpack4(const unsigned char *p, unsigned mis, int *q)
 {
+  const unsigned *w = reinterpret_cast<const unsigned *>(p - mis); // dword aligned
+  const unsigned sh = mis * 8;
+  unsigned v[4] = {0u, 0u, 0u, 0u}, d[3];
+  if (kSrc == kTracksSrcS16) {
+    if (mis) __builtin_memcpy(v, w, 12);
+    else __builtin_memcpy(v, w, 8);
+    for (int j = 0; j < 2; ++j) d[j] = __builtin_amdgcn_alignbit(v[j + 1], v[j], sh);
+    q[0] = (short)d[0];
+    q[1] = (int)d[0] >> 16;
+    q[2] = (short)d[1];
+    q[3] = (int)d[1] >> 16;
+  } else if (kSrc == kTracksSrcS24) {
+    if (mis) __builtin_memcpy(v, w, 16);
+    else __builtin_memcpy(v, w, 12);
+    for (int j = 0; j < 3; ++j) d[j] = __builtin_amdgcn_alignbit(v[j + 1], v[j], sh);
+    q[0] = (int)(d[0] << 8) >> 8;
+    q[1] = (int)(__builtin_amdgcn_alignbit(d[1], d[0], 24) << 8) >> 8;
+    q[2] = (int)(__builtin_amdgcn_alignbit(d[2], d[1], 16) << 8) >> 8;
+    q[3] = (int)d[2] >> 8;
+  } else {
+    __builtin_memcpy(q, p, 16); // S32: dword aligned as it is
+  }
+}
+
+template <int kSrc> __global__ __launch_bounds__(kThreads) void tracks_copy_kernel(TracksStageArgs a, int t0, int steps)
+{
+  typedef typename Src<kSrc>::T T;
+  constexpr u64 kStep = Src<kSrc>::kStep;
   const unsigned tid = threadIdx.x;
   const u64 t = (u64)(t0 + (int)blockIdx.y), nch = (u64)a.nch, n = a.row_frames * nch; // n: samples of a row
   const Entry e(a, t);
   // in samples of the row: [c0, c1) is the track, [z0, n) the zeros; what lies between belongs to tracks_lpc_kernel
   const u64 c0 = e.lead * nch, c1 = c0 + e.frames * nch, z0 = c1 + e.fwd * nch, have = e.have * nch;
-  const float *s = a.src + e.first * nch; // sample j of the track, j < have
+  const T *s = static_cast<const T *>(a.src) + e.first * nch * kStep; // sample j of the track, j < have, is kStep * j further
   float *row = a.rows + t * n;
   auto one = [&](u64 k) {
-    if (k >= c0 && k < c1) row[k] = k - c0 < have ? s[k - c0] : 0.0f;
+    if (k >= c0 && k < c1) row[k] = k - c0 < have ? tracks_load_sample(kSrc, s, k - c0) : 0.0f;
     else if (k >= z0) row[k] = 0.0f;
   };
   u64 head = ((16 - (reinterpret_cast<u64>(row) & 15)) & 15) >> 2; // samples in front of the row's first 16-byte boundary
   if (head > n) head = n;
   const u64 ngroups = (n - head) >> 2;
+  // where the groups of this track begin within a dword of the source (integer sources; see unpack4)
+  const unsigned mis = kSrc == kTracksSrcS16 || kSrc == kTracksSrcS24 ? (unsigned)(reinterpret_cast<u64>(s) + (head - c0) * kStep) & 3u : 0u;
   if (blockIdx.x == 0) { // head and tail samples, one lane each
     const u64 ntail = n - head - (ngroups << 2);
     if (tid < head) one(tid);
@@ -96,8 +150,16 @@ __global__ __launch_bounds__(kThreads) void tracks_copy_kernel(TracksStageArgs a
     if (g >= ngroups) break;
     const u64 k = head + (g << 2);
     float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (k >= c0 && k + 4 <= c1 && k - c0 + 4 <= have) __builtin_memcpy(v, s + (k - c0), sizeof(v)); // 16 bytes, dword aligned
-    else if (k + 4 <= c0 || (k >= c1 && k + 4 <= z0)) continue;                                    // extension frames only
+    if (k >= c0 && k + 4 <= c1 && k - c0 + 4 <= have) {
+      if (kSrc == kTracksSrcF32) {
+        __builtin_memcpy(v, s + (k - c0) * kStep, sizeof(v)); // 16 bytes, dword aligned
+      } else { // the aligned dwords that cover the group, realigned, unpacked, sign-extended, converted
+        constexpr float scale = kSrc == kTracksSrcS16 ? 0x1p-15f : kSrc == kTracksSrcS24 ? 0x1p-23f : 0x1p-31f;
+        int q[4];
+        unpack4<kSrc>(reinterpret_cast<const unsigned char *>(s + (k - c0) * kStep), mis, q);
+        for (int j = 0; j < 4; ++j) v[j] = (float)q[j] * scale;
+      }
+    } else if (k + 4 <= c0 || (k >= c1 && k + 4 <= z0)) continue; // extension frames only
     else if (k < z0) { // a group across two regions, or the track's frames that a wrong table puts past the source
       for (int j = 0; j < 4; ++j) one(k + j);
       continue;
@@ -320,9 +382,7 @@ template <typename S> hipError_t finish_src(hipStream_t stream, const TracksFini
   }
 }
 
-} // namespace
-
-hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a)
+template <int kSrc> hipError_t stage_typed(hipStream_t stream, const TracksStageArgs &a)
 {
   // copy and zero fill: 8 steps of 256 groups (32 KiB written) per workgroup, more only to stay inside the grid limit
   const u64 groups = (a.row_frames * (u64)a.nch + 3) / 4 + 1; // (+1: the head can move the last samples into one more group)
@@ -331,17 +391,30 @@ hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a)
   const unsigned gx = (unsigned)((groups + steps * kThreads - 1) / (steps * kThreads));
   for (int t0 = 0; t0 < a.ntracks; t0 += 32768) { // grid.y is a 16-bit count
     const int nt = a.ntracks - t0 < 32768 ? a.ntracks - t0 : 32768;
-    hipLaunchKernelGGL(tracks_copy_kernel, dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, t0, (int)steps);
+    hipLaunchKernelGGL(tracks_copy_kernel<kSrc>, dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, t0, (int)steps);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   // the two extensions of every (track, channel)
-  static DynLdsOnce once;
-  const hipError_t e = once.set(reinterpret_cast<const void *>(&tracks_lpc_kernel), int(sizeof(LpcShared) + kLpcLdsFrames * sizeof(float)));
+  static DynLdsOnce once; // (one per instance)
+  const hipError_t e = once.set(reinterpret_cast<const void *>(&tracks_lpc_kernel<kSrc>), int(sizeof(LpcShared) + kLpcLdsFrames * sizeof(float)));
   if (e != hipSuccess) return e;
   const size_t lds = sizeof(LpcShared) + size_t(a.prime_len) * sizeof(float);
-  hipLaunchKernelGGL(tracks_lpc_kernel, dim3((unsigned)((long long)a.ntracks * a.nch * 2)), dim3(64), lds, stream, a);
+  hipLaunchKernelGGL(tracks_lpc_kernel<kSrc>, dim3((unsigned)((long long)a.ntracks * a.nch * 2)), dim3(64), lds, stream, a);
   return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a)
+{
+  switch (a.src_kind) {
+  case kTracksSrcF32: return stage_typed<kTracksSrcF32>(stream, a);
+  case kTracksSrcS16: return stage_typed<kTracksSrcS16>(stream, a);
+  case kTracksSrcS24: return stage_typed<kTracksSrcS24>(stream, a);
+  case kTracksSrcS32: return stage_typed<kTracksSrcS32>(stream, a);
+  default: return hipErrorInvalidValue; // a missing kernel is an error, never another kernel
+  }
 }
 
 hipError_t launch_tracks_finish(hipStream_t stream, const TracksFinishArgs &a)

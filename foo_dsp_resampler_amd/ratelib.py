@@ -22,12 +22,13 @@ EXPECTED_SYMBOLS = [
     "RRX_lpc_extrapolate_device", "RRX_edge_geometry",
     "RRX_finish_device", "RRX_debug_finish_host",
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
+    "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
 RRX_FMT_FLOAT, RRX_FMT_DOUBLE = 0, 1  # sample formats of a handle (ratelib_amd.h)
 RRX_FMT_S16, RRX_FMT_S32 = 16, 32      # interleaved signed integer PCM (24-bit audio left-justified in S32)
-RRX_FMT_S24_3 = 24                     # packed 3-byte PCM: a destination of finish_device only, never a handle format
+RRX_FMT_S24_3 = 24                     # packed 3-byte PCM: a destination of finish_device and a source of tracks_stage_device, never a handle format
 _FMT_DTYPE = {RRX_FMT_FLOAT: np.dtype(np.float32), RRX_FMT_DOUBLE: np.dtype(np.float64), RRX_FMT_S16: np.dtype(np.int16),
               RRX_FMT_S32: np.dtype(np.int32)}
 _DTYPE_FMT = {d: f for f, d in _FMT_DTYPE.items()}
@@ -192,6 +193,9 @@ def lib():
             L.RRX_tracks_plan.argtypes = [P(RRConfig), P(sz), C.c_int, P(RRXTrack), P(sz), P(sz), P(sz), P(sz)]
             L.RRX_tracks_stage_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, vp, sz, vp, sz]
             L.RRX_tracks_finish_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, sz, vp, C.c_int, u64, vp, vp]
+        if hasattr(L, "RRX_tracks_stage_device_samples"):  # (as above)
+            L.RRX_tracks_stage_device_samples.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, sz]
+            L.RRX_debug_tracks_load_host.argtypes = [C.c_int, vp, sz, sz, vp]
         _lib = L
     return _lib
 
@@ -390,16 +394,29 @@ def _tracks_table(table, ntracks=None):
     return table.shape[0]
 
 
+def _tracks_src_format(dtype):
+    """the RRX_FMT_* a packed source of this torch dtype is staged as, or None: uint8 means packed 3-byte S24"""
+    return {"torch.float32": RRX_FMT_FLOAT, "torch.int16": RRX_FMT_S16, "torch.int32": RRX_FMT_S32, "torch.uint8": RRX_FMT_S24_3}.get(str(dtype))
+
+
 def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, stream=None):
-    """The stage pass of a ragged batch on the device (RRX_tracks_stage_device): `packed` is a contiguous float32 device tensor
-    [src_total, nch] of tracks laid end to end, `table` the device copy of a plan's table (TracksPlan.to_device).  Returns the rows
-    the handle is pushed from, float32 [ntracks, row_frames, nch] (`out`, or a new tensor): each track behind and in front of
-    its own LPC extension, zeros behind it.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
+    """The stage pass of a ragged batch on the device (RRX_tracks_stage_device_samples): `packed` is a contiguous device tensor of
+    tracks laid end to end -- float32, int16 (RRX_FMT_S16) or int32 (RRX_FMT_S32) [src_total, nch], or uint8 [src_total, nch * 3]
+    (RRX_FMT_S24_3: packed little-endian 24 bit, the layout tracks_finish_device returns for that format) -- and `table` the device
+    copy of a plan's table (TracksPlan.to_device).  Integer PCM is converted on load, x = s * 2^-15 / 2^-23 / 2^-31 rounded once
+    to float32 (ratelib_amd.h), so no float32 copy of the source is needed.  Returns the rows the handle is pushed from, float32
+    [ntracks, row_frames, nch] whatever the source is (`out`, or a new tensor): each track behind and in front of its own LPC
+    extension, zeros behind it.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
     import torch
-    if packed.dim() != 2 or packed.dtype != torch.float32 or not packed.is_cuda or not packed.is_contiguous():
-        raise TypeError("packed must be a contiguous float32 device tensor [frames, nch]")
+    fmt = _tracks_src_format(packed.dtype)
+    if packed.dim() != 2 or fmt is None or not packed.is_cuda or not packed.is_contiguous():
+        raise TypeError("packed must be a contiguous float32, int16 or int32 device tensor [frames, nch], or uint8 [frames, nch * 3]")
     ntracks = _tracks_table(table)
     src_total, nch = packed.shape
+    if fmt == RRX_FMT_S24_3:
+        if nch % 3 or not nch:
+            raise ValueError("a uint8 source is packed 24-bit PCM [frames, nch * 3]; its last dimension is %d" % nch)
+        nch //= 3
     shape = (ntracks, int(row_frames), nch)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=packed.device)
@@ -409,12 +426,12 @@ def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, 
         raise TypeError("the table must be on %s" % (packed.device,))
     _ensure_init()
     if not src_total:  # (nothing but zero-length tracks: the call still wants a pointer, and never reads through it)
-        packed = torch.zeros((1, nch), dtype=torch.float32, device=packed.device)
+        packed = torch.zeros((1, packed.shape[1]), dtype=packed.dtype, device=packed.device)
     ptr = getattr(stream, "cuda_stream", stream) or 0
     index = packed.device.index
-    _check(lib().RRX_tracks_stage_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
-                                         C.c_void_p(table.data_ptr()), ntracks, nch, C.c_void_p(packed.data_ptr()), src_total,
-                                         C.c_void_p(out.data_ptr()), int(row_frames)), "RRX_tracks_stage_device")
+    _check(lib().RRX_tracks_stage_device_samples(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
+                                                 C.c_void_p(table.data_ptr()), ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total,
+                                                 C.c_void_p(out.data_ptr()), int(row_frames)), "RRX_tracks_stage_device_samples")
     return out
 
 
@@ -836,17 +853,23 @@ class Resampler:
         tracks = list(tracks)
         if not 1 <= len(tracks) <= self.nstreams:
             raise ValueError("expected 1 to %d tracks (the handle's streams), got %d" % (self.nstreams, len(tracks)))
+        dt = tracks[0].dtype
+        if _tracks_src_format(dt) is None:
+            raise TypeError("expected float32, int16, int32 or uint8 (packed 24-bit) tensors, not %s" % dt)
+        last = self.nch * 3 if dt == torch.uint8 else self.nch
         for x in tracks:
-            if x.dim() != 2 or x.shape[1] != self.nch:
-                raise ValueError("expected [frames, %d] tensors, got shape %r" % (self.nch, tuple(x.shape)))
-            if x.dtype != torch.float32 or not x.is_cuda or x.device.index != self.device:
-                raise TypeError("expected torch.float32 tensors on the handle's device (cuda:%d)" % self.device)
+            if x.dtype != dt:
+                raise TypeError("the tracks of one call share a dtype: %s and %s" % (dt, x.dtype))
+            if x.dim() != 2 or x.shape[1] != last:
+                raise ValueError("expected [frames, %d] %s tensors, got shape %r" % (last, dt, tuple(x.shape)))
+            if not x.is_cuda or x.device.index != self.device:
+                raise TypeError("expected tensors on the handle's device (cuda:%d)" % self.device)
         dev = tracks[0].device
         # the streams without a track are zero-length tracks: they own no output
         plan = _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
         table = plan.to_device(dev)
         total, cap = plan.row_frames, plan.out_row_cap
-        out = tracks[0].new_empty((self.nstreams, cap, self.nch))
+        out = torch.empty((self.nstreams, cap, self.nch), dtype=torch.float32, device=dev)  # (the handle's rows are float32 whatever the tracks are)
         if not total:  # nothing but zero-length tracks
             return plan, table, out
         cur = torch.cuda.current_stream(dev)
@@ -881,7 +904,10 @@ class Resampler:
 
     def convert_tracks_device(self, tracks):
         """Whole tracks of UNEQUAL length, one per stream, device to device: convert_track_device for a ragged batch.  `tracks`
-        is a list of float32 device tensors [frames_i, nch], at most `nstreams` of them (the streams left over run empty).
+        is a list of float32 device tensors [frames_i, nch], at most `nstreams` of them (the streams left over run empty) -- or of
+        integer PCM as it is stored: all int16, all int32, or all uint8 [frames_i, nch * 3] (packed 24 bit), which the stage pass
+        converts on load (tracks_stage_device); mixed dtypes raise TypeError.  The handle is a float32 handle and the result is
+        float32 either way.
 
         The tracks are planned (tracks_plan), packed end to end, staged into rows of the longest extended length -- each with the
         LPC extension at its own two ends and zeros behind it (tracks_stage_device) -- and the rows are pushed in isamp_max
@@ -895,7 +921,9 @@ class Resampler:
 
     def convert_tracks_to_pcm_device(self, tracks, dst_format, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
-        packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  Returns (list of per-track
+        packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  The tracks may be integer PCM
+        themselves (int16, int32, or uint8 packed 24 bit, as in convert_tracks_device): PCM in, PCM out, with float32 only in the
+        rows the handle is pushed from.  Returns (list of per-track
         views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views."""
         import torch
         tracks = list(tracks)

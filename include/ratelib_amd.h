@@ -218,7 +218,8 @@ int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data
  * far, gets the bits of one call.
  *   src_format: RRX_FMT_FLOAT or RRX_FMT_DOUBLE.
  *   dst_format: RRX_FMT_S16, RRX_FMT_S32, or RRX_FMT_S24_3: three bytes a sample, little endian, two's complement (WAV's packed
- *   24 bit).  RRX_FMT_S24_3 is a buffer format of this call only, never a handle format: RRX_open_batch_fmt refuses it.
+ *   24 bit).  RRX_FMT_S24_3 is a buffer format (here, in RRX_tracks_finish_device and as a source of
+ *   RRX_tracks_stage_device_samples), never a handle format: RRX_open_batch_fmt refuses it.
  *   d_dst NULL: measure only -- nothing is written, dst_format and dst_stride are ignored, and the statistics are those of the
  *   RRX_FMT_S32 quantiser (bits = 31).
  *   d_peak (double) / d_clipped: [nstreams * nch] each, on the device, either may be NULL.  The call ACCUMULATES into what they
@@ -236,7 +237,7 @@ int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data
  * or device < -1; RR_EXTUNINIT before init_ratelib; RR_INVPARAM for a device index the process does not have; RR_INTERNAL for
  * a failed launch.  frames == 0 is RR_OK and does nothing.  Noise shaping, integer or planar sources and float destinations are
  * not offered. */
-#define RRX_FMT_S24_3 24   /* packed 3-byte signed 24-bit PCM: RRX_finish_device's destination only */
+#define RRX_FMT_S24_3 24   /* packed 3-byte signed 24-bit PCM: RRX_finish_device's destination only, and a source format of RRX_tracks_stage_device_samples */
 int RRX_finish_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
                       int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
                       const double *d_gain, int dither, unsigned long long seed, unsigned long long first_frame,
@@ -308,9 +309,37 @@ int RRX_tracks_plan(const RR_config *config, const size_t *frames, int ntracks, 
  * Returns RR_INVPARAM, before any device is touched, for a NULL pointer, ntracks < 1, nch < 1, a zero rate, row_frames == 0,
  * ntracks * nch of 2^30 or more, a size no buffer has (src_total * nch or ntracks * row_frames * nch of 2^60 samples or more) or
  * device < -1; RR_EXTUNINIT before init_ratelib or for a device that is not gfx950; RR_INVPARAM for a device index the process does
- * not have; RR_INTERNAL for a failed launch.  Float32 only, as RRX_lpc_extrapolate_device. */
+ * not have; RR_INTERNAL for a failed launch.  Float32 sources only: this is the RRX_FMT_FLOAT case of
+ * RRX_tracks_stage_device_samples, below, and the same code path. */
 int RRX_tracks_stage_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks,
                             int nch, const fb_sample_t *d_packed, size_t src_total, fb_sample_t *d_rows, size_t row_frames);
+
+/* RRX_tracks_stage_device from a packed source of integer PCM, audio as it is stored: the stage pass converts on load, so no
+ * float32 copy of the source is ever written.  src_format is RRX_FMT_FLOAT (d_packed: [src_total][nch] float32, RRX_tracks_stage_device
+ * itself), RRX_FMT_S16, RRX_FMT_S32, or RRX_FMT_S24_3 (three bytes a sample, little endian, two's complement, sign-extended:
+ * [src_total][nch * 3] bytes).  The rows are float32 whatever the source is -- the LPC arithmetic is float32, and so are the handles
+ * they are pushed to -- which is why RRX_FMT_DOUBLE is no source format of this call.
+ * The conversion is part of this ABI.  For a source sample s, with bits = 15 (S16), 23 (S24_3) or 31 (S32):
+ *   x = (float)((double)s * 2^-bits)        one rounding, to nearest even
+ * which is exact for S16 and S24_3; S32 is rounded to float32's 24 bits, and INT32_MAX becomes 1.0f.  ((float)s rounded to nearest
+ * even and then scaled by the power of two gives the same bits.)  Copied frames and the base frames of both LPC extensions are
+ * converted by this one rule, so the rows equal, bit for bit, those of RRX_tracks_stage_device on the converted source.
+ * Reads: d_packed needs the alignment of one sample (2 bytes for S16, 1 byte for S24_3, 4 for S32 and float32).  Tracks are adjacent,
+ * so a track begins at any sample, for S24_3 at any byte offset.  No byte outside [d_packed, d_packed + src_total * nch * bytes) is
+ * relied on; the copy kernel loads whole aligned dwords, so it may READ the aligned dword that holds the first byte of the source and
+ * the one that holds its last byte in full (up to 3 bytes on either side, in the same page: this cannot fault), and nothing further
+ * out.  The table clamps are RRX_tracks_stage_device's: frames past src_total read as zeros.
+ * Everything else -- what row t receives, "every frame of every row is written exactly once, nothing outside the rows is written,
+ * d_packed is only read", the unvalidated device table, device, hip_stream, stream ordering, "only enqueues", every refusal and
+ * return value -- is RRX_tracks_stage_device's, word for word; an src_format other than those four (RRX_FMT_DOUBLE included)
+ * returns RR_INVPARAM before any device is touched. */
+int RRX_tracks_stage_device_samples(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks,
+                                    int ntracks, int nch, int src_format, const void *d_packed, size_t src_total,
+                                    fb_sample_t *d_rows, size_t row_frames);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the conversion above for samples
+ * [first_sample, first_sample + count) of a HOST buffer of src_format, as one serial loop over the very per-sample function the
+ * kernels call.  RR_INVPARAM for an unknown format or a NULL pointer. */
+int RRX_debug_tracks_load_host(int src_format, const void *src, size_t first_sample, size_t count, float *out);
 
 /* RRX_finish_device per track in one call.  Track t takes frames [out_first, out_first + out_frames) of row t of d_rows
  * ([ntracks][row_frames][nch], float32 or float64: row_frames is here the pitch of the OUTPUT rows, RRX_tracks_plan's

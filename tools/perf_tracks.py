@@ -23,6 +23,23 @@ plans); medians are reported.  One JSON line, appended to --out
    "ragged_over_uniform", "rounds"}
 
   python tools/perf_tracks.py [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
+
+--pcm measures the integer sources of the stage pass instead ("Integer sources"), on the same workload, and appends
+to profiles/tracks_pcm_perf.jsonl.  Stage only, per source format S16 / S24_3 / S32, from the packed integer tracks in HBM to the
+float32 rows in HBM:
+
+  (a) int_stage       tracks_stage_device on the integer source: one pass;
+  (b) torch_then_f32  what a caller writes without it: a torch pass that converts the packed source to a float32 copy (S16 / S32:
+                      ONE elementwise kernel, torch.mul(int tensor, 2^-bits); S24_3: the bytes widened, shifted, or-ed and scaled
+                      by torch ops), then tracks_stage_device on that copy.
+
+The rows of (a) and (b) are compared once, bit for bit, before anything is timed ("rows_equal").  Then convert_tracks_to_pcm_device
+end to end, S16 tracks to S16 against float32 tracks to S16, each on a fresh handle as above.  One warm-up, `--rounds` rounds
+interleaved, HIP events, medians.  One JSON line per format {"what": "stage", "src_format", "int_stage_ms", "torch_then_f32_ms",
+"torch_convert_ms": the conversion alone, "*_rounds", "int_over_torch": (a) / (b), "source_bytes", "row_bytes", "rows_equal"} and one
+{"what": "end_to_end", "s16_tracks_ms", "f32_tracks_ms", "s16_over_f32"}.
+
+  python tools/perf_tracks.py --pcm [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
 """
 import argparse
 import json
@@ -60,17 +77,143 @@ def timed(fn):
     return e0.elapsed_time(e1), r
 
 
+PCM = (("s16", F.RRX_FMT_S16, 15), ("s24_3", F.RRX_FMT_S24_3, 23), ("s32", F.RRX_FMT_S32, 31))
+
+
+def pcm_source(lens, bits, seed):
+    """packed integer tracks [frames_total, nch] at half of full scale (int64 would not fit beside the rows: made in pieces)"""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    total = sum(lens)
+    dt = torch.int16 if bits == 15 else torch.int32
+    out = torch.empty((total, NCH), dtype=dt, device="cuda")
+    half = 1 << (bits - 1)
+    for pos in range(0, total, 1 << 26):
+        n = min(1 << 26, total - pos)
+        out[pos:pos + n] = torch.randint(-half, half, (n, NCH), generator=g, device="cuda", dtype=torch.int32).to(dt)
+    return out
+
+
+def to_s24(v):
+    """int32 [frames, nch] in [-2^23, 2^23) -> packed bytes [frames, nch * 3]"""
+    out = torch.empty(v.shape + (3,), dtype=torch.uint8, device=v.device)
+    for k in range(3):
+        out[..., k] = (v >> (8 * k)) & 0xff
+    return out.view(v.shape[0], -1)
+
+
+def torch_convert(packed, fmt, bits):
+    """the float32 copy a caller makes with torch ops"""
+    if fmt != F.RRX_FMT_S24_3:
+        return torch.mul(packed, 2.0 ** -bits)               # one kernel: integer in, float32 out
+    b = packed.view(packed.shape[0], -1, 3)
+    v = b[..., 0].to(torch.int32) | (b[..., 1].to(torch.int32) << 8) | (b[..., 2].to(torch.int8).to(torch.int32) << 16)
+    return torch.mul(v, 2.0 ** -bits)
+
+
+def pcm_main(a, lens):
+    plan = F.tracks_plan(FS, FO, lens)
+    table = plan.to_device("cuda")
+    R = plan.row_frames
+    rows = torch.empty((len(lens), R, NCH), dtype=torch.float32, device="cuda")
+    lines = []
+    for name, fmt, bits in PCM:
+        v = pcm_source(lens, 23 if bits == 23 else bits, a.seed)
+        packed = to_s24(v) if bits == 23 else v
+        del v
+        f32 = [None]
+
+        def int_stage():
+            F.tracks_stage_device(packed, table, FS, FO, R, out=rows)
+
+        def convert():
+            f32[0] = None                                    # (the caching allocator hands the copy's memory back: no hipMalloc in a round)
+            f32[0] = torch_convert(packed, fmt, bits)
+
+        def torch_then_f32():
+            convert()
+            F.tracks_stage_device(f32[0], table, FS, FO, R, out=rows)
+
+        # warm-up, and the check that the two ways give the same rows
+        torch_then_f32()
+        want = rows.clone()
+        int_stage()
+        equal = bool(torch.equal(rows.view(torch.int32), want.view(torch.int32)))
+        del want
+        convert()
+        ways = {"int_stage": int_stage, "torch_then_f32": torch_then_f32, "torch_convert": convert}
+        ms = {k: [] for k in ways}
+        for _ in range(a.rounds):
+            for k, fn in ways.items():
+                ms[k].append(timed(fn)[0])
+        med = {k: statistics.median(t) for k, t in ms.items()}
+        line = {"what": "stage", "src_format": name, "seed": a.seed, "tracks": len(lens), "nch": NCH, "in_rate": FS, "out_rate": FO,
+                "frames_total": sum(lens), "row_frames": R, "source_bytes": packed.numel() * packed.element_size(),
+                "row_bytes": rows.numel() * 4, "rows_equal": equal}
+        for k in ways:
+            line[k + "_ms"] = round(med[k], 3)
+            line[k + "_ms_rounds"] = [round(t, 3) for t in ms[k]]
+        line.update({"int_over_torch": round(med["int_stage"] / med["torch_then_f32"], 3), "rounds": a.rounds})
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+        f32[0] = packed = None
+        torch.cuda.empty_cache()
+    del rows
+    torch.cuda.empty_cache()
+    # end to end: S16 tracks -> S16 against float32 tracks -> S16
+    v = pcm_source(lens, 15, a.seed)
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + n)
+    i16 = [v[offs[t]:offs[t + 1]] for t in range(len(lens))]
+    f32t = [torch.mul(x, 2.0 ** -15) for x in i16]
+
+    def end_to_end(tracks):
+        def run():
+            r = F.Resampler(FS, FO, nch=NCH, nstreams=len(tracks))
+            views, _, _ = r.convert_tracks_to_pcm_device(tracks, F.RRX_FMT_S16, dither=True, seed=a.seed)
+            r.close()
+            return [y.shape[0] for y in views]
+        return run
+
+    ways = {"s16_tracks": end_to_end(i16), "f32_tracks": end_to_end(f32t)}
+    first = {k: round(timed(fn)[0], 2) for k, fn in ways.items()}
+    ms = {k: [] for k in ways}
+    for _ in range(a.rounds):
+        for k, fn in ways.items():
+            t, got = timed(fn)
+            ms[k].append(t)
+            assert got == [int(e.out_frames) for e in plan.table], k
+    med = {k: statistics.median(t) for k, t in ms.items()}
+    line = {"what": "end_to_end", "dst_format": "s16", "seed": a.seed, "tracks": len(lens), "nch": NCH, "in_rate": FS, "out_rate": FO,
+            "frames_total": sum(lens), "row_frames": R}
+    for k in ways:
+        line[k + "_ms"] = round(med[k], 2)
+        line[k + "_ms_rounds"] = [round(t, 2) for t in ms[k]]
+    line.update({"first_call_ms": first, "s16_over_f32": round(med["s16_tracks"] / med["f32_tracks"], 3), "rounds": a.rounds})
+    lines.append(line)
+    print(json.dumps(line), flush=True)
+    with open(a.out, "a") as f:
+        for line in lines:
+            f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=20240229)
     ap.add_argument("--tracks", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tracks_perf.jsonl"))
+    ap.add_argument("--pcm", action="store_true", help="integer sources of the stage pass instead (see above)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("perf_tracks.py needs a GPU: there is nothing to time without one")
     lens = lengths(a.seed, a.tracks)
     print("seed %d: %d tracks, %.1f to %.1f s, %.1f s in all" % (a.seed, len(lens), min(lens) / FS, max(lens) / FS, sum(lens) / FS), flush=True)
+    if a.pcm:
+        return pcm_main(a, lens)
     plan = F.tracks_plan(FS, FO, lens)
     padding = sum(plan.row_frames - int(e.frames + 2 * e.lead) for e in plan.table)
     torch.manual_seed(a.seed)
