@@ -823,6 +823,113 @@ int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tr
   return rsmp::launch_tracks_finish(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
+namespace {
+
+// the window of a window call: RR_INVPARAM unless it lies inside the rows, fits its pitch and the window buffer is one a device can hold
+int tracks_window_args(int ntracks, int nch, size_t row_frames, size_t win_first, size_t win_frames, size_t win_stride, rsmp::TracksWindow &w)
+{
+  if (win_first + win_frames < win_first || win_first + win_frames > row_frames || win_stride < win_frames) return RR_INVPARAM;
+  if (win_stride > (~size_t(0) >> 4) / size_t(nch) / size_t(ntracks)) return RR_INVPARAM;
+  w.first = win_first;
+  w.frames = win_frames;
+  w.stride = win_stride;
+  return RR_OK;
+}
+
+} // namespace
+
+// RRX_tracks_stage_device_samples on a window of the rows (tracks.hip).  Refusals first.
+int RRX_tracks_stage_window_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks, int nch,
+                                   int src_format, const void *d_packed, size_t src_total, size_t row_frames, size_t win_first, size_t win_frames,
+                                   fb_sample_t *d_win, size_t win_stride)
+{
+  const int kind = tracks_src_kind(src_format);
+  if (kind < 0) return RR_INVPARAM;
+  if (!d_tracks || !d_packed || !d_win || ntracks < 1 || nch < 1 || !in_rate || !out_rate || !row_frames) return RR_INVPARAM;
+  if (device < -1 || (long long)ntracks * nch > 0x3fffffffLL) return RR_INVPARAM; // (two workgroups per channel of every track)
+  const size_t most = (~size_t(0) >> 4) / size_t(nch);                            // no buffer has 2^60 samples, and no virtual row either
+  if (src_total > most || row_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  rsmp::TracksWindow w;
+  if (tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, w) != RR_OK) return RR_INVPARAM;
+  size_t n_add = 0, n_drop = 0, prime = 0, inbuf = 0;
+  if (RRX_edge_geometry(in_rate, out_rate, &n_add, &n_drop, &prime, &inbuf) != RR_OK || prime > size_t(rsmp::kLpcLdsFrames)) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!win_frames) return RR_OK;
+  const int rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  rsmp::TracksStageArgs a;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src = d_packed;
+  a.rows = d_win;
+  a.src_total = src_total;
+  a.row_frames = row_frames;
+  a.ntracks = ntracks;
+  a.nch = nch;
+  a.prime_len = int(prime);
+  a.src_kind = kind;
+  return rsmp::launch_tracks_stage_window(static_cast<hipStream_t>(hip_stream), a, w) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// RRX_tracks_finish_device on a window of the output rows (tracks.hip).  Refusals first.
+int RRX_tracks_finish_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                    const void *d_win, size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames, int dst_format,
+                                    void *d_dst, size_t dst_total, const double *d_gain, int dither, unsigned long long seed, double *d_peak,
+                                    unsigned long long *d_clipped)
+{
+  if (!d_tracks || !d_win || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (d_dst && dst_format != RRX_FMT_S16 && dst_format != RRX_FMT_S24_3 && dst_format != RRX_FMT_S32) return RR_INVPARAM;
+  if (!d_dst && !d_peak && !d_clipped) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks) || (d_dst && dst_total > most)) return RR_INVPARAM;
+  rsmp::TracksWindow w;
+  if (tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, w) != RR_OK) return RR_INVPARAM;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames || !win_frames) return RR_OK;
+  const int rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  rsmp::TracksFinishArgs a;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src = d_win;
+  a.dst = d_dst;
+  a.gain = d_gain;
+  a.peak = d_peak;
+  a.clipped = d_clipped;
+  a.row_frames = row_frames;
+  a.dst_total = dst_total;
+  a.seed = seed;
+  a.ntracks = ntracks;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  a.bits = !d_dst ? 31 : dst_format == RRX_FMT_S16 ? 15 : dst_format == RRX_FMT_S24_3 ? 23 : 31; // measure only: the S32 grid
+  a.dither = dither != 0;
+  return rsmp::launch_tracks_finish_window(static_cast<hipStream_t>(hip_stream), a, w) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// Test hook: what the window kernels take from one table entry -- tracks_stage_cut and tracks_finish_cut (tracks.hpp), the functions
+// the kernels call, on a host entry.  stage[10]: bk, cp, fw, z (two values each), src_frame, readable; finish[4]: w0, w1, index, dst_frame.
+int RRX_debug_tracks_window_cut(const RRX_track *entry, size_t row_frames, size_t src_total, size_t dst_total, int write, size_t win_first,
+                                size_t win_frames, unsigned long long *stage, unsigned long long *finish)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  if (!entry || !stage || !finish || win_first + win_frames < win_first || win_first + win_frames > row_frames) return RR_INVPARAM;
+  rsmp::Track tr;
+  std::memcpy(&tr, entry, sizeof(tr));
+  const rsmp::TracksWindow w = {win_first, win_frames, win_frames};
+  const rsmp::TracksStageCut c = rsmp::tracks_stage_cut(tr, row_frames, src_total, w);
+  const unsigned long long s[10] = {c.bk[0], c.bk[1], c.cp[0], c.cp[1], c.fw[0], c.fw[1], c.z[0], c.z[1], c.src_frame, c.readable};
+  std::memcpy(stage, s, sizeof(s));
+  const rsmp::TracksFinishCut f = rsmp::tracks_finish_cut(tr, row_frames, dst_total, write != 0, w);
+  const unsigned long long o[4] = {f.w0, f.w1, f.index, f.dst_frame};
+  std::memcpy(finish, o, sizeof(o));
+  return RR_OK;
+}
+
 size_t RRX_isamp_max(const RR_handle *h) { return h ? h->eng->isamp_max() : 0; }
 size_t RRX_available(const RR_handle *h) { return h ? h->eng->available() : 0; }
 int RRX_channels(const RR_handle *h) { return h ? h->eng->nch() : 0; }

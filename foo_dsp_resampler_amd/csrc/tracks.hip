@@ -24,8 +24,15 @@
 // destination, statistics in registers and LDS where lcm(4, nch) <= 1024.  The grid is sized for a full row; the workgroups past
 // a shorter track's end exit at once.
 //
-// The table is the caller's, on the device, and is not validated: every value taken from it is clamped first (Entry; the prologue of tracks_finish_kernel), so
-// a wrong table gives wrong samples and never an access outside the source, the track's own row or the destination.
+// Windows (RRX_tracks_stage_window_device / RRX_tracks_finish_window_device; DESIGN.md 11, "Windows"): the same passes on frames
+// [first, first + frames) of rows that exist nowhere as a whole, so that a batch runs in memory proportional to the window.  Each
+// kernel has a window form with the same body (copy_span, lpc_edge, finish_span) behind another prologue: the regions of the row,
+// or the track's slice, cut to the window by tracks_stage_cut / tracks_finish_cut (tracks.hpp).  The copy and finish grids are
+// sized by the window; the LPC grid is not (see tracks_lpc_window_kernel).
+//
+// The table is the caller's, on the device, and is not validated: every value taken from it is clamped first (tracks_entry and
+// tracks_slice, tracks.hpp, and the cut functions built on them), so
+// a wrong table gives wrong samples and never an access outside the source, the track's own row or window, or the destination.
 #include "tracks.hpp"
 
 #include "finish.hpp"
@@ -40,20 +47,8 @@ constexpr int kThreads = 256, kSpanMax = kThreads * 4;
 
 __device__ __forceinline__ u64 min_u(u64 x, u64 y) { return x < y ? x : y; }
 
-// Track t's input side, clamped: lead + frames + fwd <= row_frames and first + have <= src_total whatever the table says
-struct Entry {
-  u64 first, have; // the track's frames in the packed source: [first, first + have), have <= frames
-  u64 lead, frames, fwd;
-  __device__ __forceinline__ Entry(const TracksStageArgs &a, u64 t)
-  {
-    const Track tr = a.tracks[t];
-    lead = min_u(tr.lead, a.row_frames);
-    frames = min_u(tr.frames, a.row_frames - lead);
-    fwd = min_u(lead, a.row_frames - lead - frames);
-    first = min_u(tr.src_first, a.src_total);
-    have = min_u(frames, a.src_total - first);
-  }
-};
+// Track t's input side, clamped (tracks_entry, tracks.hpp)
+__device__ __forceinline__ TracksEntry entry_of(const TracksStageArgs &a, u64 t) { return tracks_entry(a.tracks[t], a.row_frames, a.src_total); }
 
 // The packed source as the kernels address it: floats as floats (the float instances are the kernels they were before the
 // integer sources came), integer PCM as bytes, kStep of them a sample
@@ -66,28 +61,67 @@ template <> struct Src<kTracksSrcF32> {
   static constexpr u64 kStep = 1;
 };
 
-template <int kSrc> __global__ __launch_bounds__(64) void tracks_lpc_kernel(TracksStageArgs a)
+// One edge (0: backward, 1: forward) of channel ch of a track: `extra` frames of extrapolation, counted outwards from the track's
+// edge.  Extrapolated frame i (lpc_channel's count, from base frame 0) is frame k = org + i of y; kWin: stored only where lo <= k < hi.
+template <int kSrc, bool kWin>
+__device__ __forceinline__ void lpc_edge(unsigned char *lds, const TracksStageArgs &a, const TracksEntry &e, int edge, u64 ch, long long extra,
+                                         float *y, long long org, long long lo, long long hi)
 {
   typedef typename Src<kSrc>::T T;
-  extern __shared__ __attribute__((aligned(16))) unsigned char tracks_lds[];
-  const int lane = threadIdx.x, edge = blockIdx.x & 1, nch = a.nch;
-  const u64 t = (blockIdx.x >> 1) / (unsigned)nch, ch = (blockIdx.x >> 1) % (unsigned)nch;
-  const Entry e(a, t);
-  const long long extra = (long long)(edge ? e.fwd : e.lead);
-  if (!extra) return;
+  const int lane = threadIdx.x, nch = a.nch;
   const long long n = (long long)min_u(e.frames, (u64)a.prime_len);      // base frames: the track's first n, or its last n
   const u64 base = edge ? e.frames - (u64)n : 0;
   const long long readable = e.have > base ? (long long)(e.have - base) : 0; // (all n of them, unless the table is wrong)
   // base frame 0 of this channel: strided single samples, read once (into LDS) through tracks_load_sample
   const T *x = static_cast<const T *>(a.src) + ((e.first + min_u(base, e.have)) * nch + ch) * Src<kSrc>::kStep;
-  float *y = a.rows + ((t * a.row_frames + e.lead + base) * nch + ch);
   if (n <= kLpcMaxOrder) { // no table of RRX_tracks_plan: a lead means more than 64 frames.  Zeros, so that the row is written all the same.
-    for (long long i = lane; i < extra; i += 64) y[(edge ? n + i : -1 - i) * nch] = 0.0f;
+    for (long long i = lane; i < extra; i += 64) {
+      const long long k = org + (edge ? n + i : -1 - i);
+      if (!kWin || (k >= lo && k < hi)) y[k * nch] = 0.0f;
+    }
     return;
   }
-  lpc_channel<true>(tracks_lds, lane, n, (float)(n + 1) / 2.0f, kLpcMaxOrder, edge ? 0 : extra, edge ? extra : 0,
+  lpc_channel<true>(lds, lane, n, (float)(n + 1) / 2.0f, kLpcMaxOrder, edge ? 0 : extra, edge ? extra : 0,
                     [=](long long i) { return i < readable ? tracks_load_sample(kSrc, x, (u64)(i * nch)) : 0.0f; },
-                    [=](long long i, float v) { y[i * nch] = v; });
+                    [=](long long i, float v) {
+                      const long long k = org + i;
+                      if (!kWin || (k >= lo && k < hi)) y[k * nch] = v;
+                    });
+}
+
+template <int kSrc> __global__ __launch_bounds__(64) void tracks_lpc_kernel(TracksStageArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char tracks_lds[];
+  const int edge = blockIdx.x & 1, nch = a.nch;
+  const u64 t = (blockIdx.x >> 1) / (unsigned)nch, ch = (blockIdx.x >> 1) % (unsigned)nch;
+  const TracksEntry e = entry_of(a, t);
+  const long long extra = (long long)(edge ? e.fwd : e.lead);
+  if (!extra) return;
+  const u64 base = edge ? e.frames - min_u(e.frames, (u64)a.prime_len) : 0;
+  float *y = a.rows + ((t * a.row_frames + e.lead + base) * nch + ch);
+  lpc_edge<kSrc, false>(tracks_lds, a, e, edge, ch, extra, y, 0, 0, 0);
+}
+
+// The window form: same grid, because the table is on the device and the host cannot pick the workgroups that have work.  One whose
+// extension does not meet the window returns before it loads a base frame.  The recursion is serial from the track's edge outwards,
+// so one that does starts there whatever the window is, runs as far as the window's far end asks for, and stores what lies inside.
+template <int kSrc> __global__ __launch_bounds__(64) void tracks_lpc_window_kernel(TracksStageArgs a, TracksWindow w)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char tracks_lds[];
+  const int edge = blockIdx.x & 1, nch = a.nch;
+  const u64 t = (blockIdx.x >> 1) / (unsigned)nch, ch = (blockIdx.x >> 1) % (unsigned)nch;
+  const TracksStageCut c = tracks_stage_cut(a.tracks[t], a.row_frames, a.src_total, w);
+  const u64 *r = edge ? c.fw : c.bk;
+  if (r[0] == r[1]) return;
+  const TracksEntry &e = c.e;
+  // in row frames: the backward recursion comes down from lead - 1 to the window's first extension frame, the forward one goes up
+  // from lead + frames to its last
+  const long long extra = (long long)(edge ? w.first + r[1] - (e.lead + e.frames) : e.lead - (w.first + r[0]));
+  const u64 base = edge ? e.frames - min_u(e.frames, (u64)a.prime_len) : 0;
+  // base frame 0 is row frame lead + base, which is window frame org (before the window: negative)
+  const long long org = (long long)(e.lead + base) - (long long)w.first;
+  float *y = a.rows + (t * w.stride * nch + ch); // window frame 0 of this channel
+  lpc_edge<kSrc, true>(tracks_lds, a, e, edge, ch, extra, y, org, (long long)r[0], (long long)r[1]);
 }
 
 // Four consecutive samples of an integer source as integers, from the aligned dwords that cover them: the inverse of Pack<bits>
@@ -120,17 +154,13 @@ template <int kSrc> __device__ __forceinline__ void unpack4(const unsigned char 
   }
 }
 
-template <int kSrc> __global__ __launch_bounds__(kThreads) void tracks_copy_kernel(TracksStageArgs a, int t0, int steps)
+// The n samples at `row` (a row, or the window of one).  [c0, c1) is the track: sample c0 + j is sample j of s where j < have and
+// zero from there; [z0, n) are zeros; what lies in front of c0 and between c1 and z0 belongs to the LPC kernel.
+template <int kSrc>
+__device__ __forceinline__ void copy_span(float *row, u64 n, u64 c0, u64 c1, u64 z0, u64 have, const typename Src<kSrc>::T *s, int steps)
 {
-  typedef typename Src<kSrc>::T T;
   constexpr u64 kStep = Src<kSrc>::kStep;
   const unsigned tid = threadIdx.x;
-  const u64 t = (u64)(t0 + (int)blockIdx.y), nch = (u64)a.nch, n = a.row_frames * nch; // n: samples of a row
-  const Entry e(a, t);
-  // in samples of the row: [c0, c1) is the track, [z0, n) the zeros; what lies between belongs to tracks_lpc_kernel
-  const u64 c0 = e.lead * nch, c1 = c0 + e.frames * nch, z0 = c1 + e.fwd * nch, have = e.have * nch;
-  const T *s = static_cast<const T *>(a.src) + e.first * nch * kStep; // sample j of the track, j < have, is kStep * j further
-  float *row = a.rows + t * n;
   auto one = [&](u64 k) {
     if (k >= c0 && k < c1) row[k] = k - c0 < have ? tracks_load_sample(kSrc, s, k - c0) : 0.0f;
     else if (k >= z0) row[k] = 0.0f;
@@ -166,6 +196,31 @@ template <int kSrc> __global__ __launch_bounds__(kThreads) void tracks_copy_kern
     }
     __builtin_memcpy(__builtin_assume_aligned(row + k, 16), v, sizeof(v));
   }
+}
+
+template <int kSrc> __global__ __launch_bounds__(kThreads) void tracks_copy_kernel(TracksStageArgs a, int t0, int steps)
+{
+  typedef typename Src<kSrc>::T T;
+  constexpr u64 kStep = Src<kSrc>::kStep;
+  const u64 t = (u64)(t0 + (int)blockIdx.y), nch = (u64)a.nch, n = a.row_frames * nch; // n: samples of a row
+  const TracksEntry e = entry_of(a, t);
+  // in samples of the row: [c0, c1) is the track, [z0, n) the zeros; what lies between belongs to tracks_lpc_kernel
+  const u64 c0 = e.lead * nch, c1 = c0 + e.frames * nch, z0 = c1 + e.fwd * nch, have = e.have * nch;
+  const T *s = static_cast<const T *>(a.src) + e.first * nch * kStep; // sample j of the track, j < have, is kStep * j further
+  copy_span<kSrc>(a.rows + t * n, n, c0, c1, z0, have, s, steps);
+}
+
+// The window form: the grid covers the window's samples, and the regions are the row's cut to the window (tracks_stage_cut).  Head,
+// groups and tail follow the alignment of the WINDOW row, per track; the misalignment of an integer source is still one value per
+// workgroup, because the groups of a window row are a whole number of groups apart as those of a row are.
+template <int kSrc> __global__ __launch_bounds__(kThreads) void tracks_copy_window_kernel(TracksStageArgs a, TracksWindow w, int t0, int steps)
+{
+  typedef typename Src<kSrc>::T T;
+  constexpr u64 kStep = Src<kSrc>::kStep;
+  const u64 t = (u64)(t0 + (int)blockIdx.y), nch = (u64)a.nch;
+  const TracksStageCut c = tracks_stage_cut(a.tracks[t], a.row_frames, a.src_total, w);
+  const T *s = static_cast<const T *>(a.src) + c.src_frame * nch * kStep; // the sample that window sample cp[0] * nch is a copy of
+  copy_span<kSrc>(a.rows + t * w.stride * nch, w.frames * nch, c.cp[0] * nch, c.cp[1] * nch, c.z[0] * nch, c.readable * nch, s, steps);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- output stage
@@ -212,23 +267,15 @@ template <> struct Pack<31> {
 
 // S: float or double rows.  kWrite = false: measure only.  kReg: statistics in registers and LDS (finish.hip).
 // Track t is stream t of RRX_finish_device: gain[t], statistics and dither channel t * nch + ch, frame 0 = its first output frame.
+// finish_span: n samples of track t from src to dst (kWrite); the first of them belongs to frame i0 of the track.
 template <typename S, int kBits, bool kWrite, bool kReg>
-__global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArgs a, int t0, int span, unsigned fps, int steps)
+__device__ __forceinline__ void finish_span(const TracksFinishArgs &a, u64 t, const S *src, unsigned char *dst, u64 n, u64 i0, int span, unsigned fps,
+                                            int steps, u64 *sh_peak, unsigned *sh_clip)
 {
-  __shared__ u64 sh_peak[kReg ? kFinishLdsChannels : 1];
-  __shared__ unsigned sh_clip[kReg ? kFinishLdsChannels : 1];
   using P = Pack<kBits>;
   const unsigned tid = threadIdx.x;
   const unsigned nch = (unsigned)a.nch;
-  const u64 t = (u64)(t0 + (int)blockIdx.y), cbase = t * nch;
-  // the track's slice, clamped: inside its row, and (when written) inside the destination
-  const Track tr = a.tracks[t];
-  const u64 of = min_u(tr.out_first, a.row_frames), df = kWrite ? min_u(tr.dst_first, a.dst_total) : 0;
-  u64 frames = min_u(tr.out_frames, a.row_frames - of);
-  if (kWrite) frames = min_u(frames, a.dst_total - df);
-  const u64 n = frames * nch;
-  const S *src = static_cast<const S *>(a.src) + (t * a.row_frames + of) * nch;
-  unsigned char *dst = kWrite ? static_cast<unsigned char *>(a.dst) + df * nch * P::kBytes : nullptr;
+  const u64 cbase = t * nch;
   const bool has_gain = a.gain != nullptr, dither = a.dither != 0;
 
   // the track's head: samples in front of the first dword boundary of the destination
@@ -257,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArg
       const u64 k = is_head ? tid : head + (ngroups << 2) + (tid - 64);
       const u64 fr = k / nch;
       const unsigned ch = (unsigned)(k - fr * nch);
-      const FinishSample r = finish_sample<kBits>((double)src[k], has_gain, gain, dither, a.seed, fr, cbase + ch);
+      const FinishSample r = finish_sample<kBits>((double)src[k], has_gain, gain, dither, a.seed, i0 + fr, cbase + ch);
       if (kWrite) finish_store_bytes<kBits>(dst + k * P::kBytes, r.q);
       if (kReg) {
         atomicMax(&sh_peak[ch], peak_bits(r.a));
@@ -276,7 +323,7 @@ __global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArg
     if (kReg) {
       const unsigned k0 = head + 4 * tid, f0 = k0 / nch;
       unsigned ch = k0 - f0 * nch;
-      u64 fr = f0 + step0 * fps;
+      u64 fr = i0 + f0 + step0 * fps;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         chj[j] = ch;
@@ -293,7 +340,7 @@ __global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArg
       if (!kReg) {
         const u64 f0 = k / nch;
         unsigned ch = (unsigned)(k - f0 * nch);
-        u64 fr = f0;
+        u64 fr = i0 + f0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           chj[j] = ch;
@@ -336,6 +383,36 @@ __global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArg
   }
 }
 
+template <typename S, int kBits, bool kWrite, bool kReg>
+__global__ __launch_bounds__(kThreads) void tracks_finish_kernel(TracksFinishArgs a, int t0, int span, unsigned fps, int steps)
+{
+  __shared__ u64 sh_peak[kReg ? kFinishLdsChannels : 1];
+  __shared__ unsigned sh_clip[kReg ? kFinishLdsChannels : 1];
+  const unsigned nch = (unsigned)a.nch;
+  const u64 t = (u64)(t0 + (int)blockIdx.y);
+  // the track's slice, clamped: inside its row, and (when written) inside the destination
+  const TracksSlice s = tracks_slice(a.tracks[t], a.row_frames, a.dst_total, kWrite);
+  const S *src = static_cast<const S *>(a.src) + (t * a.row_frames + s.of) * nch;
+  unsigned char *dst = kWrite ? static_cast<unsigned char *>(a.dst) + s.df * nch * Pack<kBits>::kBytes : nullptr;
+  finish_span<S, kBits, kWrite, kReg>(a, t, src, dst, s.frames * nch, 0, span, fps, steps, sh_peak, sh_clip);
+}
+
+// The window form: a.src holds frames [w.first, w.first + w.frames) of every output row, pitch w.stride.  The part of the track's
+// slice inside the window is processed (tracks_finish_cut); head, groups and tail follow where ITS bytes begin in the destination,
+// and the frame number finish_sample gets counts from the track's first output frame, as in the whole-row kernel.
+template <typename S, int kBits, bool kWrite, bool kReg>
+__global__ __launch_bounds__(kThreads) void tracks_finish_window_kernel(TracksFinishArgs a, TracksWindow w, int t0, int span, unsigned fps, int steps)
+{
+  __shared__ u64 sh_peak[kReg ? kFinishLdsChannels : 1];
+  __shared__ unsigned sh_clip[kReg ? kFinishLdsChannels : 1];
+  const unsigned nch = (unsigned)a.nch;
+  const u64 t = (u64)(t0 + (int)blockIdx.y);
+  const TracksFinishCut c = tracks_finish_cut(a.tracks[t], a.row_frames, a.dst_total, kWrite, w);
+  const S *src = static_cast<const S *>(a.src) + (t * w.stride + c.w0) * nch;
+  unsigned char *dst = kWrite ? static_cast<unsigned char *>(a.dst) + c.dst_frame * nch * Pack<kBits>::kBytes : nullptr;
+  finish_span<S, kBits, kWrite, kReg>(a, t, src, dst, (c.w1 - c.w0) * nch, c.index, span, fps, steps, sh_peak, sh_clip);
+}
+
 u64 gcd_u(u64 x, u64 y)
 {
   while (y) {
@@ -346,10 +423,11 @@ u64 gcd_u(u64 x, u64 y)
   return x;
 }
 
+// w: the window form, or null
 template <typename S, int kBits, bool kWrite>
-hipError_t finish_typed(hipStream_t stream, const TracksFinishArgs &a)
+hipError_t finish_typed(hipStream_t stream, const TracksFinishArgs &a, const TracksWindow *w)
 {
-  const u64 nch = (u64)a.nch, lcm4 = nch / gcd_u(nch, 4) * 4, n = a.row_frames * nch; // n: the most samples a track can have
+  const u64 nch = (u64)a.nch, lcm4 = nch / gcd_u(nch, 4) * 4, n = (w ? w->frames : a.row_frames) * nch; // n: the most samples a track can have
   static_assert(kFinishLdsChannels >= kSpanMax, "nch <= lcm(4, nch) <= kSpanMax has to fit the LDS table");
   const bool reg = lcm4 <= (u64)kSpanMax;
   const int span = reg ? int(kSpanMax / lcm4 * lcm4) : kSpanMax;
@@ -364,7 +442,9 @@ hipError_t finish_typed(hipStream_t stream, const TracksFinishArgs &a)
   for (int t0 = 0; t0 < a.ntracks; t0 += 32768) { // grid.y is a 16-bit count
     const int nt = a.ntracks - t0 < 32768 ? a.ntracks - t0 : 32768;
     const dim3 grid(gx ? gx : 1, (unsigned)nt), block(kThreads);
-    if (reg) hipLaunchKernelGGL((tracks_finish_kernel<S, kBits, kWrite, true>), grid, block, 0, stream, a, t0, span, fps, (int)steps);
+    if (w && reg) hipLaunchKernelGGL((tracks_finish_window_kernel<S, kBits, kWrite, true>), grid, block, 0, stream, a, *w, t0, span, fps, (int)steps);
+    else if (w) hipLaunchKernelGGL((tracks_finish_window_kernel<S, kBits, kWrite, false>), grid, block, 0, stream, a, *w, t0, span, fps, (int)steps);
+    else if (reg) hipLaunchKernelGGL((tracks_finish_kernel<S, kBits, kWrite, true>), grid, block, 0, stream, a, t0, span, fps, (int)steps);
     else hipLaunchKernelGGL((tracks_finish_kernel<S, kBits, kWrite, false>), grid, block, 0, stream, a, t0, span, fps, (int)steps);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -372,54 +452,71 @@ hipError_t finish_typed(hipStream_t stream, const TracksFinishArgs &a)
   return hipSuccess;
 }
 
-template <typename S> hipError_t finish_src(hipStream_t stream, const TracksFinishArgs &a)
+template <typename S> hipError_t finish_src(hipStream_t stream, const TracksFinishArgs &a, const TracksWindow *w)
 {
-  if (!a.dst) return finish_typed<S, 31, false>(stream, a);
+  if (!a.dst) return finish_typed<S, 31, false>(stream, a, w);
   switch (a.bits) {
-  case 15: return finish_typed<S, 15, true>(stream, a);
-  case 23: return finish_typed<S, 23, true>(stream, a);
-  default: return finish_typed<S, 31, true>(stream, a);
+  case 15: return finish_typed<S, 15, true>(stream, a, w);
+  case 23: return finish_typed<S, 23, true>(stream, a, w);
+  default: return finish_typed<S, 31, true>(stream, a, w);
   }
 }
 
-template <int kSrc> hipError_t stage_typed(hipStream_t stream, const TracksStageArgs &a)
+// w: the window form, or null
+template <int kSrc> hipError_t stage_typed(hipStream_t stream, const TracksStageArgs &a, const TracksWindow *w)
 {
   // copy and zero fill: 8 steps of 256 groups (32 KiB written) per workgroup, more only to stay inside the grid limit
-  const u64 groups = (a.row_frames * (u64)a.nch + 3) / 4 + 1; // (+1: the head can move the last samples into one more group)
+  const u64 groups = ((w ? w->frames : a.row_frames) * (u64)a.nch + 3) / 4 + 1; // (+1: the head can move the last samples into one more group)
   u64 steps = 8;
   while ((groups + steps * kThreads - 1) / (steps * kThreads) > 0x7fffffffull) steps *= 2;
   const unsigned gx = (unsigned)((groups + steps * kThreads - 1) / (steps * kThreads));
   for (int t0 = 0; t0 < a.ntracks; t0 += 32768) { // grid.y is a 16-bit count
     const int nt = a.ntracks - t0 < 32768 ? a.ntracks - t0 : 32768;
-    hipLaunchKernelGGL(tracks_copy_kernel<kSrc>, dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, t0, (int)steps);
+    if (w) hipLaunchKernelGGL(tracks_copy_window_kernel<kSrc>, dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, *w, t0, (int)steps);
+    else hipLaunchKernelGGL(tracks_copy_kernel<kSrc>, dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, t0, (int)steps);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   // the two extensions of every (track, channel)
-  static DynLdsOnce once; // (one per instance)
-  const hipError_t e = once.set(reinterpret_cast<const void *>(&tracks_lpc_kernel<kSrc>), int(sizeof(LpcShared) + kLpcLdsFrames * sizeof(float)));
+  static DynLdsOnce once, once_window; // (one per instance)
+  const void *fn = w ? reinterpret_cast<const void *>(&tracks_lpc_window_kernel<kSrc>) : reinterpret_cast<const void *>(&tracks_lpc_kernel<kSrc>);
+  const hipError_t e = (w ? once_window : once).set(fn, int(sizeof(LpcShared) + kLpcLdsFrames * sizeof(float)));
   if (e != hipSuccess) return e;
   const size_t lds = sizeof(LpcShared) + size_t(a.prime_len) * sizeof(float);
-  hipLaunchKernelGGL(tracks_lpc_kernel<kSrc>, dim3((unsigned)((long long)a.ntracks * a.nch * 2)), dim3(64), lds, stream, a);
+  const dim3 grid((unsigned)((long long)a.ntracks * a.nch * 2));
+  if (w) hipLaunchKernelGGL(tracks_lpc_window_kernel<kSrc>, grid, dim3(64), lds, stream, a, *w);
+  else hipLaunchKernelGGL(tracks_lpc_kernel<kSrc>, grid, dim3(64), lds, stream, a);
   return hipGetLastError();
 }
 
 } // namespace
 
-hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a)
+namespace {
+
+hipError_t stage_kind(hipStream_t stream, const TracksStageArgs &a, const TracksWindow *w)
 {
   switch (a.src_kind) {
-  case kTracksSrcF32: return stage_typed<kTracksSrcF32>(stream, a);
-  case kTracksSrcS16: return stage_typed<kTracksSrcS16>(stream, a);
-  case kTracksSrcS24: return stage_typed<kTracksSrcS24>(stream, a);
-  case kTracksSrcS32: return stage_typed<kTracksSrcS32>(stream, a);
+  case kTracksSrcF32: return stage_typed<kTracksSrcF32>(stream, a, w);
+  case kTracksSrcS16: return stage_typed<kTracksSrcS16>(stream, a, w);
+  case kTracksSrcS24: return stage_typed<kTracksSrcS24>(stream, a, w);
+  case kTracksSrcS32: return stage_typed<kTracksSrcS32>(stream, a, w);
   default: return hipErrorInvalidValue; // a missing kernel is an error, never another kernel
   }
 }
 
+} // namespace
+
+hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a) { return stage_kind(stream, a, nullptr); }
+hipError_t launch_tracks_stage_window(hipStream_t stream, const TracksStageArgs &a, const TracksWindow &w) { return stage_kind(stream, a, &w); }
+
 hipError_t launch_tracks_finish(hipStream_t stream, const TracksFinishArgs &a)
 {
-  return a.src_double ? finish_src<double>(stream, a) : finish_src<float>(stream, a);
+  return a.src_double ? finish_src<double>(stream, a, nullptr) : finish_src<float>(stream, a, nullptr);
+}
+
+hipError_t launch_tracks_finish_window(hipStream_t stream, const TracksFinishArgs &a, const TracksWindow &w)
+{
+  return a.src_double ? finish_src<double>(stream, a, &w) : finish_src<float>(stream, a, &w);
 }
 
 } // namespace rsmp

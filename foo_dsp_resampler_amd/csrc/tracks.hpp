@@ -40,6 +40,108 @@ __host__ __device__ __forceinline__ float tracks_load_sample(int kind, const voi
   }
 }
 
+// ------------------------------------------------------------------------------------------------------ interval arithmetic
+// Everything the kernels take from a table entry goes through the four functions below, which hold all the u64 clamps against
+// wrap-around: the whole-row kernels call tracks_entry / tracks_slice, the window kernels tracks_stage_cut / tracks_finish_cut,
+// which are built on them, and RRX_debug_tracks_window_cut (capi.cpp) runs the same functions on the host.
+
+// Track t's input side, clamped: lead + frames + fwd <= row_frames and first + have <= src_total whatever the table says
+struct TracksEntry {
+  unsigned long long first, have; // the track's frames in the packed source: [first, first + have), have <= frames
+  unsigned long long lead, frames, fwd;
+};
+
+__host__ __device__ __forceinline__ TracksEntry tracks_entry(const Track &tr, unsigned long long row_frames, unsigned long long src_total)
+{
+  TracksEntry e;
+  e.lead = tr.lead < row_frames ? tr.lead : row_frames;
+  e.frames = tr.frames < row_frames - e.lead ? tr.frames : row_frames - e.lead;
+  e.fwd = e.lead < row_frames - e.lead - e.frames ? e.lead : row_frames - e.lead - e.frames;
+  e.first = tr.src_first < src_total ? tr.src_first : src_total;
+  e.have = e.frames < src_total - e.first ? e.frames : src_total - e.first;
+  return e;
+}
+
+// Frames [first, first + frames) of rows of row_frames frames: what the window calls work on.  first + frames <= row_frames
+// (the callers of the kernels refuse anything else), so no sum below can wrap.
+struct TracksWindow {
+  unsigned long long first, frames;
+  unsigned long long stride;      // pitch of the window rows in frames, >= frames (the cut functions do not look at it)
+};
+
+// [lo, hi) of a row, lo <= hi <= row_frames, cut to the window and counted from the window's first frame
+__host__ __device__ __forceinline__ void tracks_window_range(const TracksWindow &w, unsigned long long lo, unsigned long long hi,
+                                                             unsigned long long *out)
+{
+  const unsigned long long end = w.first + w.frames;
+  out[0] = (lo < w.first ? w.first : lo < end ? lo : end) - w.first;
+  out[1] = (hi < w.first ? w.first : hi < end ? hi : end) - w.first;
+}
+
+// The stage pass of one track inside a window: the four regions of its row (tracks.hip), each cut to the window, as half-open
+// ranges of WINDOW frames.  They are adjacent, in this order, and cover [0, w.frames) exactly: bk[0] == 0, bk[1] == cp[0],
+// cp[1] == fw[0], fw[1] == z[0], z[1] == w.frames.
+struct TracksStageCut {
+  TracksEntry e;
+  unsigned long long bk[2], cp[2], fw[2], z[2]; // backward extension, the track, forward extension, zeros
+  unsigned long long src_frame;                  // frame of the packed source that window frame cp[0] is a copy of (cp empty: e.first)
+  unsigned long long readable;                   // of the frames [cp[0], cp[1]), the first `readable` lie inside the source; the rest read as zeros
+};
+
+__host__ __device__ __forceinline__ TracksStageCut tracks_stage_cut(const Track &tr, unsigned long long row_frames, unsigned long long src_total,
+                                                                    const TracksWindow &w)
+{
+  TracksStageCut c;
+  c.e = tracks_entry(tr, row_frames, src_total);
+  const unsigned long long c0 = c.e.lead, c1 = c0 + c.e.frames, z0 = c1 + c.e.fwd; // <= row_frames by the clamps
+  tracks_window_range(w, 0, c0, c.bk);
+  tracks_window_range(w, c0, c1, c.cp);
+  tracks_window_range(w, c1, z0, c.fw);
+  tracks_window_range(w, z0, row_frames, c.z);
+  const unsigned long long n = c.cp[1] - c.cp[0], off = n ? w.first + c.cp[0] - c0 : 0; // frame of the track that comes first
+  c.src_frame = c.e.first + off;                                                        // (<= src_total + row_frames)
+  c.readable = c.e.have > off ? (c.e.have - off < n ? c.e.have - off : n) : 0;
+  return c;
+}
+
+// Track t's output side, clamped: its slice [of, of + frames) lies inside its row and (when written) [df, df + frames) inside the
+// destination
+struct TracksSlice {
+  unsigned long long of, df, frames;
+};
+
+__host__ __device__ __forceinline__ TracksSlice tracks_slice(const Track &tr, unsigned long long row_frames, unsigned long long dst_total, bool write)
+{
+  TracksSlice s;
+  s.of = tr.out_first < row_frames ? tr.out_first : row_frames;
+  s.df = !write ? 0 : tr.dst_first < dst_total ? tr.dst_first : dst_total;
+  s.frames = tr.out_frames < row_frames - s.of ? tr.out_frames : row_frames - s.of;
+  if (write && s.frames > dst_total - s.df) s.frames = dst_total - s.df;
+  return s;
+}
+
+// The output stage of one track inside a window: window frames [w0, w1) are frames index, index + 1, ... of the track's slice
+// (the frame number its dither is keyed by) and go to frames dst_frame, dst_frame + 1, ... of the packed destination.  A slice
+// that does not meet the window gives all zeros.
+struct TracksFinishCut {
+  unsigned long long w0, w1, index, dst_frame;
+};
+
+__host__ __device__ __forceinline__ TracksFinishCut tracks_finish_cut(const Track &tr, unsigned long long row_frames, unsigned long long dst_total,
+                                                                      bool write, const TracksWindow &w)
+{
+  const TracksSlice s = tracks_slice(tr, row_frames, dst_total, write);
+  const unsigned long long end = w.first + w.frames, lo = s.of > w.first ? s.of : w.first, hi = s.of + s.frames < end ? s.of + s.frames : end;
+  TracksFinishCut c = {0, 0, 0, 0};
+  if (hi > lo) {
+    c.w0 = lo - w.first;
+    c.w1 = hi - w.first;
+    c.index = lo - s.of;
+    c.dst_frame = s.df + c.index;
+  }
+  return c;
+}
+
 // what RRX_tracks_stage_device_samples was given, after validation
 struct TracksStageArgs {
   const Track *tracks;                     // [ntracks], on the device
@@ -75,5 +177,10 @@ struct TracksFinishArgs {
 // out; every other path reads exactly the bytes of the samples it uses.
 hipError_t launch_tracks_stage(hipStream_t stream, const TracksStageArgs &a);
 hipError_t launch_tracks_finish(hipStream_t stream, const TracksFinishArgs &a);
+// The window forms (RRX_tracks_stage_window_device / RRX_tracks_finish_window_device): a.rows / a.src is the window buffer
+// [ntracks][w.stride][nch], a.row_frames the length of the virtual rows, of which no buffer exists; frames [w.first, w.first +
+// w.frames) of every row are written / read, and nothing else of the window buffer.  w.frames > 0.
+hipError_t launch_tracks_stage_window(hipStream_t stream, const TracksStageArgs &a, const TracksWindow &w);
+hipError_t launch_tracks_finish_window(hipStream_t stream, const TracksFinishArgs &a, const TracksWindow &w);
 
 } // namespace rsmp

@@ -23,6 +23,7 @@ EXPECTED_SYMBOLS = [
     "RRX_finish_device", "RRX_debug_finish_host",
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
+    "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
 ]
@@ -196,6 +197,12 @@ def lib():
         if hasattr(L, "RRX_tracks_stage_device_samples"):  # (as above)
             L.RRX_tracks_stage_device_samples.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, sz]
             L.RRX_debug_tracks_load_host.argtypes = [C.c_int, vp, sz, sz, vp]
+        if hasattr(L, "RRX_tracks_stage_window_device"):  # (as above)
+            u64 = C.c_ulonglong
+            L.RRX_tracks_stage_window_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, vp, sz]
+            L.RRX_tracks_finish_window_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp,
+                                                          C.c_int, u64, vp, vp]
+            L.RRX_debug_tracks_window_cut.argtypes = [P(RRXTrack), sz, sz, sz, C.c_int, sz, sz, P(u64), P(u64)]
         _lib = L
     return _lib
 
@@ -399,15 +406,8 @@ def _tracks_src_format(dtype):
     return {"torch.float32": RRX_FMT_FLOAT, "torch.int16": RRX_FMT_S16, "torch.int32": RRX_FMT_S32, "torch.uint8": RRX_FMT_S24_3}.get(str(dtype))
 
 
-def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, stream=None):
-    """The stage pass of a ragged batch on the device (RRX_tracks_stage_device_samples): `packed` is a contiguous device tensor of
-    tracks laid end to end -- float32, int16 (RRX_FMT_S16) or int32 (RRX_FMT_S32) [src_total, nch], or uint8 [src_total, nch * 3]
-    (RRX_FMT_S24_3: packed little-endian 24 bit, the layout tracks_finish_device returns for that format) -- and `table` the device
-    copy of a plan's table (TracksPlan.to_device).  Integer PCM is converted on load, x = s * 2^-15 / 2^-23 / 2^-31 rounded once
-    to float32 (ratelib_amd.h), so no float32 copy of the source is needed.  Returns the rows the handle is pushed from, float32
-    [ntracks, row_frames, nch] whatever the source is (`out`, or a new tensor): each track behind and in front of its own LPC
-    extension, zeros behind it.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
-    import torch
+def _tracks_stage_source(packed, table):
+    """the packed source and the table of a stage call, checked: (RRX_FMT_*, ntracks, nch, src_total)"""
     fmt = _tracks_src_format(packed.dtype)
     if packed.dim() != 2 or fmt is None or not packed.is_cuda or not packed.is_contiguous():
         raise TypeError("packed must be a contiguous float32, int16 or int32 device tensor [frames, nch], or uint8 [frames, nch * 3]")
@@ -417,21 +417,75 @@ def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, 
         if nch % 3 or not nch:
             raise ValueError("a uint8 source is packed 24-bit PCM [frames, nch * 3]; its last dimension is %d" % nch)
         nch //= 3
-    shape = (ntracks, int(row_frames), nch)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=packed.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != packed.device or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 tensor %r on %s" % (shape, packed.device))
     if table.device != packed.device:
         raise TypeError("the table must be on %s" % (packed.device,))
+    return fmt, ntracks, nch, src_total
+
+
+def _tracks_stage_out(out, shape, device):
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 tensor %r on %s" % (shape, device))
+    return out
+
+
+def _tracks_stage_pointer(packed):
+    """(nothing but zero-length tracks: the call still wants a pointer, and never reads through it)"""
+    import torch
     _ensure_init()
-    if not src_total:  # (nothing but zero-length tracks: the call still wants a pointer, and never reads through it)
-        packed = torch.zeros((1, packed.shape[1]), dtype=packed.dtype, device=packed.device)
+    if not packed.shape[0]:
+        return torch.zeros((1, packed.shape[1]), dtype=packed.dtype, device=packed.device)
+    return packed
+
+
+def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, stream=None):
+    """The stage pass of a ragged batch on the device (RRX_tracks_stage_device_samples): `packed` is a contiguous device tensor of
+    tracks laid end to end -- float32, int16 (RRX_FMT_S16) or int32 (RRX_FMT_S32) [src_total, nch], or uint8 [src_total, nch * 3]
+    (RRX_FMT_S24_3: packed little-endian 24 bit, the layout tracks_finish_device returns for that format) -- and `table` the device
+    copy of a plan's table (TracksPlan.to_device).  Integer PCM is converted on load, x = s * 2^-15 / 2^-23 / 2^-31 rounded once
+    to float32 (ratelib_amd.h), so no float32 copy of the source is needed.  Returns the rows the handle is pushed from, float32
+    [ntracks, row_frames, nch] whatever the source is (`out`, or a new tensor): each track behind and in front of its own LPC
+    extension, zeros behind it.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
+    fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
+    out = _tracks_stage_out(out, (ntracks, int(row_frames), nch), packed.device)
+    packed = _tracks_stage_pointer(packed)
     ptr = getattr(stream, "cuda_stream", stream) or 0
     index = packed.device.index
     _check(lib().RRX_tracks_stage_device_samples(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
                                                  C.c_void_p(table.data_ptr()), ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total,
                                                  C.c_void_p(out.data_ptr()), int(row_frames)), "RRX_tracks_stage_device_samples")
+    return out
+
+
+def _tracks_window(row_frames, win_first, win_frames):
+    row_frames, win_first, win_frames = int(row_frames), int(win_first), int(win_frames)
+    if win_first < 0 or win_frames < 0 or win_first + win_frames > row_frames:
+        raise ValueError("the window [%d, %d) does not lie inside rows of %d frames" % (win_first, win_first + win_frames, row_frames))
+    return row_frames, win_first, win_frames
+
+
+def tracks_stage_window_device(packed, table, in_rate, out_rate, row_frames, win_first, win_frames, out=None, stream=None):
+    """tracks_stage_device on a window of the rows (RRX_tracks_stage_window_device): frames [win_first, win_first + win_frames) of
+    every row, bit for bit what tracks_stage_device writes there, without the rows -- `row_frames` is their length, and no tensor
+    of that size is made.  Returns float32 [ntracks, win_stride, nch] with win_stride >= win_frames: `out`, of which frames
+    [0, win_frames) of every row are written and the rest is left alone, or a new tensor with win_stride == win_frames.  `packed`,
+    `table` and `stream` as in tracks_stage_device; the call only enqueues."""
+    fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
+    if out is not None and (out.dim() != 3 or out.shape[1] < win_frames):
+        raise TypeError("out must be a contiguous float32 tensor [%d, at least %d, %d] on %s" % (ntracks, win_frames, nch, packed.device))
+    out = _tracks_stage_out(out, (ntracks, win_frames if out is None else out.shape[1], nch), packed.device)
+    packed = _tracks_stage_pointer(packed)
+    if not win_frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    index = packed.device.index
+    _check(lib().RRX_tracks_stage_window_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
+                                                C.c_void_p(table.data_ptr()), ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total,
+                                                row_frames, win_first, win_frames, C.c_void_p(out.data_ptr()), out.shape[1]),
+           "RRX_tracks_stage_window_device")
     return out
 
 
@@ -444,13 +498,29 @@ def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=F
     [dst_total, nch * 3] for RRX_FMT_S24_3; `dst_format` None measures only.  `gain`: None, a float, or a float64 device tensor
     [ntracks].  `peak` (float64 [ntracks, nch]) and `clipped` (int64 [ntracks, nch]) cover each track's own frames only; they
     are allocated (zeroed) when not passed and accumulated into otherwise.  Returns (out, peak, clipped).  The call only enqueues."""
-    import torch
     dt = str(rows.dtype)
     if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
         raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
+    ntracks, row_frames, nch = rows.shape
+    seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(rows, table, dst_format, dst_total, gain, seed, out, peak, clipped)
+    dev = rows.device
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
+    _check(lib().RRX_tracks_finish_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
+                                          RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), row_frames,
+                                          dst_format or 0, C.c_void_p(out.data_ptr()) if write else None, dst_total,
+                                          C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
+                                          C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_device")
+    return out, peak, clipped
+
+
+def _tracks_finish_buffers(rows, table, dst_format, dst_total, gain, seed, out, peak, clipped):
+    """what tracks_finish_device and its window form share: the arguments checked, `gain` as a tensor or None, and `out`, `peak`
+    and `clipped` allocated where they were not passed; (seed, dst_total, gain, out, peak, clipped)"""
+    import torch
     if dst_format not in (None, RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
         raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32 or None)" % (dst_format,))
-    ntracks, row_frames, nch = rows.shape
+    ntracks, _, nch = rows.shape
     _tracks_table(table, ntracks)
     dev = rows.device
     if table.device != dev:
@@ -482,13 +552,36 @@ def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=F
         stats.append(t)
     peak, clipped = stats
     _ensure_init()
+    return seed, dst_total, gain, out, peak, clipped
+
+
+def tracks_finish_window_device(win, table, row_frames, win_first, win_frames, dst_format, dst_total, gain=None, dither=False, seed=0, out=None,
+                                peak=None, clipped=None, stream=None):
+    """tracks_finish_device on a window of the output rows (RRX_tracks_finish_window_device): `win`, a contiguous float32 or float64
+    device tensor [ntracks, win_stride, nch], holds frames [win_first, win_first + win_frames) of output rows of `row_frames` frames
+    that need not exist anywhere.  Of every track's slice the frames inside the window are processed, with the dither index and the
+    destination position they have in the whole-row call, so disjoint windows that cover the rows -- in any order, each call given
+    the `out`, `peak` and `clipped` the first one returned, which are accumulated into, not reallocated -- leave tracks_finish_device's
+    bytes and statistics.  Everything else as in tracks_finish_device.  Returns (out, peak, clipped); the call only enqueues."""
+    dt = str(win.dtype)
+    if win.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not win.is_cuda or not win.is_contiguous():
+        raise TypeError("win must be a contiguous float32 or float64 device tensor [ntracks, win_stride, nch]")
+    ntracks, win_stride, nch = win.shape
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
+    if win_frames > win_stride:
+        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
+    seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(win, table, dst_format, dst_total, gain, seed, out, peak, clipped)
+    if not win_frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out, peak, clipped
+    dev = win.device
     ptr = getattr(stream, "cuda_stream", stream) or 0
     write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
-    _check(lib().RRX_tracks_finish_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
-                                          RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), row_frames,
-                                          dst_format or 0, C.c_void_p(out.data_ptr()) if write else None, dst_total,
-                                          C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
-                                          C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_device")
+    _check(lib().RRX_tracks_finish_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
+                                                 nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(win.data_ptr()),
+                                                 win_stride, row_frames, win_first, win_frames, dst_format or 0,
+                                                 C.c_void_p(out.data_ptr()) if write else None, dst_total,
+                                                 C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
+                                                 C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_window_device")
     return out, peak, clipped
 
 
@@ -845,8 +938,8 @@ class Resampler:
         finish_kw.setdefault("stream", torch.cuda.current_stream(y.device))
         return finish_device(y, dst_format, **finish_kw)
 
-    def _convert_tracks_rows(self, tracks):
-        """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch])"""
+    def _tracks_checked(self, tracks):
+        """the tracks of a convert_tracks_* call, checked: (list of tracks, plan with the idle streams as zero-length tracks)"""
         import torch
         if self.dtype != np.float32:
             raise TypeError("convert_tracks_device needs a float32 handle (the LPC arithmetic is float32), not %s" % self.dtype)
@@ -864,9 +957,14 @@ class Resampler:
                 raise ValueError("expected [frames, %d] %s tensors, got shape %r" % (last, dt, tuple(x.shape)))
             if not x.is_cuda or x.device.index != self.device:
                 raise TypeError("expected tensors on the handle's device (cuda:%d)" % self.device)
-        dev = tracks[0].device
         # the streams without a track are zero-length tracks: they own no output
-        plan = _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
+        return tracks, _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
+
+    def _convert_tracks_rows(self, tracks):
+        """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch])"""
+        import torch
+        tracks, plan = self._tracks_checked(tracks)
+        dev = tracks[0].device
         table = plan.to_device(dev)
         total, cap = plan.row_frames, plan.out_row_cap
         out = torch.empty((self.nstreams, cap, self.nch), dtype=torch.float32, device=dev)  # (the handle's rows are float32 whatever the tracks are)
@@ -919,6 +1017,84 @@ class Resampler:
         plan, _, out = self._convert_tracks_rows(tracks)
         return [out[t, int(e.out_first):int(e.out_first + e.out_frames)] for t, e in zip(range(len(tracks)), plan.table)]
 
+    def _tracks_finish_kw(self, ntracks, finish_kw, who):
+        import torch
+        if "gain" in finish_kw and hasattr(finish_kw["gain"], "data_ptr") and self.nstreams > ntracks:  # per-track gains: the idle streams get unity
+            g = finish_kw["gain"]
+            finish_kw["gain"] = torch.cat([g, g.new_ones(self.nstreams - ntracks)])
+        for k in ("peak", "clipped"):
+            if finish_kw.get(k) is not None:
+                raise ValueError("%s is allocated by %s" % (k, who))
+
+    def convert_tracks_to_pcm_streamed(self, tracks, dst_format, window=None, **finish_kw):
+        """convert_tracks_to_pcm_device in bounded memory: the same inputs, the same (views, peak, clipped), equal bit for bit, and
+        no rows.  The tracks are planned, packed and the table uploaded as there; then ONE input window [nstreams, window, nch] and
+        ONE output window are allocated besides the packed destination and the statistics, and on torch's current stream the rows
+        are staged a window at a time (tracks_stage_window_device), pushed, and whatever the handle has available is pulled into
+        the output window and finished at the running output position (tracks_finish_window_device), then drained the same way.
+        Everything is on one stream, which orders the reuse of the two windows.  `window` (frames, at most isamp_max, the
+        default) sets the footprint: nstreams * window frames instead of nstreams * the longest track ("Windows").
+
+        The virtual rows are ceil(2 * in_rate / out_rate) + 1 frames longer than the plan's: how many frames a drained handle yields
+        in all depends on the push pattern by a frame or two (rate_base.h:436-468), and the extra zeros -- more of every track's
+        drain -- put every track's last output frame inside what comes out whatever the pattern is."""
+        import torch
+        tracks, plan = self._tracks_checked(tracks)
+        n, dev = len(tracks), tracks[0].device
+        step = self.isamp_max
+        window = step if window is None else int(window)
+        if not 1 <= window <= step:
+            raise ValueError("window must be 1 to isamp_max = %d frames, not %d" % (step, window))
+        self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_streamed")
+        if finish_kw.get("stream") is not None:
+            raise ValueError("convert_tracks_to_pcm_streamed runs on torch's current stream")
+        in_rate, out_rate = self.cfg.in_rate, self.cfg.out_rate
+        cur = torch.cuda.current_stream(dev)
+        finish_kw["stream"] = cur
+        table = plan.to_device(dev)
+        total = plan.row_frames + -(-2 * in_rate // out_rate) + 1 if plan.row_frames else 0
+        cap = total * out_rate // in_rate + 2                 # (as out_row_cap: drain leaves round(total * out_rate / in_rate) frames in all)
+        win_out = -(-window * out_rate // in_rate)            # about what one push makes available; the loop takes any size
+        win = torch.empty((self.nstreams, min(window, max(total, 1)), self.nch), dtype=torch.float32, device=dev)
+        wout = torch.empty((self.nstreams, min(win_out, cap), self.nch), dtype=torch.float32, device=dev)
+        # nothing to finish yet: allocates (and checks) the destination and the statistics
+        pcm, peak, clipped = tracks_finish_window_device(wout, table, cap, 0, 0, dst_format, plan.dst_total, **finish_kw)
+        finish_kw.update(out=pcm, peak=peak, clipped=clipped)
+        if finish_kw.get("gain") is not None and not hasattr(finish_kw["gain"], "data_ptr"):
+            finish_kw["gain"] = torch.full((self.nstreams,), float(finish_kw["gain"]), dtype=torch.float64, device=dev)  # (once, not per window)
+        got = 0
+        if total:
+            packed = torch.cat(tracks).contiguous()
+            prev = self._stream
+            self.set_stream(cur.cuda_stream)
+            try:
+                def pull():
+                    nonlocal got
+                    while self.available:
+                        if got >= cap:
+                            raise RuntimeError("convert_tracks_to_pcm_streamed: more output than %d frames in gives" % total)
+                        k = self.pull_device(wout, min(wout.shape[1], cap - got), stride=wout.shape[1])
+                        tracks_finish_window_device(wout, table, cap, got, k, dst_format, plan.dst_total, **finish_kw)
+                        got += k
+
+                for pos in range(0, total, window):
+                    k = min(window, total - pos)
+                    tracks_stage_window_device(packed, table, in_rate, out_rate, total, pos, k, out=win, stream=cur)
+                    self.push_device(win, k, stride=win.shape[1])
+                    pull()
+                self.drain()
+                pull()
+            finally:
+                if prev is None:
+                    self.use_own_stream()
+                else:
+                    self.set_stream(prev)
+        need = max(int(e.out_first + e.out_frames) for e in plan.table)
+        if got < need:
+            raise RuntimeError("convert_tracks_to_pcm_streamed: %d output frames where the plan expects %d" % (got, need))
+        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
+        return views, peak[:n], clipped[:n]
+
     def convert_tracks_to_pcm_device(self, tracks, dst_format, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
         packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  The tracks may be integer PCM
@@ -929,12 +1105,7 @@ class Resampler:
         tracks = list(tracks)
         plan, table, out = self._convert_tracks_rows(tracks)
         n = len(tracks)
-        if "gain" in finish_kw and hasattr(finish_kw["gain"], "data_ptr") and self.nstreams > n:  # per-track gains: the idle streams get unity
-            g = finish_kw["gain"]
-            finish_kw["gain"] = torch.cat([g, g.new_ones(self.nstreams - n)])
-        for k in ("peak", "clipped"):
-            if finish_kw.get(k) is not None:
-                raise ValueError("%s is allocated by convert_tracks_to_pcm_device" % k)
+        self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_device")
         finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
         pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]

@@ -361,6 +361,51 @@ int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tr
                              const double *d_gain, int dither, unsigned long long seed, double *d_peak,
                              unsigned long long *d_clipped);
 
+/* Windows: the two passes above on frames [win_first, win_first + win_frames) of the rows, so that a ragged batch runs in memory
+ * proportional to ntracks * window instead of ntracks * longest track.  The rows themselves are VIRTUAL: row_frames is their
+ * length, and no buffer of that size exists.  A handle's output does not depend on how its input is cut into pushes, and dither,
+ * peak and clip count are functions of the absolute frame, so staging window after window into one buffer, pushing it, pulling into
+ * a second one and finishing that at the running output position gives the bytes and statistics of the whole-row calls.
+ *
+ * RRX_tracks_stage_window_device: d_win is [ntracks][win_stride][nch] float32.  For j in [0, win_frames), d_win[t][j] receives, bit
+ * for bit, frame win_first + j of row t as RRX_tracks_stage_device_samples writes it for the same table, source and row_frames: the
+ * copied track, both LPC extensions, the zeros behind ext, and the clamps under a wrong table.  Every frame of the window is written
+ * exactly once; frames [win_frames, win_stride) of each window row and everything outside d_win are untouched; d_packed is only
+ * read, under the read contract of RRX_tracks_stage_device_samples (whole aligned dwords at the two ends of the source, nothing
+ * further out), in all four source formats.  An LPC extension is a serial recursion from the track's edge outwards, so a window that
+ * begins inside one recomputes it from its start: split rows into windows of thousands of frames, not dozens.
+ * device, hip_stream, stream ordering, "only enqueues", refusals and return values: RRX_tracks_stage_device_samples's (with d_win
+ * for d_rows), and RR_INVPARAM, before any device is touched, also for win_first + win_frames above row_frames (or wrapping),
+ * win_stride < win_frames, or ntracks * win_stride * nch of 2^60 samples or more.  win_frames == 0 is RR_OK and does nothing. */
+int RRX_tracks_stage_window_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks,
+                                   int ntracks, int nch, int src_format, const void *d_packed, size_t src_total, size_t row_frames,
+                                   size_t win_first, size_t win_frames, fb_sample_t *d_win, size_t win_stride);
+
+/* RRX_tracks_finish_window_device: d_win ([ntracks][win_stride][nch], float32 or float64) holds, at d_win[t][j], frame win_first + j
+ * of output row t; row_frames is the virtual pitch the whole-row call clamps to.  Of track t's slice [out_first, out_first +
+ * out_frames), clamped exactly as RRX_tracks_finish_device clamps it, the frames inside the window are processed: frame r of the row
+ * has dither index i = r - out_first -- counted from the track's own first output frame, not from the window -- and goes to frame
+ * dst_first + i of the destination.  d_peak and d_clipped accumulate.  So any set of disjoint windows that covers [0, row_frames),
+ * in any order, leaves the bytes and statistics of one RRX_tracks_finish_device call.  Exactly the bytes of the processed samples
+ * are written: a window may begin or end at any byte offset of the packed destination, and the neighbouring sample of the same
+ * track may belong to another window's call.  d_dst NULL measures only.
+ * Refusals: RRX_tracks_finish_device's (with d_win for d_rows) and the three window refusals above.  row_frames == 0 or
+ * win_frames == 0 is RR_OK and does nothing. */
+int RRX_tracks_finish_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                    const void *d_win, size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                    int dst_format, void *d_dst, size_t dst_total, const double *d_gain, int dither,
+                                    unsigned long long seed, double *d_peak, unsigned long long *d_clipped);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: what the two window calls take
+ * from one HOST table entry for the window [win_first, win_first + win_frames) of rows of row_frames frames, computed by the very
+ * functions their kernels call.  stage[10]: the window-relative half-open ranges of the backward extension, the copied track, the
+ * forward extension and the zeros (two values each; adjacent, covering [0, win_frames)), the frame of the packed source that the
+ * first copied frame comes from (no copied frame: the clamped src_first), and how many of the copied frames lie inside the source
+ * (the rest read as zeros).  finish[4]: the window-relative range of the processed frames, the track-relative index of the first
+ * and its destination frame (all zero when the slice does not meet the window); `write` zero is the d_dst NULL case.
+ * RR_INVPARAM for a NULL pointer or a window outside the rows. */
+int RRX_debug_tracks_window_cut(const RRX_track *entry, size_t row_frames, size_t src_total, size_t dst_total, int write,
+                                size_t win_first, size_t win_frames, unsigned long long *stage, unsigned long long *finish);
+
 /* Introspection: isamp_max of rate_base.h:531, frames currently pullable (fifo_occupancy of the last
  * fifo, rate_base.h:447-448), shape of the handle. */
 size_t RRX_isamp_max(const RR_handle *h);

@@ -40,6 +40,20 @@ interleaved, HIP events, medians.  One JSON line per format {"what": "stage", "s
 {"what": "end_to_end", "s16_tracks_ms", "f32_tracks_ms", "s16_over_f32"}.
 
   python tools/perf_tracks.py --pcm [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
+
+--streamed measures the window form ("Windows") on the same workload, S16 tracks in, packed S24 out with dither, and
+appends to profiles/tracks_window_perf.jsonl:
+
+  whole_rows   convert_tracks_to_pcm_device: every row staged, pushed, pulled and finished whole;
+  streamed     convert_tracks_to_pcm_streamed(window=--window, default isamp_max): two windows and no rows.
+
+Each on a fresh handle.  The two results are compared once, byte for byte and statistic for statistic, before anything is timed
+("equal").  One warm-up, `--rounds` rounds interleaved, HIP events, medians and ranges; torch.cuda.max_memory_allocated of each form
+is taken over a call of its own after the warm-up, with the tracks themselves (which both forms are handed) subtracted.  One JSON
+line {"what": "streamed", "window", "isamp_max", "whole_rows_ms", "streamed_ms", "*_rounds", "*_range_ms": [min, max],
+"streamed_over_whole_rows", "whole_rows_peak_bytes", "streamed_peak_bytes", "tracks_bytes", "first_call_ms", "equal", "parts_ms": the passes of the two forms each on its own (streamed_parts)}.
+
+  python tools/perf_tracks.py --streamed [--window FRAMES] [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
 """
 import argparse
 import json
@@ -198,20 +212,141 @@ def pcm_main(a, lens):
             f.write(json.dumps(line) + "\n")
 
 
+def streamed_parts(a, lens, plan, packed, window):
+    """Where the time of the two forms goes: the three passes of the streamed loop each on its own -- every window staged, a fresh
+    handle pushed window by window and pulled (zeros in: the resampler's time does not depend on the samples), every output window
+    finished -- against the whole-row stage and finish calls.  Medians of `--rounds` rounds, HIP events; the whole-row resampling is
+    what is left of that form's time."""
+    n, table = len(lens), plan.to_device("cuda")
+    total = plan.row_frames + -(-2 * FS // FO) + 1
+    cap = total * FO // FS + 2
+    win_out = -(-window * FO // FS)
+    win = torch.zeros((n, window, NCH), dtype=torch.float32, device="cuda")
+    wout = torch.zeros((n, win_out, NCH), dtype=torch.float32, device="cuda")
+    kw = dict(dither=True, seed=a.seed)
+    _, peak, clipped = F.tracks_finish_window_device(wout, table, cap, 0, 0, None, plan.dst_total)
+    dst = torch.empty((plan.dst_total, NCH * 3), dtype=torch.uint8, device="cuda")
+
+    def stage_windows():
+        for pos in range(0, total, window):
+            F.tracks_stage_window_device(packed, table, FS, FO, total, pos, min(window, total - pos), out=win)
+
+    def finish_windows():
+        for pos in range(0, cap, win_out):
+            F.tracks_finish_window_device(wout, table, cap, pos, min(win_out, cap - pos), F.RRX_FMT_S24_3, plan.dst_total, out=dst, peak=peak,
+                                          clipped=clipped, **kw)
+
+    def resample_windows():
+        r = F.Resampler(FS, FO, nch=NCH, nstreams=n)
+        r.set_stream(torch.cuda.current_stream().cuda_stream)
+
+        def pull():
+            while r.available:
+                r.pull_device(wout, win_out, stride=win_out)
+
+        for pos in range(0, total, window):
+            r.push_device(win, min(window, total - pos), stride=window)
+            pull()
+        r.drain()
+        pull()
+        r.close()
+
+    rows = torch.empty((n, plan.row_frames, NCH), dtype=torch.float32, device="cuda")
+    orows = torch.zeros((n, plan.out_row_cap, NCH), dtype=torch.float32, device="cuda")
+    ways = {"stage_windows": stage_windows, "resample_windows": resample_windows, "finish_windows": finish_windows,
+            "stage_whole": lambda: F.tracks_stage_device(packed, table, FS, FO, plan.row_frames, out=rows),
+            "finish_whole": lambda: F.tracks_finish_device(orows, table, F.RRX_FMT_S24_3, plan.dst_total, out=dst, peak=peak, clipped=clipped, **kw)}
+    for fn in ways.values():
+        fn()
+    ms = {k: [] for k in ways}
+    for _ in range(a.rounds):
+        for k, fn in ways.items():
+            ms[k].append(timed(fn)[0])
+    out = {k: round(statistics.median(t), 2) for k, t in ms.items()}
+    out["windows_in"], out["windows_out"] = -(-total // window), -(-cap // win_out)
+    return out
+
+
+def streamed_main(a, lens):
+    plan = F.tracks_plan(FS, FO, lens)
+    v = pcm_source(lens, 15, a.seed)
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + n)
+    tracks = [v[offs[t]:offs[t + 1]] for t in range(len(lens))]
+    kw = dict(dither=True, seed=a.seed)
+    isamp_max = [0]
+
+    def form(streamed):
+        def run(keep=False):
+            r = F.Resampler(FS, FO, nch=NCH, nstreams=len(tracks))
+            isamp_max[0] = r.isamp_max
+            if streamed:
+                res = r.convert_tracks_to_pcm_streamed(tracks, F.RRX_FMT_S24_3, window=a.window, **kw)
+            else:
+                res = r.convert_tracks_to_pcm_device(tracks, F.RRX_FMT_S24_3, **kw)
+            r.close()
+            return res if keep else [y.shape[0] for y in res[0]]
+        return run
+
+    ways = {"whole_rows": form(False), "streamed": form(True)}
+    first = {k: round(timed(fn)[0], 2) for k, fn in ways.items()}        # warm-up: code objects, the caching allocator
+    a_res, b_res = ways["whole_rows"](keep=True), ways["streamed"](keep=True)
+    equal = bool(torch.equal(a_res[0][0]._base, b_res[0][0]._base) and torch.equal(a_res[1].view(torch.int64), b_res[1].view(torch.int64))
+                 and torch.equal(a_res[2], b_res[2]))
+    del a_res, b_res
+    peak = {}
+    for k, fn in ways.items():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        peak[k] = torch.cuda.max_memory_allocated() - before
+    for fn in ways.values():                                             # (the cache was emptied: fill it again before timing)
+        fn()
+    ms = {k: [] for k in ways}
+    for _ in range(a.rounds):
+        for k, fn in ways.items():
+            t, got = timed(fn)
+            ms[k].append(t)
+            assert got == [int(e.out_frames) for e in plan.table], k
+    med = {k: statistics.median(t) for k, t in ms.items()}
+    line = {"what": "streamed", "src_format": "s16", "dst_format": "s24_3", "seed": a.seed, "tracks": len(lens), "nch": NCH, "in_rate": FS,
+            "out_rate": FO, "frames_total": sum(lens), "row_frames": plan.row_frames, "out_row_cap": plan.out_row_cap,
+            "window": a.window if a.window is not None else isamp_max[0], "isamp_max": isamp_max[0]}
+    for k in ways:
+        line[k + "_ms"] = round(med[k], 2)
+        line[k + "_ms_rounds"] = [round(t, 2) for t in ms[k]]
+        line[k + "_range_ms"] = [round(min(ms[k]), 2), round(max(ms[k]), 2)]
+        line[k + "_peak_bytes"] = peak[k]
+    line.update({"streamed_over_whole_rows": round(med["streamed"] / med["whole_rows"], 3), "tracks_bytes": v.numel() * v.element_size(),
+                 "first_call_ms": first, "equal": equal, "rounds": a.rounds, "parts_ms": streamed_parts(a, lens, plan, v, line["window"])})
+    text = json.dumps(line)
+    print(text, flush=True)
+    with open(a.out, "a") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=20240229)
     ap.add_argument("--tracks", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--pcm", action="store_true", help="integer sources of the stage pass instead (see above)")
+    ap.add_argument("--streamed", action="store_true", help="the window form against the whole-row form instead (see above)")
+    ap.add_argument("--window", type=int, default=None, help="--streamed: frames of the input window (default: isamp_max)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "tracks_window_perf.jsonl" if a.streamed else "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("perf_tracks.py needs a GPU: there is nothing to time without one")
     lens = lengths(a.seed, a.tracks)
     print("seed %d: %d tracks, %.1f to %.1f s, %.1f s in all" % (a.seed, len(lens), min(lens) / FS, max(lens) / FS, sum(lens) / FS), flush=True)
+    if a.streamed:
+        return streamed_main(a, lens)
     if a.pcm:
         return pcm_main(a, lens)
     plan = F.tracks_plan(FS, FO, lens)
