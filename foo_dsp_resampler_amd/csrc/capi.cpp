@@ -282,6 +282,12 @@ int RR_drain(RR_handle *h)
   return guarded(h, [&] { return h->eng->drain(); });
 }
 
+int RRX_reset(RR_handle *h)
+{
+  if (!h) return RR_NULLHANDLE;
+  return guarded(h, [&] { return h->eng->reset(); });
+}
+
 void RR_close(RR_handle **h)
 {
   if (h == nullptr || *h == nullptr) return;
@@ -707,6 +713,52 @@ int RRX_tracks_plan(const RR_config *config, const size_t *frames, int ntracks, 
   }
 }
 
+// The library as length-sorted batches.  Sorted descending and cut every nstreams tracks, batch b's row is the ext_frames of its first
+// track: RRX_tracks_plan is still asked, batch by batch, so that row_frames[b] IS its answer and its refusals are this call's.
+int RRX_tracks_batches(const RR_config *config, const size_t *frames, int ntracks, int nstreams, int *order, size_t *row_frames,
+                       int *nbatches, unsigned long long *resampled, unsigned long long *useful)
+{
+  if (!config || !frames || ntracks < 1 || nstreams < 1 || !order || !nbatches) return RR_INVPARAM;
+  try {
+    for (int t = 0; t < ntracks; ++t) order[t] = t;
+    std::stable_sort(order, order + ntracks, [&](int a, int b) { return frames[a] > frames[b]; });
+    std::vector<size_t> sorted(size_t(ntracks), 0);
+    for (int t = 0; t < ntracks; ++t) sorted[size_t(t)] = frames[order[t]];
+    { // the whole library first: the refusals that depend on every track (sums that overflow) are those of one RRX_tracks_plan
+      size_t sum = 0;
+      for (int t = 0; t < ntracks; ++t)
+        if (frames[t] > kTrackFramesMax || (sum += frames[t]) < frames[t]) return RR_INVPARAM;
+    }
+    const int nb = (ntracks - 1) / nstreams + 1;
+    std::vector<RRX_track> table(size_t(std::min(ntracks, nstreams)));
+    unsigned long long res = 0, use = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int t0 = b * nstreams, n = std::min(nstreams, ntracks - t0);
+      size_t row = 0, cap = 0, src = 0, dst = 0;
+      const int rc = RRX_tracks_plan(config, sorted.data() + t0, n, table.data(), &row, &cap, &src, &dst);
+      if (rc != RR_OK) return rc;
+      if (row_frames) row_frames[b] = row;
+      const unsigned long long add = (unsigned long long)nstreams * row;
+      if (row && add / row != (unsigned long long)nstreams) return RR_INVPARAM;
+      if (res + add < res) return RR_INVPARAM;
+      res += add;
+      for (int t = 0; t < n; ++t) {
+        const unsigned long long ext = table[size_t(t)].frames + 2 * table[size_t(t)].lead; // (below 2^37)
+        if (use + ext < use) return RR_INVPARAM;
+        use += ext;
+      }
+    }
+    *nbatches = nb;
+    if (resampled) *resampled = res;
+    if (useful) *useful = use;
+    return RR_OK;
+  } catch (const std::bad_alloc &) {
+    return finish(RR_ENOMEM);
+  } catch (...) {
+    return RR_INTERNAL;
+  }
+}
+
 namespace {
 
 // the device argument of a handle-free device call, checked as RRX_lpc_extrapolate_device checks it: RR_OK, or what the call returns
@@ -946,6 +998,14 @@ int RRX_describe_plan(const RR_config *config, char *buf, size_t cap)
   std::memcpy(buf, s.data(), n);
   buf[n] = 0;
   return int(n);
+}
+
+void RRX_plan_cache_clear(void) { rsmp::plan_cache_clear(); }
+
+int RRX_plan_cache_stats(unsigned long long *hits, unsigned long long *misses, int *entries)
+{
+  rsmp::plan_cache_stats(hits, misses, entries);
+  return RR_OK;
 }
 
 int RRX_describe_dispatch(const RR_config *config, int nchannels, char *buf, size_t cap)

@@ -331,9 +331,7 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
     HIP_TRY(hipMemset(stamps_, 0, 16 * sizeof(unsigned long long)));
   }
   const int ns = int(plan_.stages.size());
-  book_.wr.assign(ns + 1, 0);
-  book_.rd.assign(ns + 1, 0);
-  book_.st.assign(ns, Book::St());
+  init_book();
   rings_.assign(ns + 1, Ring());
   big_.assign(ns, BigDft());
   fuse_.assign(ns, Fuse());
@@ -341,12 +339,9 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
   for (int i = 0; i <= ns; ++i) rings_[i].frames = (i == 0 || i == ns);
   for (int i = 0; i < ns; ++i) {
     const StageSpec &sp = plan_.stages[i];
-    book_.wr[i] = sp.preload; // rate_base.h:417-422
     if (sp.kind == StageKind::Dft) {
-      book_.st[i].remL = sp.remL0;
       if ((rc = init_dft_stage(i)) != kOk) return rc;
     } else if (sp.kind == StageKind::Poly) {
-      book_.st[i].at = sp.order == 0 ? (sp.at0 >> 32) : sp.at0;
       if (!d_poly_ && (rc = upload(plan_.poly_table, &d_poly_)) != kOk) return rc;
     }
   }
@@ -359,6 +354,47 @@ int Engine::init(const Config &cfg, int nch, int nstreams)
   for (int i = 0; i <= ns; ++i)
     if ((rc = ensure_ring(i, std::max<long long>(book_.wr[i], 1))) != kOk) return rc;
   HIP_TRY(hipStreamSynchronize(stream_));
+  return kOk;
+}
+
+// The counters of a handle that has seen no frame yet: what init starts from and reset goes back to.
+void Engine::init_book()
+{
+  const int ns = int(plan_.stages.size());
+  book_ = Book();
+  book_.wr.assign(ns + 1, 0);
+  book_.rd.assign(ns + 1, 0);
+  book_.st.assign(ns, Book::St());
+  for (int i = 0; i < ns; ++i) {
+    const StageSpec &sp = plan_.stages[i];
+    book_.wr[i] = sp.preload; // rate_base.h:417-422
+    if (sp.kind == StageKind::Dft) book_.st[i].remL = sp.remL0;
+    else if (sp.kind == StageKind::Poly) book_.st[i].at = sp.order == 0 ? (sp.at0 >> 32) : sp.at0;
+  }
+}
+
+// Back to the state init left: the counters, and on the device everything init zeroed -- every ring whole, at the capacity it has
+// grown to (stages read history behind wr, and a ring position holds the same absolute indices at any capacity), and the seam rings
+// of the fused pairs.  The tables, workspaces and block tables are written before they are read, here as after init.  Only
+// enqueues: the clears go onto the handle's stream behind everything queued so far, the seam kernels of the side stream included.
+int Engine::reset()
+{
+  if (poisoned_) return kInternal;
+  return fail(reset_impl()); // a clear that was not queued leaves the device behind the counters
+}
+
+int Engine::reset_impl()
+{
+  { int rcj = join_side(); if (rcj) return rcj; }
+  for (const Ring &r : rings_) {
+    if (!r.buf) continue;
+    const size_t bytes = r.frames ? size_t(r.cap) * nch_ * S_ * size_t(eb_) : size_t(r.cap) * C_ * sizeof(double);
+    HIP_TRY(hipMemsetAsync(r.buf, 0, bytes, stream_));
+  }
+  for (const Fuse &fu : fuse_)
+    if (fu.seam) HIP_TRY(hipMemsetAsync(fu.seam, 0, size_t(C_ + 1) * fu.slots * 2 * 32 * sizeof(double), stream_));
+  init_book();
+  mir_begin_ = mir_end_ = 0; // frames still in the host mirror are dropped with the rest (a pending input slot keeps its guard event)
   return kOk;
 }
 

@@ -101,6 +101,9 @@ public:
   int flow_device(const void *ibuf, size_t in_stride, void *obuf, size_t out_stride, size_t isamp, size_t osamp, size_t *iused,
                   size_t *ogen);
   int drain();
+  // Back to the just-opened state (RRX_reset): every later sample is the one a fresh handle gives.  Frames pushed and not pulled,
+  // partial blocks, seam state and the drained state go; the stream, the profiling switch and every allocation stay.  Only enqueues.
+  int reset();
 
   // optional per-kernel timing: HIP events recorded on the launch stream around every stage launch
   void set_profiling(bool on);
@@ -113,6 +116,8 @@ private:
   int init(const Config &cfg, int nch, int nstreams);
   // the steps of init, in order
   int init_streams();
+  void init_book(); // the initial counter state: init and reset both start from it
+  int reset_impl();
   int init_dft_stage(int i);
   int init_fused_pair(int i, size_t &slab_cap);
   int init_polymf(int i);

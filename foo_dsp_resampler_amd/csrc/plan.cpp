@@ -8,6 +8,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
+#include <list>
+#include <mutex>
 #include <sstream>
 
 namespace rsmp {
@@ -194,7 +197,7 @@ const double *half_band_coefs(int n)
   return nullptr;
 }
 
-int make_plan(const Config &cfg, ChainPlan &plan)
+int design_plan(const Config &cfg, ChainPlan &plan)
 {
   plan = ChainPlan();
   plan.cfg = cfg;
@@ -329,6 +332,86 @@ int make_plan(const Config &cfg, ChainPlan &plan)
     ++si;
   }
   return 0;
+}
+
+namespace {
+
+// The six Config fields as the cache compares them: the doubles by bit pattern, so that -0.0 and 0.0, or two NaNs, are never taken
+// for one another (a NaN is refused by the planner anyway, and refusals are not kept).
+struct PlanKey {
+  size_t in_rate, out_rate;
+  uint64_t phase, bandwidth;
+  int allow_aliasing, quality;
+  explicit PlanKey(const Config &c) : in_rate(c.in_rate), out_rate(c.out_rate), allow_aliasing(c.allow_aliasing), quality(c.quality)
+  {
+    std::memcpy(&phase, &c.phase, sizeof phase);
+    std::memcpy(&bandwidth, &c.bandwidth, sizeof bandwidth);
+  }
+  bool operator==(const PlanKey &o) const
+  {
+    return in_rate == o.in_rate && out_rate == o.out_rate && phase == o.phase && bandwidth == o.bandwidth &&
+           allow_aliasing == o.allow_aliasing && quality == o.quality;
+  }
+};
+
+// Process-wide, most recently used first.  A linear search over at most kPlanCacheMax keys costs nothing beside a design.
+struct PlanCache {
+  std::mutex mu;
+  std::list<std::pair<PlanKey, ChainPlan>> plans;
+  unsigned long long hits = 0, misses = 0;
+};
+
+PlanCache &plan_cache()
+{
+  static PlanCache c;
+  return c;
+}
+
+} // namespace
+
+// The design runs outside the lock: converter threads that open different configs at once do not wait for each other.  Two
+// threads that miss on the same config both design it; the plans are the same bits (design_plan is a pure function of cfg),
+// and the second to finish finds the first one's entry and leaves it.
+int make_plan(const Config &cfg, ChainPlan &out)
+{
+  PlanCache &pc = plan_cache();
+  const PlanKey key(cfg);
+  {
+    std::lock_guard<std::mutex> lock(pc.mu);
+    for (auto it = pc.plans.begin(); it != pc.plans.end(); ++it)
+      if (it->first == key) {
+        pc.plans.splice(pc.plans.begin(), pc.plans, it);
+        ++pc.hits;
+        out = it->second;
+        return 0;
+      }
+    ++pc.misses;
+  }
+  const int rc = design_plan(cfg, out);
+  if (rc) return rc; // a refusal is cheap and is not kept
+  std::lock_guard<std::mutex> lock(pc.mu);
+  for (const auto &e : pc.plans)
+    if (e.first == key) return 0;
+  pc.plans.emplace_front(key, out);
+  if (pc.plans.size() > size_t(kPlanCacheMax)) pc.plans.pop_back();
+  return 0;
+}
+
+void plan_cache_clear()
+{
+  PlanCache &pc = plan_cache();
+  std::lock_guard<std::mutex> lock(pc.mu);
+  pc.plans.clear();
+  pc.hits = pc.misses = 0;
+}
+
+void plan_cache_stats(unsigned long long *hits, unsigned long long *misses, int *entries)
+{
+  PlanCache &pc = plan_cache();
+  std::lock_guard<std::mutex> lock(pc.mu);
+  if (hits) *hits = pc.hits;
+  if (misses) *misses = pc.misses;
+  if (entries) *entries = int(pc.plans.size());
 }
 
 std::string ChainPlan::describe() const

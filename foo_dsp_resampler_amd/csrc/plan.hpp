@@ -55,7 +55,17 @@ struct ChainPlan {
 
 // Returns 0 (RR_OK) or 6 (RR_INVPARAM) when the ratio is outside [1/5644.8, 5644.8]
 // (rate_base.h:528) or the config is out of the asserted ranges (rate_base.h:276-280).
+// A pure function of the six Config fields: it designs the filters anew on every call (under a millisecond at phase 50, 50 ms to 0.6 s otherwise).
+int design_plan(const Config &cfg, ChainPlan &out);
+
+// design_plan behind a process-wide cache, which every user of a plan goes through (Engine::init and the host-only calls of
+// capi.cpp).  Keyed by the six Config fields, the doubles by bit pattern; at most kPlanCacheMax plans, the least recently used
+// one evicted; guarded by a mutex (the plugin's converter threads open concurrently, chain.h:36).  `out` is a copy: a cached
+// plan is the same bits as a designed one, and no caller holds a reference into the cache.  Refused configs are not kept.
+constexpr int kPlanCacheMax = 16;
 int make_plan(const Config &cfg, ChainPlan &out);
+void plan_cache_clear(); // drops every plan and zeroes the counters
+void plan_cache_stats(unsigned long long *hits, unsigned long long *misses, int *entries); // any pointer may be null
 
 const double *half_band_coefs(int num_coefs); // 8..13, rate/rate_filters_generic.h:31-70
 

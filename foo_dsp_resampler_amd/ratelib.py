@@ -26,6 +26,7 @@ EXPECTED_SYMBOLS = [
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
+    "RRX_reset", "RRX_tracks_batches", "RRX_plan_cache_clear", "RRX_plan_cache_stats",
 ]
 RRX_FMT_FLOAT, RRX_FMT_DOUBLE = 0, 1  # sample formats of a handle (ratelib_amd.h)
 RRX_FMT_S16, RRX_FMT_S32 = 16, 32      # interleaved signed integer PCM (24-bit audio left-justified in S32)
@@ -203,6 +204,13 @@ def lib():
             L.RRX_tracks_finish_window_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp,
                                                           C.c_int, u64, vp, vp]
             L.RRX_debug_tracks_window_cut.argtypes = [P(RRXTrack), sz, sz, sz, C.c_int, sz, sz, P(u64), P(u64)]
+        if hasattr(L, "RRX_reset"):  # (as above)
+            u64 = C.c_ulonglong
+            L.RRX_reset.argtypes = [vp]
+            L.RRX_tracks_batches.argtypes = [P(RRConfig), P(sz), C.c_int, C.c_int, P(C.c_int), P(sz), P(C.c_int), P(u64), P(u64)]
+            L.RRX_plan_cache_clear.argtypes = []
+            L.RRX_plan_cache_clear.restype = None
+            L.RRX_plan_cache_stats.argtypes = [P(u64), P(u64), P(C.c_int)]
         _lib = L
     return _lib
 
@@ -390,6 +398,76 @@ def _tracks_plan(cfg, lengths):
 def tracks_plan(in_rate, out_rate, lengths, **kw):
     """Host-only: the geometry of a ragged batch of tracks of `lengths` frames (RRX_tracks_plan), as a TracksPlan.  Needs no GPU."""
     return _tracks_plan(_config(in_rate, out_rate, **kw), list(lengths))
+
+
+class TracksBatches:
+    """RRX_tracks_batches' answer: `order` (the track indices by length descending, ties by index), `batches` (the same cut every
+    `nstreams` tracks: a list of lists of indices), `row_frames` (per batch, what tracks_plan gives it), `resampled` (frames the
+    handle resamples: nstreams rows per batch) and `useful` (the tracks' own extended frames).  `padding` = 1 - useful / resampled."""
+
+    def __init__(self, order, nstreams, row_frames, resampled, useful):
+        self.order, self.nstreams, self.row_frames, self.resampled, self.useful = order, nstreams, row_frames, resampled, useful
+        self.batches = [order[k:k + nstreams] for k in range(0, len(order), nstreams)]
+
+    def __len__(self):
+        return len(self.batches)
+
+    @property
+    def padding(self):
+        return 1.0 - self.useful / self.resampled if self.resampled else 0.0
+
+
+def _tracks_batches(cfg, lengths, nstreams):
+    n = len(lengths)
+    if n < 1:
+        raise ValueError("a library needs at least one track")
+    if min(lengths) < 0:
+        raise ValueError("track lengths are frame counts: none may be negative")
+    nstreams = int(nstreams)
+    fr = (C.c_size_t * n)(*[int(v) for v in lengths])
+    order = (C.c_int * n)()
+    rows = (C.c_size_t * (-(-n // max(nstreams, 1))))()
+    nb = C.c_int(0)
+    res, use = C.c_ulonglong(0), C.c_ulonglong(0)
+    _check(lib().RRX_tracks_batches(C.byref(cfg), fr, n, nstreams, order, rows, C.byref(nb), C.byref(res), C.byref(use)), "RRX_tracks_batches")
+    return TracksBatches(list(order), nstreams, list(rows)[:nb.value], res.value, use.value)
+
+
+def tracks_batches(in_rate, out_rate, lengths, nstreams, **kw):
+    """Host-only: a library of tracks of `lengths` frames as the batches of a handle of `nstreams` streams, longest first
+    (RRX_tracks_batches), as a TracksBatches.  No split into batches of at most `nstreams` tracks resamples fewer frames.  Needs no GPU."""
+    return _tracks_batches(_config(in_rate, out_rate, **kw), list(lengths), nstreams)
+
+
+def plan_cache_clear():
+    """Host-only: drop every plan of the process-wide plan cache and zero its counters (RRX_plan_cache_clear)."""
+    lib().RRX_plan_cache_clear()
+
+
+def plan_cache_stats():
+    """Host-only: (hits, misses, entries) of the process-wide plan cache (RRX_plan_cache_stats)."""
+    h, m, e = C.c_ulonglong(0), C.c_ulonglong(0), C.c_int(0)
+    _check(lib().RRX_plan_cache_stats(C.byref(h), C.byref(m), C.byref(e)), "RRX_plan_cache_stats")
+    return h.value, m.value, e.value
+
+
+class _Scratch:
+    """The float32 row and window buffers of a library conversion: each is taken once, at the first batch's size -- the longest,
+    since the batches are sorted -- and handed to the later batches as views (the first call of a process spends 0.7 to 1.5 s
+    allocating rows: DESIGN.md 11)."""
+
+    def __init__(self):
+        self.flat = {}
+
+    def take(self, name, shape, device):
+        import torch
+        n = 1
+        for v in shape:
+            n *= int(v)
+        f = self.flat.get(name)
+        if f is None or f.numel() < n or f.device != device:
+            f = self.flat[name] = torch.empty(max(n, 1), dtype=torch.float32, device=device)
+        return f[:n].view(shape)
 
 
 def _tracks_table(table, ntracks=None):
@@ -635,6 +713,7 @@ class Resampler:
         self.cfg = _config(in_rate, out_rate, **kw)
         self.h = C.c_void_p()
         self._stream = None  # the caller's hipStream_t (an integer) after set_stream, None while the handle uses its own
+        self._used = False   # a data call has moved the handle away from its just-opened state (reset() brings it back)
         if dtype != np.float32:
             _check(self.L.RRX_open_batch_fmt(C.byref(self.cfg), nch, nstreams, -1 if device is None else int(device), _DTYPE_FMT[dtype],
                                              C.byref(self.h)), "RRX_open_batch_fmt")
@@ -700,6 +779,13 @@ class Resampler:
     def sync(self):
         _check(self.L.RRX_sync(self.h), "RRX_sync")
 
+    def reset(self):
+        """Back to the just-opened state (RRX_reset): whatever the handle holds is dropped, and every sample it produces from now
+        on is bit for bit what a fresh Resampler of the same arguments produces.  The stream, the profiling switch and every
+        allocation stay; the call only enqueues.  This is how one handle takes track after track."""
+        _check(self.L.RRX_reset(self.h), "RRX_reset")
+        self._used = False
+
     def profile(self, enable=True):
         _check(self.L.RRX_profile(self.h, 1 if enable else 0), "RRX_profile")
 
@@ -740,6 +826,7 @@ class Resampler:
         x, n = self._host_in(x)
         if n == 0:
             return
+        self._used = True
         if self.integer:
             _check(self.L.RRX_push_samples(self.h, self.sample_format, x.ctypes.data, n, n), "RRX_push_samples")
         elif self.double:
@@ -782,6 +869,7 @@ class Resampler:
         x, n = self._host_in(x)
         out = np.empty((max_out, self.nch), dtype=self.dtype)
         iu, og = C.c_size_t(0), C.c_size_t(0)
+        self._used = True
         if self.integer:
             _check(self.L.RRX_flow_samples(self.h, self.sample_format, x.ctypes.data if n else None, n, out.ctypes.data, max_out, n,
                                            max_out, C.byref(iu), C.byref(og)), "RRX_flow_samples")
@@ -795,6 +883,7 @@ class Resampler:
         return iu.value, out[: og.value]
 
     def drain(self):
+        self._used = True
         _check(self.L.RR_drain(self.h), "RR_drain")
 
     def process(self, x, chunk=None):
@@ -828,6 +917,7 @@ class Resampler:
 
     def push_device(self, t, frames, stride=None):
         p = self._dev_check(t)
+        self._used = True
         if self.integer:
             _check(self.L.RRX_push_device_samples(self.h, self.sample_format, p, stride or frames, frames), "RRX_push_device_samples")
             return
@@ -855,6 +945,7 @@ class Resampler:
         if tin is not None:
             self._dev_check(tin)
         self._dev_check(tout)
+        self._used = True
         if self.integer:
             _check(self.L.RRX_flow_device_samples(self.h, self.sample_format, C.c_void_p(tin.data_ptr()) if tin is not None else None,
                                                   in_stride or in_frames, C.c_void_p(tout.data_ptr()), out_stride or out_cap,
@@ -879,8 +970,8 @@ class Resampler:
         both ends by n_add frames of LPC extrapolation from its first and its last prime = min(frames, prime_len) frames
         (edge_geometry), pushed in isamp_max-sized pieces and drained, and n_drop frames are cut from each end of what comes out.
         Everything runs on torch's current stream of x's device (the handle is switched to it for the call and back afterwards);
-        no sample is copied to the host.  The handle is left drained, as after RR_drain: a track takes a handle of its own, as
-        in the plugin (foo_dsp_rate.cpp:282)."""
+        no sample is copied to the host.  The handle is left drained, as after RR_drain: the plugin gives the next track a handle of
+        its own (foo_dsp_rate.cpp:282); this one takes it after reset()."""
         import torch
         if self.dtype != np.float32:
             raise TypeError("convert_track_device needs a float32 handle (the LPC arithmetic is float32), not %s" % self.dtype)
@@ -960,21 +1051,26 @@ class Resampler:
         # the streams without a track are zero-length tracks: they own no output
         return tracks, _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
 
-    def _convert_tracks_rows(self, tracks):
-        """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch])"""
+    def _convert_tracks_rows(self, tracks, scratch=None):
+        """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch]).
+        `scratch` (a _Scratch): the staged rows and the output rows are views of its buffers instead of new tensors."""
         import torch
         tracks, plan = self._tracks_checked(tracks)
         dev = tracks[0].device
         table = plan.to_device(dev)
         total, cap = plan.row_frames, plan.out_row_cap
-        out = torch.empty((self.nstreams, cap, self.nch), dtype=torch.float32, device=dev)  # (the handle's rows are float32 whatever the tracks are)
+        if scratch is not None:
+            out = scratch.take("out_rows", (self.nstreams, cap, self.nch), dev)
+        else:
+            out = torch.empty((self.nstreams, cap, self.nch), dtype=torch.float32, device=dev)  # (the handle's rows are float32 whatever the tracks are)
         if not total:  # nothing but zero-length tracks
             return plan, table, out
         cur = torch.cuda.current_stream(dev)
         prev = self._stream
         self.set_stream(cur.cuda_stream)
         try:
-            src = tracks_stage_device(torch.cat(tracks).contiguous(), table, self.cfg.in_rate, self.cfg.out_rate, total, stream=cur)
+            rows = None if scratch is None else scratch.take("rows", (self.nstreams, total, self.nch), dev)
+            src = tracks_stage_device(torch.cat(tracks).contiguous(), table, self.cfg.in_rate, self.cfg.out_rate, total, out=rows, stream=cur)
             got = 0
 
             def pull():
@@ -1012,8 +1108,8 @@ class Resampler:
         pieces, drained and pulled, which is convert_track_device's loop.  The zeros behind a shorter track are its drain, so
         every track gets, shape and bits, what convert_track_device gives it on a one-stream handle of its own.  Returns a list
         of tensors [out_frames_i, nch]: views of the handle's output rows.  Runs on torch's current stream of the tracks'
-        device, copies no sample to the host and leaves the handle drained, as convert_track_device does.  The padding is
-        resampled too: batch tracks of similar length."""
+        device, copies no sample to the host and leaves the handle drained, as convert_track_device does (reset() makes it take the
+        next batch).  The padding is resampled too: batch tracks of similar length (tracks_batches, convert_library_to_pcm)."""
         plan, _, out = self._convert_tracks_rows(tracks)
         return [out[t, int(e.out_first):int(e.out_first + e.out_frames)] for t, e in zip(range(len(tracks)), plan.table)]
 
@@ -1026,7 +1122,7 @@ class Resampler:
             if finish_kw.get(k) is not None:
                 raise ValueError("%s is allocated by %s" % (k, who))
 
-    def convert_tracks_to_pcm_streamed(self, tracks, dst_format, window=None, **finish_kw):
+    def convert_tracks_to_pcm_streamed(self, tracks, dst_format, window=None, _scratch=None, **finish_kw):
         """convert_tracks_to_pcm_device in bounded memory: the same inputs, the same (views, peak, clipped), equal bit for bit, and
         no rows.  The tracks are planned, packed and the table uploaded as there; then ONE input window [nstreams, window, nch] and
         ONE output window are allocated besides the packed destination and the statistics, and on torch's current stream the rows
@@ -1055,8 +1151,12 @@ class Resampler:
         total = plan.row_frames + -(-2 * in_rate // out_rate) + 1 if plan.row_frames else 0
         cap = total * out_rate // in_rate + 2                 # (as out_row_cap: drain leaves round(total * out_rate / in_rate) frames in all)
         win_out = -(-window * out_rate // in_rate)            # about what one push makes available; the loop takes any size
-        win = torch.empty((self.nstreams, min(window, max(total, 1)), self.nch), dtype=torch.float32, device=dev)
-        wout = torch.empty((self.nstreams, min(win_out, cap), self.nch), dtype=torch.float32, device=dev)
+        if _scratch is not None:  # (convert_library_to_pcm: the two windows of the first batch serve every batch)
+            win = _scratch.take("win", (self.nstreams, min(window, max(total, 1)), self.nch), dev)
+            wout = _scratch.take("wout", (self.nstreams, min(win_out, cap), self.nch), dev)
+        else:
+            win = torch.empty((self.nstreams, min(window, max(total, 1)), self.nch), dtype=torch.float32, device=dev)
+            wout = torch.empty((self.nstreams, min(win_out, cap), self.nch), dtype=torch.float32, device=dev)
         # nothing to finish yet: allocates (and checks) the destination and the statistics
         pcm, peak, clipped = tracks_finish_window_device(wout, table, cap, 0, 0, dst_format, plan.dst_total, **finish_kw)
         finish_kw.update(out=pcm, peak=peak, clipped=clipped)
@@ -1095,7 +1195,7 @@ class Resampler:
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
 
-    def convert_tracks_to_pcm_device(self, tracks, dst_format, **finish_kw):
+    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
         packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  The tracks may be integer PCM
         themselves (int16, int32, or uint8 packed 24 bit, as in convert_tracks_device): PCM in, PCM out, with float32 only in the
@@ -1103,10 +1203,69 @@ class Resampler:
         views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views."""
         import torch
         tracks = list(tracks)
-        plan, table, out = self._convert_tracks_rows(tracks)
+        plan, table, out = self._convert_tracks_rows(tracks, _scratch)
         n = len(tracks)
         self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_device")
         finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
         pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
+
+    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0):
+        """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut
+        into the length-sorted batches of tracks_batches for the handle's own `nstreams` -- no other split resamples less padding
+        -- and converted batch after batch, with reset() before every batch whenever the handle has been used.  Each batch runs
+        through convert_tracks_to_pcm_device, or with `window` (frames) through convert_tracks_to_pcm_streamed in bounded memory.
+        No handle is opened, and the row and window buffers are taken once, at the first and longest batch's size, and reused as
+        views by the later batches.
+
+        `gain`: None, a float, or one value per track in the caller's order (a sequence, or a float64 device tensor [ntracks]).
+        Dither: the track of sorted rank r is stream r of the library as ONE ragged batch -- batch b is finished with
+        seed + b * nstreams * nch * 0xBF58476D1CE4E5B9 (mod 2^64), which puts that track on dither channel r * nch + ch -- so its
+        bytes and statistics are those of a one-stream finish_device on its slice with seed + r * nch * 0xBF58476D1CE4E5B9,
+        whatever `nstreams` is.  Returns (per-track PCM tensors in the caller's order, peak [ntracks, nch], clipped [ntracks, nch]).
+        Runs on torch's current stream and copies no sample to the host."""
+        import torch
+        tracks = list(tracks)
+        n, S = len(tracks), self.nstreams
+        if n < 1:
+            raise ValueError("a library needs at least one track")
+        for x in tracks:
+            if not hasattr(x, "data_ptr") or x.dim() != 2:
+                raise ValueError("expected [frames, nch] device tensors")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed must fit 64 unsigned bits")
+        dev = tracks[0].device
+        if gain is not None:
+            if hasattr(gain, "data_ptr"):
+                if gain.dtype != torch.float64 or tuple(gain.shape) != (n,) or gain.device != dev:
+                    raise TypeError("gain must be a float, %d floats, or a float64 tensor [%d] on %s" % (n, n, dev))
+            else:
+                vals = [float(gain)] * n if not hasattr(gain, "__len__") else [float(g) for g in gain]
+                if len(vals) != n:
+                    raise ValueError("%d gains for %d tracks" % (len(vals), n))
+                gain = torch.tensor(vals, dtype=torch.float64, device=dev)
+        lib_batches = _tracks_batches(self.cfg, [x.shape[0] for x in tracks], S)
+        peak = torch.zeros((n, self.nch), dtype=torch.float64, device=dev)
+        clipped = torch.zeros((n, self.nch), dtype=torch.int64, device=dev)
+        views = [None] * n
+        scratch = _Scratch()
+        for b, idx in enumerate(lib_batches.batches):
+            if self._used:
+                self.reset()
+            kw = {"dither": dither, "seed": (seed + b * S * self.nch * 0xBF58476D1CE4E5B9) % (1 << 64), "_scratch": scratch}
+            where = torch.tensor(idx, dtype=torch.int64, device=dev)
+            if gain is not None:
+                kw["gain"] = gain[where].contiguous()
+            batch = [tracks[i] for i in idx]
+            if window is None:
+                v, p, c = self.convert_tracks_to_pcm_device(batch, dst_format, **kw)
+            else:
+                v, p, c = self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **kw)
+            peak[where] = p
+            clipped[where] = c
+            if v is not None:
+                for i, vi in zip(idx, v):
+                    views[i] = vi
+        return (None if dst_format is None else views), peak, clipped

@@ -62,6 +62,24 @@ int RRX_pull_strided(RR_handle *h, fb_sample_t *obuf, size_t out_stride, size_t 
 int RRX_set_stream(RR_handle *h, void *hip_stream);
 int RRX_sync(RR_handle *h);
 
+/* Back to the just-opened state, so that one handle serves track after track (the reference has no such call: it closes and
+ * opens, chain.h:26-29).  After RRX_reset the handle behaves as one just returned by the open call that made it -- same config,
+ * channels, streams, device and sample format -- and for any sequence of data calls every sample it produces equals, bit for bit,
+ * what a fresh handle produces for that sequence, in all four handle formats, through host and device calls.  The counters are
+ * fresh as well: RRX_available is 0, RRX_isamp_max is unchanged, a later drain yields round(total_in * out_rate / in_rate), and
+ * the wrap of the counters by whole seconds behaves as on a fresh handle; RRX_track_geometry and RRX_tracks_plan therefore
+ * describe a reset handle unchanged.
+ *   Discarded: frames pushed and not pulled (those still in the page-locked host mirror of an RR_push included), partial blocks,
+ *   seam state, and the drained state.
+ *   Kept: the stream set by RRX_set_stream, the profiling switch and its records, and every allocation -- rings keep the capacity
+ *   they have grown to, which is what makes a reset cheaper than RR_close + RR_open.
+ * The call only enqueues: no allocation, no host synchronisation.  All clearing is ordered on the handle's stream behind
+ * everything queued so far, so output buffers of earlier *_device pulls are untouched and receive what was queued for them; the
+ * stream-ordering contract is that of the *_device calls.
+ * Returns RR_NULLHANDLE for NULL.  A poisoned handle (RRX_debug_fail_alloc) returns RR_INTERNAL and stays poisoned, like every
+ * data call.  A reset of a fresh handle, or a second reset in a row, is RR_OK and changes nothing observable. */
+int RRX_reset(RR_handle *h);
+
 /* Per-kernel timing for benchmarks: while enabled, every stage launch is bracketed by HIP events on the
  * handle's stream.  RRX_profile_read synchronises, returns the summed duration and launch count of the
  * chain's dominant kernel ("hot": the fused dft->polyphase kernel, or the dft stage) and of all other
@@ -291,6 +309,22 @@ int RRX_track_geometry(const RR_config *config, size_t frames, size_t *lead, siz
 int RRX_tracks_plan(const RR_config *config, const size_t *frames, int ntracks, RRX_track *table, size_t *row_frames,
                     size_t *out_row_cap, size_t *src_total, size_t *dst_total);
 
+/* Host-only (no GPU needed): a library of `ntracks` tracks as the batches of a handle of `nstreams` streams.  A batch handle
+ * resamples nstreams rows of its longest track's length whatever the other tracks hold, so tracks of like length belong together.
+ *   order[ntracks]: the track indices sorted by frames descending, ties by index ascending (ext_frames is monotonic in frames,
+ *   so this is also descending in row length).
+ *   Batch b is order[b * nstreams, min((b + 1) * nstreams, ntracks)); *nbatches = ceil(ntracks / nstreams).
+ *   row_frames[b] (NULL, or room for *nbatches entries): what RRX_tracks_plan returns for batch b.
+ *   *resampled = sum over b of nstreams * row_frames[b], the frames the handle resamples (it has nstreams streams whatever the
+ *   last batch holds); *useful = sum over t of ext_frames[t].  Either may be NULL.  1 - useful / resampled is the padding share.
+ * This split minimises sum_b row_frames[b], and with it *resampled, over every partition of the tracks into batches of at most
+ * nstreams tracks: some batch must hold the longest track and costs its row; filling that batch with the next longest tracks
+ * leaves a remainder whose k-th longest track is no longer than under any other choice, and no partition has fewer batches.
+ * Returns RR_INVPARAM for NULL config, frames, order or nbatches, ntracks < 1, nstreams < 1, and whatever RRX_tracks_plan
+ * refuses (a config the planner refuses, a track above 2^36 frames, sums that overflow). */
+int RRX_tracks_batches(const RR_config *config, const size_t *frames, int ntracks, int nstreams, int *order, size_t *row_frames,
+                       int *nbatches, unsigned long long *resampled, unsigned long long *useful);
+
 /* One pass from the packed tracks (d_packed: [src_total][nch] float32) to the rows a batch handle is pushed from (d_rows:
  * [ntracks][row_frames][nch]).  Row t receives, with ext = lead + frames + lead:
  *   [lead, lead + frames)        the track, copied;
@@ -417,6 +451,19 @@ int RRX_streams(const RR_handle *h);
  * (what rate_init decides, rate/rate_base.h:247-423).  Returns the length written (without the
  * terminator), or the negated RR_error on failure; the text is truncated to cap-1 bytes. */
 int RRX_describe_plan(const RR_config *config, char *buf, size_t cap);
+
+/* The plan cache.  Designing the filters of a config takes under a millisecond at phase 50 and 50 ms to 0.6 s at other phase
+ * settings, and the plan is a pure function of the six RR_config fields.  Every call of this library that needs a plan -- the open calls and the
+ * host-only calls RRX_describe_plan, RRX_describe_dispatch, RRX_plan_table, RRX_track_geometry, RRX_tracks_plan,
+ * RRX_tracks_batches -- takes it from a process-wide cache keyed by those fields (the doubles by bit pattern): at most 16 plans,
+ * the least recently used evicted, guarded by a mutex so that threads may open concurrently (chain.h:36).  A cached plan is the
+ * same bits as a designed one; configs the planner refuses are not kept.  Only the host-side design is shared: every handle
+ * still uploads its own device tables.
+ * RRX_plan_cache_clear drops every plan and zeroes the counters.  RRX_plan_cache_stats reports lookups served from the cache,
+ * lookups that had to design (refused configs included), and the plans held now; any pointer may be NULL; it returns RR_OK.
+ * Both are host-only. */
+void RRX_plan_cache_clear(void);
+int RRX_plan_cache_stats(unsigned long long *hits, unsigned long long *misses, int *entries);
 
 /* Host-only (no GPU needed): which kernel form the first stage pair of `config` gets on handles of `nchannels` channels per
  * stream, as JSON: {"sub_blocked": false} or {"sub_blocked": true, "two_round": .., "nsub": .., "Vs": .., "V": .., "taps": ..,

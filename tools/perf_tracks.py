@@ -54,6 +54,26 @@ line {"what": "streamed", "window", "isamp_max", "whole_rows_ms", "streamed_ms",
 "streamed_over_whole_rows", "whole_rows_peak_bytes", "streamed_peak_bytes", "tracks_bytes", "first_call_ms", "equal", "parts_ms": the passes of the two forms each on its own (streamed_parts)}.
 
   python tools/perf_tracks.py --streamed [--window FRAMES] [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
+
+--library measures a library on ONE handle ("Libraries"): the same LCG lengths, 256 tracks (--tracks) on a handle of 64
+streams (--streams), S16 tracks in, packed S24 out with dither and per-track gains, at phase 50 and at phase 25, and appends to
+profiles/tracks_library_perf.jsonl:
+
+  (a) one_handle     convert_library_to_pcm on one handle, opened once before anything is timed: sorted batches, a reset between
+                     them, rows reused;
+  (b) fresh_sorted   the same sorted batches, each through convert_tracks_to_pcm_device on a fresh handle that is opened and
+                     closed: what a caller writes without RRX_reset;
+  (c) fresh_given    the same tracks cut into batches in their given order, on fresh handles.
+
+(a) and (b) are compared first, byte for byte and statistic for statistic ("equal"); (c) puts a track on another dither channel, so
+it is compared with the two in a pass without dither ("equal_without_dither").  One warm-up, `--rounds` rounds interleaved, HIP
+events, medians and ranges.  Host times (time.perf_counter, the handle waited for): one reset against RR_close + RRX_open_batch on
+the used handle, and the first open of the config on an empty plan cache against the second.  One JSON line per phase {"what":
+"library", "phase", "tracks", "streams", "batches", "padding_sorted", "padding_given", "one_handle_ms", "fresh_sorted_ms",
+"fresh_given_ms", "*_rounds", "*_range_ms", "one_handle_over_fresh_sorted", "reset_ms", "close_open_ms", "first_open_ms",
+"second_open_ms", "plan_cache", "first_call_ms", "equal", "equal_without_dither"}.
+
+  python tools/perf_tracks.py --library [--seed 20240229] [--tracks 256] [--streams 64] [--rounds 5] [--out FILE]
 """
 import argparse
 import json
@@ -329,22 +349,135 @@ def streamed_main(a, lens):
         f.write(text + "\n")
 
 
+def library_main(a, lens):
+    S, n = a.streams, len(lens)
+    v = pcm_source(lens, 15, a.seed)
+    offs = [0]
+    for k in lens:
+        offs.append(offs[-1] + k)
+    tracks = [v[offs[t]:offs[t + 1]] for t in range(n)]
+    gains = [0.5 + (t % 7) * 0.125 for t in range(n)]
+    gain_dev = torch.tensor(gains, dtype=torch.float64, device="cuda")
+    K = 0xBF58476D1CE4E5B9
+    given = [list(range(k, min(k + S, n))) for k in range(0, n, S)]
+    for phase in (50.0, 25.0):
+        tb = F.tracks_batches(FS, FO, lens, S, phase=phase)
+        given_rows = [F.tracks_plan(FS, FO, [lens[i] for i in idx], phase=phase).row_frames for idx in given]
+        padding_given = 1.0 - tb.useful / (S * sum(given_rows))
+        # host times of the opens, before anything else warms the plan cache for this config
+        F.plan_cache_clear()
+        t0 = time.perf_counter()
+        r = F.Resampler(FS, FO, nch=NCH, nstreams=S, phase=phase)
+        first_open = (time.perf_counter() - t0) * 1e3
+        r.close()
+        t0 = time.perf_counter()
+        r = F.Resampler(FS, FO, nch=NCH, nstreams=S, phase=phase)
+        second_open = (time.perf_counter() - t0) * 1e3
+        one = [r]                                            # the one handle of (a); replaced by the close + open measurement below
+
+        def one_handle(dither=True, keep=False):
+            res = one[0].convert_library_to_pcm(tracks, F.RRX_FMT_S24_3, gain=gain_dev, dither=dither, seed=a.seed)
+            return res if keep else [y.shape[0] for y in res[0]]
+
+        def fresh(batches):
+            def run(dither=True, keep=False):
+                views, peak, clipped = [None] * n, [None] * n, [None] * n
+                for b, idx in enumerate(batches):
+                    h = F.Resampler(FS, FO, nch=NCH, nstreams=S, phase=phase)
+                    w, p, c = h.convert_tracks_to_pcm_device([tracks[i] for i in idx], F.RRX_FMT_S24_3, gain=gain_dev[idx].contiguous(),
+                                                             dither=dither, seed=(a.seed + b * S * NCH * K) % (1 << 64))
+                    h.close()
+                    for k, i in enumerate(idx):
+                        views[i], peak[i], clipped[i] = w[k], p[k], c[k]
+                return (views, torch.stack(peak), torch.stack(clipped)) if keep else [y.shape[0] for y in views]
+            return run
+
+        def same(x, y):
+            return bool(all(torch.equal(p, q) for p, q in zip(x[0], y[0])) and torch.equal(x[1].view(torch.int64), y[1].view(torch.int64))
+                        and torch.equal(x[2], y[2]))
+
+        ways = {"one_handle": one_handle, "fresh_sorted": fresh(tb.batches), "fresh_given": fresh(given)}
+        first = {k: round(timed(fn)[0], 2) for k, fn in ways.items()}        # warm-up: code objects, the caching allocator
+        x = one_handle(keep=True)
+        y = ways["fresh_sorted"](keep=True)
+        equal = same(x, y)
+        del x, y
+        x = one_handle(dither=False, keep=True)
+        equal_plain = True
+        for k in ("fresh_sorted", "fresh_given"):
+            y = ways[k](dither=False, keep=True)
+            equal_plain = equal_plain and same(x, y)
+            del y
+        del x
+        want = [F.track_geometry(FS, FO, k, phase=phase)[3] for k in lens]
+        ms = {k: [] for k in ways}
+        for _ in range(a.rounds):
+            for k, fn in ways.items():
+                t, got = timed(fn)
+                ms[k].append(t)
+                assert got == want, k
+        med = {k: statistics.median(t) for k, t in ms.items()}
+        # one reset against close + open, on the handle the library has just used
+        reset_ms, close_open_ms = [], []
+        for _ in range(a.rounds):
+            one_handle()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            one[0].reset()
+            one[0].sync()
+            reset_ms.append((time.perf_counter() - t0) * 1e3)
+            one_handle()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            one[0].close()
+            one[0] = F.Resampler(FS, FO, nch=NCH, nstreams=S, phase=phase)
+            one[0].sync()
+            close_open_ms.append((time.perf_counter() - t0) * 1e3)
+        one[0].close()
+        line = {"what": "library", "phase": phase, "src_format": "s16", "dst_format": "s24_3", "seed": a.seed, "tracks": n, "streams": S,
+                "nch": NCH, "in_rate": FS, "out_rate": FO, "frames_total": sum(lens), "batches": len(tb), "row_frames": tb.row_frames,
+                "padding_sorted": round(tb.padding, 4), "padding_given": round(padding_given, 4)}
+        for k in ways:
+            line[k + "_ms"] = round(med[k], 2)
+            line[k + "_ms_rounds"] = [round(t, 2) for t in ms[k]]
+            line[k + "_range_ms"] = [round(min(ms[k]), 2), round(max(ms[k]), 2)]
+        hits, misses, entries = F.plan_cache_stats()
+        line.update({"one_handle_over_fresh_sorted": round(med["one_handle"] / med["fresh_sorted"], 3),
+                     "reset_ms": round(statistics.median(reset_ms), 3), "reset_ms_rounds": [round(t, 3) for t in reset_ms],
+                     "close_open_ms": round(statistics.median(close_open_ms), 3), "close_open_ms_rounds": [round(t, 3) for t in close_open_ms],
+                     "first_open_ms": round(first_open, 2), "second_open_ms": round(second_open, 2),
+                     "plan_cache": {"hits": hits, "misses": misses, "entries": entries},
+                     "first_call_ms": first, "equal": equal, "equal_without_dither": equal_plain, "rounds": a.rounds})
+        text = json.dumps(line)
+        print(text, flush=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=20240229)
-    ap.add_argument("--tracks", type=int, default=64)
+    ap.add_argument("--tracks", type=int, default=None, help="default 64; --library: 256")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--pcm", action="store_true", help="integer sources of the stage pass instead (see above)")
     ap.add_argument("--streamed", action="store_true", help="the window form against the whole-row form instead (see above)")
     ap.add_argument("--window", type=int, default=None, help="--streamed: frames of the input window (default: isamp_max)")
+    ap.add_argument("--library", action="store_true", help="a library on one handle against fresh handles per batch instead (see above)")
+    ap.add_argument("--streams", type=int, default=64, help="--library: streams of the handle")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.tracks is None:
+        a.tracks = 256 if a.library else 64
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "tracks_window_perf.jsonl" if a.streamed else "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "tracks_library_perf.jsonl" if a.library else "tracks_window_perf.jsonl" if a.streamed else
+                             "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("perf_tracks.py needs a GPU: there is nothing to time without one")
     lens = lengths(a.seed, a.tracks)
     print("seed %d: %d tracks, %.1f to %.1f s, %.1f s in all" % (a.seed, len(lens), min(lens) / FS, max(lens) / FS, sum(lens) / FS), flush=True)
+    if a.library:
+        return library_main(a, lens)
     if a.streamed:
         return streamed_main(a, lens)
     if a.pcm:
