@@ -8,11 +8,12 @@ no CPU fallback: if the library (or a GPU) is missing, calls fail.
 from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_dispatch, describe_plan, edge_geometry, lib, lib_path,  # noqa: F401
                       lpc_extrapolate_device, finish_device, plan_table, RRXTrack, TracksPlan, track_geometry, tracks_plan,
                       tracks_stage_device, tracks_finish_device, tracks_stage_window_device, tracks_finish_window_device,
-                      TracksBatches, tracks_batches, plan_cache_clear, plan_cache_stats, RR_BEST, RR_NORM, RRX_FMT_FLOAT, RRX_FMT_DOUBLE, RRX_FMT_S16, RRX_FMT_S32, RRX_FMT_S24_3, EXPECTED_SYMBOLS)
+                      TracksBatches, tracks_batches, plan_cache_clear, plan_cache_stats, RR_BEST, RR_NORM, RRX_FMT_FLOAT, RRX_FMT_DOUBLE, RRX_FMT_S16, RRX_FMT_S32, RRX_FMT_S24_3, EXPECTED_SYMBOLS,
+                      finish_shaped_device, tracks_finish_shaped_device, NOISE_SHAPES, RRX_SHAPE_MAX_ORDER)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
            "TracksBatches", "tracks_batches", "plan_cache_clear", "plan_cache_stats",
            "lib_path",
            "available_symbols", "RR_BEST", "RR_NORM", "RRX_FMT_FLOAT", "RRX_FMT_DOUBLE", "RRX_FMT_S16", "RRX_FMT_S32", "RRX_FMT_S24_3",
-           "EXPECTED_SYMBOLS"]
+           "EXPECTED_SYMBOLS", "finish_shaped_device", "tracks_finish_shaped_device", "NOISE_SHAPES", "RRX_SHAPE_MAX_ORDER"]

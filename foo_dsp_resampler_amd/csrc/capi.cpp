@@ -4,11 +4,13 @@
 
 #include "engine.hpp"
 #include "finish.hpp"
+#include "finish_shaped.hpp"
 #include "lpc.hpp"
 #include "tracks.hpp"
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -873,6 +875,141 @@ int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tr
   a.bits = !d_dst ? 31 : dst_format == RRX_FMT_S16 ? 15 : dst_format == RRX_FMT_S24_3 ? 23 : 31; // measure only: the S32 grid
   a.dither = dither != 0;
   return rsmp::launch_tracks_finish(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+namespace {
+
+bool pcm_format(int f) { return f == RRX_FMT_S16 || f == RRX_FMT_S24_3 || f == RRX_FMT_S32; }
+int pcm_bits(int f) { return f == RRX_FMT_S16 ? 15 : f == RRX_FMT_S24_3 ? 23 : 31; }
+
+// the filter of the shaped calls: RR_INVPARAM for a NULL pointer, an order outside 1..RRX_SHAPE_MAX_ORDER or a non-finite
+// coefficient; `out` gets the coefficients, padded with zeros
+int shaped_filter(const double *coefs, int order, double (&out)[rsmp::kShapeMaxOrder])
+{
+  static_assert(RRX_SHAPE_MAX_ORDER == rsmp::kShapeMaxOrder, "the header's constant is the kernels'");
+  if (!coefs || order < 1 || order > RRX_SHAPE_MAX_ORDER) return RR_INVPARAM;
+  for (int k = 0; k < rsmp::kShapeMaxOrder; ++k) {
+    out[k] = k < order ? coefs[k] : 0.0;
+    if (!std::isfinite(out[k])) return RR_INVPARAM;
+  }
+  return RR_OK;
+}
+
+// RRX_finish_shaped_device / RRX_debug_finish_shaped_host: everything that can be refused from the arguments alone
+int finish_shaped_args(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams,
+                       size_t frames, int nch, const double *gain, int dither, unsigned long long seed, unsigned long long first_frame,
+                       const double *coefs, int order, size_t segment, const double *state_in, double *state_out, double *peak,
+                       unsigned long long *clipped, rsmp::ShapedArgs &a)
+{
+  if (!pcm_format(dst_format)) return RR_INVPARAM; // measure only included: the statistics are those of the write
+  int rc = shaped_filter(coefs, order, a.coefs);
+  if (rc != RR_OK) return rc;
+  rsmp::FinishArgs f;
+  rc = finish_args(src_format, src, src_stride, dst_format, dst, dst_stride, nstreams, frames, nch, gain, dither, seed, first_frame, peak,
+                   clipped, f);
+  if (rc != RR_OK) return rc;
+  if (!state_in && !rsmp::shaped_restarts(first_frame, segment)) return RR_INVPARAM; // a call without a state begins a segment
+  if (state_in && state_out) { // [nstreams * nch][16] doubles each, nstreams * nch < 2^60 / frames: no wrap for a buffer that exists
+    const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
+    const uintptr_t bytes = uintptr_t(nstreams) * uintptr_t(nch) * rsmp::kShapeMaxOrder * sizeof(double);
+    if (x < y ? y - x < bytes : x - y < bytes) return RR_INVPARAM;
+  }
+  a.src = f.src;
+  a.dst = f.dst;
+  a.gain = f.gain;
+  a.peak = f.peak;
+  a.clipped = f.clipped;
+  a.state_in = state_in;
+  a.state_out = state_out;
+  a.src_stride = f.src_stride;
+  a.dst_stride = f.dst_stride;
+  a.frames = frames;
+  a.seed = seed;
+  a.first_frame = first_frame;
+  a.segment = segment;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  a.src_double = f.src_double;
+  a.bits = pcm_bits(dst_format);
+  a.dither = f.dither;
+  a.order = order;
+  return RR_OK;
+}
+
+} // namespace
+
+// The output stage with noise-shaped dither (finish_shaped.hip).  Refusals first, as in RRX_finish_device.
+int RRX_finish_shaped_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int dst_format, void *d_dst,
+                             size_t dst_stride, int nstreams, size_t frames, int nch, const double *d_gain, int dither, unsigned long long seed,
+                             unsigned long long first_frame, const double *coefs, int order, size_t segment, const double *d_state_in,
+                             double *d_state_out, double *d_peak, unsigned long long *d_clipped)
+{
+  rsmp::ShapedArgs a;
+  const int rc = finish_shaped_args(src_format, d_src, src_stride, dst_format, d_dst, dst_stride, nstreams, frames, nch, d_gain, dither, seed,
+                                    first_frame, coefs, order, segment, d_state_in, d_state_out, d_peak, d_clipped, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_finish_shaped(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_finish_shaped_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams,
+                                 size_t frames, int nch, const double *gain, int dither, unsigned long long seed,
+                                 unsigned long long first_frame, const double *coefs, int order, size_t segment, const double *state_in,
+                                 double *state_out, double *peak, unsigned long long *clipped)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::ShapedArgs a;
+  const int rc = finish_shaped_args(src_format, src, src_stride, dst_format, dst, dst_stride, nstreams, frames, nch, gain, dither, seed,
+                                    first_frame, coefs, order, segment, state_in, state_out, peak, clipped, a);
+  if (rc != RR_OK) return rc;
+  if (frames) rsmp::finish_shaped_host(a);
+  return RR_OK;
+}
+
+// The shaped output stage of a ragged batch (finish_shaped.hip).  Refusals first, as in RRX_tracks_finish_device.
+int RRX_tracks_finish_shaped_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                    const void *d_rows, size_t row_frames, int dst_format, void *d_dst, size_t dst_total, const double *d_gain,
+                                    int dither, unsigned long long seed, const double *coefs, int order, size_t segment, double *d_peak,
+                                    unsigned long long *d_clipped)
+{
+  rsmp::TracksShapedArgs a;
+  if (!d_tracks || !d_rows || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (!pcm_format(dst_format)) return RR_INVPARAM; // measure only included
+  if (shaped_filter(coefs, order, a.coefs) != RR_OK) return RR_INVPARAM;
+  if (!d_dst && !d_peak && !d_clipped) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks) || (d_dst && dst_total > most)) return RR_INVPARAM;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames) return RR_OK;
+  const int rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  a.t.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.t.src = d_rows;
+  a.t.dst = d_dst;
+  a.t.gain = d_gain;
+  a.t.peak = d_peak;
+  a.t.clipped = d_clipped;
+  a.t.row_frames = row_frames;
+  a.t.dst_total = dst_total;
+  a.t.seed = seed;
+  a.t.ntracks = ntracks;
+  a.t.nch = nch;
+  a.t.src_double = src_format == RRX_FMT_DOUBLE;
+  a.t.bits = pcm_bits(dst_format);
+  a.t.dither = dither != 0;
+  a.segment = segment;
+  a.order = order;
+  return rsmp::launch_tracks_finish_shaped(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
 namespace {

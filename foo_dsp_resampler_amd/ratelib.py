@@ -21,6 +21,7 @@ EXPECTED_SYMBOLS = [
     "RRX_flow_device_samples",
     "RRX_lpc_extrapolate_device", "RRX_edge_geometry",
     "RRX_finish_device", "RRX_debug_finish_host",
+    "RRX_finish_shaped_device", "RRX_debug_finish_shaped_host", "RRX_tracks_finish_shaped_device",
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
@@ -34,6 +35,17 @@ RRX_FMT_S24_3 = 24                     # packed 3-byte PCM: a destination of fin
 _FMT_DTYPE = {RRX_FMT_FLOAT: np.dtype(np.float32), RRX_FMT_DOUBLE: np.dtype(np.float64), RRX_FMT_S16: np.dtype(np.int16),
               RRX_FMT_S32: np.dtype(np.int32)}
 _DTYPE_FMT = {d: f for f, d in _FMT_DTYPE.items()}
+RRX_SHAPE_MAX_ORDER = 16
+
+NOISE_SHAPES = {
+    "lipshitz5": (2.033, -2.165, 1.959, -1.590, 0.6149),
+    "wannamaker3": (1.623, -0.982, 0.109),
+    "wannamaker9": (2.412, -3.370, 3.937, -4.174, 3.353, -2.205, 1.281, -0.569, 0.0847),
+}
+"""Error-feedback filters for noise-shaped dither (finish_shaped_device, `shaping=`): the published 44.1 kHz designs -- Lipshitz's
+5-tap improved E-weighted filter and Wannamaker's 3-tap and 9-tap F-weighted filters.  They spare the ear's most sensitive band
+at 44.1 kHz only; for another rate the caller brings coefficients: wherever a name is accepted, so is any sequence of 1 to 16
+finite floats."""
 
 
 class RRConfig(C.Structure):
@@ -189,6 +201,13 @@ def lib():
             host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_int, u64, u64, vp, vp]
             L.RRX_finish_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_finish_host.argtypes = host
+        if hasattr(L, "RRX_finish_shaped_device"):  # (as above)
+            u64 = C.c_ulonglong
+            host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_int, u64, u64, vp, C.c_int, sz, vp, vp, vp, vp]
+            L.RRX_finish_shaped_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_finish_shaped_host.argtypes = host
+            L.RRX_tracks_finish_shaped_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, sz, vp, C.c_int, u64,
+                                                          vp, C.c_int, sz, vp, vp]
         if hasattr(L, "RRX_tracks_plan"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_track_geometry.argtypes = [P(RRConfig), sz, P(sz), P(sz), P(sz), P(sz)]
@@ -352,6 +371,93 @@ def finish_device(x, dst_format, gain=None, dither=False, seed=0, first_frame=0,
                                    C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed, first_frame,
                                    C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_finish_device")
     return out, peak, clipped
+
+
+def _shaping(shaping, segment):
+    """`shaping` (a name of NOISE_SHAPES or 1..16 finite floats) as a ctypes array of doubles, and `segment` checked"""
+    coefs = NOISE_SHAPES.get(shaping) if isinstance(shaping, str) else shaping
+    if coefs is None:
+        raise ValueError("unknown noise shape %r (one of %s, or 1 to %d coefficients)" % (shaping, sorted(NOISE_SHAPES), RRX_SHAPE_MAX_ORDER))
+    coefs = [float(v) for v in coefs]
+    if not 1 <= len(coefs) <= RRX_SHAPE_MAX_ORDER or not all(np.isfinite(coefs)):
+        raise ValueError("a noise shape is 1 to %d finite coefficients" % RRX_SHAPE_MAX_ORDER)
+    segment = int(segment)
+    if not 0 <= segment < 1 << 64:
+        raise ValueError("segment is a frame count, or 0 for no restart")
+    return (C.c_double * len(coefs))(*coefs), segment
+
+
+def finish_shaped_device(x, dst_format, shaping, segment=65536, gain=None, dither=True, seed=0, first_frame=0, state=None, out=None, peak=None,
+                         clipped=None, stream=None):
+    """finish_device with noise-shaped dither (RRX_finish_shaped_device): the requantisation error of a channel's previous frames
+    is fed back through the filter `shaping` -- a name of NOISE_SHAPES, or 1 to 16 finite floats -- and the error history of every
+    channel restarts at every absolute frame that is a multiple of `segment` (0: never, one serial chain per channel).
+
+    `x`, `gain`, `seed`, `first_frame`, `peak`, `clipped` and `stream` are finish_device's.  `dst_format` is RRX_FMT_S16,
+    RRX_FMT_S24_3 or RRX_FMT_S32, never None: the statistics depend on the format.  `out=False` measures only.  `state`: None, or the
+    float64 [nstreams, nch, 16] tensor an earlier call returned; a call that does not begin a segment needs it, and contiguous
+    ascending calls that hand it on leave the bytes and statistics of one call.  Returns (out, peak, clipped, state): `state` is a
+    NEW tensor, never the one passed in (the call must not read and write one buffer).  The call only enqueues."""
+    import torch
+    shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    dt = str(x.dtype)
+    if not (dt.endswith("float32") or dt.endswith("float64")):
+        raise TypeError("%s buffer: the output stage reads float32 or float64 frames" % (x.dtype,))
+    if not x.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+    coefs, segment = _shaping(shaping, segment)
+    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
+    seed, first_frame = int(seed), int(first_frame)
+    if not (0 <= seed < 1 << 64 and 0 <= first_frame and first_frame + frames < 1 << 64):
+        raise ValueError("seed and first_frame + frames must fit 64 unsigned bits")
+    if state is None and (first_frame % segment if segment else first_frame):
+        raise ValueError("a call that begins inside a segment needs the state of the call before it")
+    if not getattr(x, "is_cuda", False):
+        raise TypeError("the output stage works on device tensors: the frames must be in HBM")
+    dev = x.device
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((nstreams,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (nstreams,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (nstreams, dev))
+    if state is not None:
+        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, RRX_SHAPE_MAX_ORDER) or state.device != dev or not state.is_contiguous():
+            raise TypeError("state must be a contiguous float64 tensor [%d, %d, %d] on %s" % (nstreams, nch, RRX_SHAPE_MAX_ORDER, dev))
+    if out is False:
+        out = None
+    else:
+        odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
+        oshape = shape[:-1] + (last,)
+        if out is None:
+            out = torch.empty(oshape, dtype=odt, device=dev)
+        elif out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
+            raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
+    stats = []
+    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
+        if t is None:
+            t = torch.zeros((nstreams, nch), dtype=sdt, device=dev)
+        elif t.dtype != sdt or tuple(t.shape) != (nstreams, nch) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, nstreams, nch, dev))
+        stats.append(t)
+    peak, clipped = stats
+    # frames == 0 touches nothing, the state included: the state handed on is then the one that came in
+    new_state = torch.zeros((nstreams, nch, RRX_SHAPE_MAX_ORDER), dtype=torch.float64, device=dev) if state is None or frames else state.clone()
+    if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out, peak, clipped, new_state
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_finish_shaped_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+                                          RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
+                                          dst_format, C.c_void_p(out.data_ptr()) if out is not None else None, frames, nstreams, frames, nch,
+                                          C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed, first_frame,
+                                          C.cast(coefs, C.c_void_p), len(coefs), segment,
+                                          C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(new_state.data_ptr()),
+                                          C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_finish_shaped_device")
+    return out, peak, clipped, new_state
 
 
 class TracksPlan:
@@ -589,6 +695,34 @@ def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=F
                                           dst_format or 0, C.c_void_p(out.data_ptr()) if write else None, dst_total,
                                           C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
                                           C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_device")
+    return out, peak, clipped
+
+
+def tracks_finish_shaped_device(rows, table, dst_format, dst_total, shaping, segment=65536, gain=None, dither=True, seed=0, out=None, peak=None,
+                                clipped=None, stream=None):
+    """tracks_finish_device with noise-shaped dither (RRX_tracks_finish_shaped_device): finish_shaped_device per track, in one
+    call, with the frames and the segments counted from each track's own first output frame and no state -- whole rows only.
+    `shaping` and `segment` are finish_shaped_device's, everything else tracks_finish_device's, except that `dst_format` is never
+    None (`out=False` measures only).  Returns (out, peak, clipped).  The call only enqueues."""
+    dt = str(rows.dtype)
+    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
+        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
+    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+    coefs, segment = _shaping(shaping, segment)
+    ntracks, row_frames, nch = rows.shape
+    measure = out is False
+    seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(rows, table, None if measure else dst_format, dst_total, gain, seed,
+                                                                       None if measure else out, peak, clipped)
+    dev = rows.device
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
+    _check(lib().RRX_tracks_finish_shaped_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
+                                                 nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
+                                                 row_frames, dst_format, C.c_void_p(out.data_ptr()) if write else None, dst_total,
+                                                 C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
+                                                 C.cast(coefs, C.c_void_p), len(coefs), segment,
+                                                 C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_shaped_device")
     return out, peak, clipped
 
 
@@ -1020,13 +1154,17 @@ class Resampler:
             else:
                 self.set_stream(prev)
 
-    def convert_track_to_pcm_device(self, x, dst_format, **finish_kw):
+    def convert_track_to_pcm_device(self, x, dst_format, shaping=None, segment=65536, **finish_kw):
         """convert_track_device followed by the output stage, finish_device(..., dst_format, **finish_kw), on torch's current
         stream of x's device: whole tracks in, integer PCM (and peak / clip count per stream and channel) out.  Returns
-        finish_device's (out, peak, clipped)."""
+        finish_device's (out, peak, clipped).  With `shaping` (a name of NOISE_SHAPES or coefficients) the output stage is
+        finish_shaped_device(..., dst_format, shaping, segment, **finish_kw) instead -- noise-shaped dither, on by default there
+        -- and the same three values are returned."""
         import torch
         y = self.convert_track_device(x)
         finish_kw.setdefault("stream", torch.cuda.current_stream(y.device))
+        if shaping is not None:
+            return finish_shaped_device(y, dst_format, shaping, segment, **finish_kw)[:3]
         return finish_device(y, dst_format, **finish_kw)
 
     def _tracks_checked(self, tracks):
@@ -1122,7 +1260,7 @@ class Resampler:
             if finish_kw.get(k) is not None:
                 raise ValueError("%s is allocated by %s" % (k, who))
 
-    def convert_tracks_to_pcm_streamed(self, tracks, dst_format, window=None, _scratch=None, **finish_kw):
+    def convert_tracks_to_pcm_streamed(self, tracks, dst_format, window=None, _scratch=None, shaping=None, segment=65536, **finish_kw):
         """convert_tracks_to_pcm_device in bounded memory: the same inputs, the same (views, peak, clipped), equal bit for bit, and
         no rows.  The tracks are planned, packed and the table uploaded as there; then ONE input window [nstreams, window, nch] and
         ONE output window are allocated besides the packed destination and the statistics, and on torch's current stream the rows
@@ -1133,8 +1271,13 @@ class Resampler:
 
         The virtual rows are ceil(2 * in_rate / out_rate) + 1 frames longer than the plan's: how many frames a drained handle yields
         in all depends on the push pattern by a frame or two (rate_base.h:436-468), and the extra zeros -- more of every track's
-        drain -- put every track's last output frame inside what comes out whatever the pattern is."""
+        drain -- put every track's last output frame inside what comes out whatever the pattern is.
+
+        `shaping` is accepted for symmetry with convert_tracks_to_pcm_device and refused: noise shaping needs a per-track state
+        across windows, and the windowed form of it is not built."""
         import torch
+        if shaping is not None:
+            raise ValueError("noise shaping in the windowed form is not built: use convert_tracks_to_pcm_device")
         tracks, plan = self._tracks_checked(tracks)
         n, dev = len(tracks), tracks[0].device
         step = self.isamp_max
@@ -1195,23 +1338,28 @@ class Resampler:
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
 
-    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, **finish_kw):
+    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, shaping=None, segment=65536, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
         packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  The tracks may be integer PCM
         themselves (int16, int32, or uint8 packed 24 bit, as in convert_tracks_device): PCM in, PCM out, with float32 only in the
         rows the handle is pushed from.  Returns (list of per-track
-        views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views."""
+        views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views.
+        With `shaping` (a name of NOISE_SHAPES or coefficients) the output stage is tracks_finish_shaped_device(..., shaping,
+        segment, **finish_kw): noise-shaped dither, on by default there, in segments counted from each track's first frame."""
         import torch
         tracks = list(tracks)
         plan, table, out = self._convert_tracks_rows(tracks, _scratch)
         n = len(tracks)
         self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_device")
         finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
-        pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
+        if shaping is not None:
+            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, **finish_kw)
+        else:
+            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
 
-    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0):
+    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut
         into the length-sorted batches of tracks_batches for the handle's own `nstreams` -- no other split resamples less padding
         -- and converted batch after batch, with reset() before every batch whenever the handle has been used.  Each batch runs
@@ -1224,8 +1372,14 @@ class Resampler:
         seed + b * nstreams * nch * 0xBF58476D1CE4E5B9 (mod 2^64), which puts that track on dither channel r * nch + ch -- so its
         bytes and statistics are those of a one-stream finish_device on its slice with seed + r * nch * 0xBF58476D1CE4E5B9,
         whatever `nstreams` is.  Returns (per-track PCM tensors in the caller's order, peak [ntracks, nch], clipped [ntracks, nch]).
-        Runs on torch's current stream and copies no sample to the host."""
+        Runs on torch's current stream and copies no sample to the host.
+
+        `shaping` (a name of NOISE_SHAPES or coefficients) and `segment`: every batch is finished by tracks_finish_shaped_device
+        with the same per-batch seed, so the rule above holds with finish_shaped_device for finish_device; `dither` keeps its
+        default here.  With `window` it raises ValueError: the windowed form of noise shaping is not built."""
         import torch
+        if shaping is not None and window is not None:
+            raise ValueError("noise shaping in the windowed form is not built: leave `window` out")
         tracks = list(tracks)
         n, S = len(tracks), self.nstreams
         if n < 1:
@@ -1255,6 +1409,8 @@ class Resampler:
             if self._used:
                 self.reset()
             kw = {"dither": dither, "seed": (seed + b * S * self.nch * 0xBF58476D1CE4E5B9) % (1 << 64), "_scratch": scratch}
+            if shaping is not None:
+                kw.update(shaping=shaping, segment=segment)
             where = torch.tensor(idx, dtype=torch.int64, device=dev)
             if gain is not None:
                 kw["gain"] = gain[where].contiguous()

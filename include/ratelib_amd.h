@@ -253,8 +253,8 @@ int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data
  * first_frame + frames overflowing 64 bits, a size no buffer has -- frames * nch, or with nstreams > 1 nstreams * src_stride * nch
  * (nstreams * dst_stride * nch when d_dst is not NULL), of 2^60 samples or more, so that no offset the call computes can wrap --
  * or device < -1; RR_EXTUNINIT before init_ratelib; RR_INVPARAM for a device index the process does not have; RR_INTERNAL for
- * a failed launch.  frames == 0 is RR_OK and does nothing.  Noise shaping, integer or planar sources and float destinations are
- * not offered. */
+ * a failed launch.  frames == 0 is RR_OK and does nothing.  Noise shaping is RRX_finish_shaped_device's, below; integer or planar
+ * sources and float destinations are not offered. */
 #define RRX_FMT_S24_3 24   /* packed 3-byte signed 24-bit PCM: RRX_finish_device's destination only, and a source format of RRX_tracks_stage_device_samples */
 int RRX_finish_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
                       int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
@@ -265,6 +265,65 @@ int RRX_finish_device(int device, void *hip_stream, int src_format, const void *
 int RRX_debug_finish_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride,
                           int nstreams, size_t frames, int nch, const double *gain, int dither, unsigned long long seed,
                           unsigned long long first_frame, double *peak, unsigned long long *clipped);
+
+/* RRX_finish_device with noise-shaped dither: the requantisation error of a channel's previous 1..order frames is fed back through
+ * an FIR filter, which moves the noise out of the band the filter was designed to spare.  The recursion contains a rint, so a
+ * channel is a serial chain; to give the device independent chains the restart of the error history is PART OF THIS ABI: the
+ * history of every channel is cleared at every absolute frame that is a multiple of `segment`.  The quantised sample is then a
+ * function of (seed, stream, channel, absolute frame, and the samples of its own segment up to it).
+ *
+ * The arithmetic.  Everything is fp64 and every operation is rounded on its own (no fused multiply-add); 64-bit integers wrap.
+ * For stream s, channel ch and frame i of the call:  F = first_frame + i,  c = s * nch + ch,  bits = 15 / 23 / 31.
+ *   gain and scale   g = (double)x * d_gain[s]  (d_gain NULL: g = x);  a = fabs(g);  t = g * 2^bits   -- RRX_finish_device's
+ *   history          e[1..order] are the errors of the channel's previous 1..order frames; all of them are +0.0 when
+ *                    segment != 0 && F % segment == 0, or when F == 0
+ *   feedback         acc = +0.0;  for k = order down to 1:  acc = acc + coefs[k-1] * e[k];   w = t - acc
+ *                    (a descending sum: the newest error is added last)
+ *   dither           u = dither ? w + d(seed, F, c) : w,   d = RRX_finish_device's dither of (seed, first_frame + i, c), unchanged
+ *   quantise         q = rint(u), round half to even;  clip = !(-2^bits <= q <= 2^bits - 1);  the stored sample is
+ *                    (int)fmin(fmax(q, -2^bits), 2^bits - 1): a NaN stores -2^bits and counts as clipped
+ *   error            err = q - w, from the UNSATURATED q, so a clipped passage does not wind the filter up;
+ *                    if (!(fabs(err) <= 2.0)) err = 0.0.  A finite sample gives |err| < 1.5; only +-inf or a NaN gives anything
+ *                    else, and it then leaves no trace in the history
+ *   shift            e[k+1] = e[k],  e[1] = err
+ * Consequences:
+ *   - with order = 1 and coefs[0] = 0.0 the bytes, peaks and clip counts are RRX_finish_device's, bit for bit, with and without
+ *     dither, and for NaN, +-inf and -0.0 alike;
+ *   - padding the coefficients with zeros at the high end changes no bit: acc starts at +0.0 and +0.0 + (+-0.0) = +0.0.  The kernel
+ *     rounds order up to a compile-time size on that ground and keeps the history in registers.
+ *   coefs: a HOST pointer to `order` doubles, copied into the launch arguments; order is 1..RRX_SHAPE_MAX_ORDER and every
+ *   coefficient finite.  The call designs no filter: published 44.1 kHz designs are in the Python binding (NOISE_SHAPES).
+ *   segment: in frames; any value >= 1, or 0 for "never restart" (one lane per channel: the textbook serial form).
+ *   d_dst NULL: measure only -- nothing is written, dst_stride is ignored, but dst_format must still be valid and its bits are
+ *   used: the shaped noise is tens of LSB of the target format, and a caller who measures first and then writes must see the clip
+ *   count the write will produce.
+ *   State: [nstreams * nch][RRX_SHAPE_MAX_ORDER] doubles on the device; entry k-1 of a channel is e[k], entries at `order` and
+ *   beyond are 0.  d_state_in NULL: the call must begin a segment (first_frame % segment == 0, or first_frame == 0 for
+ *   segment 0), else RR_INVPARAM.  d_state_in not NULL is read only when the call begins inside a segment.  d_state_out not NULL
+ *   receives, for every channel, the history as it stands after the call's last frame.  The two must not overlap (RR_INVPARAM,
+ *   equal pointers included): the lane that reads the state and the lane that writes it are unordered within one launch, so a
+ *   caller ping-pongs two buffers.  Contiguous ascending calls that hand the state on leave the bytes and statistics of one call,
+ *   for any cut positions.
+ *   Everything else -- src_format, dst_format, layouts and strides, the alignment of one sample and "no byte outside the
+ *   frames * nch samples of each destination row is touched", d_peak / d_clipped and their accumulation, device and hip_stream
+ *   with the stream-ordering contract, "only enqueues: no allocation, no host synchronisation" -- is RRX_finish_device's.
+ * Returns RR_INVPARAM, before any device is touched, for every argument RRX_finish_device refuses, and further for an unknown
+ * dst_format (d_dst NULL included), coefs NULL, order outside 1..RRX_SHAPE_MAX_ORDER, a non-finite coefficient, and the state
+ * rules above; RR_EXTUNINIT before init_ratelib; RR_INTERNAL for a failed launch.  frames == 0 is RR_OK and touches nothing, the
+ * state included. */
+#define RRX_SHAPE_MAX_ORDER 16
+int RRX_finish_shaped_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
+                             int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
+                             const double *d_gain, int dither, unsigned long long seed, unsigned long long first_frame,
+                             const double *coefs, int order, size_t segment,
+                             const double *d_state_in, double *d_state_out,
+                             double *d_peak, unsigned long long *d_clipped);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: RRX_finish_shaped_device on
+ * HOST pointers, as one serial loop per channel over the very per-sample functions the kernel calls.  Same refusals, same results. */
+int RRX_debug_finish_shaped_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride,
+                                 int nstreams, size_t frames, int nch, const double *gain, int dither, unsigned long long seed,
+                                 unsigned long long first_frame, const double *coefs, int order, size_t segment,
+                                 const double *state_in, double *state_out, double *peak, unsigned long long *clipped);
 
 /* Host-only (no GPU needed): the plugin's edge geometry for a rate pair (dsp_rate::reinit, foo_dsp_rate.cpp:96-101).
  * *n_add / *n_drop = samples_len(in_rate, out_rate, 20, 8192) of util.h:38-48: frames to extrapolate at each end of the input
@@ -394,6 +453,19 @@ int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tr
                              const void *d_rows, size_t row_frames, int dst_format, void *d_dst, size_t dst_total,
                              const double *d_gain, int dither, unsigned long long seed, double *d_peak,
                              unsigned long long *d_clipped);
+
+/* RRX_finish_shaped_device per track in one call: RRX_tracks_finish_device with noise-shaped dither.  Tables, rows, the packed
+ * destination, gains, statistics, clamps (a wrong table gives wrong samples, never an access outside the buffers), device,
+ * hip_stream and refusals are RRX_tracks_finish_device's; coefs, order and segment are RRX_finish_shaped_device's, refused as
+ * there, and as there dst_format must be valid when d_dst is NULL too (its bits are used).  Frame i and the segments are counted
+ * from the track's own first output frame, and there is no state: whole rows only.  Track t gets the bytes and statistics of a
+ * one-stream RRX_finish_shaped_device call on its slice with seed + t * nch * 0xBF58476D1CE4E5B9 (mod 2^64) for seed,
+ * first_frame = 0 and no state.  row_frames == 0 is RR_OK and does nothing. */
+int RRX_tracks_finish_shaped_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                    int src_format, const void *d_rows, size_t row_frames, int dst_format, void *d_dst,
+                                    size_t dst_total, const double *d_gain, int dither, unsigned long long seed,
+                                    const double *coefs, int order, size_t segment,
+                                    double *d_peak, unsigned long long *d_clipped);
 
 /* Windows: the two passes above on frames [win_first, win_first + win_frames) of the rows, so that a ragged batch runs in memory
  * proportional to ntracks * window instead of ntracks * longest track.  The rows themselves are VIRTUAL: row_frames is their

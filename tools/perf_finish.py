@@ -24,6 +24,20 @@ One JSON line per (shape, variant), appended to --out (default profiles/finish_p
 Exit status 1 if a dither-off variant is not faster than its torch sequence.
 
   python tools/perf_finish.py [--configs 1,3] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
+
+--shaped times the noise-shaped call instead (RRX_finish_shaped_device; DESIGN.md 10, "Noise-shaped dither") on the same two
+tensors: S16, dither on, the wannamaker9 filter, segments 4096 / 16384 / 65536 / 0, interleaved in every round with the unshaped
+dithered RRX_finish_device and with the copy of the float32 tensor into pinned host memory -- what any host-side shaper would have
+to begin with.  One JSON line per (shape, segment), appended to --out (default profiles/finish_shaped_perf.jsonl):
+
+  {"config", "streams", "nch", "frames", "variant": "shaped_s16_dither", "filter", "segment", "lanes": (stream, segment, channel)
+   chains, "ms", "ms_rounds", "ns_per_frame_of_a_chain": ms / the frames of the longest chain, "unshaped_ms", "unshaped_ms_rounds",
+   "ratio_to_unshaped", "to_pinned_host_ms", "to_pinned_host_ms_rounds", "faster_than_the_copy", "steps", "warmup"}
+
+Exit status 1 if, at the default segment (65536), the shaped call is not faster than the copy.  --shaped-once CONFIG runs nothing
+but `--steps` shaped calls at the default segment on that config's tensor: the process to collect hardware counters from.
+
+  python tools/perf_finish.py --shaped [--configs 1,3] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
 """
 import argparse
 import json
@@ -134,16 +148,101 @@ def one_config(k, steps, warmup, rounds):
     return lines
 
 
+SHAPED_SEGMENTS = (4096, 16384, 65536, 0)
+SHAPED_DEFAULT = 65536
+
+
+def step_tensor(k, stream):
+    """the frames of one bench.py step of config k, as one_config makes them, and the per-stream gain"""
+    cfg = bench.CONFIGS[k]
+    fi, fo, nch, S = cfg["fi"], cfg["fo"], cfg["nch"], cfg["streams"]
+    r = F.Resampler(fi, fo, nch=nch, nstreams=S, **cfg["kw"])
+    P = r.isamp_max
+    xin = bench.lcg_noise_device(torch, S, P, nch, 12345, "cuda")
+    cap = int(P * fo / fi) + 65536
+    y = torch.empty((S, cap, nch), device="cuda", dtype=torch.float32)
+    torch.cuda.synchronize()
+    r.set_stream(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        got = r.flow_device(xin, P, y, cap)[1]
+        x = y[:, :got].contiguous()
+        g = torch.linspace(0.5, 1.0, S, dtype=torch.float64, device="cuda")
+    stream.synchronize()
+    r.use_own_stream()
+    return x, g
+
+
+def shaped_config(k, steps, warmup, rounds, segments=SHAPED_SEGMENTS, only=False):
+    stream = torch.cuda.Stream()
+    x, g = step_tensor(k, stream)
+    S, frames, nch = x.shape
+    with torch.cuda.stream(stream):
+        out16 = torch.empty(x.shape, dtype=torch.int16, device="cuda")
+        peak = torch.zeros((S, nch), dtype=torch.float64, device="cuda")
+        clipped = torch.zeros((S, nch), dtype=torch.int64, device="cuda")
+    stream.synchronize()
+
+    def shaped(segment):
+        return lambda: F.finish_shaped_device(x, F.RRX_FMT_S16, "wannamaker9", segment, gain=g, dither=True, seed=1, out=out16, peak=peak,
+                                              clipped=clipped, stream=stream)
+
+    if only:
+        timed(stream, shaped(SHAPED_DEFAULT), steps, warmup)
+        return []
+    host = torch.empty(x.shape, dtype=torch.float32, pin_memory=True)
+    unshaped = lambda: F.finish_device(x, F.RRX_FMT_S16, gain=g, dither=True, seed=1, out=out16, peak=peak, clipped=clipped, stream=stream)  # noqa: E731
+    copy = lambda: host.copy_(x, non_blocking=True)  # noqa: E731
+    ms = {seg: [] for seg in segments}
+    ums, cms = [], []
+    for _ in range(rounds):
+        for seg in segments:
+            ms[seg].append(timed(stream, shaped(seg), steps, warmup))
+            ums.append(timed(stream, unshaped, steps, warmup))
+        cms.append(timed(stream, copy, steps, warmup))
+    u, c = statistics.median(ums), statistics.median(cms)
+    lines = []
+    for seg in segments:
+        m = statistics.median(ms[seg])
+        nseg = -(-frames // seg) if seg else 1
+        lines.append({"config": k, "streams": S, "nch": nch, "frames": frames, "variant": "shaped_s16_dither", "filter": "wannamaker9",
+                      "segment": seg, "lanes": S * nseg * nch, "ms": round(m, 4), "ms_rounds": [round(t, 4) for t in ms[seg]],
+                      "ns_per_frame_of_a_chain": round(m * 1e6 / (seg if seg and seg < frames else frames), 2),
+                      "unshaped_ms": round(u, 4), "unshaped_ms_rounds": [round(t, 4) for t in ums], "ratio_to_unshaped": round(m / u, 2),
+                      "to_pinned_host_ms": round(c, 4), "to_pinned_host_ms_rounds": [round(t, 4) for t in cms],
+                      "faster_than_the_copy": bool(m < c), "steps": steps, "warmup": warmup})
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shaped", action="store_true")
+    ap.add_argument("--shaped-once", type=int, default=None, metavar="CONFIG")
     ap.add_argument("--configs", default="1,3")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "finish_perf.jsonl"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "finish_shaped_perf.jsonl" if a.shaped else "finish_perf.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("perf_finish.py needs a GPU: there is nothing to time without one")
+    if a.shaped_once is not None:
+        shaped_config(a.shaped_once, a.steps, a.warmup, 1, only=True)
+        return
+    if a.shaped:
+        late = []
+        for k in [int(v) for v in a.configs.split(",")]:
+            for line in shaped_config(k, a.steps, a.warmup, a.rounds):
+                text = json.dumps(line)
+                print(text, flush=True)
+                with open(a.out, "a") as f:
+                    f.write(text + "\n")
+                if line["segment"] == SHAPED_DEFAULT and not line["faster_than_the_copy"]:
+                    late.append((k, line["ms"], line["to_pinned_host_ms"]))
+        if late:
+            raise SystemExit("at the default segment not faster than the copy to pinned host memory: %r" % (late,))
+        return
     slower = []
     for k in [int(v) for v in a.configs.split(",")]:
         for line in one_config(k, a.steps, a.warmup, a.rounds):
