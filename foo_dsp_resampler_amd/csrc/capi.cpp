@@ -1100,6 +1100,90 @@ int RRX_tracks_finish_window_device(int device, void *hip_stream, const RRX_trac
   return rsmp::launch_tracks_finish_window(static_cast<hipStream_t>(hip_stream), a, w) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
+namespace {
+
+// RRX_tracks_finish_shaped_window_device / RRX_debug_tracks_finish_shaped_window_host: everything that can be refused from the
+// arguments alone -- what RRX_tracks_finish_window_device refuses, what RRX_tracks_finish_shaped_device adds, and the state rules
+int tracks_shaped_window_args(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win, size_t win_stride, size_t row_frames,
+                              size_t win_first, size_t win_frames, int dst_format, void *dst, size_t dst_total, const double *gain, int dither,
+                              unsigned long long seed, const double *coefs, int order, size_t segment, const double *state_in, double *state_out,
+                              double *peak, unsigned long long *clipped, rsmp::TracksShapedWindowArgs &a)
+{
+  if (!tracks || !win || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (!pcm_format(dst_format)) return RR_INVPARAM; // measure only included
+  if (shaped_filter(coefs, order, a.s.coefs) != RR_OK) return RR_INVPARAM;
+  if (!dst && !peak && !clipped) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks) || (dst && dst_total > most)) return RR_INVPARAM;
+  if (tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, a.w) != RR_OK) return RR_INVPARAM;
+  if (!state_in && win_first) return RR_INVPARAM; // only a window at frame 0 finds every track at its first frame or not begun
+  if (state_in && state_out) { // [ntracks * nch][16] doubles each, ntracks * nch < 2^60: no wrap for a buffer that exists
+    const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
+    const uintptr_t bytes = uintptr_t(ntracks) * uintptr_t(nch) * rsmp::kShapeMaxOrder * sizeof(double);
+    if (x < y ? y - x < bytes : x - y < bytes) return RR_INVPARAM;
+  }
+  a.s.t.tracks = reinterpret_cast<const rsmp::Track *>(tracks);
+  a.s.t.src = win;
+  a.s.t.dst = dst;
+  a.s.t.gain = gain;
+  a.s.t.peak = peak;
+  a.s.t.clipped = clipped;
+  a.s.t.row_frames = row_frames;
+  a.s.t.dst_total = dst_total;
+  a.s.t.seed = seed;
+  a.s.t.ntracks = ntracks;
+  a.s.t.nch = nch;
+  a.s.t.src_double = src_format == RRX_FMT_DOUBLE;
+  a.s.t.bits = pcm_bits(dst_format);
+  a.s.t.dither = dither != 0;
+  a.s.segment = segment;
+  a.s.order = order;
+  a.state_in = state_in;
+  a.state_out = state_out;
+  return RR_OK;
+}
+
+} // namespace
+
+// RRX_tracks_finish_shaped_device on a window of the output rows, the error history carried per track (finish_shaped.hip).
+// Refusals first.
+int RRX_tracks_finish_shaped_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                           const void *d_win, size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                           int dst_format, void *d_dst, size_t dst_total, const double *d_gain, int dither, unsigned long long seed,
+                                           const double *coefs, int order, size_t segment, const double *d_state_in, double *d_state_out,
+                                           double *d_peak, unsigned long long *d_clipped)
+{
+  rsmp::TracksShapedWindowArgs a;
+  const int rc = tracks_shaped_window_args(d_tracks, ntracks, nch, src_format, d_win, win_stride, row_frames, win_first, win_frames, dst_format,
+                                           d_dst, dst_total, d_gain, dither, seed, coefs, order, segment, d_state_in, d_state_out, d_peak,
+                                           d_clipped, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames || !win_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_tracks_finish_shaped_window(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_finish_shaped_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win, size_t win_stride,
+                                               size_t row_frames, size_t win_first, size_t win_frames, int dst_format, void *dst,
+                                               size_t dst_total, const double *gain, int dither, unsigned long long seed, const double *coefs,
+                                               int order, size_t segment, const double *state_in, double *state_out, double *peak,
+                                               unsigned long long *clipped)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::TracksShapedWindowArgs a;
+  const int rc = tracks_shaped_window_args(tracks, ntracks, nch, src_format, win, win_stride, row_frames, win_first, win_frames, dst_format, dst,
+                                           dst_total, gain, dither, seed, coefs, order, segment, state_in, state_out, peak, clipped, a);
+  if (rc != RR_OK) return rc;
+  if (row_frames && win_frames) rsmp::tracks_finish_shaped_window_host(a);
+  return RR_OK;
+}
+
 // Test hook: what the window kernels take from one table entry -- tracks_stage_cut and tracks_finish_cut (tracks.hpp), the functions
 // the kernels call, on a host entry.  stage[10]: bk, cp, fw, z (two values each), src_frame, readable; finish[4]: w0, w1, index, dst_frame.
 int RRX_debug_tracks_window_cut(const RRX_track *entry, size_t row_frames, size_t src_total, size_t dst_total, int write, size_t win_first,

@@ -15,6 +15,9 @@
 // Peak and clip count stay in registers and leave as one atomic each per lane (a peak only when it beats the value there).
 // The lane of a call's first segment loads its history from state_in when the call begins inside a segment; the lane of the last
 // segment stores its history to state_out.
+// The window form of the tracks kernel (tracks_finish_shaped_window_kernel) is the same lane around the part of a track's slice
+// that lies inside a window (tracks_finish_cut): segments are still counted from the track's first output frame, so a window
+// cuts every track's segments somewhere else, and the history crosses from window to window in a per-(track, channel) state.
 #include "finish_shaped.hpp"
 
 #include <cstring>
@@ -201,6 +204,69 @@ __global__ __launch_bounds__(kThreads) void tracks_finish_shaped_kernel(TracksSh
   }
 }
 
+// The window form.  a.s.t.src holds frames [w.first, w.first + w.frames) of every output row, pitch w.stride.  Track t's processed
+// frames (tracks_finish_cut) are stream t of finish_shaped_kernel with first_frame = their index in the track, frames = their
+// count and the track's entries of the state; the launch is sized from the window (a range of n frames meets at most
+// ceil(n / segment) + 1 segments), and the loop below takes whatever segments the track's range really has.  A track with no
+// frame in the window hands its state on unchanged: the lanes of segment slot 0, one per channel, copy it (zeros without a state).
+template <typename S, int kK>
+__global__ __launch_bounds__(kThreads) void tracks_finish_shaped_window_kernel(TracksShapedWindowArgs a, int t0)
+{
+  const TracksFinishArgs &ta = a.s.t;
+  const unsigned nch = (unsigned)ta.nch;
+  const u64 t = (u64)(t0 + (int)blockIdx.y), seg = a.s.segment;
+  const TracksFinishCut c = tracks_finish_cut(ta.tracks[t], ta.row_frames, ta.dst_total, ta.dst != nullptr, a.w);
+  const u64 frames = c.w1 - c.w0;
+  if (!frames) {
+    if (a.state_out)
+      for (u64 L = (u64)blockIdx.x * kThreads + threadIdx.x; L < nch; L += (u64)gridDim.x * kThreads) {
+        const u64 o = (t * nch + L) * kShapeMaxOrder;
+#pragma unroll
+        for (int k = 0; k < kShapeMaxOrder; ++k) a.state_out[o + k] = a.state_in ? a.state_in[o + k] : 0.0;
+      }
+    return;
+  }
+  const u64 first = c.index, last = c.index + (frames - 1); // frames of the track's slice, below row_frames
+  const u64 seg0 = seg ? first / seg : 0, nseg = seg ? last / seg - seg0 + 1 : 1, lanes = nseg * nch;
+  double coef[kK];
+#pragma unroll
+  for (int k = 0; k < kK; ++k) coef[k] = a.s.coefs[k];
+  LaneParams p = lane_params(ta.bits, ta.dither != 0, ta.seed, nch);
+  p.has_gain = ta.gain != nullptr;
+  if (p.has_gain) p.gain = ta.gain[t];
+  const S *row = static_cast<const S *>(ta.src) + (t * a.w.stride + c.w0) * nch;
+  unsigned char *out = ta.dst ? static_cast<unsigned char *>(ta.dst) + c.dst_frame * nch * p.bytes : nullptr;
+  // the range begins inside a segment: its first lanes take the state (first > 0 only behind w.first > 0, which has a state)
+  const bool inside = !shaped_restarts(first, seg) && a.state_in;
+
+  for (u64 L = (u64)blockIdx.x * kThreads + threadIdx.x; L < lanes; L += (u64)gridDim.x * kThreads) {
+    const u64 j = L / nch, ch = L - j * nch;
+    const u64 A = seg ? (seg0 + j) * seg : 0;                 // the segment's first frame of the track, <= last
+    const u64 F0 = A > first ? A : first;                     // the lane's first frame
+    const u64 rem = last - F0 + 1;                            // frames to the end of the range
+    const u64 n = seg && seg - (F0 - A) < rem ? seg - (F0 - A) : rem;
+    const u64 k0 = (F0 - first) * nch + ch;
+    p.c = t * nch + ch;
+    double e[kK];
+#pragma unroll
+    for (int k = 0; k < kK; ++k) e[k] = 0.0;
+    if (j == 0 && inside) {
+      const double *st = a.state_in + p.c * kShapeMaxOrder;
+#pragma unroll
+      for (int k = 0; k < kK; ++k)
+        if (k < a.s.order) e[k] = st[k];
+    }
+    u64 pk = 0, cl = 0;
+    shaped_lane<S, kK>(p, row + k0, out ? out + k0 * p.bytes : nullptr, n, F0, coef, e, pk, cl);
+    if (a.state_out && j == nseg - 1) {
+      double *st = a.state_out + p.c * kShapeMaxOrder;
+#pragma unroll
+      for (int k = 0; k < kShapeMaxOrder; ++k) st[k] = k < kK && k < a.s.order ? e[k < kK ? k : 0] : 0.0;
+    }
+    lane_stats(ta.peak, ta.clipped, p.c, pk, cl);
+  }
+}
+
 unsigned grid_x(u64 lanes)
 {
   const u64 wg = (lanes + kThreads - 1) / kThreads;
@@ -245,42 +311,92 @@ template <typename S> hipError_t tracks_src(hipStream_t stream, const TracksShap
   return a.order <= 4 ? tracks_typed<S, 4>(stream, a) : a.order <= 8 ? tracks_typed<S, 8>(stream, a) : tracks_typed<S, 16>(stream, a);
 }
 
+template <typename S, int kK> hipError_t tracks_window_typed(hipStream_t stream, const TracksShapedWindowArgs &a)
+{
+  const u64 seg = a.s.segment, n = a.w.frames;
+  u64 nseg = seg ? n / seg + (n % seg ? 1 : 0) + 1 : 1; // what n frames can meet, wherever the track's segments lie
+  if (nseg > n) nseg = n;                               // (never more segments than frames); n * nch < 2^60 (capi.cpp)
+  const unsigned gx = grid_x(nseg * (u64)a.s.t.nch);
+  for (int t0 = 0; t0 < a.s.t.ntracks; t0 += 32768) {
+    const int nt = a.s.t.ntracks - t0 < 32768 ? a.s.t.ntracks - t0 : 32768;
+    hipLaunchKernelGGL((tracks_finish_shaped_window_kernel<S, kK>), dim3(gx, (unsigned)nt), dim3(kThreads), 0, stream, a, t0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <typename S> hipError_t tracks_window_src(hipStream_t stream, const TracksShapedWindowArgs &a)
+{
+  return a.s.order <= 4   ? tracks_window_typed<S, 4>(stream, a)
+         : a.s.order <= 8 ? tracks_window_typed<S, 8>(stream, a)
+                          : tracks_window_typed<S, 16>(stream, a);
+}
+
+// One channel on the host: n frames from absolute frame F0 on, x0 at the channel's first sample and o0 (or null) at its first
+// output byte, both nch samples a frame.  The history starts from st_in when F0 lies inside a segment and goes to st_out.
+template <typename S>
+void host_chain(const S *x0, unsigned char *o0, u64 nch, u64 n, u64 F0, bool has_gain, double gain, int bits, bool dither, u64 seed, u64 c,
+                const double (&coefs)[kShapeMaxOrder], int order, u64 segment, const double *st_in, double *st_out, double *peak, u64 *clipped)
+{
+  const double scale = bits == 15 ? 0x1p15 : bits == 23 ? 0x1p23 : 0x1p31, lo = -scale, hi = scale - 1.0;
+  const int bytes = bits == 15 ? 2 : bits == 23 ? 3 : 4;
+  double e[kShapeMaxOrder] = {};
+  if (!shaped_restarts(F0, segment) && st_in)
+    for (int k = 0; k < order; ++k) e[k] = st_in[c * kShapeMaxOrder + k];
+  for (u64 i = 0; i < n; ++i) {
+    const u64 F = F0 + i;
+    if (i && shaped_restarts(F, segment))
+      for (double &v : e) v = 0.0;
+    const ShapedFront f = shaped_front((double)x0[i * nch], has_gain, gain, scale, dither, seed, F, c);
+    const FinishSample r = shaped_step<kShapeMaxOrder>(f, dither, lo, hi, coefs, e);
+    if (o0) {
+      unsigned char *o = o0 + i * nch * bytes;
+      if (bits == 15) finish_store_bytes<15>(o, r.q);
+      else if (bits == 23) finish_store_bytes<23>(o, r.q);
+      else finish_store_bytes<31>(o, r.q);
+    }
+    if (peak) {
+      u64 have, now;
+      std::memcpy(&have, peak + c, 8);
+      std::memcpy(&now, &r.a, 8);
+      if (now > have) std::memcpy(peak + c, &now, 8);
+    }
+    if (clipped && r.clip) ++clipped[c];
+  }
+  if (st_out)
+    for (int k = 0; k < kShapeMaxOrder; ++k) st_out[c * kShapeMaxOrder + k] = k < order ? e[k] : 0.0;
+}
+
 template <typename S> void host_src(const ShapedArgs &a)
 {
   const u64 nch = (u64)a.nch;
-  const double scale = a.bits == 15 ? 0x1p15 : a.bits == 23 ? 0x1p23 : 0x1p31, lo = -scale, hi = scale - 1.0;
   const int bytes = a.bits == 15 ? 2 : a.bits == 23 ? 3 : 4;
   for (u64 s = 0; s < (u64)a.nstreams; ++s) {
     const S *src = static_cast<const S *>(a.src) + s * a.src_stride;
     unsigned char *dst = a.dst ? static_cast<unsigned char *>(a.dst) + s * a.dst_stride * bytes : nullptr;
-    const double gain = a.gain ? a.gain[s] : 1.0;
+    for (u64 ch = 0; ch < nch; ++ch)
+      host_chain<S>(src + ch, dst ? dst + ch * bytes : nullptr, nch, a.frames, a.first_frame, a.gain != nullptr, a.gain ? a.gain[s] : 1.0, a.bits,
+                    a.dither != 0, a.seed, s * nch + ch, a.coefs, a.order, a.segment, a.state_in, a.state_out, a.peak, a.clipped);
+  }
+}
+
+template <typename S> void tracks_window_host_src(const TracksShapedWindowArgs &a)
+{
+  const TracksFinishArgs &ta = a.s.t;
+  const u64 nch = (u64)ta.nch;
+  const int bytes = ta.bits == 15 ? 2 : ta.bits == 23 ? 3 : 4;
+  for (u64 t = 0; t < (u64)ta.ntracks; ++t) {
+    const TracksFinishCut c = tracks_finish_cut(ta.tracks[t], ta.row_frames, ta.dst_total, ta.dst != nullptr, a.w);
+    const S *src = static_cast<const S *>(ta.src) + (t * a.w.stride + c.w0) * nch;
+    unsigned char *dst = ta.dst ? static_cast<unsigned char *>(ta.dst) + c.dst_frame * nch * bytes : nullptr;
     for (u64 ch = 0; ch < nch; ++ch) {
-      const u64 c = s * nch + ch;
-      double e[kShapeMaxOrder] = {};
-      if (!shaped_restarts(a.first_frame, a.segment))
-        for (int k = 0; k < a.order; ++k) e[k] = a.state_in[c * kShapeMaxOrder + k];
-      for (u64 i = 0; i < a.frames; ++i) {
-        const u64 F = a.first_frame + i;
-        if (i && shaped_restarts(F, a.segment))
-          for (double &v : e) v = 0.0;
-        const ShapedFront f = shaped_front((double)src[i * nch + ch], a.gain != nullptr, gain, scale, a.dither != 0, a.seed, F, c);
-        const FinishSample r = shaped_step<kShapeMaxOrder>(f, a.dither != 0, lo, hi, a.coefs, e);
-        if (dst) {
-          unsigned char *o = dst + (i * nch + ch) * bytes;
-          if (a.bits == 15) finish_store_bytes<15>(o, r.q);
-          else if (a.bits == 23) finish_store_bytes<23>(o, r.q);
-          else finish_store_bytes<31>(o, r.q);
-        }
-        if (a.peak) {
-          u64 have, now;
-          std::memcpy(&have, a.peak + c, 8);
-          std::memcpy(&now, &r.a, 8);
-          if (now > have) std::memcpy(a.peak + c, &now, 8);
-        }
-        if (a.clipped && r.clip) ++a.clipped[c];
-      }
-      if (a.state_out)
-        for (int k = 0; k < kShapeMaxOrder; ++k) a.state_out[c * kShapeMaxOrder + k] = k < a.order ? e[k] : 0.0;
+      const u64 o = (t * nch + ch) * kShapeMaxOrder;
+      if (c.w1 > c.w0)
+        host_chain<S>(src + ch, dst ? dst + ch * bytes : nullptr, nch, c.w1 - c.w0, c.index, ta.gain != nullptr, ta.gain ? ta.gain[t] : 1.0, ta.bits,
+                      ta.dither != 0, ta.seed, t * nch + ch, a.s.coefs, a.s.order, a.s.segment, a.state_in, a.state_out, ta.peak, ta.clipped);
+      else if (a.state_out)
+        for (int k = 0; k < kShapeMaxOrder; ++k) a.state_out[o + k] = a.state_in ? a.state_in[o + k] : 0.0;
     }
   }
 }
@@ -297,10 +413,21 @@ hipError_t launch_tracks_finish_shaped(hipStream_t stream, const TracksShapedArg
   return a.t.src_double ? tracks_src<double>(stream, a) : tracks_src<float>(stream, a);
 }
 
+hipError_t launch_tracks_finish_shaped_window(hipStream_t stream, const TracksShapedWindowArgs &a)
+{
+  return a.s.t.src_double ? tracks_window_src<double>(stream, a) : tracks_window_src<float>(stream, a);
+}
+
 void finish_shaped_host(const ShapedArgs &a)
 {
   if (a.src_double) host_src<double>(a);
   else host_src<float>(a);
+}
+
+void tracks_finish_shaped_window_host(const TracksShapedWindowArgs &a)
+{
+  if (a.s.t.src_double) tracks_window_host_src<double>(a);
+  else tracks_window_host_src<float>(a);
 }
 
 } // namespace rsmp

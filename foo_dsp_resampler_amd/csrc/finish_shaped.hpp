@@ -40,6 +40,15 @@ struct TracksShapedArgs {
   double coefs[kShapeMaxOrder];
 };
 
+// what RRX_tracks_finish_shaped_window_device was given, after validation: s.t.src is the window buffer [ntracks][w.stride][nch]
+// with frames [w.first, w.first + w.frames) of the output rows, s.t.row_frames the length of the virtual rows
+struct TracksShapedWindowArgs {
+  TracksShapedArgs s;
+  TracksWindow w;                     // w.frames > 0
+  const double *state_in;             // [ntracks * nch][kShapeMaxOrder]; null only with w.first == 0
+  double *state_out;                  // the same layout, every entry written; null = not wanted
+};
+
 // The part of a sample that does not depend on the channel's earlier errors: the gained sample's magnitude, the scaled sample
 // and the dither.  g and t are finish_sample's.
 struct ShapedFront {
@@ -88,12 +97,18 @@ __host__ __device__ __forceinline__ bool shaped_restarts(unsigned long long F, u
   return segment ? F % segment == 0 : F == 0;
 }
 
-// Both only enqueue on `stream`, split into as many launches as the grid limits ask for; the arguments are the caller's to
+// All three only enqueue on `stream`, split into as many launches as the grid limits ask for; the arguments are the caller's to
 // validate.  The table of the tracks form cannot be: the kernel clamps what it takes from it (tracks_slice, tracks.hpp).
 hipError_t launch_finish_shaped(hipStream_t stream, const ShapedArgs &a);
 hipError_t launch_tracks_finish_shaped(hipStream_t stream, const TracksShapedArgs &a);
+// The window form: of every track's slice the frames inside the window (tracks_finish_cut), as a one-stream shaped call on them
+// with first_frame = their index in the track and the track's entries of the state.
+hipError_t launch_tracks_finish_shaped_window(hipStream_t stream, const TracksShapedWindowArgs &a);
 // RRX_finish_shaped_device's results on host pointers, as one serial loop per channel over shaped_front and shaped_step
 // (test hook: RRX_debug_finish_shaped_host).
 void finish_shaped_host(const ShapedArgs &a);
+// RRX_tracks_finish_shaped_window_device's results on host pointers and a HOST table, as one serial loop per (track, channel) over
+// tracks_finish_cut, shaped_front and shaped_step (test hook: RRX_debug_tracks_finish_shaped_window_host).
+void tracks_finish_shaped_window_host(const TracksShapedWindowArgs &a);
 
 } // namespace rsmp

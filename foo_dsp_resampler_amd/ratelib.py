@@ -25,6 +25,7 @@ EXPECTED_SYMBOLS = [
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
+    "RRX_tracks_finish_shaped_window_device", "RRX_debug_tracks_finish_shaped_window_host",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
     "RRX_reset", "RRX_tracks_batches", "RRX_plan_cache_clear", "RRX_plan_cache_stats",
@@ -223,6 +224,11 @@ def lib():
             L.RRX_tracks_finish_window_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp,
                                                           C.c_int, u64, vp, vp]
             L.RRX_debug_tracks_window_cut.argtypes = [P(RRXTrack), sz, sz, sz, C.c_int, sz, sz, P(u64), P(u64)]
+        if hasattr(L, "RRX_tracks_finish_shaped_window_device"):  # (as above)
+            u64 = C.c_ulonglong
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp, C.c_int, u64, vp, C.c_int, sz, vp, vp, vp, vp]
+            L.RRX_tracks_finish_shaped_window_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_finish_shaped_window_host.argtypes = host
         if hasattr(L, "RRX_reset"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_reset.argtypes = [vp]
@@ -701,7 +707,8 @@ def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=F
 def tracks_finish_shaped_device(rows, table, dst_format, dst_total, shaping, segment=65536, gain=None, dither=True, seed=0, out=None, peak=None,
                                 clipped=None, stream=None):
     """tracks_finish_device with noise-shaped dither (RRX_tracks_finish_shaped_device): finish_shaped_device per track, in one
-    call, with the frames and the segments counted from each track's own first output frame and no state -- whole rows only.
+    call, with the frames and the segments counted from each track's own first output frame and no state -- whole rows only
+    (by windows, with a state per track: tracks_finish_shaped_window_device).
     `shaping` and `segment` are finish_shaped_device's, everything else tracks_finish_device's, except that `dst_format` is never
     None (`out=False` measures only).  Returns (out, peak, clipped).  The call only enqueues."""
     dt = str(rows.dtype)
@@ -795,6 +802,67 @@ def tracks_finish_window_device(win, table, row_frames, win_first, win_frames, d
                                                  C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
                                                  C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_window_device")
     return out, peak, clipped
+
+
+def tracks_finish_shaped_window_device(win, table, row_frames, win_first, win_frames, dst_format, dst_total, shaping, segment=65536, gain=None,
+                                       dither=True, seed=0, state=None, out=None, peak=None, clipped=None, stream=None):
+    """tracks_finish_shaped_device on a window of the output rows (RRX_tracks_finish_shaped_window_device): tracks_finish_window_device
+    with noise-shaped dither, the error history of every (track, channel) carried from window to window in `state`.
+
+    `win`, `table`, `row_frames`, `win_first`, `win_frames`, `dst_total`, `gain`, `seed`, `out`, `peak`, `clipped` and `stream` are
+    tracks_finish_window_device's, `shaping` and `segment` finish_shaped_device's; `dst_format` is never None (`out=False` measures
+    only).  `state`: None, or the float64 [ntracks, nch, 16] tensor the call before returned; None is allowed only for the window
+    at frame 0 (ValueError otherwise).  UNLIKE the unshaped window call this one depends on the order of the calls: windows that
+    partition [0, row_frames), taken in ascending contiguous order, each given the `out`, `peak`, `clipped` and `state` of the one
+    before, leave tracks_finish_shaped_device's bytes and statistics; anything else gives other samples.  Returns (out, peak,
+    clipped, state): `state` is a NEW tensor on every call, holding every track's history -- handed on unchanged for the tracks the
+    window did not touch, and the state that came in (or zeros) when `win_frames` is 0.  The call only enqueues."""
+    return _tracks_finish_shaped_window(win, table, row_frames, win_first, win_frames, dst_format, dst_total, shaping, segment, gain, dither, seed,
+                                        state, None, out, peak, clipped, stream)
+
+
+def _tracks_finish_shaped_window(win, table, row_frames, win_first, win_frames, dst_format, dst_total, shaping, segment, gain, dither, seed, state,
+                                 state_out, out, peak, clipped, stream):
+    """tracks_finish_shaped_window_device with the tensor that receives the state given (`state_out`, checked as `state` is; None:
+    a new one), for a caller that hands two tensors to and fro (Resampler._convert_tracks_streamed)"""
+    import torch
+    dt = str(win.dtype)
+    if win.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not win.is_cuda or not win.is_contiguous():
+        raise TypeError("win must be a contiguous float32 or float64 device tensor [ntracks, win_stride, nch]")
+    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+    coefs, segment = _shaping(shaping, segment)
+    ntracks, win_stride, nch = win.shape
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
+    if win_frames > win_stride:
+        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
+    if state is None and win_first:
+        raise ValueError("only the window at frame 0 needs no state: pass the state the call before returned")
+    dev = win.device
+    sshape = (ntracks, nch, RRX_SHAPE_MAX_ORDER)
+    for t, name in ((state, "state"), (state_out, "state_out")):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != sshape or t.device != dev or not t.is_contiguous()):
+            raise TypeError("%s must be a contiguous float64 tensor %r on %s" % (name, sshape, dev))
+    if state is not None and state_out is not None and state_out.data_ptr() == state.data_ptr():
+        raise ValueError("the call must not read and write one state tensor")
+    measure = out is False
+    seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(win, table, None if measure else dst_format, dst_total, gain, seed,
+                                                                       None if measure else out, peak, clipped)
+    if not win_frames or not row_frames:  # touches nothing, the state included: the state handed on is the one that came in
+        return out, peak, clipped, torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
+    new_state = torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out  # (every entry is written)
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
+    _check(lib().RRX_tracks_finish_shaped_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
+                                                        ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
+                                                        C.c_void_p(win.data_ptr()), win_stride, row_frames, win_first, win_frames, dst_format,
+                                                        C.c_void_p(out.data_ptr()) if write else None, dst_total,
+                                                        C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
+                                                        C.cast(coefs, C.c_void_p), len(coefs), segment,
+                                                        C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(new_state.data_ptr()),
+                                                        C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())),
+           "RRX_tracks_finish_shaped_window_device")
+    return out, peak, clipped, new_state
 
 
 def _ensure_init():
@@ -1274,19 +1342,43 @@ class Resampler:
         drain -- put every track's last output frame inside what comes out whatever the pattern is.
 
         `shaping` is accepted for symmetry with convert_tracks_to_pcm_device and refused: noise shaping needs a per-track state
-        across windows, and the windowed form of it is not built."""
-        import torch
+        across windows, and the windowed form of it is not built.  (It is built under a name of its own,
+        convert_tracks_to_pcm_streamed_shaped, which carries that state.)"""
         if shaping is not None:
             raise ValueError("noise shaping in the windowed form is not built: use convert_tracks_to_pcm_device")
+        return self._convert_tracks_streamed(tracks, dst_format, window, _scratch, None, finish_kw, "convert_tracks_to_pcm_streamed")
+
+    def convert_tracks_to_pcm_streamed_shaped(self, tracks, dst_format, shaping, segment=65536, window=None, **finish_kw):
+        """convert_tracks_to_pcm_device(..., shaping=, segment=) in bounded memory: convert_tracks_to_pcm_streamed with noise-shaped
+        dither.  The loop is that method's; every pulled window is finished by tracks_finish_shaped_window_device at the running
+        output position -- the pulls are ascending and contiguous from frame 0, the order that call needs -- and the error history of
+        every (track, channel) is handed from window to window through two state tensors [nstreams, nch, 16] (float64), allocated
+        besides the two windows.  `shaping` (a name of NOISE_SHAPES or coefficients) and `segment` are finish_shaped_device's; dither
+        is on by default, `dst_format` is never None and `out=False` measures only.  Returns (views, peak, clipped), equal bit for bit
+        to convert_tracks_to_pcm_device(tracks, dst_format, shaping=shaping, segment=segment, ...) whatever `window` is.
+
+        A track's segments that fall into different windows no longer run side by side, so this form costs about (number of output
+        windows) * min(segment, output window) frames of the serial chain where the whole-row form costs `segment` (DESIGN.md 11,
+        "Windows with noise shaping").  The name is new because convert_tracks_to_pcm_streamed(..., shaping=) is pinned as a refusal."""
+        _shaping(shaping, segment)  # (refused before anything is planned)
+        scratch = finish_kw.pop("_scratch", None)
+        return self._convert_tracks_streamed(tracks, dst_format, window, scratch, (shaping, segment), finish_kw, "convert_tracks_to_pcm_streamed_shaped")
+
+    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who):
+        """the loop of convert_tracks_to_pcm_streamed (shaped None) and convert_tracks_to_pcm_streamed_shaped (shaped = (shaping,
+        segment)): stage a window, push it, pull whatever is available into the output window and finish it at the running output
+        position, then drain the same way.  The shaped form finishes with tracks_finish_shaped_window_device and ping-pongs two
+        state tensors."""
+        import torch
         tracks, plan = self._tracks_checked(tracks)
         n, dev = len(tracks), tracks[0].device
         step = self.isamp_max
         window = step if window is None else int(window)
         if not 1 <= window <= step:
             raise ValueError("window must be 1 to isamp_max = %d frames, not %d" % (step, window))
-        self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_streamed")
+        self._tracks_finish_kw(n, finish_kw, who)
         if finish_kw.get("stream") is not None:
-            raise ValueError("convert_tracks_to_pcm_streamed runs on torch's current stream")
+            raise ValueError("%s runs on torch's current stream" % who)
         in_rate, out_rate = self.cfg.in_rate, self.cfg.out_rate
         cur = torch.cuda.current_stream(dev)
         finish_kw["stream"] = cur
@@ -1301,8 +1393,19 @@ class Resampler:
             win = torch.empty((self.nstreams, min(window, max(total, 1)), self.nch), dtype=torch.float32, device=dev)
             wout = torch.empty((self.nstreams, min(win_out, cap), self.nch), dtype=torch.float32, device=dev)
         # nothing to finish yet: allocates (and checks) the destination and the statistics
-        pcm, peak, clipped = tracks_finish_window_device(wout, table, cap, 0, 0, dst_format, plan.dst_total, **finish_kw)
-        finish_kw.update(out=pcm, peak=peak, clipped=clipped)
+        if shaped is None:
+            pcm, peak, clipped = tracks_finish_window_device(wout, table, cap, 0, 0, dst_format, plan.dst_total, **finish_kw)
+            finish_kw.update(out=pcm, peak=peak, clipped=clipped)
+        else:
+            pcm, peak, clipped = tracks_finish_shaped_window_device(wout, table, cap, 0, 0, dst_format, plan.dst_total, *shaped, **finish_kw)[:3]
+            finish_kw.update(out=False if pcm is None else pcm, peak=peak, clipped=clipped)
+            # the history of every (track, channel): read from one tensor and written to the other, window after window
+            states = [torch.zeros((self.nstreams, self.nch, RRX_SHAPE_MAX_ORDER), dtype=torch.float64, device=dev) for _ in range(2)]
+
+            def shaped_window(first, frames):
+                kw = dict({"gain": None, "dither": True, "seed": 0}, **finish_kw)
+                _tracks_finish_shaped_window(wout, table, cap, first, frames, dst_format, plan.dst_total, shaped[0], shaped[1], kw["gain"],
+                                             kw["dither"], kw["seed"], states[0], states[1], kw["out"], kw["peak"], kw["clipped"], kw["stream"])
         if finish_kw.get("gain") is not None and not hasattr(finish_kw["gain"], "data_ptr"):
             finish_kw["gain"] = torch.full((self.nstreams,), float(finish_kw["gain"]), dtype=torch.float64, device=dev)  # (once, not per window)
         got = 0
@@ -1315,9 +1418,13 @@ class Resampler:
                     nonlocal got
                     while self.available:
                         if got >= cap:
-                            raise RuntimeError("convert_tracks_to_pcm_streamed: more output than %d frames in gives" % total)
+                            raise RuntimeError("%s: more output than %d frames in gives" % (who, total))
                         k = self.pull_device(wout, min(wout.shape[1], cap - got), stride=wout.shape[1])
-                        tracks_finish_window_device(wout, table, cap, got, k, dst_format, plan.dst_total, **finish_kw)
+                        if shaped is None:
+                            tracks_finish_window_device(wout, table, cap, got, k, dst_format, plan.dst_total, **finish_kw)
+                        elif k:  # (an empty window touches nothing, the state included: the two tensors keep their roles)
+                            shaped_window(got, k)
+                            states.reverse()
                         got += k
 
                 for pos in range(0, total, window):
@@ -1334,7 +1441,7 @@ class Resampler:
                     self.set_stream(prev)
         need = max(int(e.out_first + e.out_frames) for e in plan.table)
         if got < need:
-            raise RuntimeError("convert_tracks_to_pcm_streamed: %d output frames where the plan expects %d" % (got, need))
+            raise RuntimeError("%s: %d output frames where the plan expects %d" % (who, got, need))
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
 
@@ -1376,10 +1483,30 @@ class Resampler:
 
         `shaping` (a name of NOISE_SHAPES or coefficients) and `segment`: every batch is finished by tracks_finish_shaped_device
         with the same per-batch seed, so the rule above holds with finish_shaped_device for finish_device; `dither` keeps its
-        default here.  With `window` it raises ValueError: the windowed form of noise shaping is not built."""
-        import torch
+        default here.  With `window` it raises ValueError: the windowed form of noise shaping is not built (under this name:
+        convert_library_to_pcm_streamed_shaped is that form)."""
         if shaping is not None and window is not None:
             raise ValueError("noise shaping in the windowed form is not built: leave `window` out")
+        kw = {} if shaping is None else {"shaping": shaping, "segment": segment}
+        if window is None:
+            return self._convert_library(tracks, dst_format, gain, dither, seed, lambda batch, bkw: self.convert_tracks_to_pcm_device(batch, dst_format, **kw, **bkw))
+        return self._convert_library(tracks, dst_format, gain, dither, seed,
+                                     lambda batch, bkw: self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **bkw))
+
+    def convert_library_to_pcm_streamed_shaped(self, tracks, dst_format, window, shaping, segment=65536, gain=None, dither=True, seed=0):
+        """convert_library_to_pcm(..., shaping=, segment=) in bounded memory: the library rule of that method -- length-sorted
+        batches, reset() between them, the per-batch seed shift, the window buffers taken once -- with every batch run through
+        convert_tracks_to_pcm_streamed_shaped(batch, dst_format, shaping, segment, window=window).  A track's bytes and statistics
+        are those convert_library_to_pcm(..., shaping=, segment=) gives it without a window: they depend neither on `nstreams` nor
+        on `window` (None: isamp_max).  `dst_format` is never None.  The name is new for the reason given there."""
+        _shaping(shaping, segment)
+        return self._convert_library(tracks, dst_format, gain, dither, seed,
+                                     lambda batch, bkw: self.convert_tracks_to_pcm_streamed_shaped(batch, dst_format, shaping, segment, window=window, **bkw))
+
+    def _convert_library(self, tracks, dst_format, gain, dither, seed, convert):
+        """the library rule of convert_library_to_pcm: `convert(batch, kw)` is one batch's conversion, kw its dither, seed, scratch
+        and gains"""
+        import torch
         tracks = list(tracks)
         n, S = len(tracks), self.nstreams
         if n < 1:
@@ -1409,16 +1536,11 @@ class Resampler:
             if self._used:
                 self.reset()
             kw = {"dither": dither, "seed": (seed + b * S * self.nch * 0xBF58476D1CE4E5B9) % (1 << 64), "_scratch": scratch}
-            if shaping is not None:
-                kw.update(shaping=shaping, segment=segment)
             where = torch.tensor(idx, dtype=torch.int64, device=dev)
             if gain is not None:
                 kw["gain"] = gain[where].contiguous()
             batch = [tracks[i] for i in idx]
-            if window is None:
-                v, p, c = self.convert_tracks_to_pcm_device(batch, dst_format, **kw)
-            else:
-                v, p, c = self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **kw)
+            v, p, c = convert(batch, kw)
             peak[where] = p
             clipped[where] = c
             if v is not None:

@@ -458,7 +458,8 @@ int RRX_tracks_finish_device(int device, void *hip_stream, const RRX_track *d_tr
  * destination, gains, statistics, clamps (a wrong table gives wrong samples, never an access outside the buffers), device,
  * hip_stream and refusals are RRX_tracks_finish_device's; coefs, order and segment are RRX_finish_shaped_device's, refused as
  * there, and as there dst_format must be valid when d_dst is NULL too (its bits are used).  Frame i and the segments are counted
- * from the track's own first output frame, and there is no state: whole rows only.  Track t gets the bytes and statistics of a
+ * from the track's own first output frame, and there is no state: whole rows only (RRX_tracks_finish_shaped_window_device, below,
+ * is the form by windows, with a state per track).  Track t gets the bytes and statistics of a
  * one-stream RRX_finish_shaped_device call on its slice with seed + t * nch * 0xBF58476D1CE4E5B9 (mod 2^64) for seed,
  * first_frame = 0 and no state.  row_frames == 0 is RR_OK and does nothing. */
 int RRX_tracks_finish_shaped_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
@@ -501,6 +502,56 @@ int RRX_tracks_finish_window_device(int device, void *hip_stream, const RRX_trac
                                     const void *d_win, size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
                                     int dst_format, void *d_dst, size_t dst_total, const double *d_gain, int dither,
                                     unsigned long long seed, double *d_peak, unsigned long long *d_clipped);
+/* RRX_tracks_finish_shaped_device by windows: RRX_tracks_finish_window_device with noise-shaped dither.  The error history of a
+ * channel runs on from one window into the next, so the call takes and returns a per-(track, channel) STATE, and -- unlike the
+ * unshaped window call -- it depends on the order of the calls.
+ *   Frames taken.  d_win, win_stride, row_frames, win_first, win_frames and the clamps under a wrong table are
+ *   RRX_tracks_finish_window_device's, through the same function: of track t's slice [out_first, out_first + out_frames), clamped
+ *   as there, the frames inside the window are processed.  They are frames index, index + 1, ... of the slice (index = the first
+ *   one's row frame - out_first) and go to frames dst_first + index, ... of the destination.  Exactly the bytes of the processed
+ *   samples are written, at any byte offset; d_peak and d_clipped accumulate.
+ *   Arithmetic.  Track t's processed frames get the bytes and statistics of a one-stream RRX_finish_shaped_device call on them
+ *   with first_frame = index, seed + t * nch * 0xBF58476D1CE4E5B9 (mod 2^64) for seed, d_gain[t], the same coefs, order, segment,
+ *   dither and dst_format, and track t's entries of d_state_in as the incoming state.  Segments and the dither index are counted
+ *   from the track's own first output frame, never from the window: the history of a channel is all +0.0 at index == 0 and at
+ *   every index % segment == 0 (segment != 0), so a window cuts every track's segments at a different place.
+ *   State.  d_state_in and d_state_out are [ntracks * nch][RRX_SHAPE_MAX_ORDER] doubles on the device; entry k-1 of a channel is
+ *   e[k], entries at `order` and beyond are 0.  d_state_in is read for a track only when that track's first processed frame of
+ *   this call lies inside a segment.  Every call with win_frames > 0 and row_frames > 0 writes EVERY entry of d_state_out (when
+ *   it is not NULL): for a track with processed frames in this window the history after its last one; for a track with none (not
+ *   begun, already ended, zero length) a copy of its d_state_in entries, or zeros when d_state_in is NULL.  A caller therefore
+ *   ping-pongs two buffers without knowing which tracks a window touched.  d_state_in NULL is allowed only with win_first == 0 --
+ *   no track can have begun earlier -- and is RR_INVPARAM otherwise; the table is device memory, so this is the only check the
+ *   host can make.  The two buffers must not overlap over ntracks * nch * 16 doubles (RR_INVPARAM, equal pointers included), for
+ *   the reason RRX_finish_shaped_device gives.  d_state_out may be NULL.
+ *   Order of calls.  The promise "the bytes and statistics of one RRX_tracks_finish_shaped_device call, bit for bit, for any cut
+ *   positions" holds ONLY when the windows partition [0, row_frames), are processed in ascending, contiguous order, and each
+ *   call's d_state_out is the next call's d_state_in.  Anything else -- windows out of order, a gap, an overlap, a state from
+ *   somewhere else -- gives other samples, never an access outside the buffers.
+ *   Identities.  With order = 1 and coefs[0] = 0.0 it is RRX_tracks_finish_window_device, bit for bit, with and without dither.
+ *   d_dst NULL measures only; as in the other shaped calls dst_format must still be valid and its bits are used.
+ * Returns RR_INVPARAM, before any device is touched, for everything RRX_tracks_finish_window_device refuses (the three window
+ * refusals included), everything RRX_tracks_finish_shaped_device adds (coefs NULL, order outside 1..RRX_SHAPE_MAX_ORDER, a
+ * non-finite coefficient, an unknown dst_format even with d_dst NULL) and the two state rules above.  row_frames == 0 or
+ * win_frames == 0 is RR_OK and touches nothing, the state included.  The call only enqueues (no allocation, no host
+ * synchronisation); device, hip_stream and stream ordering are the sibling calls'. */
+int RRX_tracks_finish_shaped_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                           int src_format, const void *d_win, size_t win_stride, size_t row_frames,
+                                           size_t win_first, size_t win_frames, int dst_format, void *d_dst, size_t dst_total,
+                                           const double *d_gain, int dither, unsigned long long seed,
+                                           const double *coefs, int order, size_t segment,
+                                           const double *d_state_in, double *d_state_out,
+                                           double *d_peak, unsigned long long *d_clipped);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above:
+ * RRX_tracks_finish_shaped_window_device on HOST pointers and a HOST table, as one serial loop per (track, channel) over the very
+ * functions the kernel calls for the cut and for every sample.  Same refusals, same results. */
+int RRX_debug_tracks_finish_shaped_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win,
+                                               size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                               int dst_format, void *dst, size_t dst_total, const double *gain, int dither,
+                                               unsigned long long seed, const double *coefs, int order, size_t segment,
+                                               const double *state_in, double *state_out, double *peak,
+                                               unsigned long long *clipped);
+
 /* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: what the two window calls take
  * from one HOST table entry for the window [win_first, win_first + win_frames) of rows of row_frames frames, computed by the very
  * functions their kernels call.  stage[10]: the window-relative half-open ranges of the backward extension, the copied track, the

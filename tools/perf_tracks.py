@@ -55,6 +55,22 @@ line {"what": "streamed", "window", "isamp_max", "whole_rows_ms", "streamed_ms",
 
   python tools/perf_tracks.py --streamed [--window FRAMES] [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
 
+--streamed --shaped measures noise-shaped dither in the window form on the same batch, S16 tracks in, packed S16 out, `wannamaker9`,
+at segments 4096, 16384 and 65536, and appends one line per segment to profiles/tracks_window_shaped_perf.jsonl.  Three ways in one
+process, each on a fresh handle:
+
+  streamed_shaped     convert_tracks_to_pcm_streamed_shaped(window=--window): two windows, two states and no rows;
+  whole_rows_shaped   convert_tracks_to_pcm_device(shaping=): every row whole, all segments of a track side by side;
+  streamed            convert_tracks_to_pcm_streamed, dither without shaping: what the windows cost without the serial chain.
+
+The two shaped results are compared first ("equal"); warm-up, rounds, medians, ranges and peak memory as above.  One JSON line
+{"what": "streamed_shaped", "segment", "shaping", "window", "win_out", "windows_out", "<way>_ms", "<way>_ms_rounds", "<way>_range_ms",
+"<way>_peak_bytes", "streamed_shaped_over_whole_rows_shaped", "streamed_shaped_over_streamed", "chain_frames_streamed": windows_out *
+min(segment, win_out), "chain_frames_whole_rows": min(segment, longest output), "equal"} -- the chain lengths DESIGN.md 11 predicts
+the cost from.
+
+  python tools/perf_tracks.py --streamed --shaped [--window FRAMES] [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
+
 --library measures a library on ONE handle ("Libraries"): the same LCG lengths, 256 tracks (--tracks) on a handle of 64
 streams (--streams), S16 tracks in, packed S24 out with dither and per-track gains, at phase 50 and at phase 25, and appends to
 profiles/tracks_library_perf.jsonl:
@@ -287,6 +303,92 @@ def streamed_parts(a, lens, plan, packed, window):
     return out
 
 
+def compare_ways(a, plan, ways, one, other):
+    """what the --streamed runs share: every way of `ways` ({name: run(keep=False)}) warmed up once, `one` and `other` compared byte
+    for byte and statistic for statistic, the peak allocation of each over a call of its own, then `a.rounds` rounds interleaved.
+    (first call ms, equal, peak bytes, ms per round, medians)"""
+    first = {k: round(timed(fn)[0], 2) for k, fn in ways.items()}        # warm-up: code objects, the caching allocator
+    a_res, b_res = ways[one](keep=True), ways[other](keep=True)
+    equal = bool(torch.equal(a_res[0][0]._base, b_res[0][0]._base) and torch.equal(a_res[1].view(torch.int64), b_res[1].view(torch.int64))
+                 and torch.equal(a_res[2], b_res[2]))
+    del a_res, b_res
+    peak = {}
+    for k, fn in ways.items():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        peak[k] = torch.cuda.max_memory_allocated() - before
+    for fn in ways.values():                                             # (the cache was emptied: fill it again before timing)
+        fn()
+    ms = {k: [] for k in ways}
+    for _ in range(a.rounds):
+        for k, fn in ways.items():
+            t, got = timed(fn)
+            ms[k].append(t)
+            assert got == [int(e.out_frames) for e in plan.table], k
+    return first, equal, peak, ms, {k: statistics.median(t) for k, t in ms.items()}
+
+
+def ways_into(line, ways, peak, ms, med):
+    for k in ways:
+        line[k + "_ms"] = round(med[k], 2)
+        line[k + "_ms_rounds"] = [round(t, 2) for t in ms[k]]
+        line[k + "_range_ms"] = [round(min(ms[k]), 2), round(max(ms[k]), 2)]
+        line[k + "_peak_bytes"] = peak[k]
+
+
+SHAPED_SEGMENTS = (4096, 16384, 65536)
+
+
+def streamed_shaped_main(a, lens):
+    plan = F.tracks_plan(FS, FO, lens)
+    v = pcm_source(lens, 15, a.seed)
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + n)
+    tracks = [v[offs[t]:offs[t + 1]] for t in range(len(lens))]
+    kw = dict(dither=True, seed=a.seed)
+    shaping, fmt = "wannamaker9", F.RRX_FMT_S16
+    isamp_max = [0]
+    for segment in SHAPED_SEGMENTS:
+        def form(which):
+            def run(keep=False):
+                r = F.Resampler(FS, FO, nch=NCH, nstreams=len(tracks))
+                isamp_max[0] = r.isamp_max
+                if which == "streamed_shaped":
+                    res = r.convert_tracks_to_pcm_streamed_shaped(tracks, fmt, shaping, segment, window=a.window, **kw)
+                elif which == "whole_rows_shaped":
+                    res = r.convert_tracks_to_pcm_device(tracks, fmt, shaping=shaping, segment=segment, **kw)
+                else:
+                    res = r.convert_tracks_to_pcm_streamed(tracks, fmt, window=a.window, **kw)
+                r.close()
+                return res if keep else [y.shape[0] for y in res[0]]
+            return run
+
+        ways = {k: form(k) for k in ("streamed_shaped", "whole_rows_shaped", "streamed")}
+        first, equal, peak, ms, med = compare_ways(a, plan, ways, "whole_rows_shaped", "streamed_shaped")
+        window = a.window if a.window is not None else isamp_max[0]
+        total = plan.row_frames + -(-2 * FS // FO) + 1                   # the virtual rows of the streamed forms (ratelib.py)
+        cap, win_out = total * FO // FS + 2, -(-window * FO // FS)
+        windows_out = -(-cap // min(win_out, cap))
+        line = {"what": "streamed_shaped", "segment": segment, "shaping": shaping, "src_format": "s16", "dst_format": "s16", "seed": a.seed,
+                "tracks": len(lens), "nch": NCH, "in_rate": FS, "out_rate": FO, "frames_total": sum(lens), "row_frames": plan.row_frames,
+                "out_row_cap": plan.out_row_cap, "window": window, "isamp_max": isamp_max[0], "win_out": win_out, "windows_out": windows_out}
+        ways_into(line, ways, peak, ms, med)
+        line.update({"streamed_shaped_over_whole_rows_shaped": round(med["streamed_shaped"] / med["whole_rows_shaped"], 3),
+                     "streamed_shaped_over_streamed": round(med["streamed_shaped"] / med["streamed"], 3),
+                     "chain_frames_streamed": windows_out * min(segment, win_out),
+                     "chain_frames_whole_rows": min(segment, max(int(e.out_frames) for e in plan.table)),
+                     "tracks_bytes": v.numel() * v.element_size(), "first_call_ms": first, "equal": equal, "rounds": a.rounds})
+        text = json.dumps(line)
+        print(text, flush=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+
+
 def streamed_main(a, lens):
     plan = F.tracks_plan(FS, FO, lens)
     v = pcm_source(lens, 15, a.seed)
@@ -310,37 +412,11 @@ def streamed_main(a, lens):
         return run
 
     ways = {"whole_rows": form(False), "streamed": form(True)}
-    first = {k: round(timed(fn)[0], 2) for k, fn in ways.items()}        # warm-up: code objects, the caching allocator
-    a_res, b_res = ways["whole_rows"](keep=True), ways["streamed"](keep=True)
-    equal = bool(torch.equal(a_res[0][0]._base, b_res[0][0]._base) and torch.equal(a_res[1].view(torch.int64), b_res[1].view(torch.int64))
-                 and torch.equal(a_res[2], b_res[2]))
-    del a_res, b_res
-    peak = {}
-    for k, fn in ways.items():
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        fn()
-        torch.cuda.synchronize()
-        peak[k] = torch.cuda.max_memory_allocated() - before
-    for fn in ways.values():                                             # (the cache was emptied: fill it again before timing)
-        fn()
-    ms = {k: [] for k in ways}
-    for _ in range(a.rounds):
-        for k, fn in ways.items():
-            t, got = timed(fn)
-            ms[k].append(t)
-            assert got == [int(e.out_frames) for e in plan.table], k
-    med = {k: statistics.median(t) for k, t in ms.items()}
+    first, equal, peak, ms, med = compare_ways(a, plan, ways, "whole_rows", "streamed")
     line = {"what": "streamed", "src_format": "s16", "dst_format": "s24_3", "seed": a.seed, "tracks": len(lens), "nch": NCH, "in_rate": FS,
             "out_rate": FO, "frames_total": sum(lens), "row_frames": plan.row_frames, "out_row_cap": plan.out_row_cap,
             "window": a.window if a.window is not None else isamp_max[0], "isamp_max": isamp_max[0]}
-    for k in ways:
-        line[k + "_ms"] = round(med[k], 2)
-        line[k + "_ms_rounds"] = [round(t, 2) for t in ms[k]]
-        line[k + "_range_ms"] = [round(min(ms[k]), 2), round(max(ms[k]), 2)]
-        line[k + "_peak_bytes"] = peak[k]
+    ways_into(line, ways, peak, ms, med)
     line.update({"streamed_over_whole_rows": round(med["streamed"] / med["whole_rows"], 3), "tracks_bytes": v.numel() * v.element_size(),
                  "first_call_ms": first, "equal": equal, "rounds": a.rounds, "parts_ms": streamed_parts(a, lens, plan, v, line["window"])})
     text = json.dumps(line)
@@ -463,6 +539,7 @@ def main():
     ap.add_argument("--pcm", action="store_true", help="integer sources of the stage pass instead (see above)")
     ap.add_argument("--streamed", action="store_true", help="the window form against the whole-row form instead (see above)")
     ap.add_argument("--window", type=int, default=None, help="--streamed: frames of the input window (default: isamp_max)")
+    ap.add_argument("--shaped", action="store_true", help="--streamed: noise-shaped dither in the window form instead (see above)")
     ap.add_argument("--library", action="store_true", help="a library on one handle against fresh handles per batch instead (see above)")
     ap.add_argument("--streams", type=int, default=64, help="--library: streams of the handle")
     ap.add_argument("--out", default=None)
@@ -470,7 +547,8 @@ def main():
     if a.tracks is None:
         a.tracks = 256 if a.library else 64
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "tracks_library_perf.jsonl" if a.library else "tracks_window_perf.jsonl" if a.streamed else
+        a.out = os.path.join(ROOT, "profiles", "tracks_library_perf.jsonl" if a.library else "tracks_window_shaped_perf.jsonl" if a.streamed and a.shaped else
+                             "tracks_window_perf.jsonl" if a.streamed else
                              "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("perf_tracks.py needs a GPU: there is nothing to time without one")
@@ -478,8 +556,10 @@ def main():
     print("seed %d: %d tracks, %.1f to %.1f s, %.1f s in all" % (a.seed, len(lens), min(lens) / FS, max(lens) / FS, sum(lens) / FS), flush=True)
     if a.library:
         return library_main(a, lens)
+    if a.shaped and not a.streamed:
+        raise SystemExit("--shaped goes with --streamed")
     if a.streamed:
-        return streamed_main(a, lens)
+        return streamed_shaped_main(a, lens) if a.shaped else streamed_main(a, lens)
     if a.pcm:
         return pcm_main(a, lens)
     plan = F.tracks_plan(FS, FO, lens)
