@@ -9,11 +9,13 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       lpc_extrapolate_device, finish_device, plan_table, RRXTrack, TracksPlan, track_geometry, tracks_plan,
                       tracks_stage_device, tracks_finish_device, tracks_stage_window_device, tracks_finish_window_device,
                       TracksBatches, tracks_batches, plan_cache_clear, plan_cache_stats, RR_BEST, RR_NORM, RRX_FMT_FLOAT, RRX_FMT_DOUBLE, RRX_FMT_S16, RRX_FMT_S32, RRX_FMT_S24_3, EXPECTED_SYMBOLS,
-                      finish_shaped_device, tracks_finish_shaped_device, tracks_finish_shaped_window_device, NOISE_SHAPES, RRX_SHAPE_MAX_ORDER)
+                      finish_shaped_device, tracks_finish_shaped_device, tracks_finish_shaped_window_device, NOISE_SHAPES, RRX_SHAPE_MAX_ORDER,
+                      true_peak_device, tracks_true_peak_device, TRUE_PEAK_FILTERS, RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
            "TracksBatches", "tracks_batches", "plan_cache_clear", "plan_cache_stats",
            "lib_path",
            "available_symbols", "RR_BEST", "RR_NORM", "RRX_FMT_FLOAT", "RRX_FMT_DOUBLE", "RRX_FMT_S16", "RRX_FMT_S32", "RRX_FMT_S24_3",
-           "EXPECTED_SYMBOLS", "finish_shaped_device", "tracks_finish_shaped_device", "tracks_finish_shaped_window_device", "NOISE_SHAPES", "RRX_SHAPE_MAX_ORDER"]
+           "EXPECTED_SYMBOLS", "finish_shaped_device", "tracks_finish_shaped_device", "tracks_finish_shaped_window_device", "NOISE_SHAPES", "RRX_SHAPE_MAX_ORDER",
+           "true_peak_device", "tracks_true_peak_device", "TRUE_PEAK_FILTERS", "RRX_TP_MAX_PHASES", "RRX_TP_MAX_TAPS"]

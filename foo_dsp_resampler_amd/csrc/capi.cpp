@@ -7,6 +7,7 @@
 #include "finish_shaped.hpp"
 #include "lpc.hpp"
 #include "tracks.hpp"
+#include "true_peak.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -970,6 +971,125 @@ int RRX_debug_finish_shaped_host(int src_format, const void *src, size_t src_str
   if (rc != RR_OK) return rc;
   if (frames) rsmp::finish_shaped_host(a);
   return RR_OK;
+}
+
+namespace {
+
+// the filter of the true-peak calls: RR_INVPARAM for a NULL pointer, a shape outside 1..RRX_TP_MAX_PHASES x 1..RRX_TP_MAX_TAPS or a
+// non-finite coefficient; `out` gets the phases * taps coefficients as they are, without padding
+int true_peak_filter(const double *coefs, int phases, int taps, rsmp::TruePeakFilter &out)
+{
+  static_assert(RRX_TP_MAX_PHASES == rsmp::kTpMaxPhases && RRX_TP_MAX_TAPS == rsmp::kTpMaxTaps, "the header's constants are the kernels'");
+  if (!coefs || phases < 1 || phases > RRX_TP_MAX_PHASES || taps < 1 || taps > RRX_TP_MAX_TAPS) return RR_INVPARAM;
+  for (int k = 0; k < rsmp::kTpMaxPhases * rsmp::kTpMaxTaps; ++k) {
+    out.c[k] = k < phases * taps ? coefs[k] : 0.0; // (never read beyond phases * taps)
+    if (!std::isfinite(out.c[k])) return RR_INVPARAM;
+  }
+  out.phases = phases;
+  out.taps = taps;
+  return RR_OK;
+}
+
+// RRX_true_peak_device / RRX_debug_true_peak_host: everything that can be refused from the arguments alone
+int true_peak_args(int src_format, const void *src, size_t src_stride, int nstreams, size_t frames, int nch, const double *gain,
+                   unsigned long long first_frame, const double *coefs, int phases, int taps, int flush, const double *state_in,
+                   double *state_out, double *true_peak, double *peak, rsmp::TruePeakArgs &a)
+{
+  int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  rsmp::FinishArgs f; // the sizes, strides and overflow rules are RRX_finish_device's, measuring only
+  rc = finish_args(src_format, src, src_stride, 0, nullptr, 0, nstreams, frames, nch, gain, 0, 0, first_frame, peak ? peak : true_peak, nullptr, f);
+  if (rc != RR_OK) return rc;
+  if (!state_in && first_frame) return RR_INVPARAM; // a call that does not begin the stream needs the history in front of it
+  if (state_in && state_out) { // [nstreams * nch][16] doubles each (finish_shaped_args)
+    const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
+    const uintptr_t bytes = uintptr_t(nstreams) * uintptr_t(nch) * rsmp::kTpMaxTaps * sizeof(double);
+    if (x < y ? y - x < bytes : x - y < bytes) return RR_INVPARAM;
+  }
+  a.src = f.src;
+  a.gain = gain;
+  a.state_in = first_frame ? state_in : nullptr; // in front of absolute frame 0 lies +0.0, whatever the buffer holds
+  a.state_out = state_out;
+  a.true_peak = true_peak;
+  a.peak = peak;
+  a.tracks = nullptr;
+  a.src_stride = f.src_stride;
+  a.frames = frames;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  a.src_double = f.src_double;
+  a.flush = flush != 0;
+  return RR_OK;
+}
+
+} // namespace
+
+// True peak and sample peak of device-resident frames (true_peak.hip).  Refusals first, as in RRX_finish_device.
+int RRX_true_peak_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int nstreams, size_t frames,
+                         int nch, const double *d_gain, unsigned long long first_frame, const double *coefs, int phases, int taps, int flush,
+                         const double *d_state_in, double *d_state_out, double *d_true_peak, double *d_peak)
+{
+  rsmp::TruePeakArgs a;
+  const int rc = true_peak_args(src_format, d_src, src_stride, nstreams, frames, nch, d_gain, first_frame, coefs, phases, taps, flush,
+                                d_state_in, d_state_out, d_true_peak, d_peak, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_true_peak(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_true_peak_host(int src_format, const void *src, size_t src_stride, int nstreams, size_t frames, int nch, const double *gain,
+                             unsigned long long first_frame, const double *coefs, int phases, int taps, int flush, const double *state_in,
+                             double *state_out, double *true_peak, double *peak)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::TruePeakArgs a;
+  const int rc = true_peak_args(src_format, src, src_stride, nstreams, frames, nch, gain, first_frame, coefs, phases, taps, flush, state_in,
+                                state_out, true_peak, peak, a);
+  if (rc != RR_OK) return rc;
+  if (frames) rsmp::true_peak_host(a);
+  return RR_OK;
+}
+
+// RRX_true_peak_device per track of a ragged batch (true_peak.hip).  Refusals first, as in RRX_tracks_finish_device.
+int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                const void *d_rows, size_t row_frames, const double *d_gain, const double *coefs, int phases, int taps,
+                                double *d_true_peak, double *d_peak)
+{
+  rsmp::TruePeakArgs a;
+  if (!d_tracks || !d_rows || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (!d_true_peak && !d_peak) return RR_INVPARAM;
+  const int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  a.src = d_rows;
+  a.gain = d_gain;
+  a.state_in = nullptr;
+  a.state_out = nullptr;
+  a.true_peak = d_true_peak;
+  a.peak = d_peak;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src_stride = 0;
+  a.frames = row_frames;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  a.flush = 1;
+  return rsmp::launch_true_peak(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
 // The shaped output stage of a ragged batch (finish_shaped.hip).  Refusals first, as in RRX_tracks_finish_device.

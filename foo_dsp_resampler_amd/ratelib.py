@@ -22,6 +22,7 @@ EXPECTED_SYMBOLS = [
     "RRX_lpc_extrapolate_device", "RRX_edge_geometry",
     "RRX_finish_device", "RRX_debug_finish_host",
     "RRX_finish_shaped_device", "RRX_debug_finish_shaped_host", "RRX_tracks_finish_shaped_device",
+    "RRX_true_peak_device", "RRX_debug_true_peak_host", "RRX_tracks_true_peak_device",
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
@@ -47,6 +48,22 @@ NOISE_SHAPES = {
 5-tap improved E-weighted filter and Wannamaker's 3-tap and 9-tap F-weighted filters.  They spare the ear's most sensitive band
 at 44.1 kHz only; for another rate the caller brings coefficients: wherever a name is accepted, so is any sequence of 1 to 16
 finite floats."""
+
+RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS = 8, 16
+
+
+def _bs1770():
+    p0 = (14, 90, -161, 272, -487, 1125, 7964, -838, 390, -218, 122, -68)
+    p1 = (-239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155)
+    return 4, 12, tuple(v / 8192.0 for p in (p0, p1, p1[::-1], p0[::-1]) for v in p)
+
+
+TRUE_PEAK_FILTERS = {"bs1770": _bs1770()}
+"""Oversampling filters for true_peak_device (`filter=`) as (phases, taps, phases * taps coefficients, phase-major).  "bs1770" is
+the 4 x 12 interpolator of ITU-R BS.1770-4 Annex 2, numerators over 8192: phases 2 and 3 are phases 1 and 0 reversed, the
+interleaved prototype h[4k + p] = coefs[p][k] is symmetric, and the centre tap of phase 0 is 7964 / 8192, so the true peak of a
+signal can lie under its sample peak.  Wherever a name is accepted, so is a tuple (phases, taps, coefficients) with 1..8 phases,
+1..16 taps and finite floats: the library designs no filter."""
 
 
 class RRConfig(C.Structure):
@@ -209,6 +226,12 @@ def lib():
             L.RRX_debug_finish_shaped_host.argtypes = host
             L.RRX_tracks_finish_shaped_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, sz, vp, C.c_int, u64,
                                                           vp, C.c_int, sz, vp, vp]
+        if hasattr(L, "RRX_true_peak_device"):  # (as above)
+            u64 = C.c_ulonglong
+            host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, u64, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+            L.RRX_true_peak_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_true_peak_host.argtypes = host
+            L.RRX_tracks_true_peak_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, C.c_int, C.c_int, vp, vp]
         if hasattr(L, "RRX_tracks_plan"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_track_geometry.argtypes = [P(RRConfig), sz, P(sz), P(sz), P(sz), P(sz)]
@@ -466,6 +489,89 @@ def finish_shaped_device(x, dst_format, shaping, segment=65536, gain=None, dithe
     return out, peak, clipped, new_state
 
 
+def _true_peak_filter(filter):
+    """`filter` (a name of TRUE_PEAK_FILTERS or (phases, taps, coefficients)) as (phases, taps, ctypes array of doubles)"""
+    f = TRUE_PEAK_FILTERS.get(filter) if isinstance(filter, str) else filter
+    if f is None:
+        raise ValueError("unknown true-peak filter %r (one of %s, or (phases, taps, coefficients))" % (filter, sorted(TRUE_PEAK_FILTERS)))
+    phases, taps, coefs = f
+    phases, taps, coefs = int(phases), int(taps), [float(v) for v in np.asarray(coefs, dtype=np.float64).reshape(-1)]
+    if not (1 <= phases <= RRX_TP_MAX_PHASES and 1 <= taps <= RRX_TP_MAX_TAPS and len(coefs) == phases * taps and all(np.isfinite(coefs))):
+        raise ValueError("a true-peak filter is 1..%d phases x 1..%d taps of finite coefficients, phase-major" % (RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS))
+    return phases, taps, (C.c_double * len(coefs))(*coefs)
+
+
+def _true_peak_stats(true_peak, peak, n, nch, dev):
+    """the two result tensors of a true-peak call: float64 [n, nch], allocated (zeroed) when not passed"""
+    import torch
+    stats = []
+    for t, name in ((true_peak, "true_peak"), (peak, "peak")):
+        if t is None:
+            t = torch.zeros((n, nch), dtype=torch.float64, device=dev)
+        elif t.dtype != torch.float64 or tuple(t.shape) != (n, nch) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous float64 tensor [%d, %d] on %s" % (name, n, nch, dev))
+        stats.append(t)
+    return stats
+
+
+def true_peak_device(x, gain=None, first_frame=0, filter="bs1770", flush=True, state=None, true_peak=None, peak=None, stream=None):
+    """True peak and sample peak on the device (RRX_true_peak_device): per (stream, channel), the peak of the gained frames
+    oversampled by the polyphase `filter` -- a name of TRUE_PEAK_FILTERS ("bs1770": 4x, ITU-R BS.1770-4 Annex 2) or (phases, taps,
+    coefficients) -- and the peak of the gained samples themselves, which is finish_device's measure-only peak bit for bit.  The
+    gain that normalises a track comes from max(true_peak, peak): either can be the larger one.
+
+    `x`, `gain` and `stream` are finish_device's.  `flush`: evaluate the filter's tail behind the last frame too (the last chunk
+    of a track, or a whole track).  `state`: None, or the float64 [nstreams, nch, 16] tensor the call before returned; a call with
+    first_frame > 0 needs it, and contiguous ascending calls that hand it on, with flush on the last one only, leave the bits of
+    one call.  `true_peak` / `peak` (float64 [nstreams, nch]) are allocated (zeroed) when not passed and accumulated into
+    otherwise.  Returns (true_peak, peak, state_out): `state_out` is a NEW tensor, never the one passed in.  The call only
+    enqueues."""
+    import torch
+    shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    dt = str(x.dtype)
+    if not (dt.endswith("float32") or dt.endswith("float64")):
+        raise TypeError("%s buffer: the true-peak pass reads float32 or float64 frames" % (x.dtype,))
+    if not x.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    phases, taps, coefs = _true_peak_filter(filter)
+    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
+    first_frame = int(first_frame)
+    if not (0 <= first_frame and first_frame + frames < 1 << 64):
+        raise ValueError("first_frame + frames must fit 64 unsigned bits")
+    if state is None and first_frame:
+        raise ValueError("a call that does not begin the stream needs the state of the call before it")
+    if not getattr(x, "is_cuda", False):
+        raise TypeError("the true-peak pass works on device tensors: the frames must be in HBM")
+    dev = x.device
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((nstreams,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (nstreams,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (nstreams, dev))
+    if state is not None:
+        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, RRX_TP_MAX_TAPS) or state.device != dev or not state.is_contiguous():
+            raise TypeError("state must be a contiguous float64 tensor [%d, %d, %d] on %s" % (nstreams, nch, RRX_TP_MAX_TAPS, dev))
+    true_peak, peak = _true_peak_stats(true_peak, peak, nstreams, nch, dev)
+    # frames == 0 touches nothing, the state included: the state handed on is then the one that came in
+    if frames or state is None or not first_frame:
+        new_state = torch.zeros((nstreams, nch, RRX_TP_MAX_TAPS), dtype=torch.float64, device=dev)
+    else:
+        new_state = state.clone()
+    if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return true_peak, peak, new_state
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_true_peak_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+                                      RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames, nstreams,
+                                      frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, first_frame,
+                                      C.cast(coefs, C.c_void_p), phases, taps, 1 if flush else 0,
+                                      C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(new_state.data_ptr()),
+                                      C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())), "RRX_true_peak_device")
+    return true_peak, peak, new_state
+
+
 class TracksPlan:
     """RRX_tracks_plan's answer: `table` (a ctypes array of RRXTrack, one per track), `row_frames` (length of the rows the handle
     is pushed from), `out_row_cap` (pitch of its output rows), `src_total` / `dst_total` (frames of the packed source /
@@ -702,6 +808,41 @@ def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=F
                                           C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
                                           C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_device")
     return out, peak, clipped
+
+
+def tracks_true_peak_device(rows, table, gain=None, filter="bs1770", true_peak=None, peak=None, stream=None):
+    """true_peak_device per track of a ragged batch, in one call (RRX_tracks_true_peak_device): `rows` and `table` as in
+    tracks_finish_device; track t's frames [out_first, out_first + out_frames) of row t are measured as one whole track -- from
+    +0.0 at its first output frame (the row in front of it is not history: the written file does not hold it), flushed behind its
+    last -- under `gain` (None, a float, or a float64 device tensor [ntracks]).  `filter` is true_peak_device's.  `true_peak` and
+    `peak` (float64 [ntracks, nch]) are allocated (zeroed) when not passed and accumulated into otherwise.  Returns (true_peak,
+    peak).  The call only enqueues."""
+    import torch
+    dt = str(rows.dtype)
+    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
+        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
+    ntracks, row_frames, nch = rows.shape
+    _tracks_table(table, ntracks)
+    dev = rows.device
+    if table.device != dev:
+        raise TypeError("the table must be on %s" % (dev,))
+    phases, taps, coefs = _true_peak_filter(filter)
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((ntracks,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (ntracks,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (ntracks, dev))
+    true_peak, peak = _true_peak_stats(true_peak, peak, ntracks, nch, dev)
+    if not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return true_peak, peak
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_true_peak_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
+                                             nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
+                                             row_frames, C.c_void_p(gain.data_ptr()) if gain is not None else None,
+                                             C.cast(coefs, C.c_void_p), phases, taps,
+                                             C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())), "RRX_tracks_true_peak_device")
+    return true_peak, peak
 
 
 def tracks_finish_shaped_device(rows, table, dst_format, dst_total, shaping, segment=65536, gain=None, dither=True, seed=0, out=None, peak=None,
@@ -1465,6 +1606,33 @@ class Resampler:
             pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
+
+    def convert_tracks_to_pcm_normalized(self, tracks, dst_format, target_dbtp=-1.0, shaping=None, segment=65536, dither=False, seed=0):
+        """convert_tracks_to_pcm_device with every track normalised to a TRUE peak of `target_dbtp` dBTP: the rows are converted
+        once (as in convert_tracks_device), measured with tracks_true_peak_device (the "bs1770" filter), and per track
+        m = max over its channels of max(true peak, sample peak) gives the gain 10 ** (target_dbtp / 20) / m -- or 1.0 where m is 0
+        or not finite (a silent track stays silent) -- computed on the device, without a host synchronisation; then the rows are
+        finished under that gain with tracks_finish_device, or tracks_finish_shaped_device when `shaping` is given (`segment` as
+        there).  Returns (list of per-track views of the packed PCM, peak [ntracks, nch], clipped [ntracks, nch], gain [ntracks],
+        true_peak [ntracks, nch]); `peak` is the sample peak AFTER the gain, as the output stage reports it, `true_peak` the
+        measured one BEFORE it.  Dither and shaping add their noise after the gain, so near 0 dBTP `clipped` can be nonzero with
+        them; without them, at the default target, it is zero."""
+        import torch
+        tracks = list(tracks)
+        plan, table, out = self._convert_tracks_rows(tracks)
+        n = len(tracks)
+        cur = torch.cuda.current_stream(out.device)
+        true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
+        m = torch.maximum(true_peak, sample_peak).amax(1)
+        target = 10.0 ** (float(target_dbtp) / 20.0)
+        gain = torch.where(torch.isfinite(m) & (m > 0), torch.full_like(m, target) / m, torch.ones_like(m)).contiguous()  # (one division, one rounding)
+        if shaping is not None:
+            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=gain, dither=dither,
+                                                             seed=seed, stream=cur)
+        else:
+            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
+        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
+        return views, peak[:n], clipped[:n], gain[:n], true_peak[:n]
 
     def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut

@@ -325,6 +325,55 @@ int RRX_debug_finish_shaped_host(int src_format, const void *src, size_t src_str
                                  unsigned long long first_frame, const double *coefs, int order, size_t segment,
                                  const double *state_in, double *state_out, double *peak, unsigned long long *clipped);
 
+/* True peak: the peak of the gained frames oversampled by a polyphase filter (ITU-R BS.1770-4 Annex 2 with a 4 x 12 filter, in
+ * dBTP once the caller takes 20 log10), beside the sample peak, per (stream, channel), in one pass over device-resident frames.  A
+ * track normalised to a SAMPLE peak of 0 dBFS can overshoot between the samples by several dB; the gain that normalises a track
+ * comes from max(true peak, sample peak) -- both, because a filter whose centre tap is below 1 can put the true peak under the
+ * sample peak.  The call needs no handle and writes no sample.
+ *
+ * The arithmetic is part of this ABI.  Everything is fp64 and every operation is rounded on its own (no fused multiply-add).  The
+ * filter has `phases` (1..RRX_TP_MAX_PHASES) x `taps` (1..RRX_TP_MAX_TAPS) coefficients, phase-major.  For stream s, channel ch
+ * and frame i of the call:  F = first_frame + i,  c = s * nch + ch.
+ *   gain        g[F] = (double)x * d_gain[s]  (d_gain NULL: g = x);  a = fabs(g[F])                     -- RRX_finish_device's
+ *   history     g[F-k], k = 1..taps-1, are the channel's previous gained samples; frames before absolute frame 0 are +0.0, frames
+ *               before the call's first frame come from d_state_in
+ *   phases      for p in 0..phases-1:  acc = +0.0;  for k = taps-1 down to 0:  acc = acc + coefs[p*taps + k] * g[F-k];   y_p = acc
+ *               (a descending sum: the newest sample is added last)
+ *   true peak   tp[F] = max over p of fabs(y_p), as an unsigned 64-bit maximum on the bit patterns (a NaN lies above +inf and stays)
+ * Results: d_true_peak[c] = max(what it holds, every tp[F]) and d_peak[c] = max(what it holds, every a), both by the unsigned
+ * 64-bit atomic maximum of RRX_finish_device, [nstreams * nch] doubles each on the device.  Either may be NULL, not both.  Both
+ * ACCUMULATE: the caller zeroes them, and chunked calls add up.  On the same frames and gain d_peak is RRX_finish_device's
+ * measure-only peak, bit for bit.
+ *   coefs: a HOST pointer to phases * taps finite doubles, copied into the launch arguments as they are.  The call designs no
+ *   filter; the BS.1770 table is in the Python binding (TRUE_PEAK_FILTERS).  The coefficients are never padded with zeros to a
+ *   fixed size: 0 * inf is a NaN, so a padded sum would differ for non-finite samples.
+ *   flush != 0: taps - 1 further frames of g = +0.0 are evaluated behind the call's last frame -- the filter's tail, where the
+ *   intersample peak of a track's last samples lies.  They enter d_true_peak only, neither d_peak nor the state.
+ *   State: [nstreams * nch][RRX_TP_MAX_TAPS] doubles on the device; entry j of a channel is the gained sample j + 1 frames before
+ *   the next frame to come, entries at taps - 1 and beyond are 0.  d_state_in NULL needs first_frame == 0, else RR_INVPARAM;
+ *   d_state_in not NULL is read only when first_frame > 0.  d_state_out not NULL receives, for every channel, the history after
+ *   the call's last real frame; with frames < taps - 1 it mixes new and old entries.  The two must not overlap (RR_INVPARAM, equal
+ *   pointers included), for the reason RRX_finish_shaped_device gives.  Contiguous ascending calls that hand the state on, with
+ *   flush on the last one only, leave the bits of one call with flush, for any cut positions.
+ *   Everything else -- src_format (RRX_FMT_FLOAT or RRX_FMT_DOUBLE), layouts and strides, the alignment of one sample, device and
+ *   hip_stream with the stream-ordering contract, "only enqueues: no allocation, no host synchronisation" -- is
+ *   RRX_finish_device's.
+ * Returns RR_INVPARAM, before any device is touched, for every size, stride and overflow RRX_finish_device refuses, and further
+ * for coefs NULL, phases or taps out of range, a non-finite coefficient, d_true_peak and d_peak both NULL, and the state rules
+ * above; RR_EXTUNINIT before init_ratelib; RR_INTERNAL for a failed launch.  frames == 0 is RR_OK and touches nothing, even with
+ * flush. */
+#define RRX_TP_MAX_PHASES 8
+#define RRX_TP_MAX_TAPS 16
+int RRX_true_peak_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int nstreams,
+                         size_t frames, int nch, const double *d_gain, unsigned long long first_frame,
+                         const double *coefs, int phases, int taps, int flush,
+                         const double *d_state_in, double *d_state_out, double *d_true_peak, double *d_peak);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: RRX_true_peak_device on HOST
+ * pointers, as one serial loop per channel over the very per-frame function the kernels call.  Same refusals, same results. */
+int RRX_debug_true_peak_host(int src_format, const void *src, size_t src_stride, int nstreams, size_t frames, int nch,
+                             const double *gain, unsigned long long first_frame, const double *coefs, int phases, int taps, int flush,
+                             const double *state_in, double *state_out, double *true_peak, double *peak);
+
 /* Host-only (no GPU needed): the plugin's edge geometry for a rate pair (dsp_rate::reinit, foo_dsp_rate.cpp:96-101).
  * *n_add / *n_drop = samples_len(in_rate, out_rate, 20, 8192) of util.h:38-48: frames to extrapolate at each end of the input
  * and frames to cut from each end of the output, the same duration at the two rates (n_add * out_rate == n_drop * in_rate);
@@ -467,6 +516,20 @@ int RRX_tracks_finish_shaped_device(int device, void *hip_stream, const RRX_trac
                                     size_t dst_total, const double *d_gain, int dither, unsigned long long seed,
                                     const double *coefs, int order, size_t segment,
                                     double *d_peak, unsigned long long *d_clipped);
+
+/* RRX_true_peak_device per track in one call: how a caller finds the gain that normalises each track of a ragged batch to a true
+ * peak.  Tables, rows and their clamping are RRX_tracks_finish_device's in its measure-only form: track t's slice is frames
+ * [out_first, out_first + out_frames) of row t of d_rows ([ntracks][row_frames][nch], float32 or float64), clamped to the row.
+ * Track t gets the results of a one-stream RRX_true_peak_device call on that slice with first_frame = 0, no state, flush = 1 and
+ * d_gain[t] (d_gain NULL: unity), into d_true_peak / d_peak [ntracks * nch], accumulated as there.  The frames of the row in front
+ * of the slice -- the resampled image of the LPC extension -- are NOT history: the written file does not hold them, so the filter
+ * starts from +0.0 at the track's first output frame.  A wrong table gives wrong numbers, never an access outside the rows.
+ * Refusals: RR_INVPARAM, before any device is touched, for a NULL table or source, ntracks < 1, nch < 1, an unknown source format,
+ * both result pointers NULL, the filter refusals of RRX_true_peak_device, ntracks * row_frames * nch of 2^60 samples or more, or
+ * device < -1; the rest as there.  row_frames == 0 is RR_OK and does nothing.  A form by windows is not offered. */
+int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                int src_format, const void *d_rows, size_t row_frames, const double *d_gain,
+                                const double *coefs, int phases, int taps, double *d_true_peak, double *d_peak);
 
 /* Windows: the two passes above on frames [win_first, win_first + win_frames) of the rows, so that a ragged batch runs in memory
  * proportional to ntracks * window instead of ntracks * longest track.  The rows themselves are VIRTUAL: row_frames is their
