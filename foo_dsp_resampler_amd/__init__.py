@@ -10,7 +10,9 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       tracks_stage_device, tracks_finish_device, tracks_stage_window_device, tracks_finish_window_device,
                       TracksBatches, tracks_batches, plan_cache_clear, plan_cache_stats, RR_BEST, RR_NORM, RRX_FMT_FLOAT, RRX_FMT_DOUBLE, RRX_FMT_S16, RRX_FMT_S32, RRX_FMT_S24_3, EXPECTED_SYMBOLS,
                       finish_shaped_device, tracks_finish_shaped_device, tracks_finish_shaped_window_device, NOISE_SHAPES, RRX_SHAPE_MAX_ORDER,
-                      true_peak_device, tracks_true_peak_device, TRUE_PEAK_FILTERS, RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS)
+                      true_peak_device, tracks_true_peak_device, TRUE_PEAK_FILTERS, RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS,
+                      k_weighting, K_WEIGHTING_48K, loudness_device, tracks_loudness_device, loudness_gate, loudness_gate_device, integrated_lufs,
+                      loudness_normalizing_gain)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
@@ -18,4 +20,6 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "lib_path",
            "available_symbols", "RR_BEST", "RR_NORM", "RRX_FMT_FLOAT", "RRX_FMT_DOUBLE", "RRX_FMT_S16", "RRX_FMT_S32", "RRX_FMT_S24_3",
            "EXPECTED_SYMBOLS", "finish_shaped_device", "tracks_finish_shaped_device", "tracks_finish_shaped_window_device", "NOISE_SHAPES", "RRX_SHAPE_MAX_ORDER",
-           "true_peak_device", "tracks_true_peak_device", "TRUE_PEAK_FILTERS", "RRX_TP_MAX_PHASES", "RRX_TP_MAX_TAPS"]
+           "true_peak_device", "tracks_true_peak_device", "TRUE_PEAK_FILTERS", "RRX_TP_MAX_PHASES", "RRX_TP_MAX_TAPS",
+           "k_weighting", "K_WEIGHTING_48K", "loudness_device", "tracks_loudness_device", "loudness_gate", "loudness_gate_device", "integrated_lufs",
+           "loudness_normalizing_gain"]

@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "finish.hpp"
 #include "finish_shaped.hpp"
+#include "loudness.hpp"
 #include "lpc.hpp"
 #include "tracks.hpp"
 #include "true_peak.hpp"
@@ -1090,6 +1091,194 @@ int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d
   a.src_double = src_format == RRX_FMT_DOUBLE;
   a.flush = 1;
   return rsmp::launch_true_peak(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+namespace {
+
+// the two biquads of the loudness calls and M = A^hop: RR_INVPARAM for a NULL pointer, a non-finite coefficient or hop == 0
+int loudness_filter(const double *coefs, size_t hop, rsmp::LoudnessArgs &a)
+{
+  if (!coefs || !hop) return RR_INVPARAM;
+  for (int k = 0; k < 10; ++k) {
+    a.c[k] = coefs[k];
+    if (!std::isfinite(a.c[k])) return RR_INVPARAM;
+  }
+  rsmp::loudness_power(a.c, hop, a.m);
+  return RR_OK;
+}
+
+// RRX_loudness_device / RRX_debug_loudness_host: everything that can be refused from the arguments alone
+int loudness_args(int src_format, const void *src, size_t src_stride, int nstreams, size_t frames, int nch, const double *gain,
+                  unsigned long long first_frame, const double *coefs, size_t hop, const double *state_in, double *state_out, double *energy,
+                  size_t energy_stride, double *work, size_t work_doubles, rsmp::LoudnessArgs &a)
+{
+  if (!energy) return RR_INVPARAM;
+  int rc = loudness_filter(coefs, hop, a);
+  if (rc != RR_OK) return rc;
+  rsmp::FinishArgs f; // the sizes, strides and overflow rules are RRX_finish_device's, measuring only
+  rc = finish_args(src_format, src, src_stride, 0, nullptr, 0, nstreams, frames, nch, gain, 0, 0, first_frame, energy, nullptr, f);
+  if (rc != RR_OK) return rc;
+  if (first_frame % hop) return RR_INVPARAM;
+  if (!state_in && first_frame) return RR_INVPARAM; // a call that does not begin the stream needs the state in front of it
+  if (state_in && state_out) {                      // [nstreams * nch][4] doubles each (finish_shaped_args)
+    const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
+    const uintptr_t bytes = uintptr_t(nstreams) * uintptr_t(nch) * 4 * sizeof(double);
+    if (x < y ? y - x < bytes : x - y < bytes) return RR_INVPARAM;
+  }
+  const unsigned long long n = frames / hop, first_hop = first_frame / hop;
+  if (first_hop + n > energy_stride) return RR_INVPARAM;                            // (first_frame + frames does not wrap: nor does this)
+  if (energy_stride > (~size_t(0) >> 4) / size_t(nch) / size_t(nstreams)) return RR_INVPARAM; // no buffer has 2^60 doubles
+  const unsigned long long need = rsmp::loudness_work_doubles(nstreams, nch, frames, hop);   // (< 2^62: nstreams * frames * nch < 2^60)
+  if (work_doubles < need || (need && !work)) return RR_INVPARAM;
+  a.src = f.src;
+  a.gain = gain;
+  a.state_in = first_frame ? state_in : nullptr; // S_0 = +0.0, whatever the buffer holds
+  a.state_out = state_out;
+  a.energy = energy;
+  a.work = work;
+  a.tracks = nullptr;
+  a.hops_out = nullptr;
+  a.src_stride = f.src_stride;
+  a.frames = frames;
+  a.hop = hop;
+  a.max_hops = n;
+  a.first_hop = first_hop;
+  a.energy_stride = energy_stride;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  a.src_double = f.src_double;
+  return RR_OK;
+}
+
+// RRX_loudness_gate_device / RRX_debug_loudness_gate_host
+int loudness_gate_args(const double *energy, size_t energy_stride, int nstreams, int nch, size_t nhops, const unsigned long long *hops,
+                       const double *weights, size_t hop, double abs_threshold, double rel_factor, double *result, rsmp::LoudnessGateArgs &a)
+{
+  if (!energy || !result || nstreams < 1 || nch < 1 || !hop || nhops > energy_stride) return RR_INVPARAM;
+  if (std::isnan(abs_threshold) || std::isnan(rel_factor)) return RR_INVPARAM;
+  if (energy_stride > (~size_t(0) >> 4) / size_t(nch) / size_t(nstreams)) return RR_INVPARAM; // no buffer has 2^60 doubles
+  a.energy = energy;
+  a.hops = hops;
+  a.weights = weights;
+  a.result = result;
+  a.energy_stride = energy_stride;
+  a.nhops = nhops;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  a.inv = 1.0 / (4.0 * (double)hop);
+  a.abs_threshold = abs_threshold;
+  a.rel_factor = rel_factor;
+  return RR_OK;
+}
+
+} // namespace
+
+size_t RRX_loudness_work_doubles(int nstreams, int nch, size_t frames, size_t hop)
+{
+  if (nstreams < 1 || nch < 1 || !hop) return 0;
+  return size_t(rsmp::loudness_work_doubles(nstreams, nch, frames, hop));
+}
+
+// K-weighted hop energies of device-resident frames (loudness.hip).  Refusals first, as in RRX_finish_device.
+int RRX_loudness_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int nstreams, size_t frames,
+                        int nch, const double *d_gain, unsigned long long first_frame, const double *coefs, size_t hop,
+                        const double *d_state_in, double *d_state_out, double *d_energy, size_t energy_stride, double *d_work,
+                        size_t work_doubles)
+{
+  rsmp::LoudnessArgs a;
+  const int rc = loudness_args(src_format, d_src, src_stride, nstreams, frames, nch, d_gain, first_frame, coefs, hop, d_state_in, d_state_out,
+                               d_energy, energy_stride, d_work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_loudness_host(int src_format, const void *src, size_t src_stride, int nstreams, size_t frames, int nch, const double *gain,
+                            unsigned long long first_frame, const double *coefs, size_t hop, const double *state_in, double *state_out,
+                            double *energy, size_t energy_stride, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessArgs a;
+  const int rc = loudness_args(src_format, src, src_stride, nstreams, frames, nch, gain, first_frame, coefs, hop, state_in, state_out, energy,
+                               energy_stride, work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (frames) rsmp::loudness_host(a);
+  return RR_OK;
+}
+
+// RRX_loudness_device per track of a ragged batch (loudness.hip).  Refusals first, as in RRX_tracks_true_peak_device.
+int RRX_tracks_loudness_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                               const void *d_rows, size_t row_frames, const double *d_gain, const double *coefs, size_t hop, double *d_energy,
+                               size_t energy_stride, unsigned long long *d_hops, double *d_work, size_t work_doubles)
+{
+  rsmp::LoudnessArgs a;
+  if (!d_tracks || !d_rows || ntracks < 1 || nch < 1 || !d_energy || !d_hops) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  const int rc = loudness_filter(coefs, hop, a);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks) || energy_stride > most / size_t(ntracks)) return RR_INVPARAM;
+  const unsigned long long need = rsmp::loudness_work_doubles(ntracks, nch, row_frames, hop);
+  if (work_doubles < need || (need && !d_work)) return RR_INVPARAM;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  a.src = d_rows;
+  a.gain = d_gain;
+  a.state_in = nullptr;
+  a.state_out = nullptr;
+  a.energy = d_energy;
+  a.work = d_work;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.hops_out = d_hops;
+  a.src_stride = 0;
+  a.frames = row_frames;
+  a.hop = hop;
+  a.max_hops = row_frames / hop;
+  a.first_hop = 0;
+  a.energy_stride = energy_stride;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  return rsmp::launch_loudness(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// The two-stage gate over hop energies (loudness.hip).  Refusals first, as in RRX_finish_device.
+int RRX_loudness_gate_device(int device, void *hip_stream, const double *d_energy, size_t energy_stride, int nstreams, int nch, size_t nhops,
+                             const unsigned long long *d_hops, const double *d_weights, size_t hop, double abs_threshold, double rel_factor,
+                             double *d_result)
+{
+  rsmp::LoudnessGateArgs a;
+  const int rc = loudness_gate_args(d_energy, energy_stride, nstreams, nch, nhops, d_hops, d_weights, hop, abs_threshold, rel_factor, d_result, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness_gate(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_loudness_gate_host(const double *energy, size_t energy_stride, int nstreams, int nch, size_t nhops, const unsigned long long *hops,
+                                 const double *weights, size_t hop, double abs_threshold, double rel_factor, double *result)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessGateArgs a;
+  const int rc = loudness_gate_args(energy, energy_stride, nstreams, nch, nhops, hops, weights, hop, abs_threshold, rel_factor, result, a);
+  if (rc != RR_OK) return rc;
+  rsmp::loudness_gate_host(a);
+  return RR_OK;
 }
 
 // The shaped output stage of a ragged batch (finish_shaped.hip).  Refusals first, as in RRX_tracks_finish_device.

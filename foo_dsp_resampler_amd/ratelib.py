@@ -23,6 +23,8 @@ EXPECTED_SYMBOLS = [
     "RRX_finish_device", "RRX_debug_finish_host",
     "RRX_finish_shaped_device", "RRX_debug_finish_shaped_host", "RRX_tracks_finish_shaped_device",
     "RRX_true_peak_device", "RRX_debug_true_peak_host", "RRX_tracks_true_peak_device",
+    "RRX_loudness_device", "RRX_loudness_work_doubles", "RRX_debug_loudness_host", "RRX_tracks_loudness_device",
+    "RRX_loudness_gate_device", "RRX_debug_loudness_gate_host",
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
@@ -232,6 +234,17 @@ def lib():
             L.RRX_true_peak_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_true_peak_host.argtypes = host
             L.RRX_tracks_true_peak_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, C.c_int, C.c_int, vp, vp]
+        if hasattr(L, "RRX_loudness_device"):  # (as above)
+            u64 = C.c_ulonglong
+            host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, u64, vp, sz, vp, vp, vp, sz, vp, sz]
+            L.RRX_loudness_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_loudness_host.argtypes = host
+            L.RRX_loudness_work_doubles.argtypes = [C.c_int, C.c_int, sz, sz]
+            L.RRX_loudness_work_doubles.restype = sz
+            L.RRX_tracks_loudness_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz]
+            host = [vp, sz, C.c_int, C.c_int, sz, vp, vp, sz, C.c_double, C.c_double, vp]
+            L.RRX_loudness_gate_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_loudness_gate_host.argtypes = host
         if hasattr(L, "RRX_tracks_plan"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_track_geometry.argtypes = [P(RRConfig), sz, P(sz), P(sz), P(sz), P(sz)]
@@ -843,6 +856,232 @@ def tracks_true_peak_device(rows, table, gain=None, filter="bs1770", true_peak=N
                                              C.cast(coefs, C.c_void_p), phases, taps,
                                              C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())), "RRX_tracks_true_peak_device")
     return true_peak, peak
+
+
+K_WEIGHTING_48K = (1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,
+                   1.0, -2.0, 1.0, -1.99004745483398, 0.99007225036621)
+"""The K-weighting of ITU-R BS.1770-4 at 48 kHz as published, in the order of RRX_loudness_device's `coefs`: b0, b1, b2, a1, a2 of
+the shelving stage, then of the high-pass."""
+
+
+def k_weighting(rate):
+    """The ten coefficients of RRX_loudness_device for a sampling rate: the analog prototype behind the BS.1770 table -- a shelf
+    (f0 1681.97 Hz, +4 dB, Q 0.7072) and a high-pass (f0 38.135 Hz, Q 0.5003, numerator 1, -2, 1 as published) -- through the
+    bilinear transform.  At 48000 it reproduces K_WEIGHTING_48K to the digits the table has."""
+    import math
+    rate = float(rate)
+    if not rate > 0:
+        raise ValueError("a sampling rate is positive")
+    k = math.tan(math.pi * 1681.974450955533 / rate)
+    vh = 10.0 ** (3.999843853973347 / 20.0)
+    vb = vh ** 0.4996667741545416
+    q = 0.7071752369554196
+    a0 = 1.0 + k / q + k * k
+    shelf = ((vh + vb * k / q + k * k) / a0, 2.0 * (k * k - vh) / a0, (vh - vb * k / q + k * k) / a0, 2.0 * (k * k - 1.0) / a0,
+             (1.0 - k / q + k * k) / a0)
+    k = math.tan(math.pi * 38.13547087602444 / rate)
+    q = 0.5003270373238773
+    a0 = 1.0 + k / q + k * k
+    return shelf + (1.0, -2.0, 1.0, 2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0)
+
+
+def _loudness_filter(rate, coefs, hop):
+    """(ctypes array of the ten coefficients, hop): k_weighting(rate) and rate // 10 where not given"""
+    if coefs is None:
+        if rate is None:
+            raise ValueError("give the sampling rate, or coefs and hop")
+        coefs = k_weighting(rate)
+    coefs = [float(v) for v in np.asarray(coefs, dtype=np.float64).reshape(-1)]
+    if len(coefs) != 10 or not all(np.isfinite(coefs)):
+        raise ValueError("the K-weighting is ten finite coefficients: b0, b1, b2, a1, a2 of two biquads")
+    if hop is None:
+        if rate is None:
+            raise ValueError("give the sampling rate, or coefs and hop")
+        hop = int(rate) // 10
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("a hop has at least one frame")
+    return (C.c_double * 10)(*coefs), hop
+
+
+def _loudness_gain(gain, n, dev):
+    import torch
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((n,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (n,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (n, dev))
+    return gain
+
+
+def _loudness_buffers(energy, work, n, nch, need_hops, need_work, dev):
+    """the energy tensor (float64 [n, nch, >= need_hops], allocated zeroed when not passed) and the work buffer"""
+    import torch
+    if energy is None:
+        energy = torch.zeros((n, nch, need_hops), dtype=torch.float64, device=dev)
+    elif (energy.dtype != torch.float64 or energy.dim() != 3 or tuple(energy.shape[:2]) != (n, nch) or energy.shape[2] < need_hops
+          or energy.device != dev or not energy.is_contiguous()):
+        raise TypeError("energy must be a contiguous float64 tensor [%d, %d, >= %d] on %s" % (n, nch, need_hops, dev))
+    if work is None:
+        work = torch.empty((max(need_work, 1),), dtype=torch.float64, device=dev)
+    elif work.dtype != torch.float64 or work.numel() < need_work or work.device != dev or not work.is_contiguous():
+        raise TypeError("work must be a contiguous float64 tensor of at least %d elements on %s" % (need_work, dev))
+    return energy, work
+
+
+def loudness_device(x, rate=None, gain=None, first_frame=0, state=None, energy=None, coefs=None, hop=None, work=None, stream=None):
+    """K-weighted hop energies on the device (RRX_loudness_device): for every (stream, channel) of `x` ([frames, nch] or
+    [nstreams, frames, nch], float32 or float64, contiguous, on the device) the sum of squares of the K-weighted, gained frames
+    over every whole hop of `hop` frames (default rate // 10, 100 ms), by the block decomposition the header defines.  `coefs`
+    defaults to k_weighting(rate); `gain` and `stream` are finish_device's.
+
+    `first_frame` must be a multiple of the hop; a call with first_frame > 0 needs `state`, the float64 [nstreams, nch, 4] tensor
+    the call before returned.  Frames behind the last whole hop are not measured: a chunked caller feeds them again.  `energy`
+    (float64 [nstreams, nch, >= first_frame // hop + frames // hop]) is allocated (zeroed) when not passed; the call WRITES hops
+    first_frame // hop ... of it and touches nothing else.  `work` is scratch of RRX_loudness_work_doubles doubles, allocated when
+    not passed.  Returns (energy, state_out): `state_out` is a NEW tensor.  Feed `energy` to loudness_gate_device.  The call only
+    enqueues."""
+    import torch
+    shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    dt = str(x.dtype)
+    if not (dt.endswith("float32") or dt.endswith("float64")):
+        raise TypeError("%s buffer: the loudness pass reads float32 or float64 frames" % (x.dtype,))
+    if not x.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    c, hop = _loudness_filter(rate, coefs, hop)
+    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
+    first_frame = int(first_frame)
+    if not (0 <= first_frame and first_frame + frames < 1 << 64):
+        raise ValueError("first_frame + frames must fit 64 unsigned bits")
+    if first_frame % hop:
+        raise ValueError("first_frame must be a multiple of the hop (%d)" % hop)
+    if state is None and first_frame:
+        raise ValueError("a call that does not begin the stream needs the state of the call before it")
+    if not getattr(x, "is_cuda", False):
+        raise TypeError("the loudness pass works on device tensors: the frames must be in HBM")
+    dev = x.device
+    gain = _loudness_gain(gain, nstreams, dev)
+    if state is not None:
+        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, 4) or state.device != dev or not state.is_contiguous():
+            raise TypeError("state must be a contiguous float64 tensor [%d, %d, 4] on %s" % (nstreams, nch, dev))
+    first_hop, n = first_frame // hop, frames // hop
+    need = nstreams * nch * n * 4
+    energy, work = _loudness_buffers(energy, work, nstreams, nch, first_hop + n, need, dev)
+    # frames == 0 touches nothing, the state included: the state handed on is then the one that came in
+    if frames or state is None or not first_frame:
+        new_state = torch.zeros((nstreams, nch, 4), dtype=torch.float64, device=dev)
+    else:
+        new_state = state.clone()
+    if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return energy, new_state
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_loudness_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+                                     RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames, nstreams,
+                                     frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, first_frame,
+                                     C.cast(c, C.c_void_p), hop, C.c_void_p(state.data_ptr()) if state is not None else None,
+                                     C.c_void_p(new_state.data_ptr()), C.c_void_p(energy.data_ptr()), energy.shape[2],
+                                     C.c_void_p(work.data_ptr()), work.numel()), "RRX_loudness_device")
+    return energy, new_state
+
+
+def tracks_loudness_device(rows, table, rate=None, gain=None, coefs=None, hop=None, energy=None, work=None, stream=None):
+    """loudness_device per track of a ragged batch, in one call (RRX_tracks_loudness_device): `rows` and `table` as in
+    tracks_true_peak_device; track t's frames [out_first, out_first + out_frames) of row t are measured as one whole track from
+    +0.0 under `gain` (None, a float, or a float64 device tensor [ntracks]).  Returns (energy, hops): `energy` float64 [ntracks,
+    nch, row_frames // hop] (allocated zeroed when not passed; one that is passed may hold fewer hops, and the tracks' hops are
+    clamped to it), of which track t's first hops[t] entries per channel are written, and `hops` int64 [ntracks], the whole hops of
+    every track.  Feed both to loudness_gate_device.  The call only
+    enqueues."""
+    import torch
+    dt = str(rows.dtype)
+    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
+        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
+    ntracks, row_frames, nch = rows.shape
+    _tracks_table(table, ntracks)
+    dev = rows.device
+    if table.device != dev:
+        raise TypeError("the table must be on %s" % (dev,))
+    c, hop = _loudness_filter(rate, coefs, hop)
+    gain = _loudness_gain(gain, ntracks, dev)
+    n = row_frames // hop
+    energy, work = _loudness_buffers(energy, work, ntracks, nch, n if energy is None else 0, ntracks * nch * n * 4, dev)
+    hops = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
+    if not n or not energy.shape[2]:  # (no row holds a whole hop: an empty tensor has no pointer, and there is nothing to do)
+        return energy, hops
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_loudness_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
+                                            nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
+                                            row_frames, C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(c, C.c_void_p), hop,
+                                            C.c_void_p(energy.data_ptr()), energy.shape[2],
+                                            C.c_void_p(hops.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+           "RRX_tracks_loudness_device")
+    return energy, hops
+
+
+def loudness_gate(abs_lufs=-70.0, rel_lu=-10.0):
+    """(abs_threshold, rel_factor) of RRX_loudness_gate_device for gates given in LUFS / LU: 10 ** ((abs_lufs + 0.691) / 10) and
+    10 ** (rel_lu / 10)"""
+    return 10.0 ** ((float(abs_lufs) + 0.691) / 10.0), 10.0 ** (float(rel_lu) / 10.0)
+
+
+def loudness_gate_device(energy, hop, hops=None, abs_lufs=-70.0, rel_lu=-10.0, weights=None, stream=None):
+    """The two-stage gate of BS.1770-4 on the device (RRX_loudness_gate_device) over `energy` (float64 [nstreams, nch, nhops], what
+    loudness_device / tracks_loudness_device return) for hops of `hop` frames; `hops` (int64 device tensor [nstreams], or None:
+    all of them) is the number of valid hops per stream.  `weights`: None (1.0), or per-channel weights as a sequence or a float64
+    device tensor [nch] -- BS.1770 gives 1.41 to the surround channels and 0 to the LFE.  Returns float64 [nstreams, 4]:
+    S2, N2, S1, N1 per stream; integrated_lufs turns it into LUFS.  The call only enqueues."""
+    import torch
+    if (energy.dtype != torch.float64 or energy.dim() != 3 or not getattr(energy, "is_cuda", False) or not energy.is_contiguous()):
+        raise TypeError("energy must be a contiguous float64 device tensor [nstreams, nch, nhops]")
+    nstreams, nch, nhops = energy.shape
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("a hop has at least one frame")
+    dev = energy.device
+    if hops is not None and (hops.dtype != torch.int64 or tuple(hops.shape) != (nstreams,) or hops.device != dev or not hops.is_contiguous()):
+        raise TypeError("hops must be a contiguous int64 tensor [%d] on %s" % (nstreams, dev))
+    if weights is not None and not hasattr(weights, "data_ptr"):
+        weights = torch.tensor([float(v) for v in weights], dtype=torch.float64, device=dev)
+    if weights is not None and (weights.dtype != torch.float64 or tuple(weights.shape) != (nch,) or weights.device != dev or not weights.is_contiguous()):
+        raise TypeError("weights must be %d floats, or a contiguous float64 tensor [%d] on %s" % (nch, nch, dev))
+    result = torch.zeros((nstreams, 4), dtype=torch.float64, device=dev)
+    if not nstreams or not nch or not nhops:
+        return result
+    abs_threshold, rel_factor = loudness_gate(abs_lufs, rel_lu)
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_loudness_gate_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(energy.data_ptr()), nhops,
+                                          nstreams, nch, nhops, C.c_void_p(hops.data_ptr()) if hops is not None else None,
+                                          C.c_void_p(weights.data_ptr()) if weights is not None else None, hop, abs_threshold, rel_factor,
+                                          C.c_void_p(result.data_ptr())), "RRX_loudness_gate_device")
+    return result
+
+
+def integrated_lufs(result):
+    """LUFS per stream from the gate's result [nstreams, 4] (a torch tensor, on the device or not; anything else is converted):
+    -0.691 + 10 log10(S2 / N2), and -inf where no block passed the gates (N2 == 0).  Runs where the tensor lives, without a host
+    synchronisation."""
+    import torch
+    r = result if hasattr(result, "data_ptr") else torch.as_tensor(np.asarray(result, dtype=np.float64))
+    s2, n2 = r[..., 0], r[..., 1]
+    some = n2 > 0
+    mean = s2 / torch.where(some, n2, torch.ones_like(n2))
+    return torch.where(some, -0.691 + 10.0 * torch.log10(mean), torch.full_like(mean, float("-inf")))
+
+
+def loudness_normalizing_gain(lufs, n2, m, target_lufs=-18.0, max_dbtp=-1.0):
+    """The gain of convert_tracks_to_pcm_loudness_normalized from its measurements (torch tensors [ntracks]: integrated_lufs, the
+    gate's N2, and m = the largest of true peak and sample peak): min(10 ** ((target_lufs - lufs) / 20), 10 ** (max_dbtp / 20) / m),
+    and 1.0 where N2 == 0 or m is 0 or not finite."""
+    import torch
+    ok = (n2 > 0) & torch.isfinite(m) & (m > 0)
+    by_loudness = torch.pow(10.0, (float(target_lufs) - torch.where(ok, lufs, torch.zeros_like(lufs))) / 20.0)
+    by_peak = torch.full_like(m, 10.0 ** (float(max_dbtp) / 20.0)) / torch.where(ok, m, torch.ones_like(m))
+    return torch.where(ok, torch.minimum(by_loudness, by_peak), torch.ones_like(m)).contiguous()
 
 
 def tracks_finish_shaped_device(rows, table, dst_format, dst_total, shaping, segment=65536, gain=None, dither=True, seed=0, out=None, peak=None,
@@ -1633,6 +1872,37 @@ class Resampler:
             pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n], gain[:n], true_peak[:n]
+
+    def convert_tracks_to_pcm_loudness_normalized(self, tracks, dst_format, target_lufs=-18.0, max_dbtp=-1.0, weights=None, shaping=None,
+                                                  segment=65536, dither=False, seed=0):
+        """convert_tracks_to_pcm_device with every track normalised to an integrated LOUDNESS of `target_lufs` LUFS, held under a
+        true peak of `max_dbtp` dBTP (ReplayGain 2.0, EBU R 128): the rows are converted once, measured with
+        tracks_loudness_device + loudness_gate_device (K-weighting of the output rate, hops of out_rate // 10 frames, the gates of
+        BS.1770, channel `weights` as there) and with tracks_true_peak_device, and per track, with L its loudness and m as in
+        convert_tracks_to_pcm_normalized, the gain is min(10 ** ((target_lufs - L) / 20), 10 ** (max_dbtp / 20) / m) -- or 1.0 where
+        no block passed the gates (a silent or very short track) or m is 0 or not finite -- computed on the device, without a host
+        synchronisation; then the rows are finished under that gain as in convert_tracks_to_pcm_normalized.  Returns what that
+        call returns, plus the loudness: (views, peak, clipped, gain [ntracks], true_peak [ntracks, nch], lufs [ntracks]); `lufs`
+        is the measured loudness BEFORE the gain, -inf where no block passed."""
+        import torch
+        tracks = list(tracks)
+        plan, table, out = self._convert_tracks_rows(tracks)
+        n = len(tracks)
+        cur = torch.cuda.current_stream(out.device)
+        rate = int(self.cfg.out_rate)
+        energy, hops = tracks_loudness_device(out, table, rate, stream=cur)
+        result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
+        lufs = integrated_lufs(result)
+        true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
+        m = torch.maximum(true_peak, sample_peak).amax(1)
+        gain = loudness_normalizing_gain(lufs, result[:, 1], m, target_lufs, max_dbtp)
+        if shaping is not None:
+            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=gain, dither=dither,
+                                                             seed=seed, stream=cur)
+        else:
+            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
+        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
+        return views, peak[:n], clipped[:n], gain[:n], true_peak[:n], lufs[:n]
 
     def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut

@@ -531,6 +531,106 @@ int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d
                                 int src_format, const void *d_rows, size_t row_frames, const double *d_gain,
                                 const double *coefs, int phases, int taps, double *d_true_peak, double *d_peak);
 
+/* Programme loudness (ITU-R BS.1770-4, EBU R 128): K-weighted energies of 100 ms hops per (stream, channel) of device-resident
+ * frames, from which RRX_loudness_gate_device below takes the gated mean; in LUFS once the caller takes -0.691 + 10 log10.  The
+ * call needs no handle and writes no sample.
+ *
+ * K-weighting is two biquads, an IIR recursion: a channel is one serial chain from its first frame, and restarting the state on a
+ * grid would falsify the measurement (the 38 Hz high-pass has a pole radius of 0.995 at 48 kHz).  To give the device independent
+ * chains all the same, the arithmetic that is part of this ABI is an exact BLOCK DECOMPOSITION by linear superposition, not the
+ * serial filter; it agrees with the serial filter to rounding ("Loudness").  Everything is fp64, every operation is
+ * rounded on its own, and there is no fused multiply-add.
+ *   coefs: a HOST pointer to 10 finite doubles, copied into the launch arguments: stage A is c0..c4 = b0, b1, b2, a1, a2, stage B
+ *   is c5..c9, both in transposed direct form II.  The call designs no filter (the Python binding has k_weighting(rate)).
+ *   step        per channel, with state s[0..3] and g = (double)x * d_gain[s]  (d_gain NULL: g = x), as in RRX_finish_device:
+ *                 y = c0*g + s0;   s0' = (c1*g - c3*y) + s1;   s1' = c2*g - c4*y;
+ *                 v = c5*y + s2;   s2' = (c6*y - c8*v) + s3;   s3' = c7*y - c9*v;          E = E + v*v
+ *   hop         the 100 ms piece, rate / 10 frames; any value >= 1 is accepted.  Hop k of a channel covers the absolute frames
+ *               [k*hop, (k+1)*hop).
+ *   The decomposition, with S_k the state at the start of hop k and S_0 = +0.0:
+ *     z_k       the state after running the step over hop k from an all-zero state.
+ *     A         the 4x4 matrix whose column i is one step with g = 0 from the unit state e_i, computed by the very step above.
+ *     M = A^hop computed on the host by square-and-multiply over the bits of hop from the most significant one: R = A; then for
+ *               every lower bit R = R R and, where the bit is set, R = R A.  Each entry of a product X Y is the ascending-k sum
+ *               acc = +0.0; acc = acc + X[i][k]*Y[k][j], products and sums rounded separately.
+ *     carry     S_{k+1}[i] = (((M[i][0]*S_k[0] + M[i][1]*S_k[1]) + M[i][2]*S_k[2]) + M[i][3]*S_k[3]) + z_k[i].
+ *     energy[k] the serial ascending sum E from +0.0, over hop k, of the step started from S_k.
+ *   Launches: one lane per (stream, channel, hop) computes z_k into d_work; one lane per (stream, channel) walks k ascending and
+ *   turns d_work into S_k in place; the first layout again reruns every hop from S_k and writes its energy.  M travels in the
+ *   launch arguments.  The call only enqueues -- no allocation, no host synchronisation -- hence the caller's d_work: at least
+ *   RRX_loudness_work_doubles(nstreams, nch, frames, hop) doubles on the device (nstreams * nch * (frames / hop) * 4; host only,
+ *   0 for arguments the call would refuse), whose content after the call is unspecified.
+ *   Only whole hops are processed: n = frames / hop.  The frames behind the last whole hop are not read into anything; a chunked
+ *   caller feeds them again.  first_frame % hop != 0 is RR_INVPARAM.
+ *   State: [nstreams * nch][4] doubles on the device, s[0..3] of every channel.  d_state_in is required when first_frame > 0 and
+ *   is not read at first_frame == 0.  d_state_out, when not NULL, receives S after the call's last whole hop; with n == 0 it
+ *   receives a copy of d_state_in, or zeros when that is NULL or not read.  The two must not overlap (RR_INVPARAM, equal pointers
+ *   included).  Contiguous calls cut at hop multiples that hand the state on leave the bits of one call.
+ *   d_energy: hop first_frame / hop + j of channel c = s * nch + ch is WRITTEN, not accumulated, at
+ *   d_energy[c * energy_stride + first_frame / hop + j], j < n.  Nothing else in d_energy is touched.
+ *   A NaN or +-inf sample poisons its channel's state and with it every later energy of that channel (the gate then skips the
+ *   blocks they enter); it never faults, and the other channels are exact.
+ *   Everything else -- src_format (RRX_FMT_FLOAT or RRX_FMT_DOUBLE; integer sources are not offered), layouts and strides, the
+ *   alignment of one sample, device and hip_stream with the stream-ordering contract -- is RRX_finish_device's.
+ * Returns RR_INVPARAM, before any device is touched, for every source, stride, size and overflow RRX_finish_device refuses, and
+ * further for coefs NULL, a non-finite coefficient, hop == 0, d_energy NULL, first_frame / hop + n > energy_stride, nstreams * nch *
+ * energy_stride of 2^60 doubles or more, work_doubles below RRX_loudness_work_doubles(...) (or d_work NULL where that is not 0),
+ * and the state rules above; RR_EXTUNINIT before init_ratelib; RR_INTERNAL for a failed launch.  frames == 0 is RR_OK and touches
+ * nothing, the state included. */
+int RRX_loudness_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int nstreams,
+                        size_t frames, int nch, const double *d_gain, unsigned long long first_frame,
+                        const double *coefs, size_t hop, const double *d_state_in, double *d_state_out,
+                        double *d_energy, size_t energy_stride, double *d_work, size_t work_doubles);
+size_t RRX_loudness_work_doubles(int nstreams, int nch, size_t frames, size_t hop);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: RRX_loudness_device on HOST
+ * pointers, as serial loops over the very step, carry and matrix functions the kernels use.  Same refusals, same results. */
+int RRX_debug_loudness_host(int src_format, const void *src, size_t src_stride, int nstreams, size_t frames, int nch,
+                            const double *gain, unsigned long long first_frame, const double *coefs, size_t hop,
+                            const double *state_in, double *state_out, double *energy, size_t energy_stride,
+                            double *work, size_t work_doubles);
+
+/* RRX_loudness_device per track of a ragged batch in one call.  Tables, rows and their clamping are RRX_tracks_true_peak_device's:
+ * track t's slice is frames [out_first, out_first + out_frames) of row t of d_rows ([ntracks][row_frames][nch], float32 or
+ * float64), clamped to the row.  Track t is measured as a one-stream RRX_loudness_device call on that slice with first_frame = 0,
+ * no state and d_gain[t] (d_gain NULL: unity): its hops go to d_energy[(t * nch + ch) * energy_stride + j], and d_hops[t]
+ * (unsigned 64-bit, [ntracks], on the device, WRITTEN) is their number, the clamped out_frames / hop, itself clamped to
+ * energy_stride.  Energies at index d_hops[t] and beyond are left untouched.  The row in front of the slice is not history.
+ * d_work: at least RRX_loudness_work_doubles(ntracks, nch, row_frames, hop) doubles.  A wrong table gives wrong numbers, never an
+ * access outside the rows, d_energy or d_work.
+ * Refusals: RR_INVPARAM, before any device is touched, for a NULL table, source, d_energy or d_hops, ntracks < 1, nch < 1, an
+ * unknown source format, the filter and work refusals of RRX_loudness_device, ntracks * row_frames * nch or ntracks * nch *
+ * energy_stride of 2^60 or more, or device < -1; the rest as there.  row_frames == 0 is RR_OK and does nothing.  A form by windows
+ * is not offered. */
+int RRX_tracks_loudness_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                               const void *d_rows, size_t row_frames, const double *d_gain, const double *coefs, size_t hop,
+                               double *d_energy, size_t energy_stride, unsigned long long *d_hops,
+                               double *d_work, size_t work_doubles);
+
+/* The two-stage gate of BS.1770-4 over the hop energies of RRX_loudness_device / RRX_tracks_loudness_device: 400 ms blocks of
+ * four hops, overlapping by 75 %.  The arithmetic is part of this ABI (fp64, every operation rounded on its own).  Stream s has
+ * n = nhops hops, or min(d_hops[s], nhops) when d_hops (device, [nstreams]) is not NULL; its channel ch has its hops at
+ * e = d_energy + (s * nch + ch) * energy_stride.  Block j runs over [0, n - 3); nothing passes if n < 4.
+ *   per channel   q = ((e[j] + e[j+1]) + e[j+2]) + e[j+3]
+ *   block         acc = +0.0, then ascending channels acc = acc + w[ch]*q (d_weights NULL: acc = acc + q);  z_j = acc * inv,
+ *                 inv = 1.0 / (4.0 * (double)hop), computed once on the host
+ *   pass A        j ascending and serial, over the blocks with z_j > abs_threshold: S1 (sum) and N1 (count)
+ *   threshold     T = rel_factor * (S1 / N1), the division correctly rounded
+ *   pass B        S2 and N2 over the blocks with z_j > abs_threshold && z_j > T
+ *   d_result[s] = {S2, (double)N2, S1, (double)N1}, [nstreams][4] doubles on the device, written.
+ * A NaN z_j fails every comparison and is skipped.  The caller takes -0.691 + 10 log10(S2 / N2); BS.1770's gates are
+ * abs_threshold = 10^((-70 + 0.691) / 10) and rel_factor = 10^(-10 / 10).  No libm runs on the device.
+ * Returns RR_INVPARAM, before any device is touched, for d_energy or d_result NULL, nstreams < 1, nch < 1, hop == 0,
+ * nhops > energy_stride, nstreams * nch * energy_stride of 2^60 or more, a NaN threshold or factor, or device < -1; the rest as
+ * RRX_finish_device.  The call only enqueues. */
+int RRX_loudness_gate_device(int device, void *hip_stream, const double *d_energy, size_t energy_stride, int nstreams, int nch,
+                             size_t nhops, const unsigned long long *d_hops, const double *d_weights, size_t hop,
+                             double abs_threshold, double rel_factor, double *d_result);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the gate on HOST pointers, as a
+ * serial loop over the very block function the kernel calls. */
+int RRX_debug_loudness_gate_host(const double *energy, size_t energy_stride, int nstreams, int nch, size_t nhops,
+                                 const unsigned long long *hops, const double *weights, size_t hop,
+                                 double abs_threshold, double rel_factor, double *result);
+
 /* Windows: the two passes above on frames [win_first, win_first + win_frames) of the rows, so that a ragged batch runs in memory
  * proportional to ntracks * window instead of ntracks * longest track.  The rows themselves are VIRTUAL: row_frames is their
  * length, and no buffer of that size exists.  A handle's output does not depend on how its input is cut into pushes, and dither,
