@@ -6,6 +6,7 @@
 #include "finish.hpp"
 #include "finish_shaped.hpp"
 #include "loudness.hpp"
+#include "loudness_stats.hpp"
 #include "lpc.hpp"
 #include "tracks.hpp"
 #include "true_peak.hpp"
@@ -1278,6 +1279,159 @@ int RRX_debug_loudness_gate_host(const double *energy, size_t energy_stride, int
   const int rc = loudness_gate_args(energy, energy_stride, nstreams, nch, nhops, hops, weights, hop, abs_threshold, rel_factor, result, a);
   if (rc != RR_OK) return rc;
   rsmp::loudness_gate_host(a);
+  return RR_OK;
+}
+
+namespace {
+
+// RRX_loudness_blocks_device / RRX_debug_loudness_blocks_host: the gate's refusals and those of the block geometry
+int loudness_blocks_args(const double *energy, size_t energy_stride, int nstreams, int nch, size_t nhops, const unsigned long long *hops,
+                         const double *weights, size_t hop, size_t block_hops, size_t step_hops, double *blocks, size_t blocks_stride,
+                         unsigned long long *nblocks, double *max, rsmp::LoudnessBlocksArgs &a)
+{
+  if (!energy || nstreams < 1 || nch < 1 || !hop || nhops > energy_stride) return RR_INVPARAM;
+  if (energy_stride > (~size_t(0) >> 4) / size_t(nch) / size_t(nstreams)) return RR_INVPARAM; // no buffer has 2^60 doubles
+  if (!block_hops || !step_hops || (!blocks && !nblocks && !max)) return RR_INVPARAM;
+  if ((blocks && !blocks_stride) || blocks_stride > (~size_t(0) >> 4) / size_t(nstreams)) return RR_INVPARAM;
+  a.energy = energy;
+  a.hops = hops;
+  a.weights = weights;
+  a.blocks = blocks;
+  a.nblocks = nblocks;
+  a.max = max;
+  a.energy_stride = energy_stride;
+  a.nhops = nhops;
+  a.blocks_stride = blocks_stride;
+  a.block_hops = block_hops;
+  a.step_hops = step_hops;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  a.inv = 1.0 / ((double)block_hops * (double)hop);
+  return RR_OK;
+}
+
+// the gate and the range over groups, and their twins; range: the percentiles are checked too, and abs_threshold < 0 is refused
+int loudness_groups_args(const double *blocks, size_t blocks_stride, int nstreams, const unsigned long long *nblocks, const int *group, int ngroups,
+                         double abs_threshold, double rel_factor, bool range, int pct_low, int pct_high, double *result, double *work,
+                         size_t work_doubles, rsmp::LoudnessGroupsArgs &a)
+{
+  if (!blocks || !nblocks || !group || !result || !work || nstreams < 1 || ngroups < 1) return RR_INVPARAM;
+  if (std::isnan(abs_threshold) || std::isnan(rel_factor)) return RR_INVPARAM;
+  if (blocks_stride > (~size_t(0) >> 4) / size_t(nstreams)) return RR_INVPARAM; // no buffer has 2^60 doubles
+  if (work_doubles < rsmp::loudness_groups_work_doubles(nstreams, ngroups)) return RR_INVPARAM;
+  if (range && (abs_threshold < 0 || pct_low < 0 || pct_low > 100 || pct_high < 0 || pct_high > 100)) return RR_INVPARAM;
+  a.blocks = blocks;
+  a.nblocks = nblocks;
+  a.group = group;
+  a.result = result;
+  a.work = work;
+  a.blocks_stride = blocks_stride;
+  a.nstreams = nstreams;
+  a.ngroups = ngroups;
+  a.pct_low = pct_low;
+  a.pct_high = pct_high;
+  a.abs_threshold = abs_threshold;
+  a.rel_factor = rel_factor;
+  return RR_OK;
+}
+
+} // namespace
+
+// Sliding block powers and their maximum (loudness_stats.hip).  Refusals first, as in RRX_finish_device.
+int RRX_loudness_blocks_device(int device, void *hip_stream, const double *d_energy, size_t energy_stride, int nstreams, int nch, size_t nhops,
+                               const unsigned long long *d_hops, const double *d_weights, size_t hop, size_t block_hops, size_t step_hops,
+                               double *d_blocks, size_t blocks_stride, unsigned long long *d_nblocks, double *d_max)
+{
+  rsmp::LoudnessBlocksArgs a;
+  const int rc = loudness_blocks_args(d_energy, energy_stride, nstreams, nch, nhops, d_hops, d_weights, hop, block_hops, step_hops, d_blocks,
+                                      blocks_stride, d_nblocks, d_max, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness_blocks(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_loudness_blocks_host(const double *energy, size_t energy_stride, int nstreams, int nch, size_t nhops, const unsigned long long *hops,
+                                   const double *weights, size_t hop, size_t block_hops, size_t step_hops, double *blocks, size_t blocks_stride,
+                                   unsigned long long *nblocks, double *max)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessBlocksArgs a;
+  const int rc = loudness_blocks_args(energy, energy_stride, nstreams, nch, nhops, hops, weights, hop, block_hops, step_hops, blocks, blocks_stride,
+                                      nblocks, max, a);
+  if (rc != RR_OK) return rc;
+  rsmp::loudness_blocks_host(a);
+  return RR_OK;
+}
+
+size_t RRX_loudness_groups_work_doubles(int nstreams, int ngroups)
+{
+  if (nstreams < 1 || ngroups < 1) return 0;
+  return size_t(rsmp::loudness_groups_work_doubles(nstreams, ngroups));
+}
+
+// The BS.1770 gate over the pooled blocks of groups of streams (loudness_stats.hip).  Refusals first, as in RRX_finish_device.
+int RRX_loudness_gate_groups_device(int device, void *hip_stream, const double *d_blocks, size_t blocks_stride, int nstreams,
+                                    const unsigned long long *d_nblocks, const int *d_group, int ngroups, double abs_threshold, double rel_factor,
+                                    double *d_result, double *d_work, size_t work_doubles)
+{
+  rsmp::LoudnessGroupsArgs a;
+  const int rc = loudness_groups_args(d_blocks, blocks_stride, nstreams, d_nblocks, d_group, ngroups, abs_threshold, rel_factor, false, 0, 0,
+                                      d_result, d_work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness_gate_groups(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_loudness_gate_groups_host(const double *blocks, size_t blocks_stride, int nstreams, const unsigned long long *nblocks, const int *group,
+                                        int ngroups, double abs_threshold, double rel_factor, double *result, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessGroupsArgs a;
+  const int rc = loudness_groups_args(blocks, blocks_stride, nstreams, nblocks, group, ngroups, abs_threshold, rel_factor, false, 0, 0, result, work,
+                                      work_doubles, a);
+  if (rc != RR_OK) return rc;
+  rsmp::loudness_gate_groups_host(a);
+  return RR_OK;
+}
+
+// Gated percentiles per group by exact selection (loudness_stats.hip).  Refusals first, as in RRX_finish_device.
+int RRX_loudness_range_groups_device(int device, void *hip_stream, const double *d_blocks, size_t blocks_stride, int nstreams,
+                                     const unsigned long long *d_nblocks, const int *d_group, int ngroups, double abs_threshold, double rel_factor,
+                                     int pct_low, int pct_high, double *d_result, double *d_work, size_t work_doubles)
+{
+  rsmp::LoudnessGroupsArgs a;
+  const int rc = loudness_groups_args(d_blocks, blocks_stride, nstreams, d_nblocks, d_group, ngroups, abs_threshold, rel_factor, true, pct_low,
+                                      pct_high, d_result, d_work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness_range_groups(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_loudness_range_groups_host(const double *blocks, size_t blocks_stride, int nstreams, const unsigned long long *nblocks,
+                                         const int *group, int ngroups, double abs_threshold, double rel_factor, int pct_low, int pct_high,
+                                         double *result, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessGroupsArgs a;
+  const int rc = loudness_groups_args(blocks, blocks_stride, nstreams, nblocks, group, ngroups, abs_threshold, rel_factor, true, pct_low, pct_high,
+                                      result, work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  rsmp::loudness_range_groups_host(a);
   return RR_OK;
 }
 

@@ -25,6 +25,8 @@ EXPECTED_SYMBOLS = [
     "RRX_true_peak_device", "RRX_debug_true_peak_host", "RRX_tracks_true_peak_device",
     "RRX_loudness_device", "RRX_loudness_work_doubles", "RRX_debug_loudness_host", "RRX_tracks_loudness_device",
     "RRX_loudness_gate_device", "RRX_debug_loudness_gate_host",
+    "RRX_loudness_blocks_device", "RRX_loudness_groups_work_doubles", "RRX_loudness_gate_groups_device", "RRX_loudness_range_groups_device",
+    "RRX_debug_loudness_blocks_host", "RRX_debug_loudness_gate_groups_host", "RRX_debug_loudness_range_groups_host",
     "RRX_track_geometry", "RRX_tracks_plan", "RRX_tracks_stage_device", "RRX_tracks_finish_device",
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
@@ -245,6 +247,18 @@ def lib():
             host = [vp, sz, C.c_int, C.c_int, sz, vp, vp, sz, C.c_double, C.c_double, vp]
             L.RRX_loudness_gate_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_loudness_gate_host.argtypes = host
+        if hasattr(L, "RRX_loudness_blocks_device"):  # (as above)
+            host = [vp, sz, C.c_int, C.c_int, sz, vp, vp, sz, sz, sz, vp, sz, vp, vp]
+            L.RRX_loudness_blocks_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_loudness_blocks_host.argtypes = host
+            L.RRX_loudness_groups_work_doubles.argtypes = [C.c_int, C.c_int]
+            L.RRX_loudness_groups_work_doubles.restype = sz
+            host = [vp, sz, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, sz]
+            L.RRX_loudness_gate_groups_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_loudness_gate_groups_host.argtypes = host
+            host = [vp, sz, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, sz]
+            L.RRX_loudness_range_groups_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_loudness_range_groups_host.argtypes = host
         if hasattr(L, "RRX_tracks_plan"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_track_geometry.argtypes = [P(RRConfig), sz, P(sz), P(sz), P(sz), P(sz)]
@@ -1084,6 +1098,160 @@ def loudness_normalizing_gain(lufs, n2, m, target_lufs=-18.0, max_dbtp=-1.0):
     return torch.where(ok, torch.minimum(by_loudness, by_peak), torch.ones_like(m)).contiguous()
 
 
+def _loudness_blocks(energy, hop, block_hops, step_hops, hops, weights, stream, want_blocks=True):
+    """loudness_blocks_device; want_blocks = False: the maximum alone (blocks and nblocks come back as None)"""
+    import torch
+    if (energy.dtype != torch.float64 or energy.dim() != 3 or not getattr(energy, "is_cuda", False) or not energy.is_contiguous()):
+        raise TypeError("energy must be a contiguous float64 device tensor [nstreams, nch, nhops]")
+    nstreams, nch, nhops = energy.shape
+    hop, L, P = int(hop), int(block_hops), int(step_hops)
+    if hop < 1:
+        raise ValueError("a hop has at least one frame")
+    if L < 1 or P < 1:
+        raise ValueError("a block has at least one hop, and so has the step between blocks")
+    dev = energy.device
+    if hops is not None and (hops.dtype != torch.int64 or tuple(hops.shape) != (nstreams,) or hops.device != dev or not hops.is_contiguous()):
+        raise TypeError("hops must be a contiguous int64 tensor [%d] on %s" % (nstreams, dev))
+    if weights is not None and not hasattr(weights, "data_ptr"):
+        weights = torch.tensor([float(v) for v in weights], dtype=torch.float64, device=dev)
+    if weights is not None and (weights.dtype != torch.float64 or tuple(weights.shape) != (nch,) or weights.device != dev or not weights.is_contiguous()):
+        raise TypeError("weights must be %d floats, or a contiguous float64 tensor [%d] on %s" % (nch, nch, dev))
+    most = 0 if nhops < L else (nhops - L) // P + 1
+    blocks = torch.zeros((nstreams, max(most, 1)), dtype=torch.float64, device=dev) if want_blocks else None
+    nblocks = torch.zeros((nstreams,), dtype=torch.int64, device=dev) if want_blocks else None
+    peak = torch.zeros((nstreams,), dtype=torch.float64, device=dev)
+    if not nstreams or not nch or not most:  # (no block anywhere: an empty tensor has no pointer, and there is nothing to do)
+        return blocks, nblocks, peak
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_loudness_blocks_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(energy.data_ptr()), nhops,
+                                            nstreams, nch, nhops, C.c_void_p(hops.data_ptr()) if hops is not None else None,
+                                            C.c_void_p(weights.data_ptr()) if weights is not None else None, hop, L, P,
+                                            C.c_void_p(blocks.data_ptr()) if want_blocks else None, blocks.shape[1] if want_blocks else 0,
+                                            C.c_void_p(nblocks.data_ptr()) if want_blocks else None, C.c_void_p(peak.data_ptr())),
+           "RRX_loudness_blocks_device")
+    return blocks, nblocks, peak
+
+
+def loudness_blocks_device(energy, hop, block_hops, step_hops=1, hops=None, weights=None, stream=None):
+    """Sliding block powers on the device (RRX_loudness_blocks_device) over `energy`, `hop`, `hops` and `weights` as in
+    loudness_gate_device: blocks of `block_hops` hops every `step_hops` hops -- (4, 1) is momentary loudness, (30, 1) short-term,
+    (30, 10) the 3 s blocks every second that loudness range is commonly computed on.  Returns (blocks float64 [nstreams, most],
+    nblocks int64 [nstreams], max float64 [nstreams]): stream s's first nblocks[s] blocks are written (`most` is what nhops hops
+    give, at least one column), and max[s] is the largest of them, +0.0 without one.  -0.691 + 10 log10 of a block is its loudness
+    in LUFS.  The call only enqueues."""
+    return _loudness_blocks(energy, hop, block_hops, step_hops, hops, weights, stream)
+
+
+def _loudness_groups(blocks, nblocks, groups, ngroups):
+    """the arguments of the two calls over groups, checked: (nstreams, stride, groups as an int32 device tensor, ngroups)"""
+    import torch
+    if blocks.dtype != torch.float64 or blocks.dim() != 2 or not getattr(blocks, "is_cuda", False) or not blocks.is_contiguous():
+        raise TypeError("blocks must be a contiguous float64 device tensor [nstreams, stride]")
+    nstreams, stride = blocks.shape
+    dev = blocks.device
+    if nblocks.dtype != torch.int64 or tuple(nblocks.shape) != (nstreams,) or nblocks.device != dev or not nblocks.is_contiguous():
+        raise TypeError("nblocks must be a contiguous int64 tensor [%d] on %s" % (nstreams, dev))
+    if groups is None:
+        if ngroups is not None and int(ngroups) != nstreams:
+            raise ValueError("without groups every stream is its own group: ngroups is %d" % nstreams)
+        groups, ngroups = torch.arange(nstreams, dtype=torch.int32, device=dev), nstreams
+    elif ngroups is None:
+        raise ValueError("give ngroups with the groups")
+    elif not hasattr(groups, "data_ptr"):
+        groups = torch.tensor([int(v) for v in groups], dtype=torch.int32, device=dev)
+    if groups.dtype != torch.int32 or tuple(groups.shape) != (nstreams,) or groups.device != dev or not groups.is_contiguous():
+        raise TypeError("groups must be %d ints, or a contiguous int32 tensor [%d] on %s" % (nstreams, nstreams, dev))
+    ngroups = int(ngroups)
+    if nstreams and ngroups < 1:
+        raise ValueError("there is at least one group")
+    return nstreams, stride, groups, ngroups
+
+
+def loudness_gate_groups_device(blocks, nblocks, groups, ngroups, abs_lufs=-70.0, rel_lu=-10.0, stream=None):
+    """The two-stage gate of BS.1770-4 over the POOLED blocks of groups of streams (RRX_loudness_gate_groups_device): `blocks` and
+    `nblocks` are what loudness_blocks_device returned -- (4, 1) blocks for the integrated loudness -- and may be concatenated from
+    several batches; `groups` (a sequence of ints, or an int32 device tensor [nstreams]) gives every stream's group in
+    [0, ngroups), any other value keeps the stream out of all groups.  Returns float64 [ngroups, 4]: S2, N2, S1, N1 per group,
+    which integrated_lufs turns into LUFS: the album loudness of ReplayGain 2.0 when a group is an album's tracks.  The call only
+    enqueues."""
+    import torch
+    nstreams, stride, groups, ngroups = _loudness_groups(blocks, nblocks, groups, ngroups)
+    dev = blocks.device
+    result = torch.zeros((ngroups, 4), dtype=torch.float64, device=dev)
+    if not nstreams:
+        return result
+    abs_threshold, rel_factor = loudness_gate(abs_lufs, rel_lu)
+    work = torch.empty((2 * nstreams + ngroups,), dtype=torch.float64, device=dev)
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_loudness_gate_groups_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(blocks.data_ptr()),
+                                                 stride, nstreams, C.c_void_p(nblocks.data_ptr()), C.c_void_p(groups.data_ptr()), ngroups,
+                                                 abs_threshold, rel_factor, C.c_void_p(result.data_ptr()), C.c_void_p(work.data_ptr()),
+                                                 work.numel()), "RRX_loudness_gate_groups_device")
+    return result
+
+
+def loudness_range_device(blocks, nblocks, groups=None, ngroups=None, abs_lufs=-70.0, rel_lu=-20.0, low=10, high=95, stream=None):
+    """Gated percentiles per group by exact selection (RRX_loudness_range_groups_device), the two ends of the loudness range of
+    EBU Tech 3342: arguments as in loudness_gate_groups_device -- (30, 10) or (30, 1) blocks -- with `groups` = None for every
+    stream as its own group.  Returns float64 [ngroups, 4]: P_low, P_high (the `low`-th and `high`-th percentile of the blocks that
+    pass both gates, as block powers), N2 (their number) and T (the relative threshold); loudness_range_lu turns it into LU.  The
+    call only enqueues."""
+    import torch
+    low, high = int(low), int(high)
+    if not (0 <= low <= 100 and 0 <= high <= 100):
+        raise ValueError("a percentile lies in 0..100")
+    nstreams, stride, groups, ngroups = _loudness_groups(blocks, nblocks, groups, ngroups)
+    dev = blocks.device
+    result = torch.zeros((ngroups, 4), dtype=torch.float64, device=dev)
+    if not nstreams:
+        return result
+    abs_threshold, rel_factor = loudness_gate(abs_lufs, rel_lu)
+    work = torch.empty((2 * nstreams + ngroups,), dtype=torch.float64, device=dev)
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_loudness_range_groups_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(blocks.data_ptr()),
+                                                  stride, nstreams, C.c_void_p(nblocks.data_ptr()), C.c_void_p(groups.data_ptr()), ngroups,
+                                                  abs_threshold, rel_factor, low, high, C.c_void_p(result.data_ptr()),
+                                                  C.c_void_p(work.data_ptr()), work.numel()), "RRX_loudness_range_groups_device")
+    return result
+
+
+def loudness_range_lu(result):
+    """Loudness range in LU from loudness_range_device's result [ngroups, 4] (a torch tensor, on the device or not; anything else
+    is converted): 10 log10(P_high / P_low), and 0.0 where no block passed the gates (N2 == 0).  Runs where the tensor lives."""
+    import torch
+    r = result if hasattr(result, "data_ptr") else torch.as_tensor(np.asarray(result, dtype=np.float64))
+    some = r[..., 2] > 0
+    one = torch.ones_like(r[..., 0])
+    return torch.where(some, 10.0 * torch.log10(torch.where(some, r[..., 1], one) / torch.where(some, r[..., 0], one)), torch.zeros_like(one))
+
+
+def loudness_meter_device(energy, hop, hops=None, weights=None, groups=None, ngroups=None):
+    """The numbers of EBU R 128 from hop energies that stay in HBM (`energy`, `hop`, `hops`, `weights` as in loudness_gate_device),
+    on the current stream and without a host synchronisation: a dict of float64 device tensors [nstreams] -- "integrated" (LUFS,
+    -inf where no block passed), "momentary_max" and "short_term_max" (LUFS, the largest 400 ms and 3 s block, -inf without one)
+    and "range" (LU, on 3 s blocks every second, gates at -70 LUFS and -20 LU, percentiles 10 and 95) -- and, when `groups` and
+    `ngroups` are given as in loudness_gate_groups_device, "group_integrated" and "group_range" [ngroups] over the pooled blocks of
+    each group.  Built from loudness_blocks_device, loudness_gate_groups_device and loudness_range_device."""
+    import torch
+    if not getattr(energy, "is_cuda", False):
+        raise TypeError("energy must be a contiguous float64 device tensor [nstreams, nch, nhops]")
+    cur = torch.cuda.current_stream(energy.device)
+    b4, n4, m4 = _loudness_blocks(energy, hop, 4, 1, hops, weights, cur)
+    _, _, m30 = _loudness_blocks(energy, hop, 30, 1, hops, weights, cur, want_blocks=False)
+    b30, n30, _ = _loudness_blocks(energy, hop, 30, 10, hops, weights, cur)
+    own = torch.arange(energy.shape[0], dtype=torch.int32, device=energy.device)
+    out = {"integrated": integrated_lufs(loudness_gate_groups_device(b4, n4, own, energy.shape[0], stream=cur)),
+           "momentary_max": -0.691 + 10.0 * torch.log10(m4), "short_term_max": -0.691 + 10.0 * torch.log10(m30),
+           "range": loudness_range_lu(loudness_range_device(b30, n30, own, energy.shape[0], stream=cur))}
+    if groups is not None:
+        out["group_integrated"] = integrated_lufs(loudness_gate_groups_device(b4, n4, groups, ngroups, stream=cur))
+        out["group_range"] = loudness_range_lu(loudness_range_device(b30, n30, groups, ngroups, stream=cur))
+    return out
+
+
 def tracks_finish_shaped_device(rows, table, dst_format, dst_total, shaping, segment=65536, gain=None, dither=True, seed=0, out=None, peak=None,
                                 clipped=None, stream=None):
     """tracks_finish_device with noise-shaped dither (RRX_tracks_finish_shaped_device): finish_shaped_device per track, in one
@@ -1874,7 +2042,7 @@ class Resampler:
         return views, peak[:n], clipped[:n], gain[:n], true_peak[:n]
 
     def convert_tracks_to_pcm_loudness_normalized(self, tracks, dst_format, target_lufs=-18.0, max_dbtp=-1.0, weights=None, shaping=None,
-                                                  segment=65536, dither=False, seed=0):
+                                                  segment=65536, dither=False, seed=0, album=None):
         """convert_tracks_to_pcm_device with every track normalised to an integrated LOUDNESS of `target_lufs` LUFS, held under a
         true peak of `max_dbtp` dBTP (ReplayGain 2.0, EBU R 128): the rows are converted once, measured with
         tracks_loudness_device + loudness_gate_device (K-weighting of the output rate, hops of out_rate // 10 frames, the gates of
@@ -1883,19 +2051,44 @@ class Resampler:
         no block passed the gates (a silent or very short track) or m is 0 or not finite -- computed on the device, without a host
         synchronisation; then the rows are finished under that gain as in convert_tracks_to_pcm_normalized.  Returns what that
         call returns, plus the loudness: (views, peak, clipped, gain [ntracks], true_peak [ntracks, nch], lufs [ntracks]); `lufs`
-        is the measured loudness BEFORE the gain, -inf where no block passed."""
+        is the measured loudness BEFORE the gain, -inf where no block passed.
+
+        `album` (None, or one non-negative int per track): the tracks of one album get ONE gain, which keeps the level differences
+        the album was mastered with (the album gain of ReplayGain 2.0).  L is then the album's loudness -- the gate over the pooled
+        400 ms blocks of its tracks, loudness_blocks_device + loudness_gate_groups_device -- and m the largest peak over its
+        tracks; the formula above is applied per album and gathered per track on the device.  The tuple keeps its six entries,
+        and `lufs[t]` is the loudness of t's album."""
         import torch
         tracks = list(tracks)
+        if album is not None:
+            album = [int(v) for v in album]
+            if len(album) != len(tracks) or any(v < 0 for v in album):
+                raise ValueError("album is one non-negative int per track")
         plan, table, out = self._convert_tracks_rows(tracks)
         n = len(tracks)
         cur = torch.cuda.current_stream(out.device)
         rate = int(self.cfg.out_rate)
         energy, hops = tracks_loudness_device(out, table, rate, stream=cur)
-        result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
-        lufs = integrated_lufs(result)
-        true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
-        m = torch.maximum(true_peak, sample_peak).amax(1)
-        gain = loudness_normalizing_gain(lufs, result[:, 1], m, target_lufs, max_dbtp)
+        if album is None:
+            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
+            lufs = integrated_lufs(result)
+            true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
+            m = torch.maximum(true_peak, sample_peak).amax(1)
+            gain = loudness_normalizing_gain(lufs, result[:, 1], m, target_lufs, max_dbtp)
+        else:
+            nalbums = max(album) + 1
+            of = torch.tensor(album, dtype=torch.int64, device=out.device)
+            groups = torch.full((out.shape[0],), -1, dtype=torch.int32, device=out.device)  # the streams without a track are in no album
+            groups[:n] = of.to(torch.int32)
+            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
+            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
+            per_album = integrated_lufs(result)
+            true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
+            m = torch.maximum(true_peak, sample_peak).amax(1)
+            most = torch.zeros((nalbums,), dtype=m.dtype, device=m.device).scatter_reduce(0, of, m[:n], "amax", include_self=True)
+            gain = torch.ones_like(m)
+            gain[:n] = loudness_normalizing_gain(per_album, result[:, 1], most, target_lufs, max_dbtp)[of]
+            lufs = per_album[of]
         if shaping is not None:
             pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=gain, dither=dither,
                                                              seed=seed, stream=cur)

@@ -631,6 +631,85 @@ int RRX_debug_loudness_gate_host(const double *energy, size_t energy_stride, int
                                  const unsigned long long *hops, const double *weights, size_t hop,
                                  double abs_threshold, double rel_factor, double *result);
 
+/* The loudness meter: what EBU R 128 and ReplayGain 2.0 ask for beyond the integrated loudness of one stream, from the same hop
+ * energies.  Three calls; all fp64, every operation rounded on its own, part of this ABI.  All only enqueue -- no allocation, no
+ * host synchronisation, work buffers from the caller -- and take device and hip_stream with RRX_finish_device's contract.  No libm
+ * runs on the device: the caller takes the logarithms.
+ *
+ * RRX_loudness_blocks_device: sliding block powers of L = block_hops hops every P = step_hops hops, and their maximum.  Energies,
+ * strides, d_hops, d_weights and hop as in RRX_loudness_gate_device.  Stream s with n = min(d_hops[s], nhops) valid hops has
+ *   nb = 0 if n < L, else (n - L) / P + 1, clamped to blocks_stride when d_blocks is given;   d_nblocks[s] = nb
+ *   block j begins at hop j*P:   per channel   q = e[jP], then q = q + e[jP+i] for i = 1 .. L-1 ascending
+ *                                block         acc = +0.0, then ascending channels acc = acc + w[ch]*q (d_weights NULL: acc + q);
+ *                                              z_j = acc * inv,  inv = 1.0 / ((double)L * (double)hop), computed once on the host
+ *   d_blocks[s * blocks_stride + j] = z_j for j < nb; nothing else of d_blocks is touched
+ *   d_max[s]: m = +0.0, then if (z_j > m) m = z_j over all j < nb.  A NaN fails the comparison and is skipped; the result does not
+ *   depend on the order and is reduced in parallel.  No block gives +0.0, which is -inf LUFS.
+ * With L = 4 and P = 1 the z_j have the bits of RRX_loudness_gate_device's blocks.  (4, 1) is momentary loudness, (30, 1)
+ * short-term; (30, 10) are the 3 s blocks every 1 s that loudness range is commonly computed on.  d_blocks ([nstreams][blocks_stride]
+ * doubles), d_nblocks ([nstreams] unsigned 64-bit) and d_max ([nstreams] doubles) may each be NULL, not all three.
+ * Returns RR_INVPARAM, before any device is touched, for what RRX_loudness_gate_device refuses of these arguments, and for
+ * block_hops == 0, step_hops == 0, all three outputs NULL, blocks_stride == 0 with d_blocks given, or nstreams * blocks_stride of
+ * 2^60 or more; RR_EXTUNINIT before init_ratelib; RR_INTERNAL for a failed launch. */
+int RRX_loudness_blocks_device(int device, void *hip_stream, const double *d_energy, size_t energy_stride, int nstreams, int nch,
+                               size_t nhops, const unsigned long long *d_hops, const double *d_weights, size_t hop,
+                               size_t block_hops, size_t step_hops, double *d_blocks, size_t blocks_stride,
+                               unsigned long long *d_nblocks, double *d_max);
+
+/* RRX_loudness_gate_groups_device: the two-stage gate of BS.1770-4 over the POOLED blocks of groups of streams -- the album gain of
+ * ReplayGain 2.0.  d_blocks, blocks_stride and d_nblocks (required, read clamped to blocks_stride) are what the call above left;
+ * they may have been collected from several batches.  d_group ([nstreams] int32 on the device) gives stream s's group in
+ * [0, ngroups); any other value means "in no group", and never faults.  The arithmetic is defined by this structure, not by the
+ * launch geometry:
+ *   per stream   j ascending and serial, from +0.0 and 0: S1_s and N1_s over the blocks with z > abs_threshold
+ *   per group    member streams in ascending s, serial, from +0.0: S1 = S1 + S1_s, N1 += N1_s;  T = rel_factor * (S1 / N1)
+ *   per stream   S2_s and N2_s over the blocks with z > abs_threshold && z > T, T its group's
+ *   per group    S2 and N2 the same way
+ *   d_result[g] = {S2, (double)N2, S1, (double)N1}, [ngroups][4] doubles on the device, written; the counts are exact integers.
+ * An empty group gives {+0.0, 0, +0.0, 0}; its T is NaN, as in RRX_loudness_gate_device with N1 = 0.
+ * A group of exactly ONE stream, over (4, 1) blocks, has the bits of RRX_loudness_gate_device on that stream: +0.0 + x is x for
+ * the non-negative sums.  Streams run in parallel: a whole library in one group costs its longest stream's serial walk, not the
+ * library's.
+ * d_work: at least RRX_loudness_groups_work_doubles(nstreams, ngroups) doubles on the device (host only; 0 for refused arguments;
+ * it depends on the two counts only, never on the blocks), content unspecified after the call.
+ * Returns RR_INVPARAM, before any device is touched, for d_blocks, d_nblocks, d_group, d_result or d_work NULL, nstreams < 1,
+ * ngroups < 1, nstreams * blocks_stride of 2^60 or more, a NaN threshold or factor, work_doubles too small, or device < -1; the
+ * rest as above. */
+size_t RRX_loudness_groups_work_doubles(int nstreams, int ngroups);
+int RRX_loudness_gate_groups_device(int device, void *hip_stream, const double *d_blocks, size_t blocks_stride, int nstreams,
+                                    const unsigned long long *d_nblocks, const int *d_group, int ngroups,
+                                    double abs_threshold, double rel_factor, double *d_result, double *d_work, size_t work_doubles);
+
+/* RRX_loudness_range_groups_device: gated percentiles per group by exact selection -- loudness range (EBU Tech 3342) is
+ * 10 log10(P_high / P_low) on the caller's side.  Arguments as in the call above.  T, and the multiset G of the group's blocks
+ * with z > abs_threshold && z > T, are exactly that call's.  With n = |G| and G sorted ascending by value:
+ *   P_low = G[((n-1)*pct_low + 50) / 100],  P_high = G[((n-1)*pct_high + 50) / 100]     (integer arithmetic, 0-based: Tech 3342's
+ *   round((n-1)*p/100 + 1), 1-based)
+ *   d_result[g] = {P_low, P_high, (double)n, T};  n == 0 gives {+0.0, +0.0, 0, T}.
+ * abs_threshold < 0 is refused: every element of G is then a positive double or +inf, whose order is the order of its bit pattern
+ * as an unsigned 64-bit integer, and equal values have equal bits, so the result is unique.  The device finds it by a radix
+ * select on those patterns, one workgroup per group: most significant byte first, a histogram per pass in LDS (integer counts
+ * do not depend on the order of arrival), both ranks carried through the same eight passes, the stream list walked per pass -- no
+ * sort, no buffer proportional to the block count, no limit on n; the counts are 64-bit.  Tech 3342 uses
+ * abs_threshold = 10^((-70 + 0.691) / 10), rel_factor = 10^(-20 / 10) and the percentiles 10 and 95.
+ * Refusals: those of the call above, and pct_low or pct_high outside 0..100 or abs_threshold < 0. */
+int RRX_loudness_range_groups_device(int device, void *hip_stream, const double *d_blocks, size_t blocks_stride, int nstreams,
+                                     const unsigned long long *d_nblocks, const int *d_group, int ngroups,
+                                     double abs_threshold, double rel_factor, int pct_low, int pct_high,
+                                     double *d_result, double *d_work, size_t work_doubles);
+/* Test hooks (host only, need no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the three calls on HOST pointers,
+ * as serial loops over the very functions the kernels call (the range twin sorts).  Same refusals, same results. */
+int RRX_debug_loudness_blocks_host(const double *energy, size_t energy_stride, int nstreams, int nch, size_t nhops,
+                                   const unsigned long long *hops, const double *weights, size_t hop,
+                                   size_t block_hops, size_t step_hops, double *blocks, size_t blocks_stride,
+                                   unsigned long long *nblocks, double *max);
+int RRX_debug_loudness_gate_groups_host(const double *blocks, size_t blocks_stride, int nstreams, const unsigned long long *nblocks,
+                                        const int *group, int ngroups, double abs_threshold, double rel_factor,
+                                        double *result, double *work, size_t work_doubles);
+int RRX_debug_loudness_range_groups_host(const double *blocks, size_t blocks_stride, int nstreams, const unsigned long long *nblocks,
+                                         const int *group, int ngroups, double abs_threshold, double rel_factor,
+                                         int pct_low, int pct_high, double *result, double *work, size_t work_doubles);
+
 /* Windows: the two passes above on frames [win_first, win_first + win_frames) of the rows, so that a ragged batch runs in memory
  * proportional to ntracks * window instead of ntracks * longest track.  The rows themselves are VIRTUAL: row_frames is their
  * length, and no buffer of that size exists.  A handle's output does not depend on how its input is cut into pushes, and dither,
