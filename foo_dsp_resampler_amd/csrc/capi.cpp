@@ -8,6 +8,7 @@
 #include "loudness.hpp"
 #include "loudness_stats.hpp"
 #include "lpc.hpp"
+#include "measure_window.hpp"
 #include "tracks.hpp"
 #include "true_peak.hpp"
 
@@ -1663,6 +1664,164 @@ int RRX_debug_tracks_window_cut(const RRX_track *entry, size_t row_frames, size_
   const rsmp::TracksFinishCut f = rsmp::tracks_finish_cut(tr, row_frames, dst_total, write != 0, w);
   const unsigned long long o[4] = {f.w0, f.w1, f.index, f.dst_frame};
   std::memcpy(finish, o, sizeof(o));
+  return RR_OK;
+}
+
+namespace {
+
+// the two state rules of the measuring window calls: no state only for a window at frame 0, and two buffers of `doubles` doubles
+// that do not overlap (equal pointers count)
+int measure_window_state(const double *state_in, double *state_out, size_t win_first, uintptr_t doubles)
+{
+  if (!state_in && win_first) return RR_INVPARAM; // only a window at frame 0 finds every track at its first frame or not begun
+  if (state_in && state_out) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
+    const uintptr_t bytes = doubles * sizeof(double); // ntracks * nch < 2^60: no wrap for a buffer that exists
+    if (x < y ? y - x < bytes : x - y < bytes) return RR_INVPARAM;
+  }
+  return RR_OK;
+}
+
+// RRX_tracks_true_peak_window_device / RRX_debug_tracks_true_peak_window_host: everything that can be refused from the arguments
+// alone -- what RRX_tracks_true_peak_device refuses, the three window refusals and the two state rules
+int tracks_true_peak_window_args(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win, size_t win_stride,
+                                 size_t row_frames, size_t win_first, size_t win_frames, const double *gain, const double *coefs, int phases,
+                                 int taps, const double *state_in, double *state_out, double *true_peak, double *peak,
+                                 rsmp::TruePeakWindowArgs &a)
+{
+  if (!tracks || !win || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (!true_peak && !peak) return RR_INVPARAM;
+  if (true_peak_filter(coefs, phases, taps, a.f) != RR_OK) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  if (tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, a.w) != RR_OK) return RR_INVPARAM;
+  if (measure_window_state(state_in, state_out, win_first, uintptr_t(ntracks) * uintptr_t(nch) * rsmp::kTpMaxTaps) != RR_OK) return RR_INVPARAM;
+  a.src = win;
+  a.gain = gain;
+  a.state_in = state_in;
+  a.state_out = state_out;
+  a.true_peak = true_peak;
+  a.peak = peak;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(tracks);
+  a.row_frames = row_frames;
+  a.ntracks = ntracks;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  return RR_OK;
+}
+
+// RRX_tracks_loudness_window_device / RRX_debug_tracks_loudness_window_host, likewise
+int tracks_loudness_window_args(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win, size_t win_stride,
+                                size_t row_frames, size_t win_first, size_t win_frames, const double *gain, const double *coefs, size_t hop,
+                                const double *state_in, double *state_out, double *energy, size_t energy_stride, unsigned long long *hops,
+                                double *work, size_t work_doubles, rsmp::LoudnessWindowArgs &a)
+{
+  static_assert(RRX_LOUDNESS_WIN_STATE == rsmp::kLoudnessWinState, "the header's constant is the kernels'");
+  if (!tracks || !win || ntracks < 1 || nch < 1 || !energy || !hops) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  rsmp::LoudnessArgs f;
+  if (loudness_filter(coefs, hop, f) != RR_OK) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks) || energy_stride > most / size_t(ntracks)) return RR_INVPARAM;
+  if (tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, a.w) != RR_OK) return RR_INVPARAM;
+  const unsigned long long need = rsmp::loudness_window_work_doubles(ntracks, nch, win_frames, hop); // (< 2^63: ntracks * win_frames * nch < 2^60)
+  if (work_doubles < need || (need && !work)) return RR_INVPARAM;
+  if (measure_window_state(state_in, state_out, win_first, uintptr_t(ntracks) * uintptr_t(nch) * rsmp::kLoudnessWinState) != RR_OK) return RR_INVPARAM;
+  a.src = win;
+  a.gain = gain;
+  a.state_in = state_in;
+  a.state_out = state_out;
+  a.energy = energy;
+  a.work = work;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(tracks);
+  a.hops_out = hops;
+  a.row_frames = row_frames;
+  a.hop = hop;
+  a.pieces = win_frames / hop + 2;
+  a.energy_stride = energy_stride;
+  a.ntracks = ntracks;
+  a.nch = nch;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  std::memcpy(a.c, f.c, sizeof(a.c));
+  std::memcpy(a.m, f.m, sizeof(a.m));
+  return RR_OK;
+}
+
+} // namespace
+
+// RRX_tracks_true_peak_device on a window of the output rows, the filter's history carried per track (measure_window.hip).
+// Refusals first.
+int RRX_tracks_true_peak_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                       const void *d_win, size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                       const double *d_gain, const double *coefs, int phases, int taps, const double *d_state_in,
+                                       double *d_state_out, double *d_true_peak, double *d_peak)
+{
+  rsmp::TruePeakWindowArgs a;
+  const int rc = tracks_true_peak_window_args(d_tracks, ntracks, nch, src_format, d_win, win_stride, row_frames, win_first, win_frames, d_gain,
+                                              coefs, phases, taps, d_state_in, d_state_out, d_true_peak, d_peak, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames || !win_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_true_peak_window(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_true_peak_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win, size_t win_stride,
+                                           size_t row_frames, size_t win_first, size_t win_frames, const double *gain, const double *coefs,
+                                           int phases, int taps, const double *state_in, double *state_out, double *true_peak, double *peak)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::TruePeakWindowArgs a;
+  const int rc = tracks_true_peak_window_args(tracks, ntracks, nch, src_format, win, win_stride, row_frames, win_first, win_frames, gain, coefs,
+                                              phases, taps, state_in, state_out, true_peak, peak, a);
+  if (rc != RR_OK) return rc;
+  if (row_frames && win_frames) rsmp::true_peak_window_host(a);
+  return RR_OK;
+}
+
+size_t RRX_tracks_loudness_window_work_doubles(int ntracks, int nch, size_t win_frames, size_t hop)
+{
+  if (ntracks < 1 || nch < 1 || !hop) return 0;
+  return size_t(rsmp::loudness_window_work_doubles(ntracks, nch, win_frames, hop));
+}
+
+// RRX_tracks_loudness_device on a window of the output rows, the hop in progress carried per track (measure_window.hip).
+// Refusals first.
+int RRX_tracks_loudness_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                      const void *d_win, size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                      const double *d_gain, const double *coefs, size_t hop, const double *d_state_in, double *d_state_out,
+                                      double *d_energy, size_t energy_stride, unsigned long long *d_hops, double *d_work, size_t work_doubles)
+{
+  rsmp::LoudnessWindowArgs a;
+  const int rc = tracks_loudness_window_args(d_tracks, ntracks, nch, src_format, d_win, win_stride, row_frames, win_first, win_frames, d_gain,
+                                             coefs, hop, d_state_in, d_state_out, d_energy, energy_stride, d_hops, d_work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames || !win_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness_window(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_loudness_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win, size_t win_stride,
+                                          size_t row_frames, size_t win_first, size_t win_frames, const double *gain, const double *coefs,
+                                          size_t hop, const double *state_in, double *state_out, double *energy, size_t energy_stride,
+                                          unsigned long long *hops, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessWindowArgs a;
+  const int rc = tracks_loudness_window_args(tracks, ntracks, nch, src_format, win, win_stride, row_frames, win_first, win_frames, gain, coefs,
+                                             hop, state_in, state_out, energy, energy_stride, hops, work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (row_frames && win_frames) rsmp::loudness_window_host(a);
   return RR_OK;
 }
 

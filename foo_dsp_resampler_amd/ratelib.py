@@ -31,6 +31,8 @@ EXPECTED_SYMBOLS = [
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
     "RRX_tracks_finish_shaped_window_device", "RRX_debug_tracks_finish_shaped_window_host",
+    "RRX_tracks_true_peak_window_device", "RRX_debug_tracks_true_peak_window_host", "RRX_tracks_loudness_window_work_doubles",
+    "RRX_tracks_loudness_window_device", "RRX_debug_tracks_loudness_window_host",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
     "RRX_reset", "RRX_tracks_batches", "RRX_plan_cache_clear", "RRX_plan_cache_stats",
@@ -54,6 +56,7 @@ at 44.1 kHz only; for another rate the caller brings coefficients: wherever a na
 finite floats."""
 
 RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS = 8, 16
+RRX_LOUDNESS_WIN_STATE = 16            # doubles per (track, channel) of tracks_loudness_window_device's state: S, Z, C, E, three zeros
 
 
 def _bs1770():
@@ -279,6 +282,15 @@ def lib():
             host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp, C.c_int, u64, vp, C.c_int, sz, vp, vp, vp, vp]
             L.RRX_tracks_finish_shaped_window_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_tracks_finish_shaped_window_host.argtypes = host
+        if hasattr(L, "RRX_tracks_true_peak_window_device"):  # (as above)
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+            L.RRX_tracks_true_peak_window_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_true_peak_window_host.argtypes = host
+            L.RRX_tracks_loudness_window_work_doubles.argtypes = [C.c_int, C.c_int, sz, sz]
+            L.RRX_tracks_loudness_window_work_doubles.restype = sz
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, sz]
+            L.RRX_tracks_loudness_window_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_loudness_window_host.argtypes = host
         if hasattr(L, "RRX_reset"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_reset.argtypes = [vp]
@@ -1413,6 +1425,159 @@ def _tracks_finish_shaped_window(win, table, row_frames, win_first, win_frames, 
     return out, peak, clipped, new_state
 
 
+def _tracks_measure_window(win, table, row_frames, win_first, win_frames, gain, state, state_out, width):
+    """what the two measuring window calls share: `win`, the window, the table, the gain and the two state tensors checked;
+    (dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain)"""
+    import torch
+    dt = str(win.dtype)
+    if win.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not win.is_cuda or not win.is_contiguous():
+        raise TypeError("win must be a contiguous float32 or float64 device tensor [ntracks, win_stride, nch]")
+    ntracks, win_stride, nch = win.shape
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
+    if win_frames > win_stride:
+        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
+    if state is None and win_first:
+        raise ValueError("only the window at frame 0 needs no state: pass the state the call before returned")
+    _tracks_table(table, ntracks)
+    dev = win.device
+    if table.device != dev:
+        raise TypeError("the table must be on %s" % (dev,))
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((ntracks,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (ntracks,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (ntracks, dev))
+    sshape = (ntracks, nch, width)
+    for t, name in ((state, "state"), (state_out, "state_out")):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != sshape or t.device != dev or not t.is_contiguous()):
+            raise TypeError("%s must be a contiguous float64 tensor %r on %s" % (name, sshape, dev))
+    if state is not None and state_out is not None and state_out.data_ptr() == state.data_ptr():
+        raise ValueError("the call must not read and write one state tensor")
+    return dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain
+
+
+def tracks_true_peak_window_device(win, table, row_frames, win_first, win_frames, gain=None, filter="bs1770", state=None, true_peak=None,
+                                   peak=None, stream=None):
+    """tracks_true_peak_device on a window of the output rows (RRX_tracks_true_peak_window_device): `win`, `table`, `row_frames`,
+    `win_first` and `win_frames` are tracks_finish_window_device's, `gain` and `filter` tracks_true_peak_device's.  The filter's
+    history of every (track, channel) is carried from window to window in `state`: None, or the float64 [ntracks, nch, 16] tensor
+    the call before returned; None is allowed only for the window at frame 0 (ValueError otherwise).  Windows that partition
+    [0, row_frames), taken in ascending contiguous order, each given the `true_peak`, `peak` and `state` of the one before, leave
+    tracks_true_peak_device's bits; anything else gives other numbers.  Returns (true_peak, peak, state): `state` is a NEW tensor
+    on every call -- handed on unchanged for the tracks the window did not touch, and the state that came in (or zeros) when
+    `win_frames` is 0.  The call only enqueues."""
+    return _tracks_true_peak_window(win, table, row_frames, win_first, win_frames, gain, filter, state, None, true_peak, peak, stream)
+
+
+def _tracks_true_peak_window(win, table, row_frames, win_first, win_frames, gain, filter, state, state_out, true_peak, peak, stream):
+    """tracks_true_peak_window_device with the tensor that receives the state given (`state_out`; None: a new one)"""
+    import torch
+    dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain = _tracks_measure_window(
+        win, table, row_frames, win_first, win_frames, gain, state, state_out, RRX_TP_MAX_TAPS)
+    phases, taps, coefs = _true_peak_filter(filter)
+    dev = win.device
+    true_peak, peak = _true_peak_stats(true_peak, peak, ntracks, nch, dev)
+    sshape = (ntracks, nch, RRX_TP_MAX_TAPS)
+    if not win_frames or not row_frames:  # touches nothing, the state included: the state handed on is the one that came in
+        return true_peak, peak, torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
+    new_state = torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out  # (every entry is written)
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_true_peak_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
+                                                    ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
+                                                    C.c_void_p(win.data_ptr()), win_stride, row_frames, win_first, win_frames,
+                                                    C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(coefs, C.c_void_p),
+                                                    phases, taps, C.c_void_p(state.data_ptr()) if state is not None else None,
+                                                    C.c_void_p(new_state.data_ptr()), C.c_void_p(true_peak.data_ptr()),
+                                                    C.c_void_p(peak.data_ptr())), "RRX_tracks_true_peak_window_device")
+    return true_peak, peak, new_state
+
+
+def tracks_loudness_window_device(win, table, row_frames, win_first, win_frames, rate=None, gain=None, coefs=None, hop=None, state=None,
+                                  energy=None, hops=None, work=None, stream=None):
+    """tracks_loudness_device on a window of the output rows (RRX_tracks_loudness_window_device): `win`, `table`, `row_frames`,
+    `win_first` and `win_frames` are tracks_finish_window_device's, `rate`, `gain`, `coefs` and `hop` tracks_loudness_device's.
+    Hops are counted from every track's own first output frame, so a window cuts them anywhere -- it may be shorter than a hop --
+    and `state` carries the hop in progress of every (track, channel): None, or the float64 [ntracks, nch, 16] tensor the call
+    before returned; None is allowed only for the window at frame 0 (ValueError otherwise).  `energy` (float64 [ntracks, nch,
+    nhops]) is allocated zeroed, with row_frames // hop hops, when not passed; one that is passed may hold fewer, and the tracks'
+    hops are clamped to it.  The call WRITES the energies of the hops that complete in this window and leaves the others alone.
+    `hops` (int64 [ntracks]) receives every track's hop count; `work` is scratch of RRX_tracks_loudness_window_work_doubles
+    doubles; both are allocated when not passed.  Windows that partition [0, row_frames), taken in ascending contiguous order, each
+    given the `energy` and `state` of the one before, leave tracks_loudness_device's energies and hops, bit for bit.  Returns
+    (energy, hops, state): `state` is a NEW tensor on every call, as in tracks_true_peak_window_device.  The call only enqueues."""
+    return _tracks_loudness_window(win, table, row_frames, win_first, win_frames, rate, gain, coefs, hop, state, None, energy, hops, work, stream)
+
+
+def _tracks_loudness_window(win, table, row_frames, win_first, win_frames, rate, gain, coefs, hop, state, state_out, energy, hops, work, stream):
+    """tracks_loudness_window_device with the tensor that receives the state given (`state_out`; None: a new one)"""
+    import torch
+    dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain = _tracks_measure_window(
+        win, table, row_frames, win_first, win_frames, gain, state, state_out, RRX_LOUDNESS_WIN_STATE)
+    c, hop = _loudness_filter(rate, coefs, hop)
+    dev = win.device
+    need = ntracks * nch * (win_frames // hop + 2) * 4
+    energy, work = _loudness_buffers(energy, work, ntracks, nch, row_frames // hop if energy is None else 0, need, dev)
+    if hops is None:
+        hops = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
+    elif hops.dtype != torch.int64 or tuple(hops.shape) != (ntracks,) or hops.device != dev or not hops.is_contiguous():
+        raise TypeError("hops must be a contiguous int64 tensor [%d] on %s" % (ntracks, dev))
+    sshape = (ntracks, nch, RRX_LOUDNESS_WIN_STATE)
+    if not win_frames or not row_frames:  # touches nothing, the state included: the state handed on is the one that came in
+        return energy, hops, torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
+    new_state = torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out  # (every entry is written)
+    _ensure_init()
+    if not energy.shape[2]:  # (an empty tensor has no pointer; no hop is written through this one)
+        energy_ptr = torch.zeros((1,), dtype=torch.float64, device=dev)
+    else:
+        energy_ptr = energy
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_loudness_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
+                                                   ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
+                                                   C.c_void_p(win.data_ptr()), win_stride, row_frames, win_first, win_frames,
+                                                   C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(c, C.c_void_p), hop,
+                                                   C.c_void_p(state.data_ptr()) if state is not None else None,
+                                                   C.c_void_p(new_state.data_ptr()), C.c_void_p(energy_ptr.data_ptr()), energy.shape[2],
+                                                   C.c_void_p(hops.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+           "RRX_tracks_loudness_window_device")
+    return energy, hops, new_state
+
+
+class _WindowMeter:
+    """The measuring pass of the streamed normalising conversions (Resampler._convert_tracks_streamed, `measure=`): true peak and,
+    with `rate`, hop energies of every pulled window at the running output position, each through two state tensors handed to and
+    fro.  Allocates the states, the statistics, one window's work buffer and ceil(longest output row / hop) hop energies per
+    (stream, channel); `result()` is (true_peak, sample_peak, energy or None, hops or None)."""
+
+    def __init__(self, rate, nch, plan, table, cap, win_out, dev, stream):
+        import torch
+        self.table, self.cap, self.stream, self.rate = table, cap, stream, rate
+        n = table.shape[0]
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.true_peak, self.peak = torch.zeros((n, nch), **f64), torch.zeros((n, nch), **f64)
+        self.tp_states = [torch.zeros((n, nch, RRX_TP_MAX_TAPS), **f64) for _ in range(2)]
+        self.energy = self.hops = None
+        if rate is not None:
+            hop = rate // 10
+            need = max(int(e.out_first + e.out_frames) for e in plan.table)
+            self.energy = torch.zeros((n, nch, max(1, -(-need // hop))), **f64)
+            self.hops = torch.zeros((n,), dtype=torch.int64, device=dev)
+            self.work = torch.empty((n * nch * (win_out // hop + 2) * 4,), **f64)
+            self.ld_states = [torch.zeros((n, nch, RRX_LOUDNESS_WIN_STATE), **f64) for _ in range(2)]
+
+    def __call__(self, wout, first, frames):
+        _tracks_true_peak_window(wout, self.table, self.cap, first, frames, None, "bs1770", self.tp_states[0], self.tp_states[1],
+                                 self.true_peak, self.peak, self.stream)
+        self.tp_states.reverse()
+        if self.rate is not None:
+            _tracks_loudness_window(wout, self.table, self.cap, first, frames, self.rate, None, None, None, self.ld_states[0],
+                                    self.ld_states[1], self.energy, self.hops, self.work, self.stream)
+            self.ld_states.reverse()
+
+    def result(self):
+        return self.true_peak, self.peak, self.energy, self.hops
+
+
 def _ensure_init():
     global _inited
     if not _inited:
@@ -1912,11 +2077,13 @@ class Resampler:
         scratch = finish_kw.pop("_scratch", None)
         return self._convert_tracks_streamed(tracks, dst_format, window, scratch, (shaping, segment), finish_kw, "convert_tracks_to_pcm_streamed_shaped")
 
-    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who):
+    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None):
         """the loop of convert_tracks_to_pcm_streamed (shaped None) and convert_tracks_to_pcm_streamed_shaped (shaped = (shaping,
         segment)): stage a window, push it, pull whatever is available into the output window and finish it at the running output
         position, then drain the same way.  The shaped form finishes with tracks_finish_shaped_window_device and ping-pongs two
-        state tensors."""
+        state tensors.  `measure` (the measuring pass of the normalising forms): called once as measure(plan, table, cap, longest
+        output window, device, stream), it gives a callable (_WindowMeter) that is called as (wout, first, frames) for every pulled
+        window instead of the output stage; nothing is written then, and the return is what that callable's `result()` gives."""
         import torch
         tracks, plan = self._tracks_checked(tracks)
         n, dev = len(tracks), tracks[0].device
@@ -1941,7 +2108,9 @@ class Resampler:
             win = torch.empty((self.nstreams, min(window, max(total, 1)), self.nch), dtype=torch.float32, device=dev)
             wout = torch.empty((self.nstreams, min(win_out, cap), self.nch), dtype=torch.float32, device=dev)
         # nothing to finish yet: allocates (and checks) the destination and the statistics
-        if shaped is None:
+        if measure is not None:
+            measure = measure(plan, table, cap, wout.shape[1], dev, cur)
+        elif shaped is None:
             pcm, peak, clipped = tracks_finish_window_device(wout, table, cap, 0, 0, dst_format, plan.dst_total, **finish_kw)
             finish_kw.update(out=pcm, peak=peak, clipped=clipped)
         else:
@@ -1968,7 +2137,10 @@ class Resampler:
                         if got >= cap:
                             raise RuntimeError("%s: more output than %d frames in gives" % (who, total))
                         k = self.pull_device(wout, min(wout.shape[1], cap - got), stride=wout.shape[1])
-                        if shaped is None:
+                        if measure is not None:
+                            if k:
+                                measure(wout, got, k)
+                        elif shaped is None:
                             tracks_finish_window_device(wout, table, cap, got, k, dst_format, plan.dst_total, **finish_kw)
                         elif k:  # (an empty window touches nothing, the state included: the two tensors keep their roles)
                             shaped_window(got, k)
@@ -1990,6 +2162,8 @@ class Resampler:
         need = max(int(e.out_first + e.out_frames) for e in plan.table)
         if got < need:
             raise RuntimeError("%s: %d output frames where the plan expects %d" % (who, got, need))
+        if measure is not None:
+            return measure.result()
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
 
@@ -2096,6 +2270,87 @@ class Resampler:
             pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n], gain[:n], true_peak[:n], lufs[:n]
+
+    def _streamed_under_gain(self, tracks, dst_format, window, shaping, segment, gain, dither, seed, who):
+        """pass B of the streamed normalising forms: reset(), then the streamed loop, shaped or not, under the per-track gain"""
+        if shaping is not None:
+            _shaping(shaping, segment)
+        self.reset()
+        kw = dict(gain=gain[:len(tracks)].contiguous(), dither=dither, seed=seed)
+        return self._convert_tracks_streamed(tracks, dst_format, window, None, None if shaping is None else (shaping, segment), kw, who)
+
+    def convert_tracks_to_pcm_streamed_normalized(self, tracks, dst_format, target_dbtp=-1.0, window=None, shaping=None, segment=65536,
+                                                  dither=False, seed=0):
+        """convert_tracks_to_pcm_normalized in bounded memory: the same inputs, the same (views, peak, clipped, gain, true_peak), equal
+        bit for bit whatever `window` is, and no rows.  Two passes over the same windows.  Pass A is convert_tracks_to_pcm_streamed's
+        loop with tracks_true_peak_window_device on every pulled window in place of the output stage -- the pulls are ascending and
+        contiguous from frame 0, the order that call needs; nothing is written.  The gain is derived on the device by
+        convert_tracks_to_pcm_normalized's own expressions, without a host synchronisation; the handle is reset(); pass B is the
+        streamed conversion, shaped (convert_tracks_to_pcm_streamed_shaped) or not, under that gain.  The tracks are resampled twice:
+        that is the price of never holding the rows ("Windows with true peak and loudness").  Memory: that of the
+        streamed form plus the two filter states [nstreams, nch, 16] and the statistics."""
+        import functools
+        import torch
+        tracks = list(tracks)
+        if shaping is not None:
+            _shaping(shaping, segment)  # (refused before anything is converted)
+        who = "convert_tracks_to_pcm_streamed_normalized"
+        true_peak, sample_peak, _, _ = self._convert_tracks_streamed(tracks, dst_format, window, None, None, {}, who,
+                                                                     measure=functools.partial(_WindowMeter, None, self.nch))
+        n = len(tracks)
+        m = torch.maximum(true_peak, sample_peak).amax(1)
+        target = 10.0 ** (float(target_dbtp) / 20.0)
+        gain = torch.where(torch.isfinite(m) & (m > 0), torch.full_like(m, target) / m, torch.ones_like(m)).contiguous()  # (one division, one rounding)
+        views, peak, clipped = self._streamed_under_gain(tracks, dst_format, window, shaping, segment, gain, dither, seed, who)
+        return views, peak, clipped, gain[:n], true_peak[:n]
+
+    def convert_tracks_to_pcm_streamed_loudness_normalized(self, tracks, dst_format, target_lufs=-18.0, max_dbtp=-1.0, weights=None,
+                                                           window=None, shaping=None, segment=65536, dither=False, seed=0, album=None):
+        """convert_tracks_to_pcm_loudness_normalized in bounded memory: the same inputs, `album` included, the same (views, peak,
+        clipped, gain, true_peak, lufs), equal bit for bit whatever `window` is, and no rows.  Two passes as in
+        convert_tracks_to_pcm_streamed_normalized: pass A measures every pulled window with tracks_true_peak_window_device and
+        tracks_loudness_window_device (K-weighting of the output rate, hops of out_rate // 10 frames counted from every track's own
+        first output frame, so a window cuts them anywhere); the gain comes from convert_tracks_to_pcm_loudness_normalized's own
+        expressions over the hop energies, on the device; pass B converts again under it.  Memory: that of the streamed form plus
+        the states (two of [nstreams, nch, 16] per measurement), one window's work buffer and nstreams * nch *
+        ceil(longest output row / hop) doubles of hop energies -- a ten-thousandth of the audio."""
+        import functools
+        import torch
+        tracks = list(tracks)
+        if album is not None:
+            album = [int(v) for v in album]
+            if len(album) != len(tracks) or any(v < 0 for v in album):
+                raise ValueError("album is one non-negative int per track")
+        if shaping is not None:
+            _shaping(shaping, segment)  # (refused before anything is converted)
+        who = "convert_tracks_to_pcm_streamed_loudness_normalized"
+        rate = int(self.cfg.out_rate)
+        true_peak, sample_peak, energy, hops = self._convert_tracks_streamed(tracks, dst_format, window, None, None, {}, who,
+                                                                             measure=functools.partial(_WindowMeter, rate, self.nch))
+        n = len(tracks)
+        dev = energy.device
+        cur = torch.cuda.current_stream(dev)
+        m = torch.maximum(true_peak, sample_peak).amax(1)
+        if album is None:
+            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
+            lufs = integrated_lufs(result)
+            gain = loudness_normalizing_gain(lufs, result[:, 1], m, target_lufs, max_dbtp)
+        else:
+            nalbums = max(album) + 1
+            of = torch.tensor(album, dtype=torch.int64, device=dev)
+            groups = torch.full((energy.shape[0],), -1, dtype=torch.int32, device=dev)  # the streams without a track are in no album
+            groups[:n] = of.to(torch.int32)
+            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
+            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
+            per_album = integrated_lufs(result)
+            most = torch.zeros((nalbums,), dtype=m.dtype, device=m.device).scatter_reduce(0, of, m[:n], "amax", include_self=True)
+            gain = torch.ones_like(m)
+            gain[:n] = loudness_normalizing_gain(per_album, result[:, 1], most, target_lufs, max_dbtp)[of]
+            lufs = per_album[of]
+            del blocks, nblocks
+        del energy, hops, result, sample_peak, m  # (pass B runs in the streamed form's memory, beside what is returned)
+        views, peak, clipped = self._streamed_under_gain(tracks, dst_format, window, shaping, segment, gain.contiguous(), dither, seed, who)
+        return views, peak, clipped, gain[:n], true_peak[:n], lufs[:n]
 
     def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut

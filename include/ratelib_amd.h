@@ -526,7 +526,8 @@ int RRX_tracks_finish_shaped_device(int device, void *hip_stream, const RRX_trac
  * starts from +0.0 at the track's first output frame.  A wrong table gives wrong numbers, never an access outside the rows.
  * Refusals: RR_INVPARAM, before any device is touched, for a NULL table or source, ntracks < 1, nch < 1, an unknown source format,
  * both result pointers NULL, the filter refusals of RRX_true_peak_device, ntracks * row_frames * nch of 2^60 samples or more, or
- * device < -1; the rest as there.  row_frames == 0 is RR_OK and does nothing.  A form by windows is not offered. */
+ * device < -1; the rest as there.  row_frames == 0 is RR_OK and does nothing.  The form by windows, with the history
+ * carried per track, is RRX_tracks_true_peak_window_device. */
 int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
                                 int src_format, const void *d_rows, size_t row_frames, const double *d_gain,
                                 const double *coefs, int phases, int taps, double *d_true_peak, double *d_peak);
@@ -599,8 +600,8 @@ int RRX_debug_loudness_host(int src_format, const void *src, size_t src_stride, 
  * access outside the rows, d_energy or d_work.
  * Refusals: RR_INVPARAM, before any device is touched, for a NULL table, source, d_energy or d_hops, ntracks < 1, nch < 1, an
  * unknown source format, the filter and work refusals of RRX_loudness_device, ntracks * row_frames * nch or ntracks * nch *
- * energy_stride of 2^60 or more, or device < -1; the rest as there.  row_frames == 0 is RR_OK and does nothing.  A form by windows
- * is not offered. */
+ * energy_stride of 2^60 or more, or device < -1; the rest as there.  row_frames == 0 is RR_OK and does nothing.  The form by
+ * windows, with the hop in progress carried per track, is RRX_tracks_loudness_window_device. */
 int RRX_tracks_loudness_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
                                const void *d_rows, size_t row_frames, const double *d_gain, const double *coefs, size_t hop,
                                double *d_energy, size_t energy_stride, unsigned long long *d_hops,
@@ -793,6 +794,84 @@ int RRX_debug_tracks_finish_shaped_window_host(const RRX_track *tracks, int ntra
                                                unsigned long long seed, const double *coefs, int order, size_t segment,
                                                const double *state_in, double *state_out, double *peak,
                                                unsigned long long *clipped);
+
+/* RRX_tracks_true_peak_device by windows: the true peak and the sample peak of every track of a ragged batch, measured a window
+ * of the output rows at a time.  The filter's history of a channel runs on from one window into the next, so the call takes and
+ * returns a per-(track, channel) STATE and depends on the order of the calls, as RRX_tracks_finish_shaped_window_device does.
+ *   Frames taken.  d_win, win_stride, row_frames, win_first, win_frames and the clamps under a wrong table are
+ *   RRX_tracks_finish_window_device's in its measure-only form, through the same function: of track t's clamped slice the frames
+ *   inside the window are processed; they are frames index, index + 1, ... of the slice.
+ *   Arithmetic.  Track t's processed frames get the results of a one-stream RRX_true_peak_device call on them with
+ *   first_frame = index, d_gain[t], the same filter, track t's entries of d_state_in as the history (read only when index > 0; at
+ *   index == 0 the history is +0.0, whatever the row holds in front of the slice), and flush = 1 exactly when the window holds
+ *   the slice's last frame.  The results accumulate into d_true_peak / d_peak [ntracks * nch] by the same unsigned 64-bit
+ *   maximum; the flushed taps - 1 frames enter the true peak only, neither the sample peak nor the state.
+ *   State.  d_state_in and d_state_out are [ntracks * nch][RRX_TP_MAX_TAPS] doubles on the device, laid out as in
+ *   RRX_true_peak_device.  Every call with win_frames > 0 and row_frames > 0 writes EVERY entry of d_state_out (when it is not
+ *   NULL): for a track with processed frames the history after its last processed real frame -- with fewer processed frames than
+ *   taps - 1 a mix of new and incoming entries, entries at taps - 1 and beyond 0 --; for a track with none (not begun, already
+ *   ended, zero length) a copy of its d_state_in entries, or zeros when d_state_in is NULL.  d_state_in NULL is allowed only with
+ *   win_first == 0 and is RR_INVPARAM otherwise.  The two buffers must not overlap over ntracks * nch * 16 doubles (RR_INVPARAM,
+ *   equal pointers included).  d_state_out may be NULL.
+ *   Order of calls.  Windows that partition [0, row_frames), taken in ascending contiguous order, each given the state of the one
+ *   before, leave the bits of ONE RRX_tracks_true_peak_device call in d_true_peak and d_peak, for any cut positions.  Anything
+ *   else gives other numbers, never an access outside the buffers.
+ * Returns RR_INVPARAM, before any device is touched, for everything RRX_tracks_true_peak_device refuses (with d_win for d_rows),
+ * the three window refusals of RRX_tracks_stage_window_device and the two state rules above.  row_frames == 0 or win_frames == 0
+ * is RR_OK and touches nothing, the state included.  The call only enqueues (no allocation, no host synchronisation): the LDS
+ * form where nch * taps <= 4096 and nch <= 1024, the direct form otherwise, as RRX_true_peak_device. */
+int RRX_tracks_true_peak_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                       int src_format, const void *d_win, size_t win_stride, size_t row_frames, size_t win_first,
+                                       size_t win_frames, const double *d_gain, const double *coefs, int phases, int taps,
+                                       const double *d_state_in, double *d_state_out, double *d_true_peak, double *d_peak);
+/* RRX_tracks_loudness_device by windows: the K-weighted hop energies of every track of a ragged batch, measured a window of the
+ * output rows at a time.  Hops are counted from each track's own first output frame, so a window cuts every track's hops at a
+ * different place, usually mid-hop, and may be shorter than a hop; the state therefore carries a partial hop.
+ *   Geometry.  With n = min(slice frames / hop, energy_stride) -- RRX_tracks_loudness_device's hop count -- the processed range of
+ *   track t is the window's cut of its slice (as in RRX_tracks_true_peak_window_device) intersected with slice frames
+ *   [0, n * hop): frames behind the last whole hop are never read.  With index the slice frame of the first processed one,
+ *   k0 = index / hop and r0 = index % hop, the range meets the "pieces" hop k0 + j intersected with the range, j = 0, 1, ...; the
+ *   first may begin mid-hop, the last may end mid-hop, and a range of m frames meets at most m / hop + 2 of them.
+ *   State.  [ntracks * nch][RRX_LOUDNESS_WIN_STATE] doubles: [0..3] = S, the true filter state at the start of the hop in
+ *   progress; [4..7] = Z, the state of the zero-started run after the r0 frames of that hop seen so far; [8..11] = C, the state of
+ *   the run started from S after those frames; [12] = E, the partial energy of that run; [13..15] = +0.0.  On a hop boundary
+ *   Z = 0, C = S and E = +0.0.  The state is read for a track only when index > 0.  Every call with win_frames > 0 and
+ *   row_frames > 0 writes every entry of d_state_out (when not NULL); a track without a processed frame gets a copy of its
+ *   d_state_in entries, or zeros when d_state_in is NULL.  d_state_in NULL only with win_first == 0, and no overlap of the two
+ *   buffers over ntracks * nch * 16 doubles (RR_INVPARAM, equal pointers included).
+ *   Arithmetic.  Three launches, RRX_loudness_device's block decomposition operation by operation.  (1) Every piece is run from
+ *   Z of the state (a first piece with r0 > 0) or from zeros, its end state z left in d_work.  (2) Per (track, channel) the pieces
+ *   are walked ascending from S of the state (+0.0 at index == 0): each piece's z is replaced by the start state of its hop,
+ *   S = M S + z is applied for every hop that completes in this window, and S and the z of an unfinished last piece go to the
+ *   state; d_hops[t] = n is written.  (3) Every piece is run again, a first piece with r0 > 0 from C and E of the state, every
+ *   other from its S_k and E = +0.0; a piece whose hop completes WRITES d_energy[(t * nch + ch) * energy_stride + k0 + j], an
+ *   unfinished last piece writes C and E to the state.  A serial sum cut in two gives the bits of the uncut sum, so under the
+ *   order rule of RRX_tracks_true_peak_window_device the energies and d_hops are RRX_tracks_loudness_device's bit for bit, for any
+ *   cut positions.  Energies of hops that did not complete in this call are left untouched.
+ *   d_work: RRX_tracks_loudness_window_work_doubles(ntracks, nch, win_frames, hop) = ntracks * nch * (win_frames / hop + 2) * 4
+ *   doubles of scratch (0 for ntracks < 1, nch < 1 or hop == 0).
+ * Returns RR_INVPARAM, before any device is touched, for everything RRX_tracks_loudness_device refuses (with d_win for d_rows;
+ * its work rule replaced by: work_doubles below the function above, or d_work NULL), the three window refusals and the two state
+ * rules.  row_frames == 0 or win_frames == 0 is RR_OK and touches nothing, the state included.  The call only enqueues. */
+#define RRX_LOUDNESS_WIN_STATE 16
+size_t RRX_tracks_loudness_window_work_doubles(int ntracks, int nch, size_t win_frames, size_t hop);
+int RRX_tracks_loudness_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                      int src_format, const void *d_win, size_t win_stride, size_t row_frames, size_t win_first,
+                                      size_t win_frames, const double *d_gain, const double *coefs, size_t hop,
+                                      const double *d_state_in, double *d_state_out, double *d_energy, size_t energy_stride,
+                                      unsigned long long *d_hops, double *d_work, size_t work_doubles);
+/* Test hooks (host only, need no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the two calls above on HOST
+ * pointers and a HOST table, each as one serial loop per (track, channel) over the very functions the kernels call for the cut
+ * and for every sample.  Same refusals, same results. */
+int RRX_debug_tracks_true_peak_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win,
+                                           size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                           const double *gain, const double *coefs, int phases, int taps, const double *state_in,
+                                           double *state_out, double *true_peak, double *peak);
+int RRX_debug_tracks_loudness_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *win,
+                                          size_t win_stride, size_t row_frames, size_t win_first, size_t win_frames,
+                                          const double *gain, const double *coefs, size_t hop, const double *state_in,
+                                          double *state_out, double *energy, size_t energy_stride, unsigned long long *hops,
+                                          double *work, size_t work_doubles);
 
 /* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: what the two window calls take
  * from one HOST table entry for the window [win_first, win_first + win_frames) of rows of row_frames frames, computed by the very

@@ -71,6 +71,23 @@ the cost from.
 
   python tools/perf_tracks.py --streamed --shaped [--window FRAMES] [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
 
+--streamed --normalized measures the streamed loudness-normalised conversion ("Windows with true peak and loudness")
+on the same batch, S16 tracks in, packed S24 out with dither, at the two windows measured above (isamp_max and 65536; --window: that
+one only), and appends one line per window to profiles/tracks_window_measure_perf.jsonl.  Four ways in one process, each on a fresh
+handle:
+
+  pass_a                  the measuring pass alone: the streamed loop with the two measuring window calls in place of the output stage;
+  streamed_normalized     convert_tracks_to_pcm_streamed_loudness_normalized: pass A, the gain, a reset, the streamed conversion;
+  streamed                convert_tracks_to_pcm_streamed: what one pass over the windows costs;
+  whole_rows_normalized   convert_tracks_to_pcm_loudness_normalized: every row whole, converted once.
+
+The two normalised results are compared first, every element of their tuples ("equal"); warm-up, rounds, medians, ranges and peak
+memory as above.  One JSON line {"what": "streamed_normalized", "window", "win_out", "windows_out", "hop", "<way>_ms", "<way>_ms_rounds",
+"<way>_range_ms", "<way>_peak_bytes", "pass_a_over_streamed", "streamed_normalized_over_whole_rows_normalized", "measuring_ms": pass_a -
+streamed, "predicted_loudness_ms": windows_out * 2 * hop * 230 cycles at 2.4 GHz, the cost DESIGN.md 11 predicts, "equal"}.
+
+  python tools/perf_tracks.py --streamed --normalized [--window FRAMES] [--seed 20240229] [--tracks 64] [--rounds 5] [--out FILE]
+
 --library measures a library on ONE handle ("Libraries"): the same LCG lengths, 256 tracks (--tracks) on a handle of 64
 streams (--streams), S16 tracks in, packed S24 out with dither and per-track gains, at phase 50 and at phase 25, and appends to
 profiles/tracks_library_perf.jsonl:
@@ -389,6 +406,82 @@ def streamed_shaped_main(a, lens):
             f.write(text + "\n")
 
 
+def streamed_normalized_main(a, lens):
+    plan = F.tracks_plan(FS, FO, lens)
+    v = pcm_source(lens, 15, a.seed)
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + n)
+    tracks = [v[offs[t]:offs[t + 1]] for t in range(len(lens))]
+    kw = dict(dither=True, seed=a.seed)
+    fmt = F.RRX_FMT_S24_3
+    isamp_max = [0]
+    want = [int(e.out_frames) for e in plan.table]
+    for window in (None, 65536) if a.window is None else (a.window,):
+        def form(which):
+            def run(keep=False):
+                r = F.Resampler(FS, FO, nch=NCH, nstreams=len(tracks))
+                isamp_max[0] = r.isamp_max
+                if which == "pass_a":                            # the measuring pass of the streamed loudness-normalised form, alone
+                    import functools
+                    res = r._convert_tracks_streamed(list(tracks), fmt, window, None, None, {}, "pass_a",
+                                                     measure=functools.partial(F.ratelib._WindowMeter, FO, NCH))
+                    r.close()
+                    return res if keep else want
+                if which == "streamed_normalized":
+                    res = r.convert_tracks_to_pcm_streamed_loudness_normalized(tracks, fmt, window=window, **kw)
+                elif which == "whole_rows_normalized":
+                    res = r.convert_tracks_to_pcm_loudness_normalized(tracks, fmt, **kw)
+                else:
+                    res = r.convert_tracks_to_pcm_streamed(tracks, fmt, window=window, **kw)
+                r.close()
+                return res if keep else [y.shape[0] for y in res[0]]
+            return run
+
+        ways = {k: form(k) for k in ("pass_a", "streamed_normalized", "streamed", "whole_rows_normalized")}
+        first = {k: round(timed(fn)[0], 2) for k, fn in ways.items()}        # warm-up: code objects, the caching allocator
+        x, y = ways["whole_rows_normalized"](keep=True), ways["streamed_normalized"](keep=True)
+        equal = bool(torch.equal(x[0][0]._base, y[0][0]._base) and all(torch.equal(p.contiguous().view(torch.int64), q.contiguous().view(torch.int64))
+                                                                       for p, q in zip(x[1:], y[1:])))
+        del x, y
+        peak = {}
+        for k, fn in ways.items():
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            peak[k] = torch.cuda.max_memory_allocated() - before
+        for fn in ways.values():                                             # (the cache was emptied: fill it again before timing)
+            fn()
+        ms = {k: [] for k in ways}
+        for _ in range(a.rounds):
+            for k, fn in ways.items():
+                t, got = timed(fn)
+                ms[k].append(t)
+                assert got == want, k
+        med = {k: statistics.median(t) for k, t in ms.items()}
+        win = window if window is not None else isamp_max[0]
+        total = plan.row_frames + -(-2 * FS // FO) + 1                       # the virtual rows of the streamed forms (ratelib.py)
+        cap, win_out = total * FO // FS + 2, -(-win * FO // FS)
+        windows_out = -(-cap // min(win_out, cap))
+        hop = FO // 10
+        line = {"what": "streamed_normalized", "src_format": "s16", "dst_format": "s24_3", "seed": a.seed, "tracks": len(lens), "nch": NCH,
+                "in_rate": FS, "out_rate": FO, "frames_total": sum(lens), "row_frames": plan.row_frames, "out_row_cap": plan.out_row_cap,
+                "window": win, "isamp_max": isamp_max[0], "win_out": win_out, "windows_out": windows_out, "hop": hop}
+        ways_into(line, ways, peak, ms, med)
+        line.update({"pass_a_over_streamed": round(med["pass_a"] / med["streamed"], 3),
+                     "streamed_normalized_over_whole_rows_normalized": round(med["streamed_normalized"] / med["whole_rows_normalized"], 3),
+                     "measuring_ms": round(med["pass_a"] - med["streamed"], 2),     # pass A has no output stage: a lower bound of the measuring
+                     "predicted_loudness_ms": round(windows_out * 2 * hop * 230 / 2.4e6, 1),   # windows x 2 x one hop's chain, 230 cycles a frame at 2.4 GHz
+                     "tracks_bytes": v.numel() * v.element_size(), "first_call_ms": first, "equal": equal, "rounds": a.rounds})
+        text = json.dumps(line)
+        print(text, flush=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+
+
 def streamed_main(a, lens):
     plan = F.tracks_plan(FS, FO, lens)
     v = pcm_source(lens, 15, a.seed)
@@ -540,6 +633,7 @@ def main():
     ap.add_argument("--streamed", action="store_true", help="the window form against the whole-row form instead (see above)")
     ap.add_argument("--window", type=int, default=None, help="--streamed: frames of the input window (default: isamp_max)")
     ap.add_argument("--shaped", action="store_true", help="--streamed: noise-shaped dither in the window form instead (see above)")
+    ap.add_argument("--normalized", action="store_true", help="--streamed: the streamed loudness-normalised conversion instead (see above)")
     ap.add_argument("--library", action="store_true", help="a library on one handle against fresh handles per batch instead (see above)")
     ap.add_argument("--streams", type=int, default=64, help="--library: streams of the handle")
     ap.add_argument("--out", default=None)
@@ -548,6 +642,7 @@ def main():
         a.tracks = 256 if a.library else 64
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "tracks_library_perf.jsonl" if a.library else "tracks_window_shaped_perf.jsonl" if a.streamed and a.shaped else
+                             "tracks_window_measure_perf.jsonl" if a.streamed and a.normalized else
                              "tracks_window_perf.jsonl" if a.streamed else
                              "tracks_pcm_perf.jsonl" if a.pcm else "tracks_perf.jsonl")
     if not torch.cuda.is_available():
@@ -558,6 +653,10 @@ def main():
         return library_main(a, lens)
     if a.shaped and not a.streamed:
         raise SystemExit("--shaped goes with --streamed")
+    if a.normalized and not a.streamed:
+        raise SystemExit("--normalized goes with --streamed")
+    if a.streamed and a.normalized:
+        return streamed_normalized_main(a, lens)
     if a.streamed:
         return streamed_shaped_main(a, lens) if a.shaped else streamed_main(a, lens)
     if a.pcm:
