@@ -85,6 +85,9 @@ int Engine::create(const Config &cfg, int nch, int nstreams, int device, Engine 
   if (fmt != 0 && fmt != 1 && fmt != 16 && fmt != 32) return kInvParam;
   if (nch < 1 || nstreams < 1) return kInvParam;
   if ((long long)nch * nstreams > INT_MAX / 4096) return kNoMem; // parameter guard: more channels than any device could hold fifos for
+  // an odd channel count whose pairs the kernels' 32-bit reciprocal cannot divide exactly (kernels.hpp, pair_division_exact;
+  // as pair_nchs: the pairs of a batch with an odd count per stream stay inside their stream)
+  if (!pair_division_exact(nch * nstreams, (nstreams > 1 && (nch & 1)) ? nch : 0)) return kInvParam;
   int dev_count = 0;
   if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count < 1) return kUninit; // no HIP device: fail loudly
   if (device < 0 && hipGetDevice(&device) != hipSuccess) return kUninit;
@@ -1434,7 +1437,8 @@ int Engine::feed_impl(const void *d_in, size_t stride_frames, size_t isamp, void
   ein.stride_elems = (long long)stride_frames * nch_;
   ExtOut eout;
   const long long wr_out0 = book_.wr.back();
-  if (d_out && out_cap && book_.rd.back() == wr_out0) {
+  // (no stages: the input ring IS the output fifo and no kernel writes d_out; the frames reach it by the caller's pull)
+  if (d_out && out_cap && !plan_.stages.empty() && book_.rd.back() == wr_out0) {
     eout.ptr = d_out;
     eout.begin = wr_out0;
     eout.end = wr_out0 + (long long)out_cap;

@@ -154,7 +154,8 @@ struct PairCh {
 __device__ __forceinline__ PairCh pair_channels(int pair, int C, int nchs, unsigned pps_magic)
 {
   // One branch-free, division-free, wave-uniform form for both cases: with nchs = 0 the whole handle counts as one
-  // "stream" of C channels.  pps_magic = ceil(2^32 / pairs per stream) (pair_magic; 0 = one pair per stream), exact for pair < 2^32 / pps.
+  // "stream" of C channels.  pps_magic = ceil(2^32 / pairs per stream) (pair_magic; 0 = one pair per stream): the quotient is exact while pair * pps <= 2^32,
+  // which Engine::create sees to for every pair of a handle (pair_division_exact, with the derivation and the one case that needs less).
   const int ncs = nchs > 0 ? nchs : C, pps = (ncs + 1) >> 1;
   const int strm = pps_magic ? (int)__umulhi((unsigned)pair, pps_magic) : pair /* one pair per stream */, pin = pair - strm * pps;
   PairCh r;

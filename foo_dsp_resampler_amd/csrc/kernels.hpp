@@ -140,6 +140,20 @@ __host__ __device__ inline unsigned pair_magic(int C, int nchs)
   return pps <= 1 ? 0u : (unsigned)(((1ull << 32) + pps - 1) / pps); // 0: one pair per stream, no division
 }
 
+// Can pair_channels serve every pair of such a handle?  With magic = ceil(2^32 / pps) = (2^32 + e) / pps, 0 <= e < pps, the
+// quotient __umulhi(pair, magic) = floor(pair / pps + pair * e / (pps * 2^32)) is floor(pair / pps) whenever pair * e < 2^32,
+// and pair * pps <= 2^32 sees to that for every e.  The pairs of a handle run below npairs, so npairs * pps <= 2^32 is enough.
+// One case needs less: with nchs = 0 and an even C every pair lies in "stream" 0 of pps = C / 2 pairs, the quotient is 0 or 1
+// (pair * magic < 2^32 + pps), and a quotient of 1 leaves ca = C + 2 * (pair - pps) = 2 * pair and hasb true all the same.  With
+// an odd C that slip gives 2 * pair - 1: a one-stream handle of 131 073 channels (pps = 65 537, magic = 65 536) would hand its
+// last pair channel 131 071 instead of 131 072.  Engine::create refuses what this function refuses.
+inline bool pair_division_exact(int C, int nchs)
+{
+  if (nchs <= 0 && !(C & 1)) return true;
+  const unsigned long long pps = (unsigned long long)(((nchs > 0 ? nchs : C) + 1) >> 1);
+  return (unsigned long long)pair_count(C, nchs) * pps <= (1ull << 32);
+}
+
 // Long blocks (N = 32768 ... 131072): N = 16 x M four-step transform in three launches through a workspace (dftbig.hip)
 struct BigDftArgs {
   DftArgs d;             // tw_fwd / tw_inv: fft_regs tables of the forward / inverse ROW lengths

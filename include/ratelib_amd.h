@@ -20,7 +20,9 @@ extern "C" {
  * on such a handle use packed host buffers (stride = the frame count of the call).
  * Every stream's output is bit-identical to what a handle of its own produces, for even and odd channel counts
  * alike: the channel pairs that share a complex transform never straddle two streams (with an odd count the last
- * channel of each stream rides alone, exactly as in a one-stream handle). */
+ * channel of each stream rides alone, exactly as in a one-stream handle).
+ * nchannels * nstreams above 524 287 is RR_ENOMEM before anything is allocated.  An odd nchannels is RR_INVPARAM where
+ * streams * pairs-per-stream^2 exceeds 2^32 with pairs-per-stream = (nchannels + 1) / 2 (RR_open: 131 073 channels or more). */
 int RRX_open_batch(const RR_config *config, int nchannels, int nstreams, RR_handle **const handle);
 
 /* Devices.  A handle lives on ONE HIP device: all of its memory, streams and launches.  Every entry point of both headers

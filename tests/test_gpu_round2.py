@@ -69,6 +69,26 @@ def test_enomem_runs_the_handler_once_and_leaves_no_handle():
     assert_parity(F.Resampler(44100, 96000, 2).process(x), Oracle(44100, 96000, 2).process(x))
 
 
+def test_odd_channel_counts_the_pair_division_cannot_serve_are_refused():
+    """The kernels find a pair's stream with a 32-bit reciprocal of the pairs per stream, exact while pairs x pairs per stream
+    <= 2^32 (kernels.hpp, pair_division_exact).  Engine::create refuses the odd channel counts beyond that, before any
+    allocation, as a bad argument: a one-stream handle of 131 073 channels (65 537 pairs: the last one would get channel 131 071),
+    and a batch of 3 streams of 100 001 channels (3 x 50 001 pairs of 50 001 per stream).  No handle, no allocation handler, and
+    the library keeps working."""
+    L = F.lib()
+    R._ensure_init()
+    before = R.alloc_handler_calls
+    cfg = F.RRConfig(44100, 96000, 50.0, 95.0, 0, 0)
+    for nch, S in ((131073, 1), (100001, 3)):
+        assert nch * S <= 524287                                      # inside the channel guard of the test above
+        h = C.c_void_p(0x1234)
+        rc = L.RRX_open_batch(C.byref(cfg), nch, S, C.byref(h))
+        assert rc == 6 and not h.value, (nch, S, rc)                  # RR_INVPARAM
+    assert R.alloc_handler_calls == before
+    x = lcg_noise(5000, 3, 1)
+    assert_parity(F.Resampler(44100, 96000, 3).process(x), Oracle(44100, 96000, 3).process(x))
+
+
 def test_failed_push_poisons_the_handle():
     """A device allocation that fails in the middle of a push (ring growth) returns RR_ENOMEM, runs the handler once,
     and the handle then answers RR_INTERNAL to every data call instead of continuing on skewed counters; closing it and
