@@ -413,6 +413,13 @@ int RRX_debug_walk_start(const RRX_walk_geom *g, int k, RRX_walk_start *out)
   return 0;
 }
 
+int RRX_debug_window_start(const RRX_walk_geom *g, int group, int bq, int *arith, int *table, unsigned rcp[3])
+{
+  if (!rsmp::knobs().test_hooks || !g || !arith || !table || !rcp) return -1;
+  if (g->polyL < 1 || g->step < 1 || group < 0 || group >= (g->polyL + 15) / 16 || bq < 0 || bq > 3) return -2;
+  return rsmp::fused_window_start_host(g->at0, g->step, g->polyL, group, bq, arith, table, rcp) ? 0 : -2;
+}
+
 // lpc/lpc.h:27 on device-resident frames.  Everything that can be refused from the arguments alone is refused before any
 // device is touched.
 int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data, size_t stream_stride, int nstreams, size_t data_len,

@@ -201,7 +201,7 @@ MfGeom mf_geom(const StageSpec &p)
 
 // A operands of v_mfma_f64_4x4x4 (fused.hip, polymf.hip): lane = 16k + 4b + i of cfm holds the coefficient of residue
 // 16g + 4b + i at tap 4s + k of its 4-residue block's common window, which starts at period qtab[4g + b].  cfm2 holds the same
-// tiles two k-steps per 16-byte element (half the load instructions in the lean kernel).
+// tiles two k-steps per 16-byte element (half the load instructions in the lean kernel; odd KS: the last element's second half is zero).
 struct MfOperands { std::vector<double> cfm; std::vector<int> qtab; std::vector<double2> cfm2; };
 
 MfOperands mf_operands(const MfGeom &mg, const StageSpec &p, const std::vector<double> &poly_table)
@@ -210,11 +210,7 @@ MfOperands mf_operands(const MfGeom &mg, const StageSpec &p, const std::vector<d
   MfOperands op;
   op.qtab.resize(size_t(mg.NGRP) * 4);
   for (int g = 0; g < mg.NGRP; ++g)
-    for (int bq = 0; bq < 4; ++bq) {
-      int rb = 16 * g + 4 * bq;
-      if (rb >= p.L) rb = 0; // idle block: all-zero coefficients, any in-range window will do
-      op.qtab[size_t(g) * 4 + bq] = (at0 + rb * pstep) / p.L;
-    }
+    for (int bq = 0; bq < 4; ++bq) op.qtab[size_t(g) * 4 + bq] = walk_q_table(at0, pstep, p.L, g, bq); // (idle blocks: block 0's)
   op.cfm.assign(size_t(mg.NGRP) * KS * 64, 0.0);
   op.cfm2.assign(size_t(mg.NGRP) * KSP * 64, make_double2(0.0, 0.0));
   for (int g = 0; g < mg.NGRP; ++g)
@@ -222,8 +218,6 @@ MfOperands mf_operands(const MfGeom &mg, const StageSpec &p, const std::vector<d
       for (int lane = 0; lane < 64; ++lane) {
         const int k = lane >> 4, bq = (lane >> 2) & 3, r = 16 * g + 4 * bq + (lane & 3);
         const int qb = op.qtab[size_t(g) * 4 + bq];
-        if ((KS & 1) && s == KS - 1) // the spare half of the last element carries the lane's window start
-          op.cfm2[(size_t(g) * KSP + KSP - 1) * 64 + lane].y = double(qb);
         if (r >= p.L) continue;
         const int ar = at0 + r * pstep, q = ar / p.L, ph = ar - q * p.L;
         const int j = 4 * s + k - (q - qb);
@@ -531,6 +525,10 @@ int Engine::init_fused_pair(int i, size_t &slab_cap)
     fu.KS = mg.KS;
     fu.qb_max = mg.qb_max;
     fu.qb_min = mg.qb_min;
+    // the lean kernels divide by multiply-high and shift where the other kernels read qtab: a stage without an exact
+    // reciprocal (none is known) keeps rcp_m = 0, and its lean launches are refused
+    WalkRcp rcp;
+    if (walk_rcp(p.at0 >> 32, pstep, p.L, rcp)) fu.rcp_m = rcp.m, fu.rcp_s = rcp.s;
   }
   const size_t per_launch = size_t(fu.blk_cap / std::max(1, fu.nsub) - 2) * size_t((V - d.remL0 + d.L - 1) / d.L);
   // frames of chain input per launch: divide by the rate of everything ahead of the dft stage
@@ -1080,6 +1078,8 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
   fa.cfm2 = fu.cfm2;
   fa.NGRP = fu.NGRP;
   fa.KS = fu.KS;
+  fa.rcp_m = fu.rcp_m;
+  fa.rcp_s = fu.rcp_s;
   fa.stamps = stamps_;
   const bool split = fu.nsub > 0;
   const int ntab = split ? pend.nblocks * fu.nsub : pend.nblocks; // table entries = workgroups per pair: blocks, or sub-blocks
@@ -1174,6 +1174,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
       if (eout.ptr && !ext_ok) return kInternal; // (an odd frame stride with an even channel count cannot happen)
       if (omode == 2 && !io.out_ring) return kInternal;
     }
+    if (!fa.rcp_m) return kInternal; // (no exact reciprocal of polyL for this stage's window starts)
     FusedArgs fr = fa;
     fr.d.G = fu.Gs;
     fr.d.tw_fwd = fr.d.tw_inv = twiddles(12);
@@ -1231,6 +1232,7 @@ int Engine::launch_fused_pair(Pass &ps, int i, long long count, long long step)
     fr.wst = fa.wst + b0;
     const int pi = prof_begin(true);
     const char *kn = nullptr;
+    if (fast && !fr.rcp_m) return kInternal; // (no exact reciprocal of polyL for this stage's window starts)
     if (fast) HIP_TRY(launch_fused_fast(pend_log2p, fr, io, stream_, &kn));
     else
       HIP_TRY(launch_fused(pend_log2n, pend_log2p, view(i - 1, &ein), view(i + 1, nullptr, &eout), fr, stream_, &kn));

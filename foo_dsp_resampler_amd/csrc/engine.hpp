@@ -201,6 +201,7 @@ private:
   // fused dft->vpoly0 path
   struct Fuse { bool on = false; int span = 0, NG = 0, KC = 0, kper = 0; double *seam = nullptr; double *cft = nullptr; int slots = 0;
                 double *cfm = nullptr; int NGRP = 0, KS = 0, qb_max = 0, qb_min = 0; int *qtab = nullptr; double2 *cfm2 = nullptr;
+                unsigned rcp_m = 0; int rcp_s = 0; // lean kernels: window starts by multiply-high and shift (walk_rcp); 0 = none
                 FusedBlock *blk_dev = nullptr; int blk_cap = 0; WalkStart *wst_dev = nullptr; // (two halves each)
                 // sub-blocked form (fused_fast_kernel<.., SPLIT>): nsub sub-blocks of Vs samples per block, component spectra
                 int nsub = 0, Vs = 0; double2 *Gs = nullptr; };

@@ -8,9 +8,9 @@
 //     for block ranges it has checked (fused_fast_range); other blocks go to fused_kernel;
 //   * the polyphase stage walks TILES (16 output residues x 4 periods = one accumulator pair) in group-major order, each
 //     wave a contiguous range of them: the coefficient tile changes only when the residue group does (double-buffered,
-//     prefetched a group ahead), the window start of a group comes from a host table instead of an integer division
-//     per lane, every store is issued straight after its tile under a per-lane range test (no deferred-store state,
-//     no per-step validity masks, no skip loops);
+//     requested one tile ahead of the switch), the window start of a group is a multiply-high by a host-made reciprocal
+//     instead of an integer division per lane, every store is issued straight after its tile under a per-lane range test
+//     (no deferred-store state, no per-step validity masks, no skip loops);
 //   * the next tile's samples are always prefetched (clamped address), so the wait before a tile's MFMA chain is for
 //     reads issued one whole tile earlier.
 // The old kernel spent ~1200 integer / 1650 scalar instructions per wave and had 1000+ SGPR spill moves in its code;
@@ -114,8 +114,8 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   // ahead of the input loads, whose latency covers them, and kept across the transforms.  The other instances have no scalar
   // registers to spare there (their transforms run at 96 - 106 of them): they request the record behind the last transform,
   // under the image writes.
-  // EARLY_TILES: each round's first two coefficient tiles are requested ahead of the barrier(s) in front of its image.  Not in
-  // the sub-blocked forms: at 252 - 256 vector registers the tiles would spill component 0.
+  // EARLY_TILES: each round's first coefficient tile is requested ahead of the barrier(s) in front of its image.  Not in
+  // the sub-blocked forms: at 252 - 256 vector registers the tile would spill component 0.
   constexpr bool TAB_AT_START = LOG2P == LOG2N - 1 && !SPLIT, EARLY_TILES = !SPLIT;
   // round A's request: ahead of the image writes where the registers allow it (7 k-steps), else between them and the barrier
   constexpr bool TILES_A_FIRST = TAB_AT_START && EARLY_TILES && KS <= 7;
@@ -281,18 +281,15 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
   const int rloc = 4 * bq + hi; // this lane's output residue within a 16-residue group
   const int ngrp = a.NGRP;
   const double2 *const cfm_lane = a.cfm2 + lane;
-  const int *const qtab_lane = a.qtab + bq;
 
-  // Coefficient tiles: current group, next group (in flight).  The window start of a group comes with its tile (odd KS: spare
-  // half of the last 16-byte element) and stays a double until the group becomes current, so that nothing waits for the
-  // tile load at the point where it is issued.
+  // Coefficient tiles: current group, next group (in flight during the current group's last tile).  Nothing else rides on these
+  // loads: the window start of a group is arithmetic (window_start below), so the only instructions that wait for a tile are
+  // the ones that use its coefficients.
   // (Measured and NOT kept, round 3: two register sets used alternately group by group, all four (set, sample buffer)
   // combinations spelled out so that no set is ever copied and no s_waitcnt vmcnt(0) sits behind the prefetch -- 168 VGPRs
   // with 19 spilled across round A, 2.37 against 1.96 ms.  The kernel has no registers to spare at three workgroups per CU.)
   double cc[KS], cn[KS];
-  double qcd = 0.0, qnd = 0.0;
-  int qci = 0, qni = 0;
-  auto load_tile = [&](int gg, double (&c_)[KS], double &qd_, int &qi_) {
+  auto load_tile = [&](int gg, double (&c_)[KS]) {
     constexpr int KSP = (KS + 1) / 2;
     const double2 *cp = cfm_lane + gg * (KSP * 64); // uniform offset; two k-steps per 16-byte load
 #pragma unroll
@@ -300,15 +297,12 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       const double2 d = cp[s2 * 64];
       c_[2 * s2] = d.x;
       if (2 * s2 + 1 < KS) c_[2 * s2 + 1] = d.y;
-      else qd_ = d.y;
     }
-    if (!(KS & 1)) qi_ = qtab_lane[gg * 4];
   };
-  // EARLY_TILES: a round's first two tiles are requested AHEAD of the barrier in front of its LDS image: the group comes from the
+  // EARLY_TILES: a round's first tile is requested AHEAD of the barrier in front of its LDS image: the group comes from the
   // table, the registers are dead there, and only the first `fill` needs the image.  Unconditional (a wave without tiles has g = 0).
   auto request_tiles = [&](const RoundStart &rs) {
-    load_tile(rs.g, cc, qcd, qci);
-    load_tile(min(rs.g + 1, ngrp - 1), cn, qnd, qni); // (clamped: see the group switch below)
+    load_tile(rs.g, cc);
   };
   if constexpr (!TAB_AT_START) fetch_table();
   if constexpr (TILES_A_FIRST) request_tiles(rsA); // behind the inverse transform's last exchange, ahead of the image and its barrier
@@ -439,7 +433,14 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
     // last residue group can hold residues >= polyL (polyL not a multiple of 16): its lanes get the dropped offset there.
     const int lane_off0 = __mul24(lane_ib, frame_bytes); // |lane_ib| < 2^23
     const bool lane_dead_last = 16 * (ngrp - 1) + rloc >= pl;
-    auto qof = [&](double qd_, int qi_) { return (KS & 1) ? (int)qd_ : qi_; };
+    // q(group, this lane's block) + lane_li (kernels.hpp, walk_q_table / walk_q_rcp): a handful of 32-bit vector instructions where
+    // a group becomes current, no memory access -- as a value that came with the coefficient tile (or from qtab) its use was a
+    // wait for every vector-memory operation in flight, the output stores of the tiles before it among them
+    auto window_start = [&](int gg) {
+      unsigned num = (unsigned)a.at0 + (unsigned)((16 * gg + 4 * bq) * step);
+      if (gg == ngrp - 1 && (pl & 15)) num = 16 * gg + 4 * bq >= pl ? (unsigned)a.at0 : num; // uniform: idle blocks of a partial last group
+      return walk_q_rcp(num, a.rcp_m, a.rcp_s) + lane_li;
+    };
 
     double2 x0[KS], x1[KS];
     auto fill = [&](double2 (&x)[KS], int q, int pstep) {
@@ -449,8 +450,11 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       for (int s = 0; s < KS; ++s) x[s] = xp[4 * s];
     };
     // (lane_li is added where qc changes, at the group switch: one vector add per tile for the window address, as before)
-    int qc = qof(qcd, qci) + lane_li;
+    int qc = window_start(g);
     fill(x0, qc, pc);
+    // the round's first tile has arrived before the loop is entered: left to the first use inside the loop, the wait (counted from
+    // the loop's entry) stands in every tile, where it counts output stores as if they were this load
+    asm volatile("" : "+v"(cc[KS - 1]));
 
     int left = rs.n;
     // one tile: prefetch the next tile's samples into `xn`, run the two accumulation chains on `xc`, store
@@ -466,15 +470,20 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       int pnext = pc + 4, pend_next = pend;
       if (wrap != 0 && left > 1) { // uniform.  Volatile so that it STAYS a branch: as a select the conversion runs in every tile and the
                           // tile right behind a switch waits for the tile load that was just issued
-        if constexpr (KS & 1) asm volatile("v_cvt_i32_f64 %0, %1" : "=v"(qc) : "v"(qnd));
-        else asm volatile("v_mov_b32 %0, %1" : "=v"(qc) : "v"(qni));
-        qc += lane_li;
+        qc = window_start(gnext);
+        asm volatile("" : "+v"(qc)); // (keeps the arithmetic inside the branch)
         // the next group's first period and column steps: they differ from this group's only where a run of groups ends
         // (WalkRound: twice per round at most, never in the uniform walk), so a group switch costs two scalar compares
         // (walk_next_group, on the table's run values)
         if (gnext == rs.b2) p0 = rs.p02, pend_next = rs.pe2;
         else if (gnext == rs.b1) p0 = rs.p01, pend_next = rs.pe1;
         pnext = p0;
+        // The next group's coefficient tile, requested at the head of this group's last tile: between the request and the copy at
+        // the tile's end lies exactly one output store on every path, so the waits of the copy are counted for the loads alone
+        // (vmcnt = the loads still behind + that store).  (`cn` is dead here: the previous switch copied it.  Requested a whole
+        // group ahead, behind the copy, the loads had the group's stores behind them, one per tile, which the compiler cannot
+        // count: its vmcnt(1) in front of the last copy then waited for every store but the newest.)
+        load_tile(gnext, cn);
       }
       fill(xn, qc, left > 1 ? pnext : pc); // after the last tile: a harmless re-read
       double accA = 0.0, accB = 0.0;
@@ -531,25 +540,21 @@ __device__ __forceinline__ void fused_fast_body(const FusedArgs &a, const FastIo
       if (wrap != 0 && left > 1) { // uniform: the group switches
 #pragma unroll
         for (int s = 0; s < KS; ++s) asm volatile("v_mov_b64 %0, %1" : "=v"(cc[s]) : "v"(cn[s]));
-        __builtin_amdgcn_sched_barrier(0);
-        // The copy is spelled out and fenced so that `cn`'s registers are dead before the next tile load is issued and the load
-        // can land in them directly.  (As plain assignments the copy materialises at the END of the block, behind the load:
-        // the compiler then lands the tile in scratch registers and moves it into `cn` behind an s_waitcnt vmcnt(0) right
-        // after issuing it -- a full L2 round trip, and a drain of the output stores, at every group switch.)  The load is
-        // unconditional for the same reason (clamped group index: past the wave's last group a harmless re-read).
-        load_tile(min(gnext + 1, ngrp - 1), cn, qnd, qni);
       }
       g = gnext;
       pc = pnext;
       pend = pend_next;
       --left;
     };
-    while (true) {
+    // Pairs of tiles in a loop with ONE exit, an odd last tile behind it.  (With a second exit between the two tiles the compiler
+    // routes both through one block that also leads back to the loop's head -- an edge that is never taken, on which the reads
+    // into `x1` are still pending: every register it reuses from `x1` for an address in the first tile then costs an
+    // s_waitcnt lgkmcnt(0) there, in the middle of the tile's MFMA chain.)
+    while (left >= 2) {
       tile(x0, x1);
-      if (left == 0) break;
       tile(x1, x0);
-      if (left == 0) break;
     }
+    if (left != 0) tile(x0, x1);
   };
 
   const bool run = fb.cnt > 0;
@@ -762,16 +767,20 @@ size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int 
   size_t n = 0;
   if (fb.cnt <= 0) return 0;
   const WalkStart ws = fused_walk_start(fb, ngrp, pl); // what fused_prep_kernel puts beside the entry, and all the kernels start from
+  WalkRcp rcp = {0, 0, 0};
+  const bool have_rcp = walk_rcp(p.at0, step, pl, rcp); // (without one the engine refuses the lean kernels: the plain quotient then)
   for (int round = 0; round < 2; ++round) {
     const WalkStartRound &r = ws.r[round];
     const int kb = r.kb, cnt = r.cnt;
     for (int wave = 0; wave < 4; ++wave) {
       int g = r.w[wave].g, pc = r.w[wave].pc, pend = r.w[wave].pend, p0 = pc & 3;
-      for (int left = r.w[wave].n; left > 0; --left) {
+      for (int left = r.w[wave].n; left > 0; --left) { // (the kernel takes them in pairs and an odd last one: the same sequence)
         for (int lane = 0; lane < 64; ++lane) {
           const int hi = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3, rloc = 4 * bq + hi;
-          const long long a0 = p.at0 + (long long)(16 * g + 4 * bq) * step; // qtab: window start of the 4-residue block
-          const int li = walk_lane_li(fb.base_li, kb, hi, jq, step) + int(a0 / pl) + pc * step;
+          // window start of the 4-residue block as poly_round's window_start forms it: numerator, multiply-high, shift
+          const unsigned num = unsigned(p.at0) + unsigned(walk_q_rb(g, bq, pl) * step);
+          const int q = have_rcp ? walk_q_rcp(num, rcp.m, rcp.s) : walk_q_table(p.at0, step, pl, g, bq);
+          const int li = walk_lane_li(fb.base_li, kb, hi, jq, step) + q + pc * step;
           const int ib = walk_lane_ib(fb.irel_lo, kb, jq, rloc, pl) + 16 * g + pc * pl;
           if (n < cap) {
             int *o = slots + 7 * n;
@@ -791,6 +800,18 @@ size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int 
     }
   }
   return n;
+}
+
+// the window start of (group, block) both ways: as the lean kernels compute it and as qtab holds it; false = no reciprocal
+bool fused_window_start_host(long long at0, int step, int pl, int g, int bq, int *arith, int *table, unsigned *rcp3)
+{
+  WalkRcp r;
+  if (!walk_rcp(at0, step, pl, r)) return false;
+  const unsigned num = unsigned(at0) + unsigned(walk_q_rb(g, bq, pl) * step);
+  *arith = walk_q_rcp(num, r.m, r.s);
+  *table = walk_q_table(at0, step, pl, g, bq);
+  rcp3[0] = r.m, rcp3[1] = unsigned(r.s), rcp3[2] = r.nmax;
+  return true;
 }
 
 void fused_walk_start_host(const FusedPrepArgs &p, int k, int *out56)

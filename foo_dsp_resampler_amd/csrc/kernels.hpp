@@ -247,6 +247,41 @@ __host__ __device__ inline void walk_seek(const WalkRound &r, int t, int &g, int
 // walk_lane_ib + 16 g + pc * polyL of the block, kept when that lies in [0, walk_round_cnt).
 __host__ __device__ inline int walk_lane_li(int base_li, int kb, int hi, int jq, int step) { return base_li + hi + (kb + jq) * step; }
 __host__ __device__ inline int walk_lane_ib(int irel_lo, int kb, int jq, int rloc, int pl) { return (kb + jq) * pl + rloc - irel_lo; }
+// q(g, bq): the window start of the 4-residue block rb = 16 g + 4 bq within its period, (at0 + rb * step) / polyL; an idle block
+// of a partial last group (rb >= polyL: all-zero coefficients, any in-range window will do) takes block 0's.  The host table
+// (qtab) holds these values for the generic kernel and polymf_kernel.  The lean kernels compute them where a group becomes
+// current, with no memory access: the quotient is the high half of numerator x m, shifted right by s (WalkRcp, chosen by
+// walk_rcp so that it is exact for every numerator up to nmax, the largest one a launch can form).
+__host__ __device__ inline int walk_q_rb(int g, int bq, int pl)
+{
+  const int rb = 16 * g + 4 * bq;
+  return rb >= pl ? 0 : rb;
+}
+__host__ __device__ inline int walk_q_table(long long at0, int step, int pl, int g, int bq)
+{
+  return int((at0 + (long long)walk_q_rb(g, bq, pl) * step) / pl);
+}
+struct WalkRcp { unsigned m; int s; unsigned nmax; };
+__host__ __device__ inline int walk_q_rcp(unsigned num, unsigned m, int s) { return int(unsigned(((unsigned long long)num * m) >> 32) >> s); }
+// m = ceil(2^(32 + s) / polyL) with the smallest s for which floor(num * m / 2^(32 + s)) = floor(num / polyL) for all num <= nmax:
+// num * m / 2^(32 + s) = num / polyL + num * e / (polyL * 2^(32 + s)) with e = m * polyL - 2^(32 + s) in [0, polyL), and the second
+// term cannot carry the first over an integer while it is below 1 / polyL, i.e. while nmax * e < 2^(32 + s).  False where no
+// 32-bit multiplier does it (polyL = 1 among them: m would be 2^32), or the numerators do not fit 31 bits.
+inline bool walk_rcp(long long at0, int step, int pl, WalkRcp &r)
+{
+  if (at0 < 0 || step < 1 || pl < 2) return false;
+  const long long nmax = at0 + (long long)((pl - 1) & ~3) * step;
+  if (nmax > 0x7fffffffLL) return false;
+  for (int s = 0; s < 31; ++s) {
+    const unsigned long long pow = 1ull << (32 + s), m = (pow + pl - 1) / pl, e = m * pl - pow;
+    if (m > 0xffffffffull) break;
+    if ((unsigned long long)nmax * e < pow) {
+      r = WalkRcp{unsigned(m), s, unsigned(nmax)};
+      return true;
+    }
+  }
+  return false;
+}
 // outputs of the block that a round up to period ke may store: the round ends at period ke for the groups that start at 0
 // and at ke + 1 for the others (a group that starts at 0 has exact column steps there and never reaches period ke)
 __host__ __device__ inline int walk_round_cnt(const FusedBlock &fb, const FusedWalk &w, int ke, int pl)
@@ -438,6 +473,8 @@ struct FusedArgs {
   const int *qtab;       // matrix-pipe variant: window start (at0 + rb*step)/polyL of every 4-residue block rb = 4*i, [NGRP*4]
   const double2 *cfm2;   // the same A operands two k-steps per 16-byte element: [group][(KS + 1) / 2][lane] (lean kernel)
   const WalkStart *wst = nullptr; // [nblocks] beside blk: the tile walk's start states (lean kernels only)
+  unsigned rcp_m = 0;    // lean kernels: the window start of a 4-residue block by multiply-high and shift (WalkRcp); a launch
+  int rcp_s = 0;         // of theirs with rcp_m = 0 is refused
 };
 
 // Lean fast path of the matrix-pipe variant (fused_fast.hip): both ends are plain interleaved frames in one buffer each
@@ -521,6 +558,9 @@ hipError_t launch_fused_prep(const FusedPrepArgs &p, FusedBlock *out, hipStream_
 size_t fused_walk_enumerate(const FusedPrepArgs &p, int k, long long *head, int *slots, size_t cap);
 // host only (test hook): entry k's WalkStart record as 56 ints
 void fused_walk_start_host(const FusedPrepArgs &p, int k, int *out56);
+// host only (test hook): q(g, bq) as the lean kernels compute it (walk_q_rcp) and as qtab holds it (walk_q_table), with the
+// multiplier, shift and largest numerator of walk_rcp in rcp3; false where walk_rcp finds no multiplier
+bool fused_window_start_host(long long at0, int step, int pl, int g, int bq, int *arith, int *table, unsigned *rcp3);
 
 // standalone rational polyphase stage on the matrix pipe (polymf.hip)
 struct PolyMfArgs {

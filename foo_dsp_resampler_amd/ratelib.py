@@ -14,7 +14,7 @@ EXPECTED_SYMBOLS = [
     "init_ratelib", "close_ratelib", "RR_open", "RR_flow", "RR_push", "RR_pull", "RR_drain", "RR_close", "RR_strerror",
     "RRX_open_batch", "RRX_open_batch_on", "RRX_device", "RRX_push_device", "RRX_pull_device", "RRX_flow_device", "RRX_push_strided", "RRX_pull_strided",
     "RRX_set_stream", "RRX_sync", "RRX_profile", "RRX_profile_read", "RRX_profile_report", "RRX_debug_fail_alloc",
-    "RRX_debug_tile_walk", "RRX_debug_walk_start",
+    "RRX_debug_tile_walk", "RRX_debug_walk_start", "RRX_debug_window_start",
     "RRX_open_batch_fmt", "RRX_format", "RRX_push_double", "RRX_pull_double", "RRX_flow_double", "RRX_push_device_double",
     "RRX_pull_device_double", "RRX_flow_device_double",
     "RRX_push_samples", "RRX_pull_samples", "RRX_flow_samples", "RRX_push_device_samples", "RRX_pull_device_samples",
@@ -210,6 +210,8 @@ def lib():
             L.RRX_debug_tile_walk.restype = C.c_longlong
         if hasattr(L, "RRX_debug_walk_start"):  # (likewise)
             L.RRX_debug_walk_start.argtypes = [P(WalkGeom), C.c_int, P(WalkStart)]
+        if hasattr(L, "RRX_debug_window_start"):  # (likewise)
+            L.RRX_debug_window_start.argtypes = [P(WalkGeom), C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_uint)]
         for n in ("RRX_isamp_max", "RRX_available"):
             getattr(L, n).argtypes = [vp]
             getattr(L, n).restype = sz

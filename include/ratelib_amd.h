@@ -130,6 +130,15 @@ typedef struct RRX_walk_start {
 } RRX_walk_start;
 int RRX_debug_walk_start(const RRX_walk_geom *geom, int k, RRX_walk_start *out);
 
+/* Test hook, as above (-1 unless RSMP_TEST_HOOKS is set): the window start of the 4-residue block `bq` (0 .. 3) of 16-residue
+ * group `group` within its period, both ways.  *arith is what the lean fused kernels compute where a group becomes current:
+ * the numerator at0 + rb * step (rb = 16 group + 4 bq, 0 for an idle block rb >= polyL), multiplied high by rcp[0] and shifted
+ * right by rcp[1]; *table is the entry of the host table that the other kernels read, the plain quotient by polyL.  rcp[2] is
+ * the largest numerator a launch of this geometry can form; the multiplier and shift are chosen to be exact up to it.  Only
+ * at0, polyL and step of the geometry are used.  Returns 0, or -2 where no such multiplier exists (the engine then refuses
+ * the lean kernels with RR_INTERNAL) or group / bq lie outside the stage's groups. */
+int RRX_debug_window_start(const RRX_walk_geom *geom, int group, int bq, int *arith, int *table, unsigned rcp[3]);
+
 /* Sample formats.  A handle gets its format when it is opened and keeps it: every handle opened by the calls above is
  * RRX_FMT_FLOAT (interleaved float32, fb_sample_t).  An RRX_FMT_DOUBLE handle takes and gives interleaved float64 frames
  * at both ends; the chain in between is the same fp64 arithmetic, stage kernels and geometry as on a float handle of the

@@ -17,7 +17,18 @@ the kernels that exist in only one; exit status 1 if any common kernel differs.
 prints, for every kernel of one file whose name contains the substring, its register counts, scratch size and occupancy
 (the file's metadata), and for every s_barrier that is followed by a matrix instruction before the next barrier -- the
 start of a polyphase round -- what lies between the two: instructions, integer-division sequences (v_rcp_iflag), loads
-issued, and every s_waitcnt."""
+issued, and every s_waitcnt.
+
+    python tools/isa_compare.py --meta A.s B.s
+
+prints one line per kernel of A with the register counts, ScratchSize and occupancy (waves per SIMD) of both files, and marks
+(<<<<) the kernels whose scratch is not zero in B or whose occupancy changed.
+
+    python tools/isa_compare.py --tile-loop FILE.s substring
+
+prints, for every kernel whose name contains the substring, the skeleton of each polyphase round -- from the barrier in front of
+the round's first matrix instruction to its last matrix instruction and the store behind it: labels, branches, every s_waitcnt,
+vector-memory loads and stores, the count of matrix instructions in between -- and the number of s_waitcnt vmcnt(0) inside."""
 import re
 import sys
 
@@ -72,9 +83,72 @@ def prologue(path, sub):
     return 0
 
 
+def meta(path):
+    out, name = {}, None
+    for line in open(path):
+        m = re.match(r"^([A-Za-z_][\w$.]*):", line)
+        if m and not line.startswith(".L"):
+            name = m.group(1)
+        m = re.match(r"^; (NumVgprs|TotalNumSgprs|ScratchSize|Occupancy): (\d+)", line)
+        if m and name:
+            out.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    return out
+
+
+def meta_compare(pa, pb):
+    a, b = meta(pa), meta(pb)
+    bad = 0
+    for k in sorted(a):
+        x, y = a[k], b.get(k)
+        if y is None:
+            print("only in A: %s" % k)
+            continue
+        flag = "" if y["ScratchSize"] == 0 and y["Occupancy"] == x["Occupancy"] else "  <<<<"
+        bad += bool(flag)
+        print("%-78s vgpr %3d -> %3d  sgpr %3d -> %3d  scratch %d -> %d  occupancy %d -> %d%s" %
+              (k, x["NumVgprs"], y["NumVgprs"], x["TotalNumSgprs"], y["TotalNumSgprs"], x["ScratchSize"], y["ScratchSize"],
+               x["Occupancy"], y["Occupancy"], flag))
+    print("%d kernels, %d with scratch in B or another occupancy" % (len(a), bad))
+    return 1 if bad else 0
+
+
+def tile_loop(path, sub):
+    keep = re.compile(r"(\.L\d+:|s_waitcnt|s_cbranch|s_branch|buffer_store|global_load|global_store|buffer_load|s_barrier|v_mul_hi_u32|v_cvt_i32_f64)")
+    for name, body in sorted(functions(path).items()):
+        if sub not in name:
+            continue
+        print(name)
+        bars = [i for i, s in enumerate(body) if s.startswith("s_barrier")] + [len(body)]
+        rnd = 0
+        for b, nb in zip(bars, bars[1:]):
+            mf = [i for i in range(b, nb) if body[i].startswith("v_mfma")]
+            if not mf:
+                continue
+            rnd += 1
+            end = next((i for i in range(mf[-1], nb) if "store" in body[i]), mf[-1])
+            print("  round %d: instructions %d .. %d, %d matrix instructions" % (rnd, b, end, len(mf)))
+            n = 0
+            for i in range(b, end + 1):
+                if body[i].startswith("v_mfma"):
+                    n += 1
+                    continue
+                if keep.match(body[i]):
+                    if n:
+                        print("      ... %d v_mfma ..." % n)
+                        n = 0
+                    print("    %5d  %s" % (i, body[i]))
+            inside = [i for i in range(mf[0], mf[-1]) if body[i].startswith("s_waitcnt") and "vmcnt(0)" in body[i]]
+            print("  round %d: s_waitcnt vmcnt(0) between the first and the last matrix instruction: %d" % (rnd, len(inside)))
+    return 0
+
+
 def main():
     if sys.argv[1] == "--prologue":
         return prologue(sys.argv[2], sys.argv[3])
+    if sys.argv[1] == "--meta":
+        return meta_compare(sys.argv[2], sys.argv[3])
+    if sys.argv[1] == "--tile-loop":
+        return tile_loop(sys.argv[2], sys.argv[3])
     a, b = functions(sys.argv[1]), functions(sys.argv[2])
     subs = sys.argv[3:]
     bad = 0
