@@ -13,7 +13,8 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       true_peak_device, tracks_true_peak_device, TRUE_PEAK_FILTERS, RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS,
                       k_weighting, K_WEIGHTING_48K, loudness_device, tracks_loudness_device, loudness_gate, loudness_gate_device, integrated_lufs,
                       loudness_normalizing_gain, loudness_blocks_device, loudness_gate_groups_device, loudness_range_device, loudness_range_lu,
-                      loudness_meter_device, tracks_true_peak_window_device, tracks_loudness_window_device, RRX_LOUDNESS_WIN_STATE)
+                      loudness_meter_device, tracks_true_peak_window_device, tracks_loudness_window_device, RRX_LOUDNESS_WIN_STATE,
+                      limit_device, tracks_limit_device, limit_work_doubles, RRX_LIMIT_MAX_LOOKAHEAD, RRX_LIMIT_MAX_HOLD)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
@@ -24,4 +25,5 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "true_peak_device", "tracks_true_peak_device", "TRUE_PEAK_FILTERS", "RRX_TP_MAX_PHASES", "RRX_TP_MAX_TAPS",
            "k_weighting", "K_WEIGHTING_48K", "loudness_device", "tracks_loudness_device", "loudness_gate", "loudness_gate_device", "integrated_lufs",
            "loudness_normalizing_gain", "loudness_blocks_device", "loudness_gate_groups_device", "loudness_range_device", "loudness_range_lu",
-           "loudness_meter_device", "tracks_true_peak_window_device", "tracks_loudness_window_device", "RRX_LOUDNESS_WIN_STATE"]
+           "loudness_meter_device", "tracks_true_peak_window_device", "tracks_loudness_window_device", "RRX_LOUDNESS_WIN_STATE",
+           "limit_device", "tracks_limit_device", "limit_work_doubles", "RRX_LIMIT_MAX_LOOKAHEAD", "RRX_LIMIT_MAX_HOLD"]

@@ -11,6 +11,7 @@
 #include "measure_window.hpp"
 #include "tracks.hpp"
 #include "true_peak.hpp"
+#include "limit.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1100,6 +1101,154 @@ int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d
   a.src_double = src_format == RRX_FMT_DOUBLE;
   a.flush = 1;
   return rsmp::launch_true_peak(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// r and m of every stream (limit.hip), frames + taps + lookahead doubles each: 0 for what the data calls refuse
+size_t RRX_limit_work_doubles(int nstreams, size_t frames, int taps, size_t lookahead)
+{
+  static_assert(RRX_LIMIT_MAX_LOOKAHEAD == rsmp::kLimitMaxLookahead && RRX_LIMIT_MAX_HOLD == rsmp::kLimitMaxHold, "the header's constants are the kernels'");
+  if (nstreams < 1 || taps < 1 || taps > RRX_TP_MAX_TAPS || lookahead < 1 || lookahead > RRX_LIMIT_MAX_LOOKAHEAD) return 0;
+  const size_t most = size_t(1) << 60, per = 2 * size_t(nstreams); // (2^32 at the most)
+  if (frames >= most / per) return 0;
+  const size_t each = frames + size_t(taps) + lookahead;               // below 2^60 + 2^11
+  return each >= (most + per - 1) / per ? 0 : per * each;
+}
+
+namespace {
+
+// the limiter's own arguments, shared by the three calls: ceiling, lookahead, hold, the formats and the work buffer (whose size is
+// RRX_limit_work_doubles(nstreams, frames, taps, lookahead)); a.f is set already
+int limit_common(int src_format, int dst_format, int nstreams, size_t frames, double ceiling, size_t lookahead, size_t hold, double *work,
+                 size_t work_doubles, rsmp::LimitArgs &a)
+{
+  if (dst_format != RRX_FMT_FLOAT && dst_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  if (!std::isfinite(ceiling) || !(ceiling > 0)) return RR_INVPARAM;
+  if (lookahead < 1 || lookahead > RRX_LIMIT_MAX_LOOKAHEAD || hold > RRX_LIMIT_MAX_HOLD) return RR_INVPARAM;
+  const size_t need = RRX_limit_work_doubles(nstreams, frames, a.f.taps, lookahead);
+  if (!need || !work || work_doubles < need) return RR_INVPARAM;
+  a.work = work;
+  a.work_stride = (unsigned long long)frames + (unsigned)a.f.taps + lookahead;
+  a.lookahead = (unsigned)lookahead;
+  a.hold = (unsigned)hold;
+  a.ceiling = ceiling;
+  a.inv_l = 1.0 / (double)lookahead;
+  a.src_double = src_format == RRX_FMT_DOUBLE;
+  a.dst_double = dst_format == RRX_FMT_DOUBLE;
+  return RR_OK;
+}
+
+// the overlap rule of the limiter: the destination is exactly the source, with its format and pitch, or shares no byte with it
+bool limit_overlap_ok(const void *src, uintptr_t src_bytes, const void *dst, uintptr_t dst_bytes, bool same_layout)
+{
+  const uintptr_t x = reinterpret_cast<uintptr_t>(src), y = reinterpret_cast<uintptr_t>(dst);
+  if (x == y) return same_layout;
+  return x < y ? y - x >= src_bytes : x - y >= dst_bytes;
+}
+
+// RRX_limit_device / RRX_debug_limit_host: everything that can be refused from the arguments alone
+int limit_args(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams, size_t frames,
+               int nch, const double *gain, double ceiling, const double *coefs, int phases, int taps, size_t lookahead, size_t hold,
+               double *reduction, unsigned long long *limited, double *work, size_t work_doubles, rsmp::LimitArgs &a)
+{
+  int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  double none = 0.0;
+  rsmp::FinishArgs f; // the sizes, strides and overflow rules of the source are RRX_finish_device's, measuring only
+  rc = finish_args(src_format, src, src_stride, 0, nullptr, 0, nstreams, frames, nch, gain, 0, 0, 0, &none, nullptr, f);
+  if (rc != RR_OK) return rc;
+  if (!dst) return RR_INVPARAM;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch);
+  if (nstreams > 1 && (dst_stride < frames || dst_stride > most / size_t(nstreams))) return RR_INVPARAM;
+  rc = limit_common(src_format, dst_format, nstreams, frames, ceiling, lookahead, hold, work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  const uintptr_t per = uintptr_t(nch), rows = uintptr_t(nstreams - 1); // samples below 2^60 each: no wrap
+  const uintptr_t sb = (rows * src_stride + frames) * per * (a.src_double ? 8 : 4), db = (rows * dst_stride + frames) * per * (a.dst_double ? 8 : 4);
+  if (!limit_overlap_ok(src, sb, dst, db, src_format == dst_format && (nstreams == 1 || src_stride == dst_stride))) return RR_INVPARAM;
+  a.src = src;
+  a.dst = dst;
+  a.gain = gain;
+  a.reduction = reduction;
+  a.limited = limited;
+  a.tracks = nullptr;
+  a.src_stride = f.src_stride;
+  a.dst_stride = nstreams > 1 ? (unsigned long long)dst_stride * nch : 0;
+  a.frames = frames;
+  a.nstreams = nstreams;
+  a.nch = nch;
+  return RR_OK;
+}
+
+} // namespace
+
+// The true-peak limiter on device-resident frames (limit.hip).  Refusals first, as in RRX_true_peak_device.
+int RRX_limit_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int dst_format, void *d_dst,
+                     size_t dst_stride, int nstreams, size_t frames, int nch, const double *d_gain, double ceiling, const double *coefs,
+                     int phases, int taps, size_t lookahead, size_t hold, double *d_reduction, unsigned long long *d_limited, double *d_work,
+                     size_t work_doubles)
+{
+  rsmp::LimitArgs a;
+  const int rc = limit_args(src_format, d_src, src_stride, dst_format, d_dst, dst_stride, nstreams, frames, nch, d_gain, ceiling, coefs, phases,
+                            taps, lookahead, hold, d_reduction, d_limited, d_work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_limit(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_limit_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams,
+                         size_t frames, int nch, const double *gain, double ceiling, const double *coefs, int phases, int taps,
+                         size_t lookahead, size_t hold, double *reduction, unsigned long long *limited, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LimitArgs a;
+  const int rc = limit_args(src_format, src, src_stride, dst_format, dst, dst_stride, nstreams, frames, nch, gain, ceiling, coefs, phases, taps,
+                            lookahead, hold, reduction, limited, work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  if (frames) rsmp::limit_host(a);
+  return RR_OK;
+}
+
+// RRX_limit_device per track of a ragged batch (limit.hip).  Refusals first, as in RRX_tracks_true_peak_device.
+int RRX_tracks_limit_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format, const void *d_rows,
+                            int dst_format, void *d_dst_rows, size_t row_frames, const double *d_gain, double ceiling, const double *coefs,
+                            int phases, int taps, size_t lookahead, size_t hold, double *d_reduction, unsigned long long *d_limited,
+                            double *d_work, size_t work_doubles)
+{
+  rsmp::LimitArgs a;
+  if (!d_tracks || !d_rows || !d_dst_rows || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  rc = limit_common(src_format, dst_format, ntracks, row_frames, ceiling, lookahead, hold, d_work, work_doubles, a);
+  if (rc != RR_OK) return rc;
+  const uintptr_t samples = uintptr_t(ntracks) * row_frames * uintptr_t(nch);
+  if (!limit_overlap_ok(d_rows, samples * (a.src_double ? 8 : 4), d_dst_rows, samples * (a.dst_double ? 8 : 4), src_format == dst_format))
+    return RR_INVPARAM;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  a.src = d_rows;
+  a.dst = d_dst_rows;
+  a.gain = d_gain;
+  a.reduction = d_reduction;
+  a.limited = d_limited;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src_stride = a.dst_stride = 0;
+  a.frames = row_frames;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  return rsmp::launch_limit(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
 namespace {

@@ -23,6 +23,7 @@ EXPECTED_SYMBOLS = [
     "RRX_finish_device", "RRX_debug_finish_host",
     "RRX_finish_shaped_device", "RRX_debug_finish_shaped_host", "RRX_tracks_finish_shaped_device",
     "RRX_true_peak_device", "RRX_debug_true_peak_host", "RRX_tracks_true_peak_device",
+    "RRX_limit_work_doubles", "RRX_limit_device", "RRX_tracks_limit_device", "RRX_debug_limit_host",
     "RRX_loudness_device", "RRX_loudness_work_doubles", "RRX_debug_loudness_host", "RRX_tracks_loudness_device",
     "RRX_loudness_gate_device", "RRX_debug_loudness_gate_host",
     "RRX_loudness_blocks_device", "RRX_loudness_groups_work_doubles", "RRX_loudness_gate_groups_device", "RRX_loudness_range_groups_device",
@@ -56,6 +57,7 @@ at 44.1 kHz only; for another rate the caller brings coefficients: wherever a na
 finite floats."""
 
 RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS = 8, 16
+RRX_LIMIT_MAX_LOOKAHEAD, RRX_LIMIT_MAX_HOLD = 1024, 4096
 RRX_LOUDNESS_WIN_STATE = 16            # doubles per (track, channel) of tracks_loudness_window_device's state: S, Z, C, E, three zeros
 
 
@@ -241,6 +243,14 @@ def lib():
             L.RRX_true_peak_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_true_peak_host.argtypes = host
             L.RRX_tracks_true_peak_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, C.c_int, C.c_int, vp, vp]
+        if hasattr(L, "RRX_limit_device"):  # (as above)
+            host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_double, vp, C.c_int, C.c_int, sz, sz, vp, vp, vp, sz]
+            L.RRX_limit_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_limit_host.argtypes = host
+            L.RRX_tracks_limit_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, sz, vp, C.c_double, vp, C.c_int,
+                                                  C.c_int, sz, sz, vp, vp, vp, sz]
+            L.RRX_limit_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz]
+            L.RRX_limit_work_doubles.restype = sz
         if hasattr(L, "RRX_loudness_device"):  # (as above)
             u64 = C.c_ulonglong
             host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, u64, vp, sz, vp, vp, vp, sz, vp, sz]
@@ -886,7 +896,119 @@ def tracks_true_peak_device(rows, table, gain=None, filter="bs1770", true_peak=N
     return true_peak, peak
 
 
-K_WEIGHTING_48K = (1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,
+def limit_work_doubles(nstreams, frames, taps=12, lookahead=64):
+    """Doubles of work memory that limit_device / tracks_limit_device need for `nstreams` rows of `frames` frames
+    (RRX_limit_work_doubles: nstreams * 2 * (frames + taps + lookahead)); 0 for arguments the calls refuse.  Host only."""
+    return int(lib().RRX_limit_work_doubles(int(nstreams), int(frames), int(taps), int(lookahead)))
+
+
+def _limit_params(ceiling, lookahead, hold):
+    """the limiter's scalar arguments, checked as the C call checks them"""
+    ceiling, lookahead, hold = float(ceiling), int(lookahead), int(hold)
+    if not (np.isfinite(ceiling) and ceiling > 0):
+        raise ValueError("the ceiling is a finite linear level above 0")
+    if not 1 <= lookahead <= RRX_LIMIT_MAX_LOOKAHEAD:
+        raise ValueError("lookahead is 1..%d frames" % RRX_LIMIT_MAX_LOOKAHEAD)
+    if not 0 <= hold <= RRX_LIMIT_MAX_HOLD:
+        raise ValueError("hold is 0..%d frames" % RRX_LIMIT_MAX_HOLD)
+    return ceiling, lookahead, hold
+
+
+def _limit_buffers(x, out, n, frames, taps, lookahead, dev):
+    """(out, reduction preset to 1.0, limited zeroed, work) of a limiter call on `n` rows of `frames` frames"""
+    import torch
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        odt = str(out.dtype)
+        if not (odt.endswith("float32") or odt.endswith("float64")) or tuple(out.shape) != tuple(x.shape) or out.device != dev or not out.is_contiguous():
+            raise TypeError("out must be a contiguous float32 or float64 tensor of shape %r on %s" % (tuple(x.shape), dev))
+        if out.data_ptr() == x.data_ptr() and out.dtype != x.dtype:
+            raise TypeError("in place the destination has the source's dtype")
+    reduction = torch.ones((n,), dtype=torch.float64, device=dev)
+    limited = torch.zeros((n,), dtype=torch.int64, device=dev)
+    need = limit_work_doubles(n, frames, taps, lookahead)
+    if not need:
+        raise ValueError("the rows are too large for the limiter's work buffer")
+    return out, reduction, limited, torch.empty((need,), dtype=torch.float64, device=dev)
+
+
+def limit_device(x, ceiling, gain=None, lookahead=64, hold=0, filter="bs1770", out=None, stream=None):
+    """The true-peak limiter on the device (RRX_limit_device): every frame of `x` under `gain` times a gain s[n] <= 1, one per
+    frame and linked across a stream's channels, which holds |y| at `ceiling` (a linear level; exact for finite input up to one
+    rounding) and the true peak -- true_peak_device's, with `filter` -- near it.  s is the minimum of the demanded reductions
+    over a window that begins `hold` frames behind a frame and ends `lookahead` frames and the filter's length ahead of it,
+    smoothed by a box of `lookahead` frames: it starts to fall lookahead + taps - 1 frames before a peak and returns over
+    `lookahead` frames, `hold` frames behind it.  The true peak of y can exceed the ceiling by a residual that shrinks with
+    `lookahead` (below one percent at 72); measure y with true_peak_device and trim where the bound has to hold.
+
+    `x`, `gain` and `stream` are true_peak_device's.  `out`: None (a new tensor like x), x itself (in place), or a float32 /
+    float64 tensor of x's shape that shares no memory with it.  Returns (y, reduction, limited): float64 [nstreams] the
+    smallest s of each stream (1.0 where nothing was limited) and int64 [nstreams] the frames with s < 1.  The call only
+    enqueues; its work buffer comes from torch's allocator."""
+    import torch
+    shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    dt = str(x.dtype)
+    if not (dt.endswith("float32") or dt.endswith("float64")):
+        raise TypeError("%s buffer: the limiter reads float32 or float64 frames" % (x.dtype,))
+    if not x.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    phases, taps, coefs = _true_peak_filter(filter)
+    ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
+    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
+    if not getattr(x, "is_cuda", False):
+        raise TypeError("the limiter works on device tensors: the frames must be in HBM")
+    dev = x.device
+    gain = _loudness_gain(gain, nstreams, dev)
+    out, reduction, limited, work = _limit_buffers(x, out, nstreams, frames, taps, lookahead, dev)
+    if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out, reduction, limited
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_limit_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+                                  RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
+                                  RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames,
+                                  nstreams, frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling,
+                                  C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold, C.c_void_p(reduction.data_ptr()),
+                                  C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()), "RRX_limit_device")
+    return out, reduction, limited
+
+
+def tracks_limit_device(rows, table, ceiling, gain=None, lookahead=64, hold=0, filter="bs1770", out=None, stream=None):
+    """limit_device per track of a ragged batch, in one call (RRX_tracks_limit_device): `rows`, `table` and `gain` as in
+    tracks_true_peak_device; track t's frames [out_first, out_first + out_frames) of row t are limited as one whole track -- from
+    +0.0 at its first output frame, the filter's tail behind its last -- and go to the same frames of `out`: None (in place,
+    into `rows`), or a float32 / float64 tensor of rows' shape that shares no memory with it.  Frames outside the slices are
+    not written.  Returns (out, reduction [ntracks], limited [ntracks]) as limit_device.  The call only enqueues."""
+    import torch
+    dt = str(rows.dtype)
+    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
+        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
+    ntracks, row_frames, nch = rows.shape
+    _tracks_table(table, ntracks)
+    dev = rows.device
+    if table.device != dev:
+        raise TypeError("the table must be on %s" % (dev,))
+    phases, taps, coefs = _true_peak_filter(filter)
+    ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
+    gain = _loudness_gain(gain, ntracks, dev)
+    out, reduction, limited, work = _limit_buffers(rows, rows if out is None else out, ntracks, row_frames, taps, lookahead, dev)
+    if not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out, reduction, limited
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_limit_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
+                                         RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
+                                         RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), row_frames,
+                                         C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p), phases,
+                                         taps, lookahead, hold, C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()),
+                                         C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_limit_device")
+    return out, reduction, limited
+
+
+K_WEIGHTING_48K =(1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,
                    1.0, -2.0, 1.0, -1.99004745483398, 0.99007225036621)
 """The K-weighting of ITU-R BS.1770-4 at 48 kHz as published, in the order of RRX_loudness_device's `coefs`: b0, b1, b2, a1, a2 of
 the shelving stage, then of the high-pass."""
@@ -2272,6 +2394,63 @@ class Resampler:
             pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n], gain[:n], true_peak[:n], lufs[:n]
+
+    def convert_tracks_to_pcm_loudness_limited(self, tracks, dst_format, target_lufs=-14.0, max_dbtp=-1.0, lookahead_ms=1.5, hold_ms=10.0,
+                                               weights=None, shaping=None, segment=65536, dither=False, seed=0, album=None):
+        """convert_tracks_to_pcm_loudness_normalized with a true-peak LIMITER in place of the peak-bound gain: a track with a few
+        loud transients over a quiet bed reaches `target_lufs` where the static gain min(by loudness, by peak) would leave it far
+        below.  The rows are converted once and their loudness measured as there (`weights`, `album` as there); the gain is
+        10 ** ((target_lufs - L) / 20) ALONE, 1.0 where no block passed the gates.  Then tracks_limit_device limits the rows in
+        place under that gain at the ceiling 10 ** (max_dbtp / 20), with `lookahead_ms` and `hold_ms` rounded to frames of the
+        output rate and clamped to 1..RRX_LIMIT_MAX_LOOKAHEAD and 0..RRX_LIMIT_MAX_HOLD; tracks_true_peak_device measures the
+        limited rows, and trim = min(1, ceiling / max(true peak, sample peak)) -- 1.0 where that maximum is 0 or not finite --
+        removes what the limiter leaves over the ceiling between the samples; the rows are finished under `trim` as in
+        convert_tracks_to_pcm_normalized.  Everything is computed on the device, without a host synchronisation.  Returns (views,
+        peak, clipped, gain [ntracks], trim [ntracks], reduction [ntracks], limited [ntracks], lufs [ntracks]): `reduction` the
+        limiter's smallest gain, `limited` the frames it lowered, `lufs` the loudness BEFORE the gain (of t's album with `album`)."""
+        import torch
+        tracks = list(tracks)
+        if album is not None:
+            album = [int(v) for v in album]
+            if len(album) != len(tracks) or any(v < 0 for v in album):
+                raise ValueError("album is one non-negative int per track")
+        rate = int(self.cfg.out_rate)
+        ceiling = 10.0 ** (float(max_dbtp) / 20.0)
+        lookahead = min(max(int(round(float(lookahead_ms) * rate / 1000.0)), 1), RRX_LIMIT_MAX_LOOKAHEAD)
+        hold = min(max(int(round(float(hold_ms) * rate / 1000.0)), 0), RRX_LIMIT_MAX_HOLD)
+        plan, table, out = self._convert_tracks_rows(tracks)
+        n = len(tracks)
+        cur = torch.cuda.current_stream(out.device)
+        energy, hops = tracks_loudness_device(out, table, rate, stream=cur)
+        if album is None:
+            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
+            lufs, passed = integrated_lufs(result), result[:, 1] > 0
+        else:
+            nalbums = max(album) + 1
+            of = torch.tensor(album, dtype=torch.int64, device=out.device)
+            groups = torch.full((out.shape[0],), -1, dtype=torch.int32, device=out.device)  # the streams without a track are in no album
+            groups[:n] = of.to(torch.int32)
+            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
+            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
+            per_album = integrated_lufs(result)
+            lufs = torch.full((out.shape[0],), float("-inf"), dtype=per_album.dtype, device=out.device)
+            lufs[:n] = per_album[of]
+            passed = torch.zeros((out.shape[0],), dtype=torch.bool, device=out.device)
+            passed[:n] = (result[:, 1] > 0)[of]
+        by_loudness = torch.pow(10.0, (float(target_lufs) - torch.where(passed, lufs, torch.zeros_like(lufs))) / 20.0)
+        gain = torch.where(passed, by_loudness, torch.ones_like(by_loudness)).contiguous()
+        _, reduction, limited = tracks_limit_device(out, table, ceiling, gain=gain, lookahead=lookahead, hold=hold, stream=cur)
+        true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
+        m = torch.maximum(true_peak, sample_peak).amax(1)
+        ok = torch.isfinite(m) & (m > 0)
+        trim = torch.where(ok, torch.clamp(torch.full_like(m, ceiling) / torch.where(ok, m, torch.ones_like(m)), max=1.0), torch.ones_like(m)).contiguous()
+        if shaping is not None:
+            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=trim, dither=dither,
+                                                             seed=seed, stream=cur)
+        else:
+            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=trim, dither=dither, seed=seed, stream=cur)
+        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
+        return views, peak[:n], clipped[:n], gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
 
     def _streamed_under_gain(self, tracks, dst_format, window, shaping, segment, gain, dither, seed, who):
         """pass B of the streamed normalising forms: reset(), then the streamed loop, shaped or not, under the per-track gain"""

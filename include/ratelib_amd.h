@@ -543,6 +543,83 @@ int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d
                                 int src_format, const void *d_rows, size_t row_frames, const double *d_gain,
                                 const double *coefs, int phases, int taps, double *d_true_peak, double *d_peak);
 
+/* True-peak limiter: one gain per frame, linked across a stream's channels, that holds the gained frames under a ceiling where a
+ * static gain would pull the whole track down for a few transients.  The detector is RRX_true_peak_device's; the gain is a window
+ * minimum of the demanded reductions smoothed by a box of `lookahead` frames.  Nothing in it is recursive (there is no one-pole
+ * release), so every frame is independent work.  The call needs no handle.
+ *
+ * The arithmetic is part of this ABI.  Everything is fp64 and every operation is rounded on its own (no fused multiply-add).  Per
+ * stream s, with N = frames, the filter of phases x taps as in RRX_true_peak_device, D = taps - 1, c = ceiling, L = lookahead and
+ * H = hold:
+ *   g[n][ch]  = (double)x * d_gain[s]  (d_gain NULL: g = x)                                            -- RRX_finish_device's
+ *   tp[F][ch] for F in [0, N + D): RRX_true_peak_device's tp[F] on the history g[F-k], k < taps, with +0.0 before frame 0 and
+ *             behind frame N-1 (first_frame = 0, no state, flush = 1)
+ *   a[F][ch]  = fabs(g[F][ch]) for F < N, +0.0 for F >= N
+ *   lev[F]    = max over ch of max(tp[F][ch], a[F][ch]), as an unsigned 64-bit maximum on the bit patterns (a NaN lies above +inf)
+ *   r[F]      = lev[F] > c ? c / lev[F] : 1.0   (the division correctly rounded; a NaN level fails the comparison: 1.0; +inf gives
+ *             +0.0);  r[F] = 1.0 for F < 0 and F >= N + D
+ *   m[k]      = min of r[F] over F in [k - H, k + L - 1 + D],  for k in [-(L-1), N)        (a minimum: the order does not matter)
+ *   acc       = +0.0;  for i = L-1 down to 0:  acc = acc + m[n - i]
+ *   s[n]      = fmin(acc * invL, m[n]),   invL = 1.0 / (double)L computed once on the host
+ *   y[n][ch]  = g[n][ch] * s[n], stored as a double (RRX_FMT_DOUBLE) or rounded once to float32 (RRX_FMT_FLOAT)
+ * What holds, and what does not.  Every m[n-i], 0 <= i < L, covers [n, n + D], so s[n] <= r[F] for every detector frame F whose
+ * filter window contains sample n, and a[n] enters lev[n]: for finite input |y| <= c * (1 + 2^-51) in fp64, the slack being the
+ * rounding of c / lev times lev.  The fmin keeps the serial sum's rounding from lifting s[n] above m[n].  The gain starts to fall
+ * L + D frames before a peak, is fully down D frames before it, stays down H frames behind it and returns over L frames.  The
+ * TRUE peak of y is NOT strictly bounded by c: a gain that varies inside the filter's window is not a scalar factor of the
+ * filter's sum.  The overshoot that remains shrinks with L (a few percent at L = 1, below one percent at L = 72, DESIGN.md 10,
+ * "Limiter"); a caller who needs the bound measures y with RRX_true_peak_device and trims with a static gain, as
+ * convert_tracks_to_pcm_loudness_limited of the Python binding does.
+ * Results per stream, both ACCUMULATED: d_reduction[s] (double, [nstreams] on the device; the caller presets it to 1.0) takes
+ * min(what it holds, every s[n]) by an unsigned 64-bit atomic minimum on the bit pattern (s >= +0.0 and never a NaN);
+ * d_limited[s] (unsigned 64-bit, [nstreams]; the caller zeroes it) counts the frames with s[n] < 1.0.  Either may be NULL.
+ *   A NaN sample passes through as a NaN and demands no reduction where it poisons the level; +-inf demands r = +0.0 around it
+ *   (and inf * 0 leaves a NaN in its own place).  Neither faults, and the other streams are exact.
+ *   src_format and dst_format are RRX_FMT_FLOAT or RRX_FMT_DOUBLE, each on its own; integer sources are not offered.  d_dst has
+ *   the source's geometry with dst_stride.  d_dst may be exactly d_src (in place), with equal formats and equal strides only; any
+ *   other overlap of the two extents is RR_INVPARAM.
+ *   d_work: at least RRX_limit_work_doubles(nstreams, frames, taps, lookahead) doubles on the device, which is
+ *   nstreams * 2 * (frames + taps + lookahead) -- r and m, generously -- or 0 for arguments the call would refuse and for a
+ *   product of 2^60 or more (host only).  Its content after the call is unspecified.
+ *   Launches: the detector (one lane per frame F, the gained samples staged in LDS), the window minimum (LDS tiles of r),
+ *   smoothing and product (an LDS tile of m, four frames to a lane), each split over chunks of 32768 streams.  The call only enqueues: no
+ *   allocation, no host synchronisation.  coefs (a HOST pointer), layouts, the alignment of one sample, device and hip_stream with
+ *   the stream-ordering contract are RRX_true_peak_device's.
+ * Returns RR_INVPARAM, before any device is touched, for everything RRX_true_peak_device refuses of the shared arguments (source,
+ * strides, sizes, filter, device < -1), and further for d_dst NULL, an unknown dst_format, a dst_stride below frames or beyond
+ * 2^60 samples, a ceiling that is not finite or not > 0, lookahead outside 1..RRX_LIMIT_MAX_LOOKAHEAD, hold above
+ * RRX_LIMIT_MAX_HOLD, d_work NULL or work_doubles too small, and the overlap rule; RR_EXTUNINIT before init_ratelib; RR_INTERNAL for
+ * a failed launch.  frames == 0 is RR_OK and touches nothing. */
+#define RRX_LIMIT_MAX_LOOKAHEAD 1024
+#define RRX_LIMIT_MAX_HOLD      4096
+size_t RRX_limit_work_doubles(int nstreams, size_t frames, int taps, size_t lookahead);
+int RRX_limit_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
+                     int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
+                     const double *d_gain, double ceiling, const double *coefs, int phases, int taps,
+                     size_t lookahead, size_t hold, double *d_reduction, unsigned long long *d_limited,
+                     double *d_work, size_t work_doubles);
+/* RRX_limit_device per track of a ragged batch in one call.  Tables, rows and their clamping are RRX_tracks_true_peak_device's:
+ * track t is frames [out_first, out_first + out_frames) of row t of d_rows ([ntracks][row_frames][nch]), clamped to the row, and is
+ * limited as a one-stream RRX_limit_device call on that slice under d_gain[t] -- the history in front of the slice is +0.0, not the
+ * row.  The result goes to the same frames of row t of d_dst_rows, which has the same geometry and may be d_rows (then with
+ * dst_format == src_format; any other overlap is RR_INVPARAM).  Frames of the rows outside the slices are not written.
+ * d_reduction and d_limited are [ntracks].  d_work: RRX_limit_work_doubles(ntracks, row_frames, taps, lookahead) doubles.  A wrong
+ * table gives wrong samples, never an access outside the rows or d_work.  Refusals: RR_INVPARAM, before any device is touched, for
+ * a NULL table, source or destination, ntracks < 1, nch < 1, an unknown format, ntracks * row_frames * nch of 2^60 samples or
+ * more, and the filter, ceiling, lookahead, hold, work and overlap refusals of RRX_limit_device; the rest as there.
+ * row_frames == 0 is RR_OK and does nothing. */
+int RRX_tracks_limit_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                            int src_format, const void *d_rows, int dst_format, void *d_dst_rows, size_t row_frames,
+                            const double *d_gain, double ceiling, const double *coefs, int phases, int taps,
+                            size_t lookahead, size_t hold, double *d_reduction, unsigned long long *d_limited,
+                            double *d_work, size_t work_doubles);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: RRX_limit_device on HOST
+ * pointers, as serial loops over the very per-frame functions the kernels call.  Same refusals, same results. */
+int RRX_debug_limit_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride,
+                         int nstreams, size_t frames, int nch, const double *gain, double ceiling,
+                         const double *coefs, int phases, int taps, size_t lookahead, size_t hold,
+                         double *reduction, unsigned long long *limited, double *work, size_t work_doubles);
+
 /* Programme loudness (ITU-R BS.1770-4, EBU R 128): K-weighted energies of 100 ms hops per (stream, channel) of device-resident
  * frames, from which RRX_loudness_gate_device below takes the gated mean; in LUFS once the caller takes -0.691 + 10 log10.  The
  * call needs no handle and writes no sample.

@@ -1,0 +1,143 @@
+"""The limiter (RRX_limit_device: detector, window minimum, box smoothing and product, three launches) against the true-peak pass
+and the measure-only output stage on the same rows, and the true-peak overshoot it leaves.
+
+Timing.  Input: the output tensor of one bench.py step of BASELINE configs 1 (256 streams x 2 channels) and 3 (16 streams x 32
+channels), float32, as tools/perf_true_peak.py takes it.  The limiter runs out of place into a float32 tensor through the C ABI,
+with its work buffer and results allocated once, at a ceiling of half the rows' sample peak (so that it has work to do), at
+(lookahead, hold) = (72, 0) and (1024, 4096).  Everything runs on the same tensor in the same process, `--rounds` rounds
+interleaved: in every round each candidate is warmed up `--warmup` times and then timed over `--steps` calls between two HIP
+events on the stream.  The call reads the rows twice, writes them once and moves 32 bytes of work per frame.
+
+Residuals.  Noise (sigma 0.25) and an fs/4 tone whose amplitude is modulated between 0.2 and 1.0, 48000 frames x 2 channels each,
+under gains that push their true peak 3, 6 and 12 dB over a ceiling of 10 ** (-1 / 20), limited at lookahead 1, 72 and 256 (hold
+0) into float64; the residual is max(true peak, sample peak) of the result over the ceiling, minus one.
+
+One JSON line per shape and per residual table, appended to --out (default profiles/limit_perf.jsonl) and printed:
+
+  {"config", "streams", "nch", "frames", "lookahead", "hold", "ms": median of the rounds, "ms_rounds", "gsamples_per_s",
+   "true_peak_ms", "ratio_to_true_peak", "measure_only_ms", "ratio_to_measure_only", "limited_share", "steps", "warmup"}
+  {"residuals": {signal: {"+3dB" ...: {lookahead: overshoot}}}}
+
+  python tools/perf_limit.py [--configs 1,3] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE] [--no-residuals]
+"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import torch  # noqa: E402
+
+import foo_dsp_resampler_amd as F  # noqa: E402
+from perf_finish import step_tensor, timed  # noqa: E402
+
+PAIRS = ((72, 0), (1024, 4096))
+
+
+def one_config(k, steps, warmup, rounds):
+    stream = torch.cuda.Stream()
+    x, _ = step_tensor(k, stream)
+    S, frames, nch = x.shape
+    phases, taps, coefs = F.TRUE_PEAK_FILTERS["bs1770"]
+    co = (C.c_double * len(coefs))(*coefs)
+    with torch.cuda.stream(stream):
+        tp = torch.zeros((S, nch), dtype=torch.float64, device="cuda")
+        pk = torch.zeros((S, nch), dtype=torch.float64, device="cuda")
+        pk2 = torch.zeros((S, nch), dtype=torch.float64, device="cuda")
+        cl = torch.zeros((S, nch), dtype=torch.int64, device="cuda")
+        out = torch.empty_like(x)
+        red = torch.ones((S,), dtype=torch.float64, device="cuda")
+        lim = torch.zeros((S,), dtype=torch.int64, device="cuda")
+        work = torch.empty((F.limit_work_doubles(S, frames, taps, 1024),), dtype=torch.float64, device="cuda")
+        ceiling = 0.5 * float(x.abs().max())
+    stream.synchronize()
+
+    def limiter(L, H):
+        def call():
+            F.ratelib._check(F.lib().RRX_limit_device(-1, C.c_void_p(stream.cuda_stream), F.RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
+                                                      F.RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames, S, frames, nch, None, ceiling,
+                                                      C.cast(co, C.c_void_p), phases, taps, L, H, C.c_void_p(red.data_ptr()),
+                                                      C.c_void_p(lim.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()), "RRX_limit_device")
+        return call
+
+    def true_peak():
+        return F.true_peak_device(x, true_peak=tp, peak=pk, stream=stream)
+
+    def measure_only():
+        return F.finish_device(x, None, peak=pk2, clipped=cl, stream=stream)
+
+    calls = [limiter(L, H) for L, H in PAIRS]
+    ms, tms, mms = [[] for _ in PAIRS], [], []
+    for _ in range(rounds):
+        for i, call in enumerate(calls):
+            ms[i].append(timed(stream, call, steps, warmup))
+        tms.append(timed(stream, true_peak, steps, warmup))
+        mms.append(timed(stream, measure_only, steps, warmup))
+    t, mo = statistics.median(tms), statistics.median(mms)
+    lines = []
+    for i, (L, H) in enumerate(PAIRS):
+        with torch.cuda.stream(stream):
+            lim.zero_()
+            calls[i]()
+            share = float(lim.sum()) / (S * frames)
+        stream.synchronize()
+        m = statistics.median(ms[i])
+        lines.append({"config": k, "streams": S, "nch": nch, "frames": frames, "lookahead": L, "hold": H, "ms": round(m, 4),
+                      "ms_rounds": [round(v, 4) for v in ms[i]], "gsamples_per_s": round(S * frames * nch / m / 1e6, 2),
+                      "true_peak_ms": round(t, 4), "ratio_to_true_peak": round(m / t, 2), "measure_only_ms": round(mo, 4),
+                      "ratio_to_measure_only": round(m / mo, 2), "limited_share": round(share, 4), "steps": steps, "warmup": warmup})
+    return lines
+
+
+def residuals():
+    ceiling = 10.0 ** (-1.0 / 20.0)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    n = torch.arange(48000, device="cuda", dtype=torch.float64)
+    tone = torch.sin(2 * math.pi * n / 4 + math.pi / 4) * (0.6 + 0.4 * torch.sin(2 * math.pi * n / 1531.0))
+    signals = {"noise": torch.randn((48000, 2), generator=gen, device="cuda", dtype=torch.float64) * 0.25,
+               "modulated_fs4_tone": torch.stack([tone, tone.roll(1)], dim=1).contiguous()}
+    table = {}
+    for name, x in signals.items():
+        level = float(torch.maximum(*F.true_peak_device(x)[:2]).max())
+        table[name] = {}
+        for db in (3, 6, 12):
+            gain = ceiling * 10.0 ** (db / 20.0) / level
+            row = {}
+            for L in (1, 72, 256):
+                y, _, _ = F.limit_device(x, ceiling, gain=gain, lookahead=L, hold=0)
+                row[str(L)] = float(torch.maximum(*F.true_peak_device(y)[:2]).max()) / ceiling - 1.0
+            table[name]["+%ddB" % db] = row
+    return {"residuals": table, "ceiling": ceiling, "frames": 48000, "nch": 2}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="1,3")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--no-residuals", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "limit_perf.jsonl"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("perf_limit.py needs a GPU: there is nothing to time without one")
+    lines = []
+    for k in [int(v) for v in a.configs.split(",") if v]:
+        lines += one_config(k, a.steps, a.warmup, a.rounds)
+    if not a.no_residuals:
+        lines.append(residuals())
+    for line in lines:
+        text = json.dumps(line)
+        print(text, flush=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
