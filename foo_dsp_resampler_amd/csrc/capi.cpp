@@ -1116,18 +1116,17 @@ size_t RRX_limit_work_doubles(int nstreams, size_t frames, int taps, size_t look
 
 namespace {
 
-// the limiter's own arguments, shared by the three calls: ceiling, lookahead, hold, the formats and the work buffer (whose size is
-// RRX_limit_work_doubles(nstreams, frames, taps, lookahead)); a.f is set already
-int limit_common(int src_format, int dst_format, int nstreams, size_t frames, double ceiling, size_t lookahead, size_t hold, double *work,
-                 size_t work_doubles, rsmp::LimitArgs &a)
+// the limiter's own arguments, shared by all its calls: ceiling, lookahead, hold, the formats and the work buffer, of which the
+// call needs `need` doubles (0: refused), `work_stride` for each of r and m; a.f is set already
+int limit_scalars(int src_format, int dst_format, double ceiling, size_t lookahead, size_t hold, double *work, size_t work_doubles, size_t need,
+                  unsigned long long work_stride, rsmp::LimitArgs &a)
 {
   if (dst_format != RRX_FMT_FLOAT && dst_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
   if (!std::isfinite(ceiling) || !(ceiling > 0)) return RR_INVPARAM;
   if (lookahead < 1 || lookahead > RRX_LIMIT_MAX_LOOKAHEAD || hold > RRX_LIMIT_MAX_HOLD) return RR_INVPARAM;
-  const size_t need = RRX_limit_work_doubles(nstreams, frames, a.f.taps, lookahead);
   if (!need || !work || work_doubles < need) return RR_INVPARAM;
   a.work = work;
-  a.work_stride = (unsigned long long)frames + (unsigned)a.f.taps + lookahead;
+  a.work_stride = work_stride;
   a.lookahead = (unsigned)lookahead;
   a.hold = (unsigned)hold;
   a.ceiling = ceiling;
@@ -1135,6 +1134,14 @@ int limit_common(int src_format, int dst_format, int nstreams, size_t frames, do
   a.src_double = src_format == RRX_FMT_DOUBLE;
   a.dst_double = dst_format == RRX_FMT_DOUBLE;
   return RR_OK;
+}
+
+// the whole-row calls: the work buffer is RRX_limit_work_doubles(nstreams, frames, taps, lookahead)
+int limit_common(int src_format, int dst_format, int nstreams, size_t frames, double ceiling, size_t lookahead, size_t hold, double *work,
+                 size_t work_doubles, rsmp::LimitArgs &a)
+{
+  return limit_scalars(src_format, dst_format, ceiling, lookahead, hold, work, work_doubles,
+                       RRX_limit_work_doubles(nstreams, frames, a.f.taps, lookahead), (unsigned long long)frames + (unsigned)a.f.taps + lookahead, a);
 }
 
 // the overlap rule of the limiter: the destination is exactly the source, with its format and pitch, or shares no byte with it
@@ -1978,6 +1985,119 @@ int RRX_debug_tracks_loudness_window_host(const RRX_track *tracks, int ntracks, 
                                              hop, state_in, state_out, energy, energy_stride, hops, work, work_doubles, a);
   if (rc != RR_OK) return rc;
   if (row_frames && win_frames) rsmp::loudness_window_host(a);
+  return RR_OK;
+}
+
+// how far a frame's gain reaches into the samples around it (limit.hpp): host only
+int RRX_limit_window_reach(int taps, size_t lookahead, size_t hold, size_t *back, size_t *ahead)
+{
+  if (!back || !ahead || taps < 1 || taps > RRX_TP_MAX_TAPS) return RR_INVPARAM;
+  if (lookahead < 1 || lookahead > RRX_LIMIT_MAX_LOOKAHEAD || hold > RRX_LIMIT_MAX_HOLD) return RR_INVPARAM;
+  *back = size_t(rsmp::limit_reach_back(taps, unsigned(lookahead), unsigned(hold)));
+  *ahead = size_t(rsmp::limit_reach_ahead(taps, unsigned(lookahead)));
+  return RR_OK;
+}
+
+// r and m of every track for one window (limit.hip), win_frames + 2 * lookahead + hold + 2 * taps doubles each: 0 for what the
+// data call refuses
+size_t RRX_tracks_limit_window_work_doubles(int ntracks, size_t win_frames, int taps, size_t lookahead, size_t hold)
+{
+  if (ntracks < 1 || taps < 1 || taps > RRX_TP_MAX_TAPS || lookahead < 1 || lookahead > RRX_LIMIT_MAX_LOOKAHEAD || hold > RRX_LIMIT_MAX_HOLD)
+    return 0;
+  const size_t most = size_t(1) << 60, per = 2 * size_t(ntracks); // (2^32 at the most)
+  if (win_frames >= most / per) return 0;
+  const size_t each = win_frames + 2 * lookahead + hold + 2 * size_t(taps); // below 2^60 + 2^13
+  return each >= (most + per - 1) / per ? 0 : per * each;
+}
+
+namespace {
+
+// RRX_tracks_limit_window_device / RRX_debug_tracks_limit_window_host: everything that can be refused from the arguments alone
+int tracks_limit_window_args(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *buf, size_t buf_stride, size_t buf_first,
+                             size_t buf_frames, size_t row_frames, size_t win_first, size_t win_frames, int dst_format, void *dst,
+                             size_t dst_stride, const double *gain, double ceiling, const double *coefs, int phases, int taps, size_t lookahead,
+                             size_t hold, double *reduction, unsigned long long *limited, double *work, size_t work_doubles, rsmp::LimitArgs &a,
+                             rsmp::LimitWindow &lw)
+{
+  if (!tracks || !buf || !dst || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device), and no virtual row either
+  if (row_frames > most / size_t(ntracks) || buf_stride > most / size_t(ntracks)) return RR_INVPARAM;
+  rsmp::TracksWindow w; // the window lies inside the rows, fits the destination's pitch, and the destination is one a device can hold
+  if (tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, dst_stride, w) != RR_OK) return RR_INVPARAM;
+  rc = limit_scalars(src_format, dst_format, ceiling, lookahead, hold, work, work_doubles,
+                     RRX_tracks_limit_window_work_doubles(ntracks, win_frames, a.f.taps, lookahead, hold),
+                     (unsigned long long)win_frames + 2 * lookahead + hold + 2 * (unsigned)a.f.taps, a);
+  if (rc != RR_OK) return rc;
+  // coverage: the window and its halo, as far as the rows go (every term is below 2^60 + 2^13)
+  const size_t back = size_t(rsmp::limit_reach_back(a.f.taps, unsigned(lookahead), unsigned(hold)));
+  const size_t ahead = size_t(rsmp::limit_reach_ahead(a.f.taps, unsigned(lookahead)));
+  const size_t want_first = win_first > back ? win_first - back : 0;
+  const size_t want_end = win_first + win_frames + ahead < row_frames ? win_first + win_frames + ahead : row_frames;
+  if (buf_first + buf_frames < buf_first || buf_first + buf_frames > row_frames || buf_stride < buf_frames) return RR_INVPARAM;
+  if (buf_first > want_first || buf_first + buf_frames < want_end) return RR_INVPARAM;
+  const uintptr_t sb = uintptr_t(ntracks) * buf_stride * uintptr_t(nch) * (a.src_double ? 8 : 4);
+  const uintptr_t db = uintptr_t(ntracks) * dst_stride * uintptr_t(nch) * (a.dst_double ? 8 : 4);
+  if (buf == dst || !limit_overlap_ok(buf, sb, dst, db, false)) return RR_INVPARAM;
+  a.src = buf;
+  a.dst = dst;
+  a.gain = gain;
+  a.reduction = reduction;
+  a.limited = limited;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(tracks);
+  a.src_stride = (unsigned long long)buf_stride * nch;
+  a.dst_stride = (unsigned long long)dst_stride * nch;
+  a.frames = row_frames;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  lw.win_first = win_first;
+  lw.win_frames = win_frames;
+  lw.buf_first = buf_first;
+  lw.buf_frames = buf_frames;
+  return RR_OK;
+}
+
+} // namespace
+
+// RRX_tracks_limit_device on a window of the rows, from a buffer that holds the window and its halo (limit.hip).  Refusals first.
+int RRX_tracks_limit_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                   const void *d_buf, size_t buf_stride, size_t buf_first, size_t buf_frames, size_t row_frames,
+                                   size_t win_first, size_t win_frames, int dst_format, void *d_dst, size_t dst_stride, const double *d_gain,
+                                   double ceiling, const double *coefs, int phases, int taps, size_t lookahead, size_t hold, double *d_reduction,
+                                   unsigned long long *d_limited, double *d_work, size_t work_doubles)
+{
+  rsmp::LimitArgs a;
+  rsmp::LimitWindow w;
+  int rc = tracks_limit_window_args(d_tracks, ntracks, nch, src_format, d_buf, buf_stride, buf_first, buf_frames, row_frames, win_first,
+                                    win_frames, dst_format, d_dst, dst_stride, d_gain, ceiling, coefs, phases, taps, lookahead, hold,
+                                    d_reduction, d_limited, d_work, work_doubles, a, w);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames || !win_frames) return RR_OK;
+  rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_limit(static_cast<hipStream_t>(hip_stream), a, &w) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_limit_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *buf, size_t buf_stride,
+                                       size_t buf_first, size_t buf_frames, size_t row_frames, size_t win_first, size_t win_frames,
+                                       int dst_format, void *dst, size_t dst_stride, const double *gain, double ceiling, const double *coefs,
+                                       int phases, int taps, size_t lookahead, size_t hold, double *reduction, unsigned long long *limited,
+                                       double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LimitArgs a;
+  rsmp::LimitWindow w;
+  const int rc = tracks_limit_window_args(tracks, ntracks, nch, src_format, buf, buf_stride, buf_first, buf_frames, row_frames, win_first,
+                                          win_frames, dst_format, dst, dst_stride, gain, ceiling, coefs, phases, taps, lookahead, hold,
+                                          reduction, limited, work, work_doubles, a, w);
+  if (rc != RR_OK) return rc;
+  if (row_frames && win_frames) rsmp::limit_host(a, &w);
   return RR_OK;
 }
 

@@ -19,6 +19,13 @@
 //            and leave as at most one atomic per (workgroup, stream, statistic), issued only where it changes the value.
 // Nothing outside the rows is read; nothing but the rows' frames of the destination, the work buffer and the two result arrays is
 // written.  In place the apply kernel reads a sample in the lane that writes it, after the detector is done with the rows.
+//
+// The window form (RRX_tracks_limit_window_device, DESIGN.md 11 "Windows with the limiter") runs the same three bodies on a
+// sub-range of every row: with [lo, hi) the window's cut of the slice, the detector covers F in [max(0, lo - (L - 1) - H),
+// min(N + D, hi + L - 1 + D)), the minimum the entries j in [lo, hi + L - 1), the product the frames [lo, hi); r and m are
+// stored from their first entry of that range.  Row (below) carries the ranges, and for a whole row they are constants that
+// fold away: every kernel is a template over kWin, instantiated once for each form, so the two cannot drift apart.  (The window
+// is a kernel argument of its own behind the others, all zeros for whole rows: their arguments stay where they were.)
 #include "limit.hpp"
 
 #include <cstring>
@@ -40,13 +47,33 @@ struct Row {
   double *r, *m;
   double gain;
   bool has_gain;
+  // what of the row this call works on (a whole row: lo = fa = 0, hi = frames, fb = frames + D, every frame readable)
+  unsigned long long lo, hi; // the frames that are emitted; m[0] is entry j = lo
+  unsigned long long fa, fb; // the detector frames F that are evaluated; r[0] is r[fa]
+  unsigned long long s_lo, s_hi; // the frames the source holds: the others read as +0.0
 };
 
-__host__ __device__ __forceinline__ Row row_of(const LimitArgs &a, unsigned long long s)
+template <bool kWin> __host__ __device__ __forceinline__ Row row_of(const LimitArgs &a, const LimitWindow &w, unsigned long long s)
 {
   Row r;
   const unsigned long long nch = (unsigned long long)a.nch;
-  if (a.tracks) {
+  if (kWin) {
+    // the slice, clamped into the virtual row; the sums below stay under 2 * row_frames + 2^14
+    const TracksSlice sl = tracks_slice(a.tracks[s], a.frames, 0, false);
+    const unsigned long long end = w.win_first + w.win_frames, top = sl.of + sl.frames, buf_end = w.buf_first + w.buf_frames;
+    const unsigned long long lo = sl.of > w.win_first ? sl.of : w.win_first, hi = top < end ? top : end;
+    const unsigned long long D = (unsigned long long)(a.f.taps - 1), reach = (unsigned long long)(a.lookahead - 1) + a.hold;
+    r.frames = sl.frames;
+    r.lo = hi > lo ? lo - sl.of : 0;
+    r.hi = hi > lo ? hi - sl.of : 0;
+    r.fa = r.lo > reach ? r.lo - reach : 0;
+    r.fb = r.hi + (a.lookahead - 1) + D < sl.frames + D ? r.hi + (a.lookahead - 1) + D : sl.frames + D;
+    r.s_lo = w.buf_first > sl.of ? w.buf_first - sl.of : 0;
+    r.s_hi = buf_end > sl.of ? (buf_end - sl.of < sl.frames ? buf_end - sl.of : sl.frames) : 0;
+    // frame 0 of the slice may lie in front of the buffer: the sums wrap, and wrap back at every frame that is read or written
+    r.src_at = s * a.src_stride + (sl.of - w.buf_first) * nch;
+    r.dst_at = s * a.dst_stride + (sl.of - w.win_first) * nch;
+  } else if (a.tracks) {
     const TracksSlice sl = tracks_slice(a.tracks[s], a.frames, 0, false);
     r.src_at = r.dst_at = (s * a.frames + sl.of) * nch;
     r.frames = sl.frames;
@@ -54,6 +81,11 @@ __host__ __device__ __forceinline__ Row row_of(const LimitArgs &a, unsigned long
     r.src_at = s * a.src_stride;
     r.dst_at = s * a.dst_stride;
     r.frames = a.frames;
+  }
+  if (!kWin) {
+    r.lo = r.fa = r.s_lo = 0;
+    r.hi = r.s_hi = r.frames;
+    r.fb = r.frames + (unsigned long long)(a.f.taps - 1);
   }
   r.r = a.work + s * 2 * a.work_stride;
   r.m = r.r + a.work_stride;
@@ -69,6 +101,13 @@ template <typename S> __host__ __device__ __forceinline__ double gained(const Li
   return r.has_gain ? v * r.gain : v;
 }
 
+// the same, +0.0 for a frame the source does not hold (the window form; a whole row holds all of its frames)
+template <typename S, bool kWin> __host__ __device__ __forceinline__ double gained_held(const LimitArgs &a, const Row &r, unsigned long long fr, unsigned ch)
+{
+  if (kWin && (fr < r.s_lo || fr >= r.s_hi)) return 0.0;
+  return gained<S>(a, r, fr, ch);
+}
+
 // One channel's share of a detector frame's level: h as true_peak_frame takes it, h[0] the frame itself (+0.0 behind the row)
 template <int kP, int kT> __host__ __device__ __forceinline__ unsigned long long level_of(const LimitArgs &a, const double (&h)[kTpMaxTaps])
 {
@@ -79,22 +118,23 @@ template <int kP, int kT> __host__ __device__ __forceinline__ unsigned long long
 // frame n of the row under the gain s
 template <typename S, typename T> __host__ __device__ __forceinline__ void apply(const LimitArgs &a, const Row &r, unsigned long long n, double s)
 {
-  T *dst = static_cast<T *>(a.dst) + r.dst_at + n * (unsigned)a.nch;
+  T *dst = static_cast<T *>(a.dst) + (r.dst_at + n * (unsigned)a.nch);
   for (unsigned ch = 0; ch < (unsigned)a.nch; ++ch) dst[ch] = limit_output<T>(gained<S>(a, r, n, ch), s);
 }
 
 // A workgroup takes kThreads detector frames at a time, one lane each, and stages their gained samples in LDS behind a halo of
 // taps - 1 frames, as many channels at a time as kDetectTile doubles hold; the level is the maximum over the channel groups.
-template <typename S, int kP, int kT> __global__ __launch_bounds__(kThreads) void limit_detect_kernel(LimitArgs a, int s0)
+template <typename S, int kP, int kT, bool kWin> __global__ __launch_bounds__(kThreads) void limit_detect_kernel(LimitArgs a, int s0, LimitWindow w)
 {
   __shared__ double tile[kDetectTile];
-  const Row r = row_of(a, (unsigned long long)(s0 + (int)blockIdx.y));
-  if (!r.frames) return; // (the whole workgroup)
+  const Row r = row_of<kWin>(a, w, (unsigned long long)(s0 + (int)blockIdx.y));
+  if (kWin ? r.lo >= r.hi : !r.frames) return; // (the whole workgroup)
   const int taps = kT ? kT : a.f.taps;
   const unsigned tid = threadIdx.x, nch = (unsigned)a.nch, halo = (unsigned)(taps - 1);
   const unsigned most = (unsigned)kDetectTile / ((unsigned)kThreads + halo); // channels a tile holds: 15 (16 without a halo)
-  const unsigned long long evals = r.frames + halo;
-  for (unsigned long long F0 = (unsigned long long)blockIdx.x * kThreads; F0 < evals; F0 += (unsigned long long)gridDim.x * kThreads) {
+  const unsigned long long evals = kWin ? r.fb : r.frames + halo; // (r.fb of a whole row, from the kernel's own tap count)
+  const unsigned long long first = kWin ? r.fa : 0;
+  for (unsigned long long F0 = first + (unsigned long long)blockIdx.x * kThreads; F0 < evals; F0 += (unsigned long long)gridDim.x * kThreads) {
     const unsigned nf = evals - F0 < (unsigned long long)kThreads ? (unsigned)(evals - F0) : (unsigned)kThreads;
     unsigned long long lev = 0;
     for (unsigned c0 = 0; c0 < nch; c0 += most) {
@@ -103,7 +143,7 @@ template <typename S, int kP, int kT> __global__ __launch_bounds__(kThreads) voi
       for (unsigned j = tid; j < count; j += kThreads) {
         const unsigned fi = j / cc, c = j - fi * cc;
         const unsigned long long at = F0 + fi; // the frame, counted from halo frames in front of the row
-        tile[j] = at >= halo && at - halo < r.frames ? gained<S>(a, r, at - halo, c0 + c) : 0.0;
+        tile[j] = at >= halo && at - halo < r.frames ? gained_held<S, kWin>(a, r, at - halo, c0 + c) : 0.0;
       }
       __syncthreads();
       if (tid < nf) {
@@ -116,27 +156,27 @@ template <typename S, int kP, int kT> __global__ __launch_bounds__(kThreads) voi
         }
       }
     }
-    if (tid < nf) r.r[F0 + tid] = limit_reduction(lev, a.ceiling);
+    if (tid < nf) r.r[F0 - first + tid] = limit_reduction(lev, a.ceiling);
   }
 }
 
-__global__ __launch_bounds__(kThreads) void limit_window_kernel(LimitArgs a, int s0)
+template <bool kWin> __global__ __launch_bounds__(kThreads) void limit_window_kernel(LimitArgs a, int s0, LimitWindow w)
 {
   __shared__ double tile[kLimitMinTile];
-  const Row r = row_of(a, (unsigned long long)(s0 + (int)blockIdx.y));
-  if (!r.frames) return; // (the whole workgroup)
+  const Row r = row_of<kWin>(a, w, (unsigned long long)(s0 + (int)blockIdx.y));
+  if (r.lo >= r.hi) return; // (the whole workgroup)
   const unsigned tid = threadIdx.x, L = a.lookahead, D = (unsigned)(a.f.taps - 1);
   const unsigned width = L + a.hold + D;                     // entries of r under one value of m
   const unsigned per = (unsigned)kLimitMinTile - (width - 1); // values of m a tile gives
-  const unsigned long long outs = r.frames + (L - 1), evals = r.frames + D;
+  const unsigned long long outs = r.hi - r.lo + (L - 1), evals = r.frames + D; // the entries j = r.lo + o, o < outs
   const unsigned long long back = (unsigned long long)(L - 1) + a.hold; // m[j] begins at F = j - back
   for (unsigned long long t = blockIdx.x; t * per < outs; t += gridDim.x) {
-    const unsigned long long o0 = t * per;
+    const unsigned long long o0 = t * per, j0 = r.lo + o0;
     const unsigned no = outs - o0 < per ? (unsigned)(outs - o0) : per, count = no + width - 1;
     if (t != blockIdx.x) __syncthreads(); // the readers of the tile before are done
     for (unsigned e = tid; e < count; e += kThreads) {
-      const unsigned long long at = o0 + e; // F + back
-      tile[e] = at >= back && at - back < evals ? r.r[at - back] : 1.0;
+      const unsigned long long at = j0 + e; // F + back: every F of the row that is asked for lies in [r.fa, r.fb)
+      tile[e] = at >= back && at - back < evals ? r.r[at - back - r.fa] : 1.0;
     }
     __syncthreads();
     unsigned w = 1; // entry e holds the minimum of [e, e + w) wherever e + w <= count
@@ -165,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void limit_window_kernel(LimitArgs a, int
   }
 }
 
-template <typename S, typename T> __global__ __launch_bounds__(kThreads) void limit_apply_kernel(LimitArgs a, int s0)
+template <typename S, typename T, bool kWin> __global__ __launch_bounds__(kThreads) void limit_apply_kernel(LimitArgs a, int s0, LimitWindow w)
 {
   // entry e of the tile lies at (e % kLimitLaneFrames) * kApplyPitch + e / kLimitLaneFrames: a lane's frames are consecutive, and
   // the lanes of a wave then read consecutive doubles
@@ -174,20 +214,20 @@ template <typename S, typename T> __global__ __launch_bounds__(kThreads) void li
   __shared__ unsigned long long sh_min;
   __shared__ unsigned sh_count;
   const unsigned long long s = (unsigned long long)(s0 + (int)blockIdx.y);
-  const Row r = row_of(a, s);
-  if (!r.frames) return; // (the whole workgroup)
+  const Row r = row_of<kWin>(a, w, s);
+  if (r.lo >= r.hi) return; // (the whole workgroup)
   const unsigned tid = threadIdx.x, L = a.lookahead;
   const unsigned long long one = true_peak_bits(1.0);
   if (!tid) {
     sh_min = one;
     sh_count = 0;
   }
-  for (unsigned long long n0 = (unsigned long long)blockIdx.x * kLimitApplyFrames; n0 < r.frames;
+  for (unsigned long long n0 = r.lo + (unsigned long long)blockIdx.x * kLimitApplyFrames; n0 < r.hi;
        n0 += (unsigned long long)gridDim.x * kLimitApplyFrames) {
-    const unsigned nf = r.frames - n0 < (unsigned long long)kLimitApplyFrames ? (unsigned)(r.frames - n0) : (unsigned)kLimitApplyFrames;
+    const unsigned nf = r.hi - n0 < (unsigned long long)kLimitApplyFrames ? (unsigned)(r.hi - n0) : (unsigned)kLimitApplyFrames;
     __syncthreads(); // sh_min is set; the readers of the tile and of the gains before are done
     for (unsigned e = tid; e < (unsigned)kLimitApplyFrames + L - 1; e += kThreads) // m[j], j = n0 + e: frame n reads j in [n, n + L)
-      tile[(e % kLimitLaneFrames) * kApplyPitch + e / kLimitLaneFrames] = e < nf + L - 1 ? r.m[n0 + e] : 1.0;
+      tile[(e % kLimitLaneFrames) * kApplyPitch + e / kLimitLaneFrames] = e < nf + L - 1 ? r.m[n0 - r.lo + e] : 1.0;
     __syncthreads();
     const unsigned f0 = tid * kLimitLaneFrames; // the lane's first frame in the tile
     if (f0 < nf) {
@@ -215,8 +255,8 @@ template <typename S, typename T> __global__ __launch_bounds__(kThreads) void li
     __syncthreads();
     // the tile's samples in the order they lie in memory, whatever the channel count: apply()'s product
     const unsigned long long nch = (unsigned long long)a.nch, total = nf * nch, at = n0 * nch;
-    const S *src = static_cast<const S *>(a.src) + r.src_at + at;
-    T *dst = static_cast<T *>(a.dst) + r.dst_at + at;
+    const S *src = static_cast<const S *>(a.src) + (r.src_at + at); // (the sum first: in the window form r.src_at may have wrapped)
+    T *dst = static_cast<T *>(a.dst) + (r.dst_at + at);
     for (unsigned long long j = tid; j < total; j += kThreads) {
       const double v = (double)src[j];
       dst[j] = limit_output<T>(r.has_gain ? v * r.gain : v, sh_gain[j / nch]);
@@ -234,22 +274,23 @@ template <typename S, typename T> __global__ __launch_bounds__(kThreads) void li
 
 unsigned grid_x(unsigned long long pieces) { return pieces < 1 ? 1u : pieces > 0x7fffffffull ? 0x7fffffffu : (unsigned)pieces; }
 
-template <typename S, typename T> hipError_t launch_typed(hipStream_t stream, const LimitArgs &a)
+template <typename S, typename T, bool kWin> hipError_t launch_typed(hipStream_t stream, const LimitArgs &a, const LimitWindow &w)
 {
-  // the longest row.  The caller keeps frames * nch below 2^60, so nothing here wraps.
+  // the longest row, or the longest cut of one by the window.  The caller keeps frames * nch below 2^60, so nothing here wraps.
   const unsigned long long D = (unsigned long long)(a.f.taps - 1), L = a.lookahead;
   const unsigned long long per = (unsigned long long)kLimitMinTile - (L + a.hold + D - 1);
-  const unsigned gx1 = grid_x((a.frames + D + kThreads - 1) / kThreads), gx2 = grid_x((a.frames + L - 1 + per - 1) / per),
-                 gx3 = grid_x((a.frames + kLimitApplyFrames - 1) / kLimitApplyFrames);
+  const unsigned long long emit = kWin ? w.win_frames : a.frames, evals = kWin ? emit + 2 * (L - 1) + a.hold + D : emit + D;
+  const unsigned gx1 = grid_x((evals + kThreads - 1) / kThreads), gx2 = grid_x((emit + L - 1 + per - 1) / per),
+                 gx3 = grid_x((emit + kLimitApplyFrames - 1) / kLimitApplyFrames);
   const bool bs1770 = a.f.phases == 4 && a.f.taps == 12;
   const dim3 block(kThreads);
   for (int pass = 0; pass < 3; ++pass) {
     for (int s0 = 0; s0 < a.nstreams; s0 += 32768) { // grid.y is a 16-bit count
       const unsigned ns = (unsigned)(a.nstreams - s0 < 32768 ? a.nstreams - s0 : 32768);
-      if (pass == 0 && bs1770) hipLaunchKernelGGL((limit_detect_kernel<S, 4, 12>), dim3(gx1, ns), block, 0, stream, a, s0);
-      else if (pass == 0) hipLaunchKernelGGL((limit_detect_kernel<S, 0, 0>), dim3(gx1, ns), block, 0, stream, a, s0);
-      else if (pass == 1) hipLaunchKernelGGL(limit_window_kernel, dim3(gx2, ns), block, 0, stream, a, s0);
-      else hipLaunchKernelGGL((limit_apply_kernel<S, T>), dim3(gx3, ns), block, 0, stream, a, s0);
+      if (pass == 0 && bs1770) hipLaunchKernelGGL((limit_detect_kernel<S, 4, 12, kWin>), dim3(gx1, ns), block, 0, stream, a, s0, w);
+      else if (pass == 0) hipLaunchKernelGGL((limit_detect_kernel<S, 0, 0, kWin>), dim3(gx1, ns), block, 0, stream, a, s0, w);
+      else if (pass == 1) hipLaunchKernelGGL(limit_window_kernel<kWin>, dim3(gx2, ns), block, 0, stream, a, s0, w);
+      else hipLaunchKernelGGL((limit_apply_kernel<S, T, kWin>), dim3(gx3, ns), block, 0, stream, a, s0, w);
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
@@ -257,33 +298,33 @@ template <typename S, typename T> hipError_t launch_typed(hipStream_t stream, co
   return hipSuccess;
 }
 
-template <typename S, typename T> void host_typed(const LimitArgs &a)
+template <typename S, typename T, bool kWin> void host_typed(const LimitArgs &a, const LimitWindow &w)
 {
   const unsigned L = a.lookahead, D = (unsigned)(a.f.taps - 1);
   const unsigned long long back = (unsigned long long)(L - 1) + a.hold, width = (unsigned long long)L + a.hold + D;
   for (unsigned long long s = 0; s < (unsigned long long)a.nstreams; ++s) {
-    const Row r = row_of(a, s);
-    if (!r.frames) continue;
-    const unsigned long long evals = r.frames + D, outs = r.frames + (L - 1);
-    for (unsigned long long F = 0; F < evals; ++F) {
+    const Row r = row_of<kWin>(a, w, s);
+    if (r.lo >= r.hi) continue;
+    const unsigned long long evals = r.frames + D, outs = r.hi - r.lo + (L - 1);
+    for (unsigned long long F = r.fa; F < r.fb; ++F) {
       unsigned long long lev = 0;
       for (unsigned ch = 0; ch < (unsigned)a.nch; ++ch) {
         double h[kTpMaxTaps];
-        for (unsigned k = 0; k < (unsigned)kTpMaxTaps; ++k) h[k] = k <= D && F >= k && F - k < r.frames ? gained<S>(a, r, F - k, ch) : 0.0;
+        for (unsigned k = 0; k < (unsigned)kTpMaxTaps; ++k) h[k] = k <= D && F >= k && F - k < r.frames ? gained_held<S, kWin>(a, r, F - k, ch) : 0.0;
         const unsigned long long b = level_of<0, 0>(a, h);
         lev = b > lev ? b : lev;
       }
-      r.r[F] = limit_reduction(lev, a.ceiling);
+      r.r[F - r.fa] = limit_reduction(lev, a.ceiling);
     }
-    for (unsigned long long j = 0; j < outs; ++j) {
+    for (unsigned long long o = 0; o < outs; ++o) { // entry j = r.lo + o
       double least = 1.0; // what lies outside the row
-      for (unsigned long long at = j; at < j + width; ++at)
-        if (at >= back && at - back < evals && r.r[at - back] < least) least = r.r[at - back];
-      r.m[j] = least;
+      for (unsigned long long at = r.lo + o; at < r.lo + o + width; ++at)
+        if (at >= back && at - back < evals && r.r[at - back - r.fa] < least) least = r.r[at - back - r.fa];
+      r.m[o] = least;
     }
     unsigned long long lowest = true_peak_bits(1.0), count = 0;
-    for (unsigned long long n = 0; n < r.frames; ++n) {
-      const double g = limit_smooth(r.m + n, L, a.inv_l);
+    for (unsigned long long n = r.lo; n < r.hi; ++n) {
+      const double g = limit_smooth(r.m + (n - r.lo), L, a.inv_l);
       apply<S, T>(a, r, n, g);
       if (g < 1.0) {
         const unsigned long long b = true_peak_bits(g);
@@ -302,16 +343,27 @@ template <typename S, typename T> void host_typed(const LimitArgs &a)
 
 } // namespace
 
-hipError_t launch_limit(hipStream_t stream, const LimitArgs &a)
+namespace {
+
+template <bool kWin> hipError_t launch_form(hipStream_t stream, const LimitArgs &a, const LimitWindow &w)
 {
-  if (a.src_double) return a.dst_double ? launch_typed<double, double>(stream, a) : launch_typed<double, float>(stream, a);
-  return a.dst_double ? launch_typed<float, double>(stream, a) : launch_typed<float, float>(stream, a);
+  if (a.src_double) return a.dst_double ? launch_typed<double, double, kWin>(stream, a, w) : launch_typed<double, float, kWin>(stream, a, w);
+  return a.dst_double ? launch_typed<float, double, kWin>(stream, a, w) : launch_typed<float, float, kWin>(stream, a, w);
 }
 
-void limit_host(const LimitArgs &a)
+template <bool kWin> void host_form(const LimitArgs &a, const LimitWindow &w)
 {
-  if (a.src_double) a.dst_double ? host_typed<double, double>(a) : host_typed<double, float>(a);
-  else a.dst_double ? host_typed<float, double>(a) : host_typed<float, float>(a);
+  if (a.src_double) a.dst_double ? host_typed<double, double, kWin>(a, w) : host_typed<double, float, kWin>(a, w);
+  else a.dst_double ? host_typed<float, double, kWin>(a, w) : host_typed<float, float, kWin>(a, w);
 }
+
+} // namespace
+
+hipError_t launch_limit(hipStream_t stream, const LimitArgs &a, const LimitWindow *w)
+{
+  return w ? launch_form<true>(stream, a, *w) : launch_form<false>(stream, a, LimitWindow());
+}
+
+void limit_host(const LimitArgs &a, const LimitWindow *w) { w ? host_form<true>(a, *w) : host_form<false>(a, LimitWindow()); }
 
 } // namespace rsmp

@@ -88,6 +88,27 @@ struct LimitArgs {
   TruePeakFilter f;
 };
 
+// The window form (RRX_tracks_limit_window_device; a.tracks != null) takes this beside its LimitArgs, in which `frames` is then
+// the length of the virtual rows, src the buffer [nstreams][src_stride / nch][nch] that holds their frames [buf_first, buf_first
+// + buf_frames), dst [nstreams][dst_stride / nch][nch], whose frame j receives row frame win_first + j, and work_stride
+// win_frames + 2 * lookahead + hold + 2 * taps.  Of every slice the frames inside [win_first, win_first + win_frames) are emitted.
+// (A struct of its own: the whole-row kernels' arguments stay what they were.)
+struct LimitWindow {
+  unsigned long long win_first, win_frames, buf_first, buf_frames;
+};
+
+// How far the gain of a frame reaches (RRX_limit_window_reach): frame n depends on the samples of [n - back, n + ahead] only.
+// m[n - i], i < lookahead, covers r[F], F in [n - (lookahead - 1) - hold, n + lookahead - 1 + taps - 1], and r[F] reads the
+// frames [F - (taps - 1), F].
+__host__ __device__ __forceinline__ unsigned long long limit_reach_back(int taps, unsigned lookahead, unsigned hold)
+{
+  return (unsigned long long)(lookahead - 1) + hold + (unsigned)(taps - 1);
+}
+__host__ __device__ __forceinline__ unsigned long long limit_reach_ahead(int taps, unsigned lookahead)
+{
+  return (unsigned long long)(lookahead - 1) + (unsigned)(taps - 1);
+}
+
 // Window minimum (launch 2): a workgroup holds kLimitMinTile entries of r in LDS, of which lookahead + hold + taps - 2 are halo.
 // Smoothing (launch 3): a workgroup takes kLimitApplyFrames frames, kLimitLaneFrames consecutive ones to a lane, with
 // lookahead - 1 further entries of m.
@@ -95,8 +116,11 @@ constexpr int kLimitMinTile = 8192, kLimitApplyFrames = 1024, kLimitLaneFrames =
 
 // Only enqueues on `stream`: three launches, each split into as many as the grid limits ask for; the arguments are the caller's
 // to validate.  The table of the tracks form cannot be: the kernels clamp what they take from it (tracks_slice, tracks.hpp).
-hipError_t launch_limit(hipStream_t stream, const LimitArgs &a);
-// The plain call's results on host pointers, as serial loops over the functions above (test hook: RRX_debug_limit_host).
-void limit_host(const LimitArgs &a);
+// With a window the same three launches run on the sub-range of every row that the window asks for: the detector on the frames
+// within reach of it, the minimum on the entries of m under its frames, the product on its frames.
+hipError_t launch_limit(hipStream_t stream, const LimitArgs &a, const LimitWindow *w = nullptr);
+// The plain call's results on host pointers, as serial loops over the functions above (test hooks: RRX_debug_limit_host and,
+// with a window and a host table, RRX_debug_tracks_limit_window_host).
+void limit_host(const LimitArgs &a, const LimitWindow *w = nullptr);
 
 } // namespace rsmp

@@ -34,6 +34,7 @@ EXPECTED_SYMBOLS = [
     "RRX_tracks_finish_shaped_window_device", "RRX_debug_tracks_finish_shaped_window_host",
     "RRX_tracks_true_peak_window_device", "RRX_debug_tracks_true_peak_window_host", "RRX_tracks_loudness_window_work_doubles",
     "RRX_tracks_loudness_window_device", "RRX_debug_tracks_loudness_window_host",
+    "RRX_limit_window_reach", "RRX_tracks_limit_window_work_doubles", "RRX_tracks_limit_window_device", "RRX_debug_tracks_limit_window_host",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
     "RRX_reset", "RRX_tracks_batches", "RRX_plan_cache_clear", "RRX_plan_cache_stats",
@@ -303,6 +304,14 @@ def lib():
             host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, sz]
             L.RRX_tracks_loudness_window_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_tracks_loudness_window_host.argtypes = host
+        if hasattr(L, "RRX_tracks_limit_window_device"):  # (as above)
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp, C.c_double, vp, C.c_int, C.c_int, sz, sz,
+                    vp, vp, vp, sz]
+            L.RRX_tracks_limit_window_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_limit_window_host.argtypes = host
+            L.RRX_limit_window_reach.argtypes = [C.c_int, sz, sz, P(sz), P(sz)]
+            L.RRX_tracks_limit_window_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz, sz]
+            L.RRX_tracks_limit_window_work_doubles.restype = sz
         if hasattr(L, "RRX_reset"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_reset.argtypes = [vp]
@@ -1008,6 +1017,100 @@ def tracks_limit_device(rows, table, ceiling, gain=None, lookahead=64, hold=0, f
     return out, reduction, limited
 
 
+def limit_window_reach(lookahead, hold, filter="bs1770"):
+    """(back, ahead) of the limiter (RRX_limit_window_reach): the gain of frame n depends on the samples of the frames
+    [n - back, n + ahead] and on nothing else -- back = lookahead - 1 + hold + taps - 1, ahead = lookahead - 1 + taps - 1 with the
+    taps of `filter` -- which is the halo tracks_limit_window_device needs around a window.  Host only."""
+    _, taps, _ = _true_peak_filter(filter)
+    _, lookahead, hold = _limit_params(1.0, lookahead, hold)
+    back, ahead = C.c_size_t(0), C.c_size_t(0)
+    _check(lib().RRX_limit_window_reach(taps, lookahead, hold, C.byref(back), C.byref(ahead)), "RRX_limit_window_reach")
+    return int(back.value), int(ahead.value)
+
+
+def tracks_limit_window_work_doubles(ntracks, win_frames, taps=12, lookahead=64, hold=0):
+    """Doubles of work memory that tracks_limit_window_device needs for a window of `win_frames` frames of `ntracks` tracks
+    (RRX_tracks_limit_window_work_doubles: ntracks * 2 * (win_frames + 2 * lookahead + hold + 2 * taps)); 0 for arguments the call
+    refuses.  Host only."""
+    return int(lib().RRX_tracks_limit_window_work_doubles(int(ntracks), int(win_frames), int(taps), int(lookahead), int(hold)))
+
+
+def tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, win_frames, ceiling, gain=None, lookahead=64, hold=0, filter="bs1770",
+                               out=None, reduction=None, limited=None, stream=None, buf_frames=None):
+    """tracks_limit_device on a window of the rows (RRX_tracks_limit_window_device).  The limiter has nothing recursive in it, so a
+    window needs no state, only a halo of input: `buf`, a contiguous float32 or float64 device tensor [ntracks, buf_stride, nch],
+    holds frames [buf_first, buf_first + buf_frames) of rows (`buf_frames`: None, all buf_stride of them, or fewer) of `row_frames` frames that need not exist anywhere, and must reach
+    from max(0, win_first - back) to min(row_frames, win_first + win_frames + ahead) at least, (back, ahead) =
+    limit_window_reach(lookahead, hold, filter); ValueError otherwise.  Of every track's slice the frames inside [win_first,
+    win_first + win_frames) are limited as in the whole-row call -- from +0.0 in front of the slice and behind it, whatever the
+    buffer holds there -- and go to `out[t][frame - win_first]`: None (a new float32 or float64 tensor [ntracks, win_frames, nch]
+    of buf's dtype) or a contiguous one [ntracks, dst_stride >= win_frames, nch] that shares no memory with `buf` (in place is not
+    offered: the next window's halo must be unlimited input).  Nothing else of `out` is written.  `reduction` (float64 [ntracks],
+    preset to 1.0) and `limited` (int64 [ntracks], zeroed) are allocated when not passed and ACCUMULATED into: disjoint windows
+    that cover [0, row_frames), in any order, each given the `reduction` and `limited` the first one returned, leave
+    tracks_limit_device's bits in the emitted frames and its two statistics.  `ceiling`, `gain`, `lookahead`, `hold` and `filter`
+    are tracks_limit_device's.  Returns (out, reduction, limited); the call only enqueues, its work buffer comes from torch's
+    allocator."""
+    import torch
+    dt = str(buf.dtype)
+    if buf.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not buf.is_cuda or not buf.is_contiguous():
+        raise TypeError("buf must be a contiguous float32 or float64 device tensor [ntracks, buf_frames, nch]")
+    ntracks, buf_stride, nch = buf.shape
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
+    buf_first, buf_frames = int(buf_first), buf_stride if buf_frames is None else int(buf_frames)
+    if not 0 <= buf_frames <= buf_stride:
+        raise ValueError("%d buffered frames in a tensor of %d frames a row" % (buf_frames, buf_stride))
+    _tracks_table(table, ntracks)
+    dev = buf.device
+    if table.device != dev:
+        raise TypeError("the table must be on %s" % (dev,))
+    phases, taps, coefs = _true_peak_filter(filter)
+    ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
+    back, ahead = limit_window_reach(lookahead, hold, filter)
+    if buf_first < 0 or buf_first + buf_frames > row_frames:
+        raise ValueError("the buffer [%d, %d) does not lie inside rows of %d frames" % (buf_first, buf_first + buf_frames, row_frames))
+    if buf_first > max(0, win_first - back) or buf_first + buf_frames < min(row_frames, win_first + win_frames + ahead):
+        raise ValueError("the buffer [%d, %d) does not cover the window [%d, %d) with its halo of %d frames behind and %d ahead"
+                         % (buf_first, buf_first + buf_frames, win_first, win_first + win_frames, back, ahead))
+    gain = _loudness_gain(gain, ntracks, dev)
+    if out is None:
+        out = torch.empty((ntracks, win_frames, nch), dtype=buf.dtype, device=dev)
+    else:
+        odt = str(out.dtype)
+        if (out.dim() != 3 or not (odt.endswith("float32") or odt.endswith("float64")) or out.shape[0] != ntracks or out.shape[2] != nch
+                or out.shape[1] < win_frames or out.device != dev or not out.is_contiguous()):
+            raise TypeError("out must be a contiguous float32 or float64 tensor [%d, >= %d, %d] on %s" % (ntracks, win_frames, nch, dev))
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * out.element_size()
+        if lo < buf.data_ptr() + buf.numel() * buf.element_size() and buf.data_ptr() < hi:
+            raise ValueError("out must share no memory with buf: the window form does not work in place")
+    stats = []
+    for t, sdt, name, preset in ((reduction, torch.float64, "reduction", 1.0), (limited, torch.int64, "limited", 0)):
+        if t is None:
+            t = torch.full((ntracks,), preset, dtype=sdt, device=dev)
+        elif t.dtype != sdt or tuple(t.shape) != (ntracks,) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous %s tensor [%d] on %s" % (name, sdt, ntracks, dev))
+        stats.append(t)
+    reduction, limited = stats
+    if not win_frames or not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out, reduction, limited
+    need = tracks_limit_window_work_doubles(ntracks, win_frames, taps, lookahead, hold)
+    if not need:
+        raise ValueError("the window is too large for the limiter's work buffer")
+    work = torch.empty((need,), dtype=torch.float64, device=dev)
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_limit_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
+                                                ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
+                                                C.c_void_p(buf.data_ptr()), buf_stride, buf_first, buf_frames, row_frames, win_first,
+                                                win_frames, RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT,
+                                                C.c_void_p(out.data_ptr()), out.shape[1],
+                                                C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p),
+                                                phases, taps, lookahead, hold, C.c_void_p(reduction.data_ptr()),
+                                                C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+           "RRX_tracks_limit_window_device")
+    return out, reduction, limited
+
+
 K_WEIGHTING_48K =(1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,
                    1.0, -2.0, 1.0, -1.99004745483398, 0.99007225036621)
 """The K-weighting of ITU-R BS.1770-4 at 48 kHz as published, in the order of RRX_loudness_device's `coefs`: b0, b1, b2, a1, a2 of
@@ -1702,6 +1805,53 @@ class _WindowMeter:
         return self.true_peak, self.peak, self.energy, self.hops
 
 
+class _WindowLimiter:
+    """The limiter between the pull and the next stage of the streamed conversions (Resampler._convert_tracks_streamed, `limit=`).
+    A carry buffer per row holds the pulled frames [emitted - back, pulled), (back, ahead) = limit_window_reach(lookahead, hold):
+    after every pull the frames [emitted, pulled - ahead) are limited under `gain` into a window buffer of the pulled window's shape
+    (tracks_limit_window_device; nothing while that range is empty -- a pulled window may be shorter than `ahead`), and the frames
+    still within reach are moved to the front of the second carry buffer, which then takes the first one's place.  `flush(got)`
+    emits the rest, in pieces no longer than a pulled window, with the rows as long as what was delivered.  The emitted windows are
+    ascending and contiguous from frame 0.  Memory: 2 * (back + ahead + window) + window frames per row; `reduction` and `limited`
+    are accumulated into."""
+
+    def __init__(self, ceiling, gain, lookahead, hold, reduction, limited, table, cap, wout, stream):
+        import torch
+        self.kw = dict(ceiling=ceiling, gain=gain, lookahead=lookahead, hold=hold, reduction=reduction, limited=limited, stream=stream)
+        self.table, self.cap = table, cap
+        self.back, self.ahead = limit_window_reach(lookahead, hold)
+        n, width, nch = wout.shape
+        self.bufs = [torch.empty((n, self.back + self.ahead + width, nch), dtype=wout.dtype, device=wout.device) for _ in range(2)]
+        self.out = torch.empty_like(wout)
+        self.first = self.frames = self.emitted = 0  # the carry buffer holds the frames [first, first + frames) of the rows
+
+    def _emit(self, frames, row_frames):
+        tracks_limit_window_device(self.bufs[0], self.table, row_frames, self.first, self.emitted, frames, out=self.out, buf_frames=self.frames,
+                                   **self.kw)
+        at, self.emitted = self.emitted, self.emitted + frames
+        return self.out, at, frames
+
+    def feed(self, wout, k):
+        """takes the k frames just pulled into `wout`; (window buffer, first frame, frames) of what can be emitted now, or None"""
+        self.bufs[0][:, self.frames:self.frames + k].copy_(wout[:, :k])
+        self.frames += k
+        frames = self.first + self.frames - self.ahead - self.emitted  # at most k: what could be emitted before has been
+        if frames <= 0:
+            return None
+        window = self._emit(frames, self.cap)
+        shift = max(0, self.emitted - self.back) - self.first
+        if shift:
+            self.bufs[1][:, :self.frames - shift].copy_(self.bufs[0][:, shift:self.frames])
+            self.bufs.reverse()
+            self.first, self.frames = self.first + shift, self.frames - shift
+        return window
+
+    def flush(self, got):
+        """after the final pull: the windows that cover the rest, [emitted, got), the rows being `got` frames long"""
+        while self.emitted < got:
+            yield self._emit(min(self.out.shape[1], got - self.emitted), got)
+
+
 def _ensure_init():
     global _inited
     if not _inited:
@@ -2201,13 +2351,16 @@ class Resampler:
         scratch = finish_kw.pop("_scratch", None)
         return self._convert_tracks_streamed(tracks, dst_format, window, scratch, (shaping, segment), finish_kw, "convert_tracks_to_pcm_streamed_shaped")
 
-    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None):
+    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None, limit=None):
         """the loop of convert_tracks_to_pcm_streamed (shaped None) and convert_tracks_to_pcm_streamed_shaped (shaped = (shaping,
         segment)): stage a window, push it, pull whatever is available into the output window and finish it at the running output
         position, then drain the same way.  The shaped form finishes with tracks_finish_shaped_window_device and ping-pongs two
         state tensors.  `measure` (the measuring pass of the normalising forms): called once as measure(plan, table, cap, longest
         output window, device, stream), it gives a callable (_WindowMeter) that is called as (wout, first, frames) for every pulled
-        window instead of the output stage; nothing is written then, and the return is what that callable's `result()` gives."""
+        window instead of the output stage; nothing is written then, and the return is what that callable's `result()` gives.
+        `limit` (the limited form): called once as limit(table, cap, output window, stream), it gives a _WindowLimiter, which sits
+        between the pull and the stage behind it -- that stage then sees the limited windows the limiter emits, ascending and
+        contiguous from frame 0 like the pulled ones, and the rest of them after the final pull."""
         import torch
         tracks, plan = self._tracks_checked(tracks)
         n, dev = len(tracks), tracks[0].device
@@ -2243,12 +2396,25 @@ class Resampler:
             # the history of every (track, channel): read from one tensor and written to the other, window after window
             states = [torch.zeros((self.nstreams, self.nch, RRX_SHAPE_MAX_ORDER), dtype=torch.float64, device=dev) for _ in range(2)]
 
-            def shaped_window(first, frames):
+            def shaped_window(buf, first, frames):
                 kw = dict({"gain": None, "dither": True, "seed": 0}, **finish_kw)
-                _tracks_finish_shaped_window(wout, table, cap, first, frames, dst_format, plan.dst_total, shaped[0], shaped[1], kw["gain"],
+                _tracks_finish_shaped_window(buf, table, cap, first, frames, dst_format, plan.dst_total, shaped[0], shaped[1], kw["gain"],
                                              kw["dither"], kw["seed"], states[0], states[1], kw["out"], kw["peak"], kw["clipped"], kw["stream"])
         if finish_kw.get("gain") is not None and not hasattr(finish_kw["gain"], "data_ptr"):
             finish_kw["gain"] = torch.full((self.nstreams,), float(finish_kw["gain"]), dtype=torch.float64, device=dev)  # (once, not per window)
+        if limit is not None:
+            limit = limit(table, cap, wout, cur)
+
+        def stage(buf, first, k):  # what follows the pull: frames [first, first + k) of the rows, in `buf`
+            if measure is not None:
+                if k:
+                    measure(buf, first, k)
+            elif shaped is None:
+                tracks_finish_window_device(buf, table, cap, first, k, dst_format, plan.dst_total, **finish_kw)
+            elif k:  # (an empty window touches nothing, the state included: the two tensors keep their roles)
+                shaped_window(buf, first, k)
+                states.reverse()
+
         got = 0
         if total:
             packed = torch.cat(tracks).contiguous()
@@ -2261,14 +2427,12 @@ class Resampler:
                         if got >= cap:
                             raise RuntimeError("%s: more output than %d frames in gives" % (who, total))
                         k = self.pull_device(wout, min(wout.shape[1], cap - got), stride=wout.shape[1])
-                        if measure is not None:
-                            if k:
-                                measure(wout, got, k)
-                        elif shaped is None:
-                            tracks_finish_window_device(wout, table, cap, got, k, dst_format, plan.dst_total, **finish_kw)
-                        elif k:  # (an empty window touches nothing, the state included: the two tensors keep their roles)
-                            shaped_window(got, k)
-                            states.reverse()
+                        if limit is None:
+                            stage(wout, got, k)
+                        elif k:
+                            emitted = limit.feed(wout, k)
+                            if emitted is not None:
+                                stage(*emitted)
                         got += k
 
                 for pos in range(0, total, window):
@@ -2286,6 +2450,9 @@ class Resampler:
         need = max(int(e.out_first + e.out_frames) for e in plan.table)
         if got < need:
             raise RuntimeError("%s: %d output frames where the plan expects %d" % (who, got, need))
+        if limit is not None:  # (every slice ends inside the `got` frames: rows of that length hold the same slices)
+            for emitted in limit.flush(got):
+                stage(*emitted)
         if measure is not None:
             return measure.result()
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
@@ -2395,6 +2562,31 @@ class Resampler:
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n], gain[:n], true_peak[:n], lufs[:n]
 
+    def _gain_by_loudness(self, energy, hops, n, album, weights, target_lufs, cur):
+        """(gain, lufs), both [rows], of the limited conversions from the hop energies of the rows: 10 ** ((target_lufs - L) / 20), 1.0
+        where no block passed the gates; with `album` L is the loudness of the track's album"""
+        import torch
+        rate = int(self.cfg.out_rate)
+        rows, dev = energy.shape[0], energy.device
+        if album is None:
+            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
+            lufs, passed = integrated_lufs(result), result[:, 1] > 0
+        else:
+            nalbums = max(album) + 1
+            of = torch.tensor(album, dtype=torch.int64, device=dev)
+            groups = torch.full((rows,), -1, dtype=torch.int32, device=dev)  # the streams without a track are in no album
+            groups[:n] = of.to(torch.int32)
+            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
+            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
+            per_album = integrated_lufs(result)
+            lufs = torch.full((rows,), float("-inf"), dtype=per_album.dtype, device=dev)
+            lufs[:n] = per_album[of]
+            passed = torch.zeros((rows,), dtype=torch.bool, device=dev)
+            passed[:n] = (result[:, 1] > 0)[of]
+        by_loudness = torch.pow(10.0, (float(target_lufs) - torch.where(passed, lufs, torch.zeros_like(lufs))) / 20.0)
+        gain = torch.where(passed, by_loudness, torch.ones_like(by_loudness)).contiguous()
+        return gain, lufs
+
     def convert_tracks_to_pcm_loudness_limited(self, tracks, dst_format, target_lufs=-14.0, max_dbtp=-1.0, lookahead_ms=1.5, hold_ms=10.0,
                                                weights=None, shaping=None, segment=65536, dither=False, seed=0, album=None):
         """convert_tracks_to_pcm_loudness_normalized with a true-peak LIMITER in place of the peak-bound gain: a track with a few
@@ -2422,23 +2614,7 @@ class Resampler:
         n = len(tracks)
         cur = torch.cuda.current_stream(out.device)
         energy, hops = tracks_loudness_device(out, table, rate, stream=cur)
-        if album is None:
-            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
-            lufs, passed = integrated_lufs(result), result[:, 1] > 0
-        else:
-            nalbums = max(album) + 1
-            of = torch.tensor(album, dtype=torch.int64, device=out.device)
-            groups = torch.full((out.shape[0],), -1, dtype=torch.int32, device=out.device)  # the streams without a track are in no album
-            groups[:n] = of.to(torch.int32)
-            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
-            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
-            per_album = integrated_lufs(result)
-            lufs = torch.full((out.shape[0],), float("-inf"), dtype=per_album.dtype, device=out.device)
-            lufs[:n] = per_album[of]
-            passed = torch.zeros((out.shape[0],), dtype=torch.bool, device=out.device)
-            passed[:n] = (result[:, 1] > 0)[of]
-        by_loudness = torch.pow(10.0, (float(target_lufs) - torch.where(passed, lufs, torch.zeros_like(lufs))) / 20.0)
-        gain = torch.where(passed, by_loudness, torch.ones_like(by_loudness)).contiguous()
+        gain, lufs = self._gain_by_loudness(energy, hops, n, album, weights, target_lufs, cur)
         _, reduction, limited = tracks_limit_device(out, table, ceiling, gain=gain, lookahead=lookahead, hold=hold, stream=cur)
         true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
         m = torch.maximum(true_peak, sample_peak).amax(1)
@@ -2532,6 +2708,63 @@ class Resampler:
         del energy, hops, result, sample_peak, m  # (pass B runs in the streamed form's memory, beside what is returned)
         views, peak, clipped = self._streamed_under_gain(tracks, dst_format, window, shaping, segment, gain.contiguous(), dither, seed, who)
         return views, peak, clipped, gain[:n], true_peak[:n], lufs[:n]
+
+    def convert_tracks_to_pcm_streamed_loudness_limited(self, tracks, dst_format, target_lufs=-14.0, max_dbtp=-1.0, lookahead_ms=1.5,
+                                                        hold_ms=10.0, weights=None, window=None, shaping=None, segment=65536, dither=False,
+                                                        seed=0, album=None):
+        """convert_tracks_to_pcm_loudness_limited in bounded memory: the same inputs, the same (views, peak, clipped, gain, trim,
+        reduction, limited, lufs), equal bit for bit whatever `window` is, and no rows.  Three passes over the same windows, with
+        reset() between them.  Pass A measures the hop energies of every pulled window (tracks_loudness_window_device); the gain
+        comes from convert_tracks_to_pcm_loudness_limited's own expressions, on the device.  Pass B converts again and limits under
+        that gain by windows: the limiter has nothing recursive in it, so it needs no state, only a halo -- a carry buffer per row
+        keeps the frames within reach of what is not emitted yet, and tracks_limit_window_device emits every frame once its
+        look-ahead has been pulled; the limited windows are measured with tracks_true_peak_window_device, which gives `trim`,
+        and the limiter's own statistics `reduction` and `limited`.  Pass C converts and limits once more, statistics into scratch,
+        and finishes the limited windows, shaped or not, under `trim`.  The tracks are resampled three times and limited twice:
+        that is the price of never holding the rows ("Windows with the limiter").  Memory: that of the streamed
+        form, plus per row two carry buffers of back + ahead + one output window frames and one limited window, the hop
+        energies and the states of the measuring passes."""
+        import functools
+        import torch
+        tracks = list(tracks)
+        if album is not None:
+            album = [int(v) for v in album]
+            if len(album) != len(tracks) or any(v < 0 for v in album):
+                raise ValueError("album is one non-negative int per track")
+        if shaping is not None:
+            _shaping(shaping, segment)  # (refused before anything is converted)
+        who = "convert_tracks_to_pcm_streamed_loudness_limited"
+        rate = int(self.cfg.out_rate)
+        ceiling = 10.0 ** (float(max_dbtp) / 20.0)
+        lookahead = min(max(int(round(float(lookahead_ms) * rate / 1000.0)), 1), RRX_LIMIT_MAX_LOOKAHEAD)
+        hold = min(max(int(round(float(hold_ms) * rate / 1000.0)), 0), RRX_LIMIT_MAX_HOLD)
+        n = len(tracks)
+        # pass A: the loudness
+        _, _, energy, hops = self._convert_tracks_streamed(tracks, dst_format, window, None, None, {}, who,
+                                                           measure=functools.partial(_WindowMeter, rate, self.nch))
+        dev = energy.device
+        cur = torch.cuda.current_stream(dev)
+        gain, lufs = self._gain_by_loudness(energy, hops, n, album, weights, target_lufs, cur)
+        del energy, hops
+        # pass B: what the limiter leaves over the ceiling, and its statistics
+        rows = gain.shape[0]
+        reduction = torch.ones((rows,), dtype=torch.float64, device=dev)
+        limited = torch.zeros((rows,), dtype=torch.int64, device=dev)
+        self.reset()
+        true_peak, sample_peak, _, _ = self._convert_tracks_streamed(
+            tracks, dst_format, window, None, None, {}, who, measure=functools.partial(_WindowMeter, None, self.nch),
+            limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, reduction, limited))
+        m = torch.maximum(true_peak, sample_peak).amax(1)
+        ok = torch.isfinite(m) & (m > 0)
+        trim = torch.where(ok, torch.clamp(torch.full_like(m, ceiling) / torch.where(ok, m, torch.ones_like(m)), max=1.0), torch.ones_like(m)).contiguous()
+        del true_peak, sample_peak, m
+        # pass C: the same limited windows, finished under the trim
+        self.reset()
+        kw = dict(gain=trim[:n].contiguous(), dither=dither, seed=seed)
+        views, peak, clipped = self._convert_tracks_streamed(
+            tracks, dst_format, window, None, None if shaping is None else (shaping, segment), kw, who,
+            limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, torch.ones_like(reduction), torch.zeros_like(limited)))
+        return views, peak, clipped, gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
 
     def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut

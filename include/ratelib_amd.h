@@ -961,6 +961,58 @@ int RRX_debug_tracks_loudness_window_host(const RRX_track *tracks, int ntracks, 
                                           double *state_out, double *energy, size_t energy_stride, unsigned long long *hops,
                                           double *work, size_t work_doubles);
 
+/* RRX_tracks_limit_device by windows.  The limiter has nothing recursive in it, so a window needs no state from the one before,
+ * only a HALO of input: the gain s[n] of RRX_limit_device depends on the samples of the frames [n - back, n + ahead] and on
+ * nothing else, with
+ *   back  = (L - 1) + H + D,   ahead = (L - 1) + D            (L = lookahead, H = hold, D = taps - 1)
+ * because m[n - i], i < L, covers r[F] for F in [n - (L - 1) - H, n + L - 1 + D], and r[F] reads g[F - D .. F].
+ * RRX_limit_window_reach (host only) gives the two numbers: RR_INVPARAM for a NULL pointer, taps outside 1..RRX_TP_MAX_TAPS,
+ * lookahead outside 1..RRX_LIMIT_MAX_LOOKAHEAD or hold above RRX_LIMIT_MAX_HOLD.
+ *
+ * Geometry.  The rows are virtual, of row_frames frames, as in the other window calls; track t is its slice [out_first, out_first
+ * + out_frames) of row t, clamped to the row as in RRX_tracks_limit_device.  d_buf, [ntracks][buf_stride][nch] of src_format,
+ * holds the frames [buf_first, buf_first + buf_frames) of every row; d_dst is [ntracks][dst_stride][nch] of dst_format, and
+ * d_dst[t][j] receives frame win_first + j.  Of every slice the frames inside [win_first, win_first + win_frames) are emitted.
+ * Arithmetic.  The emitted frames are those of a one-stream RRX_limit_device call on the WHOLE slice under d_gain[t], restricted
+ * to those frames: the history in front of the slice and behind it is +0.0, not what the buffer holds there.  Nothing else of
+ * d_dst is written; d_buf is only read.  d_reduction and d_limited ([ntracks]) accumulate over the emitted frames as in the
+ * whole-row call.  So any set of disjoint windows that covers [0, row_frames), in ANY order, each given the same d_reduction and
+ * d_limited, leaves in the emitted frames the bits of one RRX_tracks_limit_device call, with the same two statistics.  The price
+ * is that every window evaluates the detector on back + ahead frames more than it emits.
+ * Coverage.  The buffer must hold the window and its halo as far as the row goes:
+ *   buf_first <= max(0, win_first - back),   buf_first + buf_frames >= min(row_frames, win_first + win_frames + ahead),
+ *   buf_first + buf_frames <= row_frames (and no wrap),   buf_stride >= buf_frames,   dst_stride >= win_frames.
+ * In place is not offered -- the back halo of the next window must be unlimited input -- so any overlap of the extents of d_dst
+ * and d_buf is refused.
+ * d_work: at least RRX_tracks_limit_window_work_doubles(ntracks, win_frames, taps, lookahead, hold) doubles, which is
+ * ntracks * 2 * (win_frames + 2 * lookahead + hold + 2 * taps) -- r needs win_frames + 2 L - 2 + H + D entries, m needs
+ * win_frames + L - 1 -- or 0 for arguments the call refuses and for a product of 2^60 or more (host only).
+ * A wrong table gives wrong samples, never an access outside d_buf, d_dst or d_work; a sample the arithmetic asks for that lies
+ * outside the buffer reads as +0.0.  Three launches as in RRX_limit_device, each on the sub-range the window needs and split over
+ * chunks of 32768 tracks.  The call only enqueues: no allocation, no host synchronisation; coefs, device and hip_stream as in
+ * RRX_limit_device.
+ * Returns RR_INVPARAM, before any device is touched, for a NULL table, buffer or destination, ntracks < 1, nch < 1, an unknown
+ * format, ntracks * row_frames * nch or either buffer of 2^60 samples or more, a window that wraps or does not lie inside the
+ * rows, a violation of the coverage rule, the overlap of d_dst and d_buf, and the filter, ceiling, lookahead, hold and work
+ * refusals of RRX_limit_device (the work rule being the function above); the rest as there.  win_frames == 0 or row_frames == 0
+ * is RR_OK and touches nothing. */
+int RRX_limit_window_reach(int taps, size_t lookahead, size_t hold, size_t *back, size_t *ahead);
+size_t RRX_tracks_limit_window_work_doubles(int ntracks, size_t win_frames, int taps, size_t lookahead, size_t hold);
+int RRX_tracks_limit_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                   int src_format, const void *d_buf, size_t buf_stride, size_t buf_first, size_t buf_frames,
+                                   size_t row_frames, size_t win_first, size_t win_frames, int dst_format, void *d_dst,
+                                   size_t dst_stride, const double *d_gain, double ceiling, const double *coefs, int phases,
+                                   int taps, size_t lookahead, size_t hold, double *d_reduction, unsigned long long *d_limited,
+                                   double *d_work, size_t work_doubles);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the call above on HOST pointers
+ * and a HOST table, as one serial loop per track over the very functions the kernels call.  Same refusals, same results. */
+int RRX_debug_tracks_limit_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *buf,
+                                       size_t buf_stride, size_t buf_first, size_t buf_frames, size_t row_frames,
+                                       size_t win_first, size_t win_frames, int dst_format, void *dst, size_t dst_stride,
+                                       const double *gain, double ceiling, const double *coefs, int phases, int taps,
+                                       size_t lookahead, size_t hold, double *reduction, unsigned long long *limited,
+                                       double *work, size_t work_doubles);
+
 /* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: what the two window calls take
  * from one HOST table entry for the window [win_first, win_first + win_frames) of rows of row_frames frames, computed by the very
  * functions their kernels call.  stage[10]: the window-relative half-open ranges of the backward extension, the copied track, the

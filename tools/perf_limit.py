@@ -19,6 +19,19 @@ One JSON line per shape and per residual table, appended to --out (default profi
   {"residuals": {signal: {"+3dB" ...: {lookahead: overshoot}}}}
 
   python tools/perf_limit.py [--configs 1,3] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE] [--no-residuals]
+
+Windows.  `--window W` times the window form instead (RRX_tracks_limit_window_device, DESIGN.md 11 "Windows with the limiter"): the
+float32 output tensor of config 1 as whole-row tracks, limited in windows of W frames -- every window from the frames of the rows
+within its reach, into one window buffer -- against RRX_tracks_limit_device on the same rows in the same run, interleaved as above.
+A window evaluates the detector on back + ahead frames more than it emits, so the expectation is the whole-row time plus the
+detector's time * (back + ahead) / W plus three launches a window; the true-peak pass on the same rows stands in for the detector,
+which runs the same filter.  One line per (lookahead, hold), appended to profiles/limit_window_perf.jsonl:
+
+  {"config", "streams", "nch", "frames", "window", "windows", "lookahead", "hold", "back", "ahead", "whole_ms", "window_ms", "ms_rounds",
+   "whole_ms_rounds", "ratio", "true_peak_ms", "expected_ms": whole_ms + true_peak_ms * (back + ahead) / window, "excess_ms",
+   "excess_us_per_window", "steps", "warmup"}
+
+  python tools/perf_limit.py --window 4354 [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -32,6 +45,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import foo_dsp_resampler_amd as F  # noqa: E402
@@ -95,6 +109,75 @@ def one_config(k, steps, warmup, rounds):
     return lines
 
 
+def window_config(k, W, steps, warmup, rounds):
+    stream = torch.cuda.Stream()
+    x, _ = step_tensor(k, stream)
+    S, frames, nch = x.shape
+    phases, taps, coefs = F.TRUE_PEAK_FILTERS["bs1770"]
+    co = (C.c_double * len(coefs))(*coefs)
+    table = np.zeros((S, 6), np.uint64)  # only the output slices are looked at: every track is its whole row
+    table[:, 4] = frames
+    with torch.cuda.stream(stream):
+        # the rows with one row of slack behind them: a window's buffer begins buf_first frames into the rows, at the rows' own pitch
+        mem = torch.zeros((S * frames * nch + frames * nch,), dtype=torch.float32, device="cuda")
+        rows = mem[:S * frames * nch].view(S, frames, nch)
+        rows.copy_(x)
+        d_table = torch.from_numpy(table.view(np.int64)).cuda()
+        out = torch.empty_like(x)
+        wout = torch.empty((S, W, nch), dtype=torch.float32, device="cuda")
+        tp = torch.zeros((S, nch), dtype=torch.float64, device="cuda")
+        pk = torch.zeros((S, nch), dtype=torch.float64, device="cuda")
+        red = torch.ones((S,), dtype=torch.float64, device="cuda")
+        lim = torch.zeros((S,), dtype=torch.int64, device="cuda")
+        work = torch.empty((max(F.limit_work_doubles(S, frames, taps, 1024), F.tracks_limit_window_work_doubles(S, W, taps, 1024, 4096)),),
+                           dtype=torch.float64, device="cuda")
+        ceiling = 0.5 * float(x.abs().max())
+    stream.synchronize()
+    windows = [(first, min(W, frames - first)) for first in range(0, frames, W)]
+
+    def whole(L, H):
+        def call():
+            F.ratelib._check(F.lib().RRX_tracks_limit_device(-1, C.c_void_p(stream.cuda_stream), C.c_void_p(d_table.data_ptr()), S, nch, F.RRX_FMT_FLOAT,
+                                                             C.c_void_p(rows.data_ptr()), F.RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames, None,
+                                                             ceiling, C.cast(co, C.c_void_p), phases, taps, L, H, C.c_void_p(red.data_ptr()),
+                                                             C.c_void_p(lim.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+                             "RRX_tracks_limit_device")
+        return call
+
+    def by_windows(L, H):
+        back, ahead = F.limit_window_reach(L, H)
+
+        def call():
+            for first, n in windows:
+                b0, b1 = max(0, first - back), min(frames, first + n + ahead)
+                F.ratelib._check(F.lib().RRX_tracks_limit_window_device(
+                    -1, C.c_void_p(stream.cuda_stream), C.c_void_p(d_table.data_ptr()), S, nch, F.RRX_FMT_FLOAT,
+                    C.c_void_p(rows.data_ptr() + b0 * nch * 4), frames, b0, b1 - b0, frames, first, n, F.RRX_FMT_FLOAT, C.c_void_p(wout.data_ptr()),
+                    W, None, ceiling, C.cast(co, C.c_void_p), phases, taps, L, H, C.c_void_p(red.data_ptr()), C.c_void_p(lim.data_ptr()),
+                    C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_limit_window_device")
+        return call
+
+    def true_peak():
+        return F.true_peak_device(rows, true_peak=tp, peak=pk, stream=stream)
+
+    lines = []
+    for L, H in PAIRS:
+        back, ahead = F.limit_window_reach(L, H)
+        a, b, wms, wins, tms = whole(L, H), by_windows(L, H), [], [], []
+        for _ in range(rounds):
+            wms.append(timed(stream, a, steps, warmup))
+            wins.append(timed(stream, b, steps, warmup))
+            tms.append(timed(stream, true_peak, steps, warmup))
+        m, v, t = statistics.median(wms), statistics.median(wins), statistics.median(tms)
+        expected = m + t * (back + ahead) / W
+        lines.append({"config": k, "streams": S, "nch": nch, "frames": frames, "window": W, "windows": len(windows), "lookahead": L, "hold": H,
+                      "back": back, "ahead": ahead, "whole_ms": round(m, 4), "window_ms": round(v, 4), "ms_rounds": [round(u, 4) for u in wins],
+                      "whole_ms_rounds": [round(u, 4) for u in wms], "ratio": round(v / m, 3), "true_peak_ms": round(t, 4),
+                      "expected_ms": round(expected, 4), "excess_ms": round(v - expected, 4),
+                      "excess_us_per_window": round((v - expected) * 1000.0 / len(windows), 2), "steps": steps, "warmup": warmup})
+    return lines
+
+
 def residuals():
     ceiling = 10.0 ** (-1.0 / 20.0)
     gen = torch.Generator(device="cuda").manual_seed(7)
@@ -123,15 +206,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-residuals", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "limit_perf.jsonl"))
+    ap.add_argument("--window", type=int, default=0, help="time the window form in windows of this many frames (config 1) instead")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_limit.py needs a GPU: there is nothing to time without one")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "limit_window_perf.jsonl" if a.window else "limit_perf.jsonl")
     lines = []
-    for k in [int(v) for v in a.configs.split(",") if v]:
-        lines += one_config(k, a.steps, a.warmup, a.rounds)
-    if not a.no_residuals:
-        lines.append(residuals())
+    if a.window:
+        if a.window < 1:
+            raise SystemExit("--window is a positive frame count")
+        lines += window_config(1, a.window, a.steps, a.warmup, a.rounds)
+    else:
+        for k in [int(v) for v in a.configs.split(",") if v]:
+            lines += one_config(k, a.steps, a.warmup, a.rounds)
+        if not a.no_residuals:
+            lines.append(residuals())
     for line in lines:
         text = json.dumps(line)
         print(text, flush=True)
