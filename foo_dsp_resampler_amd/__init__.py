@@ -15,7 +15,8 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       loudness_normalizing_gain, loudness_blocks_device, loudness_gate_groups_device, loudness_range_device, loudness_range_lu,
                       loudness_meter_device, tracks_true_peak_window_device, tracks_loudness_window_device, RRX_LOUDNESS_WIN_STATE,
                       limit_device, tracks_limit_device, limit_work_doubles, RRX_LIMIT_MAX_LOOKAHEAD, RRX_LIMIT_MAX_HOLD,
-                      limit_window_reach, tracks_limit_window_work_doubles, tracks_limit_window_device)
+                      limit_window_reach, tracks_limit_window_work_doubles, tracks_limit_window_device,
+                      PackedPlan, PackedTable, packed_plan, tracks_true_peak_packed_device, tracks_loudness_packed_device, scan_tracks_pcm)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
@@ -28,4 +29,5 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "loudness_normalizing_gain", "loudness_blocks_device", "loudness_gate_groups_device", "loudness_range_device", "loudness_range_lu",
            "loudness_meter_device", "tracks_true_peak_window_device", "tracks_loudness_window_device", "RRX_LOUDNESS_WIN_STATE",
            "limit_device", "tracks_limit_device", "limit_work_doubles", "RRX_LIMIT_MAX_LOOKAHEAD", "RRX_LIMIT_MAX_HOLD",
-           "limit_window_reach", "tracks_limit_window_work_doubles", "tracks_limit_window_device"]
+           "limit_window_reach", "tracks_limit_window_work_doubles", "tracks_limit_window_device",
+           "PackedPlan", "PackedTable", "packed_plan", "tracks_true_peak_packed_device", "tracks_loudness_packed_device", "scan_tracks_pcm"]

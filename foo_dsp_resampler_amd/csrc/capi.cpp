@@ -1103,6 +1103,74 @@ int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d
   return rsmp::launch_true_peak(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
+namespace {
+
+// RRX_tracks_true_peak_packed_device / RRX_debug_tracks_true_peak_packed_host: everything that can be refused from the arguments
+// alone; `kind` is the source's rsmp::TracksSrc
+int true_peak_packed_args(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *packed, size_t src_total, size_t max_frames,
+                          const double *gain, const double *coefs, int phases, int taps, double *true_peak, double *peak,
+                          rsmp::TruePeakArgs &a, int &kind)
+{
+  if (!tracks || !packed || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  kind = tracks_src_kind(src_format);
+  if (kind < 0) return RR_INVPARAM;
+  if (!true_peak && !peak) return RR_INVPARAM;
+  const int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (src_total > most || max_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  a.src = packed;
+  a.gain = gain;
+  a.state_in = nullptr;
+  a.state_out = nullptr;
+  a.true_peak = true_peak;
+  a.peak = peak;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(tracks);
+  a.src_stride = src_total;
+  a.frames = max_frames;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  a.src_double = 0;
+  a.flush = 1;
+  return RR_OK;
+}
+
+} // namespace
+
+// True peak and sample peak of tracks at rest in a packed source (true_peak.hip).  Refusals first, as in RRX_tracks_true_peak_device.
+int RRX_tracks_true_peak_packed_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                       const void *d_packed, size_t src_total, size_t max_frames, const double *d_gain, const double *coefs,
+                                       int phases, int taps, double *d_true_peak, double *d_peak)
+{
+  rsmp::TruePeakArgs a;
+  int kind = 0;
+  const int rc = true_peak_packed_args(d_tracks, ntracks, nch, src_format, d_packed, src_total, max_frames, d_gain, coefs, phases, taps,
+                                       d_true_peak, d_peak, a, kind);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!max_frames || !src_total) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_true_peak_packed(static_cast<hipStream_t>(hip_stream), a, kind) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_true_peak_packed_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *packed, size_t src_total,
+                                           size_t max_frames, const double *gain, const double *coefs, int phases, int taps,
+                                           double *true_peak, double *peak)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::TruePeakArgs a;
+  int kind = 0;
+  const int rc = true_peak_packed_args(tracks, ntracks, nch, src_format, packed, src_total, max_frames, gain, coefs, phases, taps, true_peak,
+                                       peak, a, kind);
+  if (rc != RR_OK) return rc;
+  if (max_frames && src_total) rsmp::true_peak_packed_host(a, kind);
+  return RR_OK;
+}
+
 // r and m of every stream (limit.hip), frames + taps + lookahead doubles each: 0 for what the data calls refuse
 size_t RRX_limit_work_doubles(int nstreams, size_t frames, int taps, size_t lookahead)
 {
@@ -1416,6 +1484,80 @@ int RRX_tracks_loudness_device(int device, void *hip_stream, const RRX_track *d_
   a.nch = nch;
   a.src_double = src_format == RRX_FMT_DOUBLE;
   return rsmp::launch_loudness(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+namespace {
+
+// RRX_tracks_loudness_packed_device / RRX_debug_tracks_loudness_packed_host: everything that can be refused from the arguments
+// alone; `kind` is the source's rsmp::TracksSrc
+int loudness_packed_args(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *packed, size_t src_total, size_t max_frames,
+                         const double *gain, const double *coefs, size_t hop, double *energy, size_t energy_stride, unsigned long long *hops,
+                         double *work, size_t work_doubles, rsmp::LoudnessArgs &a, int &kind)
+{
+  if (!tracks || !packed || ntracks < 1 || nch < 1 || !energy || !hops) return RR_INVPARAM;
+  kind = tracks_src_kind(src_format);
+  if (kind < 0) return RR_INVPARAM;
+  const int rc = loudness_filter(coefs, hop, a);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (src_total > most || max_frames > most / size_t(ntracks) || energy_stride > most / size_t(ntracks)) return RR_INVPARAM;
+  const unsigned long long need = rsmp::loudness_work_doubles(ntracks, nch, max_frames, hop);
+  if (work_doubles < need || (need && !work)) return RR_INVPARAM;
+  a.src = packed;
+  a.gain = gain;
+  a.state_in = nullptr;
+  a.state_out = nullptr;
+  a.energy = energy;
+  a.work = work;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(tracks);
+  a.hops_out = hops;
+  a.src_stride = src_total;
+  a.frames = max_frames;
+  a.hop = hop;
+  a.max_hops = max_frames / hop;
+  a.first_hop = 0;
+  a.energy_stride = energy_stride;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  a.src_double = 0;
+  return RR_OK;
+}
+
+} // namespace
+
+// K-weighted hop energies of tracks at rest in a packed source (loudness.hip).  Refusals first, as in RRX_tracks_loudness_device.
+int RRX_tracks_loudness_packed_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                      const void *d_packed, size_t src_total, size_t max_frames, const double *d_gain, const double *coefs,
+                                      size_t hop, double *d_energy, size_t energy_stride, unsigned long long *d_hops, double *d_work,
+                                      size_t work_doubles)
+{
+  rsmp::LoudnessArgs a;
+  int kind = 0;
+  const int rc = loudness_packed_args(d_tracks, ntracks, nch, src_format, d_packed, src_total, max_frames, d_gain, coefs, hop, d_energy,
+                                      energy_stride, d_hops, d_work, work_doubles, a, kind);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!max_frames || !src_total) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_loudness_packed(static_cast<hipStream_t>(hip_stream), a, kind) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_loudness_packed_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *packed, size_t src_total,
+                                          size_t max_frames, const double *gain, const double *coefs, size_t hop, double *energy,
+                                          size_t energy_stride, unsigned long long *hops, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LoudnessArgs a;
+  int kind = 0;
+  const int rc = loudness_packed_args(tracks, ntracks, nch, src_format, packed, src_total, max_frames, gain, coefs, hop, energy, energy_stride,
+                                      hops, work, work_doubles, a, kind);
+  if (rc != RR_OK) return rc;
+  if (max_frames && src_total) rsmp::loudness_packed_host(a, kind);
+  return RR_OK;
 }
 
 // The two-stage gate over hop energies (loudness.hip).  Refusals first, as in RRX_finish_device.

@@ -78,8 +78,8 @@ struct LoudnessArgs {
   double *work;                    // [nstreams][max_hops][nch][4]: z_k after pass 1, S_k after the carry
   const Track *tracks;             // [nstreams] on the device: stream t is track t's slice of row t, from +0.0
   unsigned long long *hops_out;    // [nstreams], tracks only: the hops measured per track
-  unsigned long long src_stride;   // SAMPLES between streams (tracks: unused)
-  unsigned long long frames;       // per stream (tracks: the rows' length, row_frames)
+  unsigned long long src_stride;   // SAMPLES between streams (tracks: unused; packed: FRAMES of the source, src_total)
+  unsigned long long frames;       // per stream (tracks: the rows' length, row_frames; packed: max_frames)
   unsigned long long hop, max_hops; // max_hops = frames / hop: what a stream has (tracks: at most)
   unsigned long long first_hop;    // first_frame / hop
   unsigned long long energy_stride;
@@ -123,6 +123,12 @@ hipError_t launch_loudness(hipStream_t stream, const LoudnessArgs &a);
 hipError_t launch_loudness_gate(hipStream_t stream, const LoudnessGateArgs &a);
 // The plain call's results on host pointers, as serial loops over the functions above (test hooks).
 void loudness_host(const LoudnessArgs &a);
+// RRX_tracks_loudness_packed_device: a.src is a packed source of `kind` (TracksSrc) of a.src_stride frames, a.tracks the table,
+// a.frames the most frames a track is measured for (max_hops = a.frames / hop); track t is tracks_packed_cut's clamp of its entry,
+// from +0.0.  The kernel arguments keep their layout, so the kind travels beside them.  The second is its host twin: the loops of
+// loudness_host over the same rows, which also leaves hops_out.
+hipError_t launch_loudness_packed(hipStream_t stream, const LoudnessArgs &a, int kind);
+void loudness_packed_host(const LoudnessArgs &a, int kind);
 void loudness_gate_host(const LoudnessGateArgs &a);
 
 } // namespace rsmp

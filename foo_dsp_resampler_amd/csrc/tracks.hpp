@@ -40,6 +40,56 @@ __host__ __device__ __forceinline__ float tracks_load_sample(int kind, const voi
   }
 }
 
+// The measuring path (RRX_tracks_true_peak_packed_device / RRX_tracks_loudness_packed_device, include/ratelib_amd.h) reads a
+// packed source as the meters' fp64: v = (double)s * 2^-bits, bits = 15 / 23 / 31, or (double)x for float32.  This is exact for
+// all four kinds, and for S32 deliberately NOT the stage pass's value above, which is rounded to float32: a meter measures what the
+// file holds, so INT32_MAX is 1 - 2^-31 and not 1.0.  One sample as it is stored is a float, short, TracksS24 or int; the
+// kernels keep samples in flight in that form and convert where they use them.
+struct TracksS24 {
+  unsigned char b[3]; // little endian, two's complement
+};
+
+__host__ __device__ __forceinline__ double tracks_value(float x) { return (double)x; }
+__host__ __device__ __forceinline__ double tracks_value(double x) { return x; } // (the rows of the row forms)
+__host__ __device__ __forceinline__ double tracks_value(short s) { return (double)s * 0x1p-15; }
+__host__ __device__ __forceinline__ double tracks_value(int s) { return (double)s * 0x1p-31; }
+__host__ __device__ __forceinline__ double tracks_value_s24(int s) { return (double)s * 0x1p-23; } // s: the sign-extended sample
+__host__ __device__ __forceinline__ double tracks_value(TracksS24 r)
+{
+  return tracks_value_s24((int)r.b[0] | ((int)r.b[1] << 8) | (int)(signed char)r.b[2] * 65536);
+}
+
+// Sample i of a packed source at `base` as that double: tracks_load_sample's switch for the measuring path.  The kernels
+// (true_peak.hip, loudness.hip: instantiated per kind, through the same tracks_value) and the host twins behind
+// RRX_debug_tracks_true_peak_packed_host / RRX_debug_tracks_loudness_packed_host share it.  `base` needs the alignment of one
+// sample (1 byte for S24); exactly the sample's own bytes are read.
+__host__ __device__ __forceinline__ double tracks_load_value(int kind, const void *base, unsigned long long i)
+{
+  switch (kind) {
+  case kTracksSrcS16: return tracks_value(static_cast<const short *>(base)[i]);
+  case kTracksSrcS24: return tracks_value(static_cast<const TracksS24 *>(base)[i]);
+  case kTracksSrcS32: return tracks_value(static_cast<const int *>(base)[i]);
+  default: return tracks_value(static_cast<const float *>(base)[i]);
+  }
+}
+
+// What the measuring kernels are instantiated on: S = float / double are rows of the row forms, Packed<R> a packed source whose
+// samples are stored as R.  (A tag and not a flag, so that the row forms' instantiations keep their names.)
+template <typename R> struct TracksPacked {};
+template <typename S> struct TracksSrcOf {
+  using raw = S;
+  static constexpr bool packed = false;
+};
+template <typename R> struct TracksSrcOf<TracksPacked<R>> {
+  using raw = R;
+  static constexpr bool packed = true;
+};
+template <typename R> constexpr int tracks_kind_of();
+template <> constexpr int tracks_kind_of<float>() { return kTracksSrcF32; }
+template <> constexpr int tracks_kind_of<short>() { return kTracksSrcS16; }
+template <> constexpr int tracks_kind_of<TracksS24>() { return kTracksSrcS24; }
+template <> constexpr int tracks_kind_of<int>() { return kTracksSrcS32; }
+
 // ------------------------------------------------------------------------------------------------------ interval arithmetic
 // Everything the kernels take from a table entry goes through the four functions below, which hold all the u64 clamps against
 // wrap-around: the whole-row kernels call tracks_entry / tracks_slice, the window kernels tracks_stage_cut / tracks_finish_cut,
@@ -118,6 +168,22 @@ __host__ __device__ __forceinline__ TracksSlice tracks_slice(const Track &tr, un
   s.frames = tr.out_frames < row_frames - s.of ? tr.out_frames : row_frames - s.of;
   if (write && s.frames > dst_total - s.df) s.frames = dst_total - s.df;
   return s;
+}
+
+// Track t measured at rest in the packed source (the packed meter calls): only the input side of its entry counts.  first +
+// frames <= src_total and frames <= max_frames whatever the table says, so a wrong table gives wrong numbers, never a read outside
+// the source.  The kernels and the host twins both call this.
+struct TracksPackedCut {
+  unsigned long long first, frames;
+};
+
+__host__ __device__ __forceinline__ TracksPackedCut tracks_packed_cut(const Track &tr, unsigned long long src_total, unsigned long long max_frames)
+{
+  TracksPackedCut c;
+  c.first = tr.src_first < src_total ? tr.src_first : src_total;
+  c.frames = tr.frames < src_total - c.first ? tr.frames : src_total - c.first;
+  if (c.frames > max_frames) c.frames = max_frames;
+  return c;
 }
 
 // The output stage of one track inside a window: window frames [w0, w1) are frames index, index + 1, ... of the track's slice

@@ -14,6 +14,9 @@
 //     stored value.  The workgroup whose tile holds the row's last real frame writes d_state_out from its LDS.
 //   Direct form (any other channel count): one lane per (frame, channel) by division, taps read from global memory, atomics
 //     straight to global memory (only when they beat the value there); workgroup 0 of a row writes d_state_out.
+// A row can also be a track at rest in a packed source of float32, S16, packed S24 or S32 (RRX_tracks_true_peak_packed_device):
+// the same kernels instantiated on TracksPacked<R>, whose row is tracks_packed_cut's clamp of the table entry and whose samples
+// come through tracks_load_value (tracks.hpp), one load of the sample's own bytes per sample, while the tile is staged.
 // The coefficients travel in the launch arguments.  Nothing outside the rows is read; nothing but the two result arrays and
 // d_state_out is written.
 #include "true_peak.hpp"
@@ -33,9 +36,10 @@ __device__ __forceinline__ void global_max(double *dst, unsigned long long c, un
   if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
 }
 
-// one row of work
+// one row of work: S = float / double, a stream or a track's slice of its row; S = TracksPacked<R>, a track at rest in a packed
+// source of samples stored as R (tracks.hpp)
 template <typename S> struct Row {
-  const S *src;                 // sample 0 of the row's frame 0
+  const typename TracksSrcOf<S>::raw *src; // sample 0 of the row's frame 0
   const double *state;          // channel 0 of the row in d_state_in, or null
   unsigned long long frames, n; // real frames, and frames * nch
   unsigned long long evals;     // frames to evaluate: frames, plus taps - 1 when flushed
@@ -44,19 +48,26 @@ template <typename S> struct Row {
   bool has_gain;
 };
 
-template <typename S> __device__ __forceinline__ Row<S> row_of(const TruePeakArgs &a, unsigned long long s, int taps)
+template <typename S> __host__ __device__ __forceinline__ Row<S> row_of(const TruePeakArgs &a, unsigned long long s, int taps)
 {
+  using R = typename TracksSrcOf<S>::raw;
   Row<S> r;
   const unsigned long long nch = (unsigned long long)a.nch;
   bool flush;
-  if (a.tracks) {
+  if (TracksSrcOf<S>::packed) { // src_stride: the source's frames, frames: max_frames
+    const TracksPackedCut pc = tracks_packed_cut(a.tracks[s], a.src_stride, a.frames);
+    r.src = static_cast<const R *>(a.src) + pc.first * nch;
+    r.frames = pc.frames;
+    r.state = nullptr;
+    flush = true;
+  } else if (a.tracks) {
     const TracksSlice sl = tracks_slice(a.tracks[s], a.frames, 0, false);
-    r.src = static_cast<const S *>(a.src) + (s * a.frames + sl.of) * nch;
+    r.src = static_cast<const R *>(a.src) + (s * a.frames + sl.of) * nch;
     r.frames = sl.frames;
     r.state = nullptr;
     flush = true;
   } else {
-    r.src = static_cast<const S *>(a.src) + s * a.src_stride;
+    r.src = static_cast<const R *>(a.src) + s * a.src_stride;
     r.frames = a.frames;
     r.state = a.state_in ? a.state_in + s * nch * kTpMaxTaps : nullptr;
     flush = a.flush != 0;
@@ -71,11 +82,13 @@ template <typename S> __device__ __forceinline__ Row<S> row_of(const TruePeakArg
 
 // Gained sample k of the row, k counted in samples from frame 0, channel 0 and at least -(taps - 1) * nch: RRX_finish_device's
 // g inside the row, +0.0 behind it, the state (or +0.0) in front of it.
-template <typename S> __device__ __forceinline__ double gained(const Row<S> &r, long long k, unsigned nch)
+template <typename S> __host__ __device__ __forceinline__ double gained(const Row<S> &r, long long k, unsigned nch)
 {
   if (k >= 0) {
     if ((unsigned long long)k >= r.n) return 0.0;
-    const double v = (double)r.src[k];
+    double v;
+    if constexpr (TracksSrcOf<S>::packed) v = tracks_load_value(tracks_kind_of<typename TracksSrcOf<S>::raw>(), r.src, (unsigned long long)k);
+    else v = (double)r.src[k];
     return r.has_gain ? v * r.gain : v;
   }
   if (!r.state) return 0.0;
@@ -227,22 +240,19 @@ template <typename S> void host_src(const TruePeakArgs &a)
     if (now > have) std::memcpy(dst + c, &now, 8);
   };
   for (unsigned long long s = 0; s < (unsigned long long)a.nstreams; ++s) {
-    const S *src = static_cast<const S *>(a.src) + s * a.src_stride;
-    const double gain = a.gain ? a.gain[s] : 1.0;
+    const Row<S> r = row_of<S>(a, s, taps); // the kernels' row: a stream, or a track's clamped slice
     for (unsigned long long ch = 0; ch < nch; ++ch) {
       const unsigned long long c = s * nch + ch;
       double h[kTpMaxTaps];
       for (int k = 0; k < kTpMaxTaps; ++k) h[k] = 0.0;
-      for (int j = 0; j + 1 < taps; ++j) h[j + 1] = a.state_in ? a.state_in[c * kTpMaxTaps + j] : 0.0; // h[0] is the frame to come
-      const unsigned long long evals = a.frames + (a.flush ? (unsigned long long)(taps - 1) : 0ull);
-      for (unsigned long long i = 0; i < evals; ++i) {
-        const bool real = i < a.frames; // the flushed frames are +0.0 and enter the true peak only
-        const double v = real ? (double)src[i * nch + ch] : 0.0;
-        h[0] = !real ? 0.0 : a.gain ? v * gain : v;
+      for (int j = 0; j + 1 < taps; ++j) h[j + 1] = r.state ? r.state[ch * kTpMaxTaps + j] : 0.0; // h[0] is the frame to come
+      for (unsigned long long i = 0; i < r.evals; ++i) {
+        const bool real = i < r.frames; // the flushed frames are +0.0 and enter the true peak only
+        h[0] = real ? gained(r, (long long)(i * nch + ch), (unsigned)nch) : 0.0;
         if (a.true_peak) take(a.true_peak, c, true_peak_frame<0, 0>(a.f.c, a.f.phases, taps, h));
         if (real && a.peak) take(a.peak, c, true_peak_bits(fabs(h[0])));
         for (int k = kTpMaxTaps - 1; k > 0; --k) h[k] = h[k - 1];
-        if (i + 1 == a.frames && a.state_out) // the history after the last real frame
+        if (i + 1 == r.frames && a.state_out && !a.tracks) // the history after the last real frame
           for (int j = 0; j < kTpMaxTaps; ++j) a.state_out[c * kTpMaxTaps + j] = j + 1 < taps ? h[j + 1] : 0.0;
       }
     }
@@ -260,6 +270,26 @@ void true_peak_host(const TruePeakArgs &a)
 {
   if (a.src_double) host_src<double>(a);
   else host_src<float>(a);
+}
+
+hipError_t launch_true_peak_packed(hipStream_t stream, const TruePeakArgs &a, int kind)
+{
+  switch (kind) {
+  case kTracksSrcS16: return launch_src<TracksPacked<short>>(stream, a);
+  case kTracksSrcS24: return launch_src<TracksPacked<TracksS24>>(stream, a);
+  case kTracksSrcS32: return launch_src<TracksPacked<int>>(stream, a);
+  default: return launch_src<TracksPacked<float>>(stream, a);
+  }
+}
+
+void true_peak_packed_host(const TruePeakArgs &a, int kind)
+{
+  switch (kind) {
+  case kTracksSrcS16: return host_src<TracksPacked<short>>(a);
+  case kTracksSrcS24: return host_src<TracksPacked<TracksS24>>(a);
+  case kTracksSrcS32: return host_src<TracksPacked<int>>(a);
+  default: return host_src<TracksPacked<float>>(a);
+  }
 }
 
 } // namespace rsmp

@@ -60,8 +60,8 @@ struct TruePeakArgs {
   double *state_out;               // the same layout, null = not wanted
   double *true_peak, *peak;        // [nstreams * nch] each, null = not taken
   const Track *tracks;             // [nstreams] on the device: stream t is track t's slice of row t, flushed, without a state
-  unsigned long long src_stride;   // SAMPLES between streams (tracks: unused)
-  unsigned long long frames;       // per stream (tracks: the rows' length, row_frames)
+  unsigned long long src_stride;   // SAMPLES between streams (tracks: unused; packed: FRAMES of the source, src_total)
+  unsigned long long frames;       // per stream (tracks: the rows' length, row_frames; packed: max_frames)
   int nstreams, nch;
   int src_double;
   int flush;
@@ -81,5 +81,10 @@ inline bool true_peak_lds_form(int nch, int taps)
 hipError_t launch_true_peak(hipStream_t stream, const TruePeakArgs &a);
 // The plain call's results on host pointers, as one serial loop over true_peak_frame (test hook: RRX_debug_true_peak_host).
 void true_peak_host(const TruePeakArgs &a);
+// RRX_tracks_true_peak_packed_device: a.src is a packed source of `kind` (TracksSrc) of a.src_stride frames, a.tracks the table,
+// a.frames the most frames a track is measured for; track t is tracks_packed_cut's clamp of its entry, flushed, without a state.
+// The kernel arguments keep their layout, so the kind travels beside them.  The second is its host twin, the same loop as above.
+hipError_t launch_true_peak_packed(hipStream_t stream, const TruePeakArgs &a, int kind);
+void true_peak_packed_host(const TruePeakArgs &a, int kind);
 
 } // namespace rsmp

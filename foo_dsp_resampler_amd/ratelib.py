@@ -32,6 +32,8 @@ EXPECTED_SYMBOLS = [
     "RRX_tracks_stage_device_samples", "RRX_debug_tracks_load_host",
     "RRX_tracks_stage_window_device", "RRX_tracks_finish_window_device", "RRX_debug_tracks_window_cut",
     "RRX_tracks_finish_shaped_window_device", "RRX_debug_tracks_finish_shaped_window_host",
+    "RRX_tracks_true_peak_packed_device", "RRX_debug_tracks_true_peak_packed_host",
+    "RRX_tracks_loudness_packed_device", "RRX_debug_tracks_loudness_packed_host",
     "RRX_tracks_true_peak_window_device", "RRX_debug_tracks_true_peak_window_host", "RRX_tracks_loudness_window_work_doubles",
     "RRX_tracks_loudness_window_device", "RRX_debug_tracks_loudness_window_host",
     "RRX_limit_window_reach", "RRX_tracks_limit_window_work_doubles", "RRX_tracks_limit_window_device", "RRX_debug_tracks_limit_window_host",
@@ -304,6 +306,13 @@ def lib():
             host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, sz]
             L.RRX_tracks_loudness_window_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_tracks_loudness_window_host.argtypes = host
+        if hasattr(L, "RRX_tracks_true_peak_packed_device"):  # (as above)
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, vp, vp, C.c_int, C.c_int, vp, vp]
+            L.RRX_tracks_true_peak_packed_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_true_peak_packed_host.argtypes = host
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, vp, vp, sz, vp, sz, vp, vp, sz]
+            L.RRX_tracks_loudness_packed_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_loudness_packed_host.argtypes = host
         if hasattr(L, "RRX_tracks_limit_window_device"):  # (as above)
             host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp, C.c_double, vp, C.c_int, C.c_int, sz, sz,
                     vp, vp, vp, sz]
@@ -678,6 +687,55 @@ def tracks_plan(in_rate, out_rate, lengths, **kw):
     return _tracks_plan(_config(in_rate, out_rate, **kw), list(lengths))
 
 
+class PackedTable:
+    """The device copy of a table for the packed meter calls, with what they need beside it: `tensor` (int64 [ntracks, 6]),
+    `src_total` and `max_frames`.  What PackedPlan.to_device returns."""
+
+    def __init__(self, tensor, src_total, max_frames):
+        self.tensor, self.src_total, self.max_frames = tensor, int(src_total), int(max_frames)
+
+    def __len__(self):
+        return self.tensor.shape[0]
+
+
+class PackedPlan:
+    """packed_plan's answer: `table` (a ctypes array of RRXTrack with src_first as prefix sums, frames as the lengths and zeros
+    elsewhere), `src_total` (frames of the packed source) and `max_frames` (the longest track).  `array()` is the table as uint64
+    [ntracks, 6]; `to_device(device)` uploads it, as a PackedTable."""
+
+    def __init__(self, table, src_total, max_frames):
+        self.table, self.src_total, self.max_frames = table, src_total, max_frames
+
+    def __len__(self):
+        return len(self.table)
+
+    def array(self):
+        return np.frombuffer(self.table, dtype=np.uint64).reshape(len(self.table), 6).copy()
+
+    def to_device(self, device):
+        import torch
+        return PackedTable(torch.from_numpy(self.array().view(np.int64)).to(device), self.src_total, self.max_frames)
+
+
+def packed_plan(lengths):
+    """Host-only: the table of a library at rest for tracks_true_peak_packed_device / tracks_loudness_packed_device -- tracks of
+    `lengths` frames laid end to end -- as a PackedPlan.  A scan needs no rate pair and no handle (a table of tracks_plan works
+    just as well: the packed calls read only its input side).  Needs no GPU and no library."""
+    lengths = [int(v) for v in lengths]
+    if len(lengths) < 1:
+        raise ValueError("a plan needs at least one track")
+    if min(lengths) < 0:
+        raise ValueError("track lengths are frame counts: none may be negative")
+    table = (RRXTrack * len(lengths))()
+    first = 0
+    for t, n in zip(table, lengths):
+        t.src_first, t.frames = first, n
+        first += n
+    if first >= 1 << 60:
+        raise ValueError("no source has 2^60 frames")
+    return PackedPlan(table, first, max(lengths))
+
+
 class TracksBatches:
     """RRX_tracks_batches' answer: `order` (the track indices by length descending, ties by index), `batches` (the same cut every
     `nstreams` tracks: a list of lists of indices), `row_frames` (per batch, what tracks_plan gives it), `resampled` (frames the
@@ -902,6 +960,52 @@ def tracks_true_peak_device(rows, table, gain=None, filter="bs1770", true_peak=N
                                              row_frames, C.c_void_p(gain.data_ptr()) if gain is not None else None,
                                              C.cast(coefs, C.c_void_p), phases, taps,
                                              C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())), "RRX_tracks_true_peak_device")
+    return true_peak, peak
+
+
+def _packed_table(table, max_frames, device):
+    """the table of a packed meter call as (int64 device tensor [ntracks, 6], max_frames): a PackedPlan or TracksPlan is uploaded, a
+    PackedTable brings its own max_frames, a bare device tensor needs `max_frames`"""
+    if isinstance(table, (PackedPlan, TracksPlan)):
+        import torch
+        a = table.array()
+        table = PackedTable(torch.from_numpy(a.view(np.int64)).to(device), table.src_total, int(a[:, 1].max()))
+    if isinstance(table, PackedTable):
+        table, own = table.tensor, table.max_frames
+        max_frames = own if max_frames is None else max_frames
+    elif max_frames is None:
+        raise ValueError("a bare table tensor does not say how long its tracks are: give max_frames")
+    max_frames = int(max_frames)
+    if max_frames < 0:
+        raise ValueError("max_frames is a frame count")
+    return table, max_frames
+
+
+def tracks_true_peak_packed_device(packed, table, gain=None, filter="bs1770", max_frames=None, true_peak=None, peak=None, stream=None):
+    """True peak and sample peak per track of a library at rest (RRX_tracks_true_peak_packed_device): `packed` is the source of
+    tracks_stage_device -- tracks laid end to end, float32 / int16 / int32 [src_total, nch] or uint8 [src_total, nch * 3] for packed
+    24 bit -- measured as it is stored: no float copy, no rows, no handle.  `table`: a PackedPlan / TracksPlan (uploaded here), what
+    their to_device returned, or a bare int64 device tensor [ntracks, 6] with `max_frames`, the most frames a track is measured
+    for (taken from the plan otherwise).  Only src_first and frames of an entry are read, clamped to the source.  The sample value
+    is exact -- s * 2^-15 / 2^-23 / 2^-31 in float64, so INT32_MAX peaks at 1 - 2^-31 -- and from there on every track is
+    true_peak_device's one whole stream, flushed.  `gain`, `filter`, `true_peak`, `peak` and the return value are
+    tracks_true_peak_device's.  The call only enqueues."""
+    import torch
+    table, max_frames = _packed_table(table, max_frames, packed.device if hasattr(packed, "device") else None)
+    fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
+    dev = packed.device
+    phases, taps, coefs = _true_peak_filter(filter)
+    gain = _loudness_gain(gain, ntracks, dev)
+    true_peak, peak = _true_peak_stats(true_peak, peak, ntracks, nch, dev)
+    if not max_frames or not src_total:  # (an empty tensor has no pointer, and there is nothing to do)
+        return true_peak, peak
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_true_peak_packed_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
+                                                    ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total, max_frames,
+                                                    C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(coefs, C.c_void_p),
+                                                    phases, taps, C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())),
+           "RRX_tracks_true_peak_packed_device")
     return true_peak, peak
 
 
@@ -1275,6 +1379,33 @@ def tracks_loudness_device(rows, table, rate=None, gain=None, coefs=None, hop=No
     return energy, hops
 
 
+def tracks_loudness_packed_device(packed, table, rate=None, gain=None, coefs=None, hop=None, max_frames=None, energy=None, work=None, stream=None):
+    """K-weighted hop energies per track of a library at rest (RRX_tracks_loudness_packed_device): `packed`, `table` and
+    `max_frames` as in tracks_true_peak_packed_device, everything else as in tracks_loudness_device with max_frames for
+    row_frames.  Returns (energy, hops): `energy` float64 [ntracks, nch, max_frames // hop] (allocated zeroed when not passed; one
+    that is passed may hold fewer hops, and the tracks' hops are clamped to it) and `hops` int64 [ntracks].  Feed both to
+    loudness_gate_device or loudness_meter_device.  The call only enqueues."""
+    import torch
+    table, max_frames = _packed_table(table, max_frames, packed.device if hasattr(packed, "device") else None)
+    fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
+    dev = packed.device
+    c, hop = _loudness_filter(rate, coefs, hop)
+    gain = _loudness_gain(gain, ntracks, dev)
+    n = max_frames // hop
+    energy, work = _loudness_buffers(energy, work, ntracks, nch, n if energy is None else 0, ntracks * nch * n * 4, dev)
+    hops = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
+    if not n or not energy.shape[2] or not src_total:  # (no track holds a whole hop: an empty tensor has no pointer, and there is nothing to do)
+        return energy, hops
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_tracks_loudness_packed_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
+                                                   ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total, max_frames,
+                                                   C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(c, C.c_void_p), hop,
+                                                   C.c_void_p(energy.data_ptr()), energy.shape[2], C.c_void_p(hops.data_ptr()),
+                                                   C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_loudness_packed_device")
+    return energy, hops
+
+
 def loudness_gate(abs_lufs=-70.0, rel_lu=-10.0):
     """(abs_threshold, rel_factor) of RRX_loudness_gate_device for gates given in LUFS / LU: 10 ** ((abs_lufs + 0.691) / 10) and
     10 ** (rel_lu / 10)"""
@@ -1488,6 +1619,50 @@ def loudness_meter_device(energy, hop, hops=None, weights=None, groups=None, ngr
     if groups is not None:
         out["group_integrated"] = integrated_lufs(loudness_gate_groups_device(b4, n4, groups, ngroups, stream=cur))
         out["group_range"] = loudness_range_lu(loudness_range_device(b30, n30, groups, ngroups, stream=cur))
+    return out
+
+
+def scan_tracks_pcm(tracks, rate, album=None, weights=None, filter="bs1770"):
+    """A ReplayGain 2.0 / EBU R 128 scan of tracks as they are stored: `tracks` is a list of device tensors of one dtype and
+    channel count -- float32 / int16 / int32 [frames, nch], or uint8 [frames, nch * 3] for packed 24 bit -- at `rate` Hz.  One
+    torch.cat, tracks_true_peak_packed_device, tracks_loudness_packed_device and loudness_meter_device, on the current stream and
+    without a host synchronisation; no float copy, no padding to the longest track, no handle.  Returns a dict of device tensors:
+    "true_peak" and "peak" (float64 [ntracks, nch], linear), every key of loudness_meter_device ("integrated", "momentary_max",
+    "short_term_max", "range", [ntracks]) and "track_gain_db" = -18 - integrated.  `album`: one group index per track (a sequence
+    of ints; any index below 0 keeps the track out of all groups) adds "group_integrated", "group_range", "group_true_peak" /
+    "group_peak" (the maximum over each group's tracks and channels, +0.0 for a group without a track) and "album_gain_db" =
+    -18 - group_integrated, all [ngroups] with ngroups = the largest index + 1.  `weights` is loudness_gate_device's, `filter`
+    true_peak_device's."""
+    import torch
+    tracks = list(tracks)
+    if not tracks:
+        raise ValueError("a scan needs at least one track")
+    first = tracks[0]
+    for t in tracks:
+        if not hasattr(t, "data_ptr") or t.dim() != 2 or t.dtype != first.dtype or t.shape[1] != first.shape[1] or t.device != first.device:
+            raise TypeError("the tracks must be [frames, nch] tensors of one dtype, channel count and device")
+    ngroups = None
+    if album is not None:
+        album = [int(v) for v in album]
+        if len(album) != len(tracks):
+            raise ValueError("album has %d entries for %d tracks" % (len(album), len(tracks)))
+        ngroups = max(max(album) + 1, 1)
+    dev = first.device
+    table = packed_plan([t.shape[0] for t in tracks]).to_device(dev)
+    packed = torch.cat(tracks).contiguous()
+    cur = torch.cuda.current_stream(dev) if getattr(first, "is_cuda", False) else None
+    true_peak, peak = tracks_true_peak_packed_device(packed, table, filter=filter, stream=cur)
+    hop = int(rate) // 10
+    energy, hops = tracks_loudness_packed_device(packed, table, rate=rate, stream=cur)
+    out = {"true_peak": true_peak, "peak": peak}
+    out.update(loudness_meter_device(energy, hop, hops, weights, album, ngroups))
+    out["track_gain_db"] = -18.0 - out["integrated"]
+    if album is not None:
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        for key, stat in (("group_true_peak", true_peak), ("group_peak", peak)):
+            members = [[i for i, a in enumerate(album) if a == g] for g in range(ngroups)]
+            out[key] = torch.stack([stat[m].amax() if m else zero for m in members])
+        out["album_gain_db"] = -18.0 - out["group_integrated"]
     return out
 
 

@@ -266,7 +266,7 @@ int RRX_lpc_extrapolate_device(int device, void *hip_stream, fb_sample_t *d_data
  * or device < -1; RR_EXTUNINIT before init_ratelib; RR_INVPARAM for a device index the process does not have; RR_INTERNAL for
  * a failed launch.  frames == 0 is RR_OK and does nothing.  Noise shaping is RRX_finish_shaped_device's, below; integer or planar
  * sources and float destinations are not offered. */
-#define RRX_FMT_S24_3 24   /* packed 3-byte signed 24-bit PCM: RRX_finish_device's destination only, and a source format of RRX_tracks_stage_device_samples */
+#define RRX_FMT_S24_3 24   /* packed 3-byte signed 24-bit PCM: RRX_finish_device's destination only, and a source format of RRX_tracks_stage_device_samples and of the packed meter calls (RRX_tracks_true_peak_packed_device) */
 int RRX_finish_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
                       int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
                       const double *d_gain, int dither, unsigned long long seed, unsigned long long first_frame,
@@ -543,6 +543,37 @@ int RRX_tracks_true_peak_device(int device, void *hip_stream, const RRX_track *d
                                 int src_format, const void *d_rows, size_t row_frames, const double *d_gain,
                                 const double *coefs, int phases, int taps, double *d_true_peak, double *d_peak);
 
+/* RRX_true_peak_device per track of a library AT REST: the tracks lie end to end in d_packed as [src_total][nch] samples of
+ * src_format, the packed source of RRX_tracks_stage_device_samples -- RRX_FMT_FLOAT, RRX_FMT_S16, RRX_FMT_S24_3 (three bytes,
+ * little endian, two's complement) or RRX_FMT_S32; a sample is aligned to its own size, for S24_3 one byte.  No float copy, no
+ * rows padded to the longest track, no handle and no rate pair: what a ReplayGain 2.0 / EBU R 128 scan needs.
+ * Track t uses only the input side of its RRX_track entry, clamped:
+ *   first  = min(src_first, src_total)
+ *   frames = min(frames, src_total - first, max_frames)
+ * so a wrong table gives wrong numbers, never a read outside d_packed.  max_frames plays the part row_frames plays in the row
+ * forms: it bounds the grid, and a track longer than max_frames is measured up to max_frames.  (A table of RRX_tracks_plan works,
+ * and so does one with src_first as prefix sums, frames as lengths and zeros elsewhere.)
+ * The sample value is part of this ABI: v = (double)s * 2^-15 (S16), 2^-23 (S24_3) or 2^-31 (S32), and (double)x for float32,
+ * exact for all four.  For S32 this is deliberately NOT the value of the stage pass, which rounds to float32: a meter measures
+ * what the file holds, so INT32_MAX has the peak 1 - 2^-31 and not 1.0, and INT32_MIN and -32768 have 1.0.  The gained sample is
+ * d_gain ? v * d_gain[t] : v.  From there on nothing is new: track t gets, bit for bit, the results of a one-stream
+ * RRX_true_peak_device call on a float64 buffer holding its v, with first_frame = 0, no state and flush = 1, into d_true_peak /
+ * d_peak [ntracks * nch], accumulated as in RRX_tracks_true_peak_device.
+ * Reads: exactly the bytes of the samples of the clamped tracks.  device, hip_stream, "only enqueues": as there.
+ * Refusals: RR_INVPARAM, before any device is touched, for a NULL table or source, ntracks < 1, nch < 1, a format outside the four
+ * above (RRX_FMT_DOUBLE included), the filter refusals of RRX_true_peak_device, both result pointers NULL, src_total * nch or
+ * ntracks * max_frames * nch of 2^60 or more, or device < -1; the rest as there.  max_frames == 0 or src_total == 0 is RR_OK and
+ * does nothing. */
+int RRX_tracks_true_peak_packed_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                       int src_format, const void *d_packed, size_t src_total, size_t max_frames,
+                                       const double *d_gain, const double *coefs, int phases, int taps, double *d_true_peak,
+                                       double *d_peak);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the call above on HOST
+ * pointers, as a serial loop over the same clamp, the same one-sample load and the same per-frame function as the kernels. */
+int RRX_debug_tracks_true_peak_packed_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *packed,
+                                           size_t src_total, size_t max_frames, const double *gain, const double *coefs,
+                                           int phases, int taps, double *true_peak, double *peak);
+
 /* True-peak limiter: one gain per frame, linked across a stream's channels, that holds the gained frames under a ceiling where a
  * static gain would pull the whole track down for a few transients.  The detector is RRX_true_peak_device's; the gain is a window
  * minimum of the demanded reductions smoothed by a box of `lookahead` frames.  Nothing in it is recursive (there is no one-pole
@@ -694,6 +725,32 @@ int RRX_tracks_loudness_device(int device, void *hip_stream, const RRX_track *d_
                                const void *d_rows, size_t row_frames, const double *d_gain, const double *coefs, size_t hop,
                                double *d_energy, size_t energy_stride, unsigned long long *d_hops,
                                double *d_work, size_t work_doubles);
+
+/* RRX_loudness_device per track of a library at rest.  The packed source, its four formats, the clamp of the table (first, frames,
+ * max_frames) and the exact sample value v are RRX_tracks_true_peak_packed_device's, word for word.  Track t is measured as a
+ * one-stream RRX_loudness_device call on a float64 buffer holding its v, with first_frame = 0, no state and d_gain[t] (d_gain
+ * NULL: unity): its hops go to d_energy[(t * nch + ch) * energy_stride + j], bit for bit, and d_hops[t] (unsigned 64-bit,
+ * [ntracks], on the device, WRITTEN) = min(frames / hop, energy_stride) with the clamped frames.  Energies at index d_hops[t] and
+ * beyond are left untouched.  d_work: at least RRX_loudness_work_doubles(ntracks, nch, max_frames, hop) doubles.  A wrong table
+ * gives wrong numbers, never an access outside d_packed, d_energy or d_work.  Reads: an S24_3 source of one or two channels is
+ * loaded as the aligned dwords that cover the samples, so the pass may READ, as RRX_tracks_stage_device_samples may, the aligned
+ * dword that holds the first byte of the source and the one that holds its last byte in full (up to 3 bytes on either side, in
+ * the same page: this cannot fault) and nothing further out; every other source is read by exactly its samples' bytes.  The meter calls (RRX_loudness_blocks_device and the
+ * two group calls) read only hop energies and take these as they take RRX_tracks_loudness_device's.
+ * Refusals: RR_INVPARAM, before any device is touched, for a NULL table, source, d_energy or d_hops, ntracks < 1, nch < 1, a format
+ * outside the four (RRX_FMT_DOUBLE included), the filter, hop and work refusals of RRX_loudness_device, src_total * nch, ntracks *
+ * max_frames * nch or ntracks * nch * energy_stride of 2^60 or more, or device < -1; the rest as there.  max_frames == 0 or
+ * src_total == 0 is RR_OK and does nothing. */
+int RRX_tracks_loudness_packed_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                      int src_format, const void *d_packed, size_t src_total, size_t max_frames,
+                                      const double *d_gain, const double *coefs, size_t hop, double *d_energy,
+                                      size_t energy_stride, unsigned long long *d_hops, double *d_work, size_t work_doubles);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the call above on HOST
+ * pointers, as serial loops over the same clamp, the same one-sample load and the same per-frame functions as the kernels. */
+int RRX_debug_tracks_loudness_packed_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *packed,
+                                          size_t src_total, size_t max_frames, const double *gain, const double *coefs,
+                                          size_t hop, double *energy, size_t energy_stride, unsigned long long *hops,
+                                          double *work, size_t work_doubles);
 
 /* The two-stage gate of BS.1770-4 over the hop energies of RRX_loudness_device / RRX_tracks_loudness_device: 400 ms blocks of
  * four hops, overlapping by 75 %.  The arithmetic is part of this ABI (fp64, every operation rounded on its own).  Stream s has
