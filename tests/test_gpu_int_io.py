@@ -154,14 +154,34 @@ def host_run(fi, fo, nch, kw, x, fmt, chunk=4096):
     return y
 
 
+def tie_rule_reference(ref64, fmt):
+    """The oracle's fp64 output as the integer handle must give it: (the quantised samples, the mask of samples whose scaled
+    value lies within 2^bits * 1e-13 * max|o| of a rounding tie).  None may clip."""
+    bits = BITS[fmt]
+    q = ref64 * 2.0 ** bits
+    assert q.max() < 2.0 ** bits - 1 and q.min() > -2.0 ** bits  # none clip
+    window = 2.0 ** bits * 1e-13 * np.abs(ref64).max()
+    return quantise(ref64, fmt), np.abs(np.abs(q - np.floor(q)) - 0.5) <= window
+
+
+def assert_tie_rule(size, in_window, max_abs_d, differing, unexcused):
+    """The tie-window rule on the counts of a comparison of `size` samples: d = handle - quantised oracle, `in_window` samples
+    in the tie window, `differing` with d != 0, `unexcused` of those outside the window."""
+    cap = 1e-3 * size
+    assert in_window <= cap, (in_window, cap)
+    assert max_abs_d <= 1, max_abs_d
+    assert unexcused == 0, unexcused
+    assert differing <= cap, (differing, cap)
+
+
 @pytest.mark.parametrize("fmt", FMTS)
 @pytest.mark.parametrize("fi,fo,kw", [(44100, 96000, {}), (44100, 48000, BW99), (96000, 44100, {})])
 def test_against_oracle(fi, fo, kw, fmt):
     """The oracle's fp64 output fifo (pushed whole, drained), quantised in numpy, against the integer handle.  Every sample
     within 1 LSB; a sample may differ only where the oracle's scaled value lies within 2^bits * 1e-13 * max|o| of a rounding
     tie (1e-13: the fp64 parity bound of test_fp64_parity_with_oracle); at most 0.1 % of the samples may, and the oracle's own
-    count of in-window samples must be below that cap too (so the test cannot pass by excusing everything)."""
-    bits = BITS[fmt]
+    count of in-window samples must be below that cap too (so the test cannot pass by excusing everything).  (The rule itself:
+    tie_rule_reference and assert_tie_rule above, shared with tests/test_gpu_far_positions.py.)"""
     x = lcg_noise(50000, 2, 4242).reshape(-1, 2)
     if fmt == F.RRX_FMT_S16:
         s = np.rint(x.astype(np.float64) * 2.0 ** 15).astype(np.int16)
@@ -176,19 +196,11 @@ def test_against_oracle(fi, fo, kw, fmt):
     ns = len(o.plan())
     ref64 = np.stack([o.stage_fifo(ch, ns) for ch in range(2)], axis=1)
     assert ref64.shape == y.shape, (ref64.shape, y.shape)
-    q = ref64 * 2.0 ** bits
-    assert q.max() < 2.0 ** bits - 1 and q.min() > -2.0 ** bits  # none clip
-    ref = quantise(ref64, fmt)
-    window = 2.0 ** bits * 1e-13 * np.abs(ref64).max()
-    near_tie = np.abs(np.abs(q - np.floor(q)) - 0.5) <= window
-    cap = 1e-3 * y.size
+    ref, near_tie = tie_rule_reference(ref64, fmt)
     d = y.astype(np.int64) - ref.astype(np.int64)
     print("against oracle: fmt %d %d->%d differing %d, in window %d, of %d, max |d| %d" %
           (fmt, fi, fo, int(np.sum(d != 0)), int(np.sum(near_tie)), y.size, int(np.abs(d).max())))
-    assert np.sum(near_tie) <= cap, (int(np.sum(near_tie)), cap)
-    assert np.abs(d).max() <= 1
-    assert not np.any((d != 0) & ~near_tie), int(np.sum((d != 0) & ~near_tie))
-    assert np.sum(d != 0) <= cap
+    assert_tie_rule(y.size, int(np.sum(near_tie)), int(np.abs(d).max()), int(np.sum(d != 0)), int(np.sum((d != 0) & ~near_tie)))
 
 
 @pytest.mark.parametrize("fmt", FMTS)
