@@ -15,6 +15,8 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       loudness_normalizing_gain, loudness_blocks_device, loudness_gate_groups_device, loudness_range_device, loudness_range_lu,
                       loudness_meter_device, tracks_true_peak_window_device, tracks_loudness_window_device, RRX_LOUDNESS_WIN_STATE,
                       limit_device, tracks_limit_device, limit_work_doubles, RRX_LIMIT_MAX_LOOKAHEAD, RRX_LIMIT_MAX_HOLD,
+                      limit_release_coef, limit_release_work_doubles, limit_release_device, tracks_limit_release_device,
+                      RRX_LIMIT_RELEASE_MIN_BLOCK, RRX_LIMIT_RELEASE_MAX_BLOCK,
                       limit_window_reach, tracks_limit_window_work_doubles, tracks_limit_window_device,
                       PackedPlan, PackedTable, packed_plan, tracks_true_peak_packed_device, tracks_loudness_packed_device, scan_tracks_pcm)
 
@@ -29,5 +31,7 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "loudness_normalizing_gain", "loudness_blocks_device", "loudness_gate_groups_device", "loudness_range_device", "loudness_range_lu",
            "loudness_meter_device", "tracks_true_peak_window_device", "tracks_loudness_window_device", "RRX_LOUDNESS_WIN_STATE",
            "limit_device", "tracks_limit_device", "limit_work_doubles", "RRX_LIMIT_MAX_LOOKAHEAD", "RRX_LIMIT_MAX_HOLD",
+           "limit_release_coef", "limit_release_work_doubles", "limit_release_device", "tracks_limit_release_device",
+           "RRX_LIMIT_RELEASE_MIN_BLOCK", "RRX_LIMIT_RELEASE_MAX_BLOCK",
            "limit_window_reach", "tracks_limit_window_work_doubles", "tracks_limit_window_device",
            "PackedPlan", "PackedTable", "packed_plan", "tracks_true_peak_packed_device", "tracks_loudness_packed_device", "scan_tracks_pcm"]

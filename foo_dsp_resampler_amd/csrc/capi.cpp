@@ -12,6 +12,7 @@
 #include "tracks.hpp"
 #include "true_peak.hpp"
 #include "limit.hpp"
+#include "limit_release.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1324,6 +1325,131 @@ int RRX_tracks_limit_device(int device, void *hip_stream, const RRX_track *d_tra
   a.nstreams = ntracks;
   a.nch = nch;
   return rsmp::launch_limit(static_cast<hipStream_t>(hip_stream), a) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+// r, m and the block summaries C, A, B, S of every stream (limit_release.hip): 0 for what the data calls refuse
+size_t RRX_limit_release_work_doubles(int nstreams, size_t frames, int taps, size_t lookahead, size_t block)
+{
+  static_assert(RRX_LIMIT_RELEASE_MIN_BLOCK == rsmp::kLimitReleaseMinBlock && RRX_LIMIT_RELEASE_MAX_BLOCK == rsmp::kLimitReleaseMaxBlock,
+                "the header's constants are the kernels'");
+  if (block < RRX_LIMIT_RELEASE_MIN_BLOCK || block > RRX_LIMIT_RELEASE_MAX_BLOCK) return 0;
+  if (!RRX_limit_work_doubles(nstreams, frames, taps, lookahead)) return 0; // (frames below 2^60 / (2 * nstreams) from here on)
+  const size_t most = size_t(1) << 60, n = size_t(nstreams);
+  const size_t each = 2 * (frames + size_t(taps) + lookahead) + 4 * ((frames + lookahead - 1 + block - 1) / block + 1); // below 2^61
+  return each >= (most + n - 1) / n ? 0 : n * each;
+}
+
+namespace {
+
+// what the release adds to a validated limiter call: the pole, the block, and the work buffer's layout.  Per stream r, C, A in
+// the first half and m, B, S in the second, each half `a.work_stride` doubles: limit.hip's kernels find r and m where they
+// look for them.
+int limit_release_args(double release, size_t block, double *work, size_t work_doubles, rsmp::LimitArgs &a, rsmp::LimitReleaseArgs &r)
+{
+  if (!(release >= 0.0) || !(release < 1.0)) return RR_INVPARAM; // (a NaN fails both)
+  const size_t need = RRX_limit_release_work_doubles(a.nstreams, size_t(a.frames), a.f.taps, a.lookahead, block);
+  if (!need || !work || work_doubles < need) return RR_INVPARAM;
+  const unsigned long long each = a.frames + (unsigned)a.f.taps + a.lookahead;
+  const unsigned long long sums = rsmp::limit_release_blocks(a.frames + (a.lookahead - 1), unsigned(block)) + 1;
+  a.work_stride = each + 2 * sums;
+  r.work = work;
+  r.tracks = a.tracks;
+  r.frames = a.frames;
+  r.stream_stride = 2 * a.work_stride;
+  r.m_off = a.work_stride;
+  r.c_off = each;
+  r.b_off = a.work_stride + each;
+  r.sum_stride = sums;
+  r.lookahead = a.lookahead;
+  r.block = unsigned(block);
+  r.a = release;
+  r.b = 1.0 - release;
+  r.nstreams = a.nstreams;
+  return RR_OK;
+}
+
+} // namespace
+
+// RRX_limit_device with an exponential release between the window minimum and the box (limit_release.hip).  Refusals first.
+int RRX_limit_release_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride, int dst_format, void *d_dst,
+                             size_t dst_stride, int nstreams, size_t frames, int nch, const double *d_gain, double ceiling, const double *coefs,
+                             int phases, int taps, size_t lookahead, size_t hold, double release, size_t block, double *d_reduction,
+                             unsigned long long *d_limited, double *d_work, size_t work_doubles)
+{
+  rsmp::LimitArgs a;
+  rsmp::LimitReleaseArgs r;
+  // (limit_args wants RRX_limit_work_doubles of work, which the release's buffer always holds)
+  int rc = limit_args(src_format, d_src, src_stride, dst_format, d_dst, dst_stride, nstreams, frames, nch, d_gain, ceiling, coefs, phases, taps,
+                      lookahead, hold, d_reduction, d_limited, d_work, ~size_t(0), a);
+  if (rc != RR_OK) return rc;
+  rc = limit_release_args(release, block, d_work, work_doubles, a, r);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_limit_release(static_cast<hipStream_t>(hip_stream), a, r) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_limit_release_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride, int nstreams,
+                                 size_t frames, int nch, const double *gain, double ceiling, const double *coefs, int phases, int taps,
+                                 size_t lookahead, size_t hold, double release, size_t block, double *reduction, unsigned long long *limited,
+                                 double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LimitArgs a;
+  rsmp::LimitReleaseArgs r;
+  int rc = limit_args(src_format, src, src_stride, dst_format, dst, dst_stride, nstreams, frames, nch, gain, ceiling, coefs, phases, taps,
+                      lookahead, hold, reduction, limited, work, ~size_t(0), a);
+  if (rc != RR_OK) return rc;
+  rc = limit_release_args(release, block, work, work_doubles, a, r);
+  if (rc != RR_OK) return rc;
+  if (frames) rsmp::limit_release_host(a, r);
+  return RR_OK;
+}
+
+// RRX_limit_release_device per track of a ragged batch (limit_release.hip).  Refusals first, as in RRX_tracks_limit_device.
+int RRX_tracks_limit_release_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                    const void *d_rows, int dst_format, void *d_dst_rows, size_t row_frames, const double *d_gain, double ceiling,
+                                    const double *coefs, int phases, int taps, size_t lookahead, size_t hold, double release, size_t block,
+                                    double *d_reduction, unsigned long long *d_limited, double *d_work, size_t work_doubles)
+{
+  rsmp::LimitArgs a;
+  rsmp::LimitReleaseArgs r;
+  if (!d_tracks || !d_rows || !d_dst_rows || ntracks < 1 || nch < 1) return RR_INVPARAM;
+  if (src_format != RRX_FMT_FLOAT && src_format != RRX_FMT_DOUBLE) return RR_INVPARAM;
+  int rc = true_peak_filter(coefs, phases, taps, a.f);
+  if (rc != RR_OK) return rc;
+  const size_t most = (~size_t(0) >> 4) / size_t(nch); // no buffer has 2^60 samples (RRX_finish_device)
+  if (row_frames > most / size_t(ntracks)) return RR_INVPARAM;
+  rc = limit_common(src_format, dst_format, ntracks, row_frames, ceiling, lookahead, hold, d_work, ~size_t(0), a);
+  if (rc != RR_OK) return rc;
+  const uintptr_t samples = uintptr_t(ntracks) * row_frames * uintptr_t(nch);
+  if (!limit_overlap_ok(d_rows, samples * (a.src_double ? 8 : 4), d_dst_rows, samples * (a.dst_double ? 8 : 4), src_format == dst_format))
+    return RR_INVPARAM;
+  a.src = d_rows;
+  a.dst = d_dst_rows;
+  a.gain = d_gain;
+  a.reduction = d_reduction;
+  a.limited = d_limited;
+  a.tracks = reinterpret_cast<const rsmp::Track *>(d_tracks);
+  a.src_stride = a.dst_stride = 0;
+  a.frames = row_frames;
+  a.nstreams = ntracks;
+  a.nch = nch;
+  rc = limit_release_args(release, block, d_work, work_doubles, a, r);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames) return RR_OK;
+  const int dev = check_device(device);
+  if (dev != RR_OK) return dev;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_limit_release(static_cast<hipStream_t>(hip_stream), a, r) == hipSuccess ? RR_OK : RR_INTERNAL;
 }
 
 namespace {

@@ -274,7 +274,10 @@ template <typename S, typename T, bool kWin> __global__ __launch_bounds__(kThrea
 
 unsigned grid_x(unsigned long long pieces) { return pieces < 1 ? 1u : pieces > 0x7fffffffull ? 0x7fffffffu : (unsigned)pieces; }
 
-template <typename S, typename T, bool kWin> hipError_t launch_typed(hipStream_t stream, const LimitArgs &a, const LimitWindow &w)
+// the passes [first, last) of detect, window, apply: all three for the calls of this file, the first two and the last one around
+// the release (limit_release.hip)
+template <typename S, typename T, bool kWin>
+hipError_t launch_typed(hipStream_t stream, const LimitArgs &a, const LimitWindow &w, int first = 0, int last = 3)
 {
   // the longest row, or the longest cut of one by the window.  The caller keeps frames * nch below 2^60, so nothing here wraps.
   const unsigned long long D = (unsigned long long)(a.f.taps - 1), L = a.lookahead;
@@ -284,7 +287,7 @@ template <typename S, typename T, bool kWin> hipError_t launch_typed(hipStream_t
                  gx3 = grid_x((emit + kLimitApplyFrames - 1) / kLimitApplyFrames);
   const bool bs1770 = a.f.phases == 4 && a.f.taps == 12;
   const dim3 block(kThreads);
-  for (int pass = 0; pass < 3; ++pass) {
+  for (int pass = first; pass < last; ++pass) {
     for (int s0 = 0; s0 < a.nstreams; s0 += 32768) { // grid.y is a 16-bit count
       const unsigned ns = (unsigned)(a.nstreams - s0 < 32768 ? a.nstreams - s0 : 32768);
       if (pass == 0 && bs1770) hipLaunchKernelGGL((limit_detect_kernel<S, 4, 12, kWin>), dim3(gx1, ns), block, 0, stream, a, s0, w);
@@ -298,7 +301,8 @@ template <typename S, typename T, bool kWin> hipError_t launch_typed(hipStream_t
   return hipSuccess;
 }
 
-template <typename S, typename T, bool kWin> void host_typed(const LimitArgs &a, const LimitWindow &w)
+// head: r and m; tail: the gains, the product and the statistics (both for the calls of this file, one each around the release)
+template <typename S, typename T, bool kWin> void host_typed(const LimitArgs &a, const LimitWindow &w, bool head = true, bool tail = true)
 {
   const unsigned L = a.lookahead, D = (unsigned)(a.f.taps - 1);
   const unsigned long long back = (unsigned long long)(L - 1) + a.hold, width = (unsigned long long)L + a.hold + D;
@@ -306,7 +310,7 @@ template <typename S, typename T, bool kWin> void host_typed(const LimitArgs &a,
     const Row r = row_of<kWin>(a, w, s);
     if (r.lo >= r.hi) continue;
     const unsigned long long evals = r.frames + D, outs = r.hi - r.lo + (L - 1);
-    for (unsigned long long F = r.fa; F < r.fb; ++F) {
+    for (unsigned long long F = r.fa; head && F < r.fb; ++F) {
       unsigned long long lev = 0;
       for (unsigned ch = 0; ch < (unsigned)a.nch; ++ch) {
         double h[kTpMaxTaps];
@@ -316,12 +320,13 @@ template <typename S, typename T, bool kWin> void host_typed(const LimitArgs &a,
       }
       r.r[F - r.fa] = limit_reduction(lev, a.ceiling);
     }
-    for (unsigned long long o = 0; o < outs; ++o) { // entry j = r.lo + o
+    for (unsigned long long o = 0; head && o < outs; ++o) { // entry j = r.lo + o
       double least = 1.0; // what lies outside the row
       for (unsigned long long at = r.lo + o; at < r.lo + o + width; ++at)
         if (at >= back && at - back < evals && r.r[at - back - r.fa] < least) least = r.r[at - back - r.fa];
       r.m[o] = least;
     }
+    if (!tail) continue;
     unsigned long long lowest = true_peak_bits(1.0), count = 0;
     for (unsigned long long n = r.lo; n < r.hi; ++n) {
       const double g = limit_smooth(r.m + (n - r.lo), L, a.inv_l);
@@ -345,16 +350,17 @@ template <typename S, typename T, bool kWin> void host_typed(const LimitArgs &a,
 
 namespace {
 
-template <bool kWin> hipError_t launch_form(hipStream_t stream, const LimitArgs &a, const LimitWindow &w)
+template <bool kWin> hipError_t launch_form(hipStream_t stream, const LimitArgs &a, const LimitWindow &w, int first = 0, int last = 3)
 {
-  if (a.src_double) return a.dst_double ? launch_typed<double, double, kWin>(stream, a, w) : launch_typed<double, float, kWin>(stream, a, w);
-  return a.dst_double ? launch_typed<float, double, kWin>(stream, a, w) : launch_typed<float, float, kWin>(stream, a, w);
+  if (a.src_double)
+    return a.dst_double ? launch_typed<double, double, kWin>(stream, a, w, first, last) : launch_typed<double, float, kWin>(stream, a, w, first, last);
+  return a.dst_double ? launch_typed<float, double, kWin>(stream, a, w, first, last) : launch_typed<float, float, kWin>(stream, a, w, first, last);
 }
 
-template <bool kWin> void host_form(const LimitArgs &a, const LimitWindow &w)
+template <bool kWin> void host_form(const LimitArgs &a, const LimitWindow &w, bool head = true, bool tail = true)
 {
-  if (a.src_double) a.dst_double ? host_typed<double, double, kWin>(a, w) : host_typed<double, float, kWin>(a, w);
-  else a.dst_double ? host_typed<float, double, kWin>(a, w) : host_typed<float, float, kWin>(a, w);
+  if (a.src_double) a.dst_double ? host_typed<double, double, kWin>(a, w, head, tail) : host_typed<double, float, kWin>(a, w, head, tail);
+  else a.dst_double ? host_typed<float, double, kWin>(a, w, head, tail) : host_typed<float, float, kWin>(a, w, head, tail);
 }
 
 } // namespace
@@ -365,5 +371,12 @@ hipError_t launch_limit(hipStream_t stream, const LimitArgs &a, const LimitWindo
 }
 
 void limit_host(const LimitArgs &a, const LimitWindow *w) { w ? host_form<true>(a, *w) : host_form<false>(a, LimitWindow()); }
+
+hipError_t launch_limit_passes(hipStream_t stream, const LimitArgs &a, int first, int last)
+{
+  return launch_form<false>(stream, a, LimitWindow(), first, last);
+}
+
+void limit_host_passes(const LimitArgs &a, bool head, bool tail) { host_form<false>(a, LimitWindow(), head, tail); }
 
 } // namespace rsmp

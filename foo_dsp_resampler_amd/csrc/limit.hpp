@@ -81,6 +81,7 @@ struct LimitArgs {
   unsigned long long src_stride, dst_stride; // SAMPLES between streams (tracks: unused)
   unsigned long long frames;       // per stream (tracks: the rows' length, row_frames)
   unsigned long long work_stride;  // frames + taps + lookahead: room for frames + taps - 1 of r and frames + lookahead - 1 of m
+                                   // (with a release: more, the blocks' summaries lie behind each: limit_release.hpp)
   unsigned lookahead, hold;
   double ceiling, inv_l;           // inv_l = 1.0 / (double)lookahead
   int nstreams, nch;
@@ -122,5 +123,12 @@ hipError_t launch_limit(hipStream_t stream, const LimitArgs &a, const LimitWindo
 // The plain call's results on host pointers, as serial loops over the functions above (test hooks: RRX_debug_limit_host and,
 // with a window and a host table, RRX_debug_tracks_limit_window_host).
 void limit_host(const LimitArgs &a, const LimitWindow *w = nullptr);
+
+// The whole-row form in parts, for a call that puts launches of its own between the window minimum and the product (the release,
+// limit_release.hip): the launches [first, last) of detect (0), window minimum (1), product (2), which reads as m whatever the
+// work buffer then holds in its place.  launch_limit(stream, a) is launch_limit_passes(stream, a, 0, 3).
+hipError_t launch_limit_passes(hipStream_t stream, const LimitArgs &a, int first, int last);
+// limit_host likewise: head = r and m, tail = the gains, the product and the statistics
+void limit_host_passes(const LimitArgs &a, bool head, bool tail);
 
 } // namespace rsmp

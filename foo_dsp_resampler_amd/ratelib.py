@@ -2,6 +2,7 @@
 error behaviour as the reference's rate/ratelib.h:25-81)."""
 import ctypes as C
 import json
+import math
 import os
 
 import numpy as np
@@ -24,6 +25,7 @@ EXPECTED_SYMBOLS = [
     "RRX_finish_shaped_device", "RRX_debug_finish_shaped_host", "RRX_tracks_finish_shaped_device",
     "RRX_true_peak_device", "RRX_debug_true_peak_host", "RRX_tracks_true_peak_device",
     "RRX_limit_work_doubles", "RRX_limit_device", "RRX_tracks_limit_device", "RRX_debug_limit_host",
+    "RRX_limit_release_work_doubles", "RRX_limit_release_device", "RRX_tracks_limit_release_device", "RRX_debug_limit_release_host",
     "RRX_loudness_device", "RRX_loudness_work_doubles", "RRX_debug_loudness_host", "RRX_tracks_loudness_device",
     "RRX_loudness_gate_device", "RRX_debug_loudness_gate_host",
     "RRX_loudness_blocks_device", "RRX_loudness_groups_work_doubles", "RRX_loudness_gate_groups_device", "RRX_loudness_range_groups_device",
@@ -61,6 +63,7 @@ finite floats."""
 
 RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS = 8, 16
 RRX_LIMIT_MAX_LOOKAHEAD, RRX_LIMIT_MAX_HOLD = 1024, 4096
+RRX_LIMIT_RELEASE_MIN_BLOCK, RRX_LIMIT_RELEASE_MAX_BLOCK = 64, 65536
 RRX_LOUDNESS_WIN_STATE = 16            # doubles per (track, channel) of tracks_loudness_window_device's state: S, Z, C, E, three zeros
 
 
@@ -254,6 +257,15 @@ def lib():
                                                   C.c_int, sz, sz, vp, vp, vp, sz]
             L.RRX_limit_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz]
             L.RRX_limit_work_doubles.restype = sz
+        if hasattr(L, "RRX_limit_release_device"):  # (as above)
+            host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_double, vp, C.c_int, C.c_int, sz, sz, C.c_double, sz, vp, vp,
+                    vp, sz]
+            L.RRX_limit_release_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_limit_release_host.argtypes = host
+            L.RRX_tracks_limit_release_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, sz, vp, C.c_double, vp,
+                                                          C.c_int, C.c_int, sz, sz, C.c_double, sz, vp, vp, vp, sz]
+            L.RRX_limit_release_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz, sz]
+            L.RRX_limit_release_work_doubles.restype = sz
         if hasattr(L, "RRX_loudness_device"):  # (as above)
             u64 = C.c_ulonglong
             host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, u64, vp, sz, vp, vp, vp, sz, vp, sz]
@@ -1027,8 +1039,9 @@ def _limit_params(ceiling, lookahead, hold):
     return ceiling, lookahead, hold
 
 
-def _limit_buffers(x, out, n, frames, taps, lookahead, dev):
-    """(out, reduction preset to 1.0, limited zeroed, work) of a limiter call on `n` rows of `frames` frames"""
+def _limit_buffers(x, out, n, frames, taps, lookahead, dev, block=None):
+    """(out, reduction preset to 1.0, limited zeroed, work) of a limiter call on `n` rows of `frames` frames; with `block`, of a
+    call with a release"""
     import torch
     if out is None:
         out = torch.empty_like(x)
@@ -1040,7 +1053,7 @@ def _limit_buffers(x, out, n, frames, taps, lookahead, dev):
             raise TypeError("in place the destination has the source's dtype")
     reduction = torch.ones((n,), dtype=torch.float64, device=dev)
     limited = torch.zeros((n,), dtype=torch.int64, device=dev)
-    need = limit_work_doubles(n, frames, taps, lookahead)
+    need = limit_work_doubles(n, frames, taps, lookahead) if block is None else limit_release_work_doubles(n, frames, taps, lookahead, block)
     if not need:
         raise ValueError("the rows are too large for the limiter's work buffer")
     return out, reduction, limited, torch.empty((need,), dtype=torch.float64, device=dev)
@@ -1059,6 +1072,11 @@ def limit_device(x, ceiling, gain=None, lookahead=64, hold=0, filter="bs1770", o
     float64 tensor of x's shape that shares no memory with it.  Returns (y, reduction, limited): float64 [nstreams] the
     smallest s of each stream (1.0 where nothing was limited) and int64 [nstreams] the frames with s < 1.  The call only
     enqueues; its work buffer comes from torch's allocator."""
+    return _limit_device(x, ceiling, gain, lookahead, hold, filter, out, stream, None)
+
+
+def _limit_device(x, ceiling, gain, lookahead, hold, filter, out, stream, release):
+    """limit_device (release = None) and limit_release_device (release = (pole, block), checked)"""
     import torch
     shape = tuple(x.shape)
     if len(shape) not in (2, 3):
@@ -1075,17 +1093,21 @@ def limit_device(x, ceiling, gain=None, lookahead=64, hold=0, filter="bs1770", o
         raise TypeError("the limiter works on device tensors: the frames must be in HBM")
     dev = x.device
     gain = _loudness_gain(gain, nstreams, dev)
-    out, reduction, limited, work = _limit_buffers(x, out, nstreams, frames, taps, lookahead, dev)
+    out, reduction, limited, work = _limit_buffers(x, out, nstreams, frames, taps, lookahead, dev, None if release is None else release[1])
     if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out, reduction, limited
     _ensure_init()
     ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_limit_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-                                  RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
-                                  RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames,
-                                  nstreams, frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling,
-                                  C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold, C.c_void_p(reduction.data_ptr()),
-                                  C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()), "RRX_limit_device")
+    head = (-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+            RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
+            RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames,
+            nstreams, frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling,
+            C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold)
+    tail = (C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+    if release is None:
+        _check(lib().RRX_limit_device(*(head + tail)), "RRX_limit_device")
+    else:
+        _check(lib().RRX_limit_release_device(*(head + release + tail)), "RRX_limit_release_device")
     return out, reduction, limited
 
 
@@ -1095,6 +1117,11 @@ def tracks_limit_device(rows, table, ceiling, gain=None, lookahead=64, hold=0, f
     +0.0 at its first output frame, the filter's tail behind its last -- and go to the same frames of `out`: None (in place,
     into `rows`), or a float32 / float64 tensor of rows' shape that shares no memory with it.  Frames outside the slices are
     not written.  Returns (out, reduction [ntracks], limited [ntracks]) as limit_device.  The call only enqueues."""
+    return _tracks_limit_device(rows, table, ceiling, gain, lookahead, hold, filter, out, stream, None)
+
+
+def _tracks_limit_device(rows, table, ceiling, gain, lookahead, hold, filter, out, stream, release):
+    """tracks_limit_device (release = None) and tracks_limit_release_device (release = (pole, block), checked)"""
     import torch
     dt = str(rows.dtype)
     if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
@@ -1107,18 +1134,66 @@ def tracks_limit_device(rows, table, ceiling, gain=None, lookahead=64, hold=0, f
     phases, taps, coefs = _true_peak_filter(filter)
     ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
     gain = _loudness_gain(gain, ntracks, dev)
-    out, reduction, limited, work = _limit_buffers(rows, rows if out is None else out, ntracks, row_frames, taps, lookahead, dev)
+    out, reduction, limited, work = _limit_buffers(rows, rows if out is None else out, ntracks, row_frames, taps, lookahead, dev,
+                                                   None if release is None else release[1])
     if not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out, reduction, limited
     _ensure_init()
     ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_limit_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
-                                         RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
-                                         RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), row_frames,
-                                         C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p), phases,
-                                         taps, lookahead, hold, C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()),
-                                         C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_limit_device")
+    head = (-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
+            RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
+            RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), row_frames,
+            C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold)
+    tail = (C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+    if release is None:
+        _check(lib().RRX_tracks_limit_device(*(head + tail)), "RRX_tracks_limit_device")
+    else:
+        _check(lib().RRX_tracks_limit_release_device(*(head + release + tail)), "RRX_tracks_limit_release_device")
     return out, reduction, limited
+
+
+def limit_release_coef(release_ms, rate):
+    """The per-frame pole of a release with the time constant `release_ms` at `rate` frames per second:
+    exp(-1 / (release_ms * 1e-3 * rate)), the `release` of limit_release_device.  After release_ms the gain has covered 1 - 1/e of
+    its way back.  ValueError for a time that is not positive.  Host only."""
+    release_ms, rate = float(release_ms), float(rate)
+    if not (release_ms > 0 and np.isfinite(release_ms) and rate > 0 and np.isfinite(rate)):
+        raise ValueError("the release time and the rate are positive and finite")
+    return float(math.exp(-1.0 / (release_ms * 1e-3 * rate)))
+
+
+def limit_release_work_doubles(nstreams, frames, taps=12, lookahead=64, block=1024):
+    """Doubles of work memory that limit_release_device / tracks_limit_release_device need (RRX_limit_release_work_doubles:
+    nstreams * (2 * (frames + taps + lookahead) + 4 * (ceil((frames + lookahead - 1) / block) + 1))); 0 for arguments the calls
+    refuse.  Host only."""
+    return int(lib().RRX_limit_release_work_doubles(int(nstreams), int(frames), int(taps), int(lookahead), int(block)))
+
+
+def _limit_release_params(release, block):
+    """the release's two arguments, checked as the C call checks them"""
+    release, block = float(release), int(block)
+    if not 0.0 <= release < 1.0:  # (a NaN fails)
+        raise ValueError("release is a per-frame pole in [0, 1): see limit_release_coef")
+    if not RRX_LIMIT_RELEASE_MIN_BLOCK <= block <= RRX_LIMIT_RELEASE_MAX_BLOCK:
+        raise ValueError("block is %d..%d entries" % (RRX_LIMIT_RELEASE_MIN_BLOCK, RRX_LIMIT_RELEASE_MAX_BLOCK))
+    return release, block
+
+
+def limit_release_device(x, ceiling, release, gain=None, lookahead=64, hold=0, block=1024, filter="bs1770", out=None, stream=None):
+    """limit_device with an exponential release (RRX_limit_release_device): between the window minimum and the box the gain
+    follows p = min(m, release * p + (1 - release) * m), so after a peak it recovers towards what the programme then demands along
+    an exponential with the per-frame pole `release` in [0, 1) -- limit_release_coef(release_ms, rate) for a time constant; 0.0
+    gives limit_device's bits -- and never rises above limit_device's gain.  The recursion runs as a scan over blocks of `block`
+    entries (64..65536), which is part of the result's bits (include/ratelib_amd.h).  Everything else, the returns included, is
+    limit_device's."""
+    return _limit_device(x, ceiling, gain, lookahead, hold, filter, out, stream, _limit_release_params(release, block))
+
+
+def tracks_limit_release_device(rows, table, ceiling, release, gain=None, lookahead=64, hold=0, block=1024, filter="bs1770", out=None,
+                                stream=None):
+    """limit_release_device per track of a ragged batch, in one call (RRX_tracks_limit_release_device): tracks_limit_device with
+    the release of limit_release_device, every track's slice as a one-stream call of its own from the state 1.0."""
+    return _tracks_limit_device(rows, table, ceiling, gain, lookahead, hold, filter, out, stream, _limit_release_params(release, block))
 
 
 def limit_window_reach(lookahead, hold, filter="bs1770"):
@@ -2763,7 +2838,8 @@ class Resampler:
         return gain, lufs
 
     def convert_tracks_to_pcm_loudness_limited(self, tracks, dst_format, target_lufs=-14.0, max_dbtp=-1.0, lookahead_ms=1.5, hold_ms=10.0,
-                                               weights=None, shaping=None, segment=65536, dither=False, seed=0, album=None):
+                                               weights=None, shaping=None, segment=65536, dither=False, seed=0, album=None, release_ms=None,
+                                               release_block=1024):
         """convert_tracks_to_pcm_loudness_normalized with a true-peak LIMITER in place of the peak-bound gain: a track with a few
         loud transients over a quiet bed reaches `target_lufs` where the static gain min(by loudness, by peak) would leave it far
         below.  The rows are converted once and their loudness measured as there (`weights`, `album` as there); the gain is
@@ -2774,7 +2850,9 @@ class Resampler:
         removes what the limiter leaves over the ceiling between the samples; the rows are finished under `trim` as in
         convert_tracks_to_pcm_normalized.  Everything is computed on the device, without a host synchronisation.  Returns (views,
         peak, clipped, gain [ntracks], trim [ntracks], reduction [ntracks], limited [ntracks], lufs [ntracks]): `reduction` the
-        limiter's smallest gain, `limited` the frames it lowered, `lufs` the loudness BEFORE the gain (of t's album with `album`)."""
+        limiter's smallest gain, `limited` the frames it lowered, `lufs` the loudness BEFORE the gain (of t's album with `album`).
+        With `release_ms` the limiter is tracks_limit_release_device under limit_release_coef(release_ms, out_rate) in blocks of
+        `release_block` entries: the gain recovers exponentially behind a transient; None is the limiter without a release."""
         import torch
         tracks = list(tracks)
         if album is not None:
@@ -2790,7 +2868,11 @@ class Resampler:
         cur = torch.cuda.current_stream(out.device)
         energy, hops = tracks_loudness_device(out, table, rate, stream=cur)
         gain, lufs = self._gain_by_loudness(energy, hops, n, album, weights, target_lufs, cur)
-        _, reduction, limited = tracks_limit_device(out, table, ceiling, gain=gain, lookahead=lookahead, hold=hold, stream=cur)
+        if release_ms is None:
+            _, reduction, limited = tracks_limit_device(out, table, ceiling, gain=gain, lookahead=lookahead, hold=hold, stream=cur)
+        else:
+            _, reduction, limited = tracks_limit_release_device(out, table, ceiling, limit_release_coef(release_ms, rate), gain=gain,
+                                                                lookahead=lookahead, hold=hold, block=release_block, stream=cur)
         true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
         m = torch.maximum(true_peak, sample_peak).amax(1)
         ok = torch.isfinite(m) & (m > 0)

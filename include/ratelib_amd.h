@@ -651,6 +651,71 @@ int RRX_debug_limit_host(int src_format, const void *src, size_t src_stride, int
                          const double *coefs, int phases, int taps, size_t lookahead, size_t hold,
                          double *reduction, unsigned long long *limited, double *work, size_t work_doubles);
 
+/* The limiter with an exponential RELEASE: RRX_limit_device with a one-pole recursion between the window minimum and the box, so
+ * that after a transient the gain recovers along an exponential of tens to hundreds of milliseconds instead of a ramp of L frames.
+ * One step of a release is the map x -> min(t, a*x + u), and such maps are closed under composition,
+ *   min(t2, a2*min(t1, a1*x + u1) + u2) = min(min(t2, a2*t1 + u2), a2*a1*x + (a2*u1 + u2)),
+ * so a block of frames collapses into three numbers and the recursion runs as a block scan: every block summarised from nothing,
+ * a short serial carry over the summaries, every block run again from its true start state.
+ *
+ * The arithmetic is part of this ABI, the block decomposition included: fp64, every operation rounded on its own, no fused
+ * multiply-add.  g, tp, a[F], lev, r and m[k] are RRX_limit_device's, word for word.  Index the entries of m as v[j] = m[j - (L-1)],
+ * j in [0, J), J = N + L - 1.  `release` is the per-frame pole a in [0, 1) (exp(-1 / (seconds * rate)) for a time constant),
+ * b = 1.0 - a computed once on the host, and `block` the entries of a block, RRX_LIMIT_RELEASE_MIN_BLOCK..MAX_BLOCK, not
+ * necessarily a power of two.  Block i holds the entries [i*block, min((i+1)*block, J)), nb = ceil(J / block) blocks:
+ *   summary of block i with entries v_0 .. v_{n-1}:
+ *       C = v_0;  A = a;  B = b * v_0
+ *       for t = 1 .. n-1:  u = b * v_t;  C = fmin(v_t, a * C + u);  A = a * A;  B = a * B + u
+ *   carry:  S_0 = 1.0;  S_{i+1} = fmin(C_i, A_i * S_i + B_i)            (blocks ascending)
+ *   run of block i:  p = S_i;  for t = 0 .. n-1:  u = b * v_t;  p = fmin(v_t, a * p + u);  q[i*block + t] = p
+ * The start state of block i+1 is the carry's S_{i+1}, NOT the last p of block i: the two differ in rounding.  The rest is
+ * RRX_limit_device's with q in place of m: acc sums q[n - i] for i = L-1 down to 0 (as entries: q[n + L-1 - i]),
+ * s[n] = fmin(acc * invL, q[n]), y = g * s, and the statistics are as there.
+ * What holds.  q[j] <= v[j] always, so s[n] <= m[n]: the sample-peak bound |y| <= c * (1 + 2^-51) of RRX_limit_device holds
+ * unchanged, and what is said there of the TRUE peak holds too.  m is never a NaN, so q is never a NaN.  The release is towards
+ * the target, a*p + b*v, not towards 1.0: the gain recovers from the +0.0 that an infinite sample demands.  With release == 0.0
+ * the call leaves RRX_limit_device's bytes and statistics exactly (b = 1 and fmin(v, 0*p + v) = v).  The blocked form is NOT bit-equal
+ * to the plain serial recursion p = fmin(v_j, a*p + b*v_j) run from 1.0: over the cases of tests/test_limit_release_api.py the
+ * largest relative difference of q between the two is 6.8e-13, where the gain recovers from +0.0 and q is small against the sums it is read from ("Limiter: release"); it is zero wherever a minimum
+ * takes v_j, which forgets the state.  A_i + B_i need not round to 1.0 where nothing demands a reduction: behind the first block
+ * a gain can sit one rounding below 1.0, and d_limited counts such frames too (it is not below RRX_limit_device's count).
+ *   d_work: at least RRX_limit_release_work_doubles(nstreams, frames, taps, lookahead, block) doubles on the device, which is
+ *   nstreams * (2 * (frames + taps + lookahead) + 4 * (ceil((frames + lookahead - 1) / block) + 1)) -- r, m and the blocks' C, A, B, S
+ *   per stream -- or 0 for arguments the call would refuse and for a total of 2^60 doubles or more (host only).  Its content after
+ *   the call is unspecified.
+ *   Launches: RRX_limit_device's detector and window minimum, then summary (one lane per (stream, block), walking its block in
+ *   register tiles), carry (one lane per stream) and run (the summary's lanes, q over m in place), then RRX_limit_device's
+ *   smoothing and product.  The call only enqueues: no allocation, no host synchronisation; nothing outside the rows' frames of the
+ *   destination, the work buffer and the two result arrays is written.
+ * Everything else -- formats, strides, in place, d_gain, coefs, d_reduction, d_limited, device, hip_stream -- is RRX_limit_device's.
+ * Returns RR_INVPARAM, before any device is touched, for everything RRX_limit_device refuses, a release that is a NaN, below 0 or
+ * not below 1, a block outside its range, and d_work NULL or work_doubles too small; RR_EXTUNINIT before init_ratelib; RR_INTERNAL
+ * for a failed launch.  frames == 0 is RR_OK and touches nothing. */
+#define RRX_LIMIT_RELEASE_MIN_BLOCK 64
+#define RRX_LIMIT_RELEASE_MAX_BLOCK 65536
+size_t RRX_limit_release_work_doubles(int nstreams, size_t frames, int taps, size_t lookahead, size_t block);
+int RRX_limit_release_device(int device, void *hip_stream, int src_format, const void *d_src, size_t src_stride,
+                             int dst_format, void *d_dst, size_t dst_stride, int nstreams, size_t frames, int nch,
+                             const double *d_gain, double ceiling, const double *coefs, int phases, int taps,
+                             size_t lookahead, size_t hold, double release, size_t block, double *d_reduction,
+                             unsigned long long *d_limited, double *d_work, size_t work_doubles);
+/* RRX_limit_release_device per track of a ragged batch in one call, as RRX_tracks_limit_device is to RRX_limit_device: every
+ * track's slice is limited as a one-stream call of its own -- blocks count from the slice's own entry j = 0, the state 1.0 is in
+ * front of it -- and the table is clamped as there: a wrong table gives wrong samples, never an access outside the rows or d_work.
+ * d_work: RRX_limit_release_work_doubles(ntracks, row_frames, taps, lookahead, block) doubles.  Refusals: RRX_tracks_limit_device's
+ * and those of release, block and the work buffer above.  row_frames == 0 is RR_OK and does nothing. */
+int RRX_tracks_limit_release_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                    int src_format, const void *d_rows, int dst_format, void *d_dst_rows, size_t row_frames,
+                                    const double *d_gain, double ceiling, const double *coefs, int phases, int taps,
+                                    size_t lookahead, size_t hold, double release, size_t block, double *d_reduction,
+                                    unsigned long long *d_limited, double *d_work, size_t work_doubles);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: RRX_limit_release_device on HOST
+ * pointers, as serial loops over the very per-step functions the kernels call.  Same refusals, same results. */
+int RRX_debug_limit_release_host(int src_format, const void *src, size_t src_stride, int dst_format, void *dst, size_t dst_stride,
+                                 int nstreams, size_t frames, int nch, const double *gain, double ceiling,
+                                 const double *coefs, int phases, int taps, size_t lookahead, size_t hold, double release,
+                                 size_t block, double *reduction, unsigned long long *limited, double *work, size_t work_doubles);
+
 /* Programme loudness (ITU-R BS.1770-4, EBU R 128): K-weighted energies of 100 ms hops per (stream, channel) of device-resident
  * frames, from which RRX_loudness_gate_device below takes the gated mean; in LUFS once the caller takes -0.691 + 10 log10.  The
  * call needs no handle and writes no sample.

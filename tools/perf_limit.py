@@ -32,6 +32,18 @@ which runs the same filter.  One line per (lookahead, hold), appended to profile
    "excess_us_per_window", "steps", "warmup"}
 
   python tools/perf_limit.py --window 4354 [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
+
+Release.  `--release` times RRX_tracks_limit_release_device ("Limiter: release") against RRX_tracks_limit_device at
+the same lookahead and hold, on the first 64 streams of config 1's float32 output tensor as 64 whole-row stereo tracks, both out
+of place into one float32 tensor -- same rows, same run, interleaved as above -- under the pole of a 100 ms release
+at 48 kHz, in blocks of `--block` entries (default 1024).  By bytes the three launches of the release add two reads and one write
+of m, 24 bytes a frame, to the 56 bytes a stereo float32 frame costs the limiter: about 1.4 times.  One line per (lookahead,
+hold), appended to profiles/limit_release_perf.jsonl:
+
+  {"config", "tracks", "nch", "frames", "lookahead", "hold", "release", "block", "blocks_per_track", "limit_ms", "release_ms",
+   "limit_ms_rounds", "release_ms_rounds", "ratio", "extra_ms", "extra_gbytes_per_s": 24 bytes a frame over extra_ms, "steps", "warmup"}
+
+  python tools/perf_limit.py --release [--block 1024] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -178,6 +190,59 @@ def window_config(k, W, steps, warmup, rounds):
     return lines
 
 
+def release_config(k, tracks, block, steps, warmup, rounds):
+    stream = torch.cuda.Stream()
+    x, _ = step_tensor(k, stream)
+    with torch.cuda.stream(stream):
+        rows = x[:tracks].contiguous()
+    del x
+    S, frames, nch = rows.shape
+    phases, taps, coefs = F.TRUE_PEAK_FILTERS["bs1770"]
+    co = (C.c_double * len(coefs))(*coefs)
+    table = np.zeros((S, 6), np.uint64)  # only the output slices are looked at: every track is its whole row
+    table[:, 4] = frames
+    pole = F.limit_release_coef(100.0, 48000)
+    with torch.cuda.stream(stream):
+        d_table = torch.from_numpy(table.view(np.int64)).cuda()
+        out = torch.empty_like(rows)
+        red = torch.ones((S,), dtype=torch.float64, device="cuda")
+        lim = torch.zeros((S,), dtype=torch.int64, device="cuda")
+        work = torch.empty((F.limit_release_work_doubles(S, frames, taps, 1024, block),), dtype=torch.float64, device="cuda")
+        ceiling = 0.5 * float(rows.abs().max())
+    stream.synchronize()
+
+    def plain(L, H):
+        def call():
+            F.ratelib._check(F.lib().RRX_tracks_limit_device(-1, C.c_void_p(stream.cuda_stream), C.c_void_p(d_table.data_ptr()), S, nch, F.RRX_FMT_FLOAT,
+                                                             C.c_void_p(rows.data_ptr()), F.RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames, None,
+                                                             ceiling, C.cast(co, C.c_void_p), phases, taps, L, H, C.c_void_p(red.data_ptr()),
+                                                             C.c_void_p(lim.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+                             "RRX_tracks_limit_device")
+        return call
+
+    def released(L, H):
+        def call():
+            F.ratelib._check(F.lib().RRX_tracks_limit_release_device(
+                -1, C.c_void_p(stream.cuda_stream), C.c_void_p(d_table.data_ptr()), S, nch, F.RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
+                F.RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames, None, ceiling, C.cast(co, C.c_void_p), phases, taps, L, H, pole, block,
+                C.c_void_p(red.data_ptr()), C.c_void_p(lim.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_limit_release_device")
+        return call
+
+    lines = []
+    for L, H in PAIRS:
+        a, b, pms, rms = plain(L, H), released(L, H), [], []
+        for _ in range(rounds):
+            pms.append(timed(stream, a, steps, warmup))
+            rms.append(timed(stream, b, steps, warmup))
+        p, r = statistics.median(pms), statistics.median(rms)
+        lines.append({"config": k, "tracks": S, "nch": nch, "frames": frames, "lookahead": L, "hold": H, "release": pole, "block": block,
+                      "blocks_per_track": -(-(frames + L - 1) // block), "limit_ms": round(p, 4), "release_ms": round(r, 4),
+                      "limit_ms_rounds": [round(v, 4) for v in pms], "release_ms_rounds": [round(v, 4) for v in rms], "ratio": round(r / p, 3),
+                      "extra_ms": round(r - p, 4), "extra_gbytes_per_s": round(24.0 * S * frames / (r - p) / 1e6, 1) if r > p else None,
+                      "steps": steps, "warmup": warmup})
+    return lines
+
+
 def residuals():
     ceiling = 10.0 ** (-1.0 / 20.0)
     gen = torch.Generator(device="cuda").manual_seed(7)
@@ -207,14 +272,18 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-residuals", action="store_true")
     ap.add_argument("--window", type=int, default=0, help="time the window form in windows of this many frames (config 1) instead")
+    ap.add_argument("--release", action="store_true", help="time the limiter with a release against the limiter, on 64 stereo tracks")
+    ap.add_argument("--block", type=int, default=1024, help="entries of a block of the release's scan")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_limit.py needs a GPU: there is nothing to time without one")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "limit_window_perf.jsonl" if a.window else "limit_perf.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "limit_release_perf.jsonl" if a.release else "limit_window_perf.jsonl" if a.window else "limit_perf.jsonl")
     lines = []
-    if a.window:
+    if a.release:
+        lines += release_config(1, 64, a.block, a.steps, a.warmup, a.rounds)
+    elif a.window:
         if a.window < 1:
             raise SystemExit("--window is a positive frame count")
         lines += window_config(1, a.window, a.steps, a.warmup, a.rounds)
