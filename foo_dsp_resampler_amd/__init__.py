@@ -18,6 +18,7 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       limit_release_coef, limit_release_work_doubles, limit_release_device, tracks_limit_release_device,
                       RRX_LIMIT_RELEASE_MIN_BLOCK, RRX_LIMIT_RELEASE_MAX_BLOCK,
                       limit_window_reach, tracks_limit_window_work_doubles, tracks_limit_window_device,
+                      tracks_limit_release_window_work_doubles, tracks_limit_release_window_device, RRX_LIMIT_RELEASE_WIN_STATE,
                       PackedPlan, PackedTable, packed_plan, tracks_true_peak_packed_device, tracks_loudness_packed_device, scan_tracks_pcm)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
@@ -34,4 +35,5 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "limit_release_coef", "limit_release_work_doubles", "limit_release_device", "tracks_limit_release_device",
            "RRX_LIMIT_RELEASE_MIN_BLOCK", "RRX_LIMIT_RELEASE_MAX_BLOCK",
            "limit_window_reach", "tracks_limit_window_work_doubles", "tracks_limit_window_device",
+           "tracks_limit_release_window_work_doubles", "tracks_limit_release_window_device", "RRX_LIMIT_RELEASE_WIN_STATE",
            "PackedPlan", "PackedTable", "packed_plan", "tracks_true_peak_packed_device", "tracks_loudness_packed_device", "scan_tracks_pcm"]

@@ -13,6 +13,7 @@
 #include "true_peak.hpp"
 #include "limit.hpp"
 #include "limit_release.hpp"
+#include "limit_release_window.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -2366,6 +2367,106 @@ int RRX_debug_tracks_limit_window_host(const RRX_track *tracks, int ntracks, int
                                           reduction, limited, work, work_doubles, a, w);
   if (rc != RR_OK) return rc;
   if (row_frames && win_frames) rsmp::limit_host(a, &w);
+  return RR_OK;
+}
+
+// the window call's r and m of every track and C, A, B, S of the pieces of a window (limit_release_window.hip): 0 for what the
+// data call refuses
+size_t RRX_tracks_limit_release_window_work_doubles(int ntracks, size_t win_frames, int taps, size_t lookahead, size_t hold, size_t block)
+{
+  if (block < RRX_LIMIT_RELEASE_MIN_BLOCK || block > RRX_LIMIT_RELEASE_MAX_BLOCK) return 0;
+  if (!RRX_tracks_limit_window_work_doubles(ntracks, win_frames, taps, lookahead, hold)) return 0; // (win_frames below 2^60 / (2 * ntracks))
+  const size_t most = size_t(1) << 60, n = size_t(ntracks);
+  const size_t each = 2 * (win_frames + 2 * lookahead + hold + 2 * size_t(taps)) +
+                      4 * size_t(rsmp::limit_release_window_pieces(win_frames, unsigned(lookahead), unsigned(block))); // below 2^61
+  return each >= (most + n - 1) / n ? 0 : n * each;
+}
+
+namespace {
+
+// RRX_tracks_limit_release_window_device / RRX_debug_tracks_limit_release_window_host: what the release, its block, the two
+// states and the work buffer add to a validated window call.  Per track r, C, A in the first half of its share and m, B, S in
+// the second, each half `a.work_stride` doubles: limit.hip's kernels find r and m where they look for them.
+int tracks_limit_release_window_args(double release, size_t block, const double *state_in, double *state_out, double *work, size_t work_doubles,
+                                     rsmp::LimitArgs &a, const rsmp::LimitWindow &w, rsmp::LimitReleaseWindowArgs &r)
+{
+  static_assert(RRX_LIMIT_RELEASE_WIN_STATE == rsmp::kLimitReleaseWinState, "the header's constant is the kernels'");
+  if (!(release >= 0.0) || !(release < 1.0)) return RR_INVPARAM; // (a NaN fails both)
+  const size_t need = RRX_tracks_limit_release_window_work_doubles(a.nstreams, size_t(w.win_frames), a.f.taps, a.lookahead, a.hold, block);
+  if (!need || !work || work_doubles < need) return RR_INVPARAM;
+  if (measure_window_state(state_in, state_out, size_t(w.win_first), uintptr_t(a.nstreams) * rsmp::kLimitReleaseWinState) != RR_OK) return RR_INVPARAM;
+  const unsigned long long each = w.win_frames + 2 * a.lookahead + a.hold + 2 * (unsigned)a.f.taps;
+  const unsigned long long sums = rsmp::limit_release_window_pieces(w.win_frames, a.lookahead, unsigned(block));
+  a.work_stride = each + 2 * sums;
+  r.work = work;
+  r.tracks = a.tracks;
+  r.state_in = state_in;
+  r.state_out = state_out;
+  r.row_frames = a.frames;
+  r.win_first = w.win_first;
+  r.win_frames = w.win_frames;
+  r.stream_stride = 2 * a.work_stride;
+  r.m_off = a.work_stride;
+  r.c_off = each;
+  r.b_off = a.work_stride + each;
+  r.sum_stride = sums;
+  r.lookahead = a.lookahead;
+  r.block = unsigned(block);
+  r.a = release;
+  r.b = 1.0 - release;
+  r.ntracks = a.nstreams;
+  return RR_OK;
+}
+
+} // namespace
+
+// RRX_tracks_limit_window_device with the release of RRX_tracks_limit_release_device, the scan's state carried per track
+// (limit_release_window.hip).  Refusals first.
+int RRX_tracks_limit_release_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch, int src_format,
+                                           const void *d_buf, size_t buf_stride, size_t buf_first, size_t buf_frames, size_t row_frames,
+                                           size_t win_first, size_t win_frames, int dst_format, void *d_dst, size_t dst_stride,
+                                           const double *d_gain, double ceiling, const double *coefs, int phases, int taps, size_t lookahead,
+                                           size_t hold, double release, size_t block, const double *d_state_in, double *d_state_out,
+                                           double *d_reduction, unsigned long long *d_limited, double *d_work, size_t work_doubles)
+{
+  rsmp::LimitArgs a;
+  rsmp::LimitWindow w;
+  rsmp::LimitReleaseWindowArgs r;
+  // (tracks_limit_window_args wants the window call's share of work, which the release's buffer always holds)
+  int rc = tracks_limit_window_args(d_tracks, ntracks, nch, src_format, d_buf, buf_stride, buf_first, buf_frames, row_frames, win_first,
+                                    win_frames, dst_format, d_dst, dst_stride, d_gain, ceiling, coefs, phases, taps, lookahead, hold,
+                                    d_reduction, d_limited, d_work, ~size_t(0), a, w);
+  if (rc != RR_OK) return rc;
+  rc = tracks_limit_release_window_args(release, block, d_state_in, d_state_out, d_work, work_doubles, a, w, r);
+  if (rc != RR_OK) return rc;
+  if (device < -1) return RR_INVPARAM;
+  if (!g_initialized) return RR_EXTUNINIT;
+  if (!row_frames || !win_frames) return RR_OK;
+  rc = check_device(device);
+  if (rc != RR_OK) return rc;
+  rsmp::DeviceScope on(device); // restores the caller's device on return
+  if (!on.ok()) return RR_INTERNAL;
+  return rsmp::launch_limit_release_window(static_cast<hipStream_t>(hip_stream), a, w, r) == hipSuccess ? RR_OK : RR_INTERNAL;
+}
+
+int RRX_debug_tracks_limit_release_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *buf, size_t buf_stride,
+                                               size_t buf_first, size_t buf_frames, size_t row_frames, size_t win_first, size_t win_frames,
+                                               int dst_format, void *dst, size_t dst_stride, const double *gain, double ceiling,
+                                               const double *coefs, int phases, int taps, size_t lookahead, size_t hold, double release,
+                                               size_t block, const double *state_in, double *state_out, double *reduction,
+                                               unsigned long long *limited, double *work, size_t work_doubles)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  rsmp::LimitArgs a;
+  rsmp::LimitWindow w;
+  rsmp::LimitReleaseWindowArgs r;
+  int rc = tracks_limit_window_args(tracks, ntracks, nch, src_format, buf, buf_stride, buf_first, buf_frames, row_frames, win_first,
+                                    win_frames, dst_format, dst, dst_stride, gain, ceiling, coefs, phases, taps, lookahead, hold, reduction,
+                                    limited, work, ~size_t(0), a, w);
+  if (rc != RR_OK) return rc;
+  rc = tracks_limit_release_window_args(release, block, state_in, state_out, work, work_doubles, a, w, r);
+  if (rc != RR_OK) return rc;
+  if (row_frames && win_frames) rsmp::limit_release_window_host(a, w, r);
   return RR_OK;
 }
 

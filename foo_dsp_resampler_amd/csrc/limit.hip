@@ -379,4 +379,11 @@ hipError_t launch_limit_passes(hipStream_t stream, const LimitArgs &a, int first
 
 void limit_host_passes(const LimitArgs &a, bool head, bool tail) { host_form<false>(a, LimitWindow(), head, tail); }
 
+hipError_t launch_limit_window_passes(hipStream_t stream, const LimitArgs &a, const LimitWindow &w, int first, int last)
+{
+  return launch_form<true>(stream, a, w, first, last);
+}
+
+void limit_host_window_passes(const LimitArgs &a, const LimitWindow &w, bool head, bool tail) { host_form<true>(a, w, head, tail); }
+
 } // namespace rsmp

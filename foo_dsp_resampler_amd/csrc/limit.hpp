@@ -130,5 +130,9 @@ void limit_host(const LimitArgs &a, const LimitWindow *w = nullptr);
 hipError_t launch_limit_passes(hipStream_t stream, const LimitArgs &a, int first, int last);
 // limit_host likewise: head = r and m, tail = the gains, the product and the statistics
 void limit_host_passes(const LimitArgs &a, bool head, bool tail);
+// The window form in parts, likewise (the release by windows, limit_release_window.hip): the same launches on the window's
+// sub-range of every row.  launch_limit(stream, a, &w) is launch_limit_window_passes(stream, a, w, 0, 3).
+hipError_t launch_limit_window_passes(hipStream_t stream, const LimitArgs &a, const LimitWindow &w, int first, int last);
+void limit_host_window_passes(const LimitArgs &a, const LimitWindow &w, bool head, bool tail);
 
 } // namespace rsmp

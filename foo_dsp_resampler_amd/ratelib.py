@@ -39,6 +39,7 @@ EXPECTED_SYMBOLS = [
     "RRX_tracks_true_peak_window_device", "RRX_debug_tracks_true_peak_window_host", "RRX_tracks_loudness_window_work_doubles",
     "RRX_tracks_loudness_window_device", "RRX_debug_tracks_loudness_window_host",
     "RRX_limit_window_reach", "RRX_tracks_limit_window_work_doubles", "RRX_tracks_limit_window_device", "RRX_debug_tracks_limit_window_host",
+    "RRX_tracks_limit_release_window_work_doubles", "RRX_tracks_limit_release_window_device", "RRX_debug_tracks_limit_release_window_host",
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
     "RRX_reset", "RRX_tracks_batches", "RRX_plan_cache_clear", "RRX_plan_cache_stats",
@@ -64,6 +65,7 @@ finite floats."""
 RRX_TP_MAX_PHASES, RRX_TP_MAX_TAPS = 8, 16
 RRX_LIMIT_MAX_LOOKAHEAD, RRX_LIMIT_MAX_HOLD = 1024, 4096
 RRX_LIMIT_RELEASE_MIN_BLOCK, RRX_LIMIT_RELEASE_MAX_BLOCK = 64, 65536
+RRX_LIMIT_RELEASE_WIN_STATE = 8  # doubles of scan state per track between two windows (tracks_limit_release_window_device)
 RRX_LOUDNESS_WIN_STATE = 16            # doubles per (track, channel) of tracks_loudness_window_device's state: S, Z, C, E, three zeros
 
 
@@ -333,6 +335,13 @@ def lib():
             L.RRX_limit_window_reach.argtypes = [C.c_int, sz, sz, P(sz), P(sz)]
             L.RRX_tracks_limit_window_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz, sz]
             L.RRX_tracks_limit_window_work_doubles.restype = sz
+        if hasattr(L, "RRX_tracks_limit_release_window_device"):  # (as above)
+            host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp, C.c_double, vp, C.c_int, C.c_int, sz, sz,
+                    C.c_double, sz, vp, vp, vp, vp, vp, sz]
+            L.RRX_tracks_limit_release_window_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_tracks_limit_release_window_host.argtypes = host
+            L.RRX_tracks_limit_release_window_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz, sz, sz]
+            L.RRX_tracks_limit_release_window_work_doubles.restype = sz
         if hasattr(L, "RRX_reset"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_reset.argtypes = [vp]
@@ -1230,6 +1239,14 @@ def tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, win
     tracks_limit_device's bits in the emitted frames and its two statistics.  `ceiling`, `gain`, `lookahead`, `hold` and `filter`
     are tracks_limit_device's.  Returns (out, reduction, limited); the call only enqueues, its work buffer comes from torch's
     allocator."""
+    return _tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, win_frames, ceiling, gain, lookahead, hold, filter, out,
+                                       reduction, limited, stream, buf_frames, None, None, None)[:3]
+
+
+def _tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, win_frames, ceiling, gain, lookahead, hold, filter, out, reduction,
+                                limited, stream, buf_frames, release, state_in, state_out):
+    """tracks_limit_window_device (release = None) and tracks_limit_release_window_device (release = (pole, block), checked):
+    (out, reduction, limited, state_out)"""
     import torch
     dt = str(buf.dtype)
     if buf.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not buf.is_cuda or not buf.is_contiguous():
@@ -1270,24 +1287,66 @@ def tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, win
             raise TypeError("%s must be a contiguous %s tensor [%d] on %s" % (name, sdt, ntracks, dev))
         stats.append(t)
     reduction, limited = stats
+    if release is not None:
+        shape = (ntracks, RRX_LIMIT_RELEASE_WIN_STATE)
+        for t, name in ((state_in, "state_in"), (state_out, "state_out")):
+            if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
+                raise TypeError("%s must be a contiguous float64 tensor [%d, %d] on %s" % ((name,) + shape + (dev,)))
+        if state_in is None and win_first:
+            raise ValueError("only a window at frame 0 starts without a state")
+        if state_out is None:
+            state_out = torch.zeros(shape, dtype=torch.float64, device=dev)
+        if state_in is not None:
+            lo, hi = state_out.data_ptr(), state_out.data_ptr() + state_out.numel() * 8
+            if lo < state_in.data_ptr() + state_in.numel() * 8 and state_in.data_ptr() < hi:
+                raise ValueError("state_out must share no memory with state_in")
     if not win_frames or not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
-        return out, reduction, limited
-    need = tracks_limit_window_work_doubles(ntracks, win_frames, taps, lookahead, hold)
+        return out, reduction, limited, state_out
+    if release is None:
+        need = tracks_limit_window_work_doubles(ntracks, win_frames, taps, lookahead, hold)
+    else:
+        need = tracks_limit_release_window_work_doubles(ntracks, win_frames, taps, lookahead, hold, release[1])
     if not need:
         raise ValueError("the window is too large for the limiter's work buffer")
     work = torch.empty((need,), dtype=torch.float64, device=dev)
     _ensure_init()
     ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_limit_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
-                                                ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
-                                                C.c_void_p(buf.data_ptr()), buf_stride, buf_first, buf_frames, row_frames, win_first,
-                                                win_frames, RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT,
-                                                C.c_void_p(out.data_ptr()), out.shape[1],
-                                                C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p),
-                                                phases, taps, lookahead, hold, C.c_void_p(reduction.data_ptr()),
-                                                C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
-           "RRX_tracks_limit_window_device")
-    return out, reduction, limited
+    head = (-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
+            RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(buf.data_ptr()), buf_stride, buf_first, buf_frames,
+            row_frames, win_first, win_frames, RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()),
+            out.shape[1], C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p), phases, taps,
+            lookahead, hold)
+    tail = (C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+    if release is None:
+        _check(lib().RRX_tracks_limit_window_device(*(head + tail)), "RRX_tracks_limit_window_device")
+    else:
+        states = (C.c_void_p(state_in.data_ptr()) if state_in is not None else None, C.c_void_p(state_out.data_ptr()))
+        _check(lib().RRX_tracks_limit_release_window_device(*(head + release + states + tail)), "RRX_tracks_limit_release_window_device")
+    return out, reduction, limited, state_out
+
+
+def tracks_limit_release_window_work_doubles(ntracks, win_frames, taps=12, lookahead=64, hold=0, block=1024):
+    """Doubles of work memory that tracks_limit_release_window_device needs for a window of `win_frames` frames of `ntracks` tracks
+    (RRX_tracks_limit_release_window_work_doubles: ntracks * (2 * (win_frames + 2 * lookahead + hold + 2 * taps) + 4 * ((win_frames +
+    lookahead - 1) // block + 2))); 0 for arguments the call refuses.  Host only."""
+    return int(lib().RRX_tracks_limit_release_window_work_doubles(int(ntracks), int(win_frames), int(taps), int(lookahead), int(hold),
+                                                                  int(block)))
+
+
+def tracks_limit_release_window_device(buf, table, row_frames, buf_first, win_first, win_frames, ceiling, release, state_in=None, gain=None,
+                                       lookahead=64, hold=0, block=1024, filter="bs1770", out=None, reduction=None, limited=None,
+                                       state_out=None, buf_frames=None, stream=None):
+    """tracks_limit_window_device with the release of tracks_limit_release_device (RRX_tracks_limit_release_window_device).  The
+    release is a recursion, so this call takes and returns a per-track state and depends on the order of the calls: windows that
+    partition [0, row_frames), taken in ascending contiguous order, each given the `state_out` of the one before as its
+    `state_in` (and the same `reduction` and `limited`), leave tracks_limit_release_device's bits and statistics for any cut
+    positions -- the blocks of `block` entries stay on every track's own grid, and the scan's intermediate state crosses the cut
+    (include/ratelib_amd.h).  `state_in`: a contiguous float64 device tensor [ntracks, 8], or None, which only a window at frame 0
+    may pass; `state_out`: likewise, a new one when None, sharing no memory with `state_in`.  `release` and `block` are
+    limit_release_device's and checked as there; release 0.0 gives tracks_limit_window_device's bits whatever the state holds.
+    Everything else is tracks_limit_window_device's.  Returns (out, reduction, limited, state_out); the call only enqueues."""
+    return _tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, win_frames, ceiling, gain, lookahead, hold, filter, out,
+                                       reduction, limited, stream, buf_frames, _limit_release_params(release, block), state_in, state_out)
 
 
 K_WEIGHTING_48K =(1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,
@@ -2063,11 +2122,16 @@ class _WindowLimiter:
     still within reach are moved to the front of the second carry buffer, which then takes the first one's place.  `flush(got)`
     emits the rest, in pieces no longer than a pulled window, with the rows as long as what was delivered.  The emitted windows are
     ascending and contiguous from frame 0.  Memory: 2 * (back + ahead + window) + window frames per row; `reduction` and `limited`
-    are accumulated into."""
+    are accumulated into.  With `release` = (pole, block) the windows go through tracks_limit_release_window_device instead --
+    their order is the one it needs -- and two [rows, 8] state buffers take turns as its state_in and state_out, the first window
+    starting without one."""
 
-    def __init__(self, ceiling, gain, lookahead, hold, reduction, limited, table, cap, wout, stream):
+    def __init__(self, ceiling, gain, lookahead, hold, reduction, limited, table, cap, wout, stream, release=None):
         import torch
         self.kw = dict(ceiling=ceiling, gain=gain, lookahead=lookahead, hold=hold, reduction=reduction, limited=limited, stream=stream)
+        self.release = release
+        if release is not None:
+            self.states = [torch.zeros((wout.shape[0], RRX_LIMIT_RELEASE_WIN_STATE), dtype=torch.float64, device=wout.device) for _ in range(2)]
         self.table, self.cap = table, cap
         self.back, self.ahead = limit_window_reach(lookahead, hold)
         n, width, nch = wout.shape
@@ -2076,8 +2140,14 @@ class _WindowLimiter:
         self.first = self.frames = self.emitted = 0  # the carry buffer holds the frames [first, first + frames) of the rows
 
     def _emit(self, frames, row_frames):
-        tracks_limit_window_device(self.bufs[0], self.table, row_frames, self.first, self.emitted, frames, out=self.out, buf_frames=self.frames,
-                                   **self.kw)
+        if self.release is None:
+            tracks_limit_window_device(self.bufs[0], self.table, row_frames, self.first, self.emitted, frames, out=self.out,
+                                       buf_frames=self.frames, **self.kw)
+        else:
+            tracks_limit_release_window_device(self.bufs[0], self.table, row_frames, self.first, self.emitted, frames, release=self.release[0],
+                                               block=self.release[1], state_in=self.states[0] if self.emitted else None,
+                                               state_out=self.states[1], out=self.out, buf_frames=self.frames, **self.kw)
+            self.states.reverse()
         at, self.emitted = self.emitted, self.emitted + frames
         return self.out, at, frames
 
@@ -2968,7 +3038,7 @@ class Resampler:
 
     def convert_tracks_to_pcm_streamed_loudness_limited(self, tracks, dst_format, target_lufs=-14.0, max_dbtp=-1.0, lookahead_ms=1.5,
                                                         hold_ms=10.0, weights=None, window=None, shaping=None, segment=65536, dither=False,
-                                                        seed=0, album=None):
+                                                        seed=0, album=None, release_ms=None, release_block=1024):
         """convert_tracks_to_pcm_loudness_limited in bounded memory: the same inputs, the same (views, peak, clipped, gain, trim,
         reduction, limited, lufs), equal bit for bit whatever `window` is, and no rows.  Three passes over the same windows, with
         reset() between them.  Pass A measures the hop energies of every pulled window (tracks_loudness_window_device); the gain
@@ -2980,7 +3050,11 @@ class Resampler:
         and finishes the limited windows, shaped or not, under `trim`.  The tracks are resampled three times and limited twice:
         that is the price of never holding the rows ("Windows with the limiter").  Memory: that of the streamed
         form, plus per row two carry buffers of back + ahead + one output window frames and one limited window, the hop
-        energies and the states of the measuring passes."""
+        energies and the states of the measuring passes.
+        With `release_ms` the limiter has convert_tracks_to_pcm_loudness_limited's release, limit_release_coef(release_ms, out_rate)
+        in blocks of `release_block` entries, by windows: tracks_limit_release_window_device carries the scan's state per track from
+        one emitted window into the next, passes B and C each from a fresh state (two [nstreams, 8] buffers); the returns stay
+        equal to the whole-row method's bit for bit.  None is the limiter without a release."""
         import functools
         import torch
         tracks = list(tracks)
@@ -2995,6 +3069,7 @@ class Resampler:
         ceiling = 10.0 ** (float(max_dbtp) / 20.0)
         lookahead = min(max(int(round(float(lookahead_ms) * rate / 1000.0)), 1), RRX_LIMIT_MAX_LOOKAHEAD)
         hold = min(max(int(round(float(hold_ms) * rate / 1000.0)), 0), RRX_LIMIT_MAX_HOLD)
+        release = None if release_ms is None else _limit_release_params(limit_release_coef(release_ms, rate), release_block)
         n = len(tracks)
         # pass A: the loudness
         _, _, energy, hops = self._convert_tracks_streamed(tracks, dst_format, window, None, None, {}, who,
@@ -3010,7 +3085,7 @@ class Resampler:
         self.reset()
         true_peak, sample_peak, _, _ = self._convert_tracks_streamed(
             tracks, dst_format, window, None, None, {}, who, measure=functools.partial(_WindowMeter, None, self.nch),
-            limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, reduction, limited))
+            limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, reduction, limited, release=release))
         m = torch.maximum(true_peak, sample_peak).amax(1)
         ok = torch.isfinite(m) & (m > 0)
         trim = torch.where(ok, torch.clamp(torch.full_like(m, ceiling) / torch.where(ok, m, torch.ones_like(m)), max=1.0), torch.ones_like(m)).contiguous()
@@ -3020,7 +3095,8 @@ class Resampler:
         kw = dict(gain=trim[:n].contiguous(), dither=dither, seed=seed)
         views, peak, clipped = self._convert_tracks_streamed(
             tracks, dst_format, window, None, None if shaping is None else (shaping, segment), kw, who,
-            limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, torch.ones_like(reduction), torch.zeros_like(limited)))
+            limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, torch.ones_like(reduction), torch.zeros_like(limited),
+                                    release=release))
         return views, peak, clipped, gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
 
     def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):

@@ -1135,6 +1135,76 @@ int RRX_debug_tracks_limit_window_host(const RRX_track *tracks, int ntracks, int
                                        size_t lookahead, size_t hold, double *reduction, unsigned long long *limited,
                                        double *work, size_t work_doubles);
 
+/* RRX_tracks_limit_release_device by windows: RRX_tracks_limit_window_device with the exponential release of
+ * RRX_limit_release_device between the window minimum and the box.  The release is a recursion, so unlike the plain window call
+ * this one takes and returns a per-track STATE and depends on the order of the calls.  The ABI of the release is its block
+ * decomposition, and blocks are counted from each slice's own entry j = 0: a window cuts every track at a different place of its
+ * block grid, usually mid-block.  The call keeps the track's ABSOLUTE block grid and carries the scan's intermediate state across
+ * the cut, so that it leaves the bits of the whole-row call.
+ *   Entries.  As in RRX_limit_release_device: v[j] = m[j - (L-1)], j in [0, J), J = N + L - 1 for a slice of N frames; the gain of
+ *   slice frame n reads q[n .. n + L-1].  A call processes the slice frames [e0, e1) of track t, the window's cut of the clamped
+ *   slice as in the other window calls (e0 is their `index`), and computes q on the entries [e0, e1 + L-1).
+ *   State.  d_state_in and d_state_out are [ntracks][RRX_LIMIT_RELEASE_WIN_STATE] doubles on the device -- per track, not per
+ *   channel: the limiter links channels.  A state describes the scan AT AN ENTRY e; it is read at e0 and written at e1.  With
+ *   i = e / block and r = e % block:
+ *     [0]    = S, the carry's S_i (1.0 at e = 0);
+ *     [1..3] = C, A, B, the summary of the entries [i*block, e), built by the first-entry step and the extension step of
+ *              RRX_limit_release_device in order; +0.0 when r == 0;
+ *     [4]    = p, q[e - 1] run from S_i; S when r == 0;
+ *     [5..7] = +0.0.
+ *   Pieces.  The pieces of a call are the absolute blocks intersected with [e0, e1 + L-1).  A first piece with r0 = e0 % block > 0
+ *   goes on from the state: its summary extends the state's (C, A, B), its run goes on from the state's p.  Every other piece is
+ *   summarised from nothing and run from its S_i.  The carry starts from the state's S (1.0 at e0 == 0) and applies
+ *   S_{i+1} = fmin(C_i, A_i*S_i + B_i) for every block that completes inside the range.
+ *   Snapshot.  The outgoing state is written by the lanes that own the piece holding e1, as a snapshot WHILE THEY PASS e1:
+ *   the piece is never split at e1.  A serial extension cut in two keeps its bits; a block summarised in two halves and composed
+ *   does not.  Blocks that complete in the overlap [e1, e1 + L-1) are completed again by the next call, from that state, with the same
+ *   bits.
+ *   State rules, those of RRX_tracks_true_peak_window_device.  The state is read for a track only when its index e0 > 0.  Every call
+ *   with win_frames > 0 and row_frames > 0 writes EVERY entry of d_state_out (when it is not NULL); a track without a processed
+ *   frame (not begun, already ended, zero length) gets a copy of its d_state_in entries, or zeros when d_state_in is NULL.
+ *   d_state_in NULL is allowed only with win_first == 0.  The two buffers must not overlap over ntracks * 8 doubles (RR_INVPARAM,
+ *   equal pointers included).  d_state_out may be NULL.
+ *   Order of calls.  Windows that partition [0, row_frames), taken in ascending contiguous order, each given the state of the one
+ *   before, leave the bits of ONE RRX_tracks_limit_release_device call, for any cut positions: the samples, d_reduction and
+ *   d_limited.  Anything else gives other numbers, never an access outside d_buf, d_dst, d_work or the states.  With
+ *   release == 0.0 the call leaves RRX_tracks_limit_window_device's bytes and statistics, whatever the state holds and in any
+ *   order (fmin(v, 0*p + v) = v for the finite p a state holds).
+ * Everything in front of the release is RRX_tracks_limit_window_device's on the same sub-ranges -- detector, window minimum, the
+ * same back / ahead, coverage rule and clamps --, everything behind it the box, fmin, product and statistics with q in place of m.
+ *   d_work: at least RRX_tracks_limit_release_window_work_doubles(ntracks, win_frames, taps, lookahead, hold, block) doubles, which
+ *   is ntracks * (2 * (win_frames + 2 * lookahead + hold + 2 * taps) + 4 * ((win_frames + lookahead - 1) / block + 2)) -- the window
+ *   call's r and m and C, A, B, S of the pieces of a window, a range of E entries meeting at most E / block + 2 blocks -- or 0 for
+ *   arguments the call refuses and for a total of 2^60 doubles or more (host only).  Its content after the call is unspecified.
+ *   Launches: the window call's detector and window minimum, then summary (one lane per (track, piece)), carry (one wave per
+ *   track) and run (the summary's lanes, q over m in place), then the window call's smoothing and product; each split over chunks
+ *   of 32768 tracks.  The call only enqueues: no allocation, no host synchronisation.
+ * Returns RR_INVPARAM, before any device is touched, for everything RRX_tracks_limit_window_device refuses (its work rule replaced
+ * by the function above), a release that is a NaN, below 0 or not below 1, a block outside
+ * RRX_LIMIT_RELEASE_MIN_BLOCK..RRX_LIMIT_RELEASE_MAX_BLOCK, and the two state rules; RR_EXTUNINIT before init_ratelib; RR_INTERNAL
+ * for a failed launch.  win_frames == 0 or row_frames == 0 is RR_OK and touches nothing, the state included. */
+#define RRX_LIMIT_RELEASE_WIN_STATE 8
+size_t RRX_tracks_limit_release_window_work_doubles(int ntracks, size_t win_frames, int taps, size_t lookahead, size_t hold,
+                                                    size_t block);
+int RRX_tracks_limit_release_window_device(int device, void *hip_stream, const RRX_track *d_tracks, int ntracks, int nch,
+                                           int src_format, const void *d_buf, size_t buf_stride, size_t buf_first,
+                                           size_t buf_frames, size_t row_frames, size_t win_first, size_t win_frames,
+                                           int dst_format, void *d_dst, size_t dst_stride, const double *d_gain, double ceiling,
+                                           const double *coefs, int phases, int taps, size_t lookahead, size_t hold,
+                                           double release, size_t block, const double *d_state_in, double *d_state_out,
+                                           double *d_reduction, unsigned long long *d_limited, double *d_work,
+                                           size_t work_doubles);
+/* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: the call above on HOST pointers
+ * and a HOST table, as serial loops over the very functions the kernels call for the cut, the pieces and every step.  Same
+ * refusals, same results. */
+int RRX_debug_tracks_limit_release_window_host(const RRX_track *tracks, int ntracks, int nch, int src_format, const void *buf,
+                                               size_t buf_stride, size_t buf_first, size_t buf_frames, size_t row_frames,
+                                               size_t win_first, size_t win_frames, int dst_format, void *dst, size_t dst_stride,
+                                               const double *gain, double ceiling, const double *coefs, int phases, int taps,
+                                               size_t lookahead, size_t hold, double release, size_t block,
+                                               const double *state_in, double *state_out, double *reduction,
+                                               unsigned long long *limited, double *work, size_t work_doubles);
+
 /* Test hook (host only, needs no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: what the two window calls take
  * from one HOST table entry for the window [win_first, win_first + win_frames) of rows of row_frames frames, computed by the very
  * functions their kernels call.  stage[10]: the window-relative half-open ranges of the backward extension, the copied track, the

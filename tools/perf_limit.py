@@ -44,6 +44,18 @@ hold), appended to profiles/limit_release_perf.jsonl:
    "limit_ms_rounds", "release_ms_rounds", "ratio", "extra_ms", "extra_gbytes_per_s": 24 bytes a frame over extra_ms, "steps", "warmup"}
 
   python tools/perf_limit.py --release [--block 1024] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
+
+Release by windows.  `--window W --release` times RRX_tracks_limit_release_window_device ("Windows with the limiter's
+release") on the 64-track shape above, over ascending windows of W frames, every window given the state of the one before and
+read from the rows within its reach as under `--window`, against two baselines in the same run, interleaved as above:
+RRX_tracks_limit_window_device over the same windows, and the whole-row RRX_tracks_limit_release_device.  One line per
+(lookahead, hold), appended to profiles/limit_release_window_perf.jsonl:
+
+  {"config", "tracks", "nch", "frames", "window", "windows", "lookahead", "hold", "release", "block", "release_window_ms",
+   "window_ms", "whole_release_ms", the three "..._rounds", "ratio_to_window", "ratio_to_whole_release",
+   "extra_us_per_window": (release_window_ms - window_ms) / windows, "steps", "warmup"}
+
+  python tools/perf_limit.py --window 4096 --release [--block 1024] [--steps 20] [--warmup 3] [--rounds 3] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -243,6 +255,76 @@ def release_config(k, tracks, block, steps, warmup, rounds):
     return lines
 
 
+def release_window_config(k, tracks, W, block, steps, warmup, rounds):
+    stream = torch.cuda.Stream()
+    x, _ = step_tensor(k, stream)
+    S, frames, nch = tracks, x.shape[1], x.shape[2]
+    phases, taps, coefs = F.TRUE_PEAK_FILTERS["bs1770"]
+    co = (C.c_double * len(coefs))(*coefs)
+    table = np.zeros((S, 6), np.uint64)  # only the output slices are looked at: every track is its whole row
+    table[:, 4] = frames
+    pole = F.limit_release_coef(100.0, 48000)
+    with torch.cuda.stream(stream):
+        # the rows with one row of slack behind them: a window's buffer begins buf_first frames into the rows, at the rows' own pitch
+        mem = torch.zeros((S * frames * nch + frames * nch,), dtype=torch.float32, device="cuda")
+        rows = mem[:S * frames * nch].view(S, frames, nch)
+        rows.copy_(x[:S])
+        ceiling = 0.5 * float(rows.abs().max())
+        del x
+        d_table = torch.from_numpy(table.view(np.int64)).cuda()
+        out = torch.empty_like(rows)
+        wout = torch.empty((S, W, nch), dtype=torch.float32, device="cuda")
+        red = torch.ones((S,), dtype=torch.float64, device="cuda")
+        lim = torch.zeros((S,), dtype=torch.int64, device="cuda")
+        states = [torch.zeros((S, F.RRX_LIMIT_RELEASE_WIN_STATE), dtype=torch.float64, device="cuda") for _ in range(2)]
+        work = torch.empty((max(F.limit_release_work_doubles(S, frames, taps, 1024, block),
+                                F.tracks_limit_release_window_work_doubles(S, W, taps, 1024, 4096, block)),), dtype=torch.float64, device="cuda")
+    stream.synchronize()
+    windows = [(first, min(W, frames - first)) for first in range(0, frames, W)]
+    sp = C.c_void_p(stream.cuda_stream)
+
+    def by_windows(L, H, release):
+        back, ahead = F.limit_window_reach(L, H)
+
+        def call():
+            for i, (first, n) in enumerate(windows):
+                b0, b1 = max(0, first - back), min(frames, first + n + ahead)
+                head = (-1, sp, C.c_void_p(d_table.data_ptr()), S, nch, F.RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr() + b0 * nch * 4), frames, b0,
+                        b1 - b0, frames, first, n, F.RRX_FMT_FLOAT, C.c_void_p(wout.data_ptr()), W, None, ceiling, C.cast(co, C.c_void_p), phases,
+                        taps, L, H)
+                tail = (C.c_void_p(red.data_ptr()), C.c_void_p(lim.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+                if release:
+                    state = (pole, block, C.c_void_p(states[i % 2].data_ptr()) if i else None, C.c_void_p(states[1 - i % 2].data_ptr()))
+                    F.ratelib._check(F.lib().RRX_tracks_limit_release_window_device(*(head + state + tail)), "RRX_tracks_limit_release_window_device")
+                else:
+                    F.ratelib._check(F.lib().RRX_tracks_limit_window_device(*(head + tail)), "RRX_tracks_limit_window_device")
+        return call
+
+    def whole(L, H):
+        def call():
+            F.ratelib._check(F.lib().RRX_tracks_limit_release_device(
+                -1, sp, C.c_void_p(d_table.data_ptr()), S, nch, F.RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), F.RRX_FMT_FLOAT,
+                C.c_void_p(out.data_ptr()), frames, None, ceiling, C.cast(co, C.c_void_p), phases, taps, L, H, pole, block,
+                C.c_void_p(red.data_ptr()), C.c_void_p(lim.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_limit_release_device")
+        return call
+
+    lines = []
+    for L, H in PAIRS:
+        a, b, c, rw, pw, wr = by_windows(L, H, True), by_windows(L, H, False), whole(L, H), [], [], []
+        for _ in range(rounds):
+            rw.append(timed(stream, a, steps, warmup))
+            pw.append(timed(stream, b, steps, warmup))
+            wr.append(timed(stream, c, steps, warmup))
+        r, p, w = statistics.median(rw), statistics.median(pw), statistics.median(wr)
+        lines.append({"config": k, "tracks": S, "nch": nch, "frames": frames, "window": W, "windows": len(windows), "lookahead": L, "hold": H,
+                      "release": pole, "block": block, "release_window_ms": round(r, 4), "window_ms": round(p, 4), "whole_release_ms": round(w, 4),
+                      "release_window_ms_rounds": [round(v, 4) for v in rw], "window_ms_rounds": [round(v, 4) for v in pw],
+                      "whole_release_ms_rounds": [round(v, 4) for v in wr], "ratio_to_window": round(r / p, 3),
+                      "ratio_to_whole_release": round(r / w, 3), "extra_us_per_window": round((r - p) * 1000.0 / len(windows), 2),
+                      "steps": steps, "warmup": warmup})
+    return lines
+
+
 def residuals():
     ceiling = 10.0 ** (-1.0 / 20.0)
     gen = torch.Generator(device="cuda").manual_seed(7)
@@ -279,9 +361,14 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("perf_limit.py needs a GPU: there is nothing to time without one")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "limit_release_perf.jsonl" if a.release else "limit_window_perf.jsonl" if a.window else "limit_perf.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "limit_release_window_perf.jsonl" if a.release and a.window else
+                             "limit_release_perf.jsonl" if a.release else "limit_window_perf.jsonl" if a.window else "limit_perf.jsonl")
     lines = []
-    if a.release:
+    if a.release and a.window:
+        if a.window < 1:
+            raise SystemExit("--window is a positive frame count")
+        lines += release_window_config(1, 64, a.window, a.block, a.steps, a.warmup, a.rounds)
+    elif a.release:
         lines += release_config(1, 64, a.block, a.steps, a.warmup, a.rounds)
     elif a.window:
         if a.window < 1:
