@@ -1,6 +1,6 @@
 // Output stage for device-resident frames: gain, TPDF dither, PCM quantisation, peak and clipped-sample count.
 // The per-sample arithmetic below is the ABI of RRX_finish_device (include/ratelib_amd.h); the kernel (finish.hip) and the host
-// twin behind RRX_debug_finish_host (capi.cpp) are both loops around finish_sample, so they cannot drift apart.
+// twin behind RRX_debug_finish_host (capi_stage.cpp) are both loops around finish_sample, so they cannot drift apart.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>

@@ -276,7 +276,7 @@ unsigned grid_x(u64 lanes)
 template <typename S, int kK> hipError_t launch_typed(hipStream_t stream, const ShapedArgs &a)
 {
   const u64 seg = a.segment, last = a.first_frame + (a.frames - 1);
-  const u64 nseg = seg ? last / seg - a.first_frame / seg + 1 : 1; // <= frames, and frames * nch < 2^60 (capi.cpp)
+  const u64 nseg = seg ? last / seg - a.first_frame / seg + 1 : 1; // <= frames, and frames * nch < 2^60 (capi_stage.cpp)
   const unsigned gx = grid_x(nseg * (u64)a.nch);
   for (int s0 = 0; s0 < a.nstreams; s0 += 32768) { // grid.y is a 16-bit count
     const int ns = a.nstreams - s0 < 32768 ? a.nstreams - s0 : 32768;
@@ -294,7 +294,7 @@ template <typename S> hipError_t launch_src(hipStream_t stream, const ShapedArgs
 
 template <typename S, int kK> hipError_t tracks_typed(hipStream_t stream, const TracksShapedArgs &a)
 {
-  const u64 seg = a.segment, nseg = seg ? (a.t.row_frames + seg - 1) / seg : 1; // row_frames * nch < 2^60 (capi.cpp)
+  const u64 seg = a.segment, nseg = seg ? (a.t.row_frames + seg - 1) / seg : 1; // row_frames * nch < 2^60 (capi_stage.cpp)
   const u64 lanes = nseg * (u64)a.t.nch;
   const unsigned gx = grid_x(lanes);
   for (int t0 = 0; t0 < a.t.ntracks; t0 += 32768) {
@@ -315,7 +315,7 @@ template <typename S, int kK> hipError_t tracks_window_typed(hipStream_t stream,
 {
   const u64 seg = a.s.segment, n = a.w.frames;
   u64 nseg = seg ? n / seg + (n % seg ? 1 : 0) + 1 : 1; // what n frames can meet, wherever the track's segments lie
-  if (nseg > n) nseg = n;                               // (never more segments than frames); n * nch < 2^60 (capi.cpp)
+  if (nseg > n) nseg = n;                               // (never more segments than frames); n * nch < 2^60 (capi_stage.cpp)
   const unsigned gx = grid_x(nseg * (u64)a.s.t.nch);
   for (int t0 = 0; t0 < a.s.t.ntracks; t0 += 32768) {
     const int nt = a.s.t.ntracks - t0 < 32768 ? a.s.t.ntracks - t0 : 32768;

@@ -52,7 +52,7 @@ __host__ __device__ __forceinline__ Pieces pieces_of(const LimitReleaseWindowArg
   return p;
 }
 
-// the first piece goes on from the state (e0 > 0 then, and the state is there: capi.cpp refuses a null one behind frame 0)
+// the first piece goes on from the state (e0 > 0 then, and the state is there: capi_stage.cpp refuses a null one behind frame 0)
 __host__ __device__ __forceinline__ bool continues(const Pieces &p, unsigned long long k) { return k == 0 && p.c.r0 > 0; }
 
 // the entry t of piece k (which begins at `start`) behind which the state is taken, or ~0u: e1 - 1 lies in the piece, mid-block

@@ -23,7 +23,7 @@ constexpr int tracks_src_bytes(int kind) { return kind == kTracksSrcS16 ? 2 : ki
 // RRX_tracks_stage_device_samples (include/ratelib_amd.h): x = (float)((double)s * 2^-bits), bits = 15 / 23 / 31, one rounding to
 // nearest even.  S16 and S24 (three bytes, little endian, two's complement, sign-extended) are exact; S32 is rounded to float32's
 // 24 bits by the int -> float conversion, the scaling by a power of two is exact, and INT32_MAX becomes 1.0f.  The stage kernels'
-// sample-by-sample paths, the LPC base-frame loads (tracks.hip) and the host loop behind RRX_debug_tracks_load_host (capi.cpp) all
+// sample-by-sample paths, the LPC base-frame loads (tracks.hip) and the host loop behind RRX_debug_tracks_load_host (capi_stage.cpp) all
 // call this function, so they cannot drift apart; the copy kernel's group path unpacks whole dwords to the same integers.
 // `base` needs the alignment of one sample (1 byte for S24); exactly the sample's own bytes are read.
 __host__ __device__ __forceinline__ float tracks_load_sample(int kind, const void *base, unsigned long long i)
@@ -93,7 +93,7 @@ template <> constexpr int tracks_kind_of<int>() { return kTracksSrcS32; }
 // ------------------------------------------------------------------------------------------------------ interval arithmetic
 // Everything the kernels take from a table entry goes through the four functions below, which hold all the u64 clamps against
 // wrap-around: the whole-row kernels call tracks_entry / tracks_slice, the window kernels tracks_stage_cut / tracks_finish_cut,
-// which are built on them, and RRX_debug_tracks_window_cut (capi.cpp) runs the same functions on the host.
+// which are built on them, and RRX_debug_tracks_window_cut (capi_stage.cpp) runs the same functions on the host.
 
 // Track t's input side, clamped: lead + frames + fwd <= row_frames and first + have <= src_total whatever the table says
 struct TracksEntry {
