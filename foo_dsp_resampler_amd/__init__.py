@@ -19,7 +19,8 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       RRX_LIMIT_RELEASE_MIN_BLOCK, RRX_LIMIT_RELEASE_MAX_BLOCK,
                       limit_window_reach, tracks_limit_window_work_doubles, tracks_limit_window_device,
                       tracks_limit_release_window_work_doubles, tracks_limit_release_window_device, RRX_LIMIT_RELEASE_WIN_STATE,
-                      PackedPlan, PackedTable, packed_plan, tracks_true_peak_packed_device, tracks_loudness_packed_device, scan_tracks_pcm)
+                      PackedPlan, PackedTable, packed_plan, tracks_true_peak_packed_device, tracks_loudness_packed_device, scan_tracks_pcm,
+                      MIX_MATRICES, RRX_MIX_MAX_CH, mix_matrix, mix_device, tracks_stage_mix_device, tracks_stage_mix_window_device)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
@@ -36,4 +37,5 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "RRX_LIMIT_RELEASE_MIN_BLOCK", "RRX_LIMIT_RELEASE_MAX_BLOCK",
            "limit_window_reach", "tracks_limit_window_work_doubles", "tracks_limit_window_device",
            "tracks_limit_release_window_work_doubles", "tracks_limit_release_window_device", "RRX_LIMIT_RELEASE_WIN_STATE",
-           "PackedPlan", "PackedTable", "packed_plan", "tracks_true_peak_packed_device", "tracks_loudness_packed_device", "scan_tracks_pcm"]
+           "PackedPlan", "PackedTable", "packed_plan", "tracks_true_peak_packed_device", "tracks_loudness_packed_device", "scan_tracks_pcm",
+           "MIX_MATRICES", "RRX_MIX_MAX_CH", "mix_matrix", "mix_device", "tracks_stage_mix_device", "tracks_stage_mix_window_device"]

@@ -1,5 +1,6 @@
 // C ABI: the handle-free calls of include/ratelib_amd.h -- LPC edge extrapolation, the output stage and its shaped form, ragged
-// track batches, true peak, the limiter and its release, loudness and its statistics, and the window families of the track path.
+// track batches, true peak, the limiter and its release, loudness and its statistics, the window families of the track path, and
+// channel mixing.
 // A device entry validates its arguments (the family's *_args function) and ends in on_device; its host twin, a test hook, hands
 // the same *_args function to on_host.  Everything that can be refused from the arguments alone is refused before any device is
 // touched.
@@ -14,6 +15,7 @@
 #include "lpc.hpp"
 #include "measure_window.hpp"
 #include "tracks.hpp"
+#include "tracks_mix.hpp"
 #include "true_peak.hpp"
 #include "limit.hpp"
 #include "limit_release.hpp"
@@ -1589,6 +1591,117 @@ int RRX_debug_tracks_limit_release_window_host(const RRX_track *tracks, int ntra
         return rc != RR_OK ? rc : tracks_limit_release_window_args(release, block, state_in, state_out, work, work_doubles, a, w, r);
       },
       !row_frames || !win_frames, [&] { rsmp::limit_release_window_host(a, w, r); });
+}
+
+namespace {
+
+// the matrix of the mixing calls: RR_INVPARAM for a NULL pointer, a channel count outside 1..RRX_MIX_MAX_CH or a non-finite
+// coefficient; `m` gets the connected terms
+static int mix_matrix(const double *mix, int nch_src, int nch_dst, rsmp::TracksMix &m)
+{
+  static_assert(RRX_MIX_MAX_CH == rsmp::kMixMaxCh, "the header's constant is the kernels'");
+  if (!mix || nch_src < 1 || nch_src > RRX_MIX_MAX_CH || nch_dst < 1 || nch_dst > RRX_MIX_MAX_CH) return RR_INVPARAM;
+  return rsmp::tracks_mix_build(mix, nch_src, nch_dst, m) ? RR_OK : RR_INVPARAM;
+}
+
+// RRX_mix_device / RRX_debug_mix_host: everything that can be refused from the arguments alone
+static int mix_rows_args(int fmt, const void *src, size_t src_stride, int nstreams, size_t frames, int nch_src, void *dst, size_t dst_stride,
+                         int nch_dst, const double *mix, rsmp::MixRowsArgs &a, rsmp::TracksMix &m)
+{
+  const int rc = mix_matrix(mix, nch_src, nch_dst, m);
+  if (rc != RR_OK) return rc;
+  if (!float_format(fmt) || !src || !dst || nstreams < 1) return RR_INVPARAM;
+  if (nstreams > 1 && (src_stride < frames || dst_stride < frames)) return RR_INVPARAM;
+  if (frames > most_frames(RRX_MIX_MAX_CH)) return RR_INVPARAM;
+  if (nstreams > 1 && (src_stride > most_frames(RRX_MIX_MAX_CH) / size_t(nstreams) || dst_stride > most_frames(RRX_MIX_MAX_CH) / size_t(nstreams)))
+    return RR_INVPARAM;
+  // the two buffers share no byte (equal pointers overlap); samples below 2^60 each: no wrap
+  const uintptr_t size = fmt == RRX_FMT_DOUBLE ? 8 : 4, rows = uintptr_t(nstreams - 1);
+  const uintptr_t sb = (rows * src_stride + frames) * uintptr_t(nch_src) * size, db = (rows * dst_stride + frames) * uintptr_t(nch_dst) * size;
+  const uintptr_t x = reinterpret_cast<uintptr_t>(src), y = reinterpret_cast<uintptr_t>(dst);
+  if (x == y || (x < y ? y - x < sb : x - y < db)) return RR_INVPARAM;
+  a.src = src;
+  a.dst = dst;
+  a.src_stride = nstreams > 1 ? (unsigned long long)src_stride * nch_src : 0;
+  a.dst_stride = nstreams > 1 ? (unsigned long long)dst_stride * nch_dst : 0;
+  a.frames = frames;
+  a.nstreams = nstreams;
+  a.is_double = fmt == RRX_FMT_DOUBLE;
+  return RR_OK;
+}
+
+// RRX_tracks_stage_mix_device / RRX_tracks_stage_mix_window_device: the matrix, then what the un-mixed calls refuse, with nch_src
+// in the source sizes and nch in the row sizes
+static int tracks_stage_mix_args(size_t in_rate, size_t out_rate, const RRX_track *tracks, int ntracks, int src_format, int nch_src,
+                                 const void *packed, size_t src_total, int nch, const double *mix, fb_sample_t *rows, size_t row_frames,
+                                 rsmp::TracksStageArgs &a, rsmp::TracksMix &m)
+{
+  int rc = mix_matrix(mix, nch_src, nch, m);
+  if (rc == RR_OK) rc = tracks_stage_args(in_rate, out_rate, tracks, ntracks, nch, src_format, packed, src_total, rows, row_frames, a);
+  if (rc != RR_OK) return rc;
+  return src_total > most_frames(nch_src) ? RR_INVPARAM : RR_OK;
+}
+
+} // namespace
+
+// A matrix on device-resident rows (tracks_mix.hip).
+int RRX_mix_device(int device, void *hip_stream, int fmt, const void *d_src, size_t src_stride, int nstreams, size_t frames, int nch_src,
+                   void *d_dst, size_t dst_stride, int nch_dst, const double *mix)
+{
+  rsmp::MixRowsArgs a;
+  rsmp::TracksMix m;
+  const int rc = mix_rows_args(fmt, d_src, src_stride, nstreams, frames, nch_src, d_dst, dst_stride, nch_dst, mix, a, m);
+  if (rc != RR_OK) return rc;
+  return on_device(device, !frames, [&] { return rsmp::launch_mix_rows(static_cast<hipStream_t>(hip_stream), a, m); });
+}
+
+int RRX_debug_mix_host(int fmt, const void *src, size_t src_stride, int nstreams, size_t frames, int nch_src, void *dst, size_t dst_stride,
+                       int nch_dst, const double *mix)
+{
+  rsmp::MixRowsArgs a;
+  rsmp::TracksMix m;
+  return on_host([&] { return mix_rows_args(fmt, src, src_stride, nstreams, frames, nch_src, dst, dst_stride, nch_dst, mix, a, m); }, !frames,
+                 [&] { rsmp::mix_rows_host(a, m); });
+}
+
+// The stage pass of a ragged batch with the mix on load (tracks_mix.hip).
+int RRX_tracks_stage_mix_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks,
+                                int src_format, int nch_src, const void *d_packed, size_t src_total, int nch, const double *mix,
+                                fb_sample_t *d_rows, size_t row_frames)
+{
+  rsmp::TracksStageArgs a;
+  rsmp::TracksMix m;
+  const int rc = tracks_stage_mix_args(in_rate, out_rate, d_tracks, ntracks, src_format, nch_src, d_packed, src_total, nch, mix, d_rows,
+                                       row_frames, a, m);
+  if (rc != RR_OK) return rc;
+  return on_device(device, false, [&] { return rsmp::launch_tracks_stage_mix(static_cast<hipStream_t>(hip_stream), a, m); });
+}
+
+int RRX_tracks_stage_mix_window_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks,
+                                       int src_format, int nch_src, const void *d_packed, size_t src_total, int nch, const double *mix,
+                                       size_t row_frames, size_t win_first, size_t win_frames, fb_sample_t *d_win, size_t win_stride)
+{
+  rsmp::TracksStageArgs a;
+  rsmp::TracksMix m;
+  rsmp::TracksWindow w;
+  int rc = tracks_stage_mix_args(in_rate, out_rate, d_tracks, ntracks, src_format, nch_src, d_packed, src_total, nch, mix, d_win, row_frames, a, m);
+  if (rc == RR_OK) rc = tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, w);
+  if (rc != RR_OK) return rc;
+  return on_device(device, !win_frames, [&] { return rsmp::launch_tracks_stage_mix_window(static_cast<hipStream_t>(hip_stream), a, m, w); });
+}
+
+// Test hook: the mixed float32 frames of a host source, a serial loop over the function the kernels call
+int RRX_debug_tracks_mix_host(int src_format, const void *src, int nch_src, size_t first_frame, size_t count, int nch, const double *mix,
+                              float *out)
+{
+  if (!rsmp::knobs().test_hooks) return -1;
+  const int kind = tracks_src_kind(src_format);
+  rsmp::TracksMix m;
+  if (kind < 0 || !src || !out || mix_matrix(mix, nch_src, nch, m) != RR_OK) return RR_INVPARAM;
+  const size_t fb = size_t(nch_src) * rsmp::tracks_src_bytes(kind);
+  for (size_t i = 0; i < count; ++i)
+    for (int o = 0; o < nch; ++o) out[i * nch + o] = rsmp::tracks_mix_sample(m, kind, static_cast<const unsigned char *>(src) + (first_frame + i) * fb, o);
+  return RR_OK;
 }
 
 } // extern "C"

@@ -43,6 +43,7 @@ EXPECTED_SYMBOLS = [
     "RRX_isamp_max", "RRX_available", "RRX_channels", "RRX_streams",
     "RRX_describe_plan", "RRX_describe_dispatch", "RRX_plan_table",
     "RRX_reset", "RRX_tracks_batches", "RRX_plan_cache_clear", "RRX_plan_cache_stats",
+    "RRX_mix_device", "RRX_debug_mix_host", "RRX_tracks_stage_mix_device", "RRX_tracks_stage_mix_window_device", "RRX_debug_tracks_mix_host",
 ]
 RRX_FMT_FLOAT, RRX_FMT_DOUBLE = 0, 1  # sample formats of a handle (ratelib_amd.h)
 RRX_FMT_S16, RRX_FMT_S32 = 16, 32      # interleaved signed integer PCM (24-bit audio left-justified in S32)
@@ -51,6 +52,30 @@ _FMT_DTYPE = {RRX_FMT_FLOAT: np.dtype(np.float32), RRX_FMT_DOUBLE: np.dtype(np.f
               RRX_FMT_S32: np.dtype(np.int32)}
 _DTYPE_FMT = {d: f for f, d in _FMT_DTYPE.items()}
 RRX_SHAPE_MAX_ORDER = 16
+RRX_MIX_MAX_CH = 16
+
+
+def _mix_matrices():
+    h = 0.5 ** 0.5
+    m = {"stereo_to_mono": [[0.5, 0.5]],
+         "mono_to_stereo": [[1.0], [1.0]],
+         "swap": [[0.0, 1.0], [1.0, 0.0]],
+         "mid_side": [[0.5, 0.5], [0.5, -0.5]],
+         "5.1_to_stereo": [[1.0, 0.0, h, 0.0, h, 0.0], [0.0, 1.0, h, 0.0, 0.0, h]],
+         "7.1_to_stereo": [[1.0, 0.0, h, 0.0, h, 0.0, h, 0.0], [0.0, 1.0, h, 0.0, 0.0, h, 0.0, h]]}
+    out = {}
+    for k, v in m.items():
+        out[k] = np.array(v, dtype=np.float64)
+        out[k].setflags(write=False)
+    return out
+
+
+MIX_MATRICES = _mix_matrices()
+"""Channel-mixing matrices (mix_device, tracks_stage_mix_device, `mix=`): float64 [nch_dst, nch_src], rows are output channels,
+WAVE channel order (FL FR FC LFE BL BR [SL SR]).  "mid_side" is M = (L + R) / 2, S = (L - R) / 2.  The two surround downmixes are
+ITU-R BS.775's: front at 1.0, centre and surrounds at sqrt(0.5), and the LFE NOT CONNECTED -- its coefficient is zero, and a zero
+coefficient leaves the term out of the sum (ratelib_amd.h), so nothing the LFE holds reaches the output.  A full-scale source can
+clip through them: mix_matrix(name, normalize=True)."""
 
 NOISE_SHAPES = {
     "lipshitz5": (2.033, -2.165, 1.959, -1.590, 0.6149),
@@ -342,6 +367,14 @@ def lib():
             L.RRX_debug_tracks_limit_release_window_host.argtypes = host
             L.RRX_tracks_limit_release_window_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz, sz, sz]
             L.RRX_tracks_limit_release_window_work_doubles.restype = sz
+        if hasattr(L, "RRX_mix_device"):  # (as above)
+            host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, sz, C.c_int, vp]
+            L.RRX_mix_device.argtypes = [C.c_int, vp] + host
+            L.RRX_debug_mix_host.argtypes = host
+            L.RRX_tracks_stage_mix_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, vp, sz]
+            L.RRX_tracks_stage_mix_window_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, sz, sz, sz,
+                                                             vp, sz]
+            L.RRX_debug_tracks_mix_host.argtypes = [C.c_int, vp, C.c_int, sz, sz, C.c_int, vp, vp]
         if hasattr(L, "RRX_reset"):  # (as above)
             u64 = C.c_ulonglong
             L.RRX_reset.argtypes = [vp]
@@ -921,6 +954,114 @@ def tracks_stage_window_device(packed, table, in_rate, out_rate, row_frames, win
                                                 C.c_void_p(table.data_ptr()), ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total,
                                                 row_frames, win_first, win_frames, C.c_void_p(out.data_ptr()), out.shape[1]),
            "RRX_tracks_stage_window_device")
+    return out
+
+
+def mix_matrix(name, normalize=False):
+    """A matrix of MIX_MATRICES by name (a writable copy), or any array-like [nch_dst, nch_src] as float64.  normalize=True divides
+    it by its largest row sum of magnitudes when that is above 1, so that a full-scale source cannot clip."""
+    m = np.array(MIX_MATRICES[name] if isinstance(name, str) else name, dtype=np.float64)
+    if normalize:
+        worst = float(np.abs(m).sum(axis=1).max()) if m.size else 0.0
+        if worst > 1.0:
+            m = m / worst
+    return m
+
+
+def _mix_checked(matrix, nch_src=None, nch_dst=None):
+    """the matrix of a mixing call: a name of MIX_MATRICES or an array [nch_dst, nch_src] -> contiguous float64; ValueError for a
+    shape that does not fit"""
+    if isinstance(matrix, str):
+        if matrix not in MIX_MATRICES:
+            raise ValueError("unknown mix %r (MIX_MATRICES: %s)" % (matrix, ", ".join(sorted(MIX_MATRICES))))
+        matrix = MIX_MATRICES[matrix]
+    m = np.ascontiguousarray(matrix, dtype=np.float64)
+    if m.ndim != 2 or not 1 <= m.shape[0] <= RRX_MIX_MAX_CH or not 1 <= m.shape[1] <= RRX_MIX_MAX_CH:
+        raise ValueError("a mix is a matrix [nch_dst, nch_src] of 1 to %d channels each, not shape %r" % (RRX_MIX_MAX_CH, m.shape))
+    if not np.isfinite(m).all():
+        raise ValueError("the mix has a coefficient that is not finite")
+    if nch_src is not None and m.shape[1] != nch_src:
+        raise ValueError("the mix takes %d channels and the source has %d" % (m.shape[1], nch_src))
+    if nch_dst is not None and m.shape[0] != nch_dst:
+        raise ValueError("the mix gives %d channels where %d are expected" % (m.shape[0], nch_dst))
+    return m
+
+
+def mix_device(rows, matrix, out=None, stream=None, frames=None):
+    """A channel-mixing matrix on device-resident rows (RRX_mix_device): `rows` is a contiguous float32 or float64 device tensor
+    [frames, nch_src] or [nstreams, frames, nch_src], `matrix` a name of MIX_MATRICES or an array [nch_dst, nch_src].  Every
+    frame is mixed by the rule of ratelib_amd.h -- fp64 products and sums, each rounded on its own, a zero coefficient meaning
+    "not connected" -- into `out` ([..., frames or more, nch_dst] of the same dtype, which must not overlap `rows`; allocated when
+    not passed).  `frames` (default: all): only frames [0, frames) of every row are mixed, and nothing else of `out` is written.
+    Returns `out`.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
+    import torch
+    shape = tuple(rows.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    if rows.dtype not in (torch.float32, torch.float64):
+        raise TypeError("%s buffer: mix_device reads float32 or float64 frames" % (rows.dtype,))
+    if not getattr(rows, "is_cuda", False) or not rows.is_contiguous():
+        raise TypeError("mix_device works on contiguous device tensors")
+    nstreams, stride, nch_src = (1,) + shape if len(shape) == 2 else shape
+    m = _mix_checked(matrix, nch_src=nch_src)
+    nch_dst = m.shape[0]
+    frames = stride if frames is None else int(frames)
+    if not 0 <= frames <= stride:
+        raise ValueError("frames must be 0 to %d, not %d" % (stride, frames))
+    dev = rows.device
+    if out is None:
+        out = torch.empty(shape[:-1] + (nch_dst,), dtype=rows.dtype, device=dev)
+    elif (out.dtype != rows.dtype or out.dim() != len(shape) or out.shape[-1] != nch_dst or out.shape[-2] < frames or out.device != dev
+          or not out.is_contiguous() or (len(shape) == 3 and out.shape[0] != nstreams)):
+        raise TypeError("out must be a contiguous %s tensor [..., at least %d, %d] on %s" % (rows.dtype, frames, nch_dst, dev))
+    if not frames or not nstreams:
+        return out
+    _ensure_init()
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().RRX_mix_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
+                                RRX_FMT_DOUBLE if rows.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), stride, nstreams,
+                                frames, nch_src, C.c_void_p(out.data_ptr()), out.shape[-2], nch_dst, m.ctypes.data), "RRX_mix_device")
+    return out
+
+
+def tracks_stage_mix_device(packed, table, matrix, in_rate, out_rate, row_frames, out=None, stream=None):
+    """tracks_stage_device with a channel mix on load (RRX_tracks_stage_mix_device): `packed` holds nch_src channels (for uint8,
+    packed 24 bit, nch_src = shape[1] // 3), `matrix` is a name of MIX_MATRICES or an array [nch, nch_src], and the rows are
+    float32 [ntracks, row_frames, nch] -- bit for bit those of tracks_stage_device on the float32 source whose frames are the
+    mixed frames (ratelib_amd.h has the rule), LPC extensions included.  The source is read once, as it is stored.  `table`, `out`
+    and `stream` as in tracks_stage_device: the call only enqueues."""
+    fmt, ntracks, nch_src, src_total = _tracks_stage_source(packed, table)
+    m = _mix_checked(matrix, nch_src=nch_src)
+    out = _tracks_stage_out(out, (ntracks, int(row_frames), m.shape[0]), packed.device)
+    packed = _tracks_stage_pointer(packed)
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    index = packed.device.index
+    _check(lib().RRX_tracks_stage_mix_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
+                                             C.c_void_p(table.data_ptr()), ntracks, fmt, nch_src, C.c_void_p(packed.data_ptr()), src_total,
+                                             m.shape[0], m.ctypes.data, C.c_void_p(out.data_ptr()), int(row_frames)),
+           "RRX_tracks_stage_mix_device")
+    return out
+
+
+def tracks_stage_mix_window_device(packed, table, matrix, in_rate, out_rate, row_frames, win_first, win_frames, out=None, stream=None):
+    """tracks_stage_mix_device on a window of the rows (RRX_tracks_stage_mix_window_device): frames [win_first, win_first +
+    win_frames) of every row, bit for bit, as tracks_stage_window_device gives those of tracks_stage_device; `out` as there."""
+    fmt, ntracks, nch_src, src_total = _tracks_stage_source(packed, table)
+    m = _mix_checked(matrix, nch_src=nch_src)
+    nch = m.shape[0]
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
+    if out is not None and (out.dim() != 3 or out.shape[1] < win_frames):
+        raise TypeError("out must be a contiguous float32 tensor [%d, at least %d, %d] on %s" % (ntracks, win_frames, nch, packed.device))
+    out = _tracks_stage_out(out, (ntracks, win_frames if out is None else out.shape[1], nch), packed.device)
+    packed = _tracks_stage_pointer(packed)
+    if not win_frames:  # (an empty tensor has no pointer, and there is nothing to do)
+        return out
+    ptr = getattr(stream, "cuda_stream", stream) or 0
+    index = packed.device.index
+    _check(lib().RRX_tracks_stage_mix_window_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
+                                                    C.c_void_p(table.data_ptr()), ntracks, fmt, nch_src, C.c_void_p(packed.data_ptr()),
+                                                    src_total, nch, m.ctypes.data, row_frames, win_first, win_frames,
+                                                    C.c_void_p(out.data_ptr()), out.shape[1]), "RRX_tracks_stage_mix_window_device")
     return out
 
 
@@ -2542,8 +2683,13 @@ class Resampler:
             return finish_shaped_device(y, dst_format, shaping, segment, **finish_kw)[:3]
         return finish_device(y, dst_format, **finish_kw)
 
-    def _tracks_checked(self, tracks):
-        """the tracks of a convert_tracks_* call, checked: (list of tracks, plan with the idle streams as zero-length tracks)"""
+    def _tracks_mix(self, mix):
+        """the `mix=` of a convert_tracks_* call: None, or the matrix [nch, nch_src] checked against the handle's channels"""
+        return None if mix is None else _mix_checked(mix, nch_dst=self.nch)
+
+    def _tracks_checked(self, tracks, mix=None):
+        """the tracks of a convert_tracks_* call, checked: (list of tracks, plan with the idle streams as zero-length tracks).
+        `mix` (a checked matrix): the tracks have its column count of channels, not the handle's."""
         import torch
         if self.dtype != np.float32:
             raise TypeError("convert_tracks_device needs a float32 handle (the LPC arithmetic is float32), not %s" % self.dtype)
@@ -2553,7 +2699,8 @@ class Resampler:
         dt = tracks[0].dtype
         if _tracks_src_format(dt) is None:
             raise TypeError("expected float32, int16, int32 or uint8 (packed 24-bit) tensors, not %s" % dt)
-        last = self.nch * 3 if dt == torch.uint8 else self.nch
+        nch_src = self.nch if mix is None else mix.shape[1]
+        last = nch_src * 3 if dt == torch.uint8 else nch_src
         for x in tracks:
             if x.dtype != dt:
                 raise TypeError("the tracks of one call share a dtype: %s and %s" % (dt, x.dtype))
@@ -2564,11 +2711,13 @@ class Resampler:
         # the streams without a track are zero-length tracks: they own no output
         return tracks, _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
 
-    def _convert_tracks_rows(self, tracks, scratch=None):
+    def _convert_tracks_rows(self, tracks, scratch=None, mix=None):
         """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch]).
-        `scratch` (a _Scratch): the staged rows and the output rows are views of its buffers instead of new tensors."""
+        `scratch` (a _Scratch): the staged rows and the output rows are views of its buffers instead of new tensors.  `mix`: the
+        stage call is tracks_stage_mix_device."""
         import torch
-        tracks, plan = self._tracks_checked(tracks)
+        mix = self._tracks_mix(mix)
+        tracks, plan = self._tracks_checked(tracks, mix)
         dev = tracks[0].device
         table = plan.to_device(dev)
         total, cap = plan.row_frames, plan.out_row_cap
@@ -2583,7 +2732,11 @@ class Resampler:
         self.set_stream(cur.cuda_stream)
         try:
             rows = None if scratch is None else scratch.take("rows", (self.nstreams, total, self.nch), dev)
-            src = tracks_stage_device(torch.cat(tracks).contiguous(), table, self.cfg.in_rate, self.cfg.out_rate, total, out=rows, stream=cur)
+            if mix is None:
+                src = tracks_stage_device(torch.cat(tracks).contiguous(), table, self.cfg.in_rate, self.cfg.out_rate, total, out=rows, stream=cur)
+            else:
+                src = tracks_stage_mix_device(torch.cat(tracks).contiguous(), table, mix, self.cfg.in_rate, self.cfg.out_rate, total, out=rows,
+                                              stream=cur)
             got = 0
 
             def pull():
@@ -2609,7 +2762,7 @@ class Resampler:
             raise RuntimeError("convert_tracks_device: %d output frames where the plan expects %d" % (got, need))
         return plan, table, out
 
-    def convert_tracks_device(self, tracks):
+    def convert_tracks_device(self, tracks, mix=None):
         """Whole tracks of UNEQUAL length, one per stream, device to device: convert_track_device for a ragged batch.  `tracks`
         is a list of float32 device tensors [frames_i, nch], at most `nstreams` of them (the streams left over run empty) -- or of
         integer PCM as it is stored: all int16, all int32, or all uint8 [frames_i, nch * 3] (packed 24 bit), which the stage pass
@@ -2622,8 +2775,12 @@ class Resampler:
         every track gets, shape and bits, what convert_track_device gives it on a one-stream handle of its own.  Returns a list
         of tensors [out_frames_i, nch]: views of the handle's output rows.  Runs on torch's current stream of the tracks'
         device, copies no sample to the host and leaves the handle drained, as convert_track_device does (reset() makes it take the
-        next batch).  The padding is resampled too: batch tracks of similar length (tracks_batches, convert_library_to_pcm)."""
-        plan, _, out = self._convert_tracks_rows(tracks)
+        next batch).  The padding is resampled too: batch tracks of similar length (tracks_batches, convert_library_to_pcm).
+
+        `mix` (a name of MIX_MATRICES or an array [nch, nch_src]): the tracks hold nch_src channels and are mixed down (or up) to
+        the handle's nch on load, by tracks_stage_mix_device -- "these 5.1 tracks to 48 kHz stereo" reads the source once and
+        resamples two channels.  A matrix whose shape does not fit the handle or the tracks raises ValueError."""
+        plan, _, out = self._convert_tracks_rows(tracks, mix=mix)
         return [out[t, int(e.out_first):int(e.out_first + e.out_frames)] for t, e in zip(range(len(tracks)), plan.table)]
 
     def _tracks_finish_kw(self, ntracks, finish_kw, who):
@@ -2650,10 +2807,14 @@ class Resampler:
 
         `shaping` is accepted for symmetry with convert_tracks_to_pcm_device and refused: noise shaping needs a per-track state
         across windows, and the windowed form of it is not built.  (It is built under a name of its own,
-        convert_tracks_to_pcm_streamed_shaped, which carries that state.)"""
+        convert_tracks_to_pcm_streamed_shaped, which carries that state.)
+
+        `mix=` (a keyword beside those of the output stage; default None) as in convert_tracks_device: the windows are staged by
+        tracks_stage_mix_window_device."""
+        mix = finish_kw.pop("mix", None)
         if shaping is not None:
             raise ValueError("noise shaping in the windowed form is not built: use convert_tracks_to_pcm_device")
-        return self._convert_tracks_streamed(tracks, dst_format, window, _scratch, None, finish_kw, "convert_tracks_to_pcm_streamed")
+        return self._convert_tracks_streamed(tracks, dst_format, window, _scratch, None, finish_kw, "convert_tracks_to_pcm_streamed", mix=mix)
 
     def convert_tracks_to_pcm_streamed_shaped(self, tracks, dst_format, shaping, segment=65536, window=None, **finish_kw):
         """convert_tracks_to_pcm_device(..., shaping=, segment=) in bounded memory: convert_tracks_to_pcm_streamed with noise-shaped
@@ -2671,7 +2832,7 @@ class Resampler:
         scratch = finish_kw.pop("_scratch", None)
         return self._convert_tracks_streamed(tracks, dst_format, window, scratch, (shaping, segment), finish_kw, "convert_tracks_to_pcm_streamed_shaped")
 
-    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None, limit=None):
+    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None, limit=None, mix=None):
         """the loop of convert_tracks_to_pcm_streamed (shaped None) and convert_tracks_to_pcm_streamed_shaped (shaped = (shaping,
         segment)): stage a window, push it, pull whatever is available into the output window and finish it at the running output
         position, then drain the same way.  The shaped form finishes with tracks_finish_shaped_window_device and ping-pongs two
@@ -2680,9 +2841,11 @@ class Resampler:
         window instead of the output stage; nothing is written then, and the return is what that callable's `result()` gives.
         `limit` (the limited form): called once as limit(table, cap, output window, stream), it gives a _WindowLimiter, which sits
         between the pull and the stage behind it -- that stage then sees the limited windows the limiter emits, ascending and
-        contiguous from frame 0 like the pulled ones, and the rest of them after the final pull."""
+        contiguous from frame 0 like the pulled ones, and the rest of them after the final pull.  `mix`: the windows are staged by
+        tracks_stage_mix_window_device."""
         import torch
-        tracks, plan = self._tracks_checked(tracks)
+        mix = self._tracks_mix(mix)
+        tracks, plan = self._tracks_checked(tracks, mix)
         n, dev = len(tracks), tracks[0].device
         step = self.isamp_max
         window = step if window is None else int(window)
@@ -2757,7 +2920,10 @@ class Resampler:
 
                 for pos in range(0, total, window):
                     k = min(window, total - pos)
-                    tracks_stage_window_device(packed, table, in_rate, out_rate, total, pos, k, out=win, stream=cur)
+                    if mix is None:
+                        tracks_stage_window_device(packed, table, in_rate, out_rate, total, pos, k, out=win, stream=cur)
+                    else:
+                        tracks_stage_mix_window_device(packed, table, mix, in_rate, out_rate, total, pos, k, out=win, stream=cur)
                     self.push_device(win, k, stride=win.shape[1])
                     pull()
                 self.drain()
@@ -2778,17 +2944,18 @@ class Resampler:
         views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
         return views, peak[:n], clipped[:n]
 
-    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, shaping=None, segment=65536, **finish_kw):
+    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, shaping=None, segment=65536, mix=None, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
         packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  The tracks may be integer PCM
         themselves (int16, int32, or uint8 packed 24 bit, as in convert_tracks_device): PCM in, PCM out, with float32 only in the
         rows the handle is pushed from.  Returns (list of per-track
         views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views.
         With `shaping` (a name of NOISE_SHAPES or coefficients) the output stage is tracks_finish_shaped_device(..., shaping,
-        segment, **finish_kw): noise-shaped dither, on by default there, in segments counted from each track's first frame."""
+        segment, **finish_kw): noise-shaped dither, on by default there, in segments counted from each track's first frame.
+        `mix` as in convert_tracks_device."""
         import torch
         tracks = list(tracks)
-        plan, table, out = self._convert_tracks_rows(tracks, _scratch)
+        plan, table, out = self._convert_tracks_rows(tracks, _scratch, mix=mix)
         n = len(tracks)
         self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_device")
         finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
@@ -3099,7 +3266,7 @@ class Resampler:
                                     release=release))
         return views, peak, clipped, gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
 
-    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536):
+    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536, mix=None):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut
         into the length-sorted batches of tracks_batches for the handle's own `nstreams` -- no other split resamples less padding
         -- and converted batch after batch, with reset() before every batch whenever the handle has been used.  Each batch runs
@@ -3117,14 +3284,18 @@ class Resampler:
         `shaping` (a name of NOISE_SHAPES or coefficients) and `segment`: every batch is finished by tracks_finish_shaped_device
         with the same per-batch seed, so the rule above holds with finish_shaped_device for finish_device; `dither` keeps its
         default here.  With `window` it raises ValueError: the windowed form of noise shaping is not built (under this name:
-        convert_library_to_pcm_streamed_shaped is that form)."""
+        convert_library_to_pcm_streamed_shaped is that form).
+
+        `mix` as in convert_tracks_device: every batch is staged with it."""
         if shaping is not None and window is not None:
             raise ValueError("noise shaping in the windowed form is not built: leave `window` out")
         kw = {} if shaping is None else {"shaping": shaping, "segment": segment}
+        if mix is not None:
+            kw["mix"] = self._tracks_mix(mix)
         if window is None:
             return self._convert_library(tracks, dst_format, gain, dither, seed, lambda batch, bkw: self.convert_tracks_to_pcm_device(batch, dst_format, **kw, **bkw))
         return self._convert_library(tracks, dst_format, gain, dither, seed,
-                                     lambda batch, bkw: self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **bkw))
+                                     lambda batch, bkw: self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **kw, **bkw))
 
     def convert_library_to_pcm_streamed_shaped(self, tracks, dst_format, window, shaping, segment=65536, gain=None, dither=True, seed=0):
         """convert_library_to_pcm(..., shaping=, segment=) in bounded memory: the library rule of that method -- length-sorted

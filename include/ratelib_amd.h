@@ -1255,6 +1255,67 @@ int RRX_describe_dispatch(const RR_config *config, int nchannels, char *buf, siz
  * the full length.  Returns RR_OK or RR_INVPARAM. */
 int RRX_plan_table(const RR_config *config, int which, double *out, size_t cap, size_t *count);
 
+/* Channel mixing ("Channel mixing"): a matrix applied per frame -- on load in the stage pass of a ragged batch, so
+ * that a 5.1 library is read once, as stored, and only two channels are ever resampled, and on plain rows behind a handle (mono to
+ * stereo, mid/side, swap, polarity).
+ *
+ * The mixing rule is part of this ABI.  `mix` is a HOST pointer to nch_dst * nch_src finite doubles, row-major: mix[o * nch_src + c]
+ * is the coefficient of source channel c in output channel o, 1 <= nch_src, nch_dst <= RRX_MIX_MAX_CH.  The calls copy the matrix
+ * into their launch arguments (as RRX_true_peak_device copies coefs): it may be freed on return.  For one frame and output channel o
+ *   v_c = the source sample of channel c as an exact double: s * 2^-15 (S16), s * 2^-23 (S24_3), s * 2^-31 (S32), (double)x for
+ *         float32, x for float64
+ *   y_o = sum over c ascending of mix[o][c] * v_c, every product and every sum rounded on its own (fp64, no fused multiply-add),
+ *         WHERE TERMS WITH mix[o][c] == 0.0 (either sign) ARE LEFT OUT; the sum starts from its first product, not from 0.0; a row
+ *         of zeros gives +0.0
+ *   x_o = (float)y_o for float32 rows (one rounding, to nearest even), y_o for float64 rows
+ * A zero coefficient means "not connected", not a multiplication by zero: a NaN or an infinity in an unconnected channel (a dropped
+ * LFE) does not reach the output; -0.0 passes through an identity or permutation matrix unchanged; and with the identity matrix
+ * the integer sources give the bits of RRX_tracks_stage_device_samples's conversion, hence its rows.
+ * S32 is exact in the double, so a mixed S32 source is rounded ONCE, from the exact sum.  That is deliberately not the result of
+ * converting to float32 first (the un-mixed stage's conversion) and mixing afterwards.
+ *
+ * RRX_mix_device: source rows [nstreams][src_stride][nch_src] and destination rows [nstreams][dst_stride][nch_dst], both of `fmt`,
+ * RRX_FMT_FLOAT or RRX_FMT_DOUBLE; frames [0, frames) of every stream are mixed by the rule above, and nothing outside [0, frames)
+ * of a destination row is written.  Strides (in frames, ignored for nstreams == 1), the alignment of one sample, device, hip_stream,
+ * stream ordering and "only enqueues" are RRX_finish_device's.  The buffers must not overlap.  Returns RR_INVPARAM, before any
+ * device is touched, for mix NULL, a coefficient that is not finite, a channel count outside 1..RRX_MIX_MAX_CH, a format other than
+ * those two, a NULL buffer, d_dst == d_src or any other overlap, nstreams < 1, a stride below frames, sizes of 2^60 samples or more,
+ * or device < -1; RR_EXTUNINIT, RR_INTERNAL as RRX_finish_device.  frames == 0 is RR_OK and touches nothing. */
+#define RRX_MIX_MAX_CH 16
+int RRX_mix_device(int device, void *hip_stream, int fmt, const void *d_src, size_t src_stride, int nstreams, size_t frames,
+                   int nch_src, void *d_dst, size_t dst_stride, int nch_dst, const double *mix);
+
+/* RRX_tracks_stage_device_samples with the mix on load.  The packed source is [src_total][nch_src] of src_format (RRX_FMT_FLOAT,
+ * RRX_FMT_S16, RRX_FMT_S24_3 -- nch_src * 3 bytes a frame, so a track starts at any byte offset -- or RRX_FMT_S32; RRX_FMT_DOUBLE is
+ * refused as there), the rows are [ntracks][row_frames][nch] float32, and mix is [nch][nch_src].  The rows equal, bit for bit, those
+ * of RRX_tracks_stage_device on the float32 packed buffer [src_total][nch] whose frames are the mixed frames x_o of the source.  So
+ * the copied frames are mixed, both LPC extensions run on the mixed base frames (the rule is applied as they are loaded, by the
+ * same function), zeros stand behind the extension, and frames that a wrong table puts past the source are +0.0f.  RRX_track is in
+ * frames and does not change: a table of RRX_tracks_plan serves any channel pair.
+ * The read contract (only aligned dwords that hold a byte of the source are read), the clamps (a wrong table gives wrong samples,
+ * never an access outside source or rows), "every frame of every row is written exactly once", device, hip_stream, stream ordering,
+ * "only enqueues", refusals and return values are RRX_tracks_stage_device_samples's, word for word, with nch_src in the source
+ * sizes and nch in the row sizes; and RR_INVPARAM, before any device is touched, also for mix NULL, a coefficient that is not
+ * finite, or nch or nch_src outside 1..RRX_MIX_MAX_CH.
+ * RRX_tracks_stage_mix_window_device has the bits of the whole-row call for frames [win_first, win_first + win_frames), as
+ * RRX_tracks_stage_window_device has of its whole-row call, with that call's window rules and refusals. */
+int RRX_tracks_stage_mix_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks, int ntracks,
+                                int src_format, int nch_src, const void *d_packed, size_t src_total, int nch, const double *mix,
+                                fb_sample_t *d_rows, size_t row_frames);
+int RRX_tracks_stage_mix_window_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks,
+                                       int ntracks, int src_format, int nch_src, const void *d_packed, size_t src_total, int nch,
+                                       const double *mix, size_t row_frames, size_t win_first, size_t win_frames, fb_sample_t *d_win,
+                                       size_t win_stride);
+/* Test hooks (host only, need no device), refused with -1 unless RSMP_TEST_HOOKS is set as above: serial loops over the very
+ * per-frame function the kernels call.  RRX_debug_mix_host is RRX_mix_device on HOST pointers, with its refusals.
+ * RRX_debug_tracks_mix_host writes out[count][nch], the mixed float32 frames [first_frame, first_frame + count) of a HOST source
+ * [..][nch_src] of src_format; RR_INVPARAM for an unknown format, a NULL pointer, a channel count outside 1..RRX_MIX_MAX_CH or a
+ * coefficient that is not finite. */
+int RRX_debug_mix_host(int fmt, const void *src, size_t src_stride, int nstreams, size_t frames, int nch_src, void *dst,
+                       size_t dst_stride, int nch_dst, const double *mix);
+int RRX_debug_tracks_mix_host(int src_format, const void *src, int nch_src, size_t first_frame, size_t count, int nch,
+                              const double *mix, float *out);
+
 #ifdef __cplusplus
 }
 #endif
