@@ -200,7 +200,7 @@ def lib():
         _hip_rt = _share_hip_runtime_with_torch()
         L = C.CDLL(p)
         P = C.POINTER
-        vp, sz = C.c_void_p, C.c_size_t
+        vp, sz, u64 = C.c_void_p, C.c_size_t, C.c_ulonglong
         L.init_ratelib.argtypes = [_ALLOC_CB]
         L.RR_open.argtypes = [P(RRConfig), C.c_int, P(vp)]
         L.RRX_open_batch.argtypes = [P(RRConfig), C.c_int, C.c_int, P(vp)]
@@ -259,19 +259,16 @@ def lib():
             L.RRX_lpc_extrapolate_device.argtypes = [C.c_int, vp, vp, sz, C.c_int, sz, C.c_int, C.c_int, sz, sz]
             L.RRX_edge_geometry.argtypes = [sz, sz, P(sz), P(sz), P(sz), P(sz)]
         if hasattr(L, "RRX_finish_device"):  # (as above)
-            u64 = C.c_ulonglong
             host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_int, u64, u64, vp, vp]
             L.RRX_finish_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_finish_host.argtypes = host
         if hasattr(L, "RRX_finish_shaped_device"):  # (as above)
-            u64 = C.c_ulonglong
             host = [C.c_int, vp, sz, C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, C.c_int, u64, u64, vp, C.c_int, sz, vp, vp, vp, vp]
             L.RRX_finish_shaped_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_finish_shaped_host.argtypes = host
             L.RRX_tracks_finish_shaped_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, sz, vp, C.c_int, u64,
                                                           vp, C.c_int, sz, vp, vp]
         if hasattr(L, "RRX_true_peak_device"):  # (as above)
-            u64 = C.c_ulonglong
             host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, u64, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
             L.RRX_true_peak_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_true_peak_host.argtypes = host
@@ -294,7 +291,6 @@ def lib():
             L.RRX_limit_release_work_doubles.argtypes = [C.c_int, sz, C.c_int, sz, sz]
             L.RRX_limit_release_work_doubles.restype = sz
         if hasattr(L, "RRX_loudness_device"):  # (as above)
-            u64 = C.c_ulonglong
             host = [C.c_int, vp, sz, C.c_int, sz, C.c_int, vp, u64, vp, sz, vp, vp, vp, sz, vp, sz]
             L.RRX_loudness_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_loudness_host.argtypes = host
@@ -317,7 +313,6 @@ def lib():
             L.RRX_loudness_range_groups_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_loudness_range_groups_host.argtypes = host
         if hasattr(L, "RRX_tracks_plan"):  # (as above)
-            u64 = C.c_ulonglong
             L.RRX_track_geometry.argtypes = [P(RRConfig), sz, P(sz), P(sz), P(sz), P(sz)]
             L.RRX_tracks_plan.argtypes = [P(RRConfig), P(sz), C.c_int, P(RRXTrack), P(sz), P(sz), P(sz), P(sz)]
             L.RRX_tracks_stage_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, vp, sz, vp, sz]
@@ -326,13 +321,11 @@ def lib():
             L.RRX_tracks_stage_device_samples.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, sz]
             L.RRX_debug_tracks_load_host.argtypes = [C.c_int, vp, sz, sz, vp]
         if hasattr(L, "RRX_tracks_stage_window_device"):  # (as above)
-            u64 = C.c_ulonglong
             L.RRX_tracks_stage_window_device.argtypes = [C.c_int, vp, sz, sz, vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, vp, sz]
             L.RRX_tracks_finish_window_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp,
                                                           C.c_int, u64, vp, vp]
             L.RRX_debug_tracks_window_cut.argtypes = [P(RRXTrack), sz, sz, sz, C.c_int, sz, sz, P(u64), P(u64)]
         if hasattr(L, "RRX_tracks_finish_shaped_window_device"):  # (as above)
-            u64 = C.c_ulonglong
             host = [vp, C.c_int, C.c_int, C.c_int, vp, sz, sz, sz, sz, C.c_int, vp, sz, vp, C.c_int, u64, vp, C.c_int, sz, vp, vp, vp, vp]
             L.RRX_tracks_finish_shaped_window_device.argtypes = [C.c_int, vp] + host
             L.RRX_debug_tracks_finish_shaped_window_host.argtypes = host
@@ -376,7 +369,6 @@ def lib():
                                                              vp, sz]
             L.RRX_debug_tracks_mix_host.argtypes = [C.c_int, vp, C.c_int, sz, sz, C.c_int, vp, vp]
         if hasattr(L, "RRX_reset"):  # (as above)
-            u64 = C.c_ulonglong
             L.RRX_reset.argtypes = [vp]
             L.RRX_tracks_batches.argtypes = [P(RRConfig), P(sz), C.c_int, C.c_int, P(C.c_int), P(sz), P(C.c_int), P(u64), P(u64)]
             L.RRX_plan_cache_clear.argtypes = []
@@ -437,6 +429,161 @@ def edge_geometry(in_rate, out_rate):
     return tuple(x.value for x in v)
 
 
+# -- the shared preludes of the handle-free wrappers: every rule of a call shape is written once, here.  A wrapper is its own scalar
+# -- checks, these, the early return for empty input, and one C call.  The parts that touch `is_cuda` / `device` are functions of their
+# -- own, so that a wrapper refuses its scalars first.
+def _where(dev, stream):
+    """(device index, stream pointer), the two leading arguments of every *_device call: `stream` is a hipStream_t as an integer or a
+    torch stream, None / 0 the default stream"""
+    return -1 if dev.index is None else int(dev.index), getattr(stream, "cuda_stream", stream) or 0
+
+
+def _ptr(t):
+    """the pointer argument of an optional tensor: null when it was not passed.  (ctypes takes the integer of data_ptr() for a void
+    pointer as it is, so a tensor that is always there is passed as t.data_ptr().)"""
+    return None if t is None else t.data_ptr()
+
+
+_FLOAT_FMT = {}  # (by dtype object: str() of a torch dtype costs more than the rest of the lookup)
+
+
+def _float_fmt(dtype):
+    """the RRX_FMT_* of a float32 or float64 dtype (torch's, or its name); None for any other"""
+    if dtype not in _FLOAT_FMT:
+        _FLOAT_FMT[dtype] = {"float32": RRX_FMT_FLOAT, "float64": RRX_FMT_DOUBLE}.get(str(dtype).rpartition(".")[2])
+    return _FLOAT_FMT[dtype]
+
+
+def _frames_shape(x):
+    """a [frames, nch] or [nstreams, frames, nch] source: (shape, nstreams, frames, nch)"""
+    shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    return (shape,) + ((1,) + shape if len(shape) == 2 else shape)
+
+
+def _float_frames(x, who):
+    """_frames_shape of a contiguous float32 or float64 source, for the pass `who`: (shape, RRX_FMT_*, nstreams, frames, nch).
+    Touches neither the device nor the pointer: _on_device does, behind the caller's scalar checks."""
+    shape, nstreams, frames, nch = _frames_shape(x)
+    fmt = _float_fmt(x.dtype)
+    if fmt is None:
+        raise TypeError("%s buffer: %s reads float32 or float64 frames" % (x.dtype, who))
+    if not x.is_contiguous():
+        raise ValueError("the tensor must be contiguous")
+    return shape, fmt, nstreams, frames, nch
+
+
+def _on_device(x, who):
+    """the device of the source of the pass `who`; TypeError for anything that is not a device tensor"""
+    if not getattr(x, "is_cuda", False):
+        raise TypeError("%s works on device tensors: the frames must be in HBM" % who)
+    return x.device
+
+
+def _tracks_frames(t, name, middle):
+    """the rows, window or halo buffer of a per-track call, a contiguous float32 or float64 device tensor [ntracks, `middle`, nch]
+    that the messages call `name`: (RRX_FMT_*, ntracks, frames a row, nch)"""
+    fmt = _float_fmt(t.dtype)
+    if t.dim() != 3 or fmt is None or not t.is_cuda or not t.is_contiguous():
+        raise TypeError("%s must be a contiguous float32 or float64 device tensor [ntracks, %s, nch]" % (name, middle))
+    ntracks, stride, nch = t.shape
+    return fmt, ntracks, stride, nch
+
+
+def _gain(gain, n, dev):
+    """the gain of a call on `n` streams or tracks: None, or a float64 tensor [n] on `dev` -- made from a float, checked otherwise"""
+    import torch
+    if gain is not None and not hasattr(gain, "data_ptr"):
+        gain = torch.full((n,), float(gain), dtype=torch.float64, device=dev)
+    if gain is not None:
+        if gain.dtype != torch.float64 or tuple(gain.shape) != (n,) or gain.device != dev or not gain.is_contiguous():
+            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (n, dev))
+    return gain
+
+
+def _pcm_out(out, dst_format, lead, nch, dev):
+    """the destination of an output stage, `lead` + (nch,) samples of `dst_format` (packed 24 bit: nch * 3 bytes): allocated when
+    not passed, checked otherwise.  dst_format None measures only and takes no `out`.  (`out=False`, the measure-only form of the
+    shaped calls, is the caller's to turn into None.)"""
+    import torch
+    if dst_format is None:
+        if out is not None:
+            raise ValueError("dst_format=None measures only: there is nothing to write into `out`")
+        return None
+    odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
+    oshape = lead + (last,)
+    if out is None:
+        return torch.empty(oshape, dtype=odt, device=dev)
+    if out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
+        raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
+    return out
+
+
+def _finish_stats(peak, clipped, n, nch, dev):
+    """the two statistics of an output stage, float64 and int64 [n, nch]: allocated (zeroed) when not passed, accumulated into
+    otherwise"""
+    import torch
+    stats = []
+    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
+        if t is None:
+            t = torch.zeros((n, nch), dtype=sdt, device=dev)
+        elif t.dtype != sdt or tuple(t.shape) != (n, nch) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, n, nch, dev))
+        stats.append(t)
+    return stats
+
+
+def _true_peak_stats(true_peak, peak, n, nch, dev):
+    """the two result tensors of a true-peak call: float64 [n, nch], allocated (zeroed) when not passed"""
+    import torch
+    stats = []
+    for t, name in ((true_peak, "true_peak"), (peak, "peak")):
+        if t is None:
+            t = torch.zeros((n, nch), dtype=torch.float64, device=dev)
+        elif t.dtype != torch.float64 or tuple(t.shape) != (n, nch) or t.device != dev or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous float64 tensor [%d, %d] on %s" % (name, n, nch, dev))
+        stats.append(t)
+    return stats
+
+
+def _stream_state(state, nstreams, nch, width, dev):
+    """the state a chunked per-stream call takes: None, or float64 [nstreams, nch, width] on `dev`"""
+    import torch
+    if state is not None:
+        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, width) or state.device != dev or not state.is_contiguous():
+            raise TypeError("state must be a contiguous float64 tensor [%d, %d, %d] on %s" % (nstreams, nch, width, dev))
+
+
+def _state_pair(state, state_out, sshape, dev):
+    """the state a per-track window call reads and the one it writes, each None or float64 `sshape` on `dev`, and never one tensor"""
+    import torch
+    for t, name in ((state, "state"), (state_out, "state_out")):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != sshape or t.device != dev or not t.is_contiguous()):
+            raise TypeError("%s must be a contiguous float64 tensor %r on %s" % (name, sshape, dev))
+    if state is not None and state_out is not None and state_out.data_ptr() == state.data_ptr():
+        raise ValueError("the call must not read and write one state tensor")
+
+
+def _seed_and_first(seed, first_frame, frames):
+    seed, first_frame = int(seed), int(first_frame)
+    if not (0 <= seed < 1 << 64 and 0 <= first_frame and first_frame + frames < 1 << 64):
+        raise ValueError("seed and first_frame + frames must fit 64 unsigned bits")
+    return seed, first_frame
+
+
+def _first_frame(first_frame, frames):
+    first_frame = int(first_frame)
+    if not (0 <= first_frame and first_frame + frames < 1 << 64):
+        raise ValueError("first_frame + frames must fit 64 unsigned bits")
+    return first_frame
+
+
+def _shaped_dst_format(dst_format):
+    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+
+
 def lpc_extrapolate_device(t, first, data_len, extra_bkwd, extra_fwd, order=32, stream=None):
     """LPC edge extrapolation in place on the device (RRX_lpc_extrapolate_device; lpc_extrapolate2 of lpc/lpc.h:27, bit for bit).
 
@@ -444,24 +591,18 @@ def lpc_extrapolate_device(t, first, data_len, extra_bkwd, extra_fwd, order=32, 
     from frame `first` of every stream.  Frames [first - extra_bkwd, first) and [first + data_len, first + data_len + extra_fwd)
     are overwritten, nothing else.  `stream`: a hipStream_t as an integer or a torch stream (None / 0 = the default stream); the
     call only enqueues, and the ordering against work on other streams is the caller's (ratelib_amd.h)."""
-    shape = tuple(t.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    _, nstreams, frames, nch = _frames_shape(t)
     if not str(t.dtype).endswith("float32"):
         raise TypeError("%s buffer: the LPC extrapolator works on float32 frames only" % (t.dtype,))
     if not t.is_contiguous():
         raise ValueError("the tensor must be contiguous")
-    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
     first, data_len, extra_bkwd, extra_fwd = int(first), int(data_len), int(extra_bkwd), int(extra_fwd)
     if min(first, data_len, extra_bkwd, extra_fwd) < 0 or first < extra_bkwd or first + data_len + extra_fwd > frames:
         raise ValueError("frames [%d, %d) do not lie inside the tensor's %d frames"
                          % (first - extra_bkwd, first + data_len + extra_fwd, frames))
     _ensure_init()
-    index = getattr(getattr(t, "device", None), "index", None)
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_lpc_extrapolate_device(-1 if index is None else int(index), C.c_void_p(ptr),
-                                            C.c_void_p(t.data_ptr() + first * nch * 4), frames, nstreams, data_len, nch, int(order),
-                                            extra_bkwd, extra_fwd), "RRX_lpc_extrapolate_device")
+    _check(lib().RRX_lpc_extrapolate_device(*_where(t.device, stream), t.data_ptr() + first * nch * 4, frames, nstreams,
+                                            data_len, nch, int(order), extra_bkwd, extra_fwd), "RRX_lpc_extrapolate_device")
 
 
 def finish_device(x, dst_format, gain=None, dither=False, seed=0, first_frame=0, out=None, peak=None, clipped=None, stream=None):
@@ -474,54 +615,17 @@ def finish_device(x, dst_format, gain=None, dither=False, seed=0, first_frame=0,
     the frames done so far gets the bits of one call.  `out`, `peak` (float64 [nstreams, nch]) and `clipped` (int64
     [nstreams, nch]) are allocated (the statistics zeroed) when not passed; statistics that are passed are accumulated into.
     Returns (out, peak, clipped).  `stream` as in lpc_extrapolate_device: the call only enqueues."""
-    import torch
-    shape = tuple(x.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
-    dt = str(x.dtype)
-    if not (dt.endswith("float32") or dt.endswith("float64")):
-        raise TypeError("%s buffer: the output stage reads float32 or float64 frames" % (x.dtype,))
-    if not x.is_contiguous():
-        raise ValueError("the tensor must be contiguous")
+    shape, fmt, nstreams, frames, nch = _float_frames(x, "the output stage")
     if dst_format not in (None, RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
         raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32 or None)" % (dst_format,))
-    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
-    seed, first_frame = int(seed), int(first_frame)
-    if not (0 <= seed < 1 << 64 and 0 <= first_frame and first_frame + frames < 1 << 64):
-        raise ValueError("seed and first_frame + frames must fit 64 unsigned bits")
-    if not getattr(x, "is_cuda", False):
-        raise TypeError("the output stage works on device tensors: the frames must be in HBM")
-    dev = x.device
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((nstreams,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (nstreams,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (nstreams, dev))
-    if dst_format is None:
-        if out is not None:
-            raise ValueError("dst_format=None measures only: there is nothing to write into `out`")
-    else:
-        odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
-        oshape = shape[:-1] + (last,)
-        if out is None:
-            out = torch.empty(oshape, dtype=odt, device=dev)
-        elif out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
-            raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
-    stats = []
-    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
-        if t is None:
-            t = torch.zeros((nstreams, nch), dtype=sdt, device=dev)
-        elif t.dtype != sdt or tuple(t.shape) != (nstreams, nch) or t.device != dev or not t.is_contiguous():
-            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, nstreams, nch, dev))
-        stats.append(t)
-    peak, clipped = stats
+    seed, first_frame = _seed_and_first(seed, first_frame, frames)
+    dev = _on_device(x, "the output stage")
+    gain = _gain(gain, nstreams, dev)
+    out = _pcm_out(out, dst_format, shape[:-1], nch, dev)
+    peak, clipped = _finish_stats(peak, clipped, nstreams, nch, dev)
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_finish_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-                                   RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
-                                   dst_format or 0, C.c_void_p(out.data_ptr()) if out is not None else None, frames, nstreams, frames, nch,
-                                   C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed, first_frame,
-                                   C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_finish_device")
+    _check(lib().RRX_finish_device(*_where(dev, stream), fmt, x.data_ptr(), frames, dst_format or 0, _ptr(out), frames, nstreams, frames, nch,
+                                   _ptr(gain), 1 if dither else 0, seed, first_frame, peak.data_ptr(), clipped.data_ptr()), "RRX_finish_device")
     return out, peak, clipped
 
 
@@ -551,64 +655,25 @@ def finish_shaped_device(x, dst_format, shaping, segment=65536, gain=None, dithe
     ascending calls that hand it on leave the bytes and statistics of one call.  Returns (out, peak, clipped, state): `state` is a
     NEW tensor, never the one passed in (the call must not read and write one buffer).  The call only enqueues."""
     import torch
-    shape = tuple(x.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
-    dt = str(x.dtype)
-    if not (dt.endswith("float32") or dt.endswith("float64")):
-        raise TypeError("%s buffer: the output stage reads float32 or float64 frames" % (x.dtype,))
-    if not x.is_contiguous():
-        raise ValueError("the tensor must be contiguous")
-    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
-        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+    shape, fmt, nstreams, frames, nch = _float_frames(x, "the output stage")
+    _shaped_dst_format(dst_format)
     coefs, segment = _shaping(shaping, segment)
-    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
-    seed, first_frame = int(seed), int(first_frame)
-    if not (0 <= seed < 1 << 64 and 0 <= first_frame and first_frame + frames < 1 << 64):
-        raise ValueError("seed and first_frame + frames must fit 64 unsigned bits")
+    seed, first_frame = _seed_and_first(seed, first_frame, frames)
     if state is None and (first_frame % segment if segment else first_frame):
         raise ValueError("a call that begins inside a segment needs the state of the call before it")
-    if not getattr(x, "is_cuda", False):
-        raise TypeError("the output stage works on device tensors: the frames must be in HBM")
-    dev = x.device
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((nstreams,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (nstreams,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (nstreams, dev))
-    if state is not None:
-        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, RRX_SHAPE_MAX_ORDER) or state.device != dev or not state.is_contiguous():
-            raise TypeError("state must be a contiguous float64 tensor [%d, %d, %d] on %s" % (nstreams, nch, RRX_SHAPE_MAX_ORDER, dev))
-    if out is False:
-        out = None
-    else:
-        odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
-        oshape = shape[:-1] + (last,)
-        if out is None:
-            out = torch.empty(oshape, dtype=odt, device=dev)
-        elif out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
-            raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
-    stats = []
-    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
-        if t is None:
-            t = torch.zeros((nstreams, nch), dtype=sdt, device=dev)
-        elif t.dtype != sdt or tuple(t.shape) != (nstreams, nch) or t.device != dev or not t.is_contiguous():
-            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, nstreams, nch, dev))
-        stats.append(t)
-    peak, clipped = stats
+    dev = _on_device(x, "the output stage")
+    gain = _gain(gain, nstreams, dev)
+    _stream_state(state, nstreams, nch, RRX_SHAPE_MAX_ORDER, dev)
+    out = None if out is False else _pcm_out(out, dst_format, shape[:-1], nch, dev)
+    peak, clipped = _finish_stats(peak, clipped, nstreams, nch, dev)
     # frames == 0 touches nothing, the state included: the state handed on is then the one that came in
     new_state = torch.zeros((nstreams, nch, RRX_SHAPE_MAX_ORDER), dtype=torch.float64, device=dev) if state is None or frames else state.clone()
     if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out, peak, clipped, new_state
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_finish_shaped_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-                                          RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
-                                          dst_format, C.c_void_p(out.data_ptr()) if out is not None else None, frames, nstreams, frames, nch,
-                                          C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed, first_frame,
-                                          C.cast(coefs, C.c_void_p), len(coefs), segment,
-                                          C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(new_state.data_ptr()),
-                                          C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_finish_shaped_device")
+    _check(lib().RRX_finish_shaped_device(*_where(dev, stream), fmt, x.data_ptr(), frames, dst_format, _ptr(out), frames, nstreams, frames, nch,
+                                          _ptr(gain), 1 if dither else 0, seed, first_frame, C.cast(coefs, C.c_void_p), len(coefs), segment,
+                                          _ptr(state), new_state.data_ptr(), peak.data_ptr(), clipped.data_ptr()), "RRX_finish_shaped_device")
     return out, peak, clipped, new_state
 
 
@@ -624,19 +689,6 @@ def _true_peak_filter(filter):
     return phases, taps, (C.c_double * len(coefs))(*coefs)
 
 
-def _true_peak_stats(true_peak, peak, n, nch, dev):
-    """the two result tensors of a true-peak call: float64 [n, nch], allocated (zeroed) when not passed"""
-    import torch
-    stats = []
-    for t, name in ((true_peak, "true_peak"), (peak, "peak")):
-        if t is None:
-            t = torch.zeros((n, nch), dtype=torch.float64, device=dev)
-        elif t.dtype != torch.float64 or tuple(t.shape) != (n, nch) or t.device != dev or not t.is_contiguous():
-            raise TypeError("%s must be a contiguous float64 tensor [%d, %d] on %s" % (name, n, nch, dev))
-        stats.append(t)
-    return stats
-
-
 def true_peak_device(x, gain=None, first_frame=0, filter="bs1770", flush=True, state=None, true_peak=None, peak=None, stream=None):
     """True peak and sample peak on the device (RRX_true_peak_device): per (stream, channel), the peak of the gained frames
     oversampled by the polyphase `filter` -- a name of TRUE_PEAK_FILTERS ("bs1770": 4x, ITU-R BS.1770-4 Annex 2) or (phases, taps,
@@ -650,32 +702,14 @@ def true_peak_device(x, gain=None, first_frame=0, filter="bs1770", flush=True, s
     otherwise.  Returns (true_peak, peak, state_out): `state_out` is a NEW tensor, never the one passed in.  The call only
     enqueues."""
     import torch
-    shape = tuple(x.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
-    dt = str(x.dtype)
-    if not (dt.endswith("float32") or dt.endswith("float64")):
-        raise TypeError("%s buffer: the true-peak pass reads float32 or float64 frames" % (x.dtype,))
-    if not x.is_contiguous():
-        raise ValueError("the tensor must be contiguous")
+    _, fmt, nstreams, frames, nch = _float_frames(x, "the true-peak pass")
     phases, taps, coefs = _true_peak_filter(filter)
-    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
-    first_frame = int(first_frame)
-    if not (0 <= first_frame and first_frame + frames < 1 << 64):
-        raise ValueError("first_frame + frames must fit 64 unsigned bits")
+    first_frame = _first_frame(first_frame, frames)
     if state is None and first_frame:
         raise ValueError("a call that does not begin the stream needs the state of the call before it")
-    if not getattr(x, "is_cuda", False):
-        raise TypeError("the true-peak pass works on device tensors: the frames must be in HBM")
-    dev = x.device
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((nstreams,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (nstreams,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (nstreams, dev))
-    if state is not None:
-        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, RRX_TP_MAX_TAPS) or state.device != dev or not state.is_contiguous():
-            raise TypeError("state must be a contiguous float64 tensor [%d, %d, %d] on %s" % (nstreams, nch, RRX_TP_MAX_TAPS, dev))
+    dev = _on_device(x, "the true-peak pass")
+    gain = _gain(gain, nstreams, dev)
+    _stream_state(state, nstreams, nch, RRX_TP_MAX_TAPS, dev)
     true_peak, peak = _true_peak_stats(true_peak, peak, nstreams, nch, dev)
     # frames == 0 touches nothing, the state included: the state handed on is then the one that came in
     if frames or state is None or not first_frame:
@@ -685,13 +719,9 @@ def true_peak_device(x, gain=None, first_frame=0, filter="bs1770", flush=True, s
     if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return true_peak, peak, new_state
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_true_peak_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-                                      RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames, nstreams,
-                                      frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, first_frame,
-                                      C.cast(coefs, C.c_void_p), phases, taps, 1 if flush else 0,
-                                      C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(new_state.data_ptr()),
-                                      C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())), "RRX_true_peak_device")
+    _check(lib().RRX_true_peak_device(*_where(dev, stream), fmt, x.data_ptr(), frames, nstreams, frames, nch, _ptr(gain), first_frame,
+                                      C.cast(coefs, C.c_void_p), phases, taps, 1 if flush else 0, _ptr(state), new_state.data_ptr(),
+                                      true_peak.data_ptr(), peak.data_ptr()), "RRX_true_peak_device")
     return true_peak, peak, new_state
 
 
@@ -860,13 +890,19 @@ class _Scratch:
         return f[:n].view(shape)
 
 
-def _tracks_table(table, ntracks=None):
-    """the device copy of a plan's table: a contiguous int64 tensor [ntracks, 6]"""
+def _tracks_table(table, ntracks=None, dev=None):
+    """the device copy of a plan's table: a contiguous int64 tensor [ntracks, 6], with `dev` on that device"""
     if str(table.dtype) != "torch.int64" or table.dim() != 2 or table.shape[1] != 6 or not table.is_cuda or not table.is_contiguous():
         raise TypeError("the table must be a contiguous int64 device tensor [ntracks, 6] (TracksPlan.to_device)")
     if ntracks is not None and table.shape[0] != ntracks:
         raise ValueError("the table has %d entries for %d rows" % (table.shape[0], ntracks))
+    if dev is not None and table.device != dev:
+        raise _table_elsewhere(dev)
     return table.shape[0]
+
+
+def _table_elsewhere(dev):
+    return TypeError("the table must be on %s" % (dev,))
 
 
 def _tracks_src_format(dtype):
@@ -886,7 +922,7 @@ def _tracks_stage_source(packed, table):
             raise ValueError("a uint8 source is packed 24-bit PCM [frames, nch * 3]; its last dimension is %d" % nch)
         nch //= 3
     if table.device != packed.device:
-        raise TypeError("the table must be on %s" % (packed.device,))
+        raise _table_elsewhere(packed.device)
     return fmt, ntracks, nch, src_total
 
 
@@ -919,18 +955,19 @@ def tracks_stage_device(packed, table, in_rate, out_rate, row_frames, out=None, 
     fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
     out = _tracks_stage_out(out, (ntracks, int(row_frames), nch), packed.device)
     packed = _tracks_stage_pointer(packed)
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    index = packed.device.index
-    _check(lib().RRX_tracks_stage_device_samples(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
-                                                 C.c_void_p(table.data_ptr()), ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total,
-                                                 C.c_void_p(out.data_ptr()), int(row_frames)), "RRX_tracks_stage_device_samples")
+    _check(lib().RRX_tracks_stage_device_samples(*_where(packed.device, stream), int(in_rate), int(out_rate),
+                                                 table.data_ptr(), ntracks, nch, fmt, packed.data_ptr(), src_total,
+                                                 _ptr(out), int(row_frames)), "RRX_tracks_stage_device_samples")
     return out
 
 
-def _tracks_window(row_frames, win_first, win_frames):
+def _tracks_window(row_frames, win_first, win_frames, win_stride=None):
+    """the window of a window call, checked; `win_stride`: it lies in a tensor of that many frames a row"""
     row_frames, win_first, win_frames = int(row_frames), int(win_first), int(win_frames)
     if win_first < 0 or win_frames < 0 or win_first + win_frames > row_frames:
         raise ValueError("the window [%d, %d) does not lie inside rows of %d frames" % (win_first, win_first + win_frames, row_frames))
+    if win_stride is not None and win_frames > win_stride:
+        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
     return row_frames, win_first, win_frames
 
 
@@ -948,11 +985,9 @@ def tracks_stage_window_device(packed, table, in_rate, out_rate, row_frames, win
     packed = _tracks_stage_pointer(packed)
     if not win_frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    index = packed.device.index
-    _check(lib().RRX_tracks_stage_window_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
-                                                C.c_void_p(table.data_ptr()), ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total,
-                                                row_frames, win_first, win_frames, C.c_void_p(out.data_ptr()), out.shape[1]),
+    _check(lib().RRX_tracks_stage_window_device(*_where(packed.device, stream), int(in_rate), int(out_rate),
+                                                table.data_ptr(), ntracks, nch, fmt, packed.data_ptr(), src_total,
+                                                row_frames, win_first, win_frames, _ptr(out), out.shape[1]),
            "RRX_tracks_stage_window_device")
     return out
 
@@ -995,14 +1030,11 @@ def mix_device(rows, matrix, out=None, stream=None, frames=None):
     not passed).  `frames` (default: all): only frames [0, frames) of every row are mixed, and nothing else of `out` is written.
     Returns `out`.  `stream` as in lpc_extrapolate_device: the call only enqueues."""
     import torch
-    shape = tuple(rows.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
+    shape, nstreams, stride, nch_src = _frames_shape(rows)
     if rows.dtype not in (torch.float32, torch.float64):
         raise TypeError("%s buffer: mix_device reads float32 or float64 frames" % (rows.dtype,))
     if not getattr(rows, "is_cuda", False) or not rows.is_contiguous():
         raise TypeError("mix_device works on contiguous device tensors")
-    nstreams, stride, nch_src = (1,) + shape if len(shape) == 2 else shape
     m = _mix_checked(matrix, nch_src=nch_src)
     nch_dst = m.shape[0]
     frames = stride if frames is None else int(frames)
@@ -1017,10 +1049,8 @@ def mix_device(rows, matrix, out=None, stream=None, frames=None):
     if not frames or not nstreams:
         return out
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_mix_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-                                RRX_FMT_DOUBLE if rows.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), stride, nstreams,
-                                frames, nch_src, C.c_void_p(out.data_ptr()), out.shape[-2], nch_dst, m.ctypes.data), "RRX_mix_device")
+    _check(lib().RRX_mix_device(*_where(dev, stream), _float_fmt(rows.dtype), rows.data_ptr(), stride, nstreams, frames, nch_src, _ptr(out),
+                                out.shape[-2], nch_dst, m.ctypes.data), "RRX_mix_device")
     return out
 
 
@@ -1034,11 +1064,9 @@ def tracks_stage_mix_device(packed, table, matrix, in_rate, out_rate, row_frames
     m = _mix_checked(matrix, nch_src=nch_src)
     out = _tracks_stage_out(out, (ntracks, int(row_frames), m.shape[0]), packed.device)
     packed = _tracks_stage_pointer(packed)
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    index = packed.device.index
-    _check(lib().RRX_tracks_stage_mix_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
-                                             C.c_void_p(table.data_ptr()), ntracks, fmt, nch_src, C.c_void_p(packed.data_ptr()), src_total,
-                                             m.shape[0], m.ctypes.data, C.c_void_p(out.data_ptr()), int(row_frames)),
+    _check(lib().RRX_tracks_stage_mix_device(*_where(packed.device, stream), int(in_rate), int(out_rate),
+                                             table.data_ptr(), ntracks, fmt, nch_src, packed.data_ptr(), src_total,
+                                             m.shape[0], m.ctypes.data, _ptr(out), int(row_frames)),
            "RRX_tracks_stage_mix_device")
     return out
 
@@ -1056,12 +1084,10 @@ def tracks_stage_mix_window_device(packed, table, matrix, in_rate, out_rate, row
     packed = _tracks_stage_pointer(packed)
     if not win_frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    index = packed.device.index
-    _check(lib().RRX_tracks_stage_mix_window_device(-1 if index is None else int(index), C.c_void_p(ptr), int(in_rate), int(out_rate),
-                                                    C.c_void_p(table.data_ptr()), ntracks, fmt, nch_src, C.c_void_p(packed.data_ptr()),
+    _check(lib().RRX_tracks_stage_mix_window_device(*_where(packed.device, stream), int(in_rate), int(out_rate),
+                                                    table.data_ptr(), ntracks, fmt, nch_src, packed.data_ptr(),
                                                     src_total, nch, m.ctypes.data, row_frames, win_first, win_frames,
-                                                    C.c_void_p(out.data_ptr()), out.shape[1]), "RRX_tracks_stage_mix_window_device")
+                                                    _ptr(out), out.shape[1]), "RRX_tracks_stage_mix_window_device")
     return out
 
 
@@ -1074,19 +1100,13 @@ def tracks_finish_device(rows, table, dst_format, dst_total, gain=None, dither=F
     [dst_total, nch * 3] for RRX_FMT_S24_3; `dst_format` None measures only.  `gain`: None, a float, or a float64 device tensor
     [ntracks].  `peak` (float64 [ntracks, nch]) and `clipped` (int64 [ntracks, nch]) cover each track's own frames only; they
     are allocated (zeroed) when not passed and accumulated into otherwise.  Returns (out, peak, clipped).  The call only enqueues."""
-    dt = str(rows.dtype)
-    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
-        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
-    ntracks, row_frames, nch = rows.shape
+    fmt, ntracks, row_frames, nch = _tracks_frames(rows, "rows", "row_frames")
     seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(rows, table, dst_format, dst_total, gain, seed, out, peak, clipped)
     dev = rows.device
-    ptr = getattr(stream, "cuda_stream", stream) or 0
     write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
-    _check(lib().RRX_tracks_finish_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
-                                          RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()), row_frames,
-                                          dst_format or 0, C.c_void_p(out.data_ptr()) if write else None, dst_total,
-                                          C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
-                                          C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_device")
+    _check(lib().RRX_tracks_finish_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, rows.data_ptr(), row_frames, dst_format or 0,
+                                          out.data_ptr() if write else None, dst_total, _ptr(gain), 1 if dither else 0, seed, peak.data_ptr(),
+                                          clipped.data_ptr()), "RRX_tracks_finish_device")
     return out, peak, clipped
 
 
@@ -1097,31 +1117,18 @@ def tracks_true_peak_device(rows, table, gain=None, filter="bs1770", true_peak=N
     last -- under `gain` (None, a float, or a float64 device tensor [ntracks]).  `filter` is true_peak_device's.  `true_peak` and
     `peak` (float64 [ntracks, nch]) are allocated (zeroed) when not passed and accumulated into otherwise.  Returns (true_peak,
     peak).  The call only enqueues."""
-    import torch
-    dt = str(rows.dtype)
-    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
-        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
-    ntracks, row_frames, nch = rows.shape
-    _tracks_table(table, ntracks)
+    fmt, ntracks, row_frames, nch = _tracks_frames(rows, "rows", "row_frames")
     dev = rows.device
-    if table.device != dev:
-        raise TypeError("the table must be on %s" % (dev,))
+    _tracks_table(table, ntracks, dev)
     phases, taps, coefs = _true_peak_filter(filter)
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((ntracks,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (ntracks,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (ntracks, dev))
+    gain = _gain(gain, ntracks, dev)
     true_peak, peak = _true_peak_stats(true_peak, peak, ntracks, nch, dev)
     if not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return true_peak, peak
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_true_peak_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
-                                             nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
-                                             row_frames, C.c_void_p(gain.data_ptr()) if gain is not None else None,
-                                             C.cast(coefs, C.c_void_p), phases, taps,
-                                             C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())), "RRX_tracks_true_peak_device")
+    _check(lib().RRX_tracks_true_peak_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, rows.data_ptr(), row_frames, _ptr(gain),
+                                             C.cast(coefs, C.c_void_p), phases, taps, true_peak.data_ptr(), peak.data_ptr()),
+           "RRX_tracks_true_peak_device")
     return true_peak, peak
 
 
@@ -1152,21 +1159,19 @@ def tracks_true_peak_packed_device(packed, table, gain=None, filter="bs1770", ma
     is exact -- s * 2^-15 / 2^-23 / 2^-31 in float64, so INT32_MAX peaks at 1 - 2^-31 -- and from there on every track is
     true_peak_device's one whole stream, flushed.  `gain`, `filter`, `true_peak`, `peak` and the return value are
     tracks_true_peak_device's.  The call only enqueues."""
-    import torch
     table, max_frames = _packed_table(table, max_frames, packed.device if hasattr(packed, "device") else None)
     fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
     dev = packed.device
     phases, taps, coefs = _true_peak_filter(filter)
-    gain = _loudness_gain(gain, ntracks, dev)
+    gain = _gain(gain, ntracks, dev)
     true_peak, peak = _true_peak_stats(true_peak, peak, ntracks, nch, dev)
     if not max_frames or not src_total:  # (an empty tensor has no pointer, and there is nothing to do)
         return true_peak, peak
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_true_peak_packed_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
-                                                    ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total, max_frames,
-                                                    C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(coefs, C.c_void_p),
-                                                    phases, taps, C.c_void_p(true_peak.data_ptr()), C.c_void_p(peak.data_ptr())),
+    _check(lib().RRX_tracks_true_peak_packed_device(*_where(dev, stream), table.data_ptr(),
+                                                    ntracks, nch, fmt, packed.data_ptr(), src_total, max_frames,
+                                                    _ptr(gain), C.cast(coefs, C.c_void_p),
+                                                    phases, taps, true_peak.data_ptr(), peak.data_ptr()),
            "RRX_tracks_true_peak_packed_device")
     return true_peak, peak
 
@@ -1227,33 +1232,18 @@ def limit_device(x, ceiling, gain=None, lookahead=64, hold=0, filter="bs1770", o
 
 def _limit_device(x, ceiling, gain, lookahead, hold, filter, out, stream, release):
     """limit_device (release = None) and limit_release_device (release = (pole, block), checked)"""
-    import torch
-    shape = tuple(x.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
-    dt = str(x.dtype)
-    if not (dt.endswith("float32") or dt.endswith("float64")):
-        raise TypeError("%s buffer: the limiter reads float32 or float64 frames" % (x.dtype,))
-    if not x.is_contiguous():
-        raise ValueError("the tensor must be contiguous")
+    _, fmt, nstreams, frames, nch = _float_frames(x, "the limiter")
     phases, taps, coefs = _true_peak_filter(filter)
     ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
-    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
-    if not getattr(x, "is_cuda", False):
-        raise TypeError("the limiter works on device tensors: the frames must be in HBM")
-    dev = x.device
-    gain = _loudness_gain(gain, nstreams, dev)
+    dev = _on_device(x, "the limiter")
+    gain = _gain(gain, nstreams, dev)
     out, reduction, limited, work = _limit_buffers(x, out, nstreams, frames, taps, lookahead, dev, None if release is None else release[1])
     if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out, reduction, limited
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    head = (-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-            RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames,
-            RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), frames,
-            nstreams, frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling,
+    head = (*_where(dev, stream), fmt, x.data_ptr(), frames, _float_fmt(out.dtype), _ptr(out), frames, nstreams, frames, nch, _ptr(gain), ceiling,
             C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold)
-    tail = (C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+    tail = (reduction.data_ptr(), limited.data_ptr(), work.data_ptr(), work.numel())
     if release is None:
         _check(lib().RRX_limit_device(*(head + tail)), "RRX_limit_device")
     else:
@@ -1272,29 +1262,20 @@ def tracks_limit_device(rows, table, ceiling, gain=None, lookahead=64, hold=0, f
 
 def _tracks_limit_device(rows, table, ceiling, gain, lookahead, hold, filter, out, stream, release):
     """tracks_limit_device (release = None) and tracks_limit_release_device (release = (pole, block), checked)"""
-    import torch
-    dt = str(rows.dtype)
-    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
-        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
-    ntracks, row_frames, nch = rows.shape
-    _tracks_table(table, ntracks)
+    fmt, ntracks, row_frames, nch = _tracks_frames(rows, "rows", "row_frames")
     dev = rows.device
-    if table.device != dev:
-        raise TypeError("the table must be on %s" % (dev,))
+    _tracks_table(table, ntracks, dev)
     phases, taps, coefs = _true_peak_filter(filter)
     ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
-    gain = _loudness_gain(gain, ntracks, dev)
+    gain = _gain(gain, ntracks, dev)
     out, reduction, limited, work = _limit_buffers(rows, rows if out is None else out, ntracks, row_frames, taps, lookahead, dev,
                                                    None if release is None else release[1])
     if not row_frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out, reduction, limited
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    head = (-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
-            RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
-            RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()), row_frames,
-            C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold)
-    tail = (C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+    head = (*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, rows.data_ptr(), _float_fmt(out.dtype), _ptr(out), row_frames, _ptr(gain),
+            ceiling, C.cast(coefs, C.c_void_p), phases, taps, lookahead, hold)
+    tail = (reduction.data_ptr(), limited.data_ptr(), work.data_ptr(), work.numel())
     if release is None:
         _check(lib().RRX_tracks_limit_device(*(head + tail)), "RRX_tracks_limit_device")
     else:
@@ -1389,18 +1370,13 @@ def _tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, wi
     """tracks_limit_window_device (release = None) and tracks_limit_release_window_device (release = (pole, block), checked):
     (out, reduction, limited, state_out)"""
     import torch
-    dt = str(buf.dtype)
-    if buf.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not buf.is_cuda or not buf.is_contiguous():
-        raise TypeError("buf must be a contiguous float32 or float64 device tensor [ntracks, buf_frames, nch]")
-    ntracks, buf_stride, nch = buf.shape
+    fmt, ntracks, buf_stride, nch = _tracks_frames(buf, "buf", "buf_frames")
     row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
     buf_first, buf_frames = int(buf_first), buf_stride if buf_frames is None else int(buf_frames)
     if not 0 <= buf_frames <= buf_stride:
         raise ValueError("%d buffered frames in a tensor of %d frames a row" % (buf_frames, buf_stride))
-    _tracks_table(table, ntracks)
     dev = buf.device
-    if table.device != dev:
-        raise TypeError("the table must be on %s" % (dev,))
+    _tracks_table(table, ntracks, dev)
     phases, taps, coefs = _true_peak_filter(filter)
     ceiling, lookahead, hold = _limit_params(ceiling, lookahead, hold)
     back, ahead = limit_window_reach(lookahead, hold, filter)
@@ -1409,7 +1385,7 @@ def _tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, wi
     if buf_first > max(0, win_first - back) or buf_first + buf_frames < min(row_frames, win_first + win_frames + ahead):
         raise ValueError("the buffer [%d, %d) does not cover the window [%d, %d) with its halo of %d frames behind and %d ahead"
                          % (buf_first, buf_first + buf_frames, win_first, win_first + win_frames, back, ahead))
-    gain = _loudness_gain(gain, ntracks, dev)
+    gain = _gain(gain, ntracks, dev)
     if out is None:
         out = torch.empty((ntracks, win_frames, nch), dtype=buf.dtype, device=dev)
     else:
@@ -1451,17 +1427,14 @@ def _tracks_limit_window_device(buf, table, row_frames, buf_first, win_first, wi
         raise ValueError("the window is too large for the limiter's work buffer")
     work = torch.empty((need,), dtype=torch.float64, device=dev)
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    head = (-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks, nch,
-            RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(buf.data_ptr()), buf_stride, buf_first, buf_frames,
-            row_frames, win_first, win_frames, RRX_FMT_DOUBLE if out.dtype == torch.float64 else RRX_FMT_FLOAT, C.c_void_p(out.data_ptr()),
-            out.shape[1], C.c_void_p(gain.data_ptr()) if gain is not None else None, ceiling, C.cast(coefs, C.c_void_p), phases, taps,
+    head = (*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, buf.data_ptr(), buf_stride, buf_first, buf_frames, row_frames, win_first,
+            win_frames, _float_fmt(out.dtype), _ptr(out), out.shape[1], _ptr(gain), ceiling, C.cast(coefs, C.c_void_p), phases, taps,
             lookahead, hold)
-    tail = (C.c_void_p(reduction.data_ptr()), C.c_void_p(limited.data_ptr()), C.c_void_p(work.data_ptr()), work.numel())
+    tail = (reduction.data_ptr(), limited.data_ptr(), work.data_ptr(), work.numel())
     if release is None:
         _check(lib().RRX_tracks_limit_window_device(*(head + tail)), "RRX_tracks_limit_window_device")
     else:
-        states = (C.c_void_p(state_in.data_ptr()) if state_in is not None else None, C.c_void_p(state_out.data_ptr()))
+        states = (_ptr(state_in), _ptr(state_out))
         _check(lib().RRX_tracks_limit_release_window_device(*(head + release + states + tail)), "RRX_tracks_limit_release_window_device")
     return out, reduction, limited, state_out
 
@@ -1536,16 +1509,6 @@ def _loudness_filter(rate, coefs, hop):
     return (C.c_double * 10)(*coefs), hop
 
 
-def _loudness_gain(gain, n, dev):
-    import torch
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((n,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (n,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (n, dev))
-    return gain
-
-
 def _loudness_buffers(energy, work, n, nch, need_hops, need_work, dev):
     """the energy tensor (float64 [n, nch, >= need_hops], allocated zeroed when not passed) and the work buffer"""
     import torch
@@ -1574,30 +1537,16 @@ def loudness_device(x, rate=None, gain=None, first_frame=0, state=None, energy=N
     not passed.  Returns (energy, state_out): `state_out` is a NEW tensor.  Feed `energy` to loudness_gate_device.  The call only
     enqueues."""
     import torch
-    shape = tuple(x.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("expected a [frames, nch] or [nstreams, frames, nch] tensor, got shape %r" % (shape,))
-    dt = str(x.dtype)
-    if not (dt.endswith("float32") or dt.endswith("float64")):
-        raise TypeError("%s buffer: the loudness pass reads float32 or float64 frames" % (x.dtype,))
-    if not x.is_contiguous():
-        raise ValueError("the tensor must be contiguous")
+    _, fmt, nstreams, frames, nch = _float_frames(x, "the loudness pass")
     c, hop = _loudness_filter(rate, coefs, hop)
-    nstreams, frames, nch = (1,) + shape if len(shape) == 2 else shape
-    first_frame = int(first_frame)
-    if not (0 <= first_frame and first_frame + frames < 1 << 64):
-        raise ValueError("first_frame + frames must fit 64 unsigned bits")
+    first_frame = _first_frame(first_frame, frames)
     if first_frame % hop:
         raise ValueError("first_frame must be a multiple of the hop (%d)" % hop)
     if state is None and first_frame:
         raise ValueError("a call that does not begin the stream needs the state of the call before it")
-    if not getattr(x, "is_cuda", False):
-        raise TypeError("the loudness pass works on device tensors: the frames must be in HBM")
-    dev = x.device
-    gain = _loudness_gain(gain, nstreams, dev)
-    if state is not None:
-        if state.dtype != torch.float64 or tuple(state.shape) != (nstreams, nch, 4) or state.device != dev or not state.is_contiguous():
-            raise TypeError("state must be a contiguous float64 tensor [%d, %d, 4] on %s" % (nstreams, nch, dev))
+    dev = _on_device(x, "the loudness pass")
+    gain = _gain(gain, nstreams, dev)
+    _stream_state(state, nstreams, nch, 4, dev)
     first_hop, n = first_frame // hop, frames // hop
     need = nstreams * nch * n * 4
     energy, work = _loudness_buffers(energy, work, nstreams, nch, first_hop + n, need, dev)
@@ -1609,13 +1558,9 @@ def loudness_device(x, rate=None, gain=None, first_frame=0, state=None, energy=N
     if not frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return energy, new_state
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_loudness_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr),
-                                     RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(x.data_ptr()), frames, nstreams,
-                                     frames, nch, C.c_void_p(gain.data_ptr()) if gain is not None else None, first_frame,
-                                     C.cast(c, C.c_void_p), hop, C.c_void_p(state.data_ptr()) if state is not None else None,
-                                     C.c_void_p(new_state.data_ptr()), C.c_void_p(energy.data_ptr()), energy.shape[2],
-                                     C.c_void_p(work.data_ptr()), work.numel()), "RRX_loudness_device")
+    _check(lib().RRX_loudness_device(*_where(dev, stream), fmt, x.data_ptr(), frames, nstreams, frames, nch, _ptr(gain), first_frame,
+                                     C.cast(c, C.c_void_p), hop, _ptr(state), new_state.data_ptr(), energy.data_ptr(), energy.shape[2], work.data_ptr(),
+                                     work.numel()), "RRX_loudness_device")
     return energy, new_state
 
 
@@ -1628,28 +1573,19 @@ def tracks_loudness_device(rows, table, rate=None, gain=None, coefs=None, hop=No
     every track.  Feed both to loudness_gate_device.  The call only
     enqueues."""
     import torch
-    dt = str(rows.dtype)
-    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
-        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
-    ntracks, row_frames, nch = rows.shape
-    _tracks_table(table, ntracks)
+    fmt, ntracks, row_frames, nch = _tracks_frames(rows, "rows", "row_frames")
     dev = rows.device
-    if table.device != dev:
-        raise TypeError("the table must be on %s" % (dev,))
+    _tracks_table(table, ntracks, dev)
     c, hop = _loudness_filter(rate, coefs, hop)
-    gain = _loudness_gain(gain, ntracks, dev)
+    gain = _gain(gain, ntracks, dev)
     n = row_frames // hop
     energy, work = _loudness_buffers(energy, work, ntracks, nch, n if energy is None else 0, ntracks * nch * n * 4, dev)
     hops = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
     if not n or not energy.shape[2]:  # (no row holds a whole hop: an empty tensor has no pointer, and there is nothing to do)
         return energy, hops
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_loudness_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
-                                            nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
-                                            row_frames, C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(c, C.c_void_p), hop,
-                                            C.c_void_p(energy.data_ptr()), energy.shape[2],
-                                            C.c_void_p(hops.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+    _check(lib().RRX_tracks_loudness_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, rows.data_ptr(), row_frames, _ptr(gain),
+                                            C.cast(c, C.c_void_p), hop, energy.data_ptr(), energy.shape[2], _ptr(hops), work.data_ptr(), work.numel()),
            "RRX_tracks_loudness_device")
     return energy, hops
 
@@ -1665,19 +1601,16 @@ def tracks_loudness_packed_device(packed, table, rate=None, gain=None, coefs=Non
     fmt, ntracks, nch, src_total = _tracks_stage_source(packed, table)
     dev = packed.device
     c, hop = _loudness_filter(rate, coefs, hop)
-    gain = _loudness_gain(gain, ntracks, dev)
+    gain = _gain(gain, ntracks, dev)
     n = max_frames // hop
     energy, work = _loudness_buffers(energy, work, ntracks, nch, n if energy is None else 0, ntracks * nch * n * 4, dev)
     hops = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
     if not n or not energy.shape[2] or not src_total:  # (no track holds a whole hop: an empty tensor has no pointer, and there is nothing to do)
         return energy, hops
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_loudness_packed_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
-                                                   ntracks, nch, fmt, C.c_void_p(packed.data_ptr()), src_total, max_frames,
-                                                   C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(c, C.c_void_p), hop,
-                                                   C.c_void_p(energy.data_ptr()), energy.shape[2], C.c_void_p(hops.data_ptr()),
-                                                   C.c_void_p(work.data_ptr()), work.numel()), "RRX_tracks_loudness_packed_device")
+    _check(lib().RRX_tracks_loudness_packed_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, packed.data_ptr(), src_total, max_frames,
+                                                   _ptr(gain), C.cast(c, C.c_void_p), hop, energy.data_ptr(), energy.shape[2], _ptr(hops),
+                                                   work.data_ptr(), work.numel()), "RRX_tracks_loudness_packed_device")
     return energy, hops
 
 
@@ -1712,11 +1645,10 @@ def loudness_gate_device(energy, hop, hops=None, abs_lufs=-70.0, rel_lu=-10.0, w
         return result
     abs_threshold, rel_factor = loudness_gate(abs_lufs, rel_lu)
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_loudness_gate_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(energy.data_ptr()), nhops,
-                                          nstreams, nch, nhops, C.c_void_p(hops.data_ptr()) if hops is not None else None,
-                                          C.c_void_p(weights.data_ptr()) if weights is not None else None, hop, abs_threshold, rel_factor,
-                                          C.c_void_p(result.data_ptr())), "RRX_loudness_gate_device")
+    _check(lib().RRX_loudness_gate_device(*_where(dev, stream), energy.data_ptr(), nhops,
+                                          nstreams, nch, nhops, _ptr(hops),
+                                          _ptr(weights), hop, abs_threshold, rel_factor,
+                                          result.data_ptr()), "RRX_loudness_gate_device")
     return result
 
 
@@ -1768,12 +1700,11 @@ def _loudness_blocks(energy, hop, block_hops, step_hops, hops, weights, stream, 
     if not nstreams or not nch or not most:  # (no block anywhere: an empty tensor has no pointer, and there is nothing to do)
         return blocks, nblocks, peak
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_loudness_blocks_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(energy.data_ptr()), nhops,
-                                            nstreams, nch, nhops, C.c_void_p(hops.data_ptr()) if hops is not None else None,
-                                            C.c_void_p(weights.data_ptr()) if weights is not None else None, hop, L, P,
-                                            C.c_void_p(blocks.data_ptr()) if want_blocks else None, blocks.shape[1] if want_blocks else 0,
-                                            C.c_void_p(nblocks.data_ptr()) if want_blocks else None, C.c_void_p(peak.data_ptr())),
+    _check(lib().RRX_loudness_blocks_device(*_where(dev, stream), energy.data_ptr(), nhops,
+                                            nstreams, nch, nhops, _ptr(hops),
+                                            _ptr(weights), hop, L, P,
+                                            _ptr(blocks) if want_blocks else None, blocks.shape[1] if want_blocks else 0,
+                                            _ptr(nblocks) if want_blocks else None, peak.data_ptr()),
            "RRX_loudness_blocks_device")
     return blocks, nblocks, peak
 
@@ -1829,10 +1760,9 @@ def loudness_gate_groups_device(blocks, nblocks, groups, ngroups, abs_lufs=-70.0
     abs_threshold, rel_factor = loudness_gate(abs_lufs, rel_lu)
     work = torch.empty((2 * nstreams + ngroups,), dtype=torch.float64, device=dev)
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_loudness_gate_groups_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(blocks.data_ptr()),
-                                                 stride, nstreams, C.c_void_p(nblocks.data_ptr()), C.c_void_p(groups.data_ptr()), ngroups,
-                                                 abs_threshold, rel_factor, C.c_void_p(result.data_ptr()), C.c_void_p(work.data_ptr()),
+    _check(lib().RRX_loudness_gate_groups_device(*_where(dev, stream), _ptr(blocks),
+                                                 stride, nstreams, _ptr(nblocks), groups.data_ptr(), ngroups,
+                                                 abs_threshold, rel_factor, result.data_ptr(), work.data_ptr(),
                                                  work.numel()), "RRX_loudness_gate_groups_device")
     return result
 
@@ -1855,11 +1785,10 @@ def loudness_range_device(blocks, nblocks, groups=None, ngroups=None, abs_lufs=-
     abs_threshold, rel_factor = loudness_gate(abs_lufs, rel_lu)
     work = torch.empty((2 * nstreams + ngroups,), dtype=torch.float64, device=dev)
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_loudness_range_groups_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(blocks.data_ptr()),
-                                                  stride, nstreams, C.c_void_p(nblocks.data_ptr()), C.c_void_p(groups.data_ptr()), ngroups,
-                                                  abs_threshold, rel_factor, low, high, C.c_void_p(result.data_ptr()),
-                                                  C.c_void_p(work.data_ptr()), work.numel()), "RRX_loudness_range_groups_device")
+    _check(lib().RRX_loudness_range_groups_device(*_where(dev, stream), _ptr(blocks),
+                                                  stride, nstreams, _ptr(nblocks), groups.data_ptr(), ngroups,
+                                                  abs_threshold, rel_factor, low, high, result.data_ptr(),
+                                                  work.data_ptr(), work.numel()), "RRX_loudness_range_groups_device")
     return result
 
 
@@ -1948,67 +1877,45 @@ def tracks_finish_shaped_device(rows, table, dst_format, dst_total, shaping, seg
     (by windows, with a state per track: tracks_finish_shaped_window_device).
     `shaping` and `segment` are finish_shaped_device's, everything else tracks_finish_device's, except that `dst_format` is never
     None (`out=False` measures only).  Returns (out, peak, clipped).  The call only enqueues."""
-    dt = str(rows.dtype)
-    if rows.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not rows.is_cuda or not rows.is_contiguous():
-        raise TypeError("rows must be a contiguous float32 or float64 device tensor [ntracks, row_frames, nch]")
-    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
-        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+    fmt, ntracks, row_frames, nch = _tracks_frames(rows, "rows", "row_frames")
+    _shaped_dst_format(dst_format)
     coefs, segment = _shaping(shaping, segment)
-    ntracks, row_frames, nch = rows.shape
     measure = out is False
     seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(rows, table, None if measure else dst_format, dst_total, gain, seed,
                                                                        None if measure else out, peak, clipped)
-    dev = rows.device
-    ptr = getattr(stream, "cuda_stream", stream) or 0
     write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
-    _check(lib().RRX_tracks_finish_shaped_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
-                                                 nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(rows.data_ptr()),
-                                                 row_frames, dst_format, C.c_void_p(out.data_ptr()) if write else None, dst_total,
-                                                 C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
-                                                 C.cast(coefs, C.c_void_p), len(coefs), segment,
-                                                 C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_shaped_device")
+    _check(lib().RRX_tracks_finish_shaped_device(*_where(rows.device, stream), table.data_ptr(), ntracks, nch, fmt, rows.data_ptr(), row_frames, dst_format,
+                                                 out.data_ptr() if write else None, dst_total, _ptr(gain), 1 if dither else 0, seed,
+                                                 C.cast(coefs, C.c_void_p), len(coefs), segment, peak.data_ptr(), clipped.data_ptr()),
+           "RRX_tracks_finish_shaped_device")
     return out, peak, clipped
 
 
 def _tracks_finish_buffers(rows, table, dst_format, dst_total, gain, seed, out, peak, clipped):
     """what tracks_finish_device and its window form share: the arguments checked, `gain` as a tensor or None, and `out`, `peak`
     and `clipped` allocated where they were not passed; (seed, dst_total, gain, out, peak, clipped)"""
-    import torch
     if dst_format not in (None, RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
         raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32 or None)" % (dst_format,))
     ntracks, _, nch = rows.shape
-    _tracks_table(table, ntracks)
     dev = rows.device
-    if table.device != dev:
-        raise TypeError("the table must be on %s" % (dev,))
+    _tracks_table(table, ntracks, dev)
     seed, dst_total = int(seed), int(dst_total)
     if not 0 <= seed < 1 << 64 or dst_total < 0:
         raise ValueError("seed must fit 64 unsigned bits, dst_total is a frame count")
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((ntracks,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (ntracks,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (ntracks, dev))
-    if dst_format is None:
-        if out is not None:
-            raise ValueError("dst_format=None measures only: there is nothing to write into `out`")
-    else:
-        odt, last = {RRX_FMT_S16: (torch.int16, nch), RRX_FMT_S32: (torch.int32, nch), RRX_FMT_S24_3: (torch.uint8, nch * 3)}[dst_format]
-        oshape = (dst_total, last)
-        if out is None:
-            out = torch.empty(oshape, dtype=odt, device=dev)
-        elif out.dtype != odt or tuple(out.shape) != oshape or out.device != dev or not out.is_contiguous():
-            raise TypeError("out must be a contiguous %s tensor %r on %s" % (odt, oshape, dev))
-    stats = []
-    for t, sdt, name in ((peak, torch.float64, "peak"), (clipped, torch.int64, "clipped")):
-        if t is None:
-            t = torch.zeros((ntracks, nch), dtype=sdt, device=dev)
-        elif t.dtype != sdt or tuple(t.shape) != (ntracks, nch) or t.device != dev or not t.is_contiguous():
-            raise TypeError("%s must be a contiguous %s tensor [%d, %d] on %s" % (name, sdt, ntracks, nch, dev))
-        stats.append(t)
-    peak, clipped = stats
+    gain = _gain(gain, ntracks, dev)
+    out = _pcm_out(out, dst_format, (dst_total,), nch, dev)
+    peak, clipped = _finish_stats(peak, clipped, ntracks, nch, dev)
     _ensure_init()
     return seed, dst_total, gain, out, peak, clipped
+
+
+def _state_handed_on(state, state_out, sshape, dev, touched):
+    """the state a per-track window call returns.  A call that touches nothing hands on the state that came in (or zeros), as a new
+    tensor; any other writes every entry of `state_out`, or of a new tensor"""
+    import torch
+    if not touched:
+        return torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
+    return torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out
 
 
 def tracks_finish_window_device(win, table, row_frames, win_first, win_frames, dst_format, dst_total, gain=None, dither=False, seed=0, out=None,
@@ -2019,25 +1926,15 @@ def tracks_finish_window_device(win, table, row_frames, win_first, win_frames, d
     destination position they have in the whole-row call, so disjoint windows that cover the rows -- in any order, each call given
     the `out`, `peak` and `clipped` the first one returned, which are accumulated into, not reallocated -- leave tracks_finish_device's
     bytes and statistics.  Everything else as in tracks_finish_device.  Returns (out, peak, clipped); the call only enqueues."""
-    dt = str(win.dtype)
-    if win.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not win.is_cuda or not win.is_contiguous():
-        raise TypeError("win must be a contiguous float32 or float64 device tensor [ntracks, win_stride, nch]")
-    ntracks, win_stride, nch = win.shape
-    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
-    if win_frames > win_stride:
-        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
+    fmt, ntracks, win_stride, nch = _tracks_frames(win, "win", "win_stride")
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames, win_stride)
     seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(win, table, dst_format, dst_total, gain, seed, out, peak, clipped)
     if not win_frames:  # (an empty tensor has no pointer, and there is nothing to do)
         return out, peak, clipped
-    dev = win.device
-    ptr = getattr(stream, "cuda_stream", stream) or 0
     write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
-    _check(lib().RRX_tracks_finish_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()), ntracks,
-                                                 nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT, C.c_void_p(win.data_ptr()),
-                                                 win_stride, row_frames, win_first, win_frames, dst_format or 0,
-                                                 C.c_void_p(out.data_ptr()) if write else None, dst_total,
-                                                 C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
-                                                 C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())), "RRX_tracks_finish_window_device")
+    _check(lib().RRX_tracks_finish_window_device(*_where(win.device, stream), table.data_ptr(), ntracks, nch, fmt, win.data_ptr(), win_stride, row_frames,
+                                                 win_first, win_frames, dst_format or 0, out.data_ptr() if write else None, dst_total, _ptr(gain),
+                                                 1 if dither else 0, seed, peak.data_ptr(), clipped.data_ptr()), "RRX_tracks_finish_window_device")
     return out, peak, clipped
 
 
@@ -2062,75 +1959,42 @@ def _tracks_finish_shaped_window(win, table, row_frames, win_first, win_frames, 
                                  state_out, out, peak, clipped, stream):
     """tracks_finish_shaped_window_device with the tensor that receives the state given (`state_out`, checked as `state` is; None:
     a new one), for a caller that hands two tensors to and fro (Resampler._convert_tracks_streamed)"""
-    import torch
-    dt = str(win.dtype)
-    if win.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not win.is_cuda or not win.is_contiguous():
-        raise TypeError("win must be a contiguous float32 or float64 device tensor [ntracks, win_stride, nch]")
-    if dst_format not in (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
-        raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3 or RRX_FMT_S32; out=False measures only)" % (dst_format,))
+    fmt, ntracks, win_stride, nch = _tracks_frames(win, "win", "win_stride")
+    _shaped_dst_format(dst_format)
     coefs, segment = _shaping(shaping, segment)
-    ntracks, win_stride, nch = win.shape
-    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
-    if win_frames > win_stride:
-        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames, win_stride)
     if state is None and win_first:
         raise ValueError("only the window at frame 0 needs no state: pass the state the call before returned")
     dev = win.device
     sshape = (ntracks, nch, RRX_SHAPE_MAX_ORDER)
-    for t, name in ((state, "state"), (state_out, "state_out")):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != sshape or t.device != dev or not t.is_contiguous()):
-            raise TypeError("%s must be a contiguous float64 tensor %r on %s" % (name, sshape, dev))
-    if state is not None and state_out is not None and state_out.data_ptr() == state.data_ptr():
-        raise ValueError("the call must not read and write one state tensor")
+    _state_pair(state, state_out, sshape, dev)
     measure = out is False
     seed, dst_total, gain, out, peak, clipped = _tracks_finish_buffers(win, table, None if measure else dst_format, dst_total, gain, seed,
                                                                        None if measure else out, peak, clipped)
-    if not win_frames or not row_frames:  # touches nothing, the state included: the state handed on is the one that came in
-        return out, peak, clipped, torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
-    new_state = torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out  # (every entry is written)
-    ptr = getattr(stream, "cuda_stream", stream) or 0
+    new_state = _state_handed_on(state, state_out, sshape, dev, win_frames and row_frames)
+    if not win_frames or not row_frames:  # touches nothing, the state included
+        return out, peak, clipped, new_state
     write = out is not None and dst_total > 0  # (an empty tensor has no pointer: nothing to write is measure only)
-    _check(lib().RRX_tracks_finish_shaped_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
-                                                        ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
-                                                        C.c_void_p(win.data_ptr()), win_stride, row_frames, win_first, win_frames, dst_format,
-                                                        C.c_void_p(out.data_ptr()) if write else None, dst_total,
-                                                        C.c_void_p(gain.data_ptr()) if gain is not None else None, 1 if dither else 0, seed,
-                                                        C.cast(coefs, C.c_void_p), len(coefs), segment,
-                                                        C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(new_state.data_ptr()),
-                                                        C.c_void_p(peak.data_ptr()), C.c_void_p(clipped.data_ptr())),
-           "RRX_tracks_finish_shaped_window_device")
+    _check(lib().RRX_tracks_finish_shaped_window_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, win.data_ptr(), win_stride, row_frames,
+                                                        win_first, win_frames, dst_format, out.data_ptr() if write else None, dst_total, _ptr(gain),
+                                                        1 if dither else 0, seed, C.cast(coefs, C.c_void_p), len(coefs), segment, _ptr(state),
+                                                        new_state.data_ptr(), peak.data_ptr(), clipped.data_ptr()), "RRX_tracks_finish_shaped_window_device")
     return out, peak, clipped, new_state
 
 
 def _tracks_measure_window(win, table, row_frames, win_first, win_frames, gain, state, state_out, width):
     """what the two measuring window calls share: `win`, the window, the table, the gain and the two state tensors checked;
-    (dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain)"""
-    import torch
-    dt = str(win.dtype)
-    if win.dim() != 3 or not (dt.endswith("float32") or dt.endswith("float64")) or not win.is_cuda or not win.is_contiguous():
-        raise TypeError("win must be a contiguous float32 or float64 device tensor [ntracks, win_stride, nch]")
-    ntracks, win_stride, nch = win.shape
-    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames)
-    if win_frames > win_stride:
-        raise ValueError("a window of %d frames in a tensor of %d frames a row" % (win_frames, win_stride))
+    (RRX_FMT_*, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain, state shape)"""
+    fmt, ntracks, win_stride, nch = _tracks_frames(win, "win", "win_stride")
+    row_frames, win_first, win_frames = _tracks_window(row_frames, win_first, win_frames, win_stride)
     if state is None and win_first:
         raise ValueError("only the window at frame 0 needs no state: pass the state the call before returned")
-    _tracks_table(table, ntracks)
     dev = win.device
-    if table.device != dev:
-        raise TypeError("the table must be on %s" % (dev,))
-    if gain is not None and not hasattr(gain, "data_ptr"):
-        gain = torch.full((ntracks,), float(gain), dtype=torch.float64, device=dev)
-    if gain is not None:
-        if gain.dtype != torch.float64 or tuple(gain.shape) != (ntracks,) or gain.device != dev or not gain.is_contiguous():
-            raise TypeError("gain must be a float, or a contiguous float64 tensor [%d] on %s" % (ntracks, dev))
+    _tracks_table(table, ntracks, dev)
+    gain = _gain(gain, ntracks, dev)
     sshape = (ntracks, nch, width)
-    for t, name in ((state, "state"), (state_out, "state_out")):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != sshape or t.device != dev or not t.is_contiguous()):
-            raise TypeError("%s must be a contiguous float64 tensor %r on %s" % (name, sshape, dev))
-    if state is not None and state_out is not None and state_out.data_ptr() == state.data_ptr():
-        raise ValueError("the call must not read and write one state tensor")
-    return dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain
+    _state_pair(state, state_out, sshape, dev)
+    return fmt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain, sshape
 
 
 def tracks_true_peak_window_device(win, table, row_frames, win_first, win_frames, gain=None, filter="bs1770", state=None, true_peak=None,
@@ -2148,25 +2012,18 @@ def tracks_true_peak_window_device(win, table, row_frames, win_first, win_frames
 
 def _tracks_true_peak_window(win, table, row_frames, win_first, win_frames, gain, filter, state, state_out, true_peak, peak, stream):
     """tracks_true_peak_window_device with the tensor that receives the state given (`state_out`; None: a new one)"""
-    import torch
-    dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain = _tracks_measure_window(
+    fmt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain, sshape = _tracks_measure_window(
         win, table, row_frames, win_first, win_frames, gain, state, state_out, RRX_TP_MAX_TAPS)
     phases, taps, coefs = _true_peak_filter(filter)
     dev = win.device
     true_peak, peak = _true_peak_stats(true_peak, peak, ntracks, nch, dev)
-    sshape = (ntracks, nch, RRX_TP_MAX_TAPS)
-    if not win_frames or not row_frames:  # touches nothing, the state included: the state handed on is the one that came in
-        return true_peak, peak, torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
-    new_state = torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out  # (every entry is written)
+    new_state = _state_handed_on(state, state_out, sshape, dev, win_frames and row_frames)
+    if not win_frames or not row_frames:  # touches nothing, the state included
+        return true_peak, peak, new_state
     _ensure_init()
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_true_peak_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
-                                                    ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
-                                                    C.c_void_p(win.data_ptr()), win_stride, row_frames, win_first, win_frames,
-                                                    C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(coefs, C.c_void_p),
-                                                    phases, taps, C.c_void_p(state.data_ptr()) if state is not None else None,
-                                                    C.c_void_p(new_state.data_ptr()), C.c_void_p(true_peak.data_ptr()),
-                                                    C.c_void_p(peak.data_ptr())), "RRX_tracks_true_peak_window_device")
+    _check(lib().RRX_tracks_true_peak_window_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, win.data_ptr(), win_stride, row_frames,
+                                                    win_first, win_frames, _ptr(gain), C.cast(coefs, C.c_void_p), phases, taps, _ptr(state),
+                                                    new_state.data_ptr(), true_peak.data_ptr(), peak.data_ptr()), "RRX_tracks_true_peak_window_device")
     return true_peak, peak, new_state
 
 
@@ -2189,7 +2046,7 @@ def tracks_loudness_window_device(win, table, row_frames, win_first, win_frames,
 def _tracks_loudness_window(win, table, row_frames, win_first, win_frames, rate, gain, coefs, hop, state, state_out, energy, hops, work, stream):
     """tracks_loudness_window_device with the tensor that receives the state given (`state_out`; None: a new one)"""
     import torch
-    dt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain = _tracks_measure_window(
+    fmt, ntracks, win_stride, nch, row_frames, win_first, win_frames, gain, sshape = _tracks_measure_window(
         win, table, row_frames, win_first, win_frames, gain, state, state_out, RRX_LOUDNESS_WIN_STATE)
     c, hop = _loudness_filter(rate, coefs, hop)
     dev = win.device
@@ -2199,23 +2056,17 @@ def _tracks_loudness_window(win, table, row_frames, win_first, win_frames, rate,
         hops = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
     elif hops.dtype != torch.int64 or tuple(hops.shape) != (ntracks,) or hops.device != dev or not hops.is_contiguous():
         raise TypeError("hops must be a contiguous int64 tensor [%d] on %s" % (ntracks, dev))
-    sshape = (ntracks, nch, RRX_LOUDNESS_WIN_STATE)
-    if not win_frames or not row_frames:  # touches nothing, the state included: the state handed on is the one that came in
-        return energy, hops, torch.zeros(sshape, dtype=torch.float64, device=dev) if state is None else state.clone()
-    new_state = torch.empty(sshape, dtype=torch.float64, device=dev) if state_out is None else state_out  # (every entry is written)
+    new_state = _state_handed_on(state, state_out, sshape, dev, win_frames and row_frames)
+    if not win_frames or not row_frames:  # touches nothing, the state included
+        return energy, hops, new_state
     _ensure_init()
     if not energy.shape[2]:  # (an empty tensor has no pointer; no hop is written through this one)
         energy_ptr = torch.zeros((1,), dtype=torch.float64, device=dev)
     else:
         energy_ptr = energy
-    ptr = getattr(stream, "cuda_stream", stream) or 0
-    _check(lib().RRX_tracks_loudness_window_device(-1 if dev.index is None else int(dev.index), C.c_void_p(ptr), C.c_void_p(table.data_ptr()),
-                                                   ntracks, nch, RRX_FMT_DOUBLE if dt.endswith("float64") else RRX_FMT_FLOAT,
-                                                   C.c_void_p(win.data_ptr()), win_stride, row_frames, win_first, win_frames,
-                                                   C.c_void_p(gain.data_ptr()) if gain is not None else None, C.cast(c, C.c_void_p), hop,
-                                                   C.c_void_p(state.data_ptr()) if state is not None else None,
-                                                   C.c_void_p(new_state.data_ptr()), C.c_void_p(energy_ptr.data_ptr()), energy.shape[2],
-                                                   C.c_void_p(hops.data_ptr()), C.c_void_p(work.data_ptr()), work.numel()),
+    _check(lib().RRX_tracks_loudness_window_device(*_where(dev, stream), table.data_ptr(), ntracks, nch, fmt, win.data_ptr(), win_stride, row_frames,
+                                                   win_first, win_frames, _ptr(gain), C.cast(c, C.c_void_p), hop, _ptr(state), new_state.data_ptr(),
+                                                   energy_ptr.data_ptr(), energy.shape[2], _ptr(hops), work.data_ptr(), work.numel()),
            "RRX_tracks_loudness_window_device")
     return energy, hops, new_state
 
@@ -2324,6 +2175,91 @@ def _ensure_init():
 def _check(rc, what):
     if rc:
         raise RRError(rc, what)
+
+
+# -- the shared gain expressions of the Resampler.convert_tracks_to_pcm_* family: the streamed forms equal the whole-row forms bit for bit
+# -- in gain, trim and lufs because both call these
+def _album_checked(album, ntracks):
+    """the `album=` of a conversion: None, or one non-negative int per track, as a list"""
+    if album is not None:
+        album = [int(v) for v in album]
+        if len(album) != ntracks or any(v < 0 for v in album):
+            raise ValueError("album is one non-negative int per track")
+    return album
+
+
+def _limiter_frames(rate, max_dbtp, lookahead_ms, hold_ms):
+    """(ceiling, lookahead, hold) of the limited conversions: max_dbtp as a linear level, the two times rounded to frames of `rate`
+    and clamped to what the limiter takes"""
+    ceiling = 10.0 ** (float(max_dbtp) / 20.0)
+    lookahead = min(max(int(round(float(lookahead_ms) * rate / 1000.0)), 1), RRX_LIMIT_MAX_LOOKAHEAD)
+    hold = min(max(int(round(float(hold_ms) * rate / 1000.0)), 0), RRX_LIMIT_MAX_HOLD)
+    return ceiling, lookahead, hold
+
+
+def _largest_peak(true_peak, sample_peak):
+    """m [rows]: per row, the largest of true peak and sample peak over its channels"""
+    import torch
+    return torch.maximum(true_peak, sample_peak).amax(1)
+
+
+def _peak_normalizing_gain(true_peak, sample_peak, target):
+    """the gain that brings every row's largest peak to the linear level `target`; 1.0 where that peak is 0 or not finite"""
+    import torch
+    m = _largest_peak(true_peak, sample_peak)
+    return torch.where(torch.isfinite(m) & (m > 0), torch.full_like(m, target) / m, torch.ones_like(m)).contiguous()  # (one division, one rounding)
+
+
+def _trim(true_peak, sample_peak, ceiling):
+    """min(1, ceiling / m) per row; 1.0 where m, the row's largest peak, is 0 or not finite"""
+    import torch
+    m = _largest_peak(true_peak, sample_peak)
+    ok = torch.isfinite(m) & (m > 0)
+    return torch.where(ok, torch.clamp(torch.full_like(m, ceiling) / torch.where(ok, m, torch.ones_like(m)), max=1.0), torch.ones_like(m)).contiguous()
+
+
+def _loudness_measured(energy, hops, n, album, weights, rate, cur):
+    """The gated loudness of the rows' hop energies: (lufs, n2, of).  Without `album`, per row, `of` None.  With it, per album --
+    the gate over the pooled 400 ms blocks of an album's tracks -- and `of` the album of each of the `n` tracks as an index tensor;
+    the rows without a track are in no album."""
+    import torch
+    if album is None:
+        result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
+        return integrated_lufs(result), result[:, 1], None
+    dev = energy.device
+    of = torch.tensor(album, dtype=torch.int64, device=dev)
+    groups = torch.full((energy.shape[0],), -1, dtype=torch.int32, device=dev)
+    groups[:n] = of.to(torch.int32)
+    blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
+    result = loudness_gate_groups_device(blocks, nblocks, groups, max(album) + 1, stream=cur)
+    return integrated_lufs(result), result[:, 1], of
+
+
+def _loudness_normalized_gain(lufs, n2, of, m, n, target_lufs, max_dbtp):
+    """(gain [rows], lufs per track) of the loudness-normalised conversions from _loudness_measured's answer and m =
+    _largest_peak: loudness_normalizing_gain per row, or per album -- with the largest m over the album's tracks -- gathered per
+    track"""
+    import torch
+    if of is None:
+        return loudness_normalizing_gain(lufs, n2, m, target_lufs, max_dbtp), lufs
+    most = torch.zeros((lufs.shape[0],), dtype=m.dtype, device=m.device).scatter_reduce(0, of, m[:n], "amax", include_self=True)
+    gain = torch.ones_like(m)
+    gain[:n] = loudness_normalizing_gain(lufs, n2, most, target_lufs, max_dbtp)[of]
+    return gain, lufs[of]
+
+
+def _tracks_views(pcm, plan, n):
+    """the first `n` tracks' slices of the packed destination, or None for a call that measured only"""
+    return None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
+
+
+def _finish_rows(rows, table, plan, n, dst_format, shaping, segment, finish_kw):
+    """the tail of the whole-row conversions: the rows finished, shaped or not, and cut per track; (views, peak, clipped)"""
+    if shaping is not None:
+        pcm, peak, clipped = tracks_finish_shaped_device(rows, table, dst_format, plan.dst_total, shaping, segment, **finish_kw)
+    else:
+        pcm, peak, clipped = tracks_finish_device(rows, table, dst_format, plan.dst_total, **finish_kw)
+    return _tracks_views(pcm, plan, n), peak[:n], clipped[:n]
 
 
 class Resampler:
@@ -2941,8 +2877,7 @@ class Resampler:
                 stage(*emitted)
         if measure is not None:
             return measure.result()
-        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
-        return views, peak[:n], clipped[:n]
+        return _tracks_views(pcm, plan, n), peak[:n], clipped[:n]
 
     def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, shaping=None, segment=65536, mix=None, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
@@ -2959,12 +2894,7 @@ class Resampler:
         n = len(tracks)
         self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_device")
         finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
-        if shaping is not None:
-            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, **finish_kw)
-        else:
-            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, **finish_kw)
-        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
-        return views, peak[:n], clipped[:n]
+        return _finish_rows(out, table, plan, n, dst_format, shaping, segment, finish_kw)
 
     def convert_tracks_to_pcm_normalized(self, tracks, dst_format, target_dbtp=-1.0, shaping=None, segment=65536, dither=False, seed=0):
         """convert_tracks_to_pcm_device with every track normalised to a TRUE peak of `target_dbtp` dBTP: the rows are converted
@@ -2982,16 +2912,9 @@ class Resampler:
         n = len(tracks)
         cur = torch.cuda.current_stream(out.device)
         true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
-        m = torch.maximum(true_peak, sample_peak).amax(1)
-        target = 10.0 ** (float(target_dbtp) / 20.0)
-        gain = torch.where(torch.isfinite(m) & (m > 0), torch.full_like(m, target) / m, torch.ones_like(m)).contiguous()  # (one division, one rounding)
-        if shaping is not None:
-            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=gain, dither=dither,
-                                                             seed=seed, stream=cur)
-        else:
-            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
-        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
-        return views, peak[:n], clipped[:n], gain[:n], true_peak[:n]
+        gain = _peak_normalizing_gain(true_peak, sample_peak, 10.0 ** (float(target_dbtp) / 20.0))
+        views, peak, clipped = _finish_rows(out, table, plan, n, dst_format, shaping, segment, dict(gain=gain, dither=dither, seed=seed, stream=cur))
+        return views, peak, clipped, gain[:n], true_peak[:n]
 
     def convert_tracks_to_pcm_loudness_normalized(self, tracks, dst_format, target_lufs=-18.0, max_dbtp=-1.0, weights=None, shaping=None,
                                                   segment=65536, dither=False, seed=0, album=None):
@@ -3012,64 +2935,31 @@ class Resampler:
         and `lufs[t]` is the loudness of t's album."""
         import torch
         tracks = list(tracks)
-        if album is not None:
-            album = [int(v) for v in album]
-            if len(album) != len(tracks) or any(v < 0 for v in album):
-                raise ValueError("album is one non-negative int per track")
+        album = _album_checked(album, len(tracks))
         plan, table, out = self._convert_tracks_rows(tracks)
         n = len(tracks)
         cur = torch.cuda.current_stream(out.device)
         rate = int(self.cfg.out_rate)
         energy, hops = tracks_loudness_device(out, table, rate, stream=cur)
-        if album is None:
-            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
-            lufs = integrated_lufs(result)
-            true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
-            m = torch.maximum(true_peak, sample_peak).amax(1)
-            gain = loudness_normalizing_gain(lufs, result[:, 1], m, target_lufs, max_dbtp)
-        else:
-            nalbums = max(album) + 1
-            of = torch.tensor(album, dtype=torch.int64, device=out.device)
-            groups = torch.full((out.shape[0],), -1, dtype=torch.int32, device=out.device)  # the streams without a track are in no album
-            groups[:n] = of.to(torch.int32)
-            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
-            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
-            per_album = integrated_lufs(result)
-            true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
-            m = torch.maximum(true_peak, sample_peak).amax(1)
-            most = torch.zeros((nalbums,), dtype=m.dtype, device=m.device).scatter_reduce(0, of, m[:n], "amax", include_self=True)
-            gain = torch.ones_like(m)
-            gain[:n] = loudness_normalizing_gain(per_album, result[:, 1], most, target_lufs, max_dbtp)[of]
-            lufs = per_album[of]
-        if shaping is not None:
-            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=gain, dither=dither,
-                                                             seed=seed, stream=cur)
-        else:
-            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=gain, dither=dither, seed=seed, stream=cur)
-        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
-        return views, peak[:n], clipped[:n], gain[:n], true_peak[:n], lufs[:n]
+        lufs, n2, of = _loudness_measured(energy, hops, n, album, weights, rate, cur)
+        true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
+        gain, lufs = _loudness_normalized_gain(lufs, n2, of, _largest_peak(true_peak, sample_peak), n, target_lufs, max_dbtp)
+        views, peak, clipped = _finish_rows(out, table, plan, n, dst_format, shaping, segment, dict(gain=gain, dither=dither, seed=seed, stream=cur))
+        return views, peak, clipped, gain[:n], true_peak[:n], lufs[:n]
 
     def _gain_by_loudness(self, energy, hops, n, album, weights, target_lufs, cur):
         """(gain, lufs), both [rows], of the limited conversions from the hop energies of the rows: 10 ** ((target_lufs - L) / 20), 1.0
         where no block passed the gates; with `album` L is the loudness of the track's album"""
         import torch
-        rate = int(self.cfg.out_rate)
-        rows, dev = energy.shape[0], energy.device
-        if album is None:
-            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
-            lufs, passed = integrated_lufs(result), result[:, 1] > 0
-        else:
-            nalbums = max(album) + 1
-            of = torch.tensor(album, dtype=torch.int64, device=dev)
-            groups = torch.full((rows,), -1, dtype=torch.int32, device=dev)  # the streams without a track are in no album
-            groups[:n] = of.to(torch.int32)
-            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
-            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
-            per_album = integrated_lufs(result)
-            lufs = torch.full((rows,), float("-inf"), dtype=per_album.dtype, device=dev)
-            lufs[:n] = per_album[of]
+        lufs, n2, of = _loudness_measured(energy, hops, n, album, weights, int(self.cfg.out_rate), cur)
+        passed = n2 > 0
+        if of is not None:  # per album so far: gathered per track, the rows without a track at -inf and not passed
+            rows, dev = energy.shape[0], energy.device
+            album_lufs, album_passed = lufs, passed
+            lufs = torch.full((rows,), float("-inf"), dtype=album_lufs.dtype, device=dev)
+            lufs[:n] = album_lufs[of]
             passed = torch.zeros((rows,), dtype=torch.bool, device=dev)
-            passed[:n] = (result[:, 1] > 0)[of]
+            passed[:n] = album_passed[of]
         by_loudness = torch.pow(10.0, (float(target_lufs) - torch.where(passed, lufs, torch.zeros_like(lufs))) / 20.0)
         gain = torch.where(passed, by_loudness, torch.ones_like(by_loudness)).contiguous()
         return gain, lufs
@@ -3092,14 +2982,9 @@ class Resampler:
         `release_block` entries: the gain recovers exponentially behind a transient; None is the limiter without a release."""
         import torch
         tracks = list(tracks)
-        if album is not None:
-            album = [int(v) for v in album]
-            if len(album) != len(tracks) or any(v < 0 for v in album):
-                raise ValueError("album is one non-negative int per track")
+        album = _album_checked(album, len(tracks))
         rate = int(self.cfg.out_rate)
-        ceiling = 10.0 ** (float(max_dbtp) / 20.0)
-        lookahead = min(max(int(round(float(lookahead_ms) * rate / 1000.0)), 1), RRX_LIMIT_MAX_LOOKAHEAD)
-        hold = min(max(int(round(float(hold_ms) * rate / 1000.0)), 0), RRX_LIMIT_MAX_HOLD)
+        ceiling, lookahead, hold = _limiter_frames(rate, max_dbtp, lookahead_ms, hold_ms)
         plan, table, out = self._convert_tracks_rows(tracks)
         n = len(tracks)
         cur = torch.cuda.current_stream(out.device)
@@ -3111,16 +2996,9 @@ class Resampler:
             _, reduction, limited = tracks_limit_release_device(out, table, ceiling, limit_release_coef(release_ms, rate), gain=gain,
                                                                 lookahead=lookahead, hold=hold, block=release_block, stream=cur)
         true_peak, sample_peak = tracks_true_peak_device(out, table, stream=cur)
-        m = torch.maximum(true_peak, sample_peak).amax(1)
-        ok = torch.isfinite(m) & (m > 0)
-        trim = torch.where(ok, torch.clamp(torch.full_like(m, ceiling) / torch.where(ok, m, torch.ones_like(m)), max=1.0), torch.ones_like(m)).contiguous()
-        if shaping is not None:
-            pcm, peak, clipped = tracks_finish_shaped_device(out, table, dst_format, plan.dst_total, shaping, segment, gain=trim, dither=dither,
-                                                             seed=seed, stream=cur)
-        else:
-            pcm, peak, clipped = tracks_finish_device(out, table, dst_format, plan.dst_total, gain=trim, dither=dither, seed=seed, stream=cur)
-        views = None if pcm is None else [pcm[int(e.dst_first):int(e.dst_first + e.out_frames)] for _, e in zip(range(n), plan.table)]
-        return views, peak[:n], clipped[:n], gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
+        trim = _trim(true_peak, sample_peak, ceiling)
+        views, peak, clipped = _finish_rows(out, table, plan, n, dst_format, shaping, segment, dict(gain=trim, dither=dither, seed=seed, stream=cur))
+        return views, peak, clipped, gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
 
     def _streamed_under_gain(self, tracks, dst_format, window, shaping, segment, gain, dither, seed, who):
         """pass B of the streamed normalising forms: reset(), then the streamed loop, shaped or not, under the per-track gain"""
@@ -3141,7 +3019,6 @@ class Resampler:
         that is the price of never holding the rows ("Windows with true peak and loudness").  Memory: that of the
         streamed form plus the two filter states [nstreams, nch, 16] and the statistics."""
         import functools
-        import torch
         tracks = list(tracks)
         if shaping is not None:
             _shaping(shaping, segment)  # (refused before anything is converted)
@@ -3149,9 +3026,7 @@ class Resampler:
         true_peak, sample_peak, _, _ = self._convert_tracks_streamed(tracks, dst_format, window, None, None, {}, who,
                                                                      measure=functools.partial(_WindowMeter, None, self.nch))
         n = len(tracks)
-        m = torch.maximum(true_peak, sample_peak).amax(1)
-        target = 10.0 ** (float(target_dbtp) / 20.0)
-        gain = torch.where(torch.isfinite(m) & (m > 0), torch.full_like(m, target) / m, torch.ones_like(m)).contiguous()  # (one division, one rounding)
+        gain = _peak_normalizing_gain(true_peak, sample_peak, 10.0 ** (float(target_dbtp) / 20.0))
         views, peak, clipped = self._streamed_under_gain(tracks, dst_format, window, shaping, segment, gain, dither, seed, who)
         return views, peak, clipped, gain[:n], true_peak[:n]
 
@@ -3168,10 +3043,7 @@ class Resampler:
         import functools
         import torch
         tracks = list(tracks)
-        if album is not None:
-            album = [int(v) for v in album]
-            if len(album) != len(tracks) or any(v < 0 for v in album):
-                raise ValueError("album is one non-negative int per track")
+        album = _album_checked(album, len(tracks))
         if shaping is not None:
             _shaping(shaping, segment)  # (refused before anything is converted)
         who = "convert_tracks_to_pcm_streamed_loudness_normalized"
@@ -3179,27 +3051,9 @@ class Resampler:
         true_peak, sample_peak, energy, hops = self._convert_tracks_streamed(tracks, dst_format, window, None, None, {}, who,
                                                                              measure=functools.partial(_WindowMeter, rate, self.nch))
         n = len(tracks)
-        dev = energy.device
-        cur = torch.cuda.current_stream(dev)
-        m = torch.maximum(true_peak, sample_peak).amax(1)
-        if album is None:
-            result = loudness_gate_device(energy, rate // 10, hops=hops, weights=weights, stream=cur)
-            lufs = integrated_lufs(result)
-            gain = loudness_normalizing_gain(lufs, result[:, 1], m, target_lufs, max_dbtp)
-        else:
-            nalbums = max(album) + 1
-            of = torch.tensor(album, dtype=torch.int64, device=dev)
-            groups = torch.full((energy.shape[0],), -1, dtype=torch.int32, device=dev)  # the streams without a track are in no album
-            groups[:n] = of.to(torch.int32)
-            blocks, nblocks, _ = loudness_blocks_device(energy, rate // 10, 4, 1, hops=hops, weights=weights, stream=cur)
-            result = loudness_gate_groups_device(blocks, nblocks, groups, nalbums, stream=cur)
-            per_album = integrated_lufs(result)
-            most = torch.zeros((nalbums,), dtype=m.dtype, device=m.device).scatter_reduce(0, of, m[:n], "amax", include_self=True)
-            gain = torch.ones_like(m)
-            gain[:n] = loudness_normalizing_gain(per_album, result[:, 1], most, target_lufs, max_dbtp)[of]
-            lufs = per_album[of]
-            del blocks, nblocks
-        del energy, hops, result, sample_peak, m  # (pass B runs in the streamed form's memory, beside what is returned)
+        lufs, n2, of = _loudness_measured(energy, hops, n, album, weights, rate, torch.cuda.current_stream(energy.device))
+        gain, lufs = _loudness_normalized_gain(lufs, n2, of, _largest_peak(true_peak, sample_peak), n, target_lufs, max_dbtp)
+        del energy, hops, n2, sample_peak  # (pass B runs in the streamed form's memory, beside what is returned)
         views, peak, clipped = self._streamed_under_gain(tracks, dst_format, window, shaping, segment, gain.contiguous(), dither, seed, who)
         return views, peak, clipped, gain[:n], true_peak[:n], lufs[:n]
 
@@ -3225,17 +3079,12 @@ class Resampler:
         import functools
         import torch
         tracks = list(tracks)
-        if album is not None:
-            album = [int(v) for v in album]
-            if len(album) != len(tracks) or any(v < 0 for v in album):
-                raise ValueError("album is one non-negative int per track")
+        album = _album_checked(album, len(tracks))
         if shaping is not None:
             _shaping(shaping, segment)  # (refused before anything is converted)
         who = "convert_tracks_to_pcm_streamed_loudness_limited"
         rate = int(self.cfg.out_rate)
-        ceiling = 10.0 ** (float(max_dbtp) / 20.0)
-        lookahead = min(max(int(round(float(lookahead_ms) * rate / 1000.0)), 1), RRX_LIMIT_MAX_LOOKAHEAD)
-        hold = min(max(int(round(float(hold_ms) * rate / 1000.0)), 0), RRX_LIMIT_MAX_HOLD)
+        ceiling, lookahead, hold = _limiter_frames(rate, max_dbtp, lookahead_ms, hold_ms)
         release = None if release_ms is None else _limit_release_params(limit_release_coef(release_ms, rate), release_block)
         n = len(tracks)
         # pass A: the loudness
@@ -3253,10 +3102,8 @@ class Resampler:
         true_peak, sample_peak, _, _ = self._convert_tracks_streamed(
             tracks, dst_format, window, None, None, {}, who, measure=functools.partial(_WindowMeter, None, self.nch),
             limit=functools.partial(_WindowLimiter, ceiling, gain, lookahead, hold, reduction, limited, release=release))
-        m = torch.maximum(true_peak, sample_peak).amax(1)
-        ok = torch.isfinite(m) & (m > 0)
-        trim = torch.where(ok, torch.clamp(torch.full_like(m, ceiling) / torch.where(ok, m, torch.ones_like(m)), max=1.0), torch.ones_like(m)).contiguous()
-        del true_peak, sample_peak, m
+        trim = _trim(true_peak, sample_peak, ceiling)
+        del true_peak, sample_peak
         # pass C: the same limited windows, finished under the trim
         self.reset()
         kw = dict(gain=trim[:n].contiguous(), dither=dither, seed=seed)
