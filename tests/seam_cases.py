@@ -4,6 +4,7 @@ stream, the references -- the numpy models over all streams, and where a model l
 vectorised restatement of it that the host module holds to the model at a small size -- and one caller that hands the same
 argument list to a host twin (RRX_debug_*_host) or to the device call (RRX_*_device), every output starting as a guard pattern
 with a few entries more than the call owns."""
+import contextlib
 import functools
 
 import numpy as np
@@ -72,6 +73,24 @@ class Host:
         self.a = np.ascontiguousarray(a, dtype=np.float64)
 
 
+_gated_run = None
+
+
+@contextlib.contextmanager
+def gated_by(run):
+    """while this is entered, the device calls of call() are made by run(enqueue, inputs, outputs, entry point) -- enqueue(stream)
+    queues the call on a torch stream, inputs and outputs are its device tensors -- instead of on the null stream between two
+    synchronisations (tests/test_gpu_stream_order.py: the gated driver of tests/stream_gate.py).  What the callers assert of the
+    outputs stays as it is."""
+    global _gated_run
+    assert _gated_run is None
+    _gated_run = run
+    try:
+        yield
+    finally:
+        _gated_run = None
+
+
 def call(name, args, on_device):
     """RRX_<name>_device(-1, NULL, *args) or RRX_debug_<name>_host(*args): numpy arrays go as pointers (on the device: to copies
     there, which must come back unchanged), Out arrays are filled with what the call left, None is NULL"""
@@ -113,8 +132,15 @@ def call(name, args, on_device):
         else:
             ptrs.append(v)
     torch.cuda.synchronize()
-    rc = getattr(L, "RRX_%s_device" % name)(-1, None, *ptrs)
-    assert rc == 0, (name, rc)
+    if _gated_run is not None:
+        def enqueue(stream):
+            rc = getattr(L, "RRX_%s_device" % name)(-1, stream.cuda_stream, *ptrs)
+            assert rc == 0, (name, rc)
+
+        _gated_run(enqueue, [t for _, t in ins], [t for _, t in outs], "RRX_%s_device" % name)
+    else:
+        rc = getattr(L, "RRX_%s_device" % name)(-1, None, *ptrs)
+        assert rc == 0, (name, rc)
     torch.cuda.synchronize()
     for v, t in outs:
         got = t.cpu().numpy()
