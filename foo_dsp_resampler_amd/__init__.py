@@ -1,6 +1,6 @@
 """foo_dsp_resampler_amd -- Python binding of the MI355X SoX-rate engine.
 
-The product is the C-ABI shared library `libratelib_amd.so` (include/ratelib.h, include/ratelib_amd.h)
+The product is the C-ABI shared library `libratelib_amd.so` (include/ratelib.h, include/ratelib_amd.h, include/ratelib_amd_album.h)
 whose entry points are what the reference plugin binds (rate/ratelib.h:72-81).  This package is a thin
 ctypes mirror of that interface used by the tests and bench.py; it contains no signal processing and
 no CPU fallback: if the library (or a GPU) is missing, calls fail.
@@ -21,6 +21,8 @@ from .ratelib import (RRConfig, RRError, Resampler, available_symbols, describe_
                       tracks_limit_release_window_work_doubles, tracks_limit_release_window_device, RRX_LIMIT_RELEASE_WIN_STATE,
                       PackedPlan, PackedTable, packed_plan, tracks_true_peak_packed_device, tracks_loudness_packed_device, scan_tracks_pcm,
                       MIX_MATRICES, RRX_MIX_MAX_CH, mix_matrix, mix_device, tracks_stage_mix_device, tracks_stage_mix_window_device)
+from .album import (ALBUM_SYMBOLS, RRX_LINK_NONE, RRXTrackLink, TracksAlbumPlan, tracks_plan_album, tracks_stage_album_device,  # noqa: F401
+                    tracks_stage_album_window_device)
 
 __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispatch", "plan_table", "edge_geometry", "lpc_extrapolate_device", "finish_device", "lib",
            "RRXTrack", "TracksPlan", "track_geometry", "tracks_plan", "tracks_stage_device", "tracks_finish_device", "tracks_stage_window_device", "tracks_finish_window_device",
@@ -38,4 +40,6 @@ __all__ = ["RRConfig", "RRError", "Resampler", "describe_plan", "describe_dispat
            "limit_window_reach", "tracks_limit_window_work_doubles", "tracks_limit_window_device",
            "tracks_limit_release_window_work_doubles", "tracks_limit_release_window_device", "RRX_LIMIT_RELEASE_WIN_STATE",
            "PackedPlan", "PackedTable", "packed_plan", "tracks_true_peak_packed_device", "tracks_loudness_packed_device", "scan_tracks_pcm",
-           "MIX_MATRICES", "RRX_MIX_MAX_CH", "mix_matrix", "mix_device", "tracks_stage_mix_device", "tracks_stage_mix_window_device"]
+           "MIX_MATRICES", "RRX_MIX_MAX_CH", "mix_matrix", "mix_device", "tracks_stage_mix_device", "tracks_stage_mix_window_device",
+           "ALBUM_SYMBOLS", "RRX_LINK_NONE", "RRXTrackLink", "TracksAlbumPlan", "tracks_plan_album", "tracks_stage_album_device",
+           "tracks_stage_album_window_device"]

@@ -2,6 +2,7 @@
 // device / batch extensions of include/ratelib_amd.h that take a handle or a plan, all thin shims over rsmp::Engine.  The
 // handle-free calls (output stage, tracks, meters, limiter) are in capi_stage.cpp.
 #include "../../include/ratelib_amd.h"
+#include "../../include/ratelib_amd_album.h"
 
 #include "capi_common.hpp"
 #include "engine.hpp"
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -610,6 +612,94 @@ int RRX_tracks_plan(const RR_config *config, const size_t *frames, int ntracks, 
       if (dst + out_frames < dst) return RR_INVPARAM;
       dst += out_frames;
       row = std::max(row, ext);
+    }
+    size_t cap = 0;
+    if (!out_row_capacity(plan, row, &cap)) return RR_INVPARAM;
+    *row_frames = row;
+    *out_row_cap = cap;
+    *src_total = src;
+    *dst_total = dst;
+    return RR_OK;
+  } catch (const std::bad_alloc &) {
+    return finish(RR_ENOMEM);
+  } catch (...) {
+    return RR_INTERNAL;
+  }
+}
+
+namespace {
+
+// ceil(s * r2 / r1): the first output instant of the album's grid (multiples of r1 / r2 input frames) at or behind input frame s
+size_t album_grid_ceil(size_t s, size_t r1, size_t r2) { return size_t(((unsigned __int128)s * r2 + r1 - 1) / r1); }
+
+} // namespace
+
+// RRX_tracks_plan with albums (include/ratelib_amd_album.h): a row of an album track starts on the album's grid of r1 input frames,
+// so that the handle it is pushed to computes the album's output instants, and owns the instants inside its own frames.
+int RRX_tracks_plan_album(const RR_config *config, const size_t *frames, const int *group, int ntracks, RRX_track *table, RRX_track_link *links,
+                          size_t *row_frames, size_t *out_row_cap, size_t *src_total, size_t *dst_total)
+{
+  if (!config || !frames || !group || ntracks < 1 || !table || !links || !row_frames || !out_row_cap || !src_total || !dst_total) return RR_INVPARAM;
+  try {
+    rsmp::ChainPlan plan;
+    int rc = rsmp::make_plan(to_config(config), plan);
+    if (rc) return rc;
+    size_t src = 0, dst = 0, row = 0;
+    for (int t = 0; t < ntracks; ++t) // (before any track is walked: a refusal costs nothing)
+      if (frames[t] > kTrackFramesMax || (src += frames[t]) < frames[t]) return RR_INVPARAM;
+    {
+      std::set<int> seen; // albums are consecutive: an id that comes back behind another one is refused
+      for (int t = 0; t < ntracks; ++t)
+        if (group[t] >= 0 && (t == 0 || group[t] != group[t - 1]) && !seen.insert(group[t]).second) return RR_INVPARAM;
+    }
+    size_t n_add = 0, n_drop = 0, prime = 0, inbuf = 0;
+    if ((rc = RRX_edge_geometry(plan.cfg.in_rate, plan.cfg.out_rate, &n_add, &n_drop, &prime, &inbuf)) != RR_OK) return rc;
+    size_t g = plan.cfg.in_rate, b = plan.cfg.out_rate;
+    while (b) { const size_t c = g % b; g = b; b = c; }
+    const size_t r1 = plan.cfg.in_rate / g, r2 = plan.cfg.out_rate / g;
+    src = 0;
+    for (int t0 = 0; t0 < ntracks;) {
+      int t1 = t0 + 1;
+      size_t A = frames[t0];
+      if (group[t0] >= 0)
+        for (; t1 < ntracks && group[t1] == group[t0]; ++t1) A += frames[t1];
+      if (A > kTrackFramesMax) return RR_INVPARAM; // (the album is walked as one track)
+      const bool album = group[t0] >= 0 && A > size_t(2 * rsmp::kLpcMaxOrder);
+      size_t album_out = 0;
+      if (album) {
+        size_t lead = 0, ext = 0, out_first = 0;
+        if ((rc = track_geometry(plan, A, &lead, &ext, &out_first, &album_out)) != RR_OK) return rc;
+      }
+      size_t S = 0; // the track's first frame, counted from the album's
+      for (int t = t0; t < t1; ++t) {
+        size_t lead = 0, ext = 0, out_first = 0, out_frames = 0;
+        links[t].back = links[t].ahead = RRX_LINK_NONE;
+        if (!album) {
+          if ((rc = track_geometry(plan, frames[t], &lead, &ext, &out_first, &out_frames)) != RR_OK) return rc;
+        } else {
+          const size_t ph = S % r1, at = album_grid_ceil(S, r1, r2);
+          lead = n_add + ph;
+          ext = frames[t] + 2 * lead;
+          out_first = n_drop + album_grid_ceil(ph, r1, r2);
+          const size_t end = t + 1 < t1 ? album_grid_ceil(S + frames[t], r1, r2) : album_out;
+          out_frames = end > at ? end - at : 0;
+          if (CounterChain(plan).drained_total(ext) < out_first + out_frames) return RR_INTERNAL; // the row does not reach its own slice
+          if (t > t0) links[t].back = S;
+          if (t + 1 < t1) links[t].ahead = A - S - frames[t];
+        }
+        table[t].src_first = src;
+        table[t].frames = frames[t];
+        table[t].lead = lead;
+        table[t].out_first = out_first;
+        table[t].out_frames = out_frames;
+        table[t].dst_first = dst;
+        src += frames[t];
+        S += frames[t];
+        if (dst + out_frames < dst) return RR_INVPARAM;
+        dst += out_frames;
+        row = std::max(row, ext);
+      }
+      t0 = t1;
     }
     size_t cap = 0;
     if (!out_row_capacity(plan, row, &cap)) return RR_INVPARAM;

@@ -5,6 +5,7 @@
 // the same *_args function to on_host.  Everything that can be refused from the arguments alone is refused before any device is
 // touched.
 #include "../../include/ratelib_amd.h"
+#include "../../include/ratelib_amd_album.h"
 
 #include "capi_common.hpp"
 #include "engine.hpp"
@@ -15,6 +16,7 @@
 #include "lpc.hpp"
 #include "measure_window.hpp"
 #include "tracks.hpp"
+#include "tracks_album.hpp"
 #include "tracks_mix.hpp"
 #include "true_peak.hpp"
 #include "limit.hpp"
@@ -24,6 +26,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 // The library's dynamic symbol table lists the C names of the helpers that came here from capi.cpp (an unnamed namespace inside
 // extern "C" does not keep them out of it), and it stays as it was: those helpers keep their names and their linkage.  What is
@@ -1178,6 +1181,77 @@ int RRX_tracks_stage_window_device(int device, void *hip_stream, size_t in_rate,
   if (rc == RR_OK) rc = tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, w);
   if (rc != RR_OK) return rc;
   return on_device(device, !win_frames, [&] { return rsmp::launch_tracks_stage_window(static_cast<hipStream_t>(hip_stream), a, w); });
+}
+
+namespace {
+
+// The three album calls (include/ratelib_amd_album.h): what the un-linked stage calls refuse, and the window.  Whole rows are the
+// window [0, row_frames) of rows that are their own buffer.
+int tracks_album_args(size_t in_rate, size_t out_rate, const RRX_track *tracks, const RRX_track_link *links, int ntracks, int nch, int src_format,
+                      const void *packed, size_t src_total, size_t row_frames, size_t win_first, size_t win_frames, fb_sample_t *win,
+                      size_t win_stride, rsmp::TracksAlbumArgs &a, rsmp::TracksWindow &w)
+{
+  static_assert(sizeof(RRX_track_link) == sizeof(rsmp::TrackLink) && sizeof(RRX_track_link) == 2 * sizeof(unsigned long long),
+                "RRX_track_link mirrors rsmp::TrackLink");
+  static_assert(RRX_LINK_NONE == rsmp::kLinkNone, "RRX_LINK_NONE mirrors rsmp::kLinkNone");
+  int rc = tracks_stage_args(in_rate, out_rate, tracks, ntracks, nch, src_format, packed, src_total, win, row_frames, a.s);
+  if (rc == RR_OK) rc = tracks_window_args(ntracks, nch, row_frames, win_first, win_frames, win_stride, w);
+  a.links = reinterpret_cast<const rsmp::TrackLink *>(links);
+  return rc;
+}
+
+} // namespace
+
+// The stage pass of a ragged batch with links (tracks_album.hip); without them, RRX_tracks_stage_device_samples.
+int RRX_tracks_stage_album_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks,
+                                  const RRX_track_link *d_links, int ntracks, int nch, int src_format, const void *d_packed, size_t src_total,
+                                  fb_sample_t *d_rows, size_t row_frames)
+{
+  if (!d_links)
+    return RRX_tracks_stage_device_samples(device, hip_stream, in_rate, out_rate, d_tracks, ntracks, nch, src_format, d_packed, src_total, d_rows,
+                                           row_frames);
+  rsmp::TracksAlbumArgs a;
+  rsmp::TracksWindow w;
+  const int rc = tracks_album_args(in_rate, out_rate, d_tracks, d_links, ntracks, nch, src_format, d_packed, src_total, row_frames, 0, row_frames,
+                                   d_rows, row_frames, a, w);
+  if (rc != RR_OK) return rc;
+  return on_device(device, false, [&] { return rsmp::launch_tracks_stage_album(static_cast<hipStream_t>(hip_stream), a, w); });
+}
+
+int RRX_tracks_stage_album_window_device(int device, void *hip_stream, size_t in_rate, size_t out_rate, const RRX_track *d_tracks,
+                                         const RRX_track_link *d_links, int ntracks, int nch, int src_format, const void *d_packed,
+                                         size_t src_total, size_t row_frames, size_t win_first, size_t win_frames, fb_sample_t *d_win,
+                                         size_t win_stride)
+{
+  if (!d_links)
+    return RRX_tracks_stage_window_device(device, hip_stream, in_rate, out_rate, d_tracks, ntracks, nch, src_format, d_packed, src_total,
+                                          row_frames, win_first, win_frames, d_win, win_stride);
+  rsmp::TracksAlbumArgs a;
+  rsmp::TracksWindow w;
+  const int rc = tracks_album_args(in_rate, out_rate, d_tracks, d_links, ntracks, nch, src_format, d_packed, src_total, row_frames, win_first,
+                                   win_frames, d_win, win_stride, a, w);
+  if (rc != RR_OK) return rc;
+  return on_device(device, !win_frames, [&] { return rsmp::launch_tracks_stage_album(static_cast<hipStream_t>(hip_stream), a, w); });
+}
+
+int RRX_debug_tracks_stage_album_host(size_t in_rate, size_t out_rate, const RRX_track *tracks, const RRX_track_link *links, int ntracks, int nch,
+                                      int src_format, const void *packed, size_t src_total, size_t row_frames, size_t win_first,
+                                      size_t win_frames, fb_sample_t *win, size_t win_stride)
+{
+  rsmp::TracksAlbumArgs a;
+  rsmp::TracksWindow w;
+  std::vector<rsmp::TrackLink> none; // links == NULL: every edge is extrapolated
+  return on_host(
+      [&] {
+        const int rc = tracks_album_args(in_rate, out_rate, tracks, links, ntracks, nch, src_format, packed, src_total, row_frames, win_first,
+                                         win_frames, win, win_stride, a, w);
+        if (rc == RR_OK && !links) {
+          none.assign(size_t(ntracks), rsmp::TrackLink{rsmp::kLinkNone, rsmp::kLinkNone});
+          a.links = none.data();
+        }
+        return rc;
+      },
+      !win_frames, [&] { rsmp::tracks_stage_album_host(a, w); });
 }
 
 // RRX_tracks_finish_device on a window of the output rows (tracks.hip).

@@ -730,6 +730,9 @@ class TracksPlan:
     is pushed from), `out_row_cap` (pitch of its output rows), `src_total` / `dst_total` (frames of the packed source /
     destination).  `array()` is the table as uint64 [ntracks, 6]; `to_device(device)` uploads it (int64 [ntracks, 6])."""
 
+    links = None   # (album.TracksAlbumPlan: the links of a gapless plan)
+    packed = None  # (a batch of convert_library_to_pcm(gapless=): the library's packed source, which its entries point into)
+
     def __init__(self, table, row_frames, out_row_cap, src_total, dst_total):
         self.table, self.row_frames, self.out_row_cap, self.src_total, self.dst_total = table, row_frames, out_row_cap, src_total, dst_total
 
@@ -2623,10 +2626,13 @@ class Resampler:
         """the `mix=` of a convert_tracks_* call: None, or the matrix [nch, nch_src] checked against the handle's channels"""
         return None if mix is None else _mix_checked(mix, nch_dst=self.nch)
 
-    def _tracks_checked(self, tracks, mix=None):
+    def _tracks_checked(self, tracks, mix=None, gapless=None):
         """the tracks of a convert_tracks_* call, checked: (list of tracks, plan with the idle streams as zero-length tracks).
-        `mix` (a checked matrix): the tracks have its column count of channels, not the handle's."""
+        `mix` (a checked matrix): the tracks have its column count of channels, not the handle's.  `gapless`: one group id per
+        track, and the plan is album.tracks_plan_album's -- or, from convert_library_to_pcm, a batch's plan as it stands."""
         import torch
+        if gapless is not None and mix is not None:
+            raise ValueError("gapless= together with mix= is not built")
         if self.dtype != np.float32:
             raise TypeError("convert_tracks_device needs a float32 handle (the LPC arithmetic is float32), not %s" % self.dtype)
         tracks = list(tracks)
@@ -2645,15 +2651,29 @@ class Resampler:
             if not x.is_cuda or x.device.index != self.device:
                 raise TypeError("expected tensors on the handle's device (cuda:%d)" % self.device)
         # the streams without a track are zero-length tracks: they own no output
-        return tracks, _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * (self.nstreams - len(tracks)))
+        idle = self.nstreams - len(tracks)
+        if gapless is None:
+            return tracks, _tracks_plan(self.cfg, [x.shape[0] for x in tracks] + [0] * idle)
+        if isinstance(gapless, TracksPlan):
+            return tracks, gapless
+        from . import album
+        return tracks, album._tracks_plan_album(self.cfg, [x.shape[0] for x in tracks] + [0] * idle,
+                                                album._gapless_checked(gapless, len(tracks)) + [-1] * idle)
 
-    def _convert_tracks_rows(self, tracks, scratch=None, mix=None):
+    @staticmethod
+    def _tracks_staged(tracks, plan, dev):
+        """(packed source, device links or None) of a planned batch"""
+        import torch
+        packed = plan.packed if plan.packed is not None else torch.cat(tracks).contiguous()
+        return packed, None if plan.links is None else plan.links_to_device(dev)
+
+    def _convert_tracks_rows(self, tracks, scratch=None, mix=None, gapless=None):
         """convert_tracks_device up to the handle's output rows: (plan, device table, output rows [nstreams, out_row_cap, nch]).
         `scratch` (a _Scratch): the staged rows and the output rows are views of its buffers instead of new tensors.  `mix`: the
-        stage call is tracks_stage_mix_device."""
+        stage call is tracks_stage_mix_device.  `gapless`: it is album.tracks_stage_album_device, on the album plan."""
         import torch
         mix = self._tracks_mix(mix)
-        tracks, plan = self._tracks_checked(tracks, mix)
+        tracks, plan = self._tracks_checked(tracks, mix, gapless)
         dev = tracks[0].device
         table = plan.to_device(dev)
         total, cap = plan.row_frames, plan.out_row_cap
@@ -2668,7 +2688,11 @@ class Resampler:
         self.set_stream(cur.cuda_stream)
         try:
             rows = None if scratch is None else scratch.take("rows", (self.nstreams, total, self.nch), dev)
-            if mix is None:
+            if gapless is not None:
+                from . import album
+                packed, links = self._tracks_staged(tracks, plan, dev)
+                src = album.tracks_stage_album_device(packed, table, links, self.cfg.in_rate, self.cfg.out_rate, total, out=rows, stream=cur)
+            elif mix is None:
                 src = tracks_stage_device(torch.cat(tracks).contiguous(), table, self.cfg.in_rate, self.cfg.out_rate, total, out=rows, stream=cur)
             else:
                 src = tracks_stage_mix_device(torch.cat(tracks).contiguous(), table, mix, self.cfg.in_rate, self.cfg.out_rate, total, out=rows,
@@ -2698,7 +2722,7 @@ class Resampler:
             raise RuntimeError("convert_tracks_device: %d output frames where the plan expects %d" % (got, need))
         return plan, table, out
 
-    def convert_tracks_device(self, tracks, mix=None):
+    def convert_tracks_device(self, tracks, mix=None, gapless=None):
         """Whole tracks of UNEQUAL length, one per stream, device to device: convert_track_device for a ragged batch.  `tracks`
         is a list of float32 device tensors [frames_i, nch], at most `nstreams` of them (the streams left over run empty) -- or of
         integer PCM as it is stored: all int16, all int32, or all uint8 [frames_i, nch * 3] (packed 24 bit), which the stage pass
@@ -2715,8 +2739,15 @@ class Resampler:
 
         `mix` (a name of MIX_MATRICES or an array [nch, nch_src]): the tracks hold nch_src channels and are mixed down (or up) to
         the handle's nch on load, by tracks_stage_mix_device -- "these 5.1 tracks to 48 kHz stereo" reads the source once and
-        resamples two channels.  A matrix whose shape does not fit the handle or the tracks raises ValueError."""
-        plan, _, out = self._convert_tracks_rows(tracks, mix=mix)
+        resamples two channels.  A matrix whose shape does not fit the handle or the tracks raises ValueError.
+
+        `gapless` (one group id per track; negative: a single): consecutive tracks with one non-negative id are cut from one
+        master, in play order.  They are planned by album.tracks_plan_album and staged from their neighbours
+        (album.tracks_stage_album_device): an inner edge holds the neighbour's frames where a single's is extrapolated, and the
+        row starts on the album's output grid, so the album's results laid end to end are the album converted as ONE track --
+        its length exactly, its samples to the chain's rounding -- with no click at a join ("Gapless albums").
+        None is the path without it, untouched; with `mix` it raises ValueError."""
+        plan, _, out = self._convert_tracks_rows(tracks, mix=mix, gapless=gapless)
         return [out[t, int(e.out_first):int(e.out_first + e.out_frames)] for t, e in zip(range(len(tracks)), plan.table)]
 
     def _tracks_finish_kw(self, ntracks, finish_kw, who):
@@ -2746,11 +2777,14 @@ class Resampler:
         convert_tracks_to_pcm_streamed_shaped, which carries that state.)
 
         `mix=` (a keyword beside those of the output stage; default None) as in convert_tracks_device: the windows are staged by
-        tracks_stage_mix_window_device."""
+        tracks_stage_mix_window_device.  `gapless=` (a keyword like `mix=`; default None) as in convert_tracks_device: the windows
+        are staged by album.tracks_stage_album_window_device."""
         mix = finish_kw.pop("mix", None)
+        gapless = finish_kw.pop("gapless", None)
         if shaping is not None:
             raise ValueError("noise shaping in the windowed form is not built: use convert_tracks_to_pcm_device")
-        return self._convert_tracks_streamed(tracks, dst_format, window, _scratch, None, finish_kw, "convert_tracks_to_pcm_streamed", mix=mix)
+        return self._convert_tracks_streamed(tracks, dst_format, window, _scratch, None, finish_kw, "convert_tracks_to_pcm_streamed", mix=mix,
+                                             gapless=gapless)
 
     def convert_tracks_to_pcm_streamed_shaped(self, tracks, dst_format, shaping, segment=65536, window=None, **finish_kw):
         """convert_tracks_to_pcm_device(..., shaping=, segment=) in bounded memory: convert_tracks_to_pcm_streamed with noise-shaped
@@ -2768,7 +2802,8 @@ class Resampler:
         scratch = finish_kw.pop("_scratch", None)
         return self._convert_tracks_streamed(tracks, dst_format, window, scratch, (shaping, segment), finish_kw, "convert_tracks_to_pcm_streamed_shaped")
 
-    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None, limit=None, mix=None):
+    def _convert_tracks_streamed(self, tracks, dst_format, window, _scratch, shaped, finish_kw, who, measure=None, limit=None, mix=None,
+                                 gapless=None):
         """the loop of convert_tracks_to_pcm_streamed (shaped None) and convert_tracks_to_pcm_streamed_shaped (shaped = (shaping,
         segment)): stage a window, push it, pull whatever is available into the output window and finish it at the running output
         position, then drain the same way.  The shaped form finishes with tracks_finish_shaped_window_device and ping-pongs two
@@ -2778,10 +2813,10 @@ class Resampler:
         `limit` (the limited form): called once as limit(table, cap, output window, stream), it gives a _WindowLimiter, which sits
         between the pull and the stage behind it -- that stage then sees the limited windows the limiter emits, ascending and
         contiguous from frame 0 like the pulled ones, and the rest of them after the final pull.  `mix`: the windows are staged by
-        tracks_stage_mix_window_device."""
+        tracks_stage_mix_window_device; `gapless`: by album.tracks_stage_album_window_device, on the album plan."""
         import torch
         mix = self._tracks_mix(mix)
-        tracks, plan = self._tracks_checked(tracks, mix)
+        tracks, plan = self._tracks_checked(tracks, mix, gapless)
         n, dev = len(tracks), tracks[0].device
         step = self.isamp_max
         window = step if window is None else int(window)
@@ -2836,7 +2871,9 @@ class Resampler:
 
         got = 0
         if total:
-            packed = torch.cat(tracks).contiguous()
+            packed, links = self._tracks_staged(tracks, plan, dev)
+            if gapless is not None:
+                from . import album
             prev = self._stream
             self.set_stream(cur.cuda_stream)
             try:
@@ -2856,7 +2893,9 @@ class Resampler:
 
                 for pos in range(0, total, window):
                     k = min(window, total - pos)
-                    if mix is None:
+                    if gapless is not None:
+                        album.tracks_stage_album_window_device(packed, table, links, in_rate, out_rate, total, pos, k, out=win, stream=cur)
+                    elif mix is None:
                         tracks_stage_window_device(packed, table, in_rate, out_rate, total, pos, k, out=win, stream=cur)
                     else:
                         tracks_stage_mix_window_device(packed, table, mix, in_rate, out_rate, total, pos, k, out=win, stream=cur)
@@ -2879,7 +2918,7 @@ class Resampler:
             return measure.result()
         return _tracks_views(pcm, plan, n), peak[:n], clipped[:n]
 
-    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, shaping=None, segment=65536, mix=None, **finish_kw):
+    def convert_tracks_to_pcm_device(self, tracks, dst_format, _scratch=None, shaping=None, segment=65536, mix=None, gapless=None, **finish_kw):
         """convert_tracks_device followed by the ragged output stage, tracks_finish_device(..., dst_format, **finish_kw), into ONE
         packed buffer, on torch's current stream: whole tracks of unequal length in, integer PCM out.  The tracks may be integer PCM
         themselves (int16, int32, or uint8 packed 24 bit, as in convert_tracks_device): PCM in, PCM out, with float32 only in the
@@ -2887,10 +2926,10 @@ class Resampler:
         views of that buffer, peak [ntracks, nch], clipped [ntracks, nch]); the buffer itself is the `_base` of the views.
         With `shaping` (a name of NOISE_SHAPES or coefficients) the output stage is tracks_finish_shaped_device(..., shaping,
         segment, **finish_kw): noise-shaped dither, on by default there, in segments counted from each track's first frame.
-        `mix` as in convert_tracks_device."""
+        `mix` and `gapless` as in convert_tracks_device."""
         import torch
         tracks = list(tracks)
-        plan, table, out = self._convert_tracks_rows(tracks, _scratch, mix=mix)
+        plan, table, out = self._convert_tracks_rows(tracks, _scratch, mix=mix, gapless=gapless)
         n = len(tracks)
         self._tracks_finish_kw(n, finish_kw, "convert_tracks_to_pcm_device")
         finish_kw.setdefault("stream", torch.cuda.current_stream(out.device))
@@ -3113,7 +3152,8 @@ class Resampler:
                                     release=release))
         return views, peak, clipped, gain[:n], trim[:n], reduction[:n], limited[:n], lufs[:n]
 
-    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536, mix=None):
+    def convert_library_to_pcm(self, tracks, dst_format, window=None, gain=None, dither=False, seed=0, shaping=None, segment=65536, mix=None,
+                               gapless=None):
         """A whole library on this ONE handle: any number of tracks of unequal length (tensors as in convert_tracks_device), cut
         into the length-sorted batches of tracks_batches for the handle's own `nstreams` -- no other split resamples less padding
         -- and converted batch after batch, with reset() before every batch whenever the handle has been used.  Each batch runs
@@ -3133,16 +3173,27 @@ class Resampler:
         default here.  With `window` it raises ValueError: the windowed form of noise shaping is not built (under this name:
         convert_library_to_pcm_streamed_shaped is that form).
 
-        `mix` as in convert_tracks_device: every batch is staged with it."""
+        `mix` as in convert_tracks_device: every batch is staged with it.
+
+        `gapless` (one group id per track of the library, as in convert_tracks_device; `tracks` is then in play order): the
+        library is packed and planned ONCE, in the order given (album.tracks_plan_album), and every length-sorted batch takes its
+        tracks' entries of that one plan.  An entry points into the library's packed source and destination, so the tracks of an
+        album may land in different batches and are still staged from their neighbours, and all batches write ONE packed
+        destination, in which an album lies contiguous and in order: the views of its tracks are adjacent slices of that buffer.
+        With `mix` it raises ValueError."""
         if shaping is not None and window is not None:
             raise ValueError("noise shaping in the windowed form is not built: leave `window` out")
+        if gapless is not None and mix is not None:
+            raise ValueError("gapless= together with mix= is not built")
         kw = {} if shaping is None else {"shaping": shaping, "segment": segment}
         if mix is not None:
             kw["mix"] = self._tracks_mix(mix)
         if window is None:
-            return self._convert_library(tracks, dst_format, gain, dither, seed, lambda batch, bkw: self.convert_tracks_to_pcm_device(batch, dst_format, **kw, **bkw))
+            return self._convert_library(tracks, dst_format, gain, dither, seed,
+                                         lambda batch, bkw: self.convert_tracks_to_pcm_device(batch, dst_format, **kw, **bkw), gapless=gapless)
         return self._convert_library(tracks, dst_format, gain, dither, seed,
-                                     lambda batch, bkw: self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **kw, **bkw))
+                                     lambda batch, bkw: self.convert_tracks_to_pcm_streamed(batch, dst_format, window=window, **kw, **bkw),
+                                     gapless=gapless)
 
     def convert_library_to_pcm_streamed_shaped(self, tracks, dst_format, window, shaping, segment=65536, gain=None, dither=True, seed=0):
         """convert_library_to_pcm(..., shaping=, segment=) in bounded memory: the library rule of that method -- length-sorted
@@ -3154,9 +3205,9 @@ class Resampler:
         return self._convert_library(tracks, dst_format, gain, dither, seed,
                                      lambda batch, bkw: self.convert_tracks_to_pcm_streamed_shaped(batch, dst_format, shaping, segment, window=window, **bkw))
 
-    def _convert_library(self, tracks, dst_format, gain, dither, seed, convert):
+    def _convert_library(self, tracks, dst_format, gain, dither, seed, convert, gapless=None):
         """the library rule of convert_library_to_pcm: `convert(batch, kw)` is one batch's conversion, kw its dither, seed, scratch
-        and gains"""
+        and gains -- and with `gapless` its plan, a subset of the library's one album plan, and the one packed destination"""
         import torch
         tracks = list(tracks)
         n, S = len(tracks), self.nstreams
@@ -3179,6 +3230,13 @@ class Resampler:
                     raise ValueError("%d gains for %d tracks" % (len(vals), n))
                 gain = torch.tensor(vals, dtype=torch.float64, device=dev)
         lib_batches = _tracks_batches(self.cfg, [x.shape[0] for x in tracks], S)
+        if gapless is not None:
+            from . import album
+            if dst_format not in (None, RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32):
+                raise ValueError("unknown dst_format %r (RRX_FMT_S16, RRX_FMT_S24_3, RRX_FMT_S32 or None)" % (dst_format,))
+            whole = album._tracks_plan_album(self.cfg, [x.shape[0] for x in tracks], gapless)
+            packed = torch.cat(tracks).contiguous()
+            pcm = None if dst_format is None else _pcm_out(None, dst_format, (whole.dst_total,), self.nch, dev)
         peak = torch.zeros((n, self.nch), dtype=torch.float64, device=dev)
         clipped = torch.zeros((n, self.nch), dtype=torch.int64, device=dev)
         views = [None] * n
@@ -3191,6 +3249,11 @@ class Resampler:
             if gain is not None:
                 kw["gain"] = gain[where].contiguous()
             batch = [tracks[i] for i in idx]
+            if gapless is not None:
+                kw["gapless"] = whole.subset(idx, pad=S - len(idx))
+                kw["gapless"].packed = packed
+                if pcm is not None:
+                    kw["out"] = pcm
             v, p, c = convert(batch, kw)
             peak[where] = p
             clipped[where] = c
